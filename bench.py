@@ -5,11 +5,22 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One "step" = forward + backward + (RCCL gradient all-reduce) + global-norm clip + AdamW on a synthetic batch of 32
-clips of 29x88x88 per GPU; eager launches by default, `--graph` replays one HIP graph per step.  Rank 0 prints ONE JSON line.  Besides the
-contract fields it carries:
+clips of 29x88x88 per GPU; eager launches by default, `--graph` replays one HIP graph per step.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times --steps steps, writes the outputs of the last timed step if --dump-outputs DIR is given, and prints
+the line.  Everything else the benchmark measures runs only with --full, behind the timed region:
+  host_enqueue_idle_queue_ms — host time of one step's enqueue onto an empty queue
+  sustained     — 1,600 back-to-back LRW steps with the effective shader clock before and after (one GPU)
+  collective    — what the data-parallel path did in the last timed step (multi-rank or --force-collective)
   roofline      — dominant kernel of the step (by summed HIP-event time over profiled eager steps), its algorithmic
                   FLOPs / time against the dense bf16 MFMA peak (2.5 PFLOP/s, MI355X_MICROARCH.md), plus the per-kernel table
-  cpu_baseline  — oracle/lrw_oracle.py (torch fp32 port of the reference path) timed on this box's host cores, N=1 only
+  cpu_baseline  — oracle/lrw_oracle.py (torch fp32 port of the reference path) timed on the host cores, N=1 only
+  lrs           — a bounded LRS leg beside the default LRW line (one GPU), with its own roofline and a <= 400-frame timing
+
+--dump-outputs DIR writes, as float32 / float64 .npy files, what the timed path hands its caller after the last timed step: the step's
+scalar outputs (outputs.npy, one value per name in the order of output_names in the line), and a fixed, seeded sample of the updated
+fp32 parameters (params_sample.npy) and of the BatchNorm running statistics (buffers_sample.npy).  The inputs are seeded, so two runs
+with the same arguments compare output for output.
 """
 from __future__ import annotations
 
@@ -392,6 +403,40 @@ def lrs_leg(args, dev, with_cpu: bool = False) -> dict:
     }
 
 
+DUMP_SAMPLE = 1 << 22            # elements of the parameter / buffer samples of --dump-outputs (16 MiB of fp32 each at most)
+
+
+def _fixed_sample(flat: torch.Tensor, seed: int) -> torch.Tensor:
+    """`flat` itself when it holds at most DUMP_SAMPLE elements, else DUMP_SAMPLE of them at seeded, sorted positions."""
+    n = flat.numel()
+    if n <= DUMP_SAMPLE:
+        return flat.detach().float().cpu()
+    g = torch.Generator().manual_seed(seed)
+    idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=g).sort().values
+    return flat.detach()[idx.to(flat.device)].float().cpu()
+
+
+def snapshot_outputs(model, out) -> dict:
+    """Host copies of what the step just returned and samples of the state it updated, taken before a later step overwrites them."""
+    import numpy as np
+
+    names = list(out.keys()) if isinstance(out, dict) else ["loss", "loss_ctc", "loss_att", "loss_audio", "acc"][: len(out)]
+    vals = out.values() if isinstance(out, dict) else out
+    st = model.store()
+    return {"output_names": names,
+            "outputs": np.array([float("nan") if v is None else float(v.detach().float().reshape(()).item()) for v in vals], dtype=np.float64),
+            "params_sample": _fixed_sample(st.flat, 0).numpy().astype(np.float32),
+            "buffers_sample": _fixed_sample(st.bufflat, 1).numpy().astype(np.float32)}
+
+
+def write_outputs(path: str, snap: dict) -> None:
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for k in ("outputs", "params_sample", "buffers_sample"):
+        np.save(os.path.join(path, f"{k}.npy"), snap[k])
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -425,6 +470,10 @@ def main() -> None:
     ap.add_argument("--ablate", default="", help="TIMING EXPERIMENTS ONLY (gradients wrong, the line is marked invalid): comma list of conv_wgrad, lin_wgrad — "
                     "those launches are skipped (how much of the step do they cost?)")
     ap.add_argument("--dropout", type=float, default=0.1, help="LRS: dropout_rate = transformer_attn_dropout_rate (config/lrs3.yaml:20-21)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run every other measurement: idle-queue enqueue time, "
+                    "sustained leg, collective figures, roofline leg, CPU baselines and the LRS leg (the --no-* / --*-steps options shape them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs, a seeded sample of the updated "
+                    "parameters and of the running statistics as DIR/<name>.npy (float32/float64, rank 0)")
     args = ap.parse_args()
     if args.workload == "lrs" and args.batch == 32 and "--batch" not in sys.argv:
         args.batch = 16
@@ -496,19 +545,26 @@ def main() -> None:
     barrier()
     t0 = time.perf_counter()
     trainer.host_ms.clear()
-    if trainer.dp is not None:
+    if trainer.dp is not None and args.full:
         trainer.dp.measure = True
     for _ in range(args.steps):
         out = trainer.step(*batch)
     host_ms = sorted(trainer.host_ms)
     barrier()
     elapsed = time.perf_counter() - t0
-    host_idle = host_idle_queue_ms(trainer, batch) if not use_dist else None
+    from syncvsr_amd.engine import reduce_metrics
+
+    out = reduce_metrics(out)                        # sync_dist=True logging of the reference: rank-mean of the step's scalars
+    loss = float((out[0] if lrs else out["loss_total"]).item())     # read before a later step (--full) overwrites the recorded step's outputs
+    snap = snapshot_outputs(model, out) if args.dump_outputs and rank == 0 else None
+    if snap is not None:
+        write_outputs(args.dump_outputs, snap)
+    host_idle = host_idle_queue_ms(trainer, batch) if args.full and not use_dist else None
     # ---- sustained leg (behind the headline region; the headline stays the driver's --steps): SURVEY section 8(d) asks for >= 200 timed steps,
     # the driver's 20 are 0.1 s of GPU time.  >= 400 back-to-back steps (>= 2 s), with the effective shader clock (svsr_clock_probe: s_memtime /
     # s_memrealtime over a block of MFMA work) read right before and right after: a figure that holds only while the chip is cold shows here.
     sustained = None
-    if args.sustained_steps > 0 and not use_dist and args.workload == "lrw":
+    if args.full and args.sustained_steps > 0 and not use_dist and args.workload == "lrw":
         clk0 = ops.shader_clock_mhz()
         torch.cuda.synchronize()
         ts0 = time.perf_counter()
@@ -526,10 +582,6 @@ def main() -> None:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    from syncvsr_amd.engine import reduce_metrics
-
-    out = reduce_metrics(out)                        # sync_dist=True logging of the reference: rank-mean of the step's scalars
-    loss = float((out[0] if lrs else out["loss_total"]).item())
     clips_per_s = args.batch * world * args.steps / elapsed
 
     result = {
@@ -551,11 +603,15 @@ def main() -> None:
                    "hip_graph": use_graph, "enqueue": "hip_graph" if use_graph else ("native step list" if native else "eager (python)")},
         # host time of one step's enqueue (median over the timed steps, this rank): below ms_per_step the GPU is the limit
         "host_enqueue_ms": round(host_ms[len(host_ms) // 2], 4) if host_ms else None,
-        "host_enqueue_idle_queue_ms": round(host_idle, 4) if host_idle is not None else None,
+        **({"host_enqueue_idle_queue_ms": round(host_idle, 4) if host_idle is not None else None} if args.full else {}),
         "launches_per_step": int(trainer._rec.size) if getattr(trainer, "_rec", None) is not None else None,
         "step_mfma_frac": round(clips_per_s / world * TRAIN_FLOP_PER_CLIP / MFMA_PEAK_BF16, 5),
         "final_loss": round(loss, 4),
+        "full": bool(args.full),
     }
+    if snap is not None:
+        result["dumped_outputs"] = {"dir": args.dump_outputs, "output_names": snap["output_names"], "params_sample": int(snap["params_sample"].size),
+                                    "buffers_sample": int(snap["buffers_sample"].size)}
     if sustained is not None:
         result["sustained"] = sustained
     if args.ablate:
@@ -576,7 +632,7 @@ def main() -> None:
                             "padded_frames_per_s": round(clips_per_s * args.frames, 1), "valid_frames_per_step_rank0": n_frames}
         result["step_mfma_frac"] = round(step_flops * args.steps / elapsed / MFMA_PEAK_BF16, 5)
 
-    if use_dist and trainer.dp is not None:          # what the data-parallel path did in the last timed step
+    if args.full and use_dist and trainer.dp is not None:          # what the data-parallel path did in the last timed step
         st = model.store()
         result["collective"] = {
             "backend": (f"nccl (RCCL {'.'.join(map(str, torch.cuda.nccl.version()))})" if dist.get_backend() == "nccl" else dist.get_backend()),
@@ -601,10 +657,10 @@ def main() -> None:
         result["collective"]["buckets_rank0"] = trainer.dp.bucket_times()
 
     if rank == 0:
-        # ---- roofline leg: eager steps with HIP events around every contraction launch -----------------------------
-        prof = TrainStep(model, cfg, use_graph=False, data_parallel=False)      # rank 0 alone: must not issue a collective
-        model._side.enabled = model._side.enabled_small = False        # time every kernel alone, not overlapped with a side-stream neighbour
-        if True:
+        if args.full:
+            # ---- roofline leg: eager steps with HIP events around every contraction launch -----------------------------
+            prof = TrainStep(model, cfg, use_graph=False, data_parallel=False)      # rank 0 alone: must not issue a collective
+            model._side.enabled = model._side.enabled_small = False        # time every kernel alone, not overlapped with a side-stream neighbour
             prof._step_impl(*batch)
             ops.start_event_timing()
             for _ in range(max(1, args.profile_steps)):
@@ -655,7 +711,7 @@ def main() -> None:
                         small = cpu_baseline(cfg, 2, budget_s=4.0, min_timed=5)
                         result["cpu_baseline"]["batch2_value"] = round(small["value"], 3)
                         result["cpu_baseline"]["sample"] += "; batch 2: " + small["sample"]
-        if args.workload == "lrw" and world == 1 and not args.no_lrs_leg and not use_dist:
+        if args.full and args.workload == "lrw" and world == 1 and not args.no_lrs_leg and not use_dist:
             # BASELINE configs[3]: a bounded LRS measurement rides on the default line (the headline metric / value above stay LRW's)
             del prof, trainer, model
             torch.cuda.empty_cache()

@@ -6,8 +6,9 @@ ROUND=${ROUND:-6}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/round$ROUND
 rm -rf $OUT; mkdir -p $OUT
 export ROUND PYTHONUNBUFFERED=1 SVSR_SIDE_TRUNK=0 SVSR_SIDE_ENCODER=0
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-B="python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-lrs-leg --sustained-steps 0 --enqueue eager --profile-steps 1"
+B="python $ROOT/bench.py --full --no-cpu-baseline --no-lrs-leg --sustained-steps 0 --enqueue eager --profile-steps 1"
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o lrw -- $B --steps 5 --warmup 2 > $OUT/lrw_run.log 2>&1; echo "lrw stats $?"
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o lrs -- $B --workload lrs --steps 3 --warmup 2 > $OUT/lrs_run.log 2>&1; echo "lrs stats $?"
 for ctr in FETCH_SIZE WRITE_SIZE "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES"; do
@@ -22,7 +23,7 @@ timeout 800 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIV
 cd $GRAFT_REPO_ROOT
 # the side-stream (default) step for the headline number, same box
 unset SVSR_SIDE_TRUNK SVSR_SIDE_ENCODER
-python bench.py --steps 50 --warmup 5 > $OUT/bench_lrw.json 2> $OUT/bench_lrw.err; tail -c 300 $OUT/bench_lrw.json
+python bench.py --full --steps 50 --warmup 5 > $OUT/bench_lrw.json 2> $OUT/bench_lrw.err; tail -c 300 $OUT/bench_lrw.json
 # reduce the PMC csvs to per-kernel averages here (the raw files are large)
 python - <<'PY'
 import csv, glob, collections, json, os, re

@@ -1,8 +1,9 @@
 #!/bin/bash
 # One-rank RCCL path of the training step under rocprofv3 --kernel-trace: which kernels does the collective library launch, with what grid / LDS /
 # register footprint, and beside which of the step's kernels do they run?  (8 GPUs are not available to the builder.)
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp; export TMPDIR=/tmp PYTHONUNBUFFERED=1
-rm -rf /tmp/rc; timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/rc -o l -- python $GRAFT_REPO_ROOT/bench.py --force-collective --no-cpu-baseline --no-lrs-leg --sustained-steps 0 --profile-steps 0 --steps 6 --warmup 3 > /tmp/rc.log 2>&1
+rm -rf /tmp/rc; timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/rc -o l -- python $ROOT/bench.py --full --force-collective --no-cpu-baseline --no-lrs-leg --sustained-steps 0 --profile-steps 0 --steps 6 --warmup 3 > /tmp/rc.log 2>&1
 tail -1 /tmp/rc.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('ms/step', d['ms_per_step'], json.dumps(d.get('collective'))[:1500])"
 python - <<'PY'
 import csv, glob, re, collections

@@ -2,9 +2,10 @@
 # which main-stream kernels stretch under the side stream?  per-kernel time per step with the weight-gradient side stream on and off
 # (rocprofv3 --kernel-trace of the eager step; WORKLOAD=lrw|lrs)
 W=${WORKLOAD:-lrw}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp; export TMPDIR=/tmp PYTHONUNBUFFERED=1
 for side in 1 0; do
-  rm -rf /tmp/pp$side; SVSR_SIDE_TRUNK=$side SVSR_SIDE_ENCODER=$side timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/pp$side -o l -- python $GRAFT_REPO_ROOT/bench.py --workload $W --no-cpu-baseline --no-lrs-leg --profile-steps 0 --steps ${STEPS:-6} --warmup 2 --enqueue eager > /tmp/run$side.log 2>&1
+  rm -rf /tmp/pp$side; SVSR_SIDE_TRUNK=$side SVSR_SIDE_ENCODER=$side timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/pp$side -o l -- python $ROOT/bench.py --full --workload $W --no-cpu-baseline --no-lrs-leg --profile-steps 0 --steps ${STEPS:-6} --warmup 2 --enqueue eager > /tmp/run$side.log 2>&1
 done
 python - <<'PY'
 import csv, glob, collections, re, os

@@ -172,4 +172,15 @@ size_t tf_bytes(void) { return g_tf_bytes; }
 long tf_alloc_count(void) { return g_tf_allocs; }
 size_t tf_granule(void) { return g_tf_gran; }
 
+/* layout of a live allocation: bytes from `user` to the end of its mapped memory and to the end of its reservation (0 = found) */
+int tf_layout(const void* user, size_t* to_mapped_end, size_t* to_reserved_end) {
+    std::lock_guard<std::mutex> lock(g_mu);
+    auto it = g_tf_live.find(const_cast<void*>(user));
+    if (it == g_tf_live.end()) return 1;
+    const size_t off = static_cast<size_t>(static_cast<const char*>(user) - it->second.va);
+    *to_mapped_end = it->second.mapped - off;
+    *to_reserved_end = it->second.reserved - off;
+    return 0;
+}
+
 }  // extern "C"

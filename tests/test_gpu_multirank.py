@@ -1,7 +1,7 @@
 """The multi-rank benchmark flow on ONE GPU (-m gpu): two ranks share cuda:0 and gloo carries the collectives (RCCL refuses two ranks
 on one device; the 1-rank RCCL path is covered by tests/test_gpu_train.py).  This is the driver's own launch line for N > 1 — parameter
 and buffer broadcast, gradient buckets all-reduced from inside the real backward, per-step BatchNorm broadcast, rank-mean metrics, the
-rank-0-only profiling leg, the closing barrier: no rank may wait for a collective the others never issue."""
+rank-0-only profiling leg of --full, the closing barrier: no rank may wait for a collective the others never issue."""
 import json
 import os
 import socket
@@ -24,7 +24,7 @@ def test_two_rank_bench_completes(extra):
         port = str(s.getsockname()[1])
     env = dict(os.environ, SVSR_BENCH_ONE_DEVICE="1", OMP_NUM_THREADS="4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", port,
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--backend", "gloo", "--no-cpu-baseline", *extra]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--backend", "gloo", "--no-cpu-baseline", "--full", *extra]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
