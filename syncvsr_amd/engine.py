@@ -23,6 +23,7 @@ import torch.distributed as dist
 from . import ops
 from .config import Config
 from .model import TransformerLightningModule
+from .shape_cache import ShapeLRU, shape_key
 
 
 import os as _os
@@ -66,6 +67,18 @@ def _rng_state_from_tensor(t: torch.Tensor):
     return (v[0], tuple(v[1:626]), gauss)
 
 
+class _ShapeList:
+    """One recorded step list of TrainStep(native=True, max_shapes > 1): its recorder, static inputs and outputs (bytes: what the recorder
+    keeps alive)."""
+    __slots__ = ("rec", "static", "out", "nbytes")
+
+    def __init__(self) -> None:
+        self.rec: Optional[ops.StepRecorder] = None
+        self.static: Optional[list] = None
+        self.out = None
+        self.nbytes = 0
+
+
 class TrainStep:
     """forward + backward + (all-reduce) + clip + AdamW for the LRW model (`TransformerLightningModule`; its step takes
     (videos, audio_tokens, labels, word_mask)) or the LRS model (`lrs_model.E2E`; (x, lengths, audio_tokens, label));
@@ -78,11 +91,17 @@ class TrainStep:
 
     def __init__(self, model, config: Optional[Config] = None, process_group=None,
                  use_graph: bool = False, bucket_mb: float = 32.0, always_reduce: bool = False, data_parallel: bool = True,
-                 grad_comm_dtype: torch.dtype = torch.float32, native: bool = False):
+                 grad_comm_dtype: torch.dtype = torch.float32, native: bool = False, max_shapes: int = 1,
+                 max_recorded_bytes: Optional[int] = None):
         """native=True: the launch sequence of the first step is recorded into a native step list (csrc/steplist.hip) and every
         later step re-issues it with one library call per segment — eager launches on the same streams (the weight-gradient side
         stream keeps overlapping, which a captured HIP graph loses) without the per-launch host cost of the Python loop.  Batch
-        shapes are fixed by the first call, as with use_graph."""
+        shapes are fixed by the first call, as with use_graph.
+
+        max_shapes > 1 (native only): one recorded list per batch shape (shape_cache.shape_key of the prepared inputs for LRS, of the
+        batch for LRW), each with its own static inputs and outputs; parameters, optimiser state, buffers, the dropout word and the
+        scratch are shared.  A batch of a new shape is recorded (and executed) in its step; beyond `max_shapes` lists, or beyond
+        `max_recorded_bytes` kept alive by their recorders, the least recently used list is released after a device synchronisation."""
         self.model = model
         self.is_lrw = isinstance(model, TransformerLightningModule)
         if self.is_lrw:            # LRW/video/config/*.yaml: optim.optimizer / optim.scheduler / train.gradient_clip_val
@@ -120,6 +139,16 @@ class TrainStep:
             raise NotImplementedError("native=True: transformer_length_normalized_loss needs a torch kernel inside the step (use native=False)")
         if self.native and getattr(model, "layer_drop_p", 0.0) > 0.0:
             raise NotImplementedError("layer_dropout changes the launch sequence from step to step: it cannot be replayed from a recorded list")
+        if int(max_shapes) < 1:
+            raise ValueError("max_shapes must be >= 1")
+        if int(max_shapes) > 1 and not self.native:
+            raise ValueError("max_shapes > 1 keeps one recorded step list per batch shape: it needs native=True")
+        if max_recorded_bytes is not None and int(max_shapes) == 1:
+            raise ValueError("max_recorded_bytes bounds the lists of max_shapes > 1")
+        self.max_shapes = int(max_shapes)
+        self._lists = ShapeLRU(self.max_shapes, max_recorded_bytes, weight=lambda e: e.nbytes)
+        self._key: Optional[tuple] = None              # shape key of the list stepped last (max_shapes > 1)
+        self._counts: dict = {}                        # shape key -> [times recorded, times replayed]
         self._rec: Optional[ops.StepRecorder] = None
         self.fused_encoder_fallbacks = 0        # times _watch_fused_encoder switched the encoder to the launch chain
         self.host_ms: list[float] = []          # host time of the last steps' enqueue (bench.py reports the median)
@@ -241,39 +270,119 @@ class TrainStep:
         self._optimizer(st)
         return out
 
+    def _record(self, static: Optional[list], prepped) -> tuple:
+        """Records (and executes) one step on the static inputs `static` (made from `prepped` when None, else `prepped` is copied into them:
+        the input buffers a loader may be writing into stay the same).  -> (static, recorder, outputs)."""
+        model = self.model
+        if not model.training:
+            raise RuntimeError("TrainStep(native=True) records a TRAINING step: call model.train() first")
+        if static is None:
+            static = [t.clone() if torch.is_tensor(t) else t for t in prepped]
+        else:
+            for dst, src in zip(static, prepped):
+                if torch.is_tensor(dst) and dst.data_ptr() != src.data_ptr():
+                    dst.copy_(src)
+        st = model.store()
+        if not st.shadow_fresh:
+            st.refresh_shadows()
+            st.shadow_fresh = True
+        if self.dp is not None:
+            self.dp.begin_step()
+        if model._side.stream is None:
+            model._side.stream = torch.cuda.Stream()
+        model.direct_constants(static[0].device)
+        if getattr(model, "_drop_word", None) is None and (model.drop_p > 0.0 or model.attn_drop_p > 0.0 or getattr(model, "emb_drop_p", 0.0) > 0.0):
+            model._advance_dropout(static[0].device)      # creates the seed word outside the recorded region ...
+            ops.word_add(model._drop_word, -1)             # ... and leaves its value where the first forward expects it
+        rec = ops.StepRecorder()
+        with ops.recording(rec):
+            out = self._direct_impl(*static)
+        out = {k: v.detach() for k, v in out.items()} if isinstance(out, dict) else tuple(v.detach() for v in out)
+        return static, rec, out
+
+    def _count(self, key, i: int) -> None:
+        self._counts.setdefault(key, [0, 0])[i] += 1
+
     def _native_step(self, *batch):
+        if self.max_shapes > 1:
+            return self._native_step_keyed(*batch)
         model = self.model
         if self._rec is None:
-            if not model.training:
-                raise RuntimeError("TrainStep(native=True) records a TRAINING step: call model.train() first")
-            prepped = model.prepare_batch(*batch)
-            if self._static is None:
-                self._static = [t.clone() if torch.is_tensor(t) else t for t in prepped]
-            else:                        # recorded again (_watch_fused_encoder): the input buffers a loader may be writing into stay the same
-                for dst, src in zip(self._static, prepped):
-                    if torch.is_tensor(dst) and dst.data_ptr() != src.data_ptr():
-                        dst.copy_(src)
-            st = model.store()
-            if not st.shadow_fresh:
-                st.refresh_shadows()
-                st.shadow_fresh = True
-            if self.dp is not None:
-                self.dp.begin_step()
-            if model._side.stream is None:
-                model._side.stream = torch.cuda.Stream()
-            model.direct_constants(self._static[0].device)
-            if getattr(model, "_drop_word", None) is None and (model.drop_p > 0.0 or model.attn_drop_p > 0.0 or getattr(model, "emb_drop_p", 0.0) > 0.0):
-                model._advance_dropout(self._static[0].device)      # creates the seed word outside the recorded region ...
-                ops.word_add(model._drop_word, -1)                   # ... and leaves its value where the first forward expects it
-            rec = ops.StepRecorder()
-            with ops.recording(rec):
-                out = self._direct_impl(*self._static)
-            self._rec = rec
-            self._out = {k: v.detach() for k, v in out.items()} if isinstance(out, dict) else tuple(v.detach() for v in out)
-            self._main_stream = rec.main_stream
+            self._static, self._rec, self._out = self._record(self._static, model.prepare_batch(*batch))
+            self._main_stream = self._rec.main_stream
+            self._count(None, 0)
             return self._out
         if not self.is_lrw:          # LRS: the conversions (and the decoder / CTC targets) are redone per batch, then copied into the static inputs
             batch = model.prepare_batch(*batch)
+        self._replay(batch)
+        self._count(None, 1)
+        return self._out
+
+    def _native_step_keyed(self, *batch):
+        """max_shapes > 1: the list of this batch's shape key is replayed, or recorded when there is none (evicting the least recently used
+        lists beyond max_shapes / max_recorded_bytes first).  _rec / _static / _out / input_buffers() follow the list stepped last."""
+        model = self.model
+        lists = self._lists
+        last = lists.peek(self._key) if self._key is not None else None
+        if last is not None and last.rec is not None and self._rec is None:
+            self._release([last], keep_static=True)         # `_rec = None`: the shape stepped last is recorded again
+        src = tuple(batch) if self.is_lrw else model.prepare_batch(*batch)
+        key = shape_key(src)
+        e = lists.get(key)
+        if e is None or e.rec is None:
+            if e is None:
+                e = _ShapeList()
+                self._release([v for _, v in lists.put(key, e)])
+            prepped = model.prepare_batch(*batch) if self.is_lrw else src
+            e.static, e.rec, e.out = self._record(e.static, prepped)
+            e.nbytes = e.rec.kept_bytes()
+            self._bind(key, e)
+            self._count(key, 0)
+            self._release([v for _, v in lists.shrink(keep=key)])
+            return e.out
+        self._bind(key, e)
+        self._replay(src)
+        self._count(key, 1)
+        return e.out
+
+    def _bind(self, key, e: "_ShapeList") -> None:
+        self._key = key
+        self._rec, self._static, self._out, self._main_stream = e.rec, e.static, e.out, e.rec.main_stream
+
+    def _release(self, entries: list, keep_static: bool = False) -> None:
+        """Drops the recorders (and, unless keep_static, the static inputs) of `entries`.  Their tensors go back to torch's caching allocator,
+        which hands them to the next allocation on the main stream: the device must be done with them on EVERY stream first — the tail of
+        the last step's optimiser may still run on the model's side stream after step() returned — hence one device synchronisation (rare:
+        a new shape beyond the bounds, a re-recording)."""
+        live = [e for e in entries if e.rec is not None or (not keep_static and e.static is not None)]
+        if not live:
+            return
+        torch.cuda.synchronize()
+        for e in live:
+            if e.rec is self._rec:
+                self._rec = None
+            e.rec, e.out, e.nbytes = None, None, 0
+            if not keep_static:
+                e.static = None
+
+    def recorded_shapes(self) -> dict:
+        """Per shape key of a list held now: {launches, bytes (device memory its recorder keeps alive: unique storages), recorded (times),
+        replayed (times)}.  max_shapes = 1: the one list, keyed by its static inputs.  Read-only."""
+        out = {}
+        if self.max_shapes == 1:
+            if self._rec is not None:
+                n = self._counts.get(None, [0, 0])
+                out[shape_key(self._static)] = dict(launches=self._rec.size, bytes=self._rec.kept_bytes(), recorded=n[0], replayed=n[1])
+            return out
+        for key, e in self._lists.items():
+            if e.rec is None:
+                continue
+            n = self._counts.get(key, [0, 0])
+            out[key] = dict(launches=e.rec.size, bytes=e.nbytes, recorded=n[0], replayed=n[1])
+        return out
+
+    def _replay(self, batch) -> None:
+        model = self.model
         for dst, src in zip(self._static, batch):
             if not torch.is_tensor(dst):
                 continue
@@ -287,7 +396,6 @@ class TrainStep:
             self.dp.begin_step()
         self._rec.run()
         model._store.generation += 1
-        return self._out
 
     def input_buffers(self) -> Optional[tuple]:
         """The device tensors a recorded (native / captured) step reads its batch from, in the order of step()'s arguments — None
@@ -327,6 +435,7 @@ class TrainStep:
         ops.check_enc_clusters(reset=True)
         ops.disable_enc_fused("a cluster wait of svsr_enc_fwd / svsr_enc_bwd gave up (its workgroups were not resident together)")
         self.fused_encoder_fallbacks += 1
+        self._release([e for _, e in self._lists.items()], keep_static=True)      # max_shapes > 1: every list is recorded again
         self._rec = None                 # native: record the step again (now on the chain)
         self._graph = None               # graph: capture again
 

@@ -112,11 +112,25 @@ def pad(samples: list[torch.Tensor], pad_val: float = 0.0, pad_to: Optional[int]
     return out, lengths
 
 
-def collate_pad(batch: list[dict], pad_frames_to: Optional[int] = None, frames_per_unit: Optional[dict] = None) -> dict:
+def collate_pad(batch: list[dict], pad_frames_to: Optional[int] = None, frames_per_unit: Optional[dict] = None,
+                pad_targets_to_multiple: Optional[int] = None) -> dict:
     """The reference's `collate_pad` (data_module.py:34-43): {"inputs", "input_lengths", "targets", "target_lengths", ...} with
     targets padded by -1 and everything else by 0.  `pad_frames_to` (the sampler's bucket bound) pads "input" — and every key
     listed in `frames_per_unit` at its own rate, e.g. {"audio": 640} samples or {"audio": 4} tokens per video frame — to a fixed
-    length, so that all ranks of a step produce the same shapes."""
+    length, so that all ranks of a step produce the same shapes.
+
+    `pad_targets_to_multiple=k` pads the "target" tails with -1 up to the next multiple of k tokens (target_lengths stay the real
+    lengths), so that a bucketed epoch meets a few label shapes instead of one per longest transcript — what engine.TrainStep(native=True,
+    max_shapes=...) keeps one recorded list for.  The losses do not depend on it mathematically (prepare_targets drops -1 wherever it sits; CTC
+    uses per-row target lengths; the decoder's extra positions sit after the real ones under the causal mask; the label-smoothing loss is
+    normalised by the batch with length_norm off; the accuracy ignores -1), but the step is NOT bit-identical: the reductions over the target
+    rows change their row counts.  Measured on the tiny LRS case (tests/test_gpu_native_shapes.py, 3 steps): losses and accuracy
+    bit-identical, parameters within 3e-8 (one or two ulps)."""
+    if pad_targets_to_multiple is not None:
+        if int(pad_targets_to_multiple) < 1:
+            raise ValueError("pad_targets_to_multiple must be >= 1")
+        if frames_per_unit and "target" in frames_per_unit:
+            raise ValueError("'target' is padded either per video frame (frames_per_unit) or to a multiple of tokens, not both")
     out = {}
     for key in batch[0].keys():
         vals = [s[key] for s in batch if s[key] is not None]
@@ -128,6 +142,9 @@ def collate_pad(batch: list[dict], pad_frames_to: Optional[int] = None, frames_p
                 to = pad_frames_to
             elif frames_per_unit and key in frames_per_unit:
                 to = pad_frames_to * int(frames_per_unit[key])
+        if key == "target" and pad_targets_to_multiple is not None:
+            k = int(pad_targets_to_multiple)
+            to = -(-max(len(v) for v in vals) // k) * k
         c, lens = pad(vals, -1 if key == "target" else 0.0, to)
         out[key + "s"] = c
         out[key + "_lengths"] = torch.tensor(lens)

@@ -268,6 +268,16 @@ class StepRecorder:
     def size(self) -> int:
         return int(self.lib.svsr_steplist_size(self.handle))
 
+    def kept_bytes(self) -> int:
+        """Device bytes this recorder keeps alive: the unique storages of the tensors allocated during the recorded step (a grow-only
+        workspace first allocated inside the recording is counted here too, although it outlives the recorder)."""
+        seen: dict[int, int] = {}
+        for t in self.keep:
+            if torch.is_tensor(t) and t.is_cuda:
+                s = t.untyped_storage()
+                seen[s.data_ptr()] = s.nbytes()
+        return sum(seen.values())
+
     def run(self) -> None:
         """Re-issues the recorded step: segment by segment, each followed by its host callbacks."""
         failed = ctypes.c_int(-1)
