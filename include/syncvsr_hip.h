@@ -32,6 +32,12 @@ typedef void* hipStream_t;
 
 #define SVSR_OK 0
 #define SVSR_ERR_ARG 1001
+/* step-list groups (svsr_steplist_push_group): a group is open where none may be (a nested group, a break or a copy inside a group) */
+#define SVSR_ERR_GROUP_OPEN 1003
+/* step-list groups: a group index the list does not have (a copy naming it, closing with no group open) */
+#define SVSR_ERR_NO_GROUP 1004
+/* step-list groups: a skip mask whose length is not the list's group count */
+#define SVSR_ERR_MASK_SIZE 1005
 
 /* one problem of svsr_igemm_wgrad_group: the arguments of a svsr_igemm_wgrad call (device pointers; meta = the HOST meta[8] of the plan) */
 typedef struct svsr_wgrad_problem {
@@ -489,7 +495,17 @@ int svsr_scale_bf16(const void* x, void* y, int64_t n, float alpha, const unsign
  * a collective between two segments).  svsr_steplist_run(list, k, &failed) re-issues segment k (k < 0: every segment) on the
  * recorded streams and returns 0 or the first failing call's code with its op index in *failed.  Every buffer a recorded call
  * points to (device and host) must stay alive and in place while the list exists.  svsr_steplist_knows(name): 1 if the
- * entry point can be recorded.  svsr_stream_wait / svsr_memset_async are the eager twins of WAIT / MEMSET. */
+ * entry point can be recorded.  svsr_stream_wait / svsr_memset_async / svsr_memcpy_async are the eager twins of WAIT / MEMSET / COPY.
+ *
+ * Op groups (layer drop: whole encoder blocks left out of some replays).  svsr_steplist_push_group(list, n >= 0) opens group n and
+ * (list, -1) closes it; every CALL and MEMSET pushed in between belongs to group n (a group may be opened again later: the forward
+ * and the backward half of one block).  Groups do not nest (SVSR_ERR_GROUP_OPEN) and hold no BREAK (push_break returns
+ * -SVSR_ERR_GROUP_OPEN); a WAIT inside a group is issued whatever is skipped.  svsr_steplist_push_copy(list, dst, src, bytes, stream, g)
+ * appends a device-to-device hipMemcpyAsync on `stream` that is issued only in a replay where group g is skipped (g must exist:
+ * SVSR_ERR_NO_GROUP; not inside a group).  svsr_steplist_set_skips(list, mask, ngroups): mask[g] != 0 leaves group g out of every
+ * following svsr_steplist_run until it is set again; the list keeps a copy; ngroups must be svsr_steplist_groups(list)
+ * (SVSR_ERR_MASK_SIZE).  svsr_steplist_calls(list, g): CALL ops of group g (g < 0: of the whole list).  svsr_steplist_last_issued:
+ * CALL ops issued since segment 0 (or the whole list) was last run. */
 void* svsr_steplist_create(void);
 int svsr_steplist_destroy(void* list);
 int svsr_steplist_knows(const char* name);
@@ -500,8 +516,15 @@ int svsr_steplist_push_break(void* list);
 int svsr_steplist_segments(void* list);
 int64_t svsr_steplist_size(void* list);
 int svsr_steplist_run(void* list, int segment, int* failed);
+int svsr_steplist_push_group(void* list, int group);
+int svsr_steplist_push_copy(void* list, void* dst, const void* src, int64_t bytes, hipStream_t stream, int when_skipped);
+int svsr_steplist_set_skips(void* list, const uint8_t* mask, int ngroups);
+int svsr_steplist_groups(void* list);
+int64_t svsr_steplist_calls(void* list, int group);
+int64_t svsr_steplist_last_issued(void* list);
 int svsr_stream_wait(hipStream_t waiter, hipStream_t signaller);
 int svsr_memset_async(void* ptr, int value, int64_t bytes, hipStream_t stream);
+int svsr_memcpy_async(void* dst, const void* src, int64_t bytes, hipStream_t stream);
 
 /* Compute units of the current device (persistent kernels size their grids, static tile lists and cluster counts by it). */
 int svsr_device_cus(void);

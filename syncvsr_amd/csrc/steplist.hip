@@ -10,7 +10,13 @@
 //   WAIT    stream `waiter` waits for everything enqueued so far on stream `signaller` (hipEventRecord + hipStreamWaitEvent),
 //   MEMSET  hipMemsetAsync,
 //   BREAK   end of a segment: svsr_steplist_run(list, k) issues segment k and returns, so the host can put a collective
-//           (torch.distributed / RCCL) between two segments.
+//           (torch.distributed / RCCL) between two segments,
+//   COPY    hipMemcpyAsync device to device, issued only in a replay that skips the group it names.
+// Op groups (layer drop of the x-transformers encoder): every CALL and MEMSET pushed between svsr_steplist_push_group(list, n) and
+// svsr_steplist_push_group(list, -1) belongs to group n; svsr_steplist_set_skips(list, mask, ngroups) names the groups the following
+// replays leave out on the host (no launch of them is issued, no kernel runs to do nothing) and a COPY of a skipped group passes the
+// group's input on to where its output would have been.  WAITs are issued whatever is skipped, so cross-stream order holds; a
+// group never holds a BREAK.
 // Everything a CALL points to must stay alive and in place while the list exists: device buffers (the recorder on the Python side
 // keeps every tensor of the recorded step), host arrays (plan meta records, tap tables: cached for the life of the process).
 // Nothing here launches a kernel of its own; results are bit-identical to the eager step by construction.
@@ -70,11 +76,12 @@ const std::unordered_map<std::string, Entry>& registry() {
         SVSR_REG(svsr_glu_dwconv_fwd), SVSR_REG(svsr_glu_dwconv_bwd), SVSR_REG(svsr_glu_dwconv_bwd_parts), SVSR_REG(svsr_ctc_fwd), SVSR_REG(svsr_ctc_grad),
         SVSR_REG(svsr_ctc_prefix_score), SVSR_REG(svsr_lrs_targets), SVSR_REG(svsr_embed_pos_fwd), SVSR_REG(svsr_embed_pos_bwd), SVSR_REG(svsr_ls_loss_fwd),
         SVSR_REG(svsr_ls_loss_bwd), SVSR_REG(svsr_scale_bf16), SVSR_REG(svsr_word_add), SVSR_REG(svsr_lincomb2), SVSR_REG(svsr_igemm_wgrad_group), SVSR_REG(svsr_enc_fwd), SVSR_REG(svsr_enc_bwd), SVSR_REG(svsr_lincomb3_ratio), SVSR_REG(svsr_add_ln_bwd_partials), SVSR_REG(svsr_add_ln_bwd_branch), SVSR_REG(svsr_bias_act_bwd_partials),
+        SVSR_REG(svsr_memcpy_async),
     };
     return r;
 }
 
-enum { OP_CALL = 0, OP_WAIT, OP_MEMSET, OP_BREAK };
+enum { OP_CALL = 0, OP_WAIT, OP_MEMSET, OP_BREAK, OP_COPY };
 constexpr int MAX_ARGS = 48;
 
 struct Op {
@@ -83,8 +90,10 @@ struct Op {
     int nargs;
     Slot args[MAX_ARGS];
     hipEvent_t ev;            // WAIT
-    hipStream_t a, b;         // WAIT: a waits for b;  MEMSET: a = stream
+    hipStream_t a, b;         // WAIT: a waits for b;  MEMSET, COPY: a = stream
     void* ptr; int value; size_t bytes;
+    const void* src;          // COPY
+    int group;                // CALL, MEMSET: the group the op belongs to (-1: none);  COPY: the group whose skip issues it
 };
 
 struct StepList {
@@ -92,7 +101,13 @@ struct StepList {
     std::vector<size_t> seg_begin{0};
     std::vector<hipEvent_t> events;
     std::string last_error;
+    int open_group = -1;                 // group that CALL / MEMSET ops join now (-1: none)
+    std::vector<int64_t> group_calls;    // CALL ops per group; size = the list's group count
+    std::vector<uint8_t> skips;          // per-replay mask (svsr_steplist_set_skips); empty: nothing skipped
+    int64_t issued = 0;                  // CALL ops issued since segment 0 (or the whole list) was last run
 };
+
+bool skipped(const StepList* l, int group) { return group >= 0 && (size_t)group < l->skips.size() && l->skips[group] != 0; }
 
 }  // namespace
 
@@ -117,9 +132,10 @@ int svsr_steplist_push_call(void* list, const char* name, const int64_t* slots, 
     auto it = registry().find(name);
     if (it == registry().end() || it->second.nargs != nslots || nslots > MAX_ARGS) return SVSR_ERR_ARG;
     Op op{};
-    op.kind = OP_CALL; op.call = it->second.call; op.nargs = nslots;
+    op.kind = OP_CALL; op.call = it->second.call; op.nargs = nslots; op.group = l->open_group;
     for (int i = 0; i < nslots; ++i) op.args[i] = slots[i];
     l->ops.push_back(op);
+    if (l->open_group >= 0) ++l->group_calls[l->open_group];
     return SVSR_OK;
 }
 
@@ -141,7 +157,7 @@ int svsr_steplist_push_wait(void* list, hipStream_t waiter, hipStream_t signalle
     StepList* l = static_cast<StepList*>(list);
     if (l == nullptr) return SVSR_ERR_ARG;
     Op op{};
-    op.kind = OP_WAIT; op.a = waiter; op.b = signaller;
+    op.kind = OP_WAIT; op.a = waiter; op.b = signaller; op.group = -1;      // (issued whatever is skipped)
     hipError_t e = hipEventCreateWithFlags(&op.ev, wait_event_flags());
     if (e != hipSuccess) return (int)e;
     l->events.push_back(op.ev);
@@ -153,17 +169,72 @@ int svsr_steplist_push_memset(void* list, void* ptr, int value, int64_t bytes, h
     StepList* l = static_cast<StepList*>(list);
     if (l == nullptr || ptr == nullptr || bytes < 0) return SVSR_ERR_ARG;
     Op op{};
-    op.kind = OP_MEMSET; op.ptr = ptr; op.value = value; op.bytes = (size_t)bytes; op.a = stream;
+    op.kind = OP_MEMSET; op.ptr = ptr; op.value = value; op.bytes = (size_t)bytes; op.a = stream; op.group = l->open_group;
     l->ops.push_back(op);
     return SVSR_OK;
 }
 
-/* closes the current segment; returns the index of the segment that starts here */
+/* closes the current segment; returns the index of the segment that starts here (negative: an error code, the list unchanged) */
 int svsr_steplist_push_break(void* list) {
     StepList* l = static_cast<StepList*>(list);
     if (l == nullptr) return -SVSR_ERR_ARG;
+    if (l->open_group >= 0) return -SVSR_ERR_GROUP_OPEN;       // a host callback between two segments cannot be skipped
     l->seg_begin.push_back(l->ops.size());
     return (int)l->seg_begin.size() - 1;
+}
+
+/* group >= 0 opens group `group` (groups are numbered by the caller; a group may be opened again later), -1 closes the open one */
+int svsr_steplist_push_group(void* list, int group) {
+    StepList* l = static_cast<StepList*>(list);
+    if (l == nullptr || group < -1) return SVSR_ERR_ARG;
+    if (group == -1) {
+        if (l->open_group < 0) return SVSR_ERR_NO_GROUP;
+        l->open_group = -1;
+        return SVSR_OK;
+    }
+    if (l->open_group >= 0) return SVSR_ERR_GROUP_OPEN;         // groups do not nest
+    if ((size_t)group >= l->group_calls.size()) l->group_calls.resize((size_t)group + 1, 0);
+    l->open_group = group;
+    return SVSR_OK;
+}
+
+int svsr_steplist_push_copy(void* list, void* dst, const void* src, int64_t bytes, hipStream_t stream, int when_skipped) {
+    StepList* l = static_cast<StepList*>(list);
+    if (l == nullptr || dst == nullptr || src == nullptr || bytes < 0) return SVSR_ERR_ARG;
+    if (l->open_group >= 0) return SVSR_ERR_GROUP_OPEN;
+    if (when_skipped < 0 || (size_t)when_skipped >= l->group_calls.size()) return SVSR_ERR_NO_GROUP;
+    Op op{};
+    op.kind = OP_COPY; op.ptr = dst; op.src = src; op.bytes = (size_t)bytes; op.a = stream; op.group = when_skipped;
+    l->ops.push_back(op);
+    return SVSR_OK;
+}
+
+int svsr_steplist_set_skips(void* list, const uint8_t* mask, int ngroups) {
+    StepList* l = static_cast<StepList*>(list);
+    if (l == nullptr || ngroups < 0 || (mask == nullptr && ngroups > 0)) return SVSR_ERR_ARG;
+    if ((size_t)ngroups != l->group_calls.size()) return SVSR_ERR_MASK_SIZE;
+    l->skips.assign(mask, mask + ngroups);
+    return SVSR_OK;
+}
+
+int svsr_steplist_groups(void* list) {
+    StepList* l = static_cast<StepList*>(list);
+    return l == nullptr ? 0 : (int)l->group_calls.size();
+}
+
+/* CALL ops of group `group` (group < 0: of the whole list); negative: an error code */
+int64_t svsr_steplist_calls(void* list, int group) {
+    StepList* l = static_cast<StepList*>(list);
+    if (l == nullptr) return -SVSR_ERR_ARG;
+    if (group >= 0) return (size_t)group < l->group_calls.size() ? l->group_calls[group] : -SVSR_ERR_NO_GROUP;
+    int64_t n = 0;
+    for (const Op& op : l->ops) n += op.kind == OP_CALL;
+    return n;
+}
+
+int64_t svsr_steplist_last_issued(void* list) {
+    StepList* l = static_cast<StepList*>(list);
+    return l == nullptr ? 0 : l->issued;
 }
 
 int svsr_steplist_segments(void* list) {
@@ -182,18 +253,30 @@ int svsr_steplist_run(void* list, int segment, int* failed) {
     if (l == nullptr || segment >= (int)l->seg_begin.size()) return SVSR_ERR_ARG;
     const size_t lo = segment < 0 ? 0 : l->seg_begin[segment];
     const size_t hi = (segment < 0 || segment + 1 == (int)l->seg_begin.size()) ? l->ops.size() : l->seg_begin[segment + 1];
+    if (segment <= 0) l->issued = 0;
     for (size_t i = lo; i < hi; ++i) {
         const Op& op = l->ops[i];
         int rc = 0;
         switch (op.kind) {
-            case OP_CALL: rc = op.call(op.args); break;
+            case OP_CALL:
+                if (skipped(l, op.group)) continue;
+                rc = op.call(op.args);
+                ++l->issued;
+                break;
             case OP_WAIT: {
                 hipError_t e = hipEventRecord(op.ev, op.b);
                 if (e == hipSuccess) e = hipStreamWaitEvent(op.a, op.ev, 0);
                 rc = (int)e;
                 break;
             }
-            case OP_MEMSET: rc = (int)hipMemsetAsync(op.ptr, op.value, op.bytes, op.a); break;
+            case OP_MEMSET:
+                if (skipped(l, op.group)) continue;
+                rc = (int)hipMemsetAsync(op.ptr, op.value, op.bytes, op.a);
+                break;
+            case OP_COPY:
+                if (!skipped(l, op.group)) continue;
+                rc = (int)hipMemcpyAsync(op.ptr, op.src, op.bytes, hipMemcpyDeviceToDevice, op.a);
+                break;
             default: break;
         }
         if (rc != 0) {
@@ -225,6 +308,11 @@ int svsr_stream_wait(hipStream_t waiter, hipStream_t signaller) {
 int svsr_memset_async(void* ptr, int value, int64_t bytes, hipStream_t stream) {
     if (ptr == nullptr || bytes < 0) return SVSR_ERR_ARG;
     return (int)hipMemsetAsync(ptr, value, (size_t)bytes, stream);
+}
+
+int svsr_memcpy_async(void* dst, const void* src, int64_t bytes, hipStream_t stream) {
+    if (dst == nullptr || src == nullptr || bytes < 0) return SVSR_ERR_ARG;
+    return (int)hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToDevice, stream);
 }
 
 }  // extern "C"

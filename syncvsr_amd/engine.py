@@ -22,7 +22,7 @@ import torch.distributed as dist
 
 from . import ops
 from .config import Config
-from .model import TransformerLightningModule
+from .model import TransformerLightningModule, _xt_skips
 from .shape_cache import ShapeLRU, shape_key
 
 
@@ -96,7 +96,9 @@ class TrainStep:
         """native=True: the launch sequence of the first step is recorded into a native step list (csrc/steplist.hip) and every
         later step re-issues it with one library call per segment — eager launches on the same streams (the weight-gradient side
         stream keeps overlapping, which a captured HIP graph loses) without the per-launch host cost of the Python loop.  Batch
-        shapes are fixed by the first call, as with use_graph.
+        shapes are fixed by the first call, as with use_graph.  With layer_dropout (the x-transformers encoder) the list holds every
+        encoder block as an op group; each step draws the skipped blocks on the host where an eager step draws them (model._xt_skips)
+        and the replay leaves their launches out.
 
         max_shapes > 1 (native only): one recorded list per batch shape (shape_cache.shape_key of the prepared inputs for LRS, of the
         batch for LRW), each with its own static inputs and outputs; parameters, optimiser state, buffers, the dropout word and the
@@ -137,8 +139,6 @@ class TrainStep:
             raise ValueError("native=True and use_graph=True are two ways of replaying a step: pick one")
         if self.native and not self.is_lrw and getattr(model, "length_norm", False):
             raise NotImplementedError("native=True: transformer_length_normalized_loss needs a torch kernel inside the step (use native=False)")
-        if self.native and getattr(model, "layer_drop_p", 0.0) > 0.0:
-            raise NotImplementedError("layer_dropout changes the launch sequence from step to step: it cannot be replayed from a recorded list")
         if int(max_shapes) < 1:
             raise ValueError("max_shapes must be >= 1")
         if int(max_shapes) > 1 and not self.native:
@@ -295,10 +295,17 @@ class TrainStep:
             model._advance_dropout(static[0].device)      # creates the seed word outside the recorded region ...
             ops.word_add(model._drop_word, -1)             # ... and leaves its value where the first forward expects it
         rec = ops.StepRecorder()
+        if self._layer_drop():
+            rec.layer_groups = True
+            rec.skips = frozenset(_xt_skips(model))       # this step's draw: recorded append-only, see StepRecorder.group
         with ops.recording(rec):
             out = self._direct_impl(*static)
         out = {k: v.detach() for k, v in out.items()} if isinstance(out, dict) else tuple(v.detach() for v in out)
         return static, rec, out
+
+    def _layer_drop(self) -> bool:
+        """Layer drop is on: the recorded lists hold every encoder block as an op group (model._xt_encoder_forward / _backward)."""
+        return self.is_lrw and getattr(self.model, "layer_drop_p", 0.0) > 0.0
 
     def _count(self, key, i: int) -> None:
         self._counts.setdefault(key, [0, 0])[i] += 1
@@ -394,6 +401,8 @@ class TrainStep:
             raise RuntimeError("a recorded TrainStep must be replayed on the stream it was recorded on")
         if self.dp is not None:
             self.dp.begin_step()
+        if self._rec.layer_groups:
+            self._rec.set_skips(_xt_skips(model))       # once per step, as the eager forward draws it
         self._rec.run()
         model._store.generation += 1
 

@@ -1014,38 +1014,86 @@ def _xt_skips(model) -> set:
     return {n for n in range(2 * model.layers) if model._layer_rng.random() < model.layer_drop_p}
 
 
-def _xt_encoder_forward(model, st: _ParamStore, tape: dict, feats: torch.Tensor, wm: Optional[torch.Tensor], B: int, T: int) -> torch.Tensor:
-    D, Dp, S, H, E = model.dim, model.dim_p, T + 1, model.heads, model.attn_inner
+def _xt_block_fwd(model, st: _ParamStore, tape: dict, x: torch.Tensor, n: int, B: int, S: int, tab: torch.Tensor, nrot: int) -> torch.Tensor:
+    """Block `encoder.layers.{n}` (even n: attention, odd n: feed-forward) on the residual stream x -> the block's output x1."""
+    D, Dp, H, E = model.dim, model.dim_p, model.heads, model.attn_inner
     I, Ip, Up = model.inter, model.inter_p, model.glu_p
-    R = B * S
+    R, i, b = B * S, n // 2, f"encoder.layers.{n}"
+    h, inv = ops.rmsnorm_fwd(x, st.p32(f"{b}.0.0.g"), D, model.rms_eps)
+    if n % 2 == 0:
+        qkv, _ = ops.linear_fwd(h, st.s16(f"{b}.1.to_q.weight", 3 * E * Dp), None, rows=R, K=Dp, N=3 * E, x_pitch=Dp)
+        ops.rotary_(qkv, tab, S, nrot, 1)
+        dpr = model._d(f"enc.{i}.attn.probs", "attn")
+        ctx, probs = ops.mha_fwd(qkv, 3 * E, qkv[:, E:], qkv[:, 2 * E:], 3 * E, B=B, H=H, Lq=S, Lk=S, drop=dpr)
+        x1, _ = ops.linear_fwd(ctx, st.s16(f"{b}.1.to_out.weight"), None, rows=R, K=E, N=Dp, x_pitch=E, addend=x)
+        tape[b] = dict(x=x, h=h, inv=inv, qkv=qkv, ctx=ctx, probs=probs, dpr=dpr)
+    else:
+        u, _ = ops.linear_fwd(h, st.s16(f"{b}.1.ff.0.proj.weight"), st.p32(f"{b}.1.ff.0.proj.bias"), rows=R, K=Dp, N=Up, x_pitch=Dp)
+        dff = model._d(f"enc.{i}.ff.hidden")
+        y = ops.geglu_fwd(u, I, Ip, drop=dff)
+        x1, _ = ops.linear_fwd(y, st.s16(f"{b}.1.ff.3.weight"), st.p32(f"{b}.1.ff.3.bias"), rows=R, K=Ip, N=Dp, x_pitch=Ip, addend=x)
+        tape[b] = dict(x=x, h=h, inv=inv, u=u, y=y, dff=dff)
+    return x1
+
+
+def _xt_block_bwd(model, st: _ParamStore, tape: dict, dx: torch.Tensor, n: int, B: int, S: int) -> torch.Tensor:
+    """Backward of block `encoder.layers.{n}`: gradient of the residual stream after the block -> before it (the weight gradients go to
+    the flat buffer, on the side stream)."""
+    D, Dp, H, E = model.dim, model.dim_p, model.heads, model.attn_inner
+    I, Ip, Up = model.inter, model.inter_p, model.glu_p
+    R, b, t, tx = B * S, f"encoder.layers.{n}", tape[f"encoder.layers.{n}"], tape["xt"]
+    if n % 2 == 1:
+        _lin_wgrad(model, t["y"], dx, st.g32(f"{b}.1.ff.3.weight"), st.g32(f"{b}.1.ff.3.bias"), R, Ip, Dp, Ip, Dp)
+        dy = ops.linear_dgrad(dx, st.t16(f"{b}.1.ff.3.weight"), rows=R, N=Dp, K=Ip, dy_pitch=Dp)
+        du = ops.geglu_bwd(dy, t["u"], I, drop=t["dff"])
+        _lin_wgrad(model, t["h"], du, st.g32(f"{b}.1.ff.0.proj.weight"), st.g32(f"{b}.1.ff.0.proj.bias"), R, Dp, Up, Dp, Up)
+        dhn = ops.linear_dgrad(du, st.t16(f"{b}.1.ff.0.proj.weight"), rows=R, N=Up, K=Dp, dy_pitch=Up)
+    else:
+        _lin_wgrad(model, t["ctx"], dx, st.g32(f"{b}.1.to_out.weight"), None, R, E, Dp, E, Dp)
+        dctx = ops.linear_dgrad(dx, st.t16(f"{b}.1.to_out.weight"), rows=R, N=Dp, K=E, dy_pitch=Dp)
+        qkv = t["qkv"]
+        dqkv = torch.empty_like(qkv)
+        ops.mha_bwd(dctx, qkv, 3 * E, qkv[:, E:], qkv[:, 2 * E:], 3 * E, t["probs"], B=B, H=H, Lq=S, Lk=S, dq=dqkv, dq_pitch=3 * E,
+                    dk=dqkv[:, E:], dv=dqkv[:, 2 * E:], dkv_pitch=3 * E, drop=t["dpr"])
+        ops.rotary_(dqkv, tx["tab"], S, tx["nrot"], -1)           # the rotation is orthogonal: its transpose is the inverse rotation
+        gq = st.grad[st.offsets[f"{b}.1.to_q.weight"][0]:][: 3 * E * Dp]
+        _lin_wgrad(model, t["h"], dqkv, gq, None, R, Dp, 3 * E, Dp, 3 * E)
+        dhn = ops.linear_dgrad(dqkv, st.t16(f"{b}.1.qkv"), rows=R, N=3 * E, K=Dp, dy_pitch=3 * E)
+    return ops.rmsnorm_bwd(dhn, t["x"], st.p32(f"{b}.0.0.g"), t["inv"], st.g32(f"{b}.0.0.g"), D, addend=dx)
+
+
+def _xt_grouped(model, rec, n: int, fn, inp: torch.Tensor) -> torch.Tensor:
+    """Replayable layer drop (rec = ops.layer_groups()): block n's launches as op group n of the recorded list, then the pass-through
+    copy that every replay skipping n issues instead (the block's input, whole padded rows, into its output buffer).  The side stream's
+    pending launches are handed over inside the group, so none of them is issued outside it."""
+    with rec.group(n):
+        out = fn()
+        model._side.flush()
+    rec.passthrough(out, inp, n)
+    return out
+
+
+def _xt_encoder_forward(model, st: _ParamStore, tape: dict, feats: torch.Tensor, wm: Optional[torch.Tensor], B: int, T: int) -> torch.Tensor:
+    D, Dp, S, H = model.dim, model.dim_p, T + 1, model.heads
     d_in = model._d("emb.in", "emb")
     x = ops.xt_embed_fwd(feats, wm, st.p32("cls_token"), B, S, feats.shape[-1], D, Dp, drop=d_in)
     key = (S, str(feats.device))
     if key not in model._rot_tab:
         model._rot_tab[key] = ops.rotary_table(S, feats.device)
     tab = model._rot_tab[key]
-    skip = _xt_skips(model)
+    # under a recorder that replays layer drop (engine.TrainStep(native=True)) every block is emitted: the skip set was drawn by the
+    # engine, where this draws it in an eager step
+    rec = ops.layer_groups()
+    skip = _xt_skips(model) if rec is None else set()
     nrot = (3 if model.rotate_value else 2) * H
-    tape["xt"] = dict(d_in=d_in, tab=tab, nrot=nrot, F=feats.shape[-1])
-    for i in range(model.layers):
-        a, f = f"encoder.layers.{2 * i}", f"encoder.layers.{2 * i + 1}"
-        if 2 * i not in skip:
-            h, inv = ops.rmsnorm_fwd(x, st.p32(f"{a}.0.0.g"), D, model.rms_eps)
-            qkv, _ = ops.linear_fwd(h, st.s16(f"{a}.1.to_q.weight", 3 * E * Dp), None, rows=R, K=Dp, N=3 * E, x_pitch=Dp)
-            ops.rotary_(qkv, tab, S, nrot, 1)
-            dpr = model._d(f"enc.{i}.attn.probs", "attn")
-            ctx, probs = ops.mha_fwd(qkv, 3 * E, qkv[:, E:], qkv[:, 2 * E:], 3 * E, B=B, H=H, Lq=S, Lk=S, drop=dpr)
-            x1, _ = ops.linear_fwd(ctx, st.s16(f"{a}.1.to_out.weight"), None, rows=R, K=E, N=Dp, x_pitch=E, addend=x)
-            tape[a] = dict(x=x, h=h, inv=inv, qkv=qkv, ctx=ctx, probs=probs, dpr=dpr)
-            x = x1
-        if 2 * i + 1 not in skip:
-            h, inv = ops.rmsnorm_fwd(x, st.p32(f"{f}.0.0.g"), D, model.rms_eps)
-            u, _ = ops.linear_fwd(h, st.s16(f"{f}.1.ff.0.proj.weight"), st.p32(f"{f}.1.ff.0.proj.bias"), rows=R, K=Dp, N=Up, x_pitch=Dp)
-            dff = model._d(f"enc.{i}.ff.hidden")
-            y = ops.geglu_fwd(u, I, Ip, drop=dff)
-            x1, _ = ops.linear_fwd(y, st.s16(f"{f}.1.ff.3.weight"), st.p32(f"{f}.1.ff.3.bias"), rows=R, K=Ip, N=Dp, x_pitch=Ip, addend=x)
-            tape[f] = dict(x=x, h=h, inv=inv, u=u, y=y, dff=dff)
-            x = x1
+    tape["xt"] = dict(d_in=d_in, tab=tab, nrot=nrot, F=feats.shape[-1], grouped=rec is not None)
+    for n in range(2 * model.layers):
+        if n in skip:
+            continue
+        if rec is None:
+            x = _xt_block_fwd(model, st, tape, x, n, B, S, tab, nrot)
+        else:
+            x = _xt_grouped(model, rec, n, lambda: _xt_block_fwd(model, st, tape, x, n, B, S, tab, nrot), x)
     if model.final_norm:
         h, inv = ops.rmsnorm_fwd(x, st.p32("encoder.final_norm.g"), D, model.rms_eps)
         tape["xt"]["final"] = dict(x=x, inv=inv)
@@ -1054,37 +1102,23 @@ def _xt_encoder_forward(model, st: _ParamStore, tape: dict, feats: torch.Tensor,
 
 
 def _xt_encoder_backward(model, st: _ParamStore, tape: dict, dh: torch.Tensor, B: int, T: int) -> torch.Tensor:
-    D, Dp, S, H, E = model.dim, model.dim_p, T + 1, model.heads, model.attn_inner
-    I, Ip, Up = model.inter, model.inter_p, model.glu_p
-    R = B * S
+    D, S = model.dim, T + 1
     tx = tape["xt"]
+    rec = ops.layer_groups() if tx["grouped"] else None
+    if tx["grouped"] and rec is None:
+        raise RuntimeError("the forward emitted op groups for a recorded step list: its backward must run in the same recording")
     dx = dh
     if "final" in tx:
         dx = ops.rmsnorm_bwd(dx, tx["final"]["x"], st.p32("encoder.final_norm.g"), tx["final"]["inv"], st.g32("encoder.final_norm.g"), D)
     for i in reversed(range(model.layers)):
-        a, f = f"encoder.layers.{2 * i}", f"encoder.layers.{2 * i + 1}"
-        if f in tape:
-            t = tape[f]
-            _lin_wgrad(model, t["y"], dx, st.g32(f"{f}.1.ff.3.weight"), st.g32(f"{f}.1.ff.3.bias"), R, Ip, Dp, Ip, Dp)
-            dy = ops.linear_dgrad(dx, st.t16(f"{f}.1.ff.3.weight"), rows=R, N=Dp, K=Ip, dy_pitch=Dp)
-            du = ops.geglu_bwd(dy, t["u"], I, drop=t["dff"])
-            _lin_wgrad(model, t["h"], du, st.g32(f"{f}.1.ff.0.proj.weight"), st.g32(f"{f}.1.ff.0.proj.bias"), R, Dp, Up, Dp, Up)
-            dhn = ops.linear_dgrad(du, st.t16(f"{f}.1.ff.0.proj.weight"), rows=R, N=Up, K=Dp, dy_pitch=Up)
-            dx = ops.rmsnorm_bwd(dhn, t["x"], st.p32(f"{f}.0.0.g"), t["inv"], st.g32(f"{f}.0.0.g"), D, addend=dx)
-        if a in tape:
-            t = tape[a]
-            _lin_wgrad(model, t["ctx"], dx, st.g32(f"{a}.1.to_out.weight"), None, R, E, Dp, E, Dp)
-            dctx = ops.linear_dgrad(dx, st.t16(f"{a}.1.to_out.weight"), rows=R, N=Dp, K=E, dy_pitch=Dp)
-            qkv = t["qkv"]
-            dqkv = torch.empty_like(qkv)
-            ops.mha_bwd(dctx, qkv, 3 * E, qkv[:, E:], qkv[:, 2 * E:], 3 * E, t["probs"], B=B, H=H, Lq=S, Lk=S, dq=dqkv, dq_pitch=3 * E,
-                        dk=dqkv[:, E:], dv=dqkv[:, 2 * E:], dkv_pitch=3 * E, drop=t["dpr"])
-            ops.rotary_(dqkv, tx["tab"], S, tx["nrot"], -1)           # the rotation is orthogonal: its transpose is the inverse rotation
-            gq = st.grad[st.offsets[f"{a}.1.to_q.weight"][0]:][: 3 * E * Dp]
-            _lin_wgrad(model, t["h"], dqkv, gq, None, R, Dp, 3 * E, Dp, 3 * E)
-            dhn = ops.linear_dgrad(dqkv, st.t16(f"{a}.1.qkv"), rows=R, N=3 * E, K=Dp, dy_pitch=3 * E)
-            dx = ops.rmsnorm_bwd(dhn, t["x"], st.p32(f"{a}.0.0.g"), t["inv"], st.g32(f"{a}.0.0.g"), D, addend=dx)
-        _ready(model, st, f"{a}.1.to_q.weight")
+        for n in (2 * i + 1, 2 * i):
+            if f"encoder.layers.{n}" not in tape:
+                continue
+            if rec is None:
+                dx = _xt_block_bwd(model, st, tape, dx, n, B, S)
+            else:
+                dx = _xt_grouped(model, rec, n, lambda: _xt_block_bwd(model, st, tape, dx, n, B, S), dx)
+        _ready(model, st, f"encoder.layers.{2 * i}.1.to_q.weight")
     dfeats = ops.xt_embed_bwd(dx, st.g32("cls_token"), B, S, tx["F"], D, drop=tx["d_in"])
     _ready(model, st, "cls_token")
     return dfeats

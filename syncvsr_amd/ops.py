@@ -218,6 +218,12 @@ class StepRecorder:
         self.callbacks: dict[int, list[Callable[[], None]]] = {}      # segment index -> host calls that follow it
         self.main_stream: Optional[int] = None
         self.closed = False
+        # layer drop (model._xt_encoder_forward / _backward): with layer_groups set, the encoder emits every block inside op group n
+        # (`encoder.layers.{n}`) followed by a pass-through copy, and each replay leaves out the groups set_skips() names.  `skips`: the
+        # groups the RECORDING step itself skips — recorded append-only (below), their pass-through copies executed.
+        self.layer_groups = False
+        self.skips: frozenset = frozenset()
+        self.append_only = False
 
     def __del__(self):
         try:
@@ -253,6 +259,60 @@ class StepRecorder:
 
     def memset(self, ptr: int, value: int, nbytes: int, stream: int) -> None:
         _lib.check(self.lib.svsr_steplist_push_memset(self.handle, ptr, value, nbytes, stream), "svsr_steplist_push_memset")
+
+    @contextmanager
+    def group(self, n: int):
+        """Every launch and memset inside the block belongs to op group n.  When the recording step skips n (n in `skips`) they are
+        appended WITHOUT being executed: the list must hold every block for later replays, while this step produces the bits of an
+        eager step that skips n.  (Recording the whole list without executing and then running it once with the mask was the other way:
+        it would also defer what executes on the host inside the step — the collectives of host_callback, allocations sized by results —
+        while append-only touches nothing outside the skipped groups.)  Tensors allocated inside are kept alive like any other
+        (torch.empty is wrapped for the whole recording): a later replay may execute the group.  Cross-stream waits are executed and
+        recorded as always: the list issues them whatever is skipped."""
+        _lib.check(self.lib.svsr_steplist_push_group(self.handle, int(n)), f"svsr_steplist_push_group({n})")
+        self.append_only = n in self.skips
+        try:
+            yield
+        finally:
+            self.append_only = False
+            _lib.check(self.lib.svsr_steplist_push_group(self.handle, -1), "svsr_steplist_push_group(-1)")
+
+    def passthrough(self, dst: torch.Tensor, src: torch.Tensor, group: int) -> None:
+        """dst <- src (whole contiguous tensors, same size) on the current stream in every replay that skips `group` — and now, when the
+        recording step skips it."""
+        if dst.numel() * dst.element_size() != src.numel() * src.element_size() or not (dst.is_contiguous() and src.is_contiguous()):
+            raise ValueError("passthrough copies whole contiguous tensors of one size")
+        nbytes, stream = src.numel() * src.element_size(), _stream()
+        if group in self.skips:
+            _lib.check(self.lib.svsr_memcpy_async(dst.data_ptr(), src.data_ptr(), nbytes, stream), "svsr_memcpy_async")
+        _lib.check(self.lib.svsr_steplist_push_copy(self.handle, dst.data_ptr(), src.data_ptr(), nbytes, stream, int(group)),
+                   "svsr_steplist_push_copy")
+
+    @property
+    def groups(self) -> int:
+        return int(self.lib.svsr_steplist_groups(self.handle))
+
+    def calls(self, group: int = -1) -> int:
+        """CALL ops of op group `group` (-1: of the whole list)."""
+        n = int(self.lib.svsr_steplist_calls(self.handle, int(group)))
+        if n < 0:
+            _lib.check(-n, f"svsr_steplist_calls({group})")
+        return n
+
+    def set_skips(self, skips) -> None:
+        """The op groups every following run() leaves out (an iterable of group indices)."""
+        n = self.groups
+        mask = (ctypes.c_uint8 * max(n, 1))()
+        for g in skips:
+            if not 0 <= g < n:
+                raise ValueError(f"op group {g} is not in this step list ({n} groups)")
+            mask[g] = 1
+        _lib.check(self.lib.svsr_steplist_set_skips(self.handle, mask, n), "svsr_steplist_set_skips")
+
+    @property
+    def last_issued(self) -> int:
+        """Launches (CALL ops) the last run() issued."""
+        return int(self.lib.svsr_steplist_last_issued(self.handle))
 
     def add_callback(self, fn: Callable[[], None]) -> None:
         seg = self.lib.svsr_steplist_push_break(self.handle)
@@ -338,6 +398,11 @@ def recording(rec: StepRecorder):
         rec.closed = True
 
 
+def layer_groups() -> Optional[StepRecorder]:
+    """The active recorder when it asks for replayable layer drop (StepRecorder.layer_groups), else None."""
+    return _REC if _REC is not None and _REC.layer_groups else None
+
+
 def host_callback(fn: Callable[[], None]) -> None:
     """Runs fn() now; inside a recorded step it also closes the current segment and is called again after that segment in
     every replay (collectives and their stream joins: engine.GradReducer)."""
@@ -374,6 +439,9 @@ def shader_clock_mhz(blocks: int = 256, iters: int = 20000) -> float:
 def memset(t: torch.Tensor, value: int = 0) -> None:
     """hipMemsetAsync over a contiguous tensor on the current stream."""
     nbytes, stream = t.numel() * t.element_size(), _stream()
+    if _REC is not None and _REC.append_only:          # (a group the recording step skips: appended, not executed)
+        _REC.memset(t.data_ptr(), value, nbytes, stream)
+        return
     _lib.check(_lib.load().svsr_memset_async(t.data_ptr(), value, nbytes, stream), "svsr_memset_async")
     if _REC is not None:
         _REC.memset(t.data_ptr(), value, nbytes, stream)
@@ -405,6 +473,9 @@ def lincomb3_ratio(a, wa: float, b, wb: float, c, wc: float, num=None, den=None)
 
 
 def _call(name: str, *args, label: Optional[str] = None, flops: float = 0.0, nbytes: float = 0.0) -> None:
+    if _REC is not None and _REC.append_only:          # (a group the recording step skips: appended, not executed)
+        _REC.call(name, args)
+        return
     timing = _TIMING
     if timing is not None:
         s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
