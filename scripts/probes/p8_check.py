@@ -107,14 +107,13 @@ if __name__ == "__main__":
         x3 = (torch.randn(928, 6, 6, 256, device=dev) * 0.5).to(BF16); w3 = (torch.randn(256, 3, 3, 256, device=dev) * 0.05).to(BF16)
         x1 = (torch.randn(928, 22, 22, 128, device=dev) * 0.5).to(BF16)
         ops.tune("p8", 1)
-        for ph in (1, 2):
-            for stg in (1, 0):
-                for grid in (0, 224, 192):
-                    ops.tune("p8_ph", ph); ops.tune("p8_stagger", stg); ops.tune("p8_grid", grid)
-                    t2 = timeit(lambda: ops.conv2d_fwd(x2, w2, 3, 1, 1, want_stats=True), 30)
-                    t3 = timeit(lambda: ops.conv2d_fwd(x3, w3, 3, 1, 1, want_stats=True), 30)
-                    t1 = timeit(lambda: ops.conv2d_fwd(x1, w2, 3, 1, 1, want_stats=True), 10)
-                    print(f"ph {ph} stagger {stg} grid {grid}: layer2 {t2:.1f} us  layer3 {t3:.1f} us  22x22x128 {t1:.1f} us")
+        for stg in (1, 0):
+            for grid in (0, 224, 192):
+                ops.tune("p8_stagger", stg); ops.tune("p8_grid", grid)
+                t2 = timeit(lambda: ops.conv2d_fwd(x2, w2, 3, 1, 1, want_stats=True), 30)
+                t3 = timeit(lambda: ops.conv2d_fwd(x3, w3, 3, 1, 1, want_stats=True), 30)
+                t1 = timeit(lambda: ops.conv2d_fwd(x1, w2, 3, 1, 1, want_stats=True), 10)
+                print(f"stagger {stg} grid {grid}: layer2 {t2:.1f} us  layer3 {t3:.1f} us  22x22x128 {t1:.1f} us")
         sys.exit(0)
     good = True
     good &= run(16, 11, 128, 5)           # small: holes, partial tiles (the 4-wave kernel splits K here: results agree to rounding only)

@@ -166,7 +166,7 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmFwdArgs& p, f32x16 (&a
                 *reinterpret_cast<u32x4*>(reinterpret_cast<bf16_t*>(p.out) + offs[i] + n) = pack8(v);
             }
         }
-    } else if (active && vec_pitch && n + 8 <= p.Co && p.epi_batched) {
+    } else if (__builtin_expect(active && vec_pitch && n + 8 <= p.Co, 1)) {      // (the usual case; the hint keeps hipcc from spilling SGPRs here)
         long offs[ITERS];
         f32x4 lo[ITERS], hi[ITERS];
         u32x4 add8[ITERS];
@@ -533,7 +533,7 @@ __global__ __launch_bounds__(256 * KG) void k_igemm_fwd_glds(const IgemmFwdArgs 
 // ---------------------------------------------------------------------------------------------------------------------
 template <int BM, int BN, int NS, int KG = 1>
 static int launch_glds(const IgemmFwdArgs& a, int gx, int gy, hipStream_t stream) {
-    const size_t lds = (size_t)KG * NS * (BM + BN) * 64 * sizeof(bf16_t) + (size_t)BM * sizeof(long) + 128 + (size_t)svsr_tune_get(SVSR_TUNE_IGEMM_LDS_PAD);
+    const size_t lds = (size_t)KG * NS * (BM + BN) * 64 * sizeof(bf16_t) + (size_t)BM * sizeof(long) + 128;
     static size_t attr_set = 0;
     if (attr_set < lds) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_igemm_fwd_glds<BM, BN, NS, KG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -575,7 +575,6 @@ static IgemmFwdPlan igemm_fwd_plan(long M, int Co, int max_taps) {
     else { pl.bm = 64; pl.bn = 64; pl.ns = 0; }
     pl.gy = (Co + pl.bn - 1) / pl.bn;
     if (pl.ns == 0) pl.ns = ((M + pl.bm - 1) / pl.bm) * pl.gy <= (long)cus * 5 / 2 ? 4 : 3;
-    if (pl.bm == 64 && pl.bn == 64 && (svsr_tune_get(SVSR_TUNE_IGEMM_NS64) == 6 || svsr_tune_get(SVSR_TUNE_IGEMM_NS64) == 8)) pl.ns = svsr_tune_get(SVSR_TUNE_IGEMM_NS64);
     return pl;
 }
 
@@ -637,8 +636,8 @@ static int plan_emit(std::vector<PlanClass>& cls, int Nimg, int Co, int* words, 
         const int min_items = svsr_tune_get(SVSR_TUNE_P8_MIN_ITEMS);
         if (min_taps >= 4 && Co % P8_BN == 0 && tiles_m * (Co / P8_BN) >= min_items)
             return plan_emit_p8(cls, Nimg, Co, p8_pix[0], p8_pix[1], words, cap_words, meta, M, max_taps, P8_BN);
-        // too few 256 x 128 items to give every CU one (layer4: 33 row tiles x 4): 256 x 64 tiles (tune key p8_bn64)
-        if (min_taps >= 4 && Co >= 128 && tiles_m * (Co / 64) >= min_items && svsr_tune_get(SVSR_TUNE_P8_BN64))
+        // too few 256 x 128 items to give every CU one (layer4: 33 row tiles x 4): 256 x 64 tiles
+        if (min_taps >= 4 && Co >= 128 && tiles_m * (Co / 64) >= min_items)
             return plan_emit_p8(cls, Nimg, Co, p8_pix[0], p8_pix[1], words, cap_words, meta, M, max_taps, 64);
     }
     const IgemmFwdPlan pl = igemm_fwd_plan(M, Co, max_taps);
@@ -796,7 +795,6 @@ static int igemm_fwd_run(const void* in, const void* wt, void* out, void* out_pr
     a.Nimg = Nimg; a.in_pix = in_pix; a.Ci = Ci; a.in_pitch = in_pitch; a.Co = Co; a.out_pix = out_pix; a.out_pitch = out_pitch;
     a.wt_taps = wt_taps; a.act = act; a.out_f32 = out_f32; a.alpha = alpha;
     a.drop = svsr_make_drop(drop_seed, drop_site, drop_p);
-    a.epi_batched = svsr_tune_get(SVSR_TUNE_EPI_BATCHED);
     a.bnb_y = (const bf16_t*)bnb_y; a.bnb_x = (const bf16_t*)bnb_x; a.bnb_mean = bnb_mean; a.bnb_rstd = bnb_rstd;
     a.bnb_gamma = bnb_gamma; a.bnb_beta = bnb_beta; a.bnb_act = bnb_act;
     const int bm = meta[0], bn = meta[1], ns = meta[2], gx = meta[3], gy = (Co + bn - 1) / bn;
@@ -813,8 +811,6 @@ static int igemm_fwd_run(const void* in, const void* wt, void* out, void* out_pr
     SVSR_IGEMM_CASE(128, 64, 3);
     SVSR_IGEMM_CASE(64, 64, 4);
     SVSR_IGEMM_CASE(64, 64, 3);
-    SVSR_IGEMM_CASE(64, 64, 6);
-    SVSR_IGEMM_CASE(64, 64, 8);
 #undef SVSR_IGEMM_CASE
     return SVSR_ERR_ARG;
 }

@@ -576,7 +576,7 @@ static WgradUnits wgrad_units(const std::vector<long>& tap_chunks, int co_tiles,
     std::vector<int> order(nu);
     for (int i = 0; i < nu; ++i) order[i] = i;
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return w.units[a * WUNIT_WORDS + 2] > w.units[b * WUNIT_WORDS + 2]; });
-    if (svsr_tune_get(SVSR_TUNE_WG_XCD) && ntaps > 1) {
+    if (ntaps > 1) {
         // Multi-tap plans (the 3 x 3 / stride-2 convolutions): the units of all taps and channel tiles that cover the same stretch of the
         // contraction read the same rows of x and dy.  Workgroup b runs on XCD b % 8 (observed, never relied on for correctness), each XCD has
         // its own L2, and in plain index order every XCD ends up streaming ALL rows: 289 MB of fabric traffic per layer3 launch for <= 58 MB of

@@ -453,79 +453,12 @@ __global__ __launch_bounds__(256) void k_stem_pool_bwd_apply(const bf16_t* __res
 
 
 // ---------------------------------------------------------------------------------------------------------
-// LDS-tiled variants of the stem passes (backward: default; forward: opt-in, see stem_lds_fwd()).  The first versions above evaluate the activation of every conv
-// output once per pooling window that contains it (2.25x) and gather dpool/amax for every element from L2 (six times
-// the bytes of the element itself); here a workgroup stages what it needs once:
-//   forward : act(bn(x)) of the 2*PR+1 input rows behind PR pooled rows, fp32 (exact argmax), then 3x3 max from LDS
-//   backward: dpool + amax of the R/2+1 pooled rows above R input rows, then the routing gather from LDS
+// LDS-tiled variants of the stem's backward passes.  The first versions above gather dpool/amax for every element from L2 (six times
+// the bytes of the element itself); here a workgroup stages dpool + amax of the R/2+1 pooled rows above R input rows once, then
+// routes from LDS.  (The forward stays direct: an LDS-tiled form measured 225 us against 191 at 928 x 44 x 44 x 64 — that pass is
+// bound by the erf/exp VALU work, not by the redundant window reads.)
 // ---------------------------------------------------------------------------------------------------------
-#define STEM_PR 2
 #define STEM_BR 8
-
-template <int ACT>
-__global__ __launch_bounds__(256) void k_stem_fwd_lds(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, unsigned char* __restrict__ amax,
-                                                      const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                      int Hc, int Wc, int Hp, int Wp, int C) {
-    extern __shared__ __attribute__((aligned(16))) float sAct[];      // [2*PR+1][Wc][C]
-    const int cv = C >> 3;
-    const int n = blockIdx.y, ph0 = blockIdx.x * STEM_PR, h_lo = 2 * ph0 - 1;
-    const int c0 = (threadIdx.x % cv) * 8;                           // 256 % cv == 0: a thread keeps its channel group
-    float sc[8], sh[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { sc[k] = gamma[c0 + k] * rstd[c0 + k]; sh[k] = beta[c0 + k] - mean[c0 + k] * sc[k]; }
-    const int wcv = Wc * cv;
-    const int items = (2 * STEM_PR + 1) * wcv;
-    for (int e = threadIdx.x; e < items; e += 256) {
-        const int r = e / wcv, rem = e - r * wcv, w = rem / cv, h = h_lo + r;
-        float f[8];
-        if (h >= 0 && h < Hc) {
-            unpack8(*reinterpret_cast<const u32x4*>(x + (((long)n * Hc + h) * Wc + w) * C + c0), f);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) { const float z = f[k] * sc[k] + sh[k]; f[k] = ACT == 2 ? swish(z) : gelu_erf(z); }
-        } else {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) f[k] = -INFINITY;
-        }
-        float* d = sAct + (long)(r * Wc + w) * C + c0;
-        *reinterpret_cast<f32x4*>(d) = f32x4{f[0], f[1], f[2], f[3]};
-        *reinterpret_cast<f32x4*>(d + 4) = f32x4{f[4], f[5], f[6], f[7]};
-    }
-    __syncthreads();
-    const int pcv = Wp * cv;
-    for (int e = threadIdx.x; e < STEM_PR * pcv; e += 256) {
-        const int pl = e / pcv, rem = e - pl * pcv, pw = rem / cv, ph = ph0 + pl;
-        if (ph >= Hp) break;
-        float best[8];
-        int bi[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { best[k] = -INFINITY; bi[k] = 0; }
-        bool first = true;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const int h = 2 * ph - 1 + i;
-            if (h < 0 || h >= Hc) continue;
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const int w = 2 * pw - 1 + j;
-                if (w < 0 || w >= Wc) continue;
-                const float* sp = sAct + (long)((2 * pl + i) * Wc + w) * C + c0;
-                const f32x4 lo = *reinterpret_cast<const f32x4*>(sp), hi = *reinterpret_cast<const f32x4*>(sp + 4);
-                const float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-#pragma unroll
-                for (int k = 0; k < 8; ++k)
-                    if (first || v[k] > best[k]) { best[k] = v[k]; bi[k] = i * 3 + j; }
-                first = false;
-            }
-        }
-        const long o = (((long)n * Hp + ph) * Wp + pw) * C + c0;
-        *reinterpret_cast<u32x4*>(y + o) = pack8(best);
-        unsigned lo = 0, hi = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { lo |= (unsigned)bi[k] << (8 * k); hi |= (unsigned)bi[k + 4] << (8 * k); }
-        *reinterpret_cast<uint2*>(amax + o) = make_uint2(lo, hi);
-    }
-}
 
 // GP: `dpool` already is g = dpool * act'(z of the window's winner) (written by k_stem_bwd_reduce_win): no activation derivative here —
 // evaluated per convolution element it was 4 of the pass's ~6 G vector operations
@@ -768,10 +701,6 @@ static inline int ew_grid(long nvec) {
     if (b < 1) b = 1;
     return (int)b;
 }
-// measured at 928 x 44 x 44 x 64: forward 191 us (direct) vs 225 us (LDS-tiled) — the pass is bound by the erf/exp VALU work,
-// not by the redundant window reads; backward 411 us (direct) vs 360 us (LDS-tiled).  Defaults follow the measurement.
-static inline bool stem_lds_fwd() { return svsr_tune_get(SVSR_TUNE_STEM_LDS_FWD) != 0; }
-static inline bool stem_lds_bwd() { return svsr_tune_get(SVSR_TUNE_STEM_LDS_BWD) != 0; }
 static inline bool chan_ok(int C) { return C >= 8 && C <= 2048 && (2048 % C) == 0; }
 // any C % 8 == 0 up to 2048 (e.g. 768): the grid is rounded so that gridDim.x * 256 is a multiple of C/8 and every
 // thread keeps one channel group across its grid-stride loop
@@ -869,25 +798,6 @@ int svsr_stem_bn_act_pool_fwd(const void* x, void* y, void* amax, const float* m
     if (!chan_ok(C) || (act != SVSR_ACT_GELU && act != SVSR_ACT_SWISH)) return SVSR_ERR_ARG;
     StemRowIter it;
     if (!stem_iter(it, C, Wp, Hp)) return SVSR_ERR_ARG;
-    if (stem_lds_fwd() && xwin == nullptr) {
-        const size_t lds = (size_t)(2 * STEM_PR + 1) * Wc * C * sizeof(float);
-        if (lds <= 150 * 1024) {
-            static bool attr = false;
-            if (!attr) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_stem_fwd_lds<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_stem_fwd_lds<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-                attr = true;
-            }
-            const dim3 g2((Hp + STEM_PR - 1) / STEM_PR, N);
-            if (act == SVSR_ACT_SWISH)
-                hipLaunchKernelGGL(k_stem_fwd_lds<2>, g2, dim3(256), lds, stream, (const bf16_t*)x, (bf16_t*)y, (unsigned char*)amax, mean, rstd,
-                                   gamma, beta, Hc, Wc, Hp, Wp, C);
-            else
-                hipLaunchKernelGGL(k_stem_fwd_lds<1>, g2, dim3(256), lds, stream, (const bf16_t*)x, (bf16_t*)y, (unsigned char*)amax, mean, rstd,
-                                   gamma, beta, Hc, Wc, Hp, Wp, C);
-            return svsr_check_launch();
-        }
-    }
     const dim3 grid((Hp + it.rpb - 1) / it.rpb, N);
     if (act == SVSR_ACT_SWISH)
         hipLaunchKernelGGL(k_stem_bn_act_pool_fwd<2>, grid, dim3(256), 0, stream, (const bf16_t*)x, (bf16_t*)y, (unsigned char*)amax, (bf16_t*)xwin, mean,
@@ -898,12 +808,11 @@ int svsr_stem_bn_act_pool_fwd(const void* x, void* y, void* amax, const float* m
     return svsr_check_launch();
 }
 
-static inline bool stem_bwd_uses_lds(int Wp, int C) { return stem_lds_bwd() && (size_t)(STEM_BR / 2 + 1) * Wp * C * 3 <= 60 * 1024; }
-// gather-form reduce pass (k_stem_bwd_reduce_gather): tuning value 2, 64 channels, tile of 2*STEM_GP+1 conv rows within 64 KiB
+// the stem backward: LDS-tiled passes where the pooled rows fit (360 us against 411 for the plain passes at 928 x 44 x 44 x 64)
+static inline bool stem_bwd_uses_lds(int Wp, int C) { return (size_t)(STEM_BR / 2 + 1) * Wp * C * 3 <= 60 * 1024; }
+// gather-form reduce pass (k_stem_bwd_reduce_gather): 64 channels, tile of 2*STEM_GP+1 conv rows within 64 KiB
 static inline size_t stem_gather_lds(int Wc) { const size_t t = (size_t)(((2 * STEM_GP + 1) * Wc * 8 + 255) / 256 * 256) * 16; return t > 16384 ? t : 16384; }
-static inline bool stem_bwd_gathers(int Wc, int Wp, int C) {
-    return svsr_tune_get(SVSR_TUNE_STEM_LDS_BWD) >= 2 && C == 64 && stem_bwd_uses_lds(Wp, C) && stem_gather_lds(Wc) <= 64 * 1024;
-}
+static inline bool stem_bwd_gathers(int Wc, int Wp, int C) { return C == 64 && stem_bwd_uses_lds(Wp, C) && stem_gather_lds(Wc) <= 64 * 1024; }
 
 /* rows of [2][C] partials svsr_stem_bn_act_pool_bwd needs in its workspace for this shape */
 int svsr_stem_bn_act_pool_bwd_rows(int N, int Hc, int Wc, int C) {

@@ -21,35 +21,24 @@ static int g_tune[SVSR_TUNE_N] = {
     /* WG_BLOCKS    */ 0,      // target workgroups of svsr_igemm_wgrad (0: built-in per tile size)
     /* W3_BLOCKS    */ 512,    // target workgroups of svsr_conv3x3_wgrad in its 4-wave form: one round of two per CU; the 8-wave form (W3_WAVES) launches half of it, one per CU (inside the step, 8 waves: 4.874-4.878 / 4.885-4.888 / 4.977-4.986 / 4.943-4.968 ms at 512 / 384 / 640 / 768 in round 5)
     /* LN_RPB       */ 4,      // rows per workgroup of svsr_add_ln_bwd (one per wave: 16 -> 4 measured 6.00 -> 5.97 ms per LRW step)
-    /* STEM_LDS_FWD */ 0,      // LDS-tiled stem BN+act+pool forward (measured slower)
-    /* STEM_LDS_BWD */ 2,      // stem BN+act+pool backward: 0 plain, 1 LDS-tiled passes, 2 LDS-tiled apply pass + gather-form reduce pass (fastest)
-    /* IGEMM_LDS_PAD */ 0,     // extra dynamic LDS bytes per svsr_igemm_fwd workgroup (occupancy experiments: fewer co-resident blocks per CU)
     /* IGEMM_BN64_BELOW */ 300, // multi-tap convolutions with fewer 128x128 tiles than this use 128x64 tiles (three workgroups per CU)
     /* WG_SHORT_K */ 16,       // svsr_igemm_wgrad: contractions of at most this many 64-row chunks use 64-wide tiles and no K split when that fills half the chip
     /* IGEMM_KSPLIT */ 160,    // svsr_igemm_fwd: launches of at most this many 64x64 tiles with >= 12 K steps split K over two wave groups per workgroup (0: never)
-    /* EPI_BATCHED */ 1,       // svsr_igemm_fwd epilogue: all rows' staged accumulators / addend pieces requested before the first is used
-    /* STEM_WG_PIPE */ 1,      // svsr_stem_conv_wgrad: next tile's operands prefetched into registers during the MFMA block
-    /* STEM_FWD_DMA */ 1,      // svsr_stem_conv_fwd: bf16 prep pass + LDS-DMA tile fills (0: direct fp32 -> LDS path)
     /* IGEMM_LIN_BN64 */ 2048, // svsr_igemm_fwd: linears that would get 64x64 tiles use 128x64 tiles from this many rows on (0: never; LRS 768-wide outputs at 2,400 rows: 29.6 -> 29.1 ms per step)
     /* P8 */ 1,                // stride-1 3x3 convolution plans with Co % 128 == 0 and enough tiles use the persistent 8-wave 256x128 kernel (igemm_p8.hip) — also the forward of the stride-2 3x3 convolutions (3: stride 1 only)
     /* P8_GRID */ 0,           // workgroups of that kernel (0: one per CU)
     /* P8_MIN_ITEMS */ 200,    // ... from this many 256x128 tiles on (fewer leave CUs idle for the whole launch)
-    /* P8_PH */ 1,             // phases per K tile of the persistent kernel: 1 (16 MFMAs between barriers) or 2 (8)
     /* P8_STAGGER */ 3,        // bit 0: its two wave groups run their phases one barrier apart; bit 1: odd workgroups walk their rounds last to first (their first epilogue falls elsewhere than the even ones')
     /* WG_IMGMAJOR */ 1,       // svsr_igemm_wgrad plans with >= 64 images enumerate rows by (position, block of 64 images): wave-uniform DMA bases (0: row-major)
-    /* P8_BN64 */ 1,           // 3x3 plans with too few 256 x 128 items for one per CU use 256 x 64 tiles of the persistent kernel (layer4); 0: the 4-wave kernel
-    /* IGEMM_NS64 */ 0,        // ring depth of the 64x64 tiles of svsr_igemm_fwd: 0 auto (3 / 4), or 6 / 8
     /* WG_UNITS */ 1,          // svsr_igemm_wgrad plans of long contractions as balanced unit lists (format 2); 0: (K split, task) grids
     /* WG_UNIT_MAX */ 48,      // ... longest unit in 64-row chunks before the list takes a further round of workgroups
     /* WG_UNIT_MIN */ 8,       // ... shortest unit worth a slab tile of its own
     /* IGEMM_KSPLIT128 */ 12,  // svsr_igemm_fwd: dense layers on <= 288 tiles of 128 x 64 with at least this many 64-deep K steps split K over two wave groups per workgroup (0: never)
-    /* WG_XCD */ 1,            // svsr_igemm_wgrad unit lists of multi-tap plans: units dealt to the eight XCDs by the stretch of the contraction they cover (0: plain long-first order); same results
     /* W3_WAVES */ 8,          // waves per workgroup of svsr_conv3x3_wgrad: 8 (one workgroup per CU, the two wave groups split the nine taps: half the slabs, 138 instead of 247 registers per wave) or 4 (two workgroups per CU, nine taps per wave).  Round 5, same box: layer1 launch + reduce 80.1 -> 71.6 us at 928 frames, LRW step 5.03-5.05 -> 4.97-4.99 ms, LRS 23.69 -> 23.58-23.61
     /* REDUCE_CUS */ 256,      // compute units assumed when the split of a reduction is planned (svsr_reduction_cus, common.h): fixed, so the bits of a run do not depend on the partition it runs on; 0: the device's count
     /* W3_DENSE */ 1,          // svsr_conv3x3_wgrad contracts over the REAL pixels (dense dY tile, X rows gathered through a position table) instead of walking the zero-padded grid: 1.40x / 1.19x fewer MFMAs at 11 x 11 / 22 x 22 maps; 0: the padded walk of rounds 2-5
-    /* P8_WIDE */ 2,           // epilogue of the persistent 8-wave kernel (256 x 128 tiles): full 128-byte lines per row (16-byte accesses, 8 lanes per row: both fragments of a wave through one [16][64] patch) — 1: the plain epilogue, 2: the BatchNorm-backward epilogue too; 0 = 64 bytes per row (rounds 3-5).  Same outputs bit for bit; stamped epilogue 8,785 -> 7,018 cycles per tile (plain), 28,473 -> 23,176 (BatchNorm backward, whose K loop pays 7 % for 32 more live registers); same-box steps: LRW 4.991 / 4.959 / 4.960 ms, LRS 23.14 / 23.20 / 23.03 at 0 / 1 / 2
 };
-static const char* const g_tune_names[SVSR_TUNE_N] = {"igemm_tile", "igemm_m128", "wg_blocks", "w3_blocks", "ln_rpb", "stem_lds_fwd", "stem_lds_bwd", "igemm_lds_pad", "igemm_bn64_below", "wg_short_k", "igemm_ksplit", "epi_batched", "stem_wg_pipe", "stem_fwd_dma", "igemm_lin_bn64", "p8", "p8_grid", "p8_min_items", "p8_ph", "p8_stagger", "wg_imgmajor", "p8_bn64", "igemm_ns64", "wg_units", "wg_unit_max", "wg_unit_min", "igemm_ksplit128", "wg_xcd", "w3_waves", "reduce_cus", "w3_dense", "p8_wide"};
+static const char* const g_tune_names[SVSR_TUNE_N] = {"igemm_tile", "igemm_m128", "wg_blocks", "w3_blocks", "ln_rpb", "igemm_bn64_below", "wg_short_k", "igemm_ksplit", "igemm_lin_bn64", "p8", "p8_grid", "p8_min_items", "p8_stagger", "wg_imgmajor", "wg_units", "wg_unit_max", "wg_unit_min", "igemm_ksplit128", "w3_waves", "reduce_cus", "w3_dense"};
 
 int svsr_tune_get(int id) { return (id >= 0 && id < SVSR_TUNE_N) ? g_tune[id] : 0; }
 

@@ -865,7 +865,7 @@ int svsr_stem_conv_fwd_stat_rows(int B, int T, int H, int W) { return (B < 1 || 
 
 /* bytes of the workspace the DMA-fed forward path wants (0: this shape takes the direct path and needs none) */
 int64_t svsr_stem_conv_fwd_ws_bytes(int B, int T, int H, int W) {
-    if ((H & 1) || (W & 7) || H < 8 || W < 8 || B < 1 || T < 1 || !svsr_tune_get(SVSR_TUNE_STEM_FWD_DMA)) return 0;
+    if ((H & 1) || (W & 7) || H < 8 || W < 8 || B < 1 || T < 1) return 0;
     return ((int64_t)B * T * H * (W + 8) + (int64_t)STEM_W_CHUNKS * 8) * 2;
 }
 
@@ -949,7 +949,7 @@ int svsr_stem_conv_wgrad(const float* vid, const void* dy, float* dw, int B, int
         lds_set[use_tr ? 1 : 0] = lds;
     }
     // the register-pipelined kernel covers the shapes whose tile pieces fit its fixed prefetch registers (88 x 88 clips do)
-    const bool pipe = use_tr && (W & 3) == 0 && a.PW / 2 <= 32 && SW_RB * a.WoP * 8 <= 8 * 256 && svsr_tune_get(SVSR_TUNE_STEM_WG_PIPE);
+    const bool pipe = use_tr && (W & 3) == 0 && a.PW / 2 <= 32 && SW_RB * a.WoP * 8 <= 8 * 256;
     if (pipe) {
         static size_t lds_pipe = 0;
         if (lds > lds_pipe) {

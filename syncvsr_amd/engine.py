@@ -28,9 +28,6 @@ from .shape_cache import ShapeLRU, shape_key
 
 import os as _os
 
-ZERO_GRADS_EARLY = _os.environ.get("SVSR_ZERO_GRADS_EARLY", "1") != "0"       # gradient buffer zeroed at the start of the step, on the side stream (TrainStep._zero_grads_early)
-SPLIT_OPTIMIZER = _os.environ.get("SVSR_SPLIT_OPTIMIZER", "1") != "0"      # AdamW of everything behind the front-end on the side stream, beside the next forward
-
 _ROCTX = _os.environ.get("SVSR_ROCTX", "0") == "1"
 
 
@@ -159,11 +156,9 @@ class TrainStep:
         # data-gradient chain and fill its tails: LRW 8.06 -> 7.39 ms (trunk convs), LRS 31.9 -> 30.4 ms (trunk convs + the
         # 20-40 us linear GEMMs that fill about half the chip each).  Under HIP-graph replay the forked branches cost more than
         # they hide (LRW 7.85 -> 8.5 ms, LRS 33.2 ms), so a captured step keeps everything in line.
-        import os
-        graph_side = os.environ.get("SVSR_GRAPH_SIDE", "0") == "1"
-        model._side.enabled = (not use_graph or graph_side) and os.environ.get("SVSR_SIDE_TRUNK", "1") != "0"
+        model._side.enabled = not use_graph and _os.environ.get("SVSR_SIDE_TRUNK", "1") != "0"
         if not self.is_lrw:
-            model._side.enabled_small = (not use_graph or graph_side) and os.environ.get("SVSR_SIDE_ENCODER", "1") != "0"
+            model._side.enabled_small = not use_graph and _os.environ.get("SVSR_SIDE_ENCODER", "1") != "0"
         self._graph: Optional[torch.cuda.CUDAGraph] = None
         self._static: Optional[list[torch.Tensor]] = None
         self._out: Optional[dict[str, torch.Tensor]] = None
@@ -195,8 +190,6 @@ class TrainStep:
         if self.dp is not None:
             self.dp.finish()
         self._optimizer(st)
-        if self.use_graph:
-            model._side.join()       # (SVSR_GRAPH_SIDE=1: work forked onto the side stream must be joined before the capture ends)
         if trace:
             torch.cuda.nvtx.range_pop()
         if self.is_lrw:
@@ -214,11 +207,10 @@ class TrainStep:
         st.__dict__.pop("sumsq_tail_done", None)
         # no collective between the backward and the clip: the model may sum the squares of every gradient but the last while that one is
         # computed (set per step: two TrainSteps may drive one model, each with its own optimiser state)
-        model._early_sumsq = self.opt_state if (self.dp is None and ops.EARLY_SUMSQ) else None
-        if getattr(model, "accumulate_grads", False) or not ZERO_GRADS_EARLY:
+        model._early_sumsq = self.opt_state if self.dp is None else None
+        if getattr(model, "accumulate_grads", False):
             return
         model._side.run(lambda: ops.memset(st.grad, 0))
-        model._side.flush()
         st.grad_clean = True
 
     def _optimizer(self, st) -> None:
@@ -239,7 +231,7 @@ class TrainStep:
             ops.grad_sumsq(st.grad, self.opt_state)
         side = model._side
         hp = (self.lr, self.betas, self.eps, self.weight_decay, self.max_norm, self.warmup, self.total_steps, self.opt_state)
-        if not (SPLIT_OPTIMIZER and side.enabled and st.front_end < st.decay_end):
+        if not (side.enabled and st.front_end < st.decay_end):
             ops.adamw_step(st.flat, st.grad, self.m, self.v, st.w16, st.decay_end, *hp)
             ops.transpose_shadows(st.flat, st.w16, st.w16t, st.table, st.n_entries)
         else:
@@ -249,7 +241,6 @@ class TrainStep:
             nf = st.n_entries_front
             side.run(lambda: (ops.adamw_range(*bufs, st.front_end, st.decay_end, st.decay_end, *hp, advance=True),
                               ops.transpose_shadows_range(st.w16, st.w16t, st.table, nf, st.n_entries - nf)))
-            side.flush()
             ops.transpose_shadows_range(st.w16, st.w16t, st.table, 0, nf)
         st.shadow_fresh = True
         st.generation += 1

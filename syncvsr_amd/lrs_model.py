@@ -13,7 +13,6 @@ written tape, and a single autograd node for the whole model; every computation 
 from __future__ import annotations
 
 import math
-import os
 from typing import Any, Optional
 
 import torch
@@ -462,12 +461,6 @@ def _lin_bwd(model, st: _ParamStore, name: str, x, dy, rows: int, K: int, N: int
     return ops.linear_dgrad(dy, st.t16(tkey or f"{name}.weight"), rows=rows, N=N, K=K, dy_pitch=dy_pitch, addend=addend, out=out, drop=drop)
 
 
-WG_GROUP_DECODER = os.environ.get("SVSR_WG_GROUP_DECODER", "1") != "0"
-FFN_DGRAD_FUSED = os.environ.get("SVSR_LRS_FFN_DGRAD_FUSED", "1") != "0"      # _ffn_bwd: relu' + bias-gradient partials in the epilogue of w_2's data gradient
-PE_AHEAD = os.environ.get("SVSR_LRS_PE_AHEAD", "1") != "0"             # _encoder_fwd: every layer's linear_pos(pos_emb) + its transposed copy on the side stream, under the front-end
-TAILS_ON_SIDE = os.environ.get("SVSR_LRS_TAILS_SIDE", "1") != "0"      # _encoder_layer_bwd: parameter-gradient tails of the layer on the side stream
-
-
 def _flush_wg_group(model) -> None:
     """The weight gradients a decoder layer's backward collected, as ONE launch over a device table of problems (ops.linear_wgrad_group, the
     launch the word-level encoder uses): at ~800 target rows each of the layer's eight contractions is a 13-chunk K loop — 22 us of latency
@@ -491,7 +484,7 @@ def _ln_bwd(model, st: _ParamStore, dy, x, name: str, m, r, addend=None, branch=
     result is then a _WithBranch that _branch_grad recognises."""
     # (the gamma / beta reduction is postponed to the side stream: model._defer_list, flushed by _ready at the end of the layer)
     dl = _defer_list(model)
-    fuse = branch is not None and (branch[0] != 1.0 or branch[1] is not None) and ops.LN_BRANCH_FUSED and dl is not None
+    fuse = branch is not None and (branch[0] != 1.0 or branch[1] is not None) and dl is not None
     out = ops.add_ln_bwd(dy, x, None, st.p32(f"{name}.weight"), m, r, st.g32(f"{name}.weight"), st.g32(f"{name}.bias"), addend=addend,
                          defer=dl, branch=branch if fuse else None)
     if fuse:
@@ -522,7 +515,7 @@ def _ffn_bwd(model, st, t: dict, dy, p: str, R: int, D: int, U: int, alpha: floa
     """x' = x + alpha * dropout(FFN(LN(x))); dy = grad of x' -> grad of x.  branch: (alpha, drop) of the branch in front (see _ln_bwd)."""
     dys = _branch_grad(dy, alpha, t["do"])
     gs = 1.0 / (1.0 - t["dh"][2]) if t["dh"] is not None else 1.0           # dropped hidden units are the zeros of the saved h
-    if FFN_DGRAD_FUSED and U % 64 == 0 and model.use_tr:
+    if U % 64 == 0 and model.use_tr:
         # (round 6) relu' / the dropout mask and the bias gradient's partial rows in the epilogue of w_2's data gradient: one launch fewer
         # per feed-forward block in the main stream's chain, two passes over [R, U] fewer
         _lin_bwd(model, st, f"{p}.w_2", t["h"], dys, R, U, D, need_dx=False)
@@ -602,7 +595,7 @@ def _encoder_layer_bwd(model: E2E, st: _ParamStore, tape: dict, i: int, dxo, pos
     # (round 6) the two parameter-gradient tails of this layer — the depthwise convolution's partial-row sum and the position-table pass of
     # the attention backward — feed nothing but gradients of parameters: with the weight gradients on the side stream they go there too
     # (24 launches fewer in the main stream's chain per layer pair; same launches, same bits)
-    later = model._side.enabled and TAILS_ON_SIDE
+    later = model._side.enabled
     du = ops.glu_dwconv_bwd(dc, tc["u"], st.p32(f"{cm}.depthwise_conv.weight"), st.g32(f"{cm}.depthwise_conv.weight"),
                             st.g32(f"{cm}.depthwise_conv.bias"), B, T, D, K, reduce_later=later)
     if later:
@@ -687,7 +680,7 @@ def _decoder_bwd(model: E2E, st: _ParamStore, tape: dict, tg: LrsTargets, dpred,
     for i in reversed(range(model.dlayers)):
         p = f"decoder.decoders.{i}"
         t = tape[p]
-        model._wg_group = [] if WG_GROUP_DECODER else None
+        model._wg_group = []
         dx2 = _ffn_bwd(model, st, t["ff"], dx, f"{p}.feed_forward", R, D, U, 1.0, f"{p}.norm3", branch=(1.0, t["src"]["dao"]))
         ts = t["src"]
         dctx2 = _lin_bwd(model, st, f"{p}.src_attn.linear_out", ts["ctx"], _branch_grad(dx2, 1.0, ts["dao"]), R, D, D)
@@ -724,7 +717,7 @@ def _encoder_fwd(model: E2E, st: _ParamStore, tape: dict, x, ilen, training: boo
     dpos = model._d("enc.embed.pos")
     if dpos is not None:
         pos16 = ops.scale_bf16(pos16, 1.0, drop=dpos)                                      # dropout(pos_emb), embedding.py:217
-    if training and model._side.enabled and PE_AHEAD:
+    if training and model._side.enabled:
         # (round 6) every layer's projection of the position table — linear_pos(pos_emb), attention.py:238-250 — and its transposed copy for the
         # attention backward depend on the step's weights and on pos_emb alone: all of them are made on the side stream while the front-end
         # runs (behind the previous step's optimiser there; the join below is the one that existed), 24 launches off the main chain
@@ -737,7 +730,6 @@ def _encoder_fwd(model: E2E, st: _ParamStore, tape: dict, x, ilen, training: boo
                 pre[i] = (pe, ops.mha_pe_transpose(pe, model.aheads, T))
 
         model._side.run(ahead, pos16)
-        model._side.flush()
     feats = _frontend_forward(model, st, tape, videos, training)          # [R, 512] bf16
     model._side.join()                # the previous step's optimiser may still be updating everything behind the front-end on the side stream (engine.TrainStep)
     dex = model._d("enc.embed.x")
@@ -786,10 +778,7 @@ class _LrsFunction(torch.autograd.Function):
 
             # the CTC branch (its lattice is T sequential steps: ~300 us of latency, not of work) runs on the side stream next to the
             # attention decoder's forward; both only read the encoder output.  Joined below, before anything uses its results.
-            if ops.CTC_SIDE:
-                model._side.run(ctc_branch, h, small=True)
-            else:
-                ctc_branch()
+            model._side.run(ctc_branch, h, small=True)
         else:                                      # `loss_ctc = 0` (e2e_asr_transformer.py:205-208)
             dctc = h_ctc = logits_c = ctc_state = None
             loss_c = ops.zeros((), torch.float32, x.device)
@@ -806,8 +795,7 @@ class _LrsFunction(torch.autograd.Function):
         if model.length_norm:
             loss_att = loss_att / counts[1]
         if model.mtlalpha > 0.0:
-            if ops.CTC_SIDE:
-                model._side.join()
+            model._side.join()
             h_ctc, logits_c, loss_c, ctc_state = box["h_ctc"], box["logits_c"], box["loss_c"], box["ctc_state"]
         model._last = dict(feats=feats, enc_out=h, pred=pred, logits_audio=logits_a, logits_ctc=logits_c)
         if need_grad:

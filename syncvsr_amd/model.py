@@ -11,7 +11,6 @@ so ``loss_total.backward()`` works as in the reference loops while no per-op aut
 from __future__ import annotations
 
 import math
-import os
 from typing import Any, Optional
 
 import torch
@@ -32,50 +31,36 @@ class _SideStream:
     def __init__(self) -> None:
         self.stream: Optional[torch.cuda.Stream] = None
         self.keep: list = []
-        self.pending: list = []
-        self._flushing = False
+        self._issuing = False
         self.enabled = False     # set by engine.TrainStep
         # linear-layer weight gradients: neutral for the LRW encoder, a gain for the LRS linears (engine.TrainStep turns it on there)
         self.enabled_small = False
-        # launches are handed to the side stream in groups: every hand-over is one cross-stream dependency (an event record +
-        # wait: host time in eager mode, a cross-branch edge in a captured graph), and a weight gradient is in no hurry
-        self.group = int(os.environ.get("SVSR_SIDE_GROUP", "1"))     # measured (LRW, B = 32): eager 6.62 / 6.72 / 7.72 ms at 1 / 4 / all; graph 7.56 / 7.20 / 7.41
 
     def run(self, fn, *keep, small: bool = False) -> None:
-        """fn must not depend on variables that are rebound before flush() (bind them as arguments); the tensors it reads
-        must not be written in place before join()."""
+        """Issues fn on the side stream, behind what the main stream has issued so far: one cross-stream wait per call (an event record
+        + wait: host time in eager mode; handing several functions over at once measured slower).  The tensors fn reads must not be
+        written in place before join().  fn's launches go to the side stream through ops.STREAM_OVERRIDE, which is much cheaper on the
+        host than entering a torch.cuda.stream() context per launch, but its allocations still come from the main stream's pool: no
+        tensor allocated inside fn may be freed before join() (keep it in `keep`, the tape or a result box)."""
         if not (self.enabled or (small and self.enabled_small)):
             fn()
             return
-        if self._flushing:       # called from inside a function that is being issued on the side stream: issue it there, now, in order
-            self.keep.extend(keep)
-            fn()
-            return
-        self.pending.append(fn)
         self.keep.extend(keep)
-        if len(self.pending) >= self.group:
-            self.flush()
-
-    def flush(self) -> None:
-        if not self.pending or self._flushing:
+        if self._issuing:        # called from inside a function that is being issued on the side stream: issue it there, now, in order
+            fn()
             return
         if self.stream is None:
             self.stream = torch.cuda.Stream()
         ops.stream_wait(self.stream, torch.cuda.current_stream())
-        # launches go to the side stream through ops.STREAM_OVERRIDE (they allocate nothing on the device), which is
-        # much cheaper on the host than entering a torch.cuda.stream() context per weight-gradient launch
         ops.STREAM_OVERRIDE = self.stream.cuda_stream
-        self._flushing = True
+        self._issuing = True
         try:
-            for fn in self.pending:
-                fn()
+            fn()
         finally:
-            self._flushing = False
+            self._issuing = False
             ops.STREAM_OVERRIDE = None
-            self.pending.clear()
 
     def join(self) -> None:
-        self.flush()
         if self.stream is not None and (self.enabled or self.enabled_small):
             ops.stream_wait(torch.cuda.current_stream(), self.stream)
         self.keep.clear()
@@ -384,10 +369,9 @@ class TransformerLightningModule(nn.Module):
                                                                   word_mask if self.use_wb else None)
         finally:
             self._metrics_on_side = False
-        if self._side.enabled and METRICS_ON_SIDE:
+        if self._side.enabled:
             box: dict = {}
             self._side.run(lambda: box.__setitem__("t", ops.lincomb2(loss_category, loss_audio, self.lambda_audio)), loss_category, loss_audio)
-            self._side.flush()
             loss_total = box["t"]
         else:
             loss_total = ops.lincomb2(loss_category, loss_audio, self.lambda_audio)
@@ -616,21 +600,20 @@ def _frontend_forward(model, st: "_ParamStore", tape: dict, videos: torch.Tensor
     sc, sb, act = model.stem_name + ".0", model.stem_name + ".1", model.trunk_act
     c, stats = ops.stem_conv_fwd(videos, st.p32(f"{sc}.weight"), want_stats=training)
     mean, rstd = _bn_stats(st, sb, training, c.numel() // 64, stats)
-    if training and ops.STEM_KEEP_WINNERS:
+    if training:          # the convolution output at every pooling window's arg-max, for the backward
         x, amax, xwin = ops.stem_bn_gelu_pool_fwd(c, mean, rstd, st.p32(f"{sb}.weight"), st.p32(f"{sb}.bias"), model.stem_act, want_win=True)
     else:
         (x, amax), xwin = ops.stem_bn_gelu_pool_fwd(c, mean, rstd, st.p32(f"{sb}.weight"), st.p32(f"{sb}.bias"), model.stem_act), None
     tape["stem"] = dict(videos=videos, c=c, amax=amax, xwin=xwin, mean=mean, rstd=rstd, pooled_shape=tuple(x.shape))
     for prefix, inp, planes, stride, down in _trunk_blocks(model):
         xin = x
-        if down and training and model._side.enabled and DOWN_ON_SIDE:
+        if down and training and model._side.enabled:
             # (round 6) the downsample branch (1x1 convolution, its statistics and apply pass) meets the main branch only at the residual sum: on the
             # side stream beside conv1 / bn1 (3 blocks x 3 launches off the main chain: -0.035 ms LRW same box, LRS unchanged; the backward
             # twin measured SLOWER — its join waits for the weight gradients queued on that stream — and is not here)
             box: dict = {}
             model._side.run(lambda xin=xin, prefix=prefix, stride=stride: box.__setitem__(
                 "idt", _conv_bn(st, tape, xin, f"{prefix}.downsample.0", f"{prefix}.downsample.1", 1, stride, 0, training, None, 0)), xin)
-            model._side.flush()
             o1 = _conv_bn(st, tape, xin, f"{prefix}.conv1", f"{prefix}.bn1", 3, stride, 1, training, None, act)
             model._side.join()
             idt = box["idt"]
@@ -726,7 +709,6 @@ def _frontend_backward(model, st: "_ParamStore", tape: dict, dfeats: torch.Tenso
         if early is not None and st.sumsq_head:
             # every gradient but the stem convolution's is final: their sum of squares (the global-norm clip's) runs beside that last pass
             model._side.run(lambda: ops.grad_sumsq_parts(st.grad, st.sumsq_head, st.numel - st.sumsq_head, early, 0, ops.SUMSQ_PARTS - 1))
-            model._side.flush()
             st.sumsq_tail_done = True
         ops.stem_bwd_wgrad(ts["videos"], dconv, ts["amax"], ts["c"], ts["mean"], ts["rstd"], ws["coef"], st.g32(f"{sc}.weight"))
     else:
@@ -759,15 +741,6 @@ def _lin_wgrad(model, x, dy, gw, gb, rows: int, K: int, N: int, x_pitch: int, dy
     model._side.run(lambda: ops.linear_wgrad(x, dy, gw, rows=rows, K=K, N=N, x_pitch=x_pitch, dy_pitch=dy_pitch, db=gb), x, dy, small=True)
 
 
-HEADS_CONCURRENT = os.environ.get("SVSR_HEADS_CONCURRENT", "1") != "0"      # train_step_direct: the word head (forward and backward) on the side stream beside the audio head
-DOWN_ON_SIDE = os.environ.get("SVSR_DOWN_ON_SIDE", "1") != "0"      # _frontend_forward: a block's downsample branch (1x1 convolution + its BatchNorm) on the side stream beside conv1 / bn1
-METRICS_ON_SIDE = os.environ.get("SVSR_METRICS_ON_SIDE", "1") != "0"      # train_step_direct: accuracy and loss_total (read by the caller only) on the side stream
-DEFER_REDUCTIONS = os.environ.get("SVSR_DEFER_REDUCTIONS", "1") != "0"     # encoder backward: parameter-gradient reductions on the side stream
-
-
-WG_GROUP_LAYERS = int(os.environ.get("SVSR_WG_GROUP_LAYERS", "1"))      # encoder layers per grouped weight-gradient launch (0: one launch for the whole encoder)
-
-
 def _flush_lin_wgrads(model) -> None:
     """The collected linear weight gradients of this backward pass as one launch (ops.linear_wgrad_group), on the side stream when
     the trunk's weight gradients go there: nothing downstream reads them before the optimiser."""
@@ -783,7 +756,7 @@ def _flush_lin_wgrads(model) -> None:
 
 def _defer_list(model) -> Optional[list]:
     """The list ops.add_ln_bwd / ops.bias_act_bwd append their postponed reductions to (None: reduce in line)."""
-    if not DEFER_REDUCTIONS or not (model._side.enabled or model._side.enabled_small):
+    if not (model._side.enabled or model._side.enabled_small):
         return None
     d = model.__dict__.get("_deferred")
     if d is None:
@@ -804,7 +777,6 @@ def _ready(model, st: "_ParamStore", name: Optional[str]) -> None:
     region is final (backward walks the flat buffer from its end to its start); None = all gradients final."""
     _flush_deferred(model)                    # postponed parameter-gradient reductions: to the side stream, once per layer
     if model.grad_ready_hook is not None:     # (the reducer's comm stream waits for the side stream itself: engine.GradReducer._reduce)
-        model._side.flush()
         hook, lo = model.grad_ready_hook, (0 if name is None else st.offsets[name][0])
         ops.host_callback(lambda: hook(lo))   # a host-side step (collective): a segment boundary of a recorded step list
 
@@ -930,7 +902,7 @@ def _encoder_layers_backward_fused(model: TransformerLightningModule, st: _Param
         _flush_deferred(model)
         if getattr(model, "_wg_group", None) is None:
             _ready(model, st, f"{p}.attention.self.query.weight")
-        elif WG_GROUP_LAYERS > 0 and (Lc - i) % WG_GROUP_LAYERS == 0 and i > 0:
+        elif i > 0:
             _flush_lin_wgrads(model)
             model._wg_group = []
             _ready(model, st, f"{p}.attention.self.query.weight")
@@ -978,7 +950,7 @@ def _encoder_backward(model: TransformerLightningModule, st: _ParamStore, tape: 
         _flush_deferred(model)
         if getattr(model, "_wg_group", None) is None:
             _ready(model, st, f"{p}.attention.self.query.weight")
-        elif WG_GROUP_LAYERS > 0 and (model.layers - i) % WG_GROUP_LAYERS == 0 and i > 0:
+        elif i > 0:
             # the weight gradients collected so far as one launch on the side stream NOW: the encoder's backward is a chain of small
             # launches that leaves most of the chip idle, while a single launch at its end competes with the trunk's backward
             _flush_lin_wgrads(model)
@@ -1064,11 +1036,9 @@ def _xt_block_bwd(model, st: _ParamStore, tape: dict, dx: torch.Tensor, n: int, 
 
 def _xt_grouped(model, rec, n: int, fn, inp: torch.Tensor) -> torch.Tensor:
     """Replayable layer drop (rec = ops.layer_groups()): block n's launches as op group n of the recorded list, then the pass-through
-    copy that every replay skipping n issues instead (the block's input, whole padded rows, into its output buffer).  The side stream's
-    pending launches are handed over inside the group, so none of them is issued outside it."""
+    copy that every replay skipping n issues instead (the block's input, whole padded rows, into its output buffer)."""
     with rec.group(n):
         out = fn()
-        model._side.flush()
     rec.passthrough(out, inp, n)
     return out
 
@@ -1152,8 +1122,8 @@ class _LrwFunction(torch.autograd.Function):
         lab_prob = None if hard else labels.float().contiguous()
         # (round 6) inside TrainStep the word head (classifier, its loss, the metric — and in the backward its loss gradient and data gradient) is a
         # branch of its own between the two encoder launches, of 1-8 workgroups per launch: it runs on the side stream beside the audio head
-        side_heads = bool(getattr(model, "_metrics_on_side", False) and model._side.enabled and HEADS_CONCURRENT and need_grad
-                          and ops.WGRAD_GROUP and model.encoder_type == "huggingface")       # (the heads' weight gradients then follow on the side stream too)
+        side_heads = bool(getattr(model, "_metrics_on_side", False) and model._side.enabled and need_grad
+                          and model.encoder_type == "huggingface")       # (the heads' weight gradients then follow on the side stream too)
         hb: dict = {}
 
         def word_head():
@@ -1165,7 +1135,6 @@ class _LrwFunction(torch.autograd.Function):
 
         if side_heads:
             model._side.run(word_head, h)
-            model._side.flush()
         else:
             word_head()
         logits_c, loss_c, lse_c = hb["logits_c"], hb["loss_c"], hb["lse_c"]
@@ -1184,12 +1153,11 @@ class _LrwFunction(torch.autograd.Function):
             loss_a, lse_a = ops.ce_fwd(logits_a, V, tok, None, B * T * A * G, V, 0.0)
         if side_heads:
             acc = hb["acc"]
-        elif getattr(model, "_metrics_on_side", False) and model._side.enabled and METRICS_ON_SIDE:
+        elif getattr(model, "_metrics_on_side", False) and model._side.enabled:
             # (round 6) inside TrainStep the metric is read when the step is over: its two launches leave the main stream's chain (the
             # side stream is joined at the end of the backward)
             box: dict = {}
             model._side.run(lambda: box.__setitem__("acc", ops.topk_acc(logits_c, lab_idx, lab_prob)), logits_c)
-            model._side.flush()
             acc = box["acc"]
         else:
             acc = ops.topk_acc(logits_c, lab_idx, lab_prob)
@@ -1230,7 +1198,6 @@ class _LrwFunction(torch.autograd.Function):
 
         if side_heads:
             model._side.run(word_head_bwd, dlc, dh, g_cat)
-            model._side.flush()
         else:
             word_head_bwd()
         dla = torch.empty((B * T, NA), dtype=BF16, device=dev)
@@ -1240,7 +1207,7 @@ class _LrwFunction(torch.autograd.Function):
         else:
             ops.ce_bwd(th["logits_a"], V, th["tok"], None, B * T * A * G, V, 0.0, th["lse_a"], g_audio, dla, V)
         h = th["h"]
-        grouped = ops.WGRAD_GROUP and model.encoder_type == "huggingface"
+        grouped = model.encoder_type == "huggingface"
         model._wg_group = [] if grouped else None
         heads = (dict(x=h, dy=dla, dw=st.g32("audio_projection.weight"), rows=B * T, K=D, N=NA, x_pitch=D, dy_pitch=NA, seq=(S, 1, T), db=st.g32("audio_projection.bias")),
                  dict(x=h, dy=dlc, dw=st.g32("category_classifier.weight"), rows=B, K=D, N=C, x_pitch=D, dy_pitch=Cp, seq=(S, 0, 1), db=st.g32("category_classifier.bias")))

@@ -130,37 +130,13 @@ def reduction_plan_params() -> list[int]:
 def tune(key: str, value: int) -> None:
     """Result-preserving tuning knob of the library (svsr_tune); invalidates cached plans.  `bn_bwd_fused` is a host-side choice
     (which launches the trunk backward issues), kept in this module."""
-    if key == "transpose_from_bf16":
-        global TRANSPOSE_FROM_BF16
-        TRANSPOSE_FROM_BF16 = bool(value)
-        return
     if key == "bn_bwd_fused":
         global BN_BWD_FUSED
         BN_BWD_FUSED = bool(value)
         return
-    if key == "stem_keep_winners":
-        global STEM_KEEP_WINNERS
-        STEM_KEEP_WINNERS = bool(value)
-        return
-    if key == "ln_branch_fused":
-        global LN_BRANCH_FUSED
-        LN_BRANCH_FUSED = bool(value)
-        return
     if key == "colsum_multi":
         global COLSUM_MULTI
         COLSUM_MULTI = bool(value)
-        return
-    if key == "early_sumsq":
-        global EARLY_SUMSQ
-        EARLY_SUMSQ = bool(value)
-        return
-    if key == "stem_bwd_fused":
-        global STEM_BWD_FUSED
-        STEM_BWD_FUSED = bool(value)
-        return
-    if key == "ctc_side":
-        global CTC_SIDE
-        CTC_SIDE = bool(value)
         return
     rc = _lib.load().svsr_tune(key.encode(), int(value))
     if rc != 0:
@@ -600,9 +576,6 @@ class _WgradProblem(ctypes.Structure):
                 ("Co", ctypes.c_int), ("out_pix", ctypes.c_int), ("out_pitch", ctypes.c_int), ("wt_taps", ctypes.c_int)]
 
 
-WGRAD_GROUP = True      # the encoder's / heads' linear weight gradients of a backward pass in ONE launch (False: one launch each)
-
-
 _WG_TABLES: dict = {}
 
 
@@ -631,7 +604,7 @@ def linear_wgrad_group(problems: Sequence[dict]) -> None:
         else:
             S, s0, n = seq
             plan, geo = wgrad_rows_plan(rows // n, n, s0, 0, K, N, db is not None), (rows // n, S, n)
-        if not (WGRAD_GROUP and plan.bc == 64 and int(plan.meta[1]) == 3 and plan.splits == 1):
+        if not (plan.bc == 64 and int(plan.meta[1]) == 3 and plan.splits == 1):
             linear_wgrad(q["x"], q["dy"], q["dw"], rows=rows, K=K, N=N, x_pitch=q["x_pitch"], dy_pitch=q["dy_pitch"], seq=seq, db=db)
             continue
         grouped.append(_WgradProblem(_p(q["x"]), _p(q["dy"]), _p(q["dw"]), _p(db), plan.words.data_ptr(), ctypes.addressof(plan.meta),
@@ -734,7 +707,6 @@ def conv2d_dgrad(dy: torch.Tensor, w16t: torch.Tensor, k: int, stride: int, pad:
     return dx
 
 
-CTC_SIDE = True         # LRS: the CTC branch of the forward on the model's side stream, beside the attention decoder (tuning knob "ctc_side")
 BN_BWD_FUSED = True    # ReLU trunk: first pass of the BatchNorm backward inside the producing data-gradient launch (False: separate pass)
 
 
@@ -932,9 +904,6 @@ def stem_conv_wgrad(videos: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor, us
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_SWISH = 0, 1, 1, 2     # ReLU/GELU share code 1: ReLU in the BN passes, GELU in the stem pass
 
 
-STEM_KEEP_WINNERS = os.environ.get("SVSR_STEM_KEEP_WINNERS", "1") != "0"     # the stem's forward keeps the convolution output at every pooling window's arg-max for its backward
-
-
 def stem_bn_gelu_pool_fwd(x: torch.Tensor, mean, rstd, gamma, beta, act: int = ACT_GELU, want_win: bool = False):
     """-> (y, amax) or, with want_win, (y, amax, xwin): xwin = the convolution output at every window's arg-max, for
     stem_bn_gelu_pool_bwd(xwin=...) (reduce pass over pooled-size tensors, apply pass without activation derivatives)."""
@@ -961,12 +930,10 @@ def stem_bn_gelu_pool_bwd(dpool, amax, x, mean, rstd, gamma, beta, coef, dgamma,
     return dx if want_dx else gpool
 
 
-STEM_BWD_FUSED = True        # the stem's backward apply pass inside its weight-gradient pass (svsr_stem_bwd_wgrad) where the shape allows
-
-
 def stem_bwd_wgrad_ok(videos: torch.Tensor) -> bool:
+    """Whether the stem's backward apply pass can run inside its weight-gradient pass (svsr_stem_bwd_wgrad) at this shape."""
     B, _, T, H, W = videos.shape
-    return bool(STEM_BWD_FUSED and _lib.load().svsr_stem_bwd_wgrad_ok(B, T, H, W))
+    return bool(_lib.load().svsr_stem_bwd_wgrad_ok(B, T, H, W))
 
 
 def stem_bwd_wgrad(videos: torch.Tensor, gpool, amax, x, mean, rstd, coef, dw: torch.Tensor) -> None:
@@ -1080,9 +1047,6 @@ def run_deferred(fns) -> None:
             flush()
         batch.append(a)
     flush()
-
-
-LN_BRANCH_FUSED = True      # host-side knob "ln_branch_fused": a residual branch's gradient alpha * mask * dx as a second output of the LayerNorm backward in front of it (LRS layers); False: svsr_scale_bf16
 
 
 def add_ln_bwd(dy, a, r, gamma, mean, rstd, dgamma, dbeta, addend=None, out=None, defer: Optional[list] = None, branch=None):
@@ -1371,7 +1335,6 @@ def grad_sumsq(g: torch.Tensor, opt_state: torch.Tensor) -> None:
     _call("svsr_grad_sumsq", _p(g), g.numel(), _p(opt_state), _stream())
 
 
-EARLY_SUMSQ = True      # host-side knob "early_sumsq": the clip's sum of squares over everything but the stem weight on the side stream beside the stem's weight gradient
 SUMSQ_PARTS = 1024      # partial sums of squares in the optimiser's device state (loss_optim.hip OPT_PARTS)
 
 
@@ -1419,15 +1382,10 @@ def transpose_cast_multi(src, dst, table: torch.Tensor, n_entries: int) -> None:
     _call("svsr_transpose_cast_multi", _p(src), _p(dst), _p(table), n_entries, _stream())
 
 
-TRANSPOSE_FROM_BF16 = True      # tuning knob "transpose_from_bf16": refresh the transposed shadows from the bf16 shadow (half the bytes read)
-
-
 def transpose_shadows(flat, w16, dst, table: torch.Tensor, n_entries: int) -> None:
-    """Transposed bf16 shadows of the 2-D weights from the (fresh) bf16 shadow w16, or from the fp32 buffer: identical results."""
-    if TRANSPOSE_FROM_BF16:
-        _call("svsr_transpose_bf16_multi", _p(w16), _p(dst), _p(table), n_entries, _stream())
-    else:
-        transpose_cast_multi(flat, dst, table, n_entries)
+    """Transposed bf16 shadows of the 2-D weights, from the (fresh) bf16 shadow w16: the same bits as from the fp32 buffer `flat`, which
+    is not read (half the bytes)."""
+    _call("svsr_transpose_bf16_multi", _p(w16), _p(dst), _p(table), n_entries, _stream())
 
 
 # --------------------------------------------------------------------------------------------------
@@ -1435,9 +1393,6 @@ def transpose_shadows(flat, w16, dst, table: torch.Tensor, n_entries: int) -> No
 # --------------------------------------------------------------------------------------------------
 def probs_pitch(Lk: int) -> int:
     return (Lk + 7) // 8 * 8
-
-
-MHA_FLASH = os.environ.get("SVSR_MHA_FLASH", "1") != "0"     # sentence-level attention on the streamed-key kernels (mha_flash.h); False: the per-tile kernels
 
 
 class MhaLse:
@@ -1451,11 +1406,11 @@ class MhaLse:
 def mha_fwd(q, q_pitch: int, k, v, kv_pitch: int, *, B: int, H: int, Lq: int, Lk: int, pe=None, bias_u=None, bias_v=None, klen=None,
             causal: bool = False, drop=None, flash: bool = False):
     """-> (ctx [B*Lq, H*64] bf16, probs [B*H, Lq, ldp] bf16).  q/k/v are views into (fused) projection outputs.
-    flash=True (and MHA_FLASH): svsr_mha_flash_fwd — the second result is an MhaLse record (no probabilities are stored); hand it to mha_bwd."""
+    flash=True: svsr_mha_flash_fwd — the second result is an MhaLse record (no probabilities are stored); hand it to mha_bwd."""
     ldp = probs_pitch(Lk)
     ctx = torch.empty((B * Lq, H * 64), dtype=BF16, device=q.device)
     flops = 2.0 * B * H * Lq * Lk * 64 * (3 if pe is not None else 2)
-    if flash and MHA_FLASH:
+    if flash:
         lse = torch.empty((B * H, Lq), dtype=torch.float32, device=q.device)
         _call("svsr_mha_flash_fwd", _p(q), q_pitch, _p(k), _p(v), kv_pitch, _p(pe), 0 if pe is None else pe.stride(0), _p(bias_u), _p(bias_v),
               _p(klen), int(causal), B, H, 64, Lq, Lk, ldp, 0.125, _p(ctx), H * 64, _p(lse), *_drop(drop), _stream(), label="k_mhaf_fwd", flops=flops)
