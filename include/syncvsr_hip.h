@@ -325,6 +325,27 @@ int svsr_linear_ce_ok(int R, int K, int G, int V);
 int svsr_linear_ce_fwd(const void* h, const void* w, const float* bias, const int64_t* tok, int R, int K, int G, int V, int seq_S, int seq_s0, int seq_T, float* loss, float* lse, float* row_loss, hipStream_t stream);
 int svsr_linear_ce_bwd(const void* h, const void* w, const float* bias, const int64_t* tok, int R, int K, int G, int V, int seq_S, int seq_s0, int seq_T, const float* lse, const float* gout, void* dlogits, hipStream_t stream);
 
+/* ---- the wav2vec2 audio tokeniser (w2v_codec.hip) ------------------------------------------------------------------------
+ * Replaces forward_audios of the `wav2vec2` codec (LRS e2e_asr_transformer.py:167-180, LRW lightning.py:121-131): HF Wav2Vec2FeatureEncoder
+ * (7 Conv1d of 512 channels, kernels 10,3,3,3,3,2,2, strides 5,2,2,2,2,2,2, exact GELU), feature_projection.layer_norm and the quantiser's
+ * weight_proj + argmax (eval) / argmax of logits + Gumbel noise (training).  Activations: channels-last bf16 rows [B][rows][512].
+ * svsr_w2v_conv0: layer 0 in fp32 over wave fp32 [B][L_in] followed by `pad` zeros per row: F0 = (L_in + pad - 10) / 5 + 1 frames into
+ *   out [B][out_rows][512] (out_rows >= F0).  mode 0 ("layer" models): + bias, LayerNorm(512; gamma, beta, eps), GELU.  mode 1 ("group"):
+ *   the pre-norm conv output (bias may be null) and, in stats (svsr_w2v_stats_floats(B, F0) floats), per 64-frame block the per-channel
+ *   sums / sums of squares (plain stores) that svsr_w2v_norm_gelu mode 1 reduces in a fixed order.
+ * svsr_w2v_norm_gelu: in place over the F valid rows of every clip of x [B][rows][512]: mode 0 GELU(LayerNorm(512)), mode 1 GELU(GroupNorm)
+ *   with the statistics of the clip's F0 = F frames (GroupNorm(512 groups): each channel over the whole time axis, padding included).
+ * Layers 1-6 are svsr_igemm_fwd over svsr_rows_plan(B, F_out, 0, 0, 512): a stride-2 kernel-k convolution reads frames 2t .. 2t+k-1, i.e.
+ *   the contiguous k*512 values of source row t when rows overlap with pitch 1024 (Ci = k*512, in_pitch = 1024, in_pix = rows / 2).
+ * svsr_w2v_quantize: feat bf16 [R][512] (R / F clips of F frames) -> LayerNorm(512) -> logits = . W^T + bias (W bf16 [640][512]) ->
+ *   tok int64 [R / F][keep][2] = (argmax of columns 0..319, 320 + argmax of columns 320..639) of frames t < keep, ties to the lowest index:
+ *   the cropped tokens[:, :T*A] of the LRS forward, contiguous, in the layout svsr_linear_ce_fwd / svsr_ce_fwd read.  seed != null: argmax of logits + g, g = -log(-log u),
+ *   u = (hash(*seed, site, r * 640 + column) + 0.5) 2^-32 (the dropout hash of csrc/common.h).  logits_out (fp32 [R][640], optional): the logits. */
+int64_t svsr_w2v_stats_floats(int B, int F0);
+int svsr_w2v_conv0(const float* wave, int B, int L_in, int pad, const float* w, const float* bias, const float* gamma, const float* beta, float eps, void* out, int out_rows, float* stats, int mode, hipStream_t stream);
+int svsr_w2v_norm_gelu(void* x, int B, int F, int rows, const float* gamma, const float* beta, float eps, float* stats, int F0, int mode, hipStream_t stream);
+int svsr_w2v_quantize(const void* feat, int R, int F, int keep, const float* gamma, const float* beta, float eps, const void* w, const float* bias, const unsigned* seed, unsigned site, int64_t* tok, float* logits_out, hipStream_t stream);
+
 /* top-1 / top-5 accuracy (lightning.py:177-183); out2 = {top1, top5}; rows2: [B][2] float workspace. */
 int svsr_topk_acc(const float* logits, const int64_t* labels, const float* soft_labels, int B, int C, float* out2, float* rows2, hipStream_t stream);
 

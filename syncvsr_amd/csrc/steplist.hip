@@ -76,7 +76,7 @@ const std::unordered_map<std::string, Entry>& registry() {
         SVSR_REG(svsr_glu_dwconv_fwd), SVSR_REG(svsr_glu_dwconv_bwd), SVSR_REG(svsr_glu_dwconv_bwd_parts), SVSR_REG(svsr_ctc_fwd), SVSR_REG(svsr_ctc_grad),
         SVSR_REG(svsr_ctc_prefix_score), SVSR_REG(svsr_lrs_targets), SVSR_REG(svsr_embed_pos_fwd), SVSR_REG(svsr_embed_pos_bwd), SVSR_REG(svsr_ls_loss_fwd),
         SVSR_REG(svsr_ls_loss_bwd), SVSR_REG(svsr_scale_bf16), SVSR_REG(svsr_word_add), SVSR_REG(svsr_lincomb2), SVSR_REG(svsr_igemm_wgrad_group), SVSR_REG(svsr_enc_fwd), SVSR_REG(svsr_enc_bwd), SVSR_REG(svsr_lincomb3_ratio), SVSR_REG(svsr_add_ln_bwd_partials), SVSR_REG(svsr_add_ln_bwd_branch), SVSR_REG(svsr_bias_act_bwd_partials),
-        SVSR_REG(svsr_memcpy_async),
+        SVSR_REG(svsr_memcpy_async), SVSR_REG(svsr_w2v_conv0), SVSR_REG(svsr_w2v_norm_gelu), SVSR_REG(svsr_w2v_quantize),
     };
     return r;
 }

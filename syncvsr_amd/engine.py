@@ -282,7 +282,8 @@ class TrainStep:
         if model._side.stream is None:
             model._side.stream = torch.cuda.Stream()
         model.direct_constants(static[0].device)
-        if getattr(model, "_drop_word", None) is None and (model.drop_p > 0.0 or model.attn_drop_p > 0.0 or getattr(model, "emb_drop_p", 0.0) > 0.0):
+        if getattr(model, "_drop_word", None) is None and (model.drop_p > 0.0 or model.attn_drop_p > 0.0 or getattr(model, "emb_drop_p", 0.0) > 0.0
+                                                           or getattr(model, "_codec_samples", lambda: False)()):
             model._advance_dropout(static[0].device)      # creates the seed word outside the recorded region ...
             ops.word_add(model._drop_word, -1)             # ... and leaves its value where the first forward expects it
         rec = ops.StepRecorder()

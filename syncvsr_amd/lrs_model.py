@@ -4,8 +4,9 @@ Same constructor ``E2E(odim, args, ignore_id=-1)`` reading the ``model.visual_ba
 ``forward(x, lengths, audios, label) -> (loss, loss_ctc, loss_att, loss_audio, acc)`` and the same state-dict names
 (``encoder.frontend.{frontend3D,trunk}``, ``encoder.embed.0``, ``encoder.encoders.N.{self_attn,feed_forward,feed_forward_macaron,
 conv_module,norm_*}``, ``encoder.after_norm``, ``decoder.*``, ``ctc.ctc_lo``, ``audio_classifier``).  Deviations, both from
-SURVEY §8(b): the ``audios`` slot takes pre-computed audio tokens int64 [B, >=A*T, G] (the frozen wav2vec quantiser's weights are
-not available offline), and ``acc`` is a 0-d device tensor instead of a Python float (no host sync inside the step).
+SURVEY §8(b): the ``audios`` slot takes pre-computed audio tokens int64 [B, >=A*T, G] — or, after ``attach_audio_codec`` (the wav2vec2
+tokeniser of ``audio_codec.py``), float waveforms that are tokenised inside the step — and ``acc`` is a 0-d device tensor instead of a
+Python float (no host sync inside the step).
 
 As in ``model.py`` this file is orchestration only: one flat fp32 parameter buffer (+ gradient buffer + bf16 shadows), a hand
 written tape, and a single autograd node for the whole model; every computation is a launch into libsyncvsr_hip.so.
@@ -278,6 +279,43 @@ class E2E(nn.Module):
         self._side.join()             # (a TrainStep may have left the tail of its optimiser step on the side stream)
         return super().state_dict(*args, **kwargs)
 
+    # ------------------------------------------------------------------------------------------------
+    # wav2vec2 audio tokeniser (e2e_asr_transformer.py:145-157,167-180)
+    def attach_audio_codec(self, codec, sample_in_training: bool = True) -> "E2E":
+        """Registers the frozen tokeniser (audio_codec.Wav2Vec2Codec) as `self.wav2vec`, the reference's attribute: state_dict() gains its
+        `wav2vec.*` buffers, and forward / prepare_batch / train_step_direct then take float waveforms [B, 1, L] or [B, L] in the `audios`
+        slot — 8000 zeros are appended to every row and the tokens are computed inside the step.  In training mode the tokens are
+        argmax(logits + Gumbel noise) (the reference's frozen quantiser runs its gumbel_softmax branch under Lightning's model.train()),
+        keyed by the dropout seed word; sample_in_training=False keeps the eval-mode argmax.  The codec holds buffers only: it stays out of
+        parameters(), the parameter store, the optimiser, clipping and the gradient / BatchNorm-statistics collectives."""
+        from .audio_codec import Wav2Vec2Codec
+
+        if not isinstance(codec, Wav2Vec2Codec):
+            raise TypeError("attach_audio_codec takes a syncvsr_amd.audio_codec.Wav2Vec2Codec")
+        if self.codec != "wav2vec2":
+            raise ValueError(f"this model was built for the {self.codec!r} codec (args.codec): the wav2vec2 tokeniser gives 640-way tokens, A = 2")
+        codec.to(_get(self, self._specs[0][0]).device)
+        self.wav2vec = codec
+        self.codec_sample_in_training = bool(sample_in_training)
+        return self
+
+    def _codec_samples(self) -> bool:
+        """The tokeniser of this training step draws Gumbel noise (and so needs the seed word to advance every step)."""
+        return self.training and self._modules.get("wav2vec") is not None and getattr(self, "codec_sample_in_training", False)
+
+    def _tokenize(self, audios: torch.Tensor, T: int) -> torch.Tensor:
+        """float waveforms -> int64 tokens [B, T*A, 2] (forward_audios + the crop tokens[:, :T*A]), on the device."""
+        from .audio_codec import LRS_PAD
+
+        if audios.device.type != "cuda":
+            raise RuntimeError("audio waveforms must be on the MI355X device: the tokeniser has no CPU path")
+        seed = None
+        if self._codec_samples():
+            if self._drop_word is None or self._drop_word.device != audios.device:
+                self._drop_word = torch.tensor([self.dropout_seed], dtype=torch.int32, device=audios.device)
+            seed = self._drop_word
+        return self._modules["wav2vec"](audios, pad=LRS_PAD, sample=seed is not None, seed_word=seed, keep=T * self.audio_alignment)
+
     def _advance_dropout(self, dev: torch.device) -> None:
         if self._drop_word is None or self._drop_word.device != dev:
             self._drop_word = torch.tensor([self.dropout_seed], dtype=torch.int32, device=dev)
@@ -375,6 +413,8 @@ class E2E(nn.Module):
         st = self.store()
         B, T = x.shape[:2]
         A = self.audio_alignment
+        if audios.is_floating_point() and self._modules.get("wav2vec") is not None:
+            audios = self._tokenize(audios, T)
         if audios.dtype != torch.int64 or audios.dim() != 3:
             raise ValueError("pass pre-computed audio tokens int64 [B, >= A*T, G] in the `audios` slot (SURVEY §8b)")
         if audios.size(1) < T * A:
@@ -398,13 +438,24 @@ class E2E(nn.Module):
         if x.dim() != 5 or x.size(2) != 1:
             raise ValueError("x must be [B, T, 1, H, W]")
         T, A = x.size(1), self.audio_alignment
-        if audios.dtype != torch.int64 or audios.dim() != 3 or audios.size(1) < T * A:
+        codec = self._modules.get("wav2vec")
+        if audios.is_floating_point() and codec is not None:       # waveforms: tokenised inside the step (train_step_direct)
+            from .audio_codec import LRS_PAD, frame_counts
+
+            wave = codec.as_rows(audios.to(x.device))
+            if frame_counts(wave.size(1) + LRS_PAD)[-1] < T * A:
+                raise ValueError(f"{wave.size(1)} audio samples (+ {LRS_PAD} zeros) give fewer than {T * A} audio frames")
+            if wave.device.type != "cuda":
+                raise RuntimeError("audio waveforms must be on the MI355X device: the tokeniser has no CPU path")
+            codec.packed(wave.device)                              # device forms of the frozen weights exist before a step is recorded
+            audios = wave
+        elif audios.dtype != torch.int64 or audios.dim() != 3 or audios.size(1) < T * A:
             raise ValueError(f"pass pre-computed audio tokens int64 [B, >= {T * A}, G] in the `audios` slot (SURVEY §8b)")
         tg = label if isinstance(label, LrsTargets) else self.prepare_targets(label.to(x.device))
         self._pos_table("rel", T, x.device)                 # position tables of this shape exist before a step is recorded
         self._pos_table("abs", tg.ys_in.size(1), x.device)
-        return (x.float().contiguous(), lengths.to(device=x.device, dtype=torch.int32).contiguous(), audios[:, : T * A].contiguous(),
-                tg.labels, tg.ys_in, tg.ys_out)
+        return (x.float().contiguous(), lengths.to(device=x.device, dtype=torch.int32).contiguous(),
+                audios if audios.is_floating_point() else audios[:, : T * A].contiguous(), tg.labels, tg.ys_in, tg.ys_out)
 
     def direct_constants(self, dev) -> None:
         """d loss / d {loss_ctc, loss_att, loss_audio} as device scalars (made once, outside any recorded region)."""
@@ -424,6 +475,8 @@ class E2E(nn.Module):
                 pass
 
         ctx = _Ctx()
+        if tokens.is_floating_point():                 # waveforms (prepare_batch with a codec attached): tokenised in the step
+            tokens = self._tokenize(tokens, x.size(1))
         tg = LrsTargets(labels, ys_in, ys_out)
         loss_ctc, loss_att, loss_audio, counts = _LrsFunction.forward(ctx, None, self, st, x, ilen, tokens, tg, True)
         loss, acc = ops.lincomb3_ratio(loss_ctc, self.mtlalpha, loss_att, 1.0 - self.mtlalpha, loss_audio, self.audio_weight, counts[0:1], counts[1:2])
@@ -711,7 +764,7 @@ def _encoder_fwd(model: E2E, st: _ParamStore, tape: dict, x, ilen, training: boo
     B, T = x.shape[:2]
     D, R = model.adim, B * T
     videos = x.view(B, 1, T, x.size(3), x.size(4))             # [B,T,1,H,W] and [B,1,T,H,W] are the same memory (C = 1)
-    if training and (model.drop_p > 0.0 or model.attn_drop_p > 0.0):
+    if training and (model.drop_p > 0.0 or model.attn_drop_p > 0.0 or model._codec_samples()):
         model._advance_dropout(x.device)
     pos16 = model._pos_table("rel", T, x.device)
     dpos = model._d("enc.embed.pos")

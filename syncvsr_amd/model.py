@@ -199,6 +199,35 @@ class TransformerLightningModule(nn.Module):
             batch = self.cutmix(*batch)
         return self(*batch)["loss_total"]
 
+    def attach_audio_codec(self, codec, sample_in_training: bool = True) -> "TransformerLightningModule":
+        """Registers the frozen wav2vec2 tokeniser (audio_codec.Wav2Vec2Codec) as `self.wav2vec` (lightning.py:58-67) for forward_audios;
+        its buffers join state_dict() under `wav2vec.*`.  forward / training_step still take pre-computed tokens."""
+        from .audio_codec import Wav2Vec2Codec
+
+        if not isinstance(codec, Wav2Vec2Codec):
+            raise TypeError("attach_audio_codec takes a syncvsr_amd.audio_codec.Wav2Vec2Codec")
+        if self.codec != "wav2vec2":
+            raise ValueError(f"this model was built for the {self.codec!r} codec (model.wav2vec.path): the wav2vec2 tokeniser gives 640-way tokens")
+        codec.to(_get(self, self._specs[0][0]).device)
+        self.wav2vec = codec
+        self.codec_sample_in_training = bool(sample_in_training)
+        return self
+
+    def forward_audios(self, audios: torch.Tensor) -> torch.Tensor:
+        """lightning.py:121-131 for the wav2vec2 codec: float waveforms [B, L] (or [B, 1, L]) -> int64 tokens [B, F, 2] (no padding appended).
+        In training mode (with sample_in_training) the tokens are argmax(logits + Gumbel noise) keyed by the current dropout seed word."""
+        codec = self._modules.get("wav2vec")
+        if codec is None:
+            raise ValueError("forward_audios needs a wav2vec2 tokeniser: call attach_audio_codec(Wav2Vec2Codec...) first")
+        if audios.device.type != "cuda":
+            raise RuntimeError("audio waveforms must be on the MI355X device: the tokeniser has no CPU path")
+        seed = None
+        if self.training and self.codec_sample_in_training:
+            if self._drop_word is None or self._drop_word.device != audios.device:
+                self._drop_word = torch.tensor([self.dropout_seed], dtype=torch.int32, device=audios.device)
+            seed = self._drop_word
+        return codec(audios, sample=seed is not None, seed_word=seed)
+
     def _advance_dropout(self, dev: torch.device) -> None:
         if self._drop_word is None or self._drop_word.device != dev:
             self._drop_word = torch.tensor([self.dropout_seed], dtype=torch.int32, device=dev)

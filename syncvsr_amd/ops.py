@@ -1591,3 +1591,36 @@ def scale_bf16(x: torch.Tensor, alpha: float, drop=None, out: Optional[torch.Ten
     y = torch.empty_like(x) if out is None else out
     _call("svsr_scale_bf16", _p(x), _p(y), x.numel(), float(alpha), *_drop(drop), _stream())
     return y
+
+
+# --------------------------------------------------------------------------------------------------
+# wav2vec2 audio tokeniser (csrc/w2v_codec.hip)
+# --------------------------------------------------------------------------------------------------
+def w2v_stats_floats(B: int, F0: int) -> int:
+    """fp32 workspace of the GroupNorm partial sums of layer 0 (svsr_w2v_stats_floats)."""
+    n = int(_lib.load().svsr_w2v_stats_floats(B, F0))
+    if n < 0:
+        _lib.check(-n, "svsr_w2v_stats_floats")
+    return n
+
+
+def w2v_conv0(wave: torch.Tensor, B: int, L_in: int, pad: int, w: torch.Tensor, bias, gamma, beta, eps: float, out: torch.Tensor,
+              out_rows: int, stats, group: bool) -> None:
+    """Layer 0 of the feature encoder: wave fp32 [B][L_in] (+ pad zeros) -> out bf16 [B][out_rows][512] (svsr_w2v_conv0)."""
+    F0 = (L_in + pad - 10) // 5 + 1
+    _call("svsr_w2v_conv0", _p(wave), B, L_in, pad, _p(w), _p(bias), _p(gamma), _p(beta), float(eps), _p(out), out_rows, _p(stats),
+          1 if group else 0, _stream(), label="k_w2v_conv0", flops=2.0 * B * F0 * 512 * 10)
+
+
+def w2v_norm_gelu(x: torch.Tensor, B: int, F: int, rows: int, gamma, beta, eps: float, stats=None, group: bool = False) -> None:
+    """In place: GELU(LayerNorm(512)) of the F valid rows of every clip, or GELU(GroupNorm) of layer 0 from its partial sums (svsr_w2v_norm_gelu)."""
+    _call("svsr_w2v_norm_gelu", _p(x), B, F, rows, _p(gamma), _p(beta), float(eps), _p(stats), F if group else 0, 1 if group else 0,
+          _stream(), label="k_w2v_norm_gelu")
+
+
+def w2v_quantize(feat: torch.Tensor, R: int, F: int, keep: int, gamma, beta, eps: float, w16: torch.Tensor, bias: torch.Tensor,
+                 tok: torch.Tensor, seed: Optional[torch.Tensor] = None, site: int = 0, logits_out: Optional[torch.Tensor] = None) -> None:
+    """feature_projection LayerNorm + weight_proj + per-group argmax (or argmax of logits + Gumbel noise with `seed`) -> tok int64
+    [R / F][keep][2] (frames t < keep of every clip of F frames; svsr_w2v_quantize)."""
+    _call("svsr_w2v_quantize", _p(feat), R, F, keep, _p(gamma), _p(beta), float(eps), _p(w16), _p(bias), _p(seed), int(site), _p(tok), _p(logits_out),
+          _stream(), label="k_w2v_quantize", flops=2.0 * R * 512 * 640)
