@@ -526,7 +526,16 @@ int svsr_scale_bf16(const void* x, void* y, int64_t n, float alpha, const unsign
  * SVSR_ERR_NO_GROUP; not inside a group).  svsr_steplist_set_skips(list, mask, ngroups): mask[g] != 0 leaves group g out of every
  * following svsr_steplist_run until it is set again; the list keeps a copy; ngroups must be svsr_steplist_groups(list)
  * (SVSR_ERR_MASK_SIZE).  svsr_steplist_calls(list, g): CALL ops of group g (g < 0: of the whole list).  svsr_steplist_last_issued:
- * CALL ops issued since segment 0 (or the whole list) was last run. */
+ * CALL ops issued since segment 0 (or the whole list) was last run.
+ *
+ * Gradient accumulation (engine.TrainStep(accumulate = N)) keeps ONE list per batch shape for the three kinds of micro-step: the zero-fill
+ * of the gradient buffer and the optimiser tail (sums of squares, AdamW ranges, shadow transposes) are two more groups, numbered behind
+ * the layer-drop groups, and the mask of a replay names the skipped groups of both kinds.  The tail group is opened several times (around
+ * the early sum of squares inside the backward, and behind the reducer's BREAK).
+ * svsr_steplist_dry_run(list, segment, counts): what svsr_steplist_run(list, segment, ..) would issue under the current mask, without
+ * issuing anything — counts[4] = {CALL, WAIT, MEMSET, COPY} ops (WAITs are counted, as they are issued, whatever is skipped).  The walk
+ * is the one svsr_steplist_run takes; it needs no device (svsr_steplist_push_wait defers making its event to the first run where no
+ * device is present). */
 void* svsr_steplist_create(void);
 int svsr_steplist_destroy(void* list);
 int svsr_steplist_knows(const char* name);
@@ -537,6 +546,7 @@ int svsr_steplist_push_break(void* list);
 int svsr_steplist_segments(void* list);
 int64_t svsr_steplist_size(void* list);
 int svsr_steplist_run(void* list, int segment, int* failed);
+int svsr_steplist_dry_run(void* list, int segment, int64_t* counts);
 int svsr_steplist_push_group(void* list, int group);
 int svsr_steplist_push_copy(void* list, void* dst, const void* src, int64_t bytes, hipStream_t stream, int when_skipped);
 int svsr_steplist_set_skips(void* list, const uint8_t* mask, int ngroups);

@@ -17,6 +17,9 @@
 // replays leave out on the host (no launch of them is issued, no kernel runs to do nothing) and a COPY of a skipped group passes the
 // group's input on to where its output would have been.  WAITs are issued whatever is skipped, so cross-stream order holds; a
 // group never holds a BREAK.
+// Gradient accumulation (engine.TrainStep(accumulate=N)) uses two more groups of the same kind, numbered behind the layer-drop groups: the
+// zero-fill of the gradient buffer (left out of every micro-step but the first of a window) and the optimiser tail (left out of every
+// micro-step but the last); one mask per replay names the skipped groups of both kinds.
 // Everything a CALL points to must stay alive and in place while the list exists: device buffers (the recorder on the Python side
 // keeps every tensor of the recorded step), host arrays (plan meta records, tap tables: cached for the life of the process).
 // Nothing here launches a kernel of its own; results are bit-identical to the eager step by construction.
@@ -158,9 +161,14 @@ int svsr_steplist_push_wait(void* list, hipStream_t waiter, hipStream_t signalle
     if (l == nullptr) return SVSR_ERR_ARG;
     Op op{};
     op.kind = OP_WAIT; op.a = waiter; op.b = signaller; op.group = -1;      // (issued whatever is skipped)
-    hipError_t e = hipEventCreateWithFlags(&op.ev, wait_event_flags());
-    if (e != hipSuccess) return (int)e;
-    l->events.push_back(op.ev);
+    // the event is made here; where that fails (no device: host-only bookkeeping, svsr_steplist_dry_run) the first run that ISSUES the
+    // wait makes it, and reports the failure
+    if (hipEventCreateWithFlags(&op.ev, wait_event_flags()) == hipSuccess) {
+        l->events.push_back(op.ev);
+    } else {
+        op.ev = nullptr;
+        (void)hipGetLastError();
+    }
     l->ops.push_back(op);
     return SVSR_OK;
 }
@@ -247,44 +255,73 @@ int64_t svsr_steplist_size(void* list) {
     return l == nullptr ? 0 : (int64_t)l->ops.size();
 }
 
-/* issues segment `segment` (all of them for segment < 0); returns 0 or the first non-zero code, with the failing op's index in *failed */
-int svsr_steplist_run(void* list, int segment, int* failed) {
-    StepList* l = static_cast<StepList*>(list);
+}  // extern "C"
+
+namespace {
+
+// One walk serves svsr_steplist_run (ISSUE) and svsr_steplist_dry_run (counts only): what a replay leaves out is decided in ONE place.
+// counts (may be null): ops passed on, per kind {CALL, WAIT, MEMSET, COPY}.
+template <bool ISSUE>
+int walk(StepList* l, int segment, int* failed, int64_t* counts) {
     if (l == nullptr || segment >= (int)l->seg_begin.size()) return SVSR_ERR_ARG;
     const size_t lo = segment < 0 ? 0 : l->seg_begin[segment];
     const size_t hi = (segment < 0 || segment + 1 == (int)l->seg_begin.size()) ? l->ops.size() : l->seg_begin[segment + 1];
-    if (segment <= 0) l->issued = 0;
+    if (ISSUE && segment <= 0) l->issued = 0;
     for (size_t i = lo; i < hi; ++i) {
-        const Op& op = l->ops[i];
-        int rc = 0;
+        Op& op = l->ops[i];
+        int rc = 0, kind = 0;
         switch (op.kind) {
             case OP_CALL:
                 if (skipped(l, op.group)) continue;
-                rc = op.call(op.args);
-                ++l->issued;
+                if (ISSUE) { rc = op.call(op.args); ++l->issued; }
+                kind = 0;
                 break;
-            case OP_WAIT: {
-                hipError_t e = hipEventRecord(op.ev, op.b);
+            case OP_WAIT: {                      // whatever is skipped: cross-stream order does not depend on the mask
+                kind = 1;
+                if (!ISSUE) break;
+                hipError_t e = hipSuccess;
+                if (op.ev == nullptr) {          // (svsr_steplist_push_wait could not make it)
+                    e = hipEventCreateWithFlags(&op.ev, wait_event_flags());
+                    if (e == hipSuccess) l->events.push_back(op.ev); else op.ev = nullptr;
+                }
+                if (e == hipSuccess) e = hipEventRecord(op.ev, op.b);
                 if (e == hipSuccess) e = hipStreamWaitEvent(op.a, op.ev, 0);
                 rc = (int)e;
                 break;
             }
             case OP_MEMSET:
                 if (skipped(l, op.group)) continue;
-                rc = (int)hipMemsetAsync(op.ptr, op.value, op.bytes, op.a);
+                if (ISSUE) rc = (int)hipMemsetAsync(op.ptr, op.value, op.bytes, op.a);
+                kind = 2;
                 break;
             case OP_COPY:
                 if (!skipped(l, op.group)) continue;
-                rc = (int)hipMemcpyAsync(op.ptr, op.src, op.bytes, hipMemcpyDeviceToDevice, op.a);
+                if (ISSUE) rc = (int)hipMemcpyAsync(op.ptr, op.src, op.bytes, hipMemcpyDeviceToDevice, op.a);
+                kind = 3;
                 break;
-            default: break;
+            default: continue;
         }
         if (rc != 0) {
             if (failed != nullptr) *failed = (int)i;
             return rc;
         }
+        if (counts != nullptr) ++counts[kind];
     }
     return SVSR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+/* issues segment `segment` (all of them for segment < 0); returns 0 or the first non-zero code, with the failing op's index in *failed */
+int svsr_steplist_run(void* list, int segment, int* failed) { return walk<true>(static_cast<StepList*>(list), segment, failed, nullptr); }
+
+/* what svsr_steplist_run(list, segment, ..) would issue under the current skip mask, issuing nothing: counts[4] = {CALL, WAIT, MEMSET, COPY} */
+int svsr_steplist_dry_run(void* list, int segment, int64_t* counts) {
+    if (counts == nullptr) return SVSR_ERR_ARG;
+    counts[0] = counts[1] = counts[2] = counts[3] = 0;
+    return walk<false>(static_cast<StepList*>(list), segment, nullptr, counts);
 }
 
 /* `waiter` waits for everything enqueued so far on `signaller` (eager twin of the list's WAIT op) */

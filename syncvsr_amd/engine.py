@@ -76,6 +76,48 @@ class _ShapeList:
         self.nbytes = 0
 
 
+class AccumWindow:
+    """Host bookkeeping of gradient accumulation (Lightning's `accumulate_grad_batches`): a window is `n` consecutive micro-steps.  plan()
+    says what the micro-step that is due does — zero-fill the gradient buffer (the first of a window only), reduce it across the ranks and
+    run the optimiser tail (the last only); advance() moves on when that micro-step is done; flush() closes a partial window (True when
+    there is an accumulated gradient to step on); abort() abandons it.  Pure host logic: no device, no model."""
+
+    def __init__(self, n: int = 1):
+        if int(n) < 1:
+            raise ValueError("accumulate_grad_batches must be >= 1")
+        self.n = int(n)
+        self.pos = 0
+
+    def plan(self) -> dict:
+        last = self.pos == self.n - 1
+        return {"zero": self.pos == 0, "reduce": last, "optimise": last}
+
+    def advance(self) -> None:
+        self.pos = (self.pos + 1) % self.n
+
+    def flush(self) -> bool:
+        due = self.pos > 0
+        self.pos = 0
+        return due
+
+    def abort(self) -> None:
+        self.pos = 0
+
+    def state_dict(self) -> dict:
+        """{} at a window boundary (a checkpoint taken there keeps its keys), else {"accum_window": int64 [n, position]}."""
+        return {"accum_window": torch.tensor([self.n, self.pos], dtype=torch.int64)} if self.pos else {}
+
+    def load_state_dict(self, sd: dict) -> None:
+        if "accum_window" not in sd:
+            self.pos = 0
+            return
+        n, pos = (int(x) for x in sd["accum_window"].reshape(-1).tolist())
+        if n != self.n or not 0 < pos < n:
+            raise ValueError(f"this checkpoint was saved at micro-step {pos} of a window of {n}: it resumes only under accumulate={n} "
+                             f"(this TrainStep accumulates {self.n})")
+        self.pos = pos
+
+
 class TrainStep:
     """forward + backward + (all-reduce) + clip + AdamW for the LRW model (`TransformerLightningModule`; its step takes
     (videos, audio_tokens, labels, word_mask)) or the LRS model (`lrs_model.E2E`; (x, lengths, audio_tokens, label));
@@ -84,12 +126,22 @@ class TrainStep:
     After step() returns, the tail of the optimiser step (AdamW of everything behind the front-end, its shadow transposes) may still be
     running on the model's side stream, beside whatever the main stream does next.  The model's own entry points join it where they need
     the parameters (forward before the encoder, forward_videos, state_dict, load_state_dict, the LRS scorers, refresh_shadows); code that
-    touches parameters DIRECTLY (p.data, p.cpu(), an EMA update) calls synchronize() first."""
+    touches parameters DIRECTLY (p.data, p.cpu(), an EMA update) calls synchronize() first.
+
+    Gradient accumulation (`accumulate=N`, or `accumulate_grad_batches` of the config: Lightning's automatic optimisation under
+    strategy="ddp").  N consecutive step() calls (micro-steps) form a window: every micro-step's loss enters its backward times 1/N and the
+    gradients add up in the flat buffer; the buffer is zeroed in the first micro-step only; the all-reduce (none is issued before: DDP's
+    no_sync), the clip, AdamW, the shadow refresh, the schedule and state()["step"] happen in the last one only, on the accumulated gradient.
+    BatchNorm statistics, the dropout word and the layer-drop draw advance in every micro-step; step() returns the unscaled losses of its
+    micro-batch.  A window whose accumulated gradient norm is not finite is skipped as one unit.  flush() closes a partial window.
+    An exception inside a micro-step ABANDONS the window: the micro-step may have added any part of its gradient to the buffer, so what
+    the window had accumulated is not stepped on — the next step() starts a new window (and zero-fills); parameters and optimiser state
+    are as the last completed window left them (BatchNorm statistics and the dropout word keep what the abandoned micro-steps did)."""
 
     def __init__(self, model, config: Optional[Config] = None, process_group=None,
                  use_graph: bool = False, bucket_mb: float = 32.0, always_reduce: bool = False, data_parallel: bool = True,
                  grad_comm_dtype: torch.dtype = torch.float32, native: bool = False, max_shapes: int = 1,
-                 max_recorded_bytes: Optional[int] = None):
+                 max_recorded_bytes: Optional[int] = None, accumulate: Optional[int] = None):
         """native=True: the launch sequence of the first step is recorded into a native step list (csrc/steplist.hip) and every
         later step re-issues it with one library call per segment — eager launches on the same streams (the weight-gradient side
         stream keeps overlapping, which a captured HIP graph loses) without the per-launch host cost of the Python loop.  Batch
@@ -100,7 +152,12 @@ class TrainStep:
         max_shapes > 1 (native only): one recorded list per batch shape (shape_cache.shape_key of the prepared inputs for LRS, of the
         batch for LRW), each with its own static inputs and outputs; parameters, optimiser state, buffers, the dropout word and the
         scratch are shared.  A batch of a new shape is recorded (and executed) in its step; beyond `max_shapes` lists, or beyond
-        `max_recorded_bytes` kept alive by their recorders, the least recently used list is released after a device synchronisation."""
+        `max_recorded_bytes` kept alive by their recorders, the least recently used list is released after a device synchronisation.
+
+        accumulate=N (default: `train.accumulate_grad_batches` of the LRW config, `trainer.accumulate_grad_batches` of the LRS one, else 1):
+        gradient accumulation over windows of N micro-steps (class docstring).  Eager and native; under native ONE recorded list per batch
+        shape serves the first, middle and last micro-steps (the zero-fill and the optimiser tail are op groups a replay leaves out), and
+        with max_shapes > 1 the micro-batches of a window may differ in shape."""
         self.model = model
         self.is_lrw = isinstance(model, TransformerLightningModule)
         if self.is_lrw:            # LRW/video/config/*.yaml: optim.optimizer / optim.scheduler / train.gradient_clip_val
@@ -114,8 +171,15 @@ class TrainStep:
             sch = cfg.get("scheduler", {}) or {}
             clip = (cfg.get("trainer", {}) or {}).get("gradient_clip_val", 0.0)
         accum = (cfg.get("train", {}) or {}).get("accumulate_grad_batches", 1) if self.is_lrw else (cfg.get("trainer", {}) or {}).get("accumulate_grad_batches", 1)
-        if int(accum or 1) != 1:
-            raise NotImplementedError("accumulate_grad_batches != 1 is not supported by TrainStep (one optimiser step per batch)")
+        accum = int(accumulate if accumulate is not None else (accum or 1))
+        if accum < 1:
+            raise ValueError("accumulate (accumulate_grad_batches) must be >= 1")
+        if accum > 1 and use_graph:
+            raise NotImplementedError("accumulate > 1 with use_graph=True: a captured HIP graph holds the whole step, optimiser included, and "
+                                      "cannot leave the zero-fill or the optimiser out of a replay (use native=True or the eager step)")
+        self.window = AccumWindow(accum)
+        if accum > 1 or getattr(model, "_loss_scale", 1.0) != 1.0:
+            model.set_loss_scale(1.0 / accum)          # the seeds of the backward: written in place, outside any recorded region
         self.lr = float(opt.lr)
         self.betas = (float(opt.betas[0]), float(opt.betas[1]))
         self.eps = float(opt.eps)
@@ -130,6 +194,8 @@ class TrainStep:
         self.dp = GradReducer(model, process_group, bucket_mb, always_reduce, grad_comm_dtype) if data_parallel and (self.world > 1 or always_reduce) else None
         if not data_parallel:
             model.grad_ready_hook = None
+        if hasattr(model, "accumulate_into_grads"):
+            model.accumulate_into_grads(False)
         self.use_graph = use_graph
         self.native = bool(native)
         if self.native and use_graph:
@@ -171,6 +237,8 @@ class TrainStep:
 
     # -- one eager step -----------------------------------------------------------------------------
     def _step_impl(self, *batch):
+        if self.window.n > 1:
+            return self._micro_step_impl(*batch)
         model = self.model
         st = model.store()
         trace = _ROCTX                                   # SVSR_ROCTX=1: roctx ranges (rocprofv3 --marker-trace) around the phases
@@ -196,6 +264,61 @@ class TrainStep:
             return {k: v.detach() for k, v in out.items()}
         return tuple(v.detach() for v in out)
 
+    def _micro_step_impl(self, *batch):
+        """_step_impl for accumulate > 1: one micro-step of the window (AccumWindow.plan).  The backward is seeded with the model's own
+        device scalars (model.loss_seeds: 1/N folded into the loss weights) — the scalars the recorded step hands its backward."""
+        model = self.model
+        st = model.store()
+        plan = self.window.plan()
+        if self.dp is not None:
+            self.dp.begin_step(sync=plan["reduce"])
+        self._begin_micro_step(st, plan)
+        out = model(*batch)
+        losses = (out["loss_category"], out["loss_audio"]) if self.is_lrw else tuple(out[1:4])
+        torch.autograd.backward(losses, model.loss_seeds(st.flat.device))
+        model.accumulate_into_grads(False)
+        if plan["optimise"]:
+            if self.dp is not None:
+                self.dp.finish()
+            self._optimizer(st)
+        if self.is_lrw:
+            return {k: v.detach() for k, v in out.items()}
+        return tuple(v.detach() for v in out)
+
+    def _begin_micro_step(self, st, plan: dict) -> None:
+        """_zero_grads_early for accumulate > 1.  The zero-fill: executed in the first micro-step of a window; inside a recording it is the
+        list's "zero" op group whatever micro-step records (appended without being executed when this one is not the first).  The early
+        sum of squares (model._early_sumsq) belongs to the optimiser tail: asked for in the last micro-step only — and in every recording,
+        where it joins the "tail" group."""
+        model = self.model
+        rec = ops.active_recorder()
+        st.__dict__.pop("sumsq_tail_done", None)
+        model._early_sumsq = self.opt_state if self.dp is None and (plan["optimise"] or rec is not None) else None
+        if plan["zero"] or rec is not None:
+            with ops.window_group("zero"):
+                model._side.run(lambda: ops.memset(st.grad, 0))
+        if plan["zero"]:
+            st.grad_clean = True
+        model.accumulate_into_grads(not plan["zero"])
+
+    def flush(self) -> bool:
+        """Closes a partial window (the end of an epoch whose batch count is not a multiple of N: Lightning steps on the last batch): the
+        optimiser tail — all-reduce under data parallelism, clip, AdamW, shadows, schedule — runs on what has been accumulated, which keeps
+        its 1/N scale.  Nothing happens at a window boundary.  -> True when an optimiser step was made."""
+        if not self.window.flush():
+            return False
+        model = self.model
+        st = model.store()
+        model._early_sumsq = None
+        st.__dict__.pop("sumsq_tail_done", None)
+        model.accumulate_into_grads(False)
+        if self.dp is not None:
+            self.dp.begin_step()
+            self.dp.on_ready(0)
+            self.dp.finish()
+        self._optimizer(st)
+        return True
+
     def _zero_grads_early(self, st) -> None:
         """The flat gradient buffer is zeroed when the step BEGINS, on the side stream (behind the previous step's optimiser, which is the
         last reader; ahead of this step's weight gradients, the first writers there; the model joins the side stream before its encoder
@@ -208,8 +331,6 @@ class TrainStep:
         # no collective between the backward and the clip: the model may sum the squares of every gradient but the last while that one is
         # computed (set per step: two TrainSteps may drive one model, each with its own optimiser state)
         model._early_sumsq = self.opt_state if self.dp is None else None
-        if getattr(model, "accumulate_grads", False):
-            return
         model._side.run(lambda: ops.memset(st.grad, 0))
         st.grad_clean = True
 
@@ -254,6 +375,17 @@ class TrainStep:
         """_step_impl without autograd or torch kernels: every device operation is a library call (recordable)."""
         model = self.model
         st = model.store()
+        if self.window.n > 1:
+            # one list for every kind of micro-step: the zero-fill and the optimiser tail are op groups (the reducer's callbacks, between
+            # segments, do nothing unless the micro-step reduces: GradReducer.begin_step(sync))
+            self._begin_micro_step(st, self.window.plan())
+            out = model.train_step_direct(*batch)
+            model.accumulate_into_grads(False)
+            if self.dp is not None:
+                ops.host_callback(self.dp.finish)
+            with ops.window_group("tail"):
+                self._optimizer(st)
+            return out
         self._zero_grads_early(st)
         out = model.train_step_direct(*batch)
         if self.dp is not None:
@@ -277,8 +409,9 @@ class TrainStep:
         if not st.shadow_fresh:
             st.refresh_shadows()
             st.shadow_fresh = True
+        plan = self.window.plan()
         if self.dp is not None:
-            self.dp.begin_step()
+            self.dp.begin_step(sync=plan["reduce"])
         if model._side.stream is None:
             model._side.stream = torch.cuda.Stream()
         model.direct_constants(static[0].device)
@@ -290,6 +423,11 @@ class TrainStep:
         if self._layer_drop():
             rec.layer_groups = True
             rec.skips = frozenset(_xt_skips(model))       # this step's draw: recorded append-only, see StepRecorder.group
+        if self.window.n > 1:
+            # the window groups sit behind the layer-drop groups; the micro-step that records leaves out what its kind leaves out
+            base = 2 * model.layers if rec.layer_groups else 0
+            rec.window = (base, base + 1)
+            rec.skips = rec.skips | frozenset(rec.window_skips(plan["zero"], plan["optimise"]))
         with ops.recording(rec):
             out = self._direct_impl(*static)
         out = {k: v.detach() for k, v in out.items()} if isinstance(out, dict) else tuple(v.detach() for v in out)
@@ -391,6 +529,16 @@ class TrainStep:
                 dst.copy_(src if src.dim() != 2 or src.shape[1] == dst.shape[1] else src[:, : dst.shape[1]], non_blocking=True)
         if ops._stream() != self._main_stream:
             raise RuntimeError("a recorded TrainStep must be replayed on the stream it was recorded on")
+        if self._rec.window is not None:
+            plan = self.window.plan()
+            if self.dp is not None:
+                self.dp.begin_step(sync=plan["reduce"])
+            skips = _xt_skips(model) if self._rec.layer_groups else set()
+            self._rec.set_skips(skips | self._rec.window_skips(plan["zero"], plan["optimise"]))
+            self._rec.run()
+            if plan["optimise"]:
+                model._store.generation += 1
+            return
         if self.dp is not None:
             self.dp.begin_step()
         if self._rec.layer_groups:
@@ -412,16 +560,22 @@ class TrainStep:
 
     def step(self, *batch):
         """One optimisation step; returns the model's outputs (LRW: the dict of five scalars; LRS: the 5-tuple).
-        With use_graph / native the batch shapes are fixed by the first call (later batches are copied into the static buffers)."""
+        With use_graph / native the batch shapes are fixed by the first call (later batches are copied into the static buffers).
+        With accumulate = N > 1 this is one micro-step of a window (class docstring); the optimiser runs in every N-th call."""
         self._watch_fused_encoder()
         try:
-            return self._step(*batch)
+            out = self._step(*batch)
         except BaseException:
             # an aborted step must not leave its early-sum-of-squares handshake pointing at this optimiser's state (a later stand-alone
             # backward would write partial sums into it and the next optimiser step would trust them)
             self.model._early_sumsq = None
             self.model.store().__dict__.pop("sumsq_tail_done", None)
+            if self.window.n > 1:          # the window is abandoned (class docstring): the next step() starts a new one and zero-fills
+                self.window.abort()
+                self.model.accumulate_into_grads(False)
             raise
+        self.window.advance()
+        return out
 
     def _watch_fused_encoder(self) -> None:
         """Automatic fall-back of the fused encoder (csrc/enc_fused.hip).  Its launches need the 8 workgroups of a sequence resident together;
@@ -517,6 +671,12 @@ class TrainStep:
             sd["dropout_word"] = torch.tensor([rs["dropout_word"]], dtype=torch.int64)
             if "layer_rng" in rs:
                 sd["layer_rng"] = _rng_state_to_tensor(rs["layer_rng"])
+        # saved inside a window: its position and the gradient accumulated so far, so that a resumed run finishes the window (at a window
+        # boundary neither key is written)
+        win = self.window.state_dict()
+        if win:
+            sd.update(win)
+            sd["accum_grad"] = self.model.store().grad.detach().clone()
         return sd
 
     def load_state_dict(self, sd: dict[str, torch.Tensor]) -> None:
@@ -532,6 +692,13 @@ class TrainStep:
                 diff = {k: (a, b) for k, a, b in zip(ops.REDUCTION_KNOBS, then, now) if a != b}
                 warnings.warn(f"this checkpoint was written with other reduction-split knobs {diff} (then, now): the resumed run is numerically "
                               f"equivalent but not bit-identical to the original (ops.tune(key, value) restores them)")
+        self.window.load_state_dict(sd)
+        if self.window.pos:
+            st = self.model.store()
+            if "accum_grad" not in sd or sd["accum_grad"].numel() != st.grad.numel():
+                self.window.abort()
+                raise ValueError("a checkpoint saved inside a window carries the accumulated gradient (accum_grad) of this parameter layout")
+            st.grad.copy_(sd["accum_grad"])
         self.opt_state[1] = 0                    # (word 1 counts the skipped steps of THIS run; older checkpoints kept a float there)
         if "dropout_word" in sd and hasattr(self.model, "load_rng_state"):
             rs = {"dropout_word": int(sd["dropout_word"].reshape(-1)[0])}
@@ -544,7 +711,8 @@ class TrainStep:
 
     # -- introspection ------------------------------------------------------------------------------
     def state(self) -> dict[str, float]:
-        """{step, lr, grad_norm, skipped_steps} of the last optimiser step (a host synchronisation).  skipped_steps counts steps whose gradient
+        """{step, lr, grad_norm, skipped_steps} of the last optimiser step (a host synchronisation) and micro_step, the position of the
+        NEXT step() inside its accumulation window (0: at a window boundary; always 0 with accumulate = 1).  skipped_steps counts steps whose gradient
         norm was not finite: they updated nothing and did not advance `step` (svsr_adamw_step).  A fused-encoder launch whose cluster wait
         gave up (csrc/enc_fused.hip) produces such a step; it is picked up here as well as before every step (_watch_fused_encoder): the
         encoder continues on the per-layer launch chain, with a warning."""
@@ -555,7 +723,8 @@ class TrainStep:
         if not self.is_lrw and hasattr(self.model, "check_targets"):
             self.model.check_targets()          # a label outside [1, odim) reached svsr_lrs_targets: raises with the cause
         f = raw.view(torch.float32)
-        return {"step": int(raw[0]), "lr": float(f[2]), "grad_norm": float(f[3]), "skipped_steps": int(raw[1])}
+        return {"step": int(raw[0]), "lr": float(f[2]), "grad_norm": float(f[3]), "skipped_steps": int(raw[1]),
+                "micro_step": self.window.pos}
 
 
 def reduce_metrics(metrics, process_group=None):
@@ -607,6 +776,8 @@ class GradReducer:
         self.comm_stream: Optional[torch.cuda.Stream] = None
         self.top = 0
         self.launched: list[tuple[int, int]] = []
+        self.sync = True                      # begin_step(sync=False): the reducer sits out a micro-step
+        self.collectives = 0                  # gradient all-reduces issued so far (tests count them per micro-step)
         model.grad_ready_hook = self.on_ready
         # DDP construction semantics (torch DistributedDataParallel behind Lightning's strategy="ddp", reference
         # LRW/video/src/train.py:28): every rank starts from rank 0's parameters AND buffers, whatever its own seed or a
@@ -660,7 +831,15 @@ class GradReducer:
             src = dist.get_global_rank(self.group, 0) if self.group is not None else 0
             dist.broadcast(st.bufflat, src=src, group=self.group)
 
-    def begin_step(self) -> None:
+    def begin_step(self, sync: bool = True) -> None:
+        """sync=False (a micro-step of an accumulation window that is not its last; DDP's no_sync): this call, and on_ready / finish until
+        the next begin_step, do nothing — no collective is issued, gradient or buffer (torch's DistributedDataParallel with
+        broadcast_buffers=True re-broadcasts the buffers only before a forward that FOLLOWS a synchronising one, i.e. before the first
+        micro-step of a window: here that is the broadcast in the finish() of the last micro-step).  bucket_times() / exposed_ms()
+        therefore describe the last micro-step."""
+        self.sync = bool(sync)
+        if not self.sync:
+            return
         st = self._st = self.model.store()         # (store() re-validates ~300 tensors: once per step, not once per hook call)
         self.top = st.decay_end
         self.launched = []
@@ -680,6 +859,7 @@ class GradReducer:
         seg = st.grad[lo:hi]
         if self.world == 1 and not self.always:
             return
+        self.collectives += 1
         backend = self._backend
         if seg.is_cuda:
             if fence:
@@ -713,6 +893,8 @@ class GradReducer:
             seg.div_(self.world)
 
     def on_ready(self, lo: int) -> None:
+        if not self.sync:
+            return
         st = self._st if self._st is not None else self.model.store()
         # one fence per call: every bucket launched here waits for the same producers (all enqueued by now), the later ones follow
         # the first in comm-stream order
@@ -735,6 +917,8 @@ class GradReducer:
         statistics (a few KB in one flat vector) follow the buckets on the comm stream and the ONE join below covers both, so
         nothing is left un-joined when the step ends: a captured HIP graph has no dangling branch, and an eval forward or a
         state_dict() read right after the step sees the broadcast values."""
+        if not self.sync:
+            return
         if (self.world > 1 or self.always) and self.comm_stream is not None:
             st = self._st if self._st is not None else self.model.store()
             self.comm_stream.wait_stream(torch.cuda.current_stream())

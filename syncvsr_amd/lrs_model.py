@@ -461,6 +461,31 @@ class E2E(nn.Module):
         """d loss / d {loss_ctc, loss_att, loss_audio} as device scalars (made once, outside any recorded region)."""
         if getattr(self, "_g_consts", None) is None or self._g_consts[0].device != dev:
             self._g_consts = tuple(torch.full((), w, dtype=torch.float32, device=dev) for w in (self.mtlalpha, 1.0 - self.mtlalpha, self.audio_weight))
+            if getattr(self, "_loss_scale", 1.0) != 1.0:
+                self.set_loss_scale(self._loss_scale)
+
+    def set_loss_scale(self, scale: float = 1.0) -> None:
+        """Gradient accumulation (engine.TrainStep(accumulate=N) drives this with 1 / N): the seeds of the hand-written backward become
+        d (scale * loss) / d {loss_ctc, loss_att, loss_audio} — what `(loss * scale).backward()` hands the backward, in fp32: fp32(scale) times
+        the fp32 CTC, attention and audio weights.  Written IN PLACE and outside any recorded region (a recorded step list reads the
+        scalars by address).  The losses a step returns stay unscaled."""
+        self._loss_scale = float(scale)
+        if getattr(self, "_g_consts", None) is not None:
+            one = torch.tensor(self._loss_scale, dtype=torch.float32)
+            for g, w in zip(self._g_consts, (self.mtlalpha, 1.0 - self.mtlalpha, self.audio_weight)):
+                g.copy_(one * torch.tensor(w, dtype=torch.float32))
+
+    def loss_seeds(self, dev) -> tuple:
+        """(loss_ctc, loss_att, loss_audio) seeds: the device scalars train_step_direct hands its backward."""
+        self.direct_constants(dev)
+        return self._g_consts
+
+    def accumulate_into_grads(self, on: bool = True) -> None:
+        """The "do not zero" switch of the backward (as model.TransformerLightningModule.accumulate_into_grads): off, every backward() zeroes
+        the flat gradient buffer before it writes; on, the following backward() calls ADD into it — `(loss / N).backward()` per micro-batch
+        with the switch off for the first and on for the others, then optimizer.step().  engine.TrainStep sets it per micro-step and
+        leaves it off."""
+        self._keep_grads = bool(on)
 
     def train_step_direct(self, x, ilen, tokens, labels, ys_in, ys_out):
         """forward + backward of the loss WITHOUT autograd (inputs as prepare_batch returns them): every device operation is a library call,
@@ -868,7 +893,7 @@ class _LrsFunction(torch.autograd.Function):
         R = B * T
         A, G, V = model.audio_alignment, model.vq_groups, model.audio_vocab_size
         dev = th["h"].device
-        if not getattr(model, "accumulate_grads", False):
+        if not getattr(model, "_keep_grads", False):       # (accumulate_into_grads: the backward adds into the buffer)
             st.zero_grad()
         st.rebind_grads()
 

@@ -373,10 +373,43 @@ class TransformerLightningModule(nn.Module):
         return (videos.float().contiguous(), audio_tokens[:, : T * A].contiguous(), (labels.long() if hard else labels.float()).contiguous(), wm)
 
     def direct_constants(self, dev) -> None:
-        """The two loss weights d loss_total / d loss_{category, audio} as device scalars (made once, outside any recorded region)."""
+        """The two loss weights d loss_total / d loss_{category, audio} as device scalars (made once, outside any recorded region), times
+        the loss scale of set_loss_scale()."""
         if getattr(self, "_g_one", None) is None or self._g_one.device != dev:
             self._g_one = torch.ones((), dtype=torch.float32, device=dev)
             self._g_lam = torch.full((), self.lambda_audio, dtype=torch.float32, device=dev)
+            if getattr(self, "_loss_scale", 1.0) != 1.0:
+                self.set_loss_scale(self._loss_scale)
+
+    def set_loss_scale(self, scale: float = 1.0) -> None:
+        """Gradient accumulation (engine.TrainStep(accumulate=N) drives this with 1 / N): the seeds of the hand-written backward become
+        d (scale * loss_total) / d loss_{category, audio} — what `(loss_total * scale).backward()` hands the backward, in fp32: scale and
+        fp32(scale) * fp32(lambda_audio).  The device scalars are written IN PLACE and outside any recorded region: a recorded step list
+        reads them by address, so the scale needs no re-recording.  The losses a step returns stay unscaled."""
+        self._loss_scale = float(scale)
+        if getattr(self, "_g_one", None) is not None:
+            one = torch.tensor(self._loss_scale, dtype=torch.float32)
+            self._g_one.copy_(one)
+            self._g_lam.copy_(one * torch.tensor(self.lambda_audio, dtype=torch.float32))
+
+    def loss_seeds(self, dev) -> tuple:
+        """(loss_category seed, loss_audio seed): the device scalars train_step_direct hands its backward."""
+        self.direct_constants(dev)
+        return self._g_one, self._g_lam
+
+    def accumulate_into_grads(self, on: bool = True) -> None:
+        """The "do not zero" switch of the backward.  Off (the default): every backward() zeroes the flat gradient buffer (the storage behind
+        every p.grad) before it writes, so `loss.backward(); optimizer.step()` needs no zero_grad().  On: the following backward() calls ADD
+        into the buffer.  Hand-rolled accumulation over N micro-batches with a foreign optimiser:
+
+            model.accumulate_into_grads(False); (model(*b0)["loss_total"] / N).backward()      # zeroes, then writes
+            model.accumulate_into_grads(True)
+            for b in rest: (model(*b)["loss_total"] / N).backward()                             # adds
+            optimizer.step(); model.accumulate_into_grads(False)
+
+        (optimizer.zero_grad() only drops the p.grad views; the buffer is zeroed by the first backward.)  engine.TrainStep sets this
+        per micro-step and leaves it off."""
+        self._keep_grads = bool(on)
 
     def train_step_direct(self, videos, audio_tokens, labels, word_mask) -> dict[str, torch.Tensor]:
         """forward + backward of loss_total WITHOUT autograd: the same tape functions `forward()` + `loss_total.backward()` run,
@@ -737,7 +770,9 @@ def _frontend_backward(model, st: "_ParamStore", tape: dict, dfeats: torch.Tenso
         early = getattr(model, "_early_sumsq", None)      # the optimiser's device state, set by engine.TrainStep when no collective follows
         if early is not None and st.sumsq_head:
             # every gradient but the stem convolution's is final: their sum of squares (the global-norm clip's) runs beside that last pass
-            model._side.run(lambda: ops.grad_sumsq_parts(st.grad, st.sumsq_head, st.numel - st.sumsq_head, early, 0, ops.SUMSQ_PARTS - 1))
+            # (part of the optimiser tail: under gradient accumulation a recorded list leaves it out of every micro-step but the last)
+            with ops.window_group("tail"):
+                model._side.run(lambda: ops.grad_sumsq_parts(st.grad, st.sumsq_head, st.numel - st.sumsq_head, early, 0, ops.SUMSQ_PARTS - 1))
             st.sumsq_tail_done = True
         ops.stem_bwd_wgrad(ts["videos"], dconv, ts["amax"], ts["c"], ts["mean"], ts["rstd"], ws["coef"], st.g32(f"{sc}.weight"))
     else:
@@ -1207,7 +1242,7 @@ class _LrwFunction(torch.autograd.Function):
         B, T, D, S, A, G, V, C = th["dims"]
         dev = th["h"].device
         use_tr = model.use_tr
-        if not getattr(model, "accumulate_grads", False):
+        if not getattr(model, "_keep_grads", False):       # (accumulate_into_grads: the backward adds into the buffer)
             st.zero_grad()
         st.rebind_grads()
         g_cat = (g_cat if g_cat is not None else torch.zeros((), device=dev)).float().contiguous()

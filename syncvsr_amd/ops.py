@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes
 import os
 import struct
-from contextlib import contextmanager
+from contextlib import contextmanager, nullcontext
 from typing import Callable, Optional, Sequence
 
 import torch
@@ -200,6 +200,9 @@ class StepRecorder:
         self.layer_groups = False
         self.skips: frozenset = frozenset()
         self.append_only = False
+        # gradient accumulation (engine.TrainStep(accumulate=N > 1)): (zero group, tail group) — the zero-fill of the gradient buffer and the
+        # optimiser tail as op groups numbered behind the layer-drop groups (ops.window_group); None: the list holds neither (N = 1)
+        self.window: Optional[tuple] = None
 
     def __del__(self):
         try:
@@ -284,6 +287,19 @@ class StepRecorder:
                 raise ValueError(f"op group {g} is not in this step list ({n} groups)")
             mask[g] = 1
         _lib.check(self.lib.svsr_steplist_set_skips(self.handle, mask, n), "svsr_steplist_set_skips")
+
+    def window_skips(self, zero: bool, tail: bool) -> set:
+        """The window groups a micro-step leaves out: the zero-fill unless `zero`, the optimiser tail unless `tail`."""
+        if self.window is None:
+            return set()
+        return {g for g, run in zip(self.window, (zero, tail)) if not run}
+
+    def would_issue(self, segment: int = -1) -> dict:
+        """What run() would issue for `segment` (-1: the whole list) under the current skip mask: {calls, waits, memsets, copies}.  Issues
+        nothing and needs no device."""
+        counts = (ctypes.c_int64 * 4)()
+        _lib.check(self.lib.svsr_steplist_dry_run(self.handle, int(segment), counts), "svsr_steplist_dry_run")
+        return dict(zip(("calls", "waits", "memsets", "copies"), (int(c) for c in counts)))
 
     @property
     def last_issued(self) -> int:
@@ -374,9 +390,24 @@ def recording(rec: StepRecorder):
         rec.closed = True
 
 
+def active_recorder() -> Optional[StepRecorder]:
+    """The recorder of the `ops.recording` block this runs in, else None."""
+    return _REC
+
+
 def layer_groups() -> Optional[StepRecorder]:
     """The active recorder when it asks for replayable layer drop (StepRecorder.layer_groups), else None."""
     return _REC if _REC is not None and _REC.layer_groups else None
+
+
+def window_group(which: str):
+    """Context: inside a recording for gradient accumulation (StepRecorder.window), the launches and memsets of the block join the
+    window's "zero" or "tail" op group — appended without being executed when the recording micro-step leaves that group out.  Anywhere
+    else (eager steps, accumulate = 1) it does nothing."""
+    rec = _REC
+    if rec is None or rec.window is None:
+        return nullcontext()
+    return rec.group(rec.window[("zero", "tail").index(which)])
 
 
 def host_callback(fn: Callable[[], None]) -> None:
