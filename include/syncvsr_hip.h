@@ -32,6 +32,12 @@ typedef void* hipStream_t;
 
 #define SVSR_OK 0
 #define SVSR_ERR_ARG 1001
+/* Store / add mode of the entry points that write a parameter gradient (the *_v2 forms; the older symbols add to both destinations).
+ * A set bit: the destination is loaded and added to.  A clear bit: the launch is the FIRST writer of that range in this step and stores
+ * 0.f + sum without loading the destination — bit for bit what the add onto a zero-filled buffer left (-0 becomes +0), without the fill
+ * and without the read.  Every element of a destination is written in either mode. */
+#define SVSR_GRAD_ADD_DW 1
+#define SVSR_GRAD_ADD_DB 2
 /* step-list groups (svsr_steplist_push_group): a group is open where none may be (a nested group, a break or a copy inside a group) */
 #define SVSR_ERR_GROUP_OPEN 1003
 /* step-list groups: a group index the list does not have (a copy naming it, closing with no group open) */
@@ -89,6 +95,8 @@ extern "C" {
 int svsr_tune(const char* key, int value);
 int svsr_tune_value(const char* key, int* value);
 int svsr_colsum_rows(const float* ws, int nrows, int64_t ld, float* out0, int64_t n0, float* out1, int64_t n1, int accumulate, float scale, hipStream_t stream);
+/* (accumulate: 0 stores, 1 adds to both outputs; 4 | SVSR_GRAD_ADD_* bits (bit 0: out0, bit 1: out1) adds where the bit is set and stores
+ * 0.f + sum elsewhere — the split-K tail of svsr_igemm_wgrad_v2) */
 /* up to any number of svsr_colsum_rows problems, 16 per launch (the postponed parameter-gradient reductions of a layer's backward: LayerNorm
  * weight / bias, linear biases — autograd's accumulation into .grad of lightning.py's modules).  entries: n records of 64 bytes in HOST memory,
  * {const float* ws; float* out0; float* out1; int64_t ld, n0, n1; int32_t nrows, accumulate; float scale; int32_t reserved}; the outputs of
@@ -144,6 +152,9 @@ int svsr_igemm_wgrad(const void* x, const void* dyp, float* dw, float* dbias, co
  * to n separate svsr_igemm_wgrad calls (same workgroup code, one writer per element). */
 int64_t svsr_igemm_wgrad_group_bytes(int n);
 int svsr_igemm_wgrad_group(const svsr_wgrad_problem* problems, int n, void* table_dev, int64_t table_bytes, hipStream_t stream);
+/* the two above with the store / add mode of dw and dbias (SVSR_GRAD_ADD_DW | SVSR_GRAD_ADD_DB; the group: one HOST int per problem, null = all add) */
+int svsr_igemm_wgrad_v2(const void* x, const void* dyp, float* dw, float* dbias, const int* plan_dev, const int* meta, int Nimg, int in_pix, int Ci, int in_pitch, int Co, int out_pix, int out_pitch, int wt_taps, float* part, int64_t part_floats, int mode, hipStream_t stream);
+int svsr_igemm_wgrad_group_v2(const svsr_wgrad_problem* problems, const int* modes, int n, void* table_dev, int64_t table_bytes, hipStream_t stream);
 
 /* svsr_conv3x3_c64: conv3x3(64, 64), stride 1, pad 1 (layer1 of the trunk, resnet.py:8-10,36,53) forward and, with the
  * transposed weights and mirrored taps, its input-gradient; persistent workgroups, weights resident in LDS
@@ -185,6 +196,8 @@ int svsr_bn_bwd_from_stats(const void* g, const void* x, const float* mean, cons
  * Requires Ci, Co multiples of 64 and W <= 29; other shapes go through svsr_igemm_wgrad. */
 int svsr_conv3x3_wgrad_plan(int Nimg, int H, int W, int Ci, int Co, int* splits, int64_t* part_floats);
 int svsr_conv3x3_wgrad(const void* x, const void* dy, float* dw, int Nimg, int H, int W, int Ci, int Co, float* part, int64_t part_floats, hipStream_t stream);
+/* the same with the store / add mode of dw (0 or SVSR_GRAD_ADD_DW) */
+int svsr_conv3x3_wgrad_v2(const void* x, const void* dy, float* dw, int Nimg, int H, int W, int Ci, int Co, float* part, int64_t part_floats, int mode, hipStream_t stream);
 
 /* ---- 3-D stem (stem.hip) --------------------------------------------------------------------------------------
  * svsr_stem_conv_fwd replaces stem3d[0] = nn.Conv3d(1,64,(5,7,7),(1,2,2),(2,3,3),bias=False) (lightning.py:50).
@@ -371,6 +384,11 @@ int svsr_transpose_cast_multi(const float* src, void* dst, const void* table, in
 /* the same from the bf16 shadow (src16: bf16 copy of the parameter buffer, same offsets): half the bytes read, identical result */
 int svsr_transpose_bf16_multi(const void* src16, void* dst, const void* table, int n_entries, hipStream_t stream);
 int svsr_fill_f32(float* p, int64_t n, float v, hipStream_t stream);
+/* svsr_fill_ranges: base[begin, end) = the 32-bit pattern `bits` for n ranges (ranges: 2 n HOST int64 {begin, end} in floats, begin and end
+ * multiples of 4, inside [0, limit)), 16 ranges per launch: the per-step fill of the parts of the flat gradient buffer no store-mode writer
+ * covers (pads, 1-D tensors, tensors whose writers only add), as ONE launch instead of a memset of the whole buffer.  bits = 0 in a training
+ * step; a NaN pattern in the tests that prove no writer reads what it should have stored. */
+int svsr_fill_ranges(float* base, int64_t limit, const int64_t* ranges, int n, unsigned bits, hipStream_t stream);
 /* scalars on the device, so that a step never depends on a host value: *word += delta (the dropout seed word, advanced once per
  * training forward: lightning.py:150 draws fresh masks every step);  *out = *a + wb * *b  (loss_total = loss_category +
  * lambda_audio * loss_audio, lightning.py:187). */

@@ -41,6 +41,8 @@ struct WgradArgs {
     long slab;
     int splits, chunks_per_split;      // 64-row chunks per split (of the longest tap; shorter taps end early)
     int Nimg, in_pix, Ci, in_pitch, Co, out_pix, out_pitch, wt_taps;
+    int mode;              // SVSR_GRAD_ADD_DW | SVSR_GRAD_ADD_DB: the destination is loaded and added to; a clear bit STORES 0.f + sum (first writer
+                           // of the range this step: the bits an add onto a zeroed buffer leaves, without the fill and without the load)
 };
 
 __device__ unsigned g_wg_zero_page[64];     // 256 zero bytes: DMA source for rows beyond the end of a tap's row list
@@ -288,6 +290,7 @@ __device__ __forceinline__ void wg_body(const WgradArgs& p, unsigned char* smem_
     }
     // D[row = co][col = ci]: one writer per element — slab `blockIdx.x` (plain store) or, without a split, dW itself
     const bool direct = p.splits <= 1;
+    const bool add_dw = (p.mode & SVSR_GRAD_ADD_DW) != 0, add_db = (p.mode & SVSR_GRAD_ADD_DB) != 0;      // (wave-uniform: kernel arguments)
     float* dst = direct ? p.dw : p.part + (long)split_idx * p.slab;
 #pragma unroll
     for (int j = 0; j < TT; ++j) {
@@ -300,7 +303,7 @@ __device__ __forceinline__ void wg_body(const WgradArgs& p, unsigned char* smem_
                 const int co = co0 + wco + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                 if (co < p.Co) {
                     float* d = dst + ((long)co * p.wt_taps + tw) * p.Ci + ci;
-                    *d = direct ? *d + acc[i][j][r] : acc[i][j][r];
+                    *d = direct ? (add_dw ? *d : 0.f) + acc[i][j][r] : acc[i][j][r];
                 }
             }
     }
@@ -311,7 +314,7 @@ __device__ __forceinline__ void wg_body(const WgradArgs& p, unsigned char* smem_
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int co = co0 + wco + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (co < p.Co) dbd[co] = direct ? dbd[co] + accb[i][r] : accb[i][r];
+                if (co < p.Co) dbd[co] = direct ? (add_db ? dbd[co] : 0.f) + accb[i][r] : accb[i][r];
             }
     }
 }
@@ -386,7 +389,7 @@ __global__ __launch_bounds__(256) void k_igemm_wgrad_units(const WgradUnitArgs q
 // grid (BC*BC/4/64 (+1 for the bias row), tasks); a thread owns one float4 group of the fragment layout and one of four slot lanes.
 struct WgradReduceArgs {
     const float* part; float* dw; float* db; const int* plan; const int* tasktab;
-    long tile_stride; int Co, Ci, wt_taps, co_tiles, ci_tiles;
+    long tile_stride; int Co, Ci, wt_taps, co_tiles, ci_tiles, mode;
 };
 
 // Block = 64 float4 groups x 4 slot lanes: lane sl adds slots sl, sl + 4, ... in increasing order (two loads in flight), the four lane
@@ -409,7 +412,7 @@ __global__ __launch_bounds__(256) void k_wgrad_unit_reduce(const WgradReduceArgs
         for (int c = threadIdx.x; c < BC; c += 256) {
             float a = 0.f;
             for (int s = 0; s < ns; ++s) a += src[(long)s * q.tile_stride + BC * BC + c];
-            if (cot * BC + c < q.Co) q.db[cot * BC + c] += a;
+            if (cot * BC + c < q.Co) q.db[cot * BC + c] = ((q.mode & SVSR_GRAD_ADD_DB) ? q.db[cot * BC + c] : 0.f) + a;
         }
         return;
     }
@@ -442,7 +445,7 @@ __global__ __launch_bounds__(256) void k_wgrad_unit_reduce(const WgradReduceArgs
     for (int k = 0; k < 4; ++k)
         if (co + k < q.Co) {
             float* d = q.dw + ((long)(co + k) * q.wt_taps + tw) * q.Ci + ci;
-            *d += a[k];
+            *d = ((q.mode & SVSR_GRAD_ADD_DW) ? *d : 0.f) + a[k];
         }
 }
 
@@ -465,7 +468,7 @@ __global__ __launch_bounds__(256) void k_wgrad_unit_reduce_flat(const WgradReduc
         for (int c = threadIdx.x; c < BC; c += 256) {
             float a = 0.f;
             for (int s = 0; s < ns; ++s) a += src[(long)s * q.tile_stride + BC * BC + c];
-            if (cot * BC + c < q.Co) q.db[cot * BC + c] += a;
+            if (cot * BC + c < q.Co) q.db[cot * BC + c] = ((q.mode & SVSR_GRAD_ADD_DB) ? q.db[cot * BC + c] : 0.f) + a;
         }
         return;
     }
@@ -488,7 +491,7 @@ __global__ __launch_bounds__(256) void k_wgrad_unit_reduce_flat(const WgradReduc
     for (int k = 0; k < 4; ++k)
         if (co + k < q.Co) {
             float* d = q.dw + ((long)(co + k) * q.wt_taps + tw) * q.Ci + ci;
-            *d += a[k];
+            *d = ((q.mode & SVSR_GRAD_ADD_DW) ? *d : 0.f) + a[k];
         }
 }
 
@@ -559,7 +562,8 @@ static WgradUnits wgrad_units(const std::vector<long>& tap_chunks, int co_tiles,
     w.tasktab.assign((size_t)2 * ntaps * tiles, 0);
     for (int t = 0; t < ntaps; ++t) {
         const long L = tap_chunks[t];
-        const int n = (int)((L + U - 1) / U);
+        // (a tap no position reaches still gets one empty unit per tile: its part of dW is WRITTEN — as zeros — also when the launch stores)
+        const int n = L > 0 ? (int)((L + U - 1) / U) : 1;
         for (int tile = 0; tile < tiles; ++tile) {
             const int task = t * tiles + tile;         // == (t * ci_tiles + cit) * co_tiles + cot
             if (n > 1) { w.tasktab[2 * task] = w.slots; w.tasktab[2 * task + 1] = n; }
@@ -698,7 +702,7 @@ static int launch_wgrad_units(const WgradArgs& a, const int* plan_dev, const int
     WgradReduceArgs r;
     r.part = a.part; r.dw = a.dw; r.db = a.db; r.plan = plan_dev; r.tasktab = plan_dev + meta[7] + n_units * WUNIT_WORDS;
     r.tile_stride = q.tile_stride; r.Co = a.Co; r.Ci = a.Ci; r.wt_taps = a.wt_taps;
-    r.co_tiles = (a.Co + BC - 1) / BC; r.ci_tiles = (a.Ci + BC - 1) / BC;
+    r.co_tiles = (a.Co + BC - 1) / BC; r.ci_tiles = (a.Ci + BC - 1) / BC; r.mode = a.mode;
     // (slots / tasks: the mean number of partial tiles per task; with few of them a thread adds them all, see k_wgrad_unit_reduce_flat)
     if (slots <= 8 * tasks) hipLaunchKernelGGL((k_wgrad_unit_reduce_flat<BC>), dim3(BC * BC / 1024 + (a.db != nullptr ? 1 : 0), tasks), dim3(256), 0, stream, r);
     else hipLaunchKernelGGL((k_wgrad_unit_reduce<BC>), dim3(BC * BC / 256 + (a.db != nullptr ? 1 : 0), tasks), dim3(256), 0, stream, r);
@@ -752,11 +756,20 @@ int svsr_colsum_rows(const float* ws, int nrows, int64_t ld, float* out0, int64_
 int svsr_igemm_wgrad(const void* x, const void* dyp, float* dw, float* dbias, const int* plan_dev, const int* meta, int Nimg, int in_pix,
                      int Ci, int in_pitch, int Co, int out_pix, int out_pitch, int wt_taps, float* part, int64_t part_floats,
                      hipStream_t stream) {
+    return svsr_igemm_wgrad_v2(x, dyp, dw, dbias, plan_dev, meta, Nimg, in_pix, Ci, in_pitch, Co, out_pix, out_pitch, wt_taps, part, part_floats,
+                               SVSR_GRAD_ADD_DW | SVSR_GRAD_ADD_DB, stream);
+}
+
+/* the same with the store / add mode of its two destinations (include/syncvsr_hip.h SVSR_GRAD_ADD_*) */
+int svsr_igemm_wgrad_v2(const void* x, const void* dyp, float* dw, float* dbias, const int* plan_dev, const int* meta, int Nimg, int in_pix,
+                        int Ci, int in_pitch, int Co, int out_pix, int out_pitch, int wt_taps, float* part, int64_t part_floats, int mode,
+                        hipStream_t stream) {
+    if (mode < 0 || mode > 3) return SVSR_ERR_ARG;
     if (plan_dev == nullptr || meta == nullptr || Ci < 1 || Co < 1 || in_pitch % 8 != 0 || out_pitch % 8 != 0 || Ci % 8 != 0 || Nimg < 1)
         return SVSR_ERR_ARG;
     WgradArgs a;
     a.x = (const bf16_t*)x; a.dy = (const bf16_t*)dyp; a.dw = dw; a.db = dbias; a.part = part; a.plan = plan_dev;
-    a.splits = meta[2]; a.chunks_per_split = meta[3];
+    a.splits = meta[2]; a.chunks_per_split = meta[3]; a.mode = mode;
     a.slab = (long)Co * wt_taps * Ci + (dbias != nullptr ? Co : 0);
     a.Nimg = Nimg; a.in_pix = in_pix; a.Ci = Ci; a.in_pitch = in_pitch; a.Co = Co; a.out_pix = out_pix; a.out_pitch = out_pitch; a.wt_taps = wt_taps;
     const int bc = meta[0], ns = meta[1], tasks = meta[4], maxP = meta[6];
@@ -774,7 +787,7 @@ int svsr_igemm_wgrad(const void* x, const void* dyp, float* dw, float* dbias, co
     else return SVSR_ERR_ARG;
     if (rc != SVSR_OK || a.splits <= 1) return rc;
     const int64_t n = (int64_t)Co * wt_taps * Ci;
-    return svsr_colsum_rows(part, a.splits, a.slab, dw, n, dbias, dbias != nullptr ? Co : 0, 1, 1.0f, stream);
+    return svsr_colsum_rows(part, a.splits, a.slab, dw, n, dbias, dbias != nullptr ? Co : 0, mode == 3 ? 1 : (4 | mode), 1.0f, stream);
 }
 
 /* svsr_igemm_wgrad_group: n independent svsr_igemm_wgrad problems (each described like a call of its own: plan_dev + meta of
@@ -784,6 +797,11 @@ int svsr_igemm_wgrad(const void* x, const void* dyp, float* dw, float* dbias, co
 int64_t svsr_igemm_wgrad_group_bytes(int n) { return n < 1 ? 0 : (int64_t)n * (int64_t)sizeof(WgradGroupEntry); }
 
 int svsr_igemm_wgrad_group(const svsr_wgrad_problem* problems, int n, void* table_dev, int64_t table_bytes, hipStream_t stream) {
+    return svsr_igemm_wgrad_group_v2(problems, nullptr, n, table_dev, table_bytes, stream);
+}
+
+/* the same with one store / add mode per problem (modes: n host ints of SVSR_GRAD_ADD_* bits; null: every problem adds to both destinations) */
+int svsr_igemm_wgrad_group_v2(const svsr_wgrad_problem* problems, const int* modes, int n, void* table_dev, int64_t table_bytes, hipStream_t stream) {
     if (problems == nullptr || n < 1 || n > 256 || table_dev == nullptr || table_bytes < svsr_igemm_wgrad_group_bytes(n)) return SVSR_ERR_ARG;
     std::vector<WgradGroupEntry> tab((size_t)((n + WG_TABLE_CHUNK - 1) / WG_TABLE_CHUNK) * WG_TABLE_CHUNK);
     int tiles = 0, maxP = 1;
@@ -796,6 +814,8 @@ int svsr_igemm_wgrad_group(const svsr_wgrad_problem* problems, int n, void* tabl
         WgradArgs& a = tab[i].a;
         a.x = (const bf16_t*)q.x; a.dy = (const bf16_t*)q.dy; a.dw = q.dw; a.db = q.dbias; a.part = nullptr; a.plan = q.plan_dev;
         a.splits = 1; a.chunks_per_split = q.meta[3];
+        a.mode = modes != nullptr ? modes[i] : (SVSR_GRAD_ADD_DW | SVSR_GRAD_ADD_DB);
+        if (a.mode < 0 || a.mode > 3) return SVSR_ERR_ARG;
         a.slab = (long)q.Co * q.wt_taps * q.Ci + (q.dbias != nullptr ? q.Co : 0);
         a.Nimg = q.Nimg; a.in_pix = q.in_pix; a.Ci = q.Ci; a.in_pitch = q.in_pitch; a.Co = q.Co; a.out_pix = q.out_pix; a.out_pitch = q.out_pitch;
         a.wt_taps = q.wt_taps;

@@ -324,6 +324,15 @@ __global__ void k_fill_f32(float* p, long n, float v) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) p[i] = v;
 }
 
+// up to 16 ranges of one buffer, blockIdx.y = range: 16-byte stores (the ranges are 16-byte aligned)
+struct FillRanges { long begin[16], end[16]; };
+__global__ __launch_bounds__(256) void k_fill_ranges(float* __restrict__ base, const FillRanges r, unsigned bits) {
+    const long b = r.begin[blockIdx.y] / 4, e = r.end[blockIdx.y] / 4;
+    const uint4 v = make_uint4(bits, bits, bits, bits);
+    uint4* p = reinterpret_cast<uint4*>(base);
+    for (long i = b + (long)blockIdx.x * 256 + threadIdx.x; i < e; i += (long)gridDim.x * 256) p[i] = v;
+}
+
 __global__ void k_word_add(int* w, int delta) { if (threadIdx.x == 0 && blockIdx.x == 0) w[0] += delta; }
 __global__ void k_lincomb2(const float* a, const float* b, float wb, float* out) {
     // two roundings, as torch's `a + b * w` (a mul kernel, then an add kernel): no fused multiply-add here
@@ -500,6 +509,31 @@ int svsr_clip_prep(const void* src_u8, const int* params, float* dst, int B, int
 int svsr_fill_f32(float* p, int64_t n, float v, hipStream_t stream) {
     hipLaunchKernelGGL(k_fill_f32, dim3(grid_for(n)), dim3(256), 0, stream, p, (long)n, v);
     return svsr_check_launch();
+}
+
+int svsr_fill_ranges(float* base, int64_t limit, const int64_t* ranges, int n, unsigned bits, hipStream_t stream) {
+    if (base == nullptr || ranges == nullptr || n < 1 || limit < 0 || (reinterpret_cast<uintptr_t>(base) & 15) != 0) return SVSR_ERR_ARG;
+    for (int i = 0; i < n; ++i) {
+        const int64_t b = ranges[2 * i], e = ranges[2 * i + 1];
+        if (b < 0 || e < b || e > limit || (b & 3) != 0 || (e & 3) != 0) return SVSR_ERR_ARG;
+    }
+    for (int i0 = 0; i0 < n; i0 += 16) {
+        const int m = n - i0 < 16 ? n - i0 : 16;
+        FillRanges r;
+        long longest = 1;
+        for (int i = 0; i < 16; ++i) {
+            r.begin[i] = i < m ? (long)ranges[2 * (i0 + i)] : 0;
+            r.end[i] = i < m ? (long)ranges[2 * (i0 + i) + 1] : 0;
+            if (r.end[i] - r.begin[i] > longest) longest = r.end[i] - r.begin[i];
+        }
+        long gx = (longest / 4 + 255) / 256;          // one 16-byte store per thread, capped: the loop strides
+        if (gx > 2048) gx = 2048;
+        if (gx < 1) gx = 1;
+        hipLaunchKernelGGL(k_fill_ranges, dim3((unsigned)gx, (unsigned)m), dim3(256), 0, stream, base, r, bits);
+        const int rc = svsr_check_launch();
+        if (rc != SVSR_OK) return rc;
+    }
+    return SVSR_OK;
 }
 
 int svsr_word_add(int* word, int delta, hipStream_t stream) {

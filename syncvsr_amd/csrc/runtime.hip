@@ -202,7 +202,10 @@ __global__ __launch_bounds__(256) void k_colsum(const float* __restrict__ ws, in
     if (!live) return;
     float* dst = c < n0 ? out0 + c : out1 + (c - n0);
     const float v = acc * scale;
-    *dst = accumulate ? *dst + v : v;
+    // accumulate: 0 plain store, 1 (2, 3: any non-zero value below 4, as always) add to both outputs, 4 | bits: out0 is added to when bit 0 is set, out1 when bit 1 is; the other one
+    // stores 0.f + v (the bits an add onto a zeroed destination leaves: a gradient range's first writer of a step)
+    const bool add = (accumulate > 0 && accumulate < 4) || (accumulate >= 4 && ((accumulate >> (c < n0 ? 0 : 1)) & 1) != 0);
+    *dst = add ? *dst + v : (accumulate ? 0.f + v : v);
 }
 
 // Up to COLSUM_MULTI_MAX column-sum problems as ONE launch (blockIdx.y = problem): the postponed parameter-gradient reductions of a layer's
@@ -284,7 +287,8 @@ extern "C" int svsr_colsum_rows_multi(const void* entries, int n, hipStream_t st
 extern "C" int svsr_colsum_rows(const float* ws, int nrows, int64_t ld, float* out0, int64_t n0, float* out1, int64_t n1, int accumulate,
                                 float scale, hipStream_t stream) {
     const long n = (long)n0 + (long)n1;
-    if (nrows < 0 || n <= 0 || ld < n || (n1 > 0 && out1 == nullptr) || out0 == nullptr) return SVSR_ERR_ARG;
+    if (nrows < 0 || n <= 0 || ld < n || (n1 > 0 && out1 == nullptr) || out0 == nullptr || accumulate < 0 || accumulate > 7)
+        return SVSR_ERR_ARG;
     // many columns, few rows (split-K slabs): one thread per column.  Few columns, many rows (statistics, losses): row lanes.
 #define SVSR_COLSUM(CL_) hipLaunchKernelGGL(k_colsum<CL_>, dim3((unsigned)((n + CL_ - 1) / CL_)), dim3(256), 0, stream, ws, nrows, (long)ld, out0, (long)n0, out1, (long)n1, accumulate, scale)
     if (nrows <= 8 || n >= 65536) SVSR_COLSUM(256);

@@ -14,6 +14,7 @@
 // (runtime.hip) adds the slabs into dW in a fixed order (reproducible gradients).
 
 #include "common.h"
+#include "../../include/syncvsr_hip.h"
 
 #define W3_CH 128         // padded positions per chunk
 #define W3_PITCH 96        // bf16 elements per LDS row: 192 B = 48 banks, so the 4 rows a 32-lane ds_read_b64_tr_b16 group touches
@@ -33,6 +34,7 @@ struct Wgrad3Args {
     float inv_q, inv_wp;
     int chunks_per_block, total_chunks;
     int P, Ptot;           // dense form: real pixels per image, in all
+    int add;               // 1: dW is loaded and added to; 0: the launch stores 0.f + sum (first writer of dW this step)
 };
 
 // Slab format: a workgroup's nine 64 x 64 tiles leave in MFMA FRAGMENT layout — float4 group ((tap * 4 + wave) * 4 + rq) * 64 + lane holds
@@ -235,13 +237,14 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_wgrad3x3_halo(cons
         for (int r = 0; r < 16; ++r) {
             const int co = co0 + wco + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
             float* d = dwp + ((long)co * 9 + tap0 + t) * p.Ci + ci;
-            *d += acc[t][r];
+            *d = (p.add ? *d : 0.f) + acc[t][r];
         }
     }
 }
 
 // dW[co][t][ci] += sum over the splits (in split order) of a task's tiles.  grid (9 * 16 blocks of 64 float4 groups, tasks, problems)
-__global__ __launch_bounds__(256) void k_wgrad3_reduce(const float* __restrict__ part, const Wgrad3Multi m, int splits, int Ci, int ci_tiles) {
+// add == 0: the launch is the first writer of dW this step and stores 0.f + sum (no load of the destination)
+__global__ __launch_bounds__(256) void k_wgrad3_reduce(const float* __restrict__ part, const Wgrad3Multi m, int splits, int Ci, int ci_tiles, int add) {
     __shared__ f32x4 sred[4][64];
     const int gl = threadIdx.x & 63, sl = threadIdx.x >> 6;
     const int g = blockIdx.x * 64 + gl;
@@ -275,7 +278,7 @@ __global__ __launch_bounds__(256) void k_wgrad3_reduce(const float* __restrict__
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         float* d = dw + ((long)(co + k) * 9 + t) * Ci + ci;
-        *d += a[k];
+        *d = (add ? *d : 0.f) + a[k];
     }
 }
 
@@ -354,16 +357,23 @@ static int w3_launch(const Wgrad3Args& a0, const Wgrad3Multi& m, int n, const W3
     else hipLaunchKernelGGL((k_wgrad3x3_halo<4, false>), dim3(pl.splits, pl.tasks, n), dim3(256), lds, stream, a, m);
     int rc = svsr_check_launch();
     if (rc != SVSR_OK || pl.splits <= 1) return rc;
-    hipLaunchKernelGGL(k_wgrad3_reduce, dim3(W3_TILE_FLOATS / 4 / 64, pl.tasks, n), dim3(256), 0, stream, (const float*)part, m, pl.splits, a.Ci, a.Ci >> 6);
+    hipLaunchKernelGGL(k_wgrad3_reduce, dim3(W3_TILE_FLOATS / 4 / 64, pl.tasks, n), dim3(256), 0, stream, (const float*)part, m, pl.splits, a.Ci, a.Ci >> 6, a.add);
     return svsr_check_launch();
 }
 
 extern "C" int svsr_conv3x3_wgrad(const void* x, const void* dy, float* dw, int Nimg, int H, int W, int Ci, int Co, float* part,
                                   int64_t part_floats, hipStream_t stream) {
+    return svsr_conv3x3_wgrad_v2(x, dy, dw, Nimg, H, W, Ci, Co, part, part_floats, SVSR_GRAD_ADD_DW, stream);
+}
+
+/* the same with the store / add mode of dw (include/syncvsr_hip.h SVSR_GRAD_ADD_DW) */
+extern "C" int svsr_conv3x3_wgrad_v2(const void* x, const void* dy, float* dw, int Nimg, int H, int W, int Ci, int Co, float* part,
+                                     int64_t part_floats, int mode, hipStream_t stream) {
+    if (mode != 0 && mode != SVSR_GRAD_ADD_DW) return SVSR_ERR_ARG;
     Wgrad3Args a;
     const int rc0 = w3_fill_args(a, Nimg, H, W, Ci, Co);
     if (rc0 != SVSR_OK) return rc0;
-    a.x = (const bf16_t*)x; a.dy = (const bf16_t*)dy; a.dw = dw;
+    a.x = (const bf16_t*)x; a.dy = (const bf16_t*)dy; a.dw = dw; a.add = mode != 0;
     Wgrad3Multi m{};
     m.x[0] = a.x; m.dy[0] = a.dy; m.dw[0] = dw;
     return w3_launch(a, m, 1, w3_plan(Nimg, H, W, Ci, Co), part, part_floats, stream);

@@ -320,9 +320,10 @@ class TrainStep:
         return True
 
     def _zero_grads_early(self, st) -> None:
-        """The flat gradient buffer is zeroed when the step BEGINS, on the side stream (behind the previous step's optimiser, which is the
+        """The flat gradient buffer's zero-fill — the whole buffer, or with a first-touch map (_coverage) only the ranges no store-mode writer
+        covers (LRW: 1.3 of 128 MB; the covered spans' first writers store) — is issued when the step BEGINS, on the side stream (behind the previous step's optimiser, which is the
         last reader; ahead of this step's weight gradients, the first writers there; the model joins the side stream before its encoder
-        runs, long before the backward's main-stream writers): the 128 MB (LRW) / 1 GB (LRS) fill leaves the main stream, where it sat in front
+        runs, long before the backward's main-stream writers): the fill (whole buffer: 128 MB LRW / 1 GB LRS) leaves the main stream, where it sat in front
         of the backward (17 / 140 us).  The backward's own zero_grad() then finds `grad_clean` set and does nothing."""
         model = self.model
         # (a step that aborted between its backward and its optimiser — an exception in the training loop — must not leave its handshake
@@ -331,8 +332,27 @@ class TrainStep:
         # no collective between the backward and the clip: the model may sum the squares of every gradient but the last while that one is
         # computed (set per step: two TrainSteps may drive one model, each with its own optimiser state)
         model._early_sumsq = self.opt_state if self.dp is None else None
-        model._side.run(lambda: ops.memset(st.grad, 0))
+        cov = self._coverage(st)
+        if cov is None:
+            model._side.run(lambda: ops.memset(st.grad, 0))
+        else:
+            # only what no store-mode writer covers is filled (one launch over the holes); the covered spans' first writers store
+            model._side.run(cov.fill)
+            cov.begin()
         st.grad_clean = True
+
+    def _coverage(self, st) -> Optional["ops.GradCoverage"]:
+        """The first-touch map of this model's gradient buffer (ops.GradCoverage), or None where the whole-buffer fill stays: models that declare
+        no spans (model.grad_store_spans: the x-transformers encoder with its layer drop), ops.GRAD_STORE off (tests: the all-add reference).  Used by the steps of
+        accumulate = 1 only: a window's micro-steps share one recorded list, whose frozen modes cannot tell the first micro-step from the rest."""
+        if not ops.GRAD_STORE or not hasattr(self.model, "grad_store_spans"):
+            return None
+        key, cov = self.__dict__.get("_cover", (None, None))
+        if key != st.grad.data_ptr():
+            spans = self.model.grad_store_spans(st.offsets, st.phys)
+            cov = ops.GradCoverage(st.grad, spans) if spans else None
+            self._cover = (st.grad.data_ptr(), cov)
+        return cov
 
     def _optimizer(self, st) -> None:
         """Global-norm clip + AdamW + bf16 shadows.  With the model's side stream in use the update is SPLIT: the visual front-end's weights
@@ -342,6 +362,11 @@ class TrainStep:
         before state_dict(); the step counter advances behind the last range."""
         model = self.model
         model._early_sumsq = None        # (a backward outside a step must not write this optimiser's state)
+        stale = ops.end_grad_coverage()
+        if stale:
+            raise RuntimeError(f"{len(stale)} gradient ranges planned as first-touch stores had no writer in this step (first: elements "
+                               f"[{stale[0][0]}, {stale[0][1]})): their content is the previous step's — model.grad_store_spans is out of step "
+                               f"with the backward")
         if st.sumsq_head:
             # two ranges, always the same two (one association whatever ran early): [head, n) -> partial sums 0..1022 — already summed on the
             # side stream beside the stem's weight gradient when the model could (model._early_sumsq) — and the stem weight -> partial 1023
@@ -570,6 +595,7 @@ class TrainStep:
             # backward would write partial sums into it and the next optimiser step would trust them)
             self.model._early_sumsq = None
             self.model.store().__dict__.pop("sumsq_tail_done", None)
+            ops.end_grad_coverage()      # (and the next backward outside a step adds, as it always did)
             if self.window.n > 1:          # the window is abandoned (class docstring): the next step() starts a new one and zero-fills
                 self.window.abort()
                 self.model.accumulate_into_grads(False)

@@ -480,6 +480,19 @@ class E2E(nn.Module):
         self.direct_constants(dev)
         return self._g_consts
 
+    def grad_store_spans(self, offsets: dict, phys: dict) -> list:
+        """[lo, hi) element ranges of the flat gradient buffer whose first writer in a backward pass is a weight-gradient launch with a store
+        mode (ops.GradCoverage; model.TransformerLightningModule.grad_store_spans): every tensor of kind `linear_w` — all of them are written
+        by _lin_bwd (ops.linear_wgrad / linear_wgrad_group; fused projections are one launch over adjacent spans) — and the trunk's
+        convolutions (model._conv_wgrad), one writer each, unless stored with pads.  The stem, the depthwise convolutions, the position
+        biases, the decoder's embedding and every 1-D tensor stay with the zero-fill."""
+        spans = []
+        for n, shape, kind in self._specs:
+            if (kind == "linear_w" or (kind == "conv" and len(shape) == 4)) and tuple(phys[n]) == tuple(offsets[n][2]):
+                o, numel, _ = offsets[n]
+                spans.append((o, o + numel))
+        return spans
+
     def accumulate_into_grads(self, on: bool = True) -> None:
         """The "do not zero" switch of the backward (as model.TransformerLightningModule.accumulate_into_grads): off, every backward() zeroes
         the flat gradient buffer before it writes; on, the following backward() calls ADD into it — `(loss / N).backward()` per micro-batch

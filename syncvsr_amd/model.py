@@ -411,6 +411,33 @@ class TransformerLightningModule(nn.Module):
         per micro-step and leaves it off."""
         self._keep_grads = bool(on)
 
+    def grad_store_spans(self, offsets: dict, phys: dict) -> list:
+        """[lo, hi) element ranges of the flat gradient buffer whose first writer in a backward pass is a weight-gradient launch with a store
+        mode (ops.GradCoverage): the trunk's convolutions (ops.conv2d_wgrad) and, with the HF encoder, its dense layers and the two heads
+        (ops.linear_wgrad / linear_wgrad_group; query | key | value are ONE launch over their adjacent storage).  Each has exactly one writer
+        per backward.  Tensors stored with pads (the launches write the logical corner only; pads must stay zero) are left to the zero-fill, and
+        so is everything else: the stem's weight, the embeddings, every 1-D tensor.  The x-transformers encoder declares nothing — layer drop
+        leaves whole blocks without a writer — and keeps the whole-buffer fill."""
+        if self.encoder_type != "huggingface":
+            return []
+        names = [(n, 1) for n, s, k in self._specs if k == "conv" and len(s) == 4]
+        for i in range(self.layers):
+            p = f"encoder.encoder.layer.{i}"
+            names += [(f"{p}.attention.self.query.weight", 3), (f"{p}.attention.output.dense.weight", 1), (f"{p}.intermediate.dense.weight", 1),
+                      (f"{p}.output.dense.weight", 1)]
+        names += [("audio_projection.weight", 1), ("category_classifier.weight", 1)]
+        spans = []
+        for n, mult in names:
+            o, numel, shape = offsets[n]
+            if tuple(phys[n]) != tuple(shape):
+                continue
+            if mult == 3:       # key and value follow query in storage
+                kv = [offsets[n.replace("query", w)] for w in ("key", "value")]
+                if [e[0] for e in kv] != [o + numel, o + 2 * numel] or any(tuple(phys[n.replace("query", w)]) != tuple(e[2]) for w, e in zip(("key", "value"), kv)):
+                    continue
+            spans.append((o, o + mult * numel))
+        return spans
+
     def train_step_direct(self, videos, audio_tokens, labels, word_mask) -> dict[str, torch.Tensor]:
         """forward + backward of loss_total WITHOUT autograd: the same tape functions `forward()` + `loss_total.backward()` run,
         called directly, with loss_total and the two loss weights formed on the device.  Inputs as prepare_batch returns them.

@@ -5,6 +5,7 @@ libsyncvsr_hip.so on the current HIP stream.  Tensors are NHWC bf16 activations 
 """
 from __future__ import annotations
 
+import bisect
 import ctypes
 import os
 import struct
@@ -454,6 +455,117 @@ def memset(t: torch.Tensor, value: int = 0) -> None:
         _REC.memset(t.data_ptr(), value, nbytes, stream)
 
 
+# --------------------------------------------------------------------------------------------------
+# first touch stores: which ranges of the flat gradient buffer need no zero-fill
+# --------------------------------------------------------------------------------------------------
+GRAD_STORE = True          # False: whole-buffer zero-fill, every writer adds (the behaviour before first-touch stores)
+GRAD_FILL_NAN = False      # tests only (a step list or HIP graph recorded while it is set carries the whole-buffer NaN fill in every replay: never reuse one): the whole buffer is filled with NaNs ahead of the step's zero-fill — a range that is planned as stored but read would show
+
+
+class GradCoverage:
+    """Per-step bookkeeping of the flat fp32 gradient buffer `grad` for engine.TrainStep.  `spans` = [lo, hi) element ranges (whole tensors,
+    16-byte aligned starts, no overlap) whose FIRST writer of a step is a weight-gradient launch with a store mode (igemm_wgrad, conv2d_wgrad,
+    linear_wgrad_group): that launch stores 0.f + sum instead of adding to zeros, later writers of the range in the same step add.  Everything
+    else — `holes`: 1-D tensors, pads, tensors whose writers only add — is zero-filled by ONE svsr_fill_ranges launch per step (fill()).
+    begin() arms the map for a step; the wrappers ask touch(); end() returns the planned spans no launch stored (must be empty: their
+    gradient would be last step's).  A launch is matched to a span by its exact [lo, hi), or to a run of adjacent spans it tiles exactly: one that only overlaps a planned span (a
+    layer's weight written in pieces, query / key / value as three launches) would add onto memory nobody zeroed, so touch() raises before
+    that launch is issued.  Beyond that, TrainStep's check of end() — after the step's kernels are enqueued, before the optimiser's; in
+    native mode at record time only, which is enough because a replay repeats the recorded launches — is the only protection."""
+
+    def __init__(self, grad: torch.Tensor, spans):
+        self.grad, self.base, self.numel = grad, grad.data_ptr(), grad.numel()
+        self.spans, self.holes = self.plan(spans, self.numel)
+        self._planned = set(self.spans)
+        self._los = [lo for lo, _ in self.spans]
+        self._ranges = (ctypes.c_int64 * (2 * max(1, len(self.holes))))(*[v for h in self.holes for v in h])
+        self._touched: set = set()
+
+    @staticmethod
+    def plan(spans, numel: int) -> tuple:
+        """-> (sorted spans, holes): holes = the complement of the spans in [0, numel), each hole's start rounded DOWN to a multiple of 4
+        (the fill runs before the step's first store: up to three elements at the end of a span are zeroed first, then stored)."""
+        spans = sorted({(int(lo), int(hi)) for lo, hi in spans})
+        holes, at = [], 0
+        for lo, hi in spans:
+            if lo % 4 or lo < at or hi <= lo or hi > numel:
+                raise ValueError(f"gradient span [{lo}, {hi}) is misaligned, empty, overlaps its neighbour or leaves the buffer")
+            if lo > at:
+                holes.append((at // 4 * 4, lo))
+            at = hi
+        if numel % 4:
+            raise ValueError("the flat gradient buffer is a multiple of 4 elements")
+        if at < numel:
+            holes.append((at // 4 * 4, numel))
+        return spans, holes
+
+    def hole_elems(self) -> int:
+        return sum(hi - lo for lo, hi in self.holes)
+
+    def fill(self) -> None:
+        """The step's zero-fill on the current stream: the holes only."""
+        if GRAD_FILL_NAN:
+            _call("svsr_fill_f32", self.base, self.numel, float("nan"), _stream())
+        if self.holes:
+            _call("svsr_fill_ranges", self.base, self.numel, self._ranges, len(self.holes), 0, _stream())
+
+    def begin(self) -> None:
+        global _COVER
+        self._touched = set()
+        _COVER = self
+
+    def touch(self, ptr: int, n: int) -> int:
+        """1 (add) or 0 (store: the first writer of a planned span this step) for a launch that writes n floats at `ptr`."""
+        lo = (ptr - self.base) // 4
+        key = (lo, lo + n)
+        if key not in self._planned:
+            # one launch over several adjacent tensors (query | key | value, key | value of a source attention): it must tile whole planned
+            # spans exactly, and they share one fate — all stored now, or all written before (add)
+            i = bisect.bisect_left(self._los, lo)
+            run, at = [], lo
+            while i + len(run) < len(self.spans) and self.spans[i + len(run)][0] == at and self.spans[i + len(run)][1] <= lo + n:
+                at = self.spans[i + len(run)][1]
+                run.append(self.spans[i + len(run)])
+            if len(run) > 1 and at == lo + n:
+                done = [s in self._touched for s in run]
+                if all(done):
+                    return 1
+                if any(done):
+                    raise RuntimeError(f"a weight-gradient launch writes elements [{lo}, {lo + n}) of the gradient buffer: some of the first-touch spans "
+                                       f"it covers were written earlier in this step, others not — it can neither add nor store")
+                self._touched.update(run)
+                return 0
+            i = bisect.bisect_right(self._los, lo)       # spans are disjoint: only spans[i - 1] and spans[i] can overlap [lo, lo + n)
+            for s in self.spans[max(0, i - 1) : i + 1]:
+                if s[0] < lo + n and lo < s[1]:
+                    raise RuntimeError(f"a weight-gradient launch writes elements [{lo}, {lo + n}) of the gradient buffer, part of the first-touch span "
+                                       f"[{s[0]}, {s[1]}) but not all of it: the span is not zero-filled, so the launch can neither add nor store")
+            return 1
+        if key in self._touched:
+            return 1
+        self._touched.add(key)
+        return 0
+
+    def end(self) -> list:
+        global _COVER
+        if _COVER is self:
+            _COVER = None
+        return sorted(self._planned - self._touched)
+
+
+_COVER: Optional[GradCoverage] = None
+
+
+def _grad_add(dw: torch.Tensor, n: int) -> int:
+    """SVSR_GRAD_ADD_DW bit of a weight-gradient launch writing n floats at dw: 1 unless an armed GradCoverage says this is the first
+    writer of a planned span (outside a TrainStep nothing is armed: every launch adds, as `dw += ...` always meant)."""
+    return 1 if _COVER is None else _COVER.touch(dw.data_ptr(), n)
+
+
+def end_grad_coverage() -> list:
+    return [] if _COVER is None else _COVER.end()
+
+
 def zeros(shape, dtype, device) -> torch.Tensor:
     t = torch.empty(shape, dtype=dtype, device=device)
     memset(t, 0)
@@ -594,10 +706,15 @@ def igemm_fwd(plan: Plan, inp: torch.Tensor, wt: torch.Tensor, out: torch.Tensor
 
 
 def igemm_wgrad(plan: WPlan, x: torch.Tensor, dyp: torch.Tensor, dw: torch.Tensor, *, Nimg: int, in_pix: int, Ci: int, in_pitch: int,
-                Co: int, out_pix: int, out_pitch: int, wt_taps: int = 1, db: Optional[torch.Tensor] = None, flops: float = 0.0) -> None:
+                Co: int, out_pix: int, out_pitch: int, wt_taps: int = 1, db: Optional[torch.Tensor] = None, flops: float = 0.0,
+                mode: Optional[int] = None) -> None:
+    """mode (SVSR_GRAD_ADD_DW = 1 | SVSR_GRAD_ADD_DB = 2 of include/syncvsr_hip.h): None = decided here — dw by the armed GradCoverage,
+    else added to; db always added to (bias gradients live in the zero-filled 1-D tail of the buffer)."""
     part = scratch(plan.part_floats) if plan.part_floats else None
-    _call("svsr_igemm_wgrad", _p(x), _p(dyp), _p(dw), _p(db), plan.words.data_ptr(), plan.meta, Nimg, in_pix, Ci, in_pitch, Co, out_pix,
-          out_pitch, wt_taps, _p(part), plan.part_floats, _stream(), label=plan.label, flops=flops)
+    if mode is None:
+        mode = _grad_add(dw, Co * wt_taps * Ci) | 2
+    _call("svsr_igemm_wgrad_v2", _p(x), _p(dyp), _p(dw), _p(db), plan.words.data_ptr(), plan.meta, Nimg, in_pix, Ci, in_pitch, Co, out_pix,
+          out_pitch, wt_taps, _p(part), plan.part_floats, mode, _stream(), label=plan.label, flops=flops)
 
 
 class _WgradProblem(ctypes.Structure):
@@ -627,7 +744,7 @@ def _group_table(nbytes: int, device) -> torch.Tensor:
 def linear_wgrad_group(problems: Sequence[dict]) -> None:
     """problems: keyword arguments of linear_wgrad calls (x, dy, dw, rows, K, N, x_pitch, dy_pitch, seq, db).  Those whose plan has no K
     split on 64-wide tiles go out as one svsr_igemm_wgrad_group launch; the others (none at the LRW shapes) as launches of their own."""
-    grouped, keep = [], []
+    grouped, keep, modes = [], [], []
     for q in problems:
         rows, K, N, seq, db = q["rows"], q["K"], q["N"], q.get("seq"), q.get("db")
         if seq is None:
@@ -641,13 +758,15 @@ def linear_wgrad_group(problems: Sequence[dict]) -> None:
         grouped.append(_WgradProblem(_p(q["x"]), _p(q["dy"]), _p(q["dw"]), _p(db), plan.words.data_ptr(), ctypes.addressof(plan.meta),
                                      geo[0], geo[1], K, q["x_pitch"], N, geo[2], q["dy_pitch"], 1))
         keep.append(plan)
+        modes.append(_grad_add(q["dw"], N * K) | 2)
     if not grouped:
         return
     arr = (_WgradProblem * len(grouped))(*grouped)
     nbytes = int(_lib.load().svsr_igemm_wgrad_group_bytes(len(grouped)))
     table = _group_table(nbytes, problems[0]["x"].device)
     flops = sum(2.0 * q["rows"] * q["K"] * q["N"] for q in problems)
-    _call("svsr_igemm_wgrad_group", arr, len(grouped), _p(table), nbytes, _stream(), label="k_igemm_wgrad_group<64,3>", flops=flops)
+    _call("svsr_igemm_wgrad_group_v2", arr, (ctypes.c_int * len(modes))(*modes), len(grouped), _p(table), nbytes, _stream(),
+          label="k_igemm_wgrad_group<64,3>", flops=flops)
 
 
 def conv_out_size(n: int, k: int, stride: int, pad: int) -> int:
@@ -782,19 +901,19 @@ def bn_bwd_from_stats(g, x, mean, rstd, gamma, stats, coef, dgamma, dbeta) -> to
     return dx
 
 
-def conv2d_wgrad(x: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor, k: int, stride: int, pad: int, use_tr: bool = True) -> None:
-    """dw fp32 [Co][k][k][Ci] += sum dy[n,y,x,co] * x[n, y*s+kh-pad, x*s+kw-pad, ci]."""
+def conv2d_wgrad(x: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor, k: int, stride: int, pad: int, use_tr: bool = True, mode: Optional[int] = None) -> None:
+    """dw fp32 [Co][k][k][Ci] += sum dy[n,y,x,co] * x[n, y*s+kh-pad, x*s+kw-pad, ci]  (mode 0: = 0.f + sum, see igemm_wgrad)."""
     N, H, W, Ci = x.shape
     _, Ho, Wo, Co = dy.shape
     if HALO_WGRAD and use_tr and k == 3 and stride == 1 and pad == 1 and W <= 29 and H * W >= 100 and Ci % 64 == 0 and Co % 64 == 0:
         # all nine taps in one pass over zero-padded coordinates (wgrad3x3.hip)
         _, nfl = _query("svsr_conv3x3_wgrad_plan", N, H, W, Ci, Co)
         part = scratch(nfl) if nfl else None
-        _call("svsr_conv3x3_wgrad", _p(x), _p(dy), _p(dw), N, H, W, Ci, Co, _p(part), nfl, _stream(), label="k_wgrad3x3_halo",
-              flops=2.0 * N * H * W * Co * Ci * 9)
+        _call("svsr_conv3x3_wgrad_v2", _p(x), _p(dy), _p(dw), N, H, W, Ci, Co, _p(part), nfl, _grad_add(dw, Co * 9 * Ci) if mode is None else mode & 1, _stream(),
+              label="k_wgrad3x3_halo", flops=2.0 * N * H * W * Co * Ci * 9)
         return
     igemm_wgrad(wgrad_conv_plan(N, H, W, Ci, Co, k, stride, pad), x, dy, dw, Nimg=N, in_pix=H * W, Ci=Ci, in_pitch=Ci, Co=Co,
-                out_pix=Ho * Wo, out_pitch=Co, wt_taps=k * k, flops=2.0 * N * Ho * Wo * Co * Ci * k * k)
+                out_pix=Ho * Wo, out_pitch=Co, wt_taps=k * k, flops=2.0 * N * Ho * Wo * Co * Ci * k * k, mode=mode)
 
 
 def halo_wgrad_ok(x: torch.Tensor, dy: torch.Tensor, k: int, stride: int, pad: int) -> bool:
@@ -884,7 +1003,7 @@ def linear_dgrad_relu(dy: torch.Tensor, w16t: torch.Tensor, *, rows: int, N: int
 
 
 def linear_wgrad(x: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor, *, rows: int, K: int, N: int, x_pitch: int, dy_pitch: int,
-                 seq: Optional[tuple[int, int, int]] = None, use_tr: bool = True, db: Optional[torch.Tensor] = None) -> None:
+                 seq: Optional[tuple[int, int, int]] = None, use_tr: bool = True, db: Optional[torch.Tensor] = None, mode: Optional[int] = None) -> None:
     """dw fp32 [N][K] += dy[rows, N]^T @ x[rows, K];  db fp32 [N] += column sums of dy (bias gradient), if given.
     (`use_tr` is accepted for the callers' sake: the generic kernel always builds its fragments with transpose reads.)"""
     if seq is None:
@@ -892,7 +1011,7 @@ def linear_wgrad(x: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor, *, rows: i
     else:
         S, s0, n = seq
         plan, geo = wgrad_rows_plan(rows // n, n, s0, 0, K, N, db is not None), dict(Nimg=rows // n, in_pix=S, out_pix=n)
-    igemm_wgrad(plan, x, dy, dw, Ci=K, in_pitch=x_pitch, Co=N, out_pitch=dy_pitch, db=db, flops=2.0 * rows * N * K, **geo)
+    igemm_wgrad(plan, x, dy, dw, Ci=K, in_pitch=x_pitch, Co=N, out_pitch=dy_pitch, db=db, flops=2.0 * rows * N * K, mode=mode, **geo)
 
 
 # --------------------------------------------------------------------------------------------------
