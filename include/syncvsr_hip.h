@@ -525,6 +525,24 @@ int svsr_ls_loss_bwd(const float* logits, int ld, const int64_t* target, int R, 
  * advances once per step.  drop_seed == null or p == 0 disables it. */
 int svsr_scale_bf16(const void* x, void* y, int64_t n, float alpha, const unsigned* drop_seed, unsigned drop_site, float drop_p, hipStream_t stream);
 
+/* ---- Transformer language-model scorer of the beam search (lrs_lm.hip) -----------------------------------------------
+ * Replaces the cached self-attention of TransformerLM.score / batch_score (reference LRS/video/espnet/nets/pytorch_backend/lm/
+ * transformer.py:176-250 -> transformer/encoder.py:291-319 -> encoder_layer.py:98-120 -> attention.py:38-108), whose cache is
+ * re-stacked per hypothesis and re-projected over the whole prefix every step.  Here the state of a search is, per layer, an
+ * APPEND-ONLY pool of bf16 rows q | k | v (pitch elements per row, >= 3 * H * 64) shared by all hypotheses, plus ONE int32 row table
+ * [n][table_pitch]: entry p of row b names the pool row of position p of hypothesis b.
+ *   e >= 0: row e, visible as a key;  e == -1: no row (never a key; as a query: zeros);  e <= -2: row -e - 2, a query but never a key
+ *   (the reference's key mask `ys != 0`, lm/transformer.py:135-138).  Rows outside [0, pool_rows) count as e == -1.
+ * svsr_mha_table_fwd: for hypothesis b and query position j in [L - Lq, L): q of row table[b][j] against the keys / values of rows
+ * table[b][0..j] (causal by construction), softmax in fp32 (scores * scale), ctx bf16 [n * Lq][ctx_pitch] (H * 64 written per row).
+ * Lq = 1 is a beam step, Lq = L the prefix pass.  A query without a visible key writes zeros.  One wave per (b, j, head); it gathers
+ * (j + 1) * 256 bytes: n * Lq * H * L * 256 at most per launch, no contraction — latency / gather bound by construction.
+ * svsr_lm_embed_fwd: the tail of the LM's input layer (encoder.py:143-150 after Embedding + Linear): out bf16 [R][D] =
+ * relu(LayerNorm(x[r]; gamma, beta, eps)) * scale + pe[pos[r]], x bf16 rows of pitch x_pitch, pe fp32 [pe_rows][D], pos int32 [R]
+ * (clamped into the table), D % 8 == 0 up to 2048. */
+int svsr_mha_table_fwd(const void* pool, int pool_rows, int64_t pitch, const int* table, int table_pitch, int n, int Lq, int L, int H, float scale, void* ctx, int64_t ctx_pitch, hipStream_t stream);
+int svsr_lm_embed_fwd(const void* x, int64_t x_pitch, const float* gamma, const float* beta, const float* pe, int pe_rows, const int* pos, int R, int D, float eps, float scale, void* out, hipStream_t stream);
+
 /* ---- native step enqueuer (steplist.hip; host code, launches nothing of its own) -----------------------------------
  * Stands where the reference's per-step host loop stands (pl.Trainer.fit -> training_step, LRW/video/src/train.py:23-45,
  * lightning.py:194-202): ONE host call per optimisation step instead of one per launch.  A list records, once, the launch

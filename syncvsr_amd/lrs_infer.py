@@ -384,13 +384,19 @@ class BatchBeamSearch:
 
 def get_beam_search_decoder(model, token_list, rnnlm=None, rnnlm_conf=None, penalty=0, ctc_weight: float = 0.1, lm_weight: float = 0.0,
                             beam_size: int = 40, scorers: Optional[dict] = None) -> BatchBeamSearch:
-    """LRS/video/lightning.py:237-279.  Language-model rescoring (`rnnlm`) is not part of this package: the reference's default
-    passes none (lm_weight 0.0)."""
-    if rnnlm:
-        raise NotImplementedError("language-model scorers are outside this package (the reference's test loop passes rnnlm=None)")
+    """LRS/video/lightning.py:237-279.  `rnnlm`: a `lrs_lm.TransformerLM`, or the path of a transformer-LM state dict with `rnnlm_conf` the
+    path of its model.json (default: next to it) or a mapping of its arguments; it scores under "lm" with weight `lm_weight` (and is
+    dropped when that is 0, beam_search.py:73-76).  The reference's RNN language models are not part of this package."""
     sos = eos = model.odim - 1
     scorers = dict(scorers) if scorers is not None else model.scorers()
-    scorers["lm"] = None
+    if not rnnlm:
+        lm = None
+    else:
+        from .lrs_lm import load_lm
+
+        lm = load_lm(len(token_list), rnnlm, rnnlm_conf)
+        lm.beam_hint = int(beam_size)
+    scorers["lm"] = lm
     scorers["length_bonus"] = LengthBonus(len(token_list))
     weights = {"decoder": 1.0 - ctc_weight, "ctc": ctc_weight, "lm": lm_weight, "length_bonus": penalty}
     return BatchBeamSearch(beam_size=beam_size, vocab_size=len(token_list), weights=weights, scorers=scorers, sos=sos, eos=eos,

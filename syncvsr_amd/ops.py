@@ -1774,3 +1774,32 @@ def w2v_quantize(feat: torch.Tensor, R: int, F: int, keep: int, gamma, beta, eps
     [R / F][keep][2] (frames t < keep of every clip of F frames; svsr_w2v_quantize)."""
     _call("svsr_w2v_quantize", _p(feat), R, F, keep, _p(gamma), _p(beta), float(eps), _p(w16), _p(bias), _p(seed), int(site), _p(tok), _p(logits_out),
           _stream(), label="k_w2v_quantize", flops=2.0 * R * 512 * 640)
+
+
+# --------------------------------------------------------------------------------------------------
+# Transformer language-model scorer (csrc/lrs_lm.hip)
+# --------------------------------------------------------------------------------------------------
+def mha_table_fwd(pool: torch.Tensor, table: torch.Tensor, *, n: int, Lq: int, L: int, H: int, scale: float, pool_rows: Optional[int] = None,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pool bf16 [rows, pitch >= 3 * H * 64] (q | k | v per row), table int32 [n, >= L] -> ctx bf16 [n * Lq, H * 64]: query positions
+    L - Lq .. L - 1 of every hypothesis over the keys its table names (svsr_mha_table_fwd; entry encoding: include/syncvsr_hip.h)."""
+    assert pool.dtype == BF16 and pool.dim() == 2 and pool.stride(1) == 1 and table.dtype == torch.int32 and table.dim() == 2 and table.stride(1) == 1
+    assert table.shape[0] >= n and table.shape[1] >= L
+    rows = pool.shape[0] if pool_rows is None else int(pool_rows)
+    assert 0 < rows <= pool.shape[0]
+    D = H * 64
+    ctx = torch.empty((n * Lq, D), dtype=BF16, device=pool.device) if out is None else out
+    _call("svsr_mha_table_fwd", _p(pool), rows, pool.stride(0), _p(table), table.stride(0), n, Lq, L, H, float(scale), _p(ctx), ctx.stride(0), _stream(),
+          label="k_mha_table", flops=4.0 * n * Lq * L * D, nbytes=256.0 * n * Lq * H * L)
+    return ctx
+
+
+def lm_embed_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, pe: torch.Tensor, pos: torch.Tensor, D: int, eps: float, scale: float) -> torch.Tensor:
+    """x bf16 [R, >= D] -> bf16 [R, D] = relu(LayerNorm(x)) * scale + pe[pos] (svsr_lm_embed_fwd); pe fp32 [rows, D], pos int32 [R]."""
+    R = x.shape[0]
+    assert x.dtype == BF16 and x.stride(1) == 1 and pe.dtype == torch.float32 and pe.is_contiguous() and pe.shape[1] == D
+    assert pos.dtype == torch.int32 and pos.is_contiguous() and pos.numel() == R
+    out = torch.empty((R, D), dtype=BF16, device=x.device)
+    _call("svsr_lm_embed_fwd", _p(x), x.stride(0), _p(gamma), _p(beta), _p(pe), pe.shape[0], _p(pos), R, D, float(eps), float(scale), _p(out), _stream(),
+          label="k_lm_embed")
+    return out
