@@ -543,6 +543,35 @@ int svsr_scale_bf16(const void* x, void* y, int64_t n, float alpha, const unsign
 int svsr_mha_table_fwd(const void* pool, int pool_rows, int64_t pitch, const int* table, int table_pitch, int n, int Lq, int L, int H, float scale, void* ctx, int64_t ctx_pitch, hipStream_t stream);
 int svsr_lm_embed_fwd(const void* x, int64_t x_pitch, const float* gamma, const float* beta, const float* pe, int pe_rows, const int* pos, int R, int D, float eps, float scale, void* out, hipStream_t stream);
 
+/* ---- multi-clip beam search (lrs_search.hip; BatchBeamSearch.forward_clips of syncvsr_amd/lrs_infer.py) -----------------
+ * C clips advance through one search in lock step.  The n live hypotheses are rows grouped by clip: clip_of int32 [n] is non-decreasing,
+ * clip c owns rows row_lo[c] .. row_lo[c + 1] - 1 (row_lo int32 [C + 1]; an empty range: the clip has finished).
+ *
+ * svsr_beam_select: the selection of one search position (batch_beam_search.py:146-158 per clip), two launches.  Planes s0 .. s(nplanes-1)
+ * fp32 [n][ldv] with weights w0 .., run fp32 [n].  total[r][v] = ((((0 + w0 * s0[r][v]) + w1 * s1[r][v]) + ...) + run[r]), every product
+ * and sum rounded on its own (no FMA): bit for bit what `weighted = zeros; weighted += w_k * s_k; ...; weighted += run[:, None]` gives.
+ * Per clip the k_c = min(beam, rows_c * V) best (r, v) are written, best first, at output rows out_off[c] .. out_off[c] + k_c - 1
+ * (out_off int32 [C]; the caller knows rows_c and lays the outputs out compactly): prev int64 (global row r), tok int64 (v), total fp32,
+ * vals fp32 [nplanes][out_rows] (each plane's value at the winner), clip_out int32 (= clip_of[r]); count int32 [C] = k_c.  Order: higher
+ * total first, ties to the lower (row, token); NaN sorts above everything (torch.topk's rule).  The result is a pure function of the
+ * inputs: no atomics, no dependence on arrival.  max_rows >= the rows of the largest clip.  cand: workspace of
+ * C * svsr_beam_select_slices(V, beam, max_rows) * beam 64-bit words.  Bounds (SVSR_ERR_ARG; svsr_beam_select_slices returns 0):
+ * nplanes <= 4, beam <= 256, max_rows * V <= 2^20, and slices * beam <= 4096 with slices = ceil(max_rows * V / 4096) — beam 40 over 5,049
+ * units holds up to 82 rows per clip, the search never has more than `beam`.
+ *
+ * svsr_ctc_prefix_score_clips: svsr_ctc_prefix_score with logp fp32 [C][Tmax][ldp], tlen int32 [C], r_prev fp32 [n][Tmax][2]: hypothesis r
+ * walks the tlen[clip_of[r]] frames of its clip's posteriors, eos takes logaddexp of r_prev at that clip's last frame, frames
+ * tlen .. Tmax - 1 of r_new [n][S][Tmax][2] are -1e10, and nothing reads logp or r_prev beyond a clip's length.  A row whose clip is
+ * outside [0, C) or has no frame, and a candidate outside [0, V), score -1e10.
+ *
+ * svsr_mha_src_step_fwd: source attention of one query row per hypothesis: q bf16 [n] rows of q_pitch (H * 64 read), kv bf16
+ * [C * Tmax] rows of kv_pitch = k | v (2 * H * 64 read) projected once per clip; row r attends to rows clip_of[r] * Tmax + [0, tlen[clip]);
+ * softmax in fp32 (scores * scale); ctx bf16 [n] rows of ctx_pitch.  One wave per (row, head); it gathers tlen * 256 bytes. */
+int svsr_beam_select_slices(int V, int beam, int max_rows);
+int svsr_beam_select(const float* s0, const float* s1, const float* s2, const float* s3, float w0, float w1, float w2, float w3, int nplanes, int64_t ldv, const float* run, const int* clip_of, const int* row_lo, const int* out_off, int n, int C, int V, int beam, int max_rows, int out_rows, void* cand, int64_t* prev, int64_t* tok, float* total, float* vals, int* clip_out, int* count, hipStream_t stream);
+int svsr_ctc_prefix_score_clips(const float* logp, int ldp, const float* r_prev, const int64_t* last, const int64_t* ids, const int* clip_of, const int* tlen, float* r_new, float* psi, int C, int Tmax, int V, int n, int S, int out_len, int blank, int eos, hipStream_t stream);
+int svsr_mha_src_step_fwd(const void* q, int64_t q_pitch, const void* kv, int64_t kv_pitch, const int* clip_of, const int* tlen, int C, int Tmax, int n, int H, float scale, void* ctx, int64_t ctx_pitch, hipStream_t stream);
+
 /* ---- native step enqueuer (steplist.hip; host code, launches nothing of its own) -----------------------------------
  * Stands where the reference's per-step host loop stands (pl.Trainer.fit -> training_step, LRW/video/src/train.py:23-45,
  * lightning.py:194-202): ONE host call per optimisation step instead of one per launch.  A list records, once, the launch

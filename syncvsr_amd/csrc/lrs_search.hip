@@ -1,0 +1,344 @@
+// Multi-clip beam search of the LRS inference surface (syncvsr_amd/lrs_infer.py BatchBeamSearch.forward_clips), gfx950, wave64:
+//   * k_beam_select_slices / k_beam_select_merge: the selection step of one search position for every clip at once — the weighted
+//     sum of the scorers' planes, the running score, and the per-clip top `beam` (the torch statement: lrs_infer.beam_select_reference)
+//   * k_ctc_prefix_score_clips: k_ctc_prefix_score (lrs_misc.hip) with every hypothesis walking the frames of ITS clip
+//   * k_mha_src_step: source attention of one query row per hypothesis against the keys / values of its clip
+// No float atomics and no order that depends on arrival anywhere: every output is a pure function of the inputs.
+#include "common.h"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Selection.  Element (r, v) of clip c (rows lo_c .. hi_c - 1 of the planes, flat index f = (r - lo_c) * V + v) has the total
+//   t = ((((0 + w0 * s0[r][v]) + w1 * s1[r][v]) + ...) + run[r])          every product and sum rounded on its own (no FMA)
+// which is, operation for operation, what `weighted = zeros; weighted += w_k * s_k ...; weighted += score[:, None]` evaluates.
+// Order: higher t first, ties to the lower f.  Both are carried by ONE 64-bit key, key = ord(t) << 20 | (2^20 - 1 - f) with ord() the
+// usual monotone map of fp32 bits to unsigned (NaN above everything, as torch.topk sorts it): keys of one clip are distinct, so
+// "the k largest keys" is a set that no schedule can change.
+// Stage 1 (grid: slices x clips): a workgroup owns SL consecutive f, 256 threads hold BS_PER keys each in registers, and `k` rounds of a
+// workgroup-wide max (wave reduction by DPP shuffles, then 4 partials through LDS) peel off the slice's best min(k, slice) keys in order.
+// Stage 2 (grid: clips): the same rounds over the slices' candidates (at most BS_CAND); the winner's planes are read again for the
+// outputs, so the totals are recomputed, not decoded.
+// ---------------------------------------------------------------------------------------------------------------------
+#define BS_THREADS 256
+#define BS_PER 16
+#define BS_CAND (BS_THREADS * BS_PER)          // keys one workgroup ranks: the largest slice, and slices * beam of the merge
+#define BS_IDX_BITS 20
+#define BS_IDX_MASK ((1u << BS_IDX_BITS) - 1u)
+#define BS_MAX_PLANES 4
+
+struct BeamPlanes {
+    const float* s[BS_MAX_PLANES];
+    float w[BS_MAX_PLANES];
+    int n;
+};
+
+// (the library is built with -ffp-contract=fast, and neither `#pragma clang fp contract(off)` nor __fmul_rn keeps the compiler from fusing
+// these into v_fmac_f32 after inlining: the two instructions are named, so each rounds on its own)
+__device__ __forceinline__ float mul_rn(float a, float b) { float r; asm volatile("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ float add_rn(float a, float b) { float r; asm volatile("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+
+__device__ __forceinline__ float beam_total(const BeamPlanes& p, const float* __restrict__ run, long ldv, int r, int v) {
+    float t = 0.f;
+#pragma unroll
+    for (int i = 0; i < BS_MAX_PLANES; ++i)
+        if (i < p.n) t = add_rn(t, mul_rn(p.w[i], p.s[i][(long)r * ldv + v]));
+    return add_rn(t, run[r]);
+}
+
+__device__ __forceinline__ unsigned beam_ord(float t) {
+    if (t != t) return 0xffffffffu;
+    const unsigned u = __float_as_uint(t);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long k) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)k, o, 64);
+        const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(k >> 32), o, 64);
+        const unsigned long long other = ((unsigned long long)hi << 32) | lo;
+        k = other > k ? other : k;
+    }
+    return k;
+}
+
+// the `rounds` largest of the workgroup's keys (0 = no key), in order, into win[0 .. rounds): every thread returns with win[] complete
+__device__ __forceinline__ void beam_rounds(unsigned long long (&key)[BS_PER], int rounds, unsigned long long* part, unsigned long long* win) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long cur = 0;
+#pragma unroll
+    for (int i = 0; i < BS_PER; ++i) cur = key[i] > cur ? key[i] : cur;
+    for (int k = 0; k < rounds; ++k) {
+        const unsigned long long wm = wave_max_u64(cur);
+        if (lane == 0) part[(k & 1) * 4 + wave] = wm;
+        __syncthreads();                                  // (part is double buffered: one barrier per round is enough)
+        unsigned long long best = part[(k & 1) * 4];
+#pragma unroll
+        for (int w = 1; w < BS_THREADS / 64; ++w) { const unsigned long long o = part[(k & 1) * 4 + w]; best = o > best ? o : best; }
+        if (threadIdx.x == 0) win[k] = best;
+        if (best != 0 && cur == best) {                   // keys are distinct: exactly one thread owns the winner
+            cur = 0;
+#pragma unroll
+            for (int i = 0; i < BS_PER; ++i) {
+                if (key[i] == best) key[i] = 0;
+                cur = key[i] > cur ? key[i] : cur;
+            }
+        }
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(BS_THREADS) void k_beam_select_slices(BeamPlanes p, const float* __restrict__ run, const int* __restrict__ row_lo,
+                                                                   long ldv, int V, int beam, int SL, int n,
+                                                                   unsigned long long* __restrict__ cand) {
+    __shared__ unsigned long long part[8];
+    __shared__ unsigned long long win[BS_CAND / 16];      // beam <= 256
+    const int c = blockIdx.y, g = blockIdx.x;
+    int lo = row_lo[c], hi = row_lo[c + 1];
+    lo = lo < 0 ? 0 : lo; hi = hi > n ? n : hi;           // (a damaged range cannot make the kernel leave the planes)
+    const long N = hi > lo ? (long)(hi - lo) * V : 0;
+    const long f0 = (long)g * SL;
+    if (f0 >= N) return;                                  // whole workgroups leave
+    const int len = (int)(N - f0 < SL ? N - f0 : SL);
+    unsigned long long key[BS_PER];
+#pragma unroll
+    for (int i = 0; i < BS_PER; ++i) {
+        const int j = i * BS_THREADS + threadIdx.x;       // consecutive lanes read consecutive tokens
+        key[i] = 0;
+        if (j < len) {
+            const unsigned f = (unsigned)f0 + (unsigned)j;                  // N <= 2^20: 32-bit index arithmetic
+            const int r = lo + (int)(f / (unsigned)V), v = (int)(f % (unsigned)V);
+            key[i] = ((unsigned long long)beam_ord(beam_total(p, run, ldv, r, v)) << BS_IDX_BITS) | (unsigned long long)(BS_IDX_MASK - (unsigned)f);
+        }
+    }
+    const int k = beam < len ? beam : len;
+    beam_rounds(key, k, part, win);
+    unsigned long long* out = cand + ((long)c * gridDim.x + g) * beam;
+    for (int i = threadIdx.x; i < k; i += BS_THREADS) out[i] = win[i];
+}
+
+__global__ __launch_bounds__(BS_THREADS) void k_beam_select_merge(BeamPlanes p, const float* __restrict__ run, const int* __restrict__ clip_of,
+                                                                  const int* __restrict__ row_lo, const int* __restrict__ out_off, long ldv, int V,
+                                                                  int beam, int SL, int G, int n, int out_rows,
+                                                                  const unsigned long long* __restrict__ cand, long* __restrict__ prev,
+                                                                  long* __restrict__ tok, float* __restrict__ total, float* __restrict__ vals,
+                                                                  int* __restrict__ clip_out, int* __restrict__ count) {
+    __shared__ unsigned long long part[8];
+    __shared__ unsigned long long win[BS_CAND / 16];
+    const int c = blockIdx.x;
+    int lo = row_lo[c], hi = row_lo[c + 1];
+    lo = lo < 0 ? 0 : lo; hi = hi > n ? n : hi;
+    const long N = hi > lo ? (long)(hi - lo) * V : 0;
+    const int k = (int)(N < beam ? N : beam);
+    if (threadIdx.x == 0) count[c] = k;
+    if (k == 0) return;
+    const int Gc = (int)((N + SL - 1) / SL);              // slices of this clip that hold elements (<= G)
+    unsigned long long key[BS_PER];
+#pragma unroll
+    for (int i = 0; i < BS_PER; ++i) {
+        const int j = i * BS_THREADS + threadIdx.x;       // candidate j = slice j / beam, rank j % beam
+        key[i] = 0;
+        const int g = j / beam, q = j - g * beam;
+        if (g < Gc && g < G) {
+            const long left = N - (long)g * SL;
+            const int len = (int)(left < SL ? left : SL);
+            if (q < (beam < len ? beam : len)) key[i] = cand[((long)c * G + g) * beam + q];
+        }
+    }
+    beam_rounds(key, k, part, win);
+    const int o0 = out_off[c];
+    for (int i = threadIdx.x; i < k; i += BS_THREADS) {
+        const int o = o0 + i;
+        if (o < 0 || o >= out_rows) continue;
+        const unsigned f = BS_IDX_MASK - (unsigned)(win[i] & BS_IDX_MASK);
+        if ((long)f >= N) continue;                       // (cannot happen with keys this launch pair made)
+        const int r = lo + (int)(f / (unsigned)V), v = (int)(f % (unsigned)V);
+        prev[o] = r;
+        tok[o] = v;
+        total[o] = beam_total(p, run, ldv, r, v);
+        for (int i2 = 0; i2 < p.n; ++i2) vals[(long)i2 * out_rows + o] = p.s[i2][(long)r * ldv + v];
+        clip_out[o] = clip_of[r];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// CTC prefix scores, one thread per (hypothesis, candidate) as k_ctc_prefix_score: hypothesis h belongs to clip c = clip_of[h] and walks
+// the Tc = tlen[c] frames of logp[c]; frames Tc .. Tmax - 1 of the new state are LOGZERO and nothing reads the padding of logp or r_prev.
+// ---------------------------------------------------------------------------------------------------------------------
+#define CTC_LOGZERO (-1.0e10f)
+__device__ __forceinline__ float lae(float a, float b) {
+    const float m = fmaxf(a, b);
+    return m + __logf(__expf(a - m) + __expf(b - m));
+}
+
+__global__ __launch_bounds__(256) void k_ctc_prefix_score_clips(const float* __restrict__ logp, const float* __restrict__ r_prev,
+                                                                const long* __restrict__ last, const long* __restrict__ ids,
+                                                                const int* __restrict__ clip_of, const int* __restrict__ tlen,
+                                                                float* __restrict__ r_new, float* __restrict__ psi, int C, int Tmax, int V, int ldp,
+                                                                int n, int S, int out_len, int blank, int eos) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)n * S) return;
+    const int h = (int)(idx / S), j = (int)(idx - (long)h * S);
+    float* rn_out = r_new + idx * Tmax * 2;
+    const int clip = clip_of[h];
+    int c = ids != nullptr ? (int)ids[(long)h * S + j] : j;
+    int T = (clip >= 0 && clip < C) ? tlen[clip] : 0;
+    T = T > Tmax ? Tmax : T;
+    if (T < 1 || c < 0 || c >= V) {                        // no clip / no such label: an impossible extension, never a stray read
+        for (int t = 0; t < Tmax; ++t) { rn_out[2 * t] = CTC_LOGZERO; rn_out[2 * t + 1] = CTC_LOGZERO; }
+        psi[idx] = CTC_LOGZERO;
+        return;
+    }
+    const float* lp = logp + (long)clip * Tmax * ldp;
+    const float* rp = r_prev + (long)h * Tmax * 2;
+    const bool same = c == (int)last[h];
+    const int start = out_len > 1 ? out_len : 1;
+    for (int t = 0; t < start - 1 && t < T; ++t) { rn_out[2 * t] = CTC_LOGZERO; rn_out[2 * t + 1] = CTC_LOGZERO; }
+    float rn = (out_len == 0) ? lp[c] : CTC_LOGZERO, rb = CTC_LOGZERO;          // r[start-1]
+    if (start - 1 < T) { rn_out[2 * (start - 1)] = rn; rn_out[2 * (start - 1) + 1] = rb; }
+    float acc = rn;
+    for (int t = start; t < T; ++t) {
+        const float pn = rp[2 * (t - 1)], pb = rp[2 * (t - 1) + 1];
+        const float phi = same ? pb : lae(pn, pb);
+        const float x = lp[(long)t * ldp + c], xb = lp[(long)t * ldp + blank];
+        acc = lae(acc, phi + x);
+        const float nn = lae(rn, phi) + x;
+        const float nb = lae(rn, rb) + xb;
+        rn = nn; rb = nb;
+        rn_out[2 * t] = rn; rn_out[2 * t + 1] = rb;
+    }
+    for (int t = T; t < Tmax; ++t) { rn_out[2 * t] = CTC_LOGZERO; rn_out[2 * t + 1] = CTC_LOGZERO; }
+    if (c == eos) acc = lae(rp[2 * (T - 1)], rp[2 * (T - 1) + 1]);
+    if (c == blank) acc = CTC_LOGZERO;
+    psi[idx] = acc;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Source attention of a beam step: one wave per (hypothesis r, head h).  The query is row r of q; the keys / values are rows
+// clip_of[r] * Tmax + [0, tlen[clip]) of kv (k | v per row, projected once per clip and layer).  Structure of k_mha_table (lrs_lm.hip):
+// keys in chunks of 64, lane l owns key c * 64 + l for the scores, online softmax in fp32, then lane l owns channel l of the weighted
+// sum of the values.  A row without a clip or a clip without frames writes zeros.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_mha_src_step(const bf16_t* __restrict__ q, long q_pitch, const bf16_t* __restrict__ kv, long kv_pitch,
+                                                      const int* __restrict__ clip_of, const int* __restrict__ tlen, int C, int Tmax, int n, int H,
+                                                      float scale, bf16_t* __restrict__ ctx, long ctx_pitch) {
+    const int lane = threadIdx.x & 63;
+    const long w = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (w >= (long)n * H) return;                          // whole waves leave: nothing below synchronises across waves
+    const int h = (int)(w % H), r = (int)(w / H);
+    const int D = H * 64;
+    bf16_t* out = ctx + (long)r * ctx_pitch + h * 64 + lane;
+    const int clip = clip_of[r];
+    int T = (clip >= 0 && clip < C) ? tlen[clip] : 0;
+    T = T > Tmax ? Tmax : T;
+    if (T < 1) { *out = 0; return; }
+    const bf16_t* base = kv + (long)clip * Tmax * kv_pitch + h * 64;
+
+    float qf[64];
+    {
+        const u32x4* qp = reinterpret_cast<const u32x4*>(q + (long)r * q_pitch + h * 64);
+#pragma unroll
+        for (int c = 0; c < 8; ++c) unpack8(qp[c], qf + c * 8);
+    }
+    float m = -INFINITY, l = 0.f, acc = 0.f;
+    for (int k0 = 0; k0 < T; k0 += 64) {
+        const int kk = k0 + lane;
+        float s = -INFINITY;
+        if (kk < T) {
+            const u32x4* kp = reinterpret_cast<const u32x4*>(base + (long)kk * kv_pitch);
+            float d = 0.f;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                float kf[8];
+                unpack8(kp[c], kf);
+#pragma unroll
+                for (int t = 0; t < 8; ++t) d += qf[c * 8 + t] * kf[t];
+            }
+            s = d * scale;
+        }
+        const float mc = wave_max(s);                      // (lane 0 of every chunk holds a live key: mc is finite unless a score is)
+        const float mn = fmaxf(m, mc);
+        const float corr = __expf(m - mn);                 // m = -inf on the first chunk: exp(-inf) = 0
+        const float p = kk < T ? __expf(s - mn) : 0.f;
+        l = l * corr + wave_sum(p);
+        acc *= corr;
+        m = mn;
+        const int cnt = min(64, T - k0);
+        const bf16_t* vbase = base + D + lane;
+        for (int k = 0; k < cnt; ++k) {
+            const float pk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p), k));
+            acc += pk * bf2f(vbase[(long)(k0 + k) * kv_pitch]);
+        }
+    }
+    *out = l > 0.f ? f2bf(acc / l) : (bf16_t)0;
+}
+
+extern "C" {
+
+// elements per stage-1 workgroup: the shortest slice whose candidates (slices * beam) one merge workgroup can rank; 0: none does
+static int beam_slice_len(int V, int beam, int max_rows) {
+    const long N = (long)max_rows * V;
+    for (int SL = 1024; SL <= BS_CAND; SL *= 2)
+        if ((N + SL - 1) / SL * beam <= BS_CAND) return SL;
+    return 0;
+}
+
+/* slices per clip of svsr_beam_select for clips of at most max_rows rows (cand holds C * slices * beam 64-bit words); 0: unsupported */
+int svsr_beam_select_slices(int V, int beam, int max_rows) {
+    if (V < 1 || beam < 1 || beam > BS_CAND / 16 || max_rows < 1 || (long)max_rows * V > (long)BS_IDX_MASK + 1) return 0;
+    const int SL = beam_slice_len(V, beam, max_rows);
+    return SL == 0 ? 0 : (int)(((long)max_rows * V + SL - 1) / SL);
+}
+
+int svsr_beam_select(const float* s0, const float* s1, const float* s2, const float* s3, float w0, float w1, float w2, float w3, int nplanes,
+                     int64_t ldv, const float* run, const int* clip_of, const int* row_lo, const int* out_off, int n, int C, int V, int beam,
+                     int max_rows, int out_rows, void* cand, int64_t* prev, int64_t* tok, float* total, float* vals, int* clip_out, int* count,
+                     hipStream_t stream) {
+    if (nplanes < 1 || nplanes > BS_MAX_PLANES || n < 1 || C < 1 || V < 1 || ldv < V || beam < 1 || beam > BS_CAND / 16 || max_rows < 1 ||
+        max_rows > n || out_rows < 1)
+        return SVSR_ERR_ARG;
+    if ((long)max_rows * V > (long)BS_IDX_MASK + 1) return SVSR_ERR_ARG;        // the flat index of a clip's element has BS_IDX_BITS bits
+    const int SL = beam_slice_len(V, beam, max_rows);
+    if (SL == 0) return SVSR_ERR_ARG;                                           // slices * beam candidates must fit one merge workgroup
+    const int G = svsr_beam_select_slices(V, beam, max_rows);
+    const float* s[BS_MAX_PLANES] = {s0, s1, s2, s3};
+    const float w[BS_MAX_PLANES] = {w0, w1, w2, w3};
+    BeamPlanes p;
+    p.n = nplanes;
+    for (int i = 0; i < BS_MAX_PLANES; ++i) {
+        if (i < nplanes && s[i] == nullptr) return SVSR_ERR_ARG;
+        p.s[i] = i < nplanes ? s[i] : nullptr;
+        p.w[i] = i < nplanes ? w[i] : 0.f;
+    }
+    if (C > 65535) return SVSR_ERR_ARG;
+    hipLaunchKernelGGL(k_beam_select_slices, dim3(G, C), dim3(BS_THREADS), 0, stream, p, run, row_lo, (long)ldv, V, beam, SL, n,
+                       (unsigned long long*)cand);
+    hipLaunchKernelGGL(k_beam_select_merge, dim3(C), dim3(BS_THREADS), 0, stream, p, run, clip_of, row_lo, out_off, (long)ldv, V, beam, SL, G, n,
+                       out_rows, (const unsigned long long*)cand, (long*)prev, (long*)tok, total, vals, clip_out, count);
+    return svsr_check_launch();
+}
+
+int svsr_ctc_prefix_score_clips(const float* logp, int ldp, const float* r_prev, const int64_t* last, const int64_t* ids, const int* clip_of,
+                                const int* tlen, float* r_new, float* psi, int C, int Tmax, int V, int n, int S, int out_len, int blank, int eos,
+                                hipStream_t stream) {
+    if (C < 1 || Tmax < 1 || V < 2 || n < 1 || S < 1 || (ids == nullptr && S != V) || ldp < V || out_len < 0 || blank < 0 || blank >= V || eos < 0 ||
+        eos >= V || clip_of == nullptr || tlen == nullptr)
+        return SVSR_ERR_ARG;
+    if (((long)n * S + 255) / 256 > 0x7fffffffL) return SVSR_ERR_ARG;          // one thread per (hypothesis, candidate), as svsr_ctc_prefix_score
+    hipLaunchKernelGGL(k_ctc_prefix_score_clips, dim3((unsigned)(((long)n * S + 255) / 256)), dim3(256), 0, stream, logp, r_prev, (const long*)last,
+                       (const long*)ids, clip_of, tlen, r_new, psi, C, Tmax, V, ldp, n, S, out_len, blank, eos);
+    return svsr_check_launch();
+}
+
+int svsr_mha_src_step_fwd(const void* q, int64_t q_pitch, const void* kv, int64_t kv_pitch, const int* clip_of, const int* tlen, int C, int Tmax, int n,
+                          int H, float scale, void* ctx, int64_t ctx_pitch, hipStream_t stream) {
+    if (C < 1 || Tmax < 1 || n < 1 || H < 1 || clip_of == nullptr || tlen == nullptr) return SVSR_ERR_ARG;
+    if (q_pitch < (int64_t)H * 64 || q_pitch % 8 != 0 || kv_pitch < 2L * H * 64 || kv_pitch % 8 != 0 || ctx_pitch < (int64_t)H * 64) return SVSR_ERR_ARG;
+    if ((((uintptr_t)q | (uintptr_t)kv) & 15) != 0) return SVSR_ERR_ARG;       // 16-byte loads of 64-channel head slices
+    const long waves = (long)n * H;
+    if (waves > (1L << 30)) return SVSR_ERR_ARG;
+    hipLaunchKernelGGL(k_mha_src_step, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, (const bf16_t*)q, (long)q_pitch, (const bf16_t*)kv,
+                       (long)kv_pitch, clip_of, tlen, C, Tmax, n, H, scale, (bf16_t*)ctx, (long)ctx_pitch);
+    return svsr_check_launch();
+}
+
+}  // extern "C"

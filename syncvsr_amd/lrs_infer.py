@@ -16,6 +16,11 @@ batch_score` (transformer/decoder.py:153-220), `CTCPrefixScorer` (scorers/ctc.py
     of caching per-layer outputs: the decoder's self-attention is causal, so the last row is identical either way.
 
 The search itself is device-agnostic host logic over torch tensors; the two neural scorers need the HIP library.
+
+`BatchBeamSearch.forward_clips(xs [C, Tmax, D], lengths)` / `decode_clips` decode C clips in ONE lock-step search (the reference decodes its
+test list clip after clip): rows stay grouped by clip, the scorers are clip-aware (`batch_init_state_clips`, `batch_score_clips` /
+`batch_score_partial_clips`; any other scorer is wrapped in `PerClipScorers`), the selection of a position is one HIP entry point for all
+clips (svsr_beam_select; CPU tensors: its torch statement `beam_select_reference`), and the host synchronises once per position.
 """
 from __future__ import annotations
 
@@ -73,6 +78,14 @@ class LengthBonus:
 
     def select_states(self, states, prev, tok):
         return None
+
+    # -- clip-aware protocol (BatchBeamSearch.forward_clips): the bonus does not look at the clip
+    def batch_init_state_clips(self, xs, lengths):
+        self._like = xs
+        return None
+
+    def batch_score_clips(self, ys, states, clip_of):
+        return torch.ones((ys.shape[0], self.n), dtype=self._like.dtype, device=self._like.device), None
 
 
 class DecoderScorer:
@@ -203,6 +216,73 @@ class DecoderScorer:
                               out_f32=True, out_pitch=Vp)[0]
         return pred[:, :V], tuple(new_cache)
 
+    # -- clip-aware protocol (BatchBeamSearch.forward_clips) ---------------------------------------
+    def batch_init_state_clips(self, xs: torch.Tensor, lengths):
+        """xs [C, Tmax, ddim] padded encoder outputs, lengths [C]: projects the source keys / values of every clip and layer in ONE
+        [C * Tmax]-row GEMM per layer; a step's query rows find their clip's block through `clip_of` (svsr_mha_src_step_fwd), so no
+        per-hypothesis copy of them is ever made.  Rows beyond a clip's length are projected but never read."""
+        m = self.model
+        if m.training:
+            raise RuntimeError("batch_init_state_clips is an inference entry point: call model.eval() first")
+        if xs.dim() != 3 or xs.size(-1) != m.ddim:
+            raise ValueError(f"xs is {tuple(xs.shape)}, the decoder expects [clips, frames, ddim = {m.ddim}] (the reference feeds the encoder "
+                             "output to the decoder directly at inference, lightning.py:114-119, which needs adim == ddim)")
+        if xs.device.type != "cuda":
+            raise RuntimeError("syncvsr_amd runs on an MI355X HIP device only; there is no CPU fallback (use oracle/ for checking)")
+        st = m.store()
+        m._side.join()
+        if not st.shadow_fresh:
+            st.refresh_shadows()
+            self._mem = None
+        C, Tmax, D = xs.shape
+        tlen = torch.as_tensor(lengths, dtype=torch.int32).to(xs.device).contiguous()
+        with torch.no_grad():
+            mem = xs.to(BF16).reshape(C * Tmax, D).contiguous()
+            kv = [_lin_kv(st, mem, f"decoder.decoders.{i}.src_attn.linear_k", C * Tmax, D) for i in range(m.dlayers)]
+        self._clips = dict(kv=kv, tlen=tlen, C=C, Tmax=Tmax, dev=xs.device)
+        return None
+
+    def batch_score_clips(self, ys: torch.Tensor, states, clip_of: torch.Tensor):
+        """ys int64 [n, L], states: None (first position) or the batched cache (per-layer [n, L-1, 3*ddim]), clip_of int32 [n] ->
+        (log-probabilities of the next token [n, odim], new cache).  Every position, the first included, goes through the one-row step:
+        the cache of the first position is empty."""
+        from .lrs_model import _ffn_fwd, _lin, _ln
+
+        m, ck = self.model, self._clips
+        D, U, H = m.ddim, m.dunits, m.dheads
+        n, L = ys.shape
+        st = m.store()
+        if states is None:
+            if L != 1:
+                raise ValueError("the decoder scorer of a multi-clip search starts from the <sos> column: states may be None at the first position only")
+            states = tuple(torch.empty((n, 0, 3 * D), dtype=BF16, device=ys.device) for _ in range(m.dlayers))
+        if len(states) != m.dlayers or states[0].shape != (n, L - 1, 3 * D):
+            raise ValueError(f"cache entries are {tuple(states[0].shape)}, expected ({n}, {L - 1}, {3 * D}): the cache must come from the "
+                             "previous scoring call for the same hypotheses")
+        with torch.no_grad():
+            pe = m._pos_table("abs", L, ys.device)
+            x = ops.embed_pos_fwd(ys[:, -1:].contiguous(), st.p32("decoder.embed.0.weight"), pe[L - 1 : L].contiguous(), 1, D, math.sqrt(D))   # [n, D]
+            new_cache = []
+            for i in range(m.dlayers):
+                p = f"decoder.decoders.{i}"
+                c = states[i]
+                t1, _, _ = _ln(st, x, f"{p}.norm1")
+                qkv = _lin(st, t1, f"{p}.self_attn.linear_q", n, D, 3 * D)
+                kv = torch.cat((c[:, :, D:], qkv[:, D:].unsqueeze(1)), dim=1).view(n * L, 2 * D)
+                ctx, _ = ops.mha_fwd(qkv, 3 * D, kv, kv[:, D:], 2 * D, B=n, H=H, Lq=1, Lk=L)
+                x1 = _lin(st, ctx, f"{p}.self_attn.linear_out", n, D, D, addend=x)
+                t2, _, _ = _ln(st, x1, f"{p}.norm2")
+                q = _lin(st, t2, f"{p}.src_attn.linear_q", n, D, D)
+                ctx2 = ops.mha_src_step_fwd(q, ck["kv"][i], clip_of, ck["tlen"], Tmax=ck["Tmax"], H=H)
+                x2 = _lin(st, ctx2, f"{p}.src_attn.linear_out", n, D, D, addend=x1)
+                x = _ffn_fwd(m, st, {}, "ff", x2, f"{p}.feed_forward", n, D, U, 1.0, f"{p}.norm3", f"dec.{i}.ff")
+                new_cache.append(torch.cat((c, torch.cat((x, qkv[:, D:]), dim=1).unsqueeze(1)), dim=1))
+            tn, _, _ = _ln(st, x, "decoder.after_norm")
+            V = m.odim
+            pred = ops.linear_fwd(tn, st.s16("decoder.output_layer.weight"), st.p32("decoder.output_layer.bias"), rows=n, K=D, N=V, x_pitch=D,
+                                  out_f32=True, out_pitch=(V + 63) // 64 * 64)[0]
+            return torch.log_softmax(pred[:, :V].float(), dim=-1), tuple(new_cache)
+
     def score(self, ys: torch.Tensor, state, x: torch.Tensor):
         logp, cache = self.forward_one_step(ys.unsqueeze(0), None, x.unsqueeze(0), cache=None if state is None else [c.unsqueeze(0) for c in state])
         return logp.squeeze(0), [c.squeeze(0) for c in cache]
@@ -276,6 +356,43 @@ class CTCPrefixScorer:
         full[:, self.blank] = LOGZERO
         return full - s_prev.unsqueeze(1), (r_new, full, ids_c)
 
+    # -- clip-aware protocol (BatchBeamSearch.forward_clips) ---------------------------------------
+    def batch_init_state_clips(self, xs: torch.Tensor, lengths):
+        """xs [C, Tmax, adim]: the posteriors of every clip in one GEMM + one log-softmax -> self.logp_clips fp32 [C, Tmax, odim]."""
+        C, Tmax = xs.shape[:2]
+        self.logp_clips = self.ctc_log_softmax(xs.reshape(C * Tmax, xs.shape[2])).view(C, Tmax, -1)
+        self.tlen = torch.as_tensor(lengths, dtype=torch.int32).to(xs.device).contiguous()
+        return None
+
+    def _prefix_clips(self, logp, tlen, r_prev, last, ids, clip_of, out_len):
+        return ops.ctc_prefix_score_clips(logp, tlen, r_prev, last, ids, clip_of, out_len, self.blank, self.eos)
+
+    def batch_score_partial_clips(self, y: torch.Tensor, ids: Optional[torch.Tensor], state, clip_of: torch.Tensor):
+        """`batch_score_partial` with hypothesis r scored against the tlen[clip_of[r]] frames of its own clip.  State: (r [n, Tmax, 2] with
+        -1e10 beyond the clip's length, s [n])."""
+        logp, tlen = self.logp_clips, self.tlen
+        C, Tmax, V = logp.shape
+        n = y.shape[0]
+        cl = clip_of.long()
+        if state is None:
+            live = torch.arange(Tmax, device=logp.device).unsqueeze(0) < tlen.unsqueeze(1)                  # [C, Tmax]
+            r0 = torch.full((C, Tmax, 2), LOGZERO, dtype=logp.dtype, device=logp.device)
+            r0[:, :, 1] = torch.where(live, torch.cumsum(logp[:, :, self.blank], 1), r0[:, :, 1])
+            r_prev = r0[cl].contiguous()
+            s_prev = torch.zeros(n, dtype=logp.dtype, device=logp.device)
+        else:
+            r_prev, s_prev = state
+        ids_c = None if ids is None else ids.contiguous()
+        r_new, psi = self._prefix_clips(logp, tlen, r_prev.contiguous(), y[:, -1].contiguous(), ids_c, clip_of, y.shape[1] - 1)
+        if ids_c is None:
+            full = psi.clone()
+        else:
+            full = torch.full((n, V), LOGZERO, dtype=logp.dtype, device=logp.device).scatter_(1, ids_c, psi)
+        end = r_prev[torch.arange(n, device=logp.device), tlen.long()[cl] - 1]                                  # [n, 2]: the clip's last frame
+        full[:, self.eos] = torch.logaddexp(end[:, 0], end[:, 1])
+        full[:, self.blank] = LOGZERO
+        return full - s_prev.unsqueeze(1), (r_new, full, ids_c)
+
     def select_states(self, pending, prev: torch.Tensor, tok: torch.Tensor):
         """State of the extensions (prev[i], tok[i])."""
         r_new, full, ids = pending
@@ -286,6 +403,119 @@ class CTCPrefixScorer:
                 1, ids, torch.arange(ids.shape[1], device=full.device).expand_as(ids))
             j = idmap[prev, tok]
         return r_new[prev, j].contiguous(), full[prev, tok].contiguous()
+
+
+
+# ----------------------------------------------------------------------------------------------------
+# multi-clip search: the adapter for single-clip scorers, and the torch statement of the selection step
+# ----------------------------------------------------------------------------------------------------
+def _ranges(clip_of) -> dict:
+    """{clip: (first row, end row)} of a non-decreasing row -> clip map (host side)."""
+    out: dict = {}
+    for r, c in enumerate(clip_of.tolist() if isinstance(clip_of, torch.Tensor) else clip_of):
+        lo, _ = out.get(c, (r, r))
+        out[c] = (lo, r + 1)
+    return out
+
+
+class _ClipStates:
+    """State of a PerClipScorers: {clip: (first row, end row, that clip's batched state)}.  Indexing by a tensor of rows (the search's
+    `keep` gather) splits the rows by clip and indexes every clip's state with its local rows."""
+
+    def __init__(self, per: dict):
+        self.per = per
+
+    def split(self, rows: torch.Tensor):
+        """rows (global, grouped by clip in clip order) -> [(clip, positions lo, hi in `rows`, local rows)]."""
+        host = rows.tolist()
+        out, pos = [], 0
+        for c, (lo, hi, _) in self.per.items():
+            start = pos
+            while pos < len(host) and lo <= host[pos] < hi:
+                pos += 1
+            if pos > start:
+                out.append((c, start, pos, rows[start:pos] - lo))
+        if pos != len(host):
+            raise ValueError("rows of a multi-clip search must stay grouped by clip, in clip order")
+        return out
+
+    def __getitem__(self, keep: torch.Tensor) -> "_ClipStates":
+        return _ClipStates({c: (a, b, BatchBeamSearch._take(self.per[c][2], loc)) for c, a, b, loc in self.split(keep)})
+
+
+class PerClipScorers:
+    """Adapter: any scorer that speaks the single-clip protocol (`batch_init_state(x)`, `batch_score(ys, states, xs)` or
+    `batch_score_partial(y, ids, state, x)`, `select_states`) as a clip-aware scorer of `BatchBeamSearch.forward_clips`.  Rows are split by
+    clip, the wrapped scorer is called once per clip with that clip's unpadded encoder output, and the answers are concatenated: correct
+    for every scorer, and as slow as one search per clip for this scorer's share of a step.  The single-clip protocol lets a scorer keep
+    data of its clip on itself (CTCPrefixScorer.logp), so every clip gets its own shallow copy of the wrapped scorer."""
+
+    def __init__(self, scorer):
+        self.scorer = scorer
+        self._per: dict = {}
+        if hasattr(scorer, "batch_score_partial"):
+            self.batch_score_partial_clips = self._batch_score_partial_clips
+            self.batch_score_partial = None                  # (marks a partial scorer for BatchBeamSearch's constructor)
+
+    def batch_init_state_clips(self, xs: torch.Tensor, lengths):
+        import copy
+
+        self._per = {}
+        per = {}
+        for c, T in enumerate(int(v) for v in lengths):
+            d = copy.copy(self.scorer)
+            x = xs[c, :T]
+            self._per[c] = (d, x)
+            per[c] = (c, c + 1, d.batch_init_state(x))
+        return _ClipStates(per)
+
+    def _each(self, ys, states, clip_of, call):
+        rng = _ranges(clip_of)
+        scores, per = [], {}
+        for c, (lo, hi) in rng.items():
+            d, x = self._per[c]
+            st = states.per[c][2] if isinstance(states, _ClipStates) and c in states.per else None
+            sc, new = call(d, x, lo, hi, st)
+            scores.append(sc)
+            per[c] = (lo, hi, new)
+        return torch.cat(scores, dim=0), _ClipStates(per)
+
+    def batch_score_clips(self, ys, states, clip_of):
+        return self._each(ys, states, clip_of, lambda d, x, lo, hi, st: d.batch_score(ys[lo:hi], st, x.unsqueeze(0).expand(hi - lo, *x.shape)))
+
+    def _batch_score_partial_clips(self, ys, ids, states, clip_of):
+        return self._each(ys, states, clip_of,
+                          lambda d, x, lo, hi, st: d.batch_score_partial(ys[lo:hi], None if ids is None else ids[lo:hi], st, x))
+
+    def select_states(self, states: _ClipStates, prev: torch.Tensor, tok: torch.Tensor):
+        return _ClipStates({c: (a, b, self._per[c][0].select_states(states.per[c][2], loc, tok[a:b])) for c, a, b, loc in states.split(prev)})
+
+
+def beam_select_reference(planes, weights, run: torch.Tensor, row_lo, beam: int, V: int):
+    """The torch statement of the selection step of a multi-clip search — what svsr_beam_select computes, and the path of CPU tensors.
+    planes [n, >= V] with their weights, in order; run [n]; row_lo: host list [C + 1] of the clips' row ranges.  weighted = zeros;
+    weighted += w_k * s_k for every plane; weighted += run[:, None]; per clip the min(beam, rows * V) best (row, token), higher first,
+    ties to the lower (row, token) -> (prev [m] global rows, tok [m], total [m], vals [P, m]: each plane at the winners, count: list [C])."""
+    n = run.numel()
+    weighted = torch.zeros((n, V), dtype=run.dtype, device=run.device)
+    for w, sc in zip(weights, planes):
+        weighted += w * sc[:, :V].to(run.dtype)
+    weighted += run.unsqueeze(1)
+    prev, tok, count = [], [], []
+    for c in range(len(row_lo) - 1):
+        lo, hi = int(row_lo[c]), int(row_lo[c + 1])
+        k = min(int(beam), max(hi - lo, 0) * V)
+        count.append(k)
+        if k == 0:
+            continue
+        order = torch.sort(weighted[lo:hi].reshape(-1), descending=True, stable=True)[1][:k]
+        prev.append(lo + torch.div(order, V, rounding_mode="trunc"))
+        tok.append(order % V)
+    if not prev:
+        e = torch.empty(0, dtype=torch.int64, device=run.device)
+        return e, e, weighted.new_empty(0), weighted.new_empty((len(planes), 0)), count
+    prev, tok = torch.cat(prev), torch.cat(tok)
+    return prev, tok, weighted[prev, tok], torch.stack([sc[prev, tok].to(run.dtype) for sc in planes]), count
 
 
 # ----------------------------------------------------------------------------------------------------
@@ -381,6 +611,168 @@ class BatchBeamSearch:
 
     __call__ = forward
 
+    # ------------------------------------------------------------------------------------------------
+    # multi-clip search: C clips advance through ONE search in lock step
+    # ------------------------------------------------------------------------------------------------
+    # Device bytes the CTC scorer's pending state [rows, candidates, Tmax, 2] fp32 of one step may take.  A batch whose C * beam rows
+    # would exceed it is decoded in groups of consecutive clips that fit (full-vocabulary partial scoring, ctc_weight == 1.0, at beam 40
+    # over 5,049 units and 150 frames is 242 MB per clip: 8 clips per group; with the pre-beam of 60 candidates it is 2.9 MB per clip).
+    clip_workspace_bytes = 2 << 30
+
+    def clips_per_group(self, Tmax: int) -> int:
+        """Clips `forward_clips` decodes together at `Tmax` padded frames under `clip_workspace_bytes` (at least 1)."""
+        if not self.part_scorers:
+            return 1 << 30
+        cand = self.pre_beam_size if self.do_pre_beam else self.n_vocab
+        return max(1, int(self.clip_workspace_bytes) // (self.beam_size * cand * int(Tmax) * 2 * 4))
+
+    def _clip_scorers(self) -> dict:
+        out = {}
+        for k, d in self.scorers.items():
+            if isinstance(d, PerClipScorers):
+                out[k] = d
+            elif hasattr(d, "batch_init_state_clips") and hasattr(d, "batch_score_partial_clips" if k in self.part_scorers else "batch_score_clips"):
+                out[k] = d
+            else:
+                out[k] = PerClipScorers(d)
+        return out
+
+    def _select(self, planes, weights, run_score, clip_of, rows, meta):
+        """-> (prev, tok, total, vals [P, m], clip_of of the winners).  rows: host list of rows per clip; meta: int32 device tensor
+        row_lo [C + 1] | out_off [C] (made where the host last synchronised), None on CPU."""
+        V, beam = self.n_vocab, self.beam_size
+        if run_score.device.type == "cuda":
+            if run_score.dtype != torch.float32:
+                raise NotImplementedError(f"the selection kernel of a multi-clip search adds fp32 planes; the encoder outputs are {run_score.dtype}")
+            C = len(rows)
+            prev, tok, total, vals, clip_out, _ = ops.beam_select(
+                [s.to(torch.float32) for s in planes], weights, run_score.contiguous(), clip_of, meta[: C + 1], meta[C + 1 :], beam=beam, V=V,
+                max_rows=max(rows), out_rows=sum(min(beam, r * V) for r in rows))
+            return prev, tok, total, vals, clip_out
+        row_lo = [0]
+        for r in rows:
+            row_lo.append(row_lo[-1] + r)
+        prev, tok, total, vals, _ = beam_select_reference(planes, weights, run_score, row_lo, beam, V)
+        return prev, tok, total, vals, clip_of[prev]
+
+    def _search_clips(self, run: dict, scorers: dict, rows: list, dtype) -> dict:
+        """One position of every live clip: `_search` with clip-aware scorers and the per-clip selection."""
+        yseq, clip_of = run["yseq"], run["clip_of"]
+        sc, st = {}, {}
+        for k in self.full_scorers:
+            sc[k], st[k] = scorers[k].batch_score_clips(yseq, run["states"][k], clip_of)
+        part_ids = None
+        if self.do_pre_beam:
+            if self.pre_beam_score_key == "full":
+                pre = torch.zeros((yseq.shape[0], self.n_vocab), dtype=dtype, device=yseq.device)
+                for k in self.full_scorers:
+                    pre += self.weights[k] * sc[k].to(dtype)
+            else:
+                pre = sc[self.pre_beam_score_key]
+            part_ids = torch.topk(pre, self.pre_beam_size, dim=-1)[1]          # per row: the clips do not meet here
+        for k in self.part_scorers:
+            sc[k], st[k] = scorers[k].batch_score_partial_clips(yseq, part_ids, run["states"][k], clip_of)
+        order = list(self.full_scorers) + list(self.part_scorers)              # the order `_search` adds the planes up in
+        prev, tok, total, vals, new_clip = self._select([sc[k].to(dtype) for k in order], [self.weights[k] for k in order], run["score"], clip_of,
+                                                        rows, run["meta"])
+        return dict(
+            yseq=torch.cat((yseq[prev], tok.unsqueeze(1)), dim=1),
+            score=total,
+            scores={k: run["scores"][k][prev] + vals[j] for j, k in enumerate(order)},
+            states={k: scorers[k].select_states(st[k], prev, tok) for k in order},
+            clip_of=new_clip,
+        )
+
+    def forward_clips(self, xs: torch.Tensor, lengths, maxlenratio: float = 0.0, minlenratio: float = 0.0) -> list:
+        """xs: padded encoder outputs of C clips [C, Tmax, D], lengths [C] (int tensor or list) -> per clip the ended hypotheses, best
+        first: element c is what `forward(xs[c, :lengths[c]])` returns.  All clips start together, so every live hypothesis has the same
+        prefix length at every position; each clip keeps its own length limit, end detection and ended list, and a clip that has finished
+        simply stops contributing rows.  One host synchronisation per position for all clips together.  Scorers without the clip-aware
+        methods are wrapped in `PerClipScorers`.  Batches beyond `clips_per_group(Tmax)` clips are decoded in groups of consecutive
+        clips (`clip_workspace_bytes`)."""
+        if xs.dim() != 3:
+            raise ValueError(f"xs must be [clips, frames, D], got {tuple(xs.shape)}")
+        lens = [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+        C, Tmax = xs.shape[:2]
+        if len(lens) != C:
+            raise ValueError(f"{len(lens)} lengths for {C} clips")
+        if any(t < 1 or t > Tmax for t in lens):
+            raise ValueError(f"lengths must lie in [1, {Tmax}] (the padded frame count), got {lens}")
+        G = self.clips_per_group(Tmax)
+        out: list = []
+        for g0 in range(0, C, G):
+            ls = lens[g0 : g0 + G]
+            out += self._forward_group(xs[g0 : g0 + G, : max(ls)], ls, maxlenratio, minlenratio)
+        return out
+
+    def _forward_group(self, xs: torch.Tensor, lens: list, maxlenratio: float, minlenratio: float) -> list:
+        C, dev, dt = xs.shape[0], xs.device, xs.dtype
+        V, beam = self.n_vocab, self.beam_size
+        if maxlenratio == 0:
+            maxlen = list(lens)
+        elif maxlenratio < 0:
+            maxlen = [-1 * int(maxlenratio)] * C
+        else:
+            maxlen = [max(1, int(maxlenratio * t)) for t in lens]
+        scorers = self._clip_scorers()
+        rows = [1 if maxlen[c] > 0 else 0 for c in range(C)]                      # live hypotheses per clip (host bookkeeping)
+        first = [c for c in range(C) if rows[c]]
+        run = dict(yseq=torch.full((len(first), 1), self.sos, dtype=torch.int64, device=dev), score=torch.zeros(len(first), dtype=dt, device=dev),
+                   scores={k: torch.zeros(len(first), dtype=dt, device=dev) for k in self.scorers},
+                   states={k: d.batch_init_state_clips(xs, lens) for k, d in scorers.items()},
+                   clip_of=torch.tensor(first, dtype=torch.int32, device=dev), meta=self._meta(rows, dev))
+        ended: list[list] = [[] for _ in range(C)]
+        wide = torch.float64 if dt == torch.float64 else torch.float32          # one read-back row type that holds tokens and scores exactly
+        i = 0
+        while sum(rows) > 0:
+            run = self._search_clips(run, scorers, rows, dt)
+            rows = [min(beam, r * V) for r in rows]
+            names = list(run["scores"])
+            host = torch.stack([run["yseq"][:, -1].to(wide), run["score"].to(wide)] + [run["scores"][k].to(wide) for k in names]).cpu()
+            if dt not in (torch.float32, torch.float64):
+                host = host.to(dt)
+            last, score, parts = host[0].tolist(), host[1].tolist(), [h.tolist() for h in host[2:]]
+            keep, b = [], 0
+            for c in range(C):
+                n_c, limit, kept = rows[c], i == maxlen[c] - 1, 0
+                for r in range(b, b + n_c):
+                    if limit or int(last[r]) == self.eos:      # batch_beam_search.py:318-334: the length limit closes every running hypothesis
+                        y = run["yseq"][r]
+                        if limit:
+                            y = torch.cat((y, y.new_full((1,), self.eos)))
+                        ended[c].append(Hypothesis(yseq=y, score=score[r], scores={k: parts[j][r] for j, k in enumerate(names)}))
+                    else:
+                        keep.append(r)
+                        kept += 1
+                if kept and maxlenratio == 0.0 and end_detect([dict(score=h.score, yseq=h.yseq) for h in ended[c]], i):
+                    del keep[len(keep) - kept :]
+                    kept = 0
+                b += n_c
+                rows[c] = kept
+            if len(keep) != b:                                   # rows of ended hypotheses and of finished clips leave together
+                kt = torch.tensor(keep, dtype=torch.int64, device=dev)
+                run = dict(yseq=run["yseq"][kt], score=run["score"][kt], scores={k: v[kt] for k, v in run["scores"].items()},
+                           states={k: self._take(v, kt) for k, v in run["states"].items()}, clip_of=run["clip_of"][kt])
+            run["meta"] = self._meta(rows, dev)
+            i += 1
+        out = []
+        for c in range(C):
+            nbest = sorted(ended[c], key=lambda h: h.score, reverse=True)
+            if not nbest and minlenratio >= 0.1:                 # beam_search.py:383-392
+                nbest = self._forward_group(xs[c : c + 1, : lens[c]], lens[c : c + 1], maxlenratio, max(0.0, minlenratio - 0.1))[0]
+            out.append(nbest)
+        return out
+
+    def _meta(self, rows: list, dev):
+        """row_lo [C + 1] | out_off [C] of the next selection as one int32 device tensor (CPU tensors: not needed)."""
+        if dev.type != "cuda":
+            return None
+        lo, off = [0], [0]
+        for r in rows:
+            lo.append(lo[-1] + r)
+            off.append(off[-1] + min(self.beam_size, r * self.n_vocab))
+        return torch.tensor(lo + off[:-1], dtype=torch.int32, device=dev)
+
 
 def get_beam_search_decoder(model, token_list, rnnlm=None, rnnlm_conf=None, penalty=0, ctc_weight: float = 0.1, lm_weight: float = 0.0,
                             beam_size: int = 40, scorers: Optional[dict] = None) -> BatchBeamSearch:
@@ -401,3 +793,17 @@ def get_beam_search_decoder(model, token_list, rnnlm=None, rnnlm_conf=None, pena
     weights = {"decoder": 1.0 - ctc_weight, "ctc": ctc_weight, "lm": lm_weight, "length_bonus": penalty}
     return BatchBeamSearch(beam_size=beam_size, vocab_size=len(token_list), weights=weights, scorers=scorers, sos=sos, eos=eos,
                            token_list=token_list, pre_beam_score_key=None if ctc_weight == 1.0 else "decoder")
+
+
+def decode_clips(model, search: BatchBeamSearch, clips: torch.Tensor, lengths) -> list:
+    """The batched twin of `ModelModule.forward` (LRS/video/lightning.py:98-106) up to the token ids: clips [C, Tmax, 1, H, W] padded
+    along T, lengths [C] -> per clip the n-best list of `search.forward_clips` over `model.encoder(clips, masks)`."""
+    if clips.dim() != 5 or clips.size(2) != 1:
+        raise ValueError("clips must be [C, Tmax, 1, H, W]")
+    C, Tmax = clips.shape[:2]
+    lens = torch.as_tensor(lengths, dtype=torch.int64).to(clips.device)
+    if lens.numel() != C or int(lens.min()) < 1 or int(lens.max()) > Tmax:
+        raise ValueError(f"lengths must be {C} values in [1, {Tmax}]")
+    masks = (torch.arange(Tmax, device=clips.device).unsqueeze(0) < lens.unsqueeze(1)).unsqueeze(1)          # [C, 1, Tmax], make_non_pad_mask
+    enc, _ = model.encoder(clips, masks)
+    return search.forward_clips(enc, lens.tolist())

@@ -294,6 +294,15 @@ class TransformerLM(nn.Module):
         pool = LMPool(self.layers, 3 * self.att_unit, beam * (maxlen + 1), x.device)
         return LMState(pool, torch.empty((0, 0), dtype=torch.int32, device=x.device))
 
+    # -- clip-aware protocol (BatchBeamSearch.forward_clips): the language model does not look at the clip; rows are rows ---------------
+    def batch_init_state_clips(self, xs, lengths):
+        """One pool for the C clips of a multi-clip search: `beam_hint` rows per clip over the longest clip's positions."""
+        lens = [int(v) for v in lengths]
+        return self.batch_init_state(xs[0], beam=self.beam_hint * len(lens), maxlen=max(lens))
+
+    def batch_score_clips(self, ys: torch.Tensor, states, clip_of: torch.Tensor = None):
+        return self.batch_score(ys, states, None)
+
     def workspace_bytes(self, beam: int, maxlen: int) -> int:
         """Device bytes of the state of one search: the pools `batch_init_state(beam=, maxlen=)` sizes + the row table."""
         return self.layers * beam * (maxlen + 1) * 3 * self.att_unit * 2 + beam * (maxlen + 1) * 4

@@ -102,6 +102,12 @@ class _DecoderFacade(_Holder):
     def select_states(self, states, prev, tok):
         return self._scorer().select_states(states, prev, tok)
 
+    def batch_init_state_clips(self, xs, lengths):
+        return self._scorer().batch_init_state_clips(xs, lengths)
+
+    def batch_score_clips(self, ys, states, clip_of):
+        return self._scorer().batch_score_clips(ys, states, clip_of)
+
 
 class _CtcFacade(_Holder):
     """`E2E.ctc` inference helpers (ctc.py:154-181) on hs_pad [B, T, adim]."""

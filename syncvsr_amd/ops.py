@@ -1803,3 +1803,85 @@ def lm_embed_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, pe: t
     _call("svsr_lm_embed_fwd", _p(x), x.stride(0), _p(gamma), _p(beta), _p(pe), pe.shape[0], _p(pos), R, D, float(eps), float(scale), _p(out), _stream(),
           label="k_lm_embed")
     return out
+
+
+# --------------------------------------------------------------------------------------------------
+# Multi-clip beam search (csrc/lrs_search.hip)
+# --------------------------------------------------------------------------------------------------
+BEAM_SELECT_MAX_PLANES = 4
+
+
+def beam_select_slices(V: int, beam: int, max_rows: int) -> int:
+    """Stage-1 workgroups per clip of svsr_beam_select for clips of at most `max_rows` rows; 0: outside the kernel's bounds."""
+    return int(_lib.load().svsr_beam_select_slices(int(V), int(beam), int(max_rows)))
+
+
+def beam_select(planes, weights, run: torch.Tensor, clip_of: torch.Tensor, row_lo: torch.Tensor, out_off: torch.Tensor, *, beam: int, V: int,
+                max_rows: int, out_rows: int):
+    """The selection step of a multi-clip search (svsr_beam_select): planes fp32 [n, >= V] (up to 4, one row pitch), weights floats, run fp32
+    [n], clip_of int32 [n], row_lo int32 [C + 1], out_off int32 [C], max_rows = rows of the largest clip, out_rows = sum_c min(beam, rows_c * V)
+    -> (prev int64 [out_rows], tok int64 [out_rows], total fp32 [out_rows], vals fp32 [len(planes), out_rows], clip_out int32 [out_rows],
+    count int32 [C]).  Outside the kernel's bounds (include/syncvsr_hip.h) it raises: there is no other path."""
+    P = len(planes)
+    n, C = run.numel(), row_lo.numel() - 1
+    if not 1 <= P <= BEAM_SELECT_MAX_PLANES:
+        raise ValueError(f"svsr_beam_select adds up 1 to {BEAM_SELECT_MAX_PLANES} score planes, got {P}")
+    ldv = planes[0].stride(0)
+    planes = [s if (s.stride(0) == ldv and s.stride(1) == 1) else s.contiguous() for s in planes]
+    if any(s.stride(0) != ldv for s in planes):
+        planes = [s.contiguous() for s in planes]
+        ldv = planes[0].stride(0)
+    assert all(s.dtype == torch.float32 and s.dim() == 2 and s.shape[0] == n and s.shape[1] >= V and s.stride(1) == 1 for s in planes)
+    assert run.dtype == torch.float32 and run.is_contiguous() and clip_of.dtype == torch.int32 and clip_of.is_contiguous() and clip_of.numel() == n
+    assert row_lo.dtype == torch.int32 and row_lo.is_contiguous() and out_off.dtype == torch.int32 and out_off.is_contiguous() and out_off.numel() >= C
+    G = beam_select_slices(V, beam, max_rows)
+    if G < 1:
+        raise ValueError(f"svsr_beam_select cannot rank clips of {max_rows} rows x {V} units at beam {beam}: it needs beam <= 256, rows * V <= 2^20 "
+                         "and ceil(rows * V / 4096) * beam <= 4096")
+    dev = run.device
+    cand = torch.empty(C * G * beam, dtype=torch.int64, device=dev)
+    prev = torch.empty(out_rows, dtype=torch.int64, device=dev)
+    tok = torch.empty(out_rows, dtype=torch.int64, device=dev)
+    total = torch.empty(out_rows, dtype=torch.float32, device=dev)
+    vals = torch.empty((P, out_rows), dtype=torch.float32, device=dev)
+    clip_out = torch.empty(out_rows, dtype=torch.int32, device=dev)
+    count = torch.empty(C, dtype=torch.int32, device=dev)
+    ptrs = [_p(s) for s in planes] + [None] * (BEAM_SELECT_MAX_PLANES - P)
+    ws = [float(w) for w in weights] + [0.0] * (BEAM_SELECT_MAX_PLANES - P)
+    _call("svsr_beam_select", *ptrs, *ws, P, ldv, _p(run), _p(clip_of), _p(row_lo), _p(out_off), n, C, int(V), int(beam), int(max_rows), int(out_rows),
+          _p(cand), _p(prev), _p(tok), _p(total), _p(vals), _p(clip_out), _p(count), _stream(), label="k_beam_select",
+          nbytes=4.0 * n * V * P)
+    return prev, tok, total, vals, clip_out, count
+
+
+def ctc_prefix_score_clips(logp: torch.Tensor, tlen: torch.Tensor, r_prev: torch.Tensor, last: torch.Tensor, ids: Optional[torch.Tensor],
+                           clip_of: torch.Tensor, out_len: int, blank: int, eos: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """logp fp32 [C, Tmax, V], tlen int32 [C], r_prev fp32 [n, Tmax, 2], last int64 [n], ids int64 [n, S] or None (all V labels), clip_of
+    int32 [n] -> (r_new fp32 [n, S, Tmax, 2], psi fp32 [n, S]).  See svsr_ctc_prefix_score_clips."""
+    C, Tmax, V = logp.shape
+    n = r_prev.shape[0]
+    assert logp.dtype == torch.float32 and logp.is_contiguous() and r_prev.dtype == torch.float32 and r_prev.shape == (n, Tmax, 2)
+    assert r_prev.is_contiguous() and last.dtype == torch.int64 and last.is_contiguous() and last.numel() == n
+    assert tlen.dtype == torch.int32 and tlen.is_contiguous() and tlen.numel() == C
+    assert clip_of.dtype == torch.int32 and clip_of.is_contiguous() and clip_of.numel() == n
+    assert ids is None or (ids.dtype == torch.int64 and ids.is_contiguous() and ids.shape[0] == n)
+    S = V if ids is None else ids.shape[1]
+    r_new = torch.empty((n, S, Tmax, 2), dtype=torch.float32, device=logp.device)
+    psi = torch.empty((n, S), dtype=torch.float32, device=logp.device)
+    _call("svsr_ctc_prefix_score_clips", _p(logp), V, _p(r_prev), _p(last), _p(ids), _p(clip_of), _p(tlen), _p(r_new), _p(psi), C, Tmax, V, n, S,
+          int(out_len), int(blank), int(eos), _stream(), label="k_ctc_prefix_clips")
+    return r_new, psi
+
+
+def mha_src_step_fwd(q: torch.Tensor, kv: torch.Tensor, clip_of: torch.Tensor, tlen: torch.Tensor, *, Tmax: int, H: int,
+                     scale: float = 0.125) -> torch.Tensor:
+    """q bf16 [n, >= H * 64], kv bf16 [C * Tmax, >= 2 * H * 64] (k | v per row), clip_of int32 [n], tlen int32 [C] -> ctx bf16 [n, H * 64]: row r
+    over the tlen[clip_of[r]] source frames of its clip (svsr_mha_src_step_fwd)."""
+    n, C = q.shape[0], tlen.numel()
+    assert q.dtype == BF16 and q.dim() == 2 and q.stride(1) == 1 and kv.dtype == BF16 and kv.dim() == 2 and kv.stride(1) == 1
+    assert kv.shape[0] == C * Tmax and clip_of.dtype == torch.int32 and clip_of.is_contiguous() and clip_of.numel() == n
+    assert tlen.dtype == torch.int32 and tlen.is_contiguous()
+    ctx = torch.empty((n, H * 64), dtype=BF16, device=q.device)
+    _call("svsr_mha_src_step_fwd", _p(q), q.stride(0), _p(kv), kv.stride(0), _p(clip_of), _p(tlen), C, int(Tmax), n, H, float(scale), _p(ctx),
+          ctx.stride(0), _stream(), label="k_mha_src_step", flops=4.0 * n * Tmax * H * 64, nbytes=256.0 * n * H * Tmax)
+    return ctx

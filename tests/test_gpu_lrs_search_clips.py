@@ -1,0 +1,394 @@
+"""Multi-clip beam search on the GPU (-m gpu): the three entry points of csrc/lrs_search.hip against their statements, the clip-aware
+decoder step against the single-clip one, and `BatchBeamSearch.forward_clips` under the criteria tests/test_gpu_lrs_infer.py and
+tests/test_gpu_lrs_lm.py apply to `forward`, per clip."""
+import numpy as np
+import pytest
+import torch
+
+from golden_cases import build_lrs_infer_case
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def dev():
+    if not torch.cuda.is_available():
+        pytest.skip("needs an MI355X")
+    return torch.device("cuda:0")
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# svsr_beam_select
+# ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("rows,V,beam", [([1], 41, 40), ([1, 5, 2, 3], 300, 7), ([40] * 16, 5049, 40), ([40, 0, 17], 5049, 40), ([3, 2], 41, 256)])
+def test_beam_select_kernel_equals_its_torch_statement(dev, rows, V, beam):
+    from syncvsr_amd import ops
+    from syncvsr_amd.lrs_infer import LOGZERO, beam_select_reference
+
+    g = torch.Generator().manual_seed(V + len(rows))
+    n, C = sum(rows), len(rows)
+    row_lo = [0]
+    for r in rows:
+        row_lo.append(row_lo[-1] + r)
+    out_off, o = [], 0
+    for r in rows:
+        out_off.append(o)
+        o += min(beam, r * V)
+    # log-probability-like planes on a coarse grid (exact ties among the best), a CTC-like plane that is LOGZERO outside a few candidates
+    planes = [(-torch.randint(0, 40, (n, V), generator=g).float() * 0.25), torch.full((n, V), LOGZERO), -torch.rand(n, V, generator=g) * 8]
+    live = torch.rand(n, V, generator=g) < (0.9 if V < 100 else 0.01)
+    planes[1][live] = -torch.randint(0, 16, (int(live.sum()),), generator=g).float() * 0.5
+    planes[2] = (planes[2] * 4).round() / 4
+    weights = [0.9, 0.1, 0.3]
+    run = -torch.randint(0, 6, (n,), generator=g).float() * 0.5
+    planes = [p.to(dev) for p in planes]
+    run = run.to(dev)
+    clip_of = torch.tensor([c for c, r in enumerate(rows) for _ in range(r)], dtype=torch.int32, device=dev)
+    w_prev, w_tok, w_total, w_vals, w_count = beam_select_reference(planes, weights, run, row_lo, beam, V)
+    got = []
+    for _ in range(2):
+        got.append(ops.beam_select(planes, weights, run, clip_of, torch.tensor(row_lo, dtype=torch.int32, device=dev),
+                                   torch.tensor(out_off, dtype=torch.int32, device=dev), beam=beam, V=V, max_rows=max(rows), out_rows=o))
+    prev, tok, total, vals, clip_out, count = got[0]
+    torch.cuda.synchronize()
+    assert count.tolist() == w_count
+    assert torch.equal(prev, w_prev) and torch.equal(tok, w_tok)
+    assert torch.equal(total.view(torch.int32), w_total.view(torch.int32))                  # bit for bit
+    assert torch.equal(vals, w_vals) and torch.equal(clip_out, clip_of[w_prev])
+    assert all(torch.equal(a, b) for a, b in zip(got[0], got[1]))                            # run to run
+    t = w_total.cpu()
+    ties = sum(int((t[row_lo_c : row_lo_c + k][1:] == t[row_lo_c : row_lo_c + k][:-1]).sum()) for row_lo_c, k in zip(out_off, w_count))
+    print(f"rows {rows[:4]}.. V {V} beam {beam}: {o} winners, {ties} exact ties among neighbours, {int((t < -1e8).sum())} LOGZERO winners")
+    assert ties > 0
+
+
+def test_beam_select_rejects_what_it_cannot_rank(dev):
+    from syncvsr_amd import ops
+
+    assert ops.beam_select_slices(5049, 40, 40) == 99 and ops.beam_select_slices(5049, 40, 82) > 0
+    assert ops.beam_select_slices(5049, 40, 83) == 0 and ops.beam_select_slices(41, 257, 1) == 0 and ops.beam_select_slices(5049, 1, 208) == 0
+    z = torch.zeros(83, 5049, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    with pytest.raises(ValueError, match="cannot rank"):
+        ops.beam_select([z], [1.0], z[:, 0].contiguous(), torch.zeros(83, **i32), torch.tensor([0, 83], **i32), torch.tensor([0], **i32), beam=40, V=5049,
+                        max_rows=83, out_rows=40)
+    with pytest.raises(ValueError, match="planes"):
+        ops.beam_select([z] * 5, [1.0] * 5, z[:, 0].contiguous(), torch.zeros(83, **i32), torch.tensor([0, 83], **i32), torch.tensor([0], **i32), beam=4,
+                        V=5049, max_rows=83, out_rows=4)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# svsr_ctc_prefix_score_clips
+# ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("tlens,V,per,S", [([16, 9, 5], 41, 3, 7), ([150, 37, 88, 4], 5049, 10, 60), ([37, 20], 300, 2, None)])
+def test_ctc_prefix_clips_kernel_matches_restatement_per_clip(dev, tlens, V, per, S):
+    """Tolerances of test_ctc_prefix_kernel_matches_restatement_over_several_steps; the padding of logp and r_prev is NaN throughout: a
+    read of it would surface in the outputs."""
+    from oracle import lrs_oracle as O
+    from syncvsr_amd import ops
+
+    g = torch.Generator().manual_seed(sum(tlens) + V)
+    C, Tmax, eos = len(tlens), max(tlens), V - 1
+    logp = torch.full((C, Tmax, V), float("nan"))
+    for c, T in enumerate(tlens):
+        logp[c, :T] = torch.log_softmax(2.0 * torch.randn(T, V, generator=g), dim=-1)
+    n = C * per
+    clip_of = torch.arange(C).repeat_interleave(per)
+    r_prev = torch.full((n, Tmax, 2), float("nan"))
+    for r in range(n):
+        T = tlens[clip_of[r]]
+        r_prev[r, :T, 0] = O.CTC_LOGZERO
+        r_prev[r, :T, 1] = torch.cumsum(logp[clip_of[r], :T, 0], 0)
+    last = torch.full((n,), eos, dtype=torch.int64)
+    tl = torch.tensor(tlens, dtype=torch.int32, device=dev)
+    for step in range(4):
+        ids = None if S is None else torch.stack([torch.randperm(V, generator=g)[:S] for _ in range(n)])
+        if ids is not None and step > 0:
+            ids[:, 0] = last
+            ids[0, 1], ids[1, 1] = eos, 0
+        r_new, psi = ops.ctc_prefix_score_clips(logp.to(dev), tl, r_prev.to(dev).contiguous(), last.to(dev), None if ids is None else ids.to(dev),
+                                                clip_of.to(dev, torch.int32), step, 0, eos)
+        torch.cuda.synchronize()
+        r_new, psi = r_new.cpu(), psi.cpu()
+        assert bool(torch.isfinite(r_new).all()) and bool(torch.isfinite(psi).all())
+        nxt = torch.full((n, Tmax, 2), float("nan"))
+        j = torch.randint(1 if S is None else 2, (S or V) - 1, (n,), generator=g)
+        for r in range(n):
+            c, T = int(clip_of[r]), tlens[clip_of[r]]
+            r_ref, psi_ref = O.ctc_prefix_score(logp[c, :T].double(), r_prev[r : r + 1, :T].double(), last[r : r + 1], None if ids is None else ids[r : r + 1],
+                                                step, 0, eos)
+            live = psi_ref[0] > -1e9
+            assert torch.equal(live, psi[r] > -1e9), (step, r)
+            np.testing.assert_allclose(psi[r].numpy()[live.numpy()], psi_ref[0].numpy()[live.numpy()], atol=2e-4, rtol=1e-5)
+            rl = r_ref[0] > -1e9
+            np.testing.assert_allclose(r_new[r, :, :T].numpy()[rl.numpy()], r_ref[0].numpy()[rl.numpy()], atol=5e-4, rtol=1e-5)
+            assert bool((r_new[r, :, :T][~rl] < -1e9).all()) and bool((r_new[r, :, T:] == O.CTC_LOGZERO).all())
+            nxt[r, :T] = r_ref[0, j[r]].float()
+        r_prev = nxt
+        last = (j if ids is None else ids[torch.arange(n), j]).long()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the searches
+# ----------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def tiny(dev):
+    from syncvsr_amd.lrs_model import E2E
+
+    args, odim, sd, clip, runs, gold = build_lrs_infer_case("lrs_infer_tiny")
+    model = E2E(odim, args)
+    model.load_state_dict(sd, strict=True)
+    model.to(dev).eval()
+    return model, args, odim, sd, clip, runs, gold
+
+
+def _derived(enc, seed=17):
+    """The clips of tests/test_lrs_search_clips_cpu.py: the golden encoder output, a truncation, two seeded perturbations (one truncated)."""
+    g = torch.Generator().manual_seed(seed)
+    T = enc.shape[0]
+    a = enc + 0.5 * torch.randn(enc.shape, generator=g, dtype=torch.float64).to(enc.dtype)
+    b = enc.flip(0) + 0.8 * torch.randn(enc.shape, generator=g, dtype=torch.float64).to(enc.dtype)
+    return [enc, enc[: (9 * T) // 16], a, b[: (5 * T) // 16]]
+
+
+def _pad(clips):
+    lens = [c.shape[0] for c in clips]
+    xs = torch.full((len(clips), max(lens), clips[0].shape[1]), 3.0, dtype=clips[0].dtype)         # (padding that would show if it were read)
+    for i, c in enumerate(clips):
+        xs[i, : lens[i]] = c
+    return xs, lens
+
+
+def test_decoder_step_with_per_row_clips_equals_the_single_clip_step(dev, tiny):
+    """Seven positions, rows re-ordered and dropped like the search does: the clip-aware step against `forward_one_step` on each clip's own
+    rows and unpadded memory, within the 3e-2 test_decoder_cache_steps_equal_prefix_recomputation allows between batch shapes."""
+    model, args, odim, sd, clip, runs, gold = tiny
+    sc = model.decoder._scorer()
+    clips = _derived(torch.from_numpy(gold["enc_feat"]))
+    xs, lens = _pad(clips)
+    sc.batch_init_state_clips(xs.to(dev), lens)
+    g = torch.Generator().manual_seed(2)
+    clip_of = torch.tensor([0, 0, 0, 1, 2, 2, 3, 3, 3, 3], dtype=torch.int32, device=dev)
+    n = clip_of.numel()
+    ys = torch.full((n, 1), odim - 1, dtype=torch.int64, device=dev)
+    states = None
+    for step in range(7):
+        logp, states = sc.batch_score_clips(ys, states, clip_of)
+        assert logp.shape == (n, odim) and states[0].shape == (n, ys.shape[1], 3 * model.ddim)
+        for c in range(4):
+            rows = torch.nonzero(clip_of == c).view(-1)
+            if rows.numel() == 0:
+                continue
+            mem = clips[c].to(dev).unsqueeze(0).expand(rows.numel(), -1, -1)
+            want, _ = sc.forward_one_step(ys[rows], None, mem, cache=None)
+            err = float((logp[rows] - want).abs().max())
+            assert err <= 3e-2, (step, c, err)
+        tok = torch.where(torch.arange(n, device=dev) % 2 == 0, logp.argmax(-1), torch.randint(0, odim - 1, (n,), generator=g).to(dev))
+        prev = torch.arange(n, device=dev)
+        if step == 2:
+            prev = torch.tensor([1, 0, 0, 4, 5, 8, 6], device=dev)              # clip 1 leaves, rows of the others are re-ordered inside their clip
+        ys = torch.cat((ys[prev], tok[prev].unsqueeze(1)), dim=1)
+        states = sc.select_states(states, prev, tok[prev])
+        clip_of = clip_of[prev].contiguous()
+        n = prev.numel()
+    with pytest.raises(ValueError, match="ddim"):
+        sc.batch_init_state_clips(xs[:, :, :-1].to(dev), lens)
+
+
+def _rescore(sd, args, odim, enc, yseq, ctcw, maxlen, lm_ref=None, lmw=0.0):
+    """Scores of one hypothesis under the fp64 scorers, accumulated along its own path (tests/test_gpu_lrs_infer.py, test_gpu_lrs_lm.py)."""
+    from oracle import lrs_oracle as O
+
+    dec, ctc = O.OracleDecoderScorer(sd, args), O.make_oracle_ctc_scorer(sd, odim - 1)
+    ctc.batch_init_state(enc)
+    y = torch.tensor([yseq[:1]])
+    state, tot = None, dict(decoder=0.0, ctc=0.0, lm=0.0)
+    for tok in yseq[1 : 1 + maxlen]:                      # a closing <eos> forced at the length limit is not scored
+        d, _ = dec.batch_score(y, [None], enc.unsqueeze(0))
+        c, pend = ctc.batch_score_partial(y, None, state, enc)
+        tot["decoder"] += float(d[0, tok])
+        tot["ctc"] += float(c[0, tok])
+        if lmw != 0:
+            tot["lm"] += float(lm_ref.batch_score(y, None, None)[0][0, tok])
+        state = ctc.select_states(pend, torch.tensor([0]), torch.tensor([tok]))
+        y = torch.cat((y, torch.tensor([[tok]])), dim=1)
+    return (1 - ctcw) * tot["decoder"] + ctcw * tot["ctc"] + lmw * tot["lm"], tot
+
+
+def _reference_search(sd64, args, odim, x64, beam, ctcw, lm_ref=None, lmw=0.0):
+    """The single-clip search under the fp64 scorers (tests/test_lrs_infer_cpu.py ties it to the reference's own n-best)."""
+    from oracle import lrs_oracle as O
+    from syncvsr_amd.lrs_infer import get_beam_search_decoder
+
+    class _M:
+        pass
+
+    m = _M()
+    m.odim = odim
+    bs = get_beam_search_decoder(m, [f"t{i}" for i in range(odim)], ctc_weight=ctcw, beam_size=beam,
+                                 scorers=dict(decoder=O.OracleDecoderScorer(sd64, args), ctc=O.make_oracle_ctc_scorer(sd64, odim - 1)))
+    return bs.forward(x64)
+
+
+def _check_clip(nbest, ref, sd64, args, odim, x64, beam, ctcw, where, margin=0.05, lm_ref=None, lmw=0.0):
+    """The per-clip criteria of test_beam_search_on_the_gpu_finds_the_reference_hypotheses."""
+    want, gs = ref[0].yseq.tolist(), [h.score for h in ref]
+    second = gs[1] if len(gs) > 1 else -1e30
+    print(f"{where}: hip best {nbest[0].yseq.tolist()} {nbest[0].score:.4f} | reference {want} {gs[0]:.4f} (2nd {second:.4f})")
+    if gs[0] - second > 0.2 and beam >= 5:
+        assert nbest[0].yseq.tolist() == want, (where, nbest[0].yseq.tolist(), want)
+        assert abs(nbest[0].score - gs[0]) <= 2e-2 * abs(gs[0]) + 0.05
+    else:
+        assert nbest[0].score >= gs[0] - margin * abs(gs[0])
+    for h in nbest[:3]:
+        tot, parts = _rescore(sd64, args, odim, x64, h.yseq.tolist(), ctcw, x64.shape[0], lm_ref, lmw)
+        d = h.asdict()
+        assert abs(d["score"] - tot) <= 2e-2 * abs(tot) + 0.05, (where, d, tot)
+        for k in ("decoder", "ctc") + (("lm",) if lmw != 0 else ()):
+            assert abs(d["scores"][k] - parts[k]) <= 2e-2 * abs(parts[k]) + 0.05, (where, k, d, parts)
+    assert all(nbest[i].score >= nbest[i + 1].score for i in range(len(nbest) - 1))
+    assert all(h.yseq[0] == odim - 1 and h.yseq[-1] == odim - 1 for h in nbest)
+
+
+def _no_boundary_ties(monkeypatch):
+    """torch.topk stays for the pre-beam: only the SET of candidates reaches the search (the CTC scorer scatters them into a full plane),
+    so its tie order could change a result only through a tie between the last candidate kept and the first one left out."""
+    inner = torch.topk
+    seen = []
+
+    def topk(x, k, dim=-1, *a, **kw):
+        if x.dim() == 2 and k < x.shape[-1]:
+            v = inner(x, k + 1, dim=dim)[0]
+            assert bool((v[:, k - 1] > v[:, k]).all()), "a tie at the pre-beam boundary: torch.topk's tie order would matter on these inputs"
+            seen.append(x.shape[0])
+        return inner(x, k, dim, *a, **kw)
+
+    monkeypatch.setattr(torch, "topk", topk)
+    return seen
+
+
+def test_forward_clips_tiny_model_four_clips(dev, tiny, monkeypatch):
+    from syncvsr_amd.lrs_infer import get_beam_search_decoder
+
+    model, args, odim, sd, clip, runs, gold = tiny
+    sd64 = {k: v.double() if v.is_floating_point() else v for k, v in sd.items()}
+    tokens = [f"t{i}" for i in range(odim)]
+    clips = _derived(torch.from_numpy(gold["enc_feat"]))
+    xs, lens = _pad(clips)
+    seen = _no_boundary_ties(monkeypatch)
+    for r, (beam, ctcw) in enumerate(runs):
+        bs = get_beam_search_decoder(model, tokens, ctc_weight=ctcw, beam_size=beam)
+        got = bs.forward_clips(xs.to(dev), torch.tensor(lens))
+        again = bs.forward_clips(xs.to(dev), lens)
+        assert len(got) == 4
+        for c in range(4):
+            ref = _reference_search(sd64, args, odim, clips[c].double(), beam, ctcw)
+            _check_clip(got[c], ref, sd64, args, odim, clips[c].double(), beam, ctcw, f"run{r} clip{c}")
+            assert [h.asdict() for h in got[c]] == [h.asdict() for h in again[c]]                  # run to run
+        gy = gold[f"run{r}.yseq"]                                                                    # clip 0 is the reference's own clip
+        if gold[f"run{r}.score"][0] - gold[f"run{r}.score"][1] > 0.2 and beam >= 5:
+            assert got[0][0].yseq.tolist() == gy[0][gy[0] >= 0].tolist()
+        # one clip through forward_clips is the search `forward` runs: same hypotheses, scores within the bound between batch shapes
+        one = bs.forward_clips(clips[1].unsqueeze(0).to(dev), [lens[1]])[0]
+        single = bs.forward(clips[1].to(dev))
+        assert one[0].yseq.tolist() == single[0].yseq.tolist() and abs(one[0].score - single[0].score) <= 2e-2 * abs(single[0].score) + 0.05
+    assert seen, "the pre-beam never ran"
+    with pytest.raises(ValueError, match="lengths"):
+        bs.forward_clips(xs.to(dev), [lens[0] + 1] + lens[1:])
+    # clips -> encoder -> search (decode_clips), against the search on the encoder output of the clip alone
+    from syncvsr_amd.lrs_infer import decode_clips
+
+    bs = get_beam_search_decoder(model, tokens, ctc_weight=0.1, beam_size=30)
+    T = clip.shape[0]
+    batch = torch.zeros(2, T, *clip.shape[1:])
+    batch[0], batch[1, : T - 5] = clip, clip[: T - 5]
+    out = decode_clips(model, bs, batch.to(dev), [T, T - 5])
+    gy = gold["run1.yseq"]
+    assert out[0][0].yseq.tolist() == gy[0][gy[0] >= 0].tolist()
+    assert abs(out[0][0].score - gold["run1.score"][0]) <= 0.05 * abs(gold["run1.score"][0])
+    enc1, _ = model.encoder(clip[: T - 5].unsqueeze(0).to(dev), None)
+    alone = bs.forward(enc1.squeeze(0))
+    assert abs(out[1][0].score - alone[0].score) <= 0.05 * abs(alone[0].score) and len(out[1][0].yseq) <= T - 5 + 2
+
+
+def test_forward_clips_shipped_model_beside_two_shorter_clips(dev):
+    """The 252 M-parameter model, 5,049 units, beam 40, CTC weight 0.1: the golden clip as clip 0 beside two shorter derived clips.  Clip 0
+    under test_shipped_model_with_the_reference_search_settings' criteria; every clip's reported scores equal the fp64 re-scoring."""
+    from syncvsr_amd.lrs_infer import get_beam_search_decoder
+    from syncvsr_amd.lrs_model import E2E
+
+    args, odim, sd, clip, runs, gold = build_lrs_infer_case("lrs_infer_full")
+    model = E2E(odim, args)
+    model.load_state_dict(sd, strict=True)
+    model.to(dev).eval()
+    g_enc = torch.from_numpy(gold["enc_feat"])
+    d = _derived(g_enc, seed=23)
+    clips = [g_enc, d[1], d[3]]
+    xs, lens = _pad(clips)
+    beam, ctcw = runs[0]
+    bs = get_beam_search_decoder(model, [f"t{i}" for i in range(odim)], ctc_weight=ctcw, beam_size=beam)
+    got = bs.forward_clips(xs.to(dev), lens)
+    gs = gold["run0.score"]
+    print(f"clip 0: hip best {got[0][0].score:.4f} ({len(got[0][0].yseq)} tokens) | reference {gs[0]:.4f} (2nd {gs[1]:.4f})")
+    assert got[0][0].score >= gs[0] - 0.02 * abs(gs[0])
+    sd64 = {k: v.double() if v.is_floating_point() else v for k, v in sd.items()}
+    for c in range(3):
+        tot, parts = _rescore(sd64, args, odim, clips[c].double(), got[c][0].yseq.tolist(), ctcw, lens[c])
+        h = got[c][0].asdict()
+        print(f"clip {c}: {h['score']:.4f} (fp64 {tot:.4f})")
+        assert abs(h["score"] - tot) <= 2e-2 * abs(tot) + 0.05, (c, h["score"], tot)
+        assert abs(h["scores"]["decoder"] - parts["decoder"]) <= 2e-2 * abs(parts["decoder"]) + 0.05
+        assert abs(h["scores"]["ctc"] - parts["ctc"]) <= 2e-2 * abs(parts["ctc"]) + 0.05
+        single = bs.forward(clips[c].to(dev))
+        assert got[c][0].score >= single[0].score - 0.02 * abs(single[0].score)
+
+
+def test_forward_clips_with_the_language_model(dev, tiny):
+    """`lrs_lm_tiny`, lm_weight > 0, three clips: per clip the criteria of test_lm_fused_beam_search_finds_the_reference_hypotheses against the
+    fp64 single-clip search, and the pool sized for C x beam rows never had to grow."""
+    from lm_cases import LM_RUNS, lm_case
+    from lm_restatement import LMRestatement
+    from syncvsr_amd.lrs_infer import get_beam_search_decoder
+    from syncvsr_amd.lrs_lm import LMPool, TransformerLM
+
+    model, args, odim, sd, clip, runs, _ = tiny
+    conf, V, lsd, gold = lm_case("lrs_lm_tiny")
+    lm = TransformerLM(V, conf)
+    lm.load_state_dict(lsd, strict=True)
+    lm.to(dev)
+    lm_ref = LMRestatement(lsd, conf)
+    sd64 = {k: v.double() if v.is_floating_point() else v for k, v in sd.items()}
+    clips = _derived(torch.from_numpy(gold["enc_feat"]))[:3]
+    xs, lens = _pad(clips)
+    tokens = [f"t{i}" for i in range(odim)]
+    pools = []
+    inner = LMPool.__init__
+
+    def spy(self, *a, **k):
+        inner(self, *a, **k)
+        pools.append(self)
+
+    LMPool.__init__ = spy
+    try:
+        ran = 0
+        for r, (beam, ctcw, lmw) in enumerate(LM_RUNS):
+            if lmw == 0:
+                continue
+            ran += 1
+            bs = get_beam_search_decoder(model, tokens, rnnlm=lm, ctc_weight=ctcw, lm_weight=lmw, beam_size=beam)
+            del pools[:]
+            got = bs.forward_clips(xs.to(dev), lens)
+            assert len(pools) == 1 and pools[0].grown == 0 and pools[0].capacity == 3 * beam * (max(lens) + 1), (len(pools), pools[0].grown)
+            for c in range(3):
+                from oracle import lrs_oracle as O
+                from syncvsr_amd.lrs_infer import BatchBeamSearch, LengthBonus
+
+                ref = BatchBeamSearch(beam_size=beam, vocab_size=odim, weights={"decoder": 1 - ctcw, "ctc": ctcw, "lm": lmw, "length_bonus": 0},
+                                      scorers=dict(decoder=O.OracleDecoderScorer(sd64, args), ctc=O.make_oracle_ctc_scorer(sd64, odim - 1), lm=lm_ref,
+                                                   length_bonus=LengthBonus(odim)), sos=odim - 1, eos=odim - 1, pre_beam_score_key="decoder")
+                _check_clip(got[c], ref.forward(clips[c].double()), sd64, args, odim, clips[c].double(), beam, ctcw, f"lm run{r} clip{c}",
+                            lm_ref=lm_ref, lmw=lmw)
+                assert "lm" in got[c][0].scores
+        assert ran >= 1
+    finally:
+        LMPool.__init__ = inner

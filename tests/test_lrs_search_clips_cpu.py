@@ -1,0 +1,236 @@
+"""Multi-clip beam search on CPU: `BatchBeamSearch.forward_clips` (syncvsr_amd/lrs_infer.py) driven by the oracle's fp64 scorers through
+`PerClipScorers` must return, for every clip of a padded batch, exactly what `forward` returns for that clip alone — and for the golden
+clip what the reference's own search returned (tests/golden/lrs_infer_tiny.npz).  fp64 and the same scorer calls: there is no rounding
+excuse, the bound is 1e-9.  Also here: the torch statement of the selection step against a brute-force stable sort on planes with exact
+ties, the row order after a finished clip's rows are dropped, and the grouping of a batch under the workspace bound."""
+import numpy as np
+import pytest
+import torch
+
+from golden_cases import build_lrs_infer_case
+
+
+def _clips(gold):
+    """Four clips of different lengths from the golden encoder output: itself, a truncation, two seeded perturbations (one truncated)."""
+    enc = torch.from_numpy(gold["enc_feat"]).double()
+    g = torch.Generator().manual_seed(17)
+    a = enc + 0.5 * torch.randn(enc.shape, generator=g, dtype=torch.float64)
+    b = enc.flip(0) + 0.8 * torch.randn(enc.shape, generator=g, dtype=torch.float64)
+    clips = [enc, enc[:9], a, b[:5]]
+    lens = [c.shape[0] for c in clips]
+    xs = torch.zeros(len(clips), max(lens), enc.shape[1], dtype=torch.float64)
+    for i, c in enumerate(clips):
+        xs[i, : lens[i]] = c
+    return clips, xs, lens
+
+
+def _searches(sd, args, odim, beam, ctcw):
+    """(single-clip search over the raw oracle scorers, multi-clip search over the same scorers behind PerClipScorers)"""
+    from oracle import lrs_oracle as O
+    from syncvsr_amd.lrs_infer import PerClipScorers, get_beam_search_decoder
+
+    class _M:
+        pass
+
+    m = _M()
+    m.odim = odim
+    tokens = [f"t{i}" for i in range(odim)]
+    one = get_beam_search_decoder(m, tokens, ctc_weight=ctcw, beam_size=beam,
+                                  scorers=dict(decoder=O.OracleDecoderScorer(sd, args), ctc=O.make_oracle_ctc_scorer(sd, odim - 1)))
+    many = get_beam_search_decoder(m, tokens, ctc_weight=ctcw, beam_size=beam,
+                                   scorers=dict(decoder=PerClipScorers(O.OracleDecoderScorer(sd, args)),
+                                                ctc=PerClipScorers(O.make_oracle_ctc_scorer(sd, odim - 1))))
+    return one, many
+
+
+def _same_nbest(got, want, where):
+    assert len(got) == len(want), (where, len(got), len(want))
+    for i, (g, w) in enumerate(zip(got, want)):
+        assert g.yseq.tolist() == w.yseq.tolist(), (where, i, g.yseq.tolist(), w.yseq.tolist())
+        assert abs(g.score - w.score) <= 1e-9, (where, i, g.score, w.score)
+        assert set(g.scores) == set(w.scores)
+        for k in w.scores:
+            assert abs(g.scores[k] - w.scores[k]) <= 1e-9, (where, i, k, g.scores[k], w.scores[k])
+
+
+@pytest.fixture(scope="module")
+def case():
+    args, odim, sd, clip, runs, gold = build_lrs_infer_case("lrs_infer_tiny")
+    sd = {k: v.double() if v.is_floating_point() else v for k, v in sd.items()}
+    return args, odim, sd, runs, gold
+
+
+def test_forward_clips_equals_forward_per_clip_and_the_reference_nbest(case):
+    args, odim, sd, runs, gold = case
+    clips, xs, lens = _clips(gold)
+    assert len(lens) >= 4 and len(set(lens)) >= 3
+    for r, (beam, ctcw) in enumerate(runs):
+        one, many = _searches(sd, args, odim, beam, ctcw)
+        live = []                                                # rows per clip before every position
+        inner = many._search_clips
+
+        def spy(run, scorers, rows, dtype, inner=inner, live=live):
+            live.append(list(rows))
+            return inner(run, scorers, rows, dtype)
+
+        many._search_clips = spy
+        got = many.forward_clips(xs, torch.tensor(lens))
+        assert len(got) == len(clips)
+        for c, x in enumerate(clips):
+            _same_nbest(got[c], one.forward(x), (r, c))
+        # the golden clip: the reference's own n-best, as tests/test_lrs_infer_cpu.py asserts it
+        nbest = got[0]
+        assert len(nbest) == int(gold[f"run{r}.n_ended"])
+        gy = gold[f"run{r}.yseq"]
+        for i in range(gy.shape[0]):
+            want = gy[i][gy[i] >= 0]
+            assert nbest[i].yseq.tolist() == want.tolist(), (r, i)
+            assert abs(nbest[i].score - gold[f"run{r}.score"][i]) < 1e-4
+            assert abs(nbest[i].scores["decoder"] - gold[f"run{r}.score_decoder"][i]) < 1e-4
+            assert abs(nbest[i].scores["ctc"] - gold[f"run{r}.score_ctc"][i]) < 1e-4
+        # the inputs do what the test is about: clips leave the search at different positions, and one of them at its own length limit
+        last = [max(i for i, rows in enumerate(live) if rows[c] > 0) for c in range(len(clips))]
+        print(f"run{r}: beam {beam} ctc {ctcw}: last position per clip {last}, lengths {lens}")
+        assert len(set(last)) >= 2, last
+        assert any(last[c] == lens[c] - 1 for c in range(len(clips))), (last, lens)
+        # rows stay grouped by clip, in clip order, while clips drop out: every position's row counts are bounded by the beam
+        assert all(0 <= n <= beam for rows in live for n in rows)
+        assert any(rows[c] == 0 and any(rows[d] > 0 for d in range(c + 1, len(clips))) for rows in live for c in range(len(clips))), \
+            "no clip in front of a live one ever finished: the row order after a drop was not exercised"
+
+
+def test_one_clip_equals_forward_and_groups_under_the_workspace_bound_change_nothing(case):
+    args, odim, sd, runs, gold = case
+    clips, xs, lens = _clips(gold)
+    beam, ctcw = runs[0]
+    one, many = _searches(sd, args, odim, beam, ctcw)
+    for c in (0, 3):
+        got = many.forward_clips(clips[c].unsqueeze(0), [lens[c]])
+        assert len(got) == 1
+        _same_nbest(got[0], one.forward(clips[c]), c)
+    whole = many.forward_clips(xs, lens)
+    # the documented bound: rows * candidates * Tmax * 2 fp32 of the CTC scorer's pending state per group
+    per_clip = beam * many.pre_beam_size * max(lens) * 8
+    assert many.do_pre_beam and many.clips_per_group(max(lens)) == (2 << 30) // per_clip
+    many.clip_workspace_bytes = 2 * per_clip + 1                   # two clips fit, three do not
+    assert many.clips_per_group(max(lens)) == 2
+    grouped = many.forward_clips(xs, lens)
+    for c in range(len(clips)):
+        _same_nbest(grouped[c], whole[c], ("grouped", c))
+    many.clip_workspace_bytes = 1                                  # not even one fits: one clip per group, never zero
+    assert many.clips_per_group(max(lens)) == 1
+    # full-vocabulary partial scoring (ctc_weight == 1.0): no pre-beam, the bound counts every unit
+    _, full = _searches(sd, args, odim, 3, 1.0)
+    assert not full.do_pre_beam and full.clips_per_group(150) == (2 << 30) // (3 * odim * 150 * 8)
+    got = full.forward_clips(xs[:2], lens[:2])
+    ref, _ = _searches(sd, args, odim, 3, 1.0)
+    for c in range(2):
+        _same_nbest(got[c], ref.forward(clips[c]), ("ctc only", c))
+
+
+def test_unsupported_use_raises(case):
+    args, odim, sd, runs, gold = case
+    clips, xs, lens = _clips(gold)
+    _, many = _searches(sd, args, odim, 4, 0.1)
+    with pytest.raises(ValueError, match="lengths"):
+        many.forward_clips(xs, [lens[0] + 1] + lens[1:])
+    with pytest.raises(ValueError, match="lengths"):
+        many.forward_clips(xs, [0] + lens[1:])
+    with pytest.raises(ValueError, match="lengths"):
+        many.forward_clips(xs, lens[:-1])
+    with pytest.raises(ValueError):
+        many.forward_clips(xs[0], lens[:1])
+
+
+def _brute_force(planes, weights, run, row_lo, beam, V):
+    """Python restatement: totals accumulated in the statement's order, then a stable sort of (-(total), row, token) per clip."""
+    tot = torch.zeros((run.numel(), V), dtype=run.dtype)
+    for w, s in zip(weights, planes):
+        tot = tot + w * s
+    tot = tot + run.unsqueeze(1)
+    prev, tok, count = [], [], []
+    for c in range(len(row_lo) - 1):
+        items = [(-float(tot[r, v]), r, v) for r in range(row_lo[c], row_lo[c + 1]) for v in range(V)]
+        items.sort()                                             # tuples: higher total first, then the lower row, then the lower token
+        items = items[: min(beam, len(items))]
+        count.append(len(items))
+        prev += [r for _, r, _ in items]
+        tok += [v for _, _, v in items]
+    return prev, tok, count, tot
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+def test_selection_statement_against_a_brute_force_sort_with_exact_ties(dtype):
+    from syncvsr_amd.lrs_infer import LOGZERO, beam_select_reference
+
+    g = torch.Generator().manual_seed(3)
+    ties = 0
+    for rows, V, beam in ([1], 7, 5), ([3, 0, 2, 5], 11, 6), ([2, 2], 3, 40), ([4, 1, 3], 29, 8):
+        n = sum(rows)
+        row_lo = [0]
+        for r in rows:
+            row_lo.append(row_lo[-1] + r)
+        # few distinct values: exact ties everywhere, inside rows, across rows of a clip and across clips; plus LOGZERO entries
+        planes = [torch.randint(-1, 2, (n, V), generator=g).to(dtype) * 0.5 for _ in range(3)]
+        planes[1][torch.rand(n, V, generator=g) < 0.3] = LOGZERO
+        weights = [0.5, 0.25, 2.0]
+        run = torch.randint(-2, 2, (n,), generator=g).to(dtype)
+        prev, tok, total, vals, count = beam_select_reference(planes, weights, run, row_lo, beam, V)
+        w_prev, w_tok, w_count, tot = _brute_force(planes, weights, run, row_lo, beam, V)
+        assert count == w_count == [min(beam, r * V) for r in rows]
+        assert prev.tolist() == w_prev and tok.tolist() == w_tok, (rows, V, beam)
+        assert torch.equal(total, tot[prev, tok])
+        for j in range(3):
+            assert torch.equal(vals[j], planes[j][prev, tok])
+        ties += sum(1 for i in range(1, len(w_prev)) if float(tot[w_prev[i], w_tok[i]]) == float(tot[w_prev[i - 1], w_tok[i - 1]]))
+    assert ties >= 8, "the planes must hold exact ties among the winners"
+
+
+def test_row_order_after_a_finished_clip_is_dropped():
+    """Scripted scorer: clip 1 of three ends at the second position while its neighbours go on.  The rows of clips 0 and 2 must then be
+    adjacent, in clip order, each clip's rows in score order — and both clips must go on being scored with their own encoder output."""
+    from syncvsr_amd.lrs_infer import BatchBeamSearch, PerClipScorers
+
+    V, eos = 6, 5
+    seen = []
+
+    class Scripted:
+        def batch_init_state(self, x):
+            return None
+
+        def batch_score(self, ys, states, xs):
+            n, L = ys.shape
+            tag = int(xs[0, 0, 0])                               # the clip's identity travels in its encoder output
+            seen.append((L, tag, n))
+            sc = torch.full((n, V), -20.0, dtype=torch.float64)
+            if tag == 1 and L >= 2:
+                sc[:, eos] = -0.1                                # clip 1: everything ends at the second position
+            else:
+                sc[:, 1], sc[:, 2] = -0.5 - 0.01 * tag, -0.7 - 0.01 * tag - 0.013 * L      # (position dependent: no two paths tie)
+                if L >= 4:
+                    sc[:, eos] = -0.1
+            return sc, None
+
+        def select_states(self, states, prev, tok):
+            return None
+
+    xs = torch.zeros(3, 8, 2, dtype=torch.float64)
+    for c in range(3):
+        xs[c, :, 0] = c
+    bs = BatchBeamSearch(beam_size=2, vocab_size=V, weights=dict(s=1.0), scorers=dict(s=PerClipScorers(Scripted())), sos=eos, eos=eos)
+    calls = []
+    inner = bs._search_clips
+
+    def spy(run, scorers, rows, dtype):
+        calls.append((list(rows), run["clip_of"].tolist()))
+        return inner(run, scorers, rows, dtype)
+
+    bs._search_clips = spy
+    out = bs.forward_clips(xs, [8, 8, 8])
+    single = BatchBeamSearch(beam_size=2, vocab_size=V, weights=dict(s=1.0), scorers=dict(s=Scripted()), sos=eos, eos=eos)
+    for c in range(3):
+        _same_nbest(out[c], single.forward(xs[c]), c)
+    assert calls[0] == ([1, 1, 1], [0, 1, 2]) and calls[1] == ([2, 2, 2], [0, 0, 1, 1, 2, 2])
+    assert ([2, 0, 2], [0, 0, 2, 2]) in calls                  # clip 1 gone: its neighbours' rows close up, in clip order
+    assert out[1] and all(len(h.yseq) == 3 for h in out[1]) and all(len(h.yseq) > 3 for h in out[0] + out[2])
+    assert len(calls) == 4                                        # well before the length limit of 8: the clips ended on their own
