@@ -543,6 +543,32 @@ int svsr_scale_bf16(const void* x, void* y, int64_t n, float alpha, const unsign
 int svsr_mha_table_fwd(const void* pool, int pool_rows, int64_t pitch, const int* table, int table_pitch, int n, int Lq, int L, int H, float scale, void* ctx, int64_t ctx_pitch, hipStream_t stream);
 int svsr_lm_embed_fwd(const void* x, int64_t x_pitch, const float* gamma, const float* beta, const float* pe, int pe_rows, const int* pos, int R, int D, float eps, float scale, void* out, hipStream_t stream);
 
+/* ---- dense temporal back-end of the DC-TCN word-level model (dctcn.hip; syncvsr_amd/dctcn.py, eval path) ---------------------
+ * Replaces DenseTemporalConvNet.forward (reference LRW/video/src/tcn/models/densetcn.py:38-192, se_module.py:8-23) and the consensus of
+ * DCTCNLightningModule.forward (lightning.py:278-279).  Activations are channels-last bf16 rows [B*T][pitch]; a layer reads the first n_in
+ * channels of a row and writes its channels at an offset, so a dense block's `torch.cat(features, 1)` is one buffer and never a copy.
+ *
+ * svsr_tconv_fwd: nb (1..3) dilated temporal convolutions of the same rows in one launch.  `branches` is a HOST table of nb x 8 64-bit
+ * words, read during the call only: {k, w, gate, scale, shift, slope, out_off, res_off} — k odd in 1..7; w bf16 [co][k][n_in] (tap-major
+ * within an output channel); gate fp32 [B][n_in] or 0; scale / shift fp32 [co] (BatchNorm(eval) and the conv bias folded: the bf16
+ * weights stay unscaled); slope fp32 [co] (act 3 only).  For branch i, row (b, t), channel c < co:
+ *   y = act(scale[c] * sum_{j < k} sum_{ci < n_in} bf16(gate[b][ci] * x[b][t + (j - (k-1)/2) * d][ci]) * w[c][j][ci] + shift[c])
+ *   out[b*T + t][out_off + c] = bf16(res ? res_act(y + res[b*T + t][res_off + c]) : y)
+ * with rows outside [0, T) of the SAME clip contributing zero ("same" padding per clip: Conv1d(padding = (k-1)d) + symmetric Chomp1d);
+ * fp32 accumulation on MFMA; act: 0 none, 1 ReLU, 2 Swish, 3 PReLU; res_act: 0 none, 2 Swish; res bf16 rows of res_pitch.  out may be the
+ * buffer x points into when the written channels lie behind n_in.  Taken: any B, T >= 1; n_in a multiple of 64 (>= 64); co a multiple of
+ * 64; d >= 1 with (k - 1) * d / 2 <= 16; x and w 16-byte aligned, x_pitch a multiple of 8.  Anything else: SVSR_ERR_ARG.
+ *
+ * svsr_tcn_se_fwd: the nb squeeze-and-excitation gates of a layer: m = mean over t of x[b][t][:n_in] (computed once), gate[i][b] =
+ * sigmoid(W2_i swish(W1_i m)); w1 bf16 [nb][R][n_in], w2 bf16 [nb][n_in][R], gate fp32 [nb][B][n_in]; R a multiple of 4, n_in a multiple
+ * of 64 up to 8192.
+ *
+ * svsr_tcn_norm_pool_fwd: h bf16 [B*T][C] = x * scale + shift (norm5); pooled bf16 [B][C] = sum_t h * mask[b][t] / (sum_t mask[b][t] + 1e-6)
+ * over the stored h, mask fp32 [B][T]; C a multiple of 8. */
+int svsr_tconv_fwd(const void* x, int64_t x_pitch, int B, int T, int n_in, int d, int nb, const int64_t* branches, int co, int act, void* out, int64_t out_pitch, const void* res, int64_t res_pitch, int res_act, hipStream_t stream);
+int svsr_tcn_se_fwd(const void* x, int64_t x_pitch, int B, int T, int n_in, int R, int nb, const void* w1, const void* w2, float* gate, hipStream_t stream);
+int svsr_tcn_norm_pool_fwd(const void* x, int64_t x_pitch, int B, int T, int C, const float* scale, const float* shift, const float* mask, void* h, void* pooled, hipStream_t stream);
+
 /* ---- multi-clip beam search (lrs_search.hip; BatchBeamSearch.forward_clips of syncvsr_amd/lrs_infer.py) -----------------
  * C clips advance through one search in lock step.  The n live hypotheses are rows grouped by clip: clip_of int32 [n] is non-decreasing,
  * clip c owns rows row_lo[c] .. row_lo[c + 1] - 1 (row_lo int32 [C + 1]; an empty range: the clip has finished).

@@ -1,0 +1,192 @@
+"""Eval forward of the DC-TCN word-level model (syncvsr_amd/dctcn.py) beside a torch eager bf16 module built from the SAME state dict, in
+the same process on the same device: the back-end alone (front-end features in, word logits out) and the whole forward (videos in, logits
+out) at B = 96 and B = 32, T = 29, 96 x 96.
+
+    python scripts/dctcn_bench.py [--batches 96,32] [--rounds 7] [--iters 50] [--out profiles/dctcn_eval.json]
+    rocprofv3 --kernel-trace --stats -d <dir> -- python scripts/dctcn_bench.py --profile-only        # kernel table, in a run of its own
+
+Times are wall-clock between device synchronisations (host dispatch included), the two implementations ALTERNATING round by round after
+warm-up of every shape; per implementation the median over rounds of the mean of `--iters` calls, and the minimum.  The convolution
+event figures (tconv_ms, se_ms: device events around the host calls, ops.start_event_timing) include dispatch gaps and are NOT kernel times:
+kernel time comes from the rocprofv3 run above.  The convolution FLOPs from the shapes (2 * rows * n_in * k *
+co per branch), the peak from --peak-tflops (dense bf16 of the device).  Prints one JSON line and writes it to --out.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+
+TCN = "model.tcn.tcn_trunk.features"
+
+
+class EagerDCTCN:
+    """Plain torch eager, bf16 weights and activations ([B, C, T] as torch's Conv1d wants), BatchNorm in eval mode: the baseline."""
+
+    def __init__(self, sd: dict, dims: dict, dev):
+        self.W = {k: (v.to(dev).to(torch.bfloat16) if v.is_floating_point() else v.to(dev)) for k, v in sd.items()}
+        self.dims = dims
+
+    def bn(self, x, p):
+        W = self.W
+        return F.batch_norm(x, W[f"{p}.running_mean"], W[f"{p}.running_var"], W[f"{p}.weight"], W[f"{p}.bias"], False, 0.0, 1e-5)
+
+    def frontend(self, videos):
+        W = self.W
+        B, _, T = videos.shape[:3]
+        h = F.conv3d(videos.to(torch.bfloat16), W["model.frontend3D.0.weight"], None, stride=(1, 2, 2), padding=(2, 3, 3))
+        h = F.max_pool3d(F.silu(self.bn(h, "model.frontend3D.1")), (1, 3, 3), (1, 2, 2), (0, 1, 1))
+        h = h.transpose(1, 2).reshape(B * T, 64, h.size(3), h.size(4))
+        for li in range(1, 5):
+            for bi in range(2):
+                p = f"model.trunk.layer{li}.{bi}"
+                stride = 2 if (bi == 0 and li > 1) else 1
+                o = F.silu(self.bn(F.conv2d(h, W[f"{p}.conv1.weight"], None, stride=stride, padding=1), f"{p}.bn1"))
+                o = self.bn(F.conv2d(o, W[f"{p}.conv2.weight"], None, stride=1, padding=1), f"{p}.bn2")
+                r = self.bn(F.conv2d(h, W[f"{p}.downsample.0.weight"], None, stride=stride), f"{p}.downsample.1") if f"{p}.downsample.0.weight" in W else h
+                h = F.silu(o + r)
+        return h.mean((2, 3)).view(B, T, 512)
+
+    def backend(self, feats, word_mask, attention_mask):
+        W, dm = self.W, self.dims
+        x = feats
+        if dm["in_size"] == 513:
+            x = torch.cat([x, word_mask.to(x.dtype).unsqueeze(2)], dim=-1)
+        x = x.transpose(1, 2)
+        p = f"{TCN}.transition0"
+        x = F.prelu(self.bn(F.conv1d(x, W[f"{p}.conv.weight"]), f"{p}.norm"), W[f"{p}.prelu.weight"])
+        ks, ds = dm["ks"], dm["ds"]
+        for bi, nl in enumerate(dm["blocks"]):
+            feats_list = [x]
+            for li in range(nl):
+                p = f"{TCN}.denseblock{bi + 1}.denselayer{li + 1}"
+                d = ds[li % len(ds)]
+                xc = torch.cat(feats_list, 1)
+                outs = []
+                for ki, k in enumerate(ks):
+                    y = xc.mean(2)
+                    y = torch.sigmoid(F.linear(F.silu(F.linear(y, W[f"{p}.cbcr0_se_{ki}.fc.0.weight"])), W[f"{p}.cbcr0_se_{ki}.fc.2.weight"]))
+                    c = F.conv1d(xc * y.unsqueeze(2), W[f"{p}.cbcr0_{ki}.net.0.weight"], W[f"{p}.cbcr0_{ki}.net.0.bias"], padding=(k - 1) * d, dilation=d)
+                    c = self.bn(c, f"{p}.cbcr0_{ki}.net.1")
+                    outs.append(F.silu(c[:, :, (k - 1) * d // 2: c.size(2) - (k - 1) * d // 2].contiguous()))
+                o0 = torch.cat(outs, 1)
+                outs = []
+                for ki, k in enumerate(ks):
+                    c = F.conv1d(o0, W[f"{p}.cbcr1_{ki}.net.0.weight"], W[f"{p}.cbcr1_{ki}.net.0.bias"], padding=(k - 1) * d, dilation=d)
+                    c = self.bn(c, f"{p}.cbcr1_{ki}.net.1")
+                    outs.append(F.silu(c[:, :, (k - 1) * d // 2: c.size(2) - (k - 1) * d // 2].contiguous()))
+                res = F.conv1d(xc, W[f"{p}.downsample.weight"], W[f"{p}.downsample.bias"])
+                feats_list.append(F.silu(torch.cat(outs, 1) + res))
+            x = torch.cat(feats_list, 1)
+            if bi != len(dm["blocks"]) - 1:
+                p = f"{TCN}.transition{bi + 1}"
+                x = F.silu(self.bn(F.conv1d(x, W[f"{p}.conv.weight"]), f"{p}.norm"))
+        h = self.bn(x, f"{TCN}.norm5")
+        am = attention_mask.to(h.dtype)
+        pooled = (h * am.unsqueeze(1)).sum(2) / (am.sum(1, keepdim=True) + 1e-6)
+        return F.linear(pooled, W["video_classifier.weight"], W["video_classifier.bias"]).float()
+
+
+def _time(fn, iters: int) -> float:
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / iters
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", default="96,32")
+    ap.add_argument("--frames", type=int, default=29)
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--peak-tflops", type=float, default=2500.0, help="dense bf16 peak of the device (MI355X: 2.5 PFLOP/s)")
+    ap.add_argument("--profile-only", action="store_true", help="a few untimed forwards per shape (for a rocprofv3 run of its own)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dctcn_eval.json"))
+    a = ap.parse_args()
+    from syncvsr_amd import ops
+    from syncvsr_amd.dctcn import DCTCNLightningModule
+    from syncvsr_amd.dctcn_init import dctcn_dims, dctcn_init_state_dict, dctcn_synthetic_batch, default_dctcn_config
+
+    dev = torch.device("cuda:0")
+    cfg = default_dctcn_config()
+    sd = dctcn_init_state_dict(cfg, seed=0)
+    model = DCTCNLightningModule(cfg)
+    model.load_state_dict(sd)
+    model.to(dev).eval()
+    eager = EagerDCTCN(sd, dctcn_dims(cfg), dev)
+    T, rows = a.frames, []
+    for B in [int(v) for v in a.batches.split(",")]:
+        videos, _, _, wm, am = [t.to(dev) for t in dctcn_synthetic_batch(cfg, B, T, seed=B)]
+        st = model.store()
+        C = model.dims["out_size"]
+
+        def hip_backend(feats):
+            with torch.no_grad():
+                stack = model._backend(st, feats, wm, B, T)
+                h, pooled = ops.tcn_norm_pool_fwd(stack, *model._prep["norm5"], am.contiguous(), B=B, T=T, C=C)
+                return ops.linear_fwd(pooled, st.s16("video_classifier.weight"), st.p32("video_classifier.bias"), rows=B, K=C, N=model.dims["classes"],
+                                      x_pitch=C, out_f32=True)[0]
+
+        with torch.no_grad():
+            model.predict(videos, wm, am)                                        # builds the store and the prepared weights
+            feats16 = eager.frontend(videos).contiguous()                        # one set of features for both back-ends
+            feats_hip = feats16.reshape(B * T, 512).contiguous()
+            ref, got = eager.backend(feats16, wm, am), hip_backend(feats_hip)
+        agree = float((got - ref).norm() / ref.norm())
+        fns = {
+            "hip_backend": lambda: hip_backend(feats_hip),
+            "eager_backend": lambda: eager.backend(feats16, wm, am),
+            "hip_forward": lambda: model.predict(videos, wm, am),
+            "eager_forward": lambda: eager.backend(eager.frontend(videos), wm, am),
+        }
+        with torch.no_grad():
+            for fn in fns.values():                                              # warm-up of every shape
+                _time(fn, 3)
+            if a.profile_only:
+                continue
+            samples = {k: [] for k in fns}
+            for _ in range(a.rounds):                                            # alternating: one round of each implementation in turn
+                for k, fn in fns.items():
+                    samples[k].append(_time(fn, a.iters))
+            ops.start_event_timing()
+            hip_backend(feats_hip)
+            torch.cuda.synchronize()
+            ev = ops.stop_event_timing()
+        row = dict(B=B, T=T, backend_agreement_rel=round(agree, 5))
+        for k, v in samples.items():
+            row[f"{k}_ms_median"], row[f"{k}_ms_min"] = round(statistics.median(v), 4), round(min(v), 4)
+        row["backend_eager_over_hip"] = round(row["eager_backend_ms_median"] / row["hip_backend_ms_median"], 3)
+        row["forward_eager_over_hip"] = round(row["eager_forward_ms_median"] / row["hip_forward_ms_median"], 3)
+        tc = ev.get("k_tconv", {})
+        row["tconv_launches"], row["tconv_ms"], row["tconv_gflop"] = tc.get("launches"), tc.get("ms"), None if not tc else round(tc.get("flops", 0.0) / 1e9, 2)
+        if tc and tc.get("ms"):
+            row["tconv_tflops"] = round(tc["flops"] / (tc["ms"] * 1e-3) / 1e12, 2)
+            row["tconv_share_of_bf16_peak"] = round(row["tconv_tflops"] / a.peak_tflops, 4)
+        row["se_ms"], row["norm_pool_ms"] = ev.get("k_tcn_se", {}).get("ms"), ev.get("k_tcn_norm_pool", {}).get("ms")
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    if a.profile_only:
+        return
+    out = dict(what="DC-TCN eval forward: HIP back-end vs torch eager bf16 from the same state dict, same process, alternating rounds",
+               device=torch.cuda.get_device_name(0), rounds=a.rounds, iters=a.iters, peak_tflops=a.peak_tflops, rows=rows)
+    line = json.dumps(out)
+    print(line)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

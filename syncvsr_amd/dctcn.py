@@ -1,0 +1,300 @@
+"""HIP-native twin of the reference's ``DCTCNLightningModule`` (``LRW/video/src/lightning.py:226-334``): the word-level model of
+``LRW/video/config/dc-tcn-base.yaml`` — Conv3d stem + Swish ResNet18 (the front-end the LRS model already runs, ``model._frontend_forward``)
+followed by the densely connected temporal convolution network (``tcn/models/densetcn.py``) with squeeze-and-excitation gates, the masked-mean
+consensus and the two heads.
+
+EVAL / INFERENCE PATH ONLY (``validation_step`` / ``test_step`` / ``inference.py``): a forward in training mode raises NotImplementedError
+(mixup, dropout, batch-statistic BatchNorm1d and the backward are not built), it never runs a wrong forward silently.
+
+Back-end layout (csrc/dctcn.hip): channels-last bf16 rows; ONE [B*T, reduced + layers * growth] buffer per dense block is the feature
+stack (a layer reads a channel prefix through the row pitch and writes its channels at an offset: no ``torch.cat``).  Per layer: one launch
+for the three gates (svsr_tcn_se_fwd), one for the three gated first-stage branches, one for the 1x1 downsample, one for the three
+second-stage branches with ``Swish(out1 + res)`` in the epilogue (svsr_tconv_fwd).  BatchNorm(eval) and the conv bias are a per-channel fp32
+scale / shift applied to the fp32 accumulator; the bf16 weights are never scaled.
+
+Reference defects resolved here: ``self.vq_groups`` is never set there (2, as TransformerLightningModule); the module reads
+``config.optim.loss_audio_weight`` while the yaml has ``optim.lambda_audio`` (either is accepted); fairseq's codec is not loaded — audio
+tokens arrive pre-tokenised, and ``load_state_dict`` ignores ``wav2vec.*`` keys (as inference.py's strict=False does) while staying strict
+about everything else.
+"""
+from __future__ import annotations
+
+from typing import Any, Optional
+
+import torch
+import torch.nn as nn
+
+from . import ops
+from .config import Config
+from .dctcn_init import (SE_REDUCTION, TCN, dctcn_buffer_specs, dctcn_dims, dctcn_init_state_dict, dctcn_layers, dctcn_param_specs)
+from .model import _attach, _frontend_forward, _get, _ParamStore, _SideStream
+
+BF16 = torch.bfloat16
+
+
+def _unsupported(config: Config) -> list[str]:
+    """Every reason this configuration cannot run, together (as lrs_model.E2E lists them)."""
+    why: list[str] = []
+    d = config.model.dctcn
+    if str(d.get("modality", "video")) != "video":
+        why.append("modality must be video")
+    if str(d.get("backbone_type", "resnet")) != "resnet":
+        why.append("backbone_type must be resnet (the ResNet18 trunk is the one front-end built here)")
+    if str(d.get("relu_type", "prelu")) != "swish":
+        why.append("relu_type must be swish (the shipped dc-tcn-base.yaml)")
+    if float(d.get("width_mult", 1.0)) != 1.0:
+        why.append("width_mult must be 1.0")
+    if bool(d.get("extract_feats", False)):
+        why.append("extract_feats is not supported (it returns the front-end features and skips the temporal network)")
+    if d.get("tcn_options"):
+        why.append("tcn_options (the multi-branch TCN back-end) is not built: use densetcn_options")
+    o = d.get("densetcn_options")
+    if not o:
+        why.append("densetcn_options is required")
+        return why
+    ks, ds = [int(v) for v in o.kernel_size_set], [int(v) for v in o.dilation_size_set]
+    blocks, growth, reduced = [int(v) for v in o.block_config], [int(v) for v in o.growth_rate_set], int(o.reduced_size)
+    if not 1 <= len(ks) <= 3:
+        why.append("kernel_size_set must hold one to three kernel sizes (svsr_tconv_fwd takes up to three branches per launch)")
+    if len(growth) != len(blocks):
+        why.append("growth_rate_set needs one entry per block")
+        return why
+    if not bool(o.squeeze_excitation):
+        why.append("squeeze_excitation must be true (the shipped configuration)")
+    if reduced % 64:
+        why.append("reduced_size must be a multiple of 64")
+    for bi, nl in enumerate(blocks):
+        g = growth[bi]
+        if g % len(ks) or (g // len(ks)) % 64:
+            why.append(f"growth rate {g} of block {bi + 1}: every branch must be a multiple of 64 channels wide")
+            continue
+        for li in range(nl):
+            n_in, dl = reduced + li * g, ds[li % len(ds)]
+            for k in ks:
+                if not (ops.tconv_ok(n_in, g // len(ks), k, dl) and ops.tconv_ok(g, g // len(ks), k, dl)):
+                    why.append(f"block {bi + 1} layer {li + 1}: kernel size {k} with dilation {dl} on {n_in} channels is outside what svsr_tconv_fwd "
+                               f"takes (odd k <= 7, (k - 1) * d / 2 <= {ops.TCONV_MAX_HALO}, channels a multiple of 64)")
+    return why
+
+
+class DCTCNLightningModule(nn.Module):
+    def __init__(self, config: Config, seed: Optional[int] = None):
+        super().__init__()
+        if not isinstance(config, Config):
+            config = Config(config)
+        self.config = config
+        why = _unsupported(config)
+        if why:
+            raise NotImplementedError("; ".join(why))
+        self.dims = dctcn_dims(config)
+        self.audio_alignment, self.vq_groups, self.audio_vocab_size = self.dims["A"], self.dims["G"], self.dims["V"]
+        optim = config.get("optim", Config())
+        w = optim.get("loss_audio_weight", optim.get("lambda_audio"))         # the module reads the first, the shipped yaml holds the second
+        if w is None:
+            raise ValueError("config.optim needs loss_audio_weight or lambda_audio")
+        self.lambda_audio = float(w)
+        self.mixup_alpha = float(optim.get("mixup_alpha", 0.0))
+        self.label_smoothing = float(config.get_path("train.label_smoothing", 0.0))
+        self.use_boundary = bool(config.model.dctcn.use_boundary)
+        self._specs = dctcn_param_specs(config)
+        self._bspecs = dctcn_buffer_specs(config)
+        sd = dctcn_init_state_dict(config, seed=0 if seed is None else seed)
+        for name, shape, kind in self._specs:
+            t = sd[name]
+            if kind == "conv" and len(shape) == 4:
+                t = t.contiguous(memory_format=torch.channels_last)
+            _attach(self, name, t, True)
+        for name, shape, kind in self._bspecs:
+            _attach(self, name, sd[name], False)
+        self.stem_name, self.trunk_name = "model.frontend3D", "model.trunk"
+        self.stem_act = self.trunk_act = ops.ACT_SWISH                        # tcn/model.py:118-119, tcn/models/resnet.py with relu_type swish
+        self._side = _SideStream()
+        self._store: Optional[_ParamStore] = None
+        self._prep: Optional[dict] = None
+        self._last: dict[str, Any] = {}
+        self.register_load_state_dict_post_hook(lambda module, incompatible: module.mark_params_dirty())
+        self.eval()
+
+    # ------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _fwd_rank(name: str) -> int:
+        return 0 if name.startswith("model.frontend3D") else 1 if name.startswith("model.trunk") else 2
+
+    def _transposed_entries(self, offsets) -> list:
+        return []                    # no backward: no transposed shadows beyond the front-end's own
+
+    def mark_params_dirty(self) -> None:
+        """Call after changing parameters or buffers in place: the bf16 shadows, the tap-major convolution weights and the folded BatchNorm
+        coefficients are rebuilt at the next forward (load_state_dict and .to(device) do this themselves)."""
+        self._prep = None
+        if self._store is not None:
+            self._store.shadow_fresh = False
+
+    def store(self) -> _ParamStore:
+        dev = _get(self, self._specs[0][0]).device
+        if self._store is None or self._store.device != dev or not self._store.owns(self):
+            self._store = _ParamStore(self, dev)
+            self._prep = None
+        return self._store
+
+    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
+        """`wav2vec.*` keys (the frozen codec of a reference checkpoint) are ignored; everything else is checked as `strict` says."""
+        kept = {k: v for k, v in state_dict.items() if not k.startswith("wav2vec.")}
+        return super().load_state_dict(kept, strict=strict, assign=assign)
+
+    # ------------------------------------------------------------------------------------------------
+    def _bn_affine(self, st: _ParamStore, bn: str, bias: Optional[str]):
+        """BatchNorm1d(eval) after a convolution with bias -> fp32 (scale, shift) for the accumulator: y = scale * acc + shift."""
+        scale = st.p32(f"{bn}.weight") * torch.rsqrt(st.buffers[f"{bn}.running_var"] + ops.BN_EPS)
+        shift = st.p32(f"{bn}.bias") - st.buffers[f"{bn}.running_mean"] * scale
+        if bias is not None:
+            shift = shift + st.p32(bias) * scale
+        return scale.contiguous(), shift.contiguous()
+
+    def _w16(self, st: _ParamStore, name: str, pad_to: Optional[int] = None) -> torch.Tensor:
+        """bf16 shadow of Conv1d weight [co, ci, k] as tap-major [co, k, ci] (ci zero-padded to pad_to)."""
+        shape = st.offsets[name][2]
+        w = st.s16(name).view(shape).permute(0, 2, 1)
+        if pad_to is not None and pad_to != shape[1]:
+            out = torch.zeros((shape[0], shape[2], pad_to), dtype=BF16, device=w.device)
+            out[:, :, : shape[1]] = w
+            return out
+        return w.contiguous()
+
+    def _prepare(self, st: _ParamStore) -> dict:
+        if self._prep is not None:
+            return self._prep
+        st.refresh_shadows()
+        st.shadow_fresh = True          # eval only: nothing but load_state_dict / mark_params_dirty changes a weight
+        dm, dev = self.dims, st.device
+        ks = dm["ks"]
+        P: dict[str, Any] = {}
+        p = f"{TCN}.transition0"
+        self.in_pad = (dm["in_size"] + 63) // 64 * 64
+        sc, sh = self._bn_affine(st, f"{p}.norm", None)
+        P["t0"] = dict(k=1, w=self._w16(st, f"{p}.conv.weight", self.in_pad), scale=sc, shift=sh, slope=st.p32(f"{p}.prelu.weight"), out_off=0)
+        layers, trans = dctcn_layers(self.config)
+        P["layers"] = []
+        for p, n_in, g, d, bi in layers:
+            gb = g // len(ks)
+            L: dict[str, Any] = dict(n_in=n_in, g=g, gb=gb, d=d, bi=bi)
+            L["se_w1"] = torch.stack([st.s16(f"{p}.cbcr0_se_{i}.fc.0.weight").view(n_in // SE_REDUCTION, n_in) for i in range(len(ks))]).contiguous()
+            L["se_w2"] = torch.stack([st.s16(f"{p}.cbcr0_se_{i}.fc.2.weight").view(n_in, n_in // SE_REDUCTION) for i in range(len(ks))]).contiguous()
+            for stage in (0, 1):
+                brs = []
+                for i, k in enumerate(ks):
+                    c = f"{p}.cbcr{stage}_{i}.net"
+                    sc, sh = self._bn_affine(st, f"{c}.1", f"{c}.0.bias")
+                    brs.append(dict(k=k, w=self._w16(st, f"{c}.0.weight"), scale=sc, shift=sh, out_off=(i * gb if stage == 0 else n_in + i * gb),
+                                    res_off=i * gb))
+                L[f"stage{stage}"] = brs
+            L["down"] = dict(k=1, w=self._w16(st, f"{p}.downsample.weight"), scale=torch.ones(g, dtype=torch.float32, device=dev),
+                             shift=st.p32(f"{p}.downsample.bias"), out_off=0)
+            P["layers"].append(L)
+        P["trans"] = {}
+        for name, n, bi in trans:
+            sc, sh = self._bn_affine(st, f"{name}.norm", None)
+            P["trans"][bi] = dict(k=1, w=self._w16(st, f"{name}.conv.weight"), scale=sc, shift=sh, out_off=0, n_in=n)
+        P["norm5"] = self._bn_affine(st, f"{TCN}.norm5", None)
+        self._prep = P
+        return P
+
+    # ------------------------------------------------------------------------------------------------
+    def _backend(self, st: _ParamStore, feats: torch.Tensor, word_mask: Optional[torch.Tensor], B: int, T: int, keep: Optional[dict] = None):
+        """feats bf16 [B*T, 512] -> the last block's feature stack bf16 [B*T, C] (before norm5)."""
+        P, dm, dev = self._prepare(st), self.dims, feats.device
+        R = dm["reduced"]
+        if self.use_boundary:
+            if word_mask is None:
+                raise ValueError("use_boundary: word_mask [B, T] is required")
+            x0 = torch.zeros((B * T, self.in_pad), dtype=BF16, device=dev)
+            x0[:, :512] = feats
+            x0[:, 512] = word_mask.reshape(B * T).to(BF16)
+        else:
+            x0 = feats
+        width = lambda bi: R + dm["blocks"][bi] * dm["growth"][bi]          # noqa: E731
+        stack = torch.empty((B * T, width(0)), dtype=BF16, device=dev)
+        ops.tconv_fwd(x0, B=B, T=T, n_in=x0.shape[1], d=1, branches=[P["t0"]], co=R, act=ops.ACT_PRELU, out=stack)
+        if keep is not None:
+            keep["transition0"] = stack[:, :R].float().view(B, T, R)
+        nlayers = len(P["layers"])
+        for i, L in enumerate(P["layers"]):
+            n_in, g, gb, d, bi = L["n_in"], L["g"], L["gb"], L["d"], L["bi"]
+            gates = ops.tcn_se_fwd(stack, L["se_w1"], L["se_w2"], B=B, T=T, n_in=n_in)
+            out0 = torch.empty((B * T, g), dtype=BF16, device=dev)
+            ops.tconv_fwd(stack, B=B, T=T, n_in=n_in, d=d, branches=[dict(br, gate=gates[j]) for j, br in enumerate(L["stage0"])], co=gb,
+                          act=ops.ACT_SWISH, out=out0)
+            res = torch.empty((B * T, g), dtype=BF16, device=dev)
+            ops.tconv_fwd(stack, B=B, T=T, n_in=n_in, d=1, branches=[L["down"]], co=g, act=ops.ACT_NONE, out=res)
+            ops.tconv_fwd(out0, B=B, T=T, n_in=g, d=d, branches=L["stage1"], co=gb, act=ops.ACT_SWISH, out=stack, res=res, res_act=ops.ACT_SWISH)
+            if i + 1 == nlayers or P["layers"][i + 1]["bi"] != bi:
+                if keep is not None:
+                    keep[f"denseblock{bi + 1}"] = stack.float().view(B, T, -1)
+                if bi in P["trans"]:
+                    tr = P["trans"][bi]
+                    nxt = torch.empty((B * T, width(bi + 1)), dtype=BF16, device=dev)
+                    ops.tconv_fwd(stack, B=B, T=T, n_in=tr["n_in"], d=1, branches=[tr], co=R, act=ops.ACT_SWISH, out=nxt)
+                    stack = nxt
+        return stack
+
+    def _run(self, videos: torch.Tensor, word_mask, attention_mask, keep: Optional[dict] = None):
+        if self.training:
+            raise NotImplementedError("DCTCNLightningModule: only the eval / inference path is built (no mixup, dropout, batch-statistic "
+                                      "BatchNorm1d or backward yet): call .eval() first")
+        if videos.device.type != "cuda":
+            raise RuntimeError("syncvsr_amd runs on an MI355X HIP device only; there is no CPU fallback")
+        if videos.dim() != 5 or videos.size(1) != 1:
+            raise ValueError("videos must be [B, 1, T, H, W]")
+        st = self.store()
+        self._prepare(st)
+        B, _, T = videos.shape[:3]
+        C = self.dims["out_size"]
+        with torch.no_grad():
+            feats = _frontend_forward(self, st, {}, videos.float().contiguous(), False)
+            stack = self._backend(st, feats, word_mask, B, T, keep)
+            if attention_mask is None:
+                attention_mask = torch.ones((B, T), dtype=torch.float32, device=videos.device)
+            scale, shift = self._prep["norm5"]
+            h, pooled = ops.tcn_norm_pool_fwd(stack, scale, shift, attention_mask.to(torch.float32).contiguous(), B=B, T=T, C=C)
+            logits_c, _ = ops.linear_fwd(pooled, st.s16("video_classifier.weight"), st.p32("video_classifier.bias"), rows=B, K=C,
+                                         N=self.dims["classes"], x_pitch=C, out_f32=True)
+        return st, h, logits_c
+
+    def features(self, videos: torch.Tensor, word_mask: Optional[torch.Tensor] = None, keep: Optional[dict] = None) -> torch.Tensor:
+        """last_hidden_states of the reference, time-major: fp32 [B, T, C] (C = 1664 for the shipped configuration)."""
+        B, _, T = videos.shape[:3]
+        _, h, _ = self._run(videos, word_mask, None, keep)
+        return h.float().view(B, T, -1)
+
+    def predict(self, videos: torch.Tensor, word_mask: Optional[torch.Tensor] = None, attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """fp32 word logits [B, num_classes] (what inference.py takes the argmax of)."""
+        return self._run(videos, word_mask, attention_mask)[2]
+
+    def forward(self, videos: torch.Tensor, audios: torch.Tensor, labels: torch.Tensor, word_mask: torch.Tensor,
+                attention_mask: torch.Tensor) -> dict[str, torch.Tensor]:
+        """lightning.py:255-312 in eval mode (lam = 0).  audios: pre-computed vq-wav2vec tokens int64 [B, >= A*T, 2]."""
+        B, _, T = videos.shape[:3]
+        A, G, V = self.audio_alignment, self.vq_groups, self.audio_vocab_size
+        if audios.dtype != torch.int64 or audios.dim() != 3 or audios.size(2) != G:
+            raise ValueError("pass pre-computed audio tokens int64 [B, >= A*T, 2] in the `audios` slot (the fairseq codec is not loaded)")
+        if audios.size(1) < T * A:
+            raise ValueError(f"audio tokens have {audios.size(1)} steps, need >= {T * A}")
+        st, h, logits_c = self._run(videos, word_mask, attention_mask)
+        C, NA = self.dims["out_size"], A * G * V
+        with torch.no_grad():
+            lab = labels.long().contiguous()
+            loss_c, _ = ops.ce_fwd(logits_c, self.dims["classes"], lab, None, B, self.dims["classes"], self.label_smoothing)
+            tok = audios[:, : T * A].contiguous().reshape(-1)
+            # (the logits are stored: svsr_linear_ce_ok takes K up to 576, the shipped width is 1664)
+            logits_a, _ = ops.linear_fwd(h, st.s16("audio_projection.weight"), st.p32("audio_projection.bias"), rows=B * T, K=C, N=NA, x_pitch=C)
+            loss_a, _ = ops.ce_fwd(logits_a, V, tok, None, B * T * A * G, V, 0.0)
+            acc = ops.topk_acc(logits_c, lab, None)
+            loss_total = ops.lincomb2(loss_c, loss_a, self.lambda_audio)
+        self._last = dict(last_hidden_states=h, logits_category=logits_c, logits_audio=logits_a)
+        return {"loss_total": loss_total, "loss_category": loss_c, "loss_audio": loss_a, "accuracy_top1": acc[0], "accuracy_top5": acc[1]}
+
+    def validation_step(self, batch: dict, idx: int = 0) -> dict:
+        return {f"val/{k}": v for k, v in self(**batch).items()}
+
+    def test_step(self, batch: dict, idx: int = 0) -> dict:
+        return {f"test/{k}": v for k, v in self(**batch).items()}

@@ -1885,3 +1885,75 @@ def mha_src_step_fwd(q: torch.Tensor, kv: torch.Tensor, clip_of: torch.Tensor, t
     _call("svsr_mha_src_step_fwd", _p(q), q.stride(0), _p(kv), kv.stride(0), _p(clip_of), _p(tlen), C, int(Tmax), n, H, float(scale), _p(ctx),
           ctx.stride(0), _stream(), label="k_mha_src_step", flops=4.0 * n * Tmax * H * 64, nbytes=256.0 * n * H * Tmax)
     return ctx
+
+
+# --------------------------------------------------------------------------------------------------
+# Dense temporal back-end of the DC-TCN model (csrc/dctcn.hip)
+# --------------------------------------------------------------------------------------------------
+ACT_PRELU = 3
+TCONV_MAX_HALO = 16      # (k - 1) * d / 2 rows of the same clip on either side of a time tile (csrc/dctcn.hip TC_HALO)
+
+
+_TCONV_TABLES: list = []
+
+
+def tconv_ok(n_in: int, co: int, k: int, d: int) -> bool:
+    """The shapes svsr_tconv_fwd takes (anything else is SVSR_ERR_ARG there)."""
+    return n_in >= 64 and n_in % 64 == 0 and co >= 64 and co % 64 == 0 and k in (1, 3, 5, 7) and d >= 1 and (k - 1) * d // 2 <= TCONV_MAX_HALO
+
+
+def tconv_fwd(x: torch.Tensor, *, B: int, T: int, n_in: int, d: int, branches: Sequence[dict], co: int, act: int, out: torch.Tensor,
+              res: Optional[torch.Tensor] = None, res_act: int = ACT_NONE) -> torch.Tensor:
+    """Up to three dilated temporal convolutions of the rows x bf16 [B*T, pitch >= n_in] in one launch (svsr_tconv_fwd).  Each branch is a dict
+    k, w (bf16 [co, k, n_in]), scale / shift (fp32 [co]), out_off, and optionally gate (fp32 [B, n_in]), slope (fp32 [co], PReLU), res_off.
+    out bf16 [B*T, pitch]: channels [out_off, out_off + co) of every row are written, nothing else."""
+    assert x.dtype == BF16 and x.dim() == 2 and x.stride(1) == 1 and x.shape[0] >= B * T and x.shape[1] >= n_in
+    assert out.dtype == BF16 and out.dim() == 2 and out.stride(1) == 1 and out.shape[0] >= B * T
+    if res is not None:
+        assert res.dtype == BF16 and res.dim() == 2 and res.stride(1) == 1 and res.shape[0] >= B * T
+    rows = []
+    flops = 0.0
+    for i, br in enumerate(branches):
+        w, k = br["w"], int(br["k"])
+        assert w.dtype == BF16 and w.is_contiguous() and tuple(w.shape) == (co, k, n_in), (tuple(w.shape), (co, k, n_in))
+        for n in ("scale", "shift", "slope"):
+            t = br.get(n)
+            assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == co)
+        g = br.get("gate")
+        assert g is None or (g.dtype == torch.float32 and g.is_contiguous() and tuple(g.shape) == (B, n_in))
+        off, roff = int(br["out_off"]), int(br.get("res_off", 0))
+        assert 0 <= off and off + co <= out.shape[1] and (res is None or (0 <= roff and roff + co <= res.shape[1]))
+        rows.append((k, _p(w), _p(g) or 0, _p(br["scale"]), _p(br["shift"]), _p(br.get("slope")) or 0, off, roff))
+        flops += 2.0 * B * T * n_in * k * co
+    tab = torch.tensor(rows, dtype=torch.int64)          # host table, read during the call only
+    if _REC is not None:
+        _TCONV_TABLES.append(tab)                       # a recorded step list re-reads it at every replay: keep it alive
+    _call("svsr_tconv_fwd", _p(x), x.stride(0), B, T, n_in, int(d), len(branches), tab.data_ptr(), co, int(act), _p(out), out.stride(0), _p(res),
+          0 if res is None else res.stride(0), int(res_act), _stream(), label="k_tconv", flops=flops)
+    return out
+
+
+def tcn_se_fwd(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, *, B: int, T: int, n_in: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x bf16 [B*T, pitch >= n_in], w1 bf16 [nb, R, n_in], w2 bf16 [nb, n_in, R] -> gate fp32 [nb, B, n_in] = sigmoid(W2 swish(W1 mean_t x))
+    (svsr_tcn_se_fwd): the time mean once, the nb gates of a layer in one launch."""
+    nb, R = w1.shape[0], w1.shape[1]
+    assert x.dtype == BF16 and x.dim() == 2 and x.stride(1) == 1 and x.shape[0] >= B * T and x.shape[1] >= n_in
+    assert w1.dtype == BF16 and w1.is_contiguous() and tuple(w1.shape) == (nb, R, n_in)
+    assert w2.dtype == BF16 and w2.is_contiguous() and tuple(w2.shape) == (nb, n_in, R)
+    gate = torch.empty((nb, B, n_in), dtype=torch.float32, device=x.device) if out is None else out
+    assert gate.dtype == torch.float32 and gate.is_contiguous() and tuple(gate.shape) == (nb, B, n_in)
+    _call("svsr_tcn_se_fwd", _p(x), x.stride(0), B, T, n_in, R, nb, _p(w1), _p(w2), _p(gate), _stream(), label="k_tcn_se")
+    return gate
+
+
+def tcn_norm_pool_fwd(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, mask: torch.Tensor, *, B: int, T: int, C: int):
+    """x bf16 [B*T, pitch >= C], mask fp32 [B, T] -> (h bf16 [B*T, C] = x * scale + shift, pooled bf16 [B, C] = masked mean of h over time)
+    (svsr_tcn_norm_pool_fwd)."""
+    assert x.dtype == BF16 and x.dim() == 2 and x.stride(1) == 1 and x.shape[0] >= B * T and x.shape[1] >= C
+    assert mask.dtype == torch.float32 and mask.is_contiguous() and mask.numel() == B * T
+    for t in (scale, shift):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == C
+    h = torch.empty((B * T, C), dtype=BF16, device=x.device)
+    pooled = torch.empty((B, C), dtype=BF16, device=x.device)
+    _call("svsr_tcn_norm_pool_fwd", _p(x), x.stride(0), B, T, C, _p(scale), _p(shift), _p(mask), _p(h), _p(pooled), _stream(), label="k_tcn_norm_pool")
+    return h, pooled
