@@ -494,7 +494,9 @@ int svsr_ctc_grad(const float* logits, int ld, const int64_t* labels, int Lmax, 
  * r_prev fp32 [n][T][2] = (non-blank, blank) forward log-probabilities of each hypothesis' prefix; last int64 [n] = last label
  * of each prefix; ids int64 [n][S] = candidate labels per hypothesis (null: all V labels, S = V); out_len = labels in the
  * prefixes without <sos>.  Writes r_new fp32 [n][S][T][2] (state of every extension) and psi fp32 [n][S] (log prefix
- * probability; eos -> total probability of the prefix, blank -> -1e10). */
+ * probability; eos -> total probability of the prefix, blank -> -1e10).  A candidate outside [0, V) is an impossible extension: its
+ * r_new and psi are -1e10 and logp is not read for it.  Defined in lrs_search.hip: the kernel of svsr_ctc_prefix_score_clips with one
+ * clip of T frames. */
 int svsr_ctc_prefix_score(const float* logp, int ldp, const float* r_prev, const int64_t* last, const int64_t* ids, float* r_new, float* psi, int T, int V, int n, int S, int out_len, int blank, int eos, hipStream_t stream);
 
 /* Decoder input: x[r] = emb[tok[r]] * scale + pe[r % L]  (torch.nn.Embedding + PositionalEncoding, decoder.py:80-84,
@@ -585,7 +587,7 @@ int svsr_tcn_norm_pool_fwd(const void* x, int64_t x_pitch, int B, int T, int C, 
  * nplanes <= 4, beam <= 256, max_rows * V <= 2^20, and slices * beam <= 4096 with slices = ceil(max_rows * V / 4096) — beam 40 over 5,049
  * units holds up to 82 rows per clip, the search never has more than `beam`.
  *
- * svsr_ctc_prefix_score_clips: svsr_ctc_prefix_score with logp fp32 [C][Tmax][ldp], tlen int32 [C], r_prev fp32 [n][Tmax][2]: hypothesis r
+ * svsr_ctc_prefix_score_clips: svsr_ctc_prefix_score (the same kernel) with logp fp32 [C][Tmax][ldp], tlen int32 [C], r_prev fp32 [n][Tmax][2]: hypothesis r
  * walks the tlen[clip_of[r]] frames of its clip's posteriors, eos takes logaddexp of r_prev at that clip's last frame, frames
  * tlen .. Tmax - 1 of r_new [n][S][Tmax][2] are -1e10, and nothing reads logp or r_prev beyond a clip's length.  A row whose clip is
  * outside [0, C) or has no frame, and a candidate outside [0, V), score -1e10.

@@ -1,7 +1,7 @@
 // Multi-clip beam search of the LRS inference surface (syncvsr_amd/lrs_infer.py BatchBeamSearch.forward_clips), gfx950, wave64:
 //   * k_beam_select_slices / k_beam_select_merge: the selection step of one search position for every clip at once — the weighted
 //     sum of the scorers' planes, the running score, and the per-clip top `beam` (the torch statement: lrs_infer.beam_select_reference)
-//   * k_ctc_prefix_score_clips: k_ctc_prefix_score (lrs_misc.hip) with every hypothesis walking the frames of ITS clip
+//   * k_ctc_prefix_score_clips: the CTC prefix recursion of both searches, every hypothesis walking the frames of ITS clip
 //   * k_mha_src_step: source attention of one query row per hypothesis against the keys / values of its clip
 // No float atomics and no order that depends on arrival anywhere: every output is a pure function of the inputs.
 #include "common.h"
@@ -161,8 +161,15 @@ __global__ __launch_bounds__(BS_THREADS) void k_beam_select_merge(BeamPlanes p, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// CTC prefix scores, one thread per (hypothesis, candidate) as k_ctc_prefix_score: hypothesis h belongs to clip c = clip_of[h] and walks
-// the Tc = tlen[c] frames of logp[c]; frames Tc .. Tmax - 1 of the new state are LOGZERO and nothing reads the padding of logp or r_prev.
+// CTC prefix scores for beam search (Watanabe et al., "Hybrid CTC/attention architecture for end-to-end speech recognition",
+// Algorithm 2; the reference vectorises it in torch, espnet/nets/ctc_prefix_score.py:11-165, one launch of ~10 small kernels per
+// frame).  Here one thread owns one (hypothesis, candidate label) pair and walks the frames of the recursion in registers:
+//   r_n[t] = logaddexp(r_n[t-1], phi[t-1]) + logp[t][c]         phi[t] = r_b_prev[t] if c == last label else logaddexp(r_n_prev[t], r_b_prev[t])
+//   r_b[t] = logaddexp(r_n[t-1], r_b[t-1]) + logp[t][blank]
+//   psi    = logsumexp(r_n[start-1], phi[t-1] + logp[t][c] for t in [start, T)),   start = max(#labels in the prefix, 1)
+// eos gets logaddexp(r_n_prev[T-1], r_b_prev[T-1]), blank gets LOGZERO.  r_new [n][S][Tmax][2] is the state of each extension.
+// Hypothesis h belongs to clip c = clip_of[h] (null: clip 0) and walks the Tc = tlen[c] (null: Tmax) frames of logp[c]; frames
+// Tc .. Tmax - 1 of the new state are LOGZERO and nothing reads the padding of logp or r_prev.
 // ---------------------------------------------------------------------------------------------------------------------
 #define CTC_LOGZERO (-1.0e10f)
 __device__ __forceinline__ float lae(float a, float b) {
@@ -179,9 +186,9 @@ __global__ __launch_bounds__(256) void k_ctc_prefix_score_clips(const float* __r
     if (idx >= (long)n * S) return;
     const int h = (int)(idx / S), j = (int)(idx - (long)h * S);
     float* rn_out = r_new + idx * Tmax * 2;
-    const int clip = clip_of[h];
-    int c = ids != nullptr ? (int)ids[(long)h * S + j] : j;
-    int T = (clip >= 0 && clip < C) ? tlen[clip] : 0;
+    const int clip = clip_of != nullptr ? clip_of[h] : 0;
+    const int c = ids != nullptr ? (int)ids[(long)h * S + j] : j;
+    int T = (clip >= 0 && clip < C) ? (tlen != nullptr ? tlen[clip] : Tmax) : 0;
     T = T > Tmax ? Tmax : T;
     if (T < 1 || c < 0 || c >= V) {                        // no clip / no such label: an impossible extension, never a stray read
         for (int t = 0; t < Tmax; ++t) { rn_out[2 * t] = CTC_LOGZERO; rn_out[2 * t + 1] = CTC_LOGZERO; }
@@ -317,16 +324,32 @@ int svsr_beam_select(const float* s0, const float* s1, const float* s2, const fl
     return svsr_check_launch();
 }
 
+// one thread per (hypothesis, candidate), no grid-stride loop in the kernel: the grid covers every pair (full-vocabulary scoring at a
+// wide beam exceeds a capped grid)
+static int ctc_prefix_launch(const float* logp, int ldp, const float* r_prev, const int64_t* last, const int64_t* ids, const int* clip_of,
+                             const int* tlen, float* r_new, float* psi, int C, int Tmax, int V, int n, int S, int out_len, int blank, int eos,
+                             hipStream_t stream) {
+    if (((long)n * S + 255) / 256 > 0x7fffffffL) return SVSR_ERR_ARG;
+    hipLaunchKernelGGL(k_ctc_prefix_score_clips, dim3((unsigned)(((long)n * S + 255) / 256)), dim3(256), 0, stream, logp, r_prev, (const long*)last,
+                       (const long*)ids, clip_of, tlen, r_new, psi, C, Tmax, V, ldp, n, S, out_len, blank, eos);
+    return svsr_check_launch();
+}
+
 int svsr_ctc_prefix_score_clips(const float* logp, int ldp, const float* r_prev, const int64_t* last, const int64_t* ids, const int* clip_of,
                                 const int* tlen, float* r_new, float* psi, int C, int Tmax, int V, int n, int S, int out_len, int blank, int eos,
                                 hipStream_t stream) {
     if (C < 1 || Tmax < 1 || V < 2 || n < 1 || S < 1 || (ids == nullptr && S != V) || ldp < V || out_len < 0 || blank < 0 || blank >= V || eos < 0 ||
         eos >= V || clip_of == nullptr || tlen == nullptr)
         return SVSR_ERR_ARG;
-    if (((long)n * S + 255) / 256 > 0x7fffffffL) return SVSR_ERR_ARG;          // one thread per (hypothesis, candidate), as svsr_ctc_prefix_score
-    hipLaunchKernelGGL(k_ctc_prefix_score_clips, dim3((unsigned)(((long)n * S + 255) / 256)), dim3(256), 0, stream, logp, r_prev, (const long*)last,
-                       (const long*)ids, clip_of, tlen, r_new, psi, C, Tmax, V, ldp, n, S, out_len, blank, eos);
-    return svsr_check_launch();
+    return ctc_prefix_launch(logp, ldp, r_prev, last, ids, clip_of, tlen, r_new, psi, C, Tmax, V, n, S, out_len, blank, eos, stream);
+}
+
+// one clip of T frames: the same kernel with every hypothesis in clip 0 and no length table
+int svsr_ctc_prefix_score(const float* logp, int ldp, const float* r_prev, const int64_t* last, const int64_t* ids, float* r_new, float* psi, int T,
+                          int V, int n, int S, int out_len, int blank, int eos, hipStream_t stream) {
+    if (T < 1 || V < 2 || n < 1 || S < 1 || (ids == nullptr && S != V) || ldp < V || out_len < 0 || blank < 0 || blank >= V || eos < 0 || eos >= V)
+        return SVSR_ERR_ARG;
+    return ctc_prefix_launch(logp, ldp, r_prev, last, ids, nullptr, nullptr, r_new, psi, 1, T, V, n, S, out_len, blank, eos, stream);
 }
 
 int svsr_mha_src_step_fwd(const void* q, int64_t q_pitch, const void* kv, int64_t kv_pitch, const int* clip_of, const int* tlen, int C, int Tmax, int n,

@@ -11,7 +11,7 @@ batch_score` (transformer/decoder.py:153-220), `CTCPrefixScorer` (scorers/ctc.py
   * the search state is batched tensors from start to end (token matrix, score vector, CTC forward variables [n, T, 2]) — the
     reference converts to and from per-hypothesis Python objects every step (batch_beam_search.py:230-275);
   * the CTC prefix recursion over the T frames runs in ONE HIP kernel per step, one thread per (hypothesis, candidate) pair
-    (csrc/lrs_misc.hip k_ctc_prefix_score) instead of ~10 small torch kernels per frame (ctc_prefix_score.py:139-146);
+    (csrc/lrs_search.hip k_ctc_prefix_score_clips) instead of ~10 small torch kernels per frame (ctc_prefix_score.py:139-146);
   * the decoder scorer recomputes the prefix with the training kernels (one [n * L]-row batch keeps the MFMA tiles full) instead
     of caching per-layer outputs: the decoder's self-attention is causal, so the last row is identical either way.
 
@@ -116,6 +116,13 @@ class DecoderScorer:
         return None if states is None else tuple(c[prev] for c in states)
 
     # -- source-attention keys / values -----------------------------------------------------------
+    def _src_kv(self, st, mem, rows: int):
+        """Per layer, the fused source-attention k | v projection of `rows` memory rows: bf16 [rows, 2 * ddim]."""
+        from .lrs_model import _lin
+
+        m = self.model
+        return [_lin(st, mem, f"decoder.decoders.{i}.src_attn.linear_k", rows, m.ddim, 2 * m.ddim) for i in range(m.dlayers)]
+
     def _memory_kv(self, st, memory: torch.Tensor, n: int, T: int):
         m = self.model
         D = m.ddim
@@ -135,11 +142,11 @@ class DecoderScorer:
         if aliased or n == 1:
             if c["row"] is None:
                 mem = memory[0].to(BF16).contiguous()
-                c["row"] = [_lin_kv(st, mem, f"decoder.decoders.{i}.src_attn.linear_k", T, D) for i in range(m.dlayers)]
+                c["row"] = self._src_kv(st, mem, T)
             kv = [r.unsqueeze(0).expand(n, T, 2 * D).reshape(n * T, 2 * D).contiguous() if n > 1 else r for r in c["row"]]
         else:
             mem = memory.to(BF16).reshape(n * T, D).contiguous()
-            kv = [_lin_kv(st, mem, f"decoder.decoders.{i}.src_attn.linear_k", n * T, D) for i in range(m.dlayers)]
+            kv = self._src_kv(st, mem, n * T)
         c["by_n"] = {n: kv}                                  # (the beam only shrinks or stays: one width at a time is enough)
         return kv
 
@@ -156,11 +163,7 @@ class DecoderScorer:
         if memory.size(-1) != m.ddim:
             raise ValueError(f"memory is {memory.size(-1)} wide, the decoder expects ddim = {m.ddim} (the reference feeds the encoder "
                              "output to the decoder directly at inference, lightning.py:114-119, which needs adim == ddim)")
-        st = m.store()
-        m._side.join()                # (a TrainStep may have left the tail of its optimiser step on the side stream)
-        if not st.shadow_fresh:
-            st.refresh_shadows()
-            self._mem = None                         # projected with the old weights
+        st = _fresh_store(m, self)
         n, L = tgt.shape
         T, D = memory.size(1), m.ddim
         if memory_mask is not None:
@@ -186,14 +189,22 @@ class DecoderScorer:
         return torch.log_softmax(logits.float(), dim=-1), new_cache
 
     def _step_cached(self, st, tgt, memory, ilen, cache, n: int, L: int, T: int):
-        """Position L-1 of every hypothesis on top of `cache` (decoder_layer.py:67-127 with tgt_q = tgt[:, -1:])."""
+        """Position L-1 of every hypothesis on top of `cache`, every row attending to its own `memory` row."""
+        D, H = self.model.ddim, self.model.dheads
+        memkv = self._memory_kv(st, memory, n, T)
+        return self._step(st, tgt, cache, lambda i, q: ops.mha_fwd(q, D, memkv[i], memkv[i][:, D:], 2 * D, B=n, H=H, Lq=1, Lk=T, klen=ilen)[0])
+
+    def _step(self, st, ys, cache, src_attn):
+        """Position L-1 of every hypothesis on top of `cache` (decoder_layer.py:67-127 with tgt_q = tgt[:, -1:]): ys int64 [n, L], cache
+        per-layer [n, L-1, 3*ddim], src_attn(layer index, q bf16 [n, ddim]) -> the source-attention context of that layer ->
+        (logits fp32 [n, odim], new cache)."""
         from .lrs_model import _ffn_fwd, _lin, _ln
 
         m = self.model
         D, U, H = m.ddim, m.dunits, m.dheads
-        memkv = self._memory_kv(st, memory, n, T)
-        pe = m._pos_table("abs", L, memory.device)
-        x = ops.embed_pos_fwd(tgt[:, -1:].contiguous(), st.p32("decoder.embed.0.weight"), pe[L - 1 : L].contiguous(), 1, D, math.sqrt(D))   # [n, D]
+        n, L = ys.shape
+        pe = m._pos_table("abs", L, ys.device)
+        x = ops.embed_pos_fwd(ys[:, -1:].contiguous(), st.p32("decoder.embed.0.weight"), pe[L - 1 : L].contiguous(), 1, D, math.sqrt(D))   # [n, D]
         new_cache = []
         for i in range(m.dlayers):
             p = f"decoder.decoders.{i}"
@@ -204,16 +215,14 @@ class DecoderScorer:
             ctx, _ = ops.mha_fwd(qkv, 3 * D, kv, kv[:, D:], 2 * D, B=n, H=H, Lq=1, Lk=L)                     # the last query sees every key
             x1 = _lin(st, ctx, f"{p}.self_attn.linear_out", n, D, D, addend=x)
             t2, _, _ = _ln(st, x1, f"{p}.norm2")
-            q = _lin(st, t2, f"{p}.src_attn.linear_q", n, D, D)
-            ctx2, _ = ops.mha_fwd(q, D, memkv[i], memkv[i][:, D:], 2 * D, B=n, H=H, Lq=1, Lk=T, klen=ilen)
+            ctx2 = src_attn(i, _lin(st, t2, f"{p}.src_attn.linear_q", n, D, D))
             x2 = _lin(st, ctx2, f"{p}.src_attn.linear_out", n, D, D, addend=x1)
             x = _ffn_fwd(m, st, {}, "ff", x2, f"{p}.feed_forward", n, D, U, 1.0, f"{p}.norm3", f"dec.{i}.ff")
             new_cache.append(torch.cat((c, torch.cat((x, qkv[:, D:]), dim=1).unsqueeze(1)), dim=1))
         tn, _, _ = _ln(st, x, "decoder.after_norm")
         V = m.odim
-        Vp = (V + 63) // 64 * 64
         pred = ops.linear_fwd(tn, st.s16("decoder.output_layer.weight"), st.p32("decoder.output_layer.bias"), rows=n, K=D, N=V, x_pitch=D,
-                              out_f32=True, out_pitch=Vp)[0]
+                              out_f32=True, out_pitch=(V + 63) // 64 * 64)[0]
         return pred[:, :V], tuple(new_cache)
 
     # -- clip-aware protocol (BatchBeamSearch.forward_clips) ---------------------------------------
@@ -229,16 +238,11 @@ class DecoderScorer:
                              "output to the decoder directly at inference, lightning.py:114-119, which needs adim == ddim)")
         if xs.device.type != "cuda":
             raise RuntimeError("syncvsr_amd runs on an MI355X HIP device only; there is no CPU fallback (use oracle/ for checking)")
-        st = m.store()
-        m._side.join()
-        if not st.shadow_fresh:
-            st.refresh_shadows()
-            self._mem = None
+        st = _fresh_store(m, self)
         C, Tmax, D = xs.shape
         tlen = torch.as_tensor(lengths, dtype=torch.int32).to(xs.device).contiguous()
         with torch.no_grad():
-            mem = xs.to(BF16).reshape(C * Tmax, D).contiguous()
-            kv = [_lin_kv(st, mem, f"decoder.decoders.{i}.src_attn.linear_k", C * Tmax, D) for i in range(m.dlayers)]
+            kv = self._src_kv(st, xs.to(BF16).reshape(C * Tmax, D).contiguous(), C * Tmax)
         self._clips = dict(kv=kv, tlen=tlen, C=C, Tmax=Tmax, dev=xs.device)
         return None
 
@@ -246,10 +250,8 @@ class DecoderScorer:
         """ys int64 [n, L], states: None (first position) or the batched cache (per-layer [n, L-1, 3*ddim]), clip_of int32 [n] ->
         (log-probabilities of the next token [n, odim], new cache).  Every position, the first included, goes through the one-row step:
         the cache of the first position is empty."""
-        from .lrs_model import _ffn_fwd, _lin, _ln
-
         m, ck = self.model, self._clips
-        D, U, H = m.ddim, m.dunits, m.dheads
+        D, H = m.ddim, m.dheads
         n, L = ys.shape
         st = m.store()
         if states is None:
@@ -260,28 +262,8 @@ class DecoderScorer:
             raise ValueError(f"cache entries are {tuple(states[0].shape)}, expected ({n}, {L - 1}, {3 * D}): the cache must come from the "
                              "previous scoring call for the same hypotheses")
         with torch.no_grad():
-            pe = m._pos_table("abs", L, ys.device)
-            x = ops.embed_pos_fwd(ys[:, -1:].contiguous(), st.p32("decoder.embed.0.weight"), pe[L - 1 : L].contiguous(), 1, D, math.sqrt(D))   # [n, D]
-            new_cache = []
-            for i in range(m.dlayers):
-                p = f"decoder.decoders.{i}"
-                c = states[i]
-                t1, _, _ = _ln(st, x, f"{p}.norm1")
-                qkv = _lin(st, t1, f"{p}.self_attn.linear_q", n, D, 3 * D)
-                kv = torch.cat((c[:, :, D:], qkv[:, D:].unsqueeze(1)), dim=1).view(n * L, 2 * D)
-                ctx, _ = ops.mha_fwd(qkv, 3 * D, kv, kv[:, D:], 2 * D, B=n, H=H, Lq=1, Lk=L)
-                x1 = _lin(st, ctx, f"{p}.self_attn.linear_out", n, D, D, addend=x)
-                t2, _, _ = _ln(st, x1, f"{p}.norm2")
-                q = _lin(st, t2, f"{p}.src_attn.linear_q", n, D, D)
-                ctx2 = ops.mha_src_step_fwd(q, ck["kv"][i], clip_of, ck["tlen"], Tmax=ck["Tmax"], H=H)
-                x2 = _lin(st, ctx2, f"{p}.src_attn.linear_out", n, D, D, addend=x1)
-                x = _ffn_fwd(m, st, {}, "ff", x2, f"{p}.feed_forward", n, D, U, 1.0, f"{p}.norm3", f"dec.{i}.ff")
-                new_cache.append(torch.cat((c, torch.cat((x, qkv[:, D:]), dim=1).unsqueeze(1)), dim=1))
-            tn, _, _ = _ln(st, x, "decoder.after_norm")
-            V = m.odim
-            pred = ops.linear_fwd(tn, st.s16("decoder.output_layer.weight"), st.p32("decoder.output_layer.bias"), rows=n, K=D, N=V, x_pitch=D,
-                                  out_f32=True, out_pitch=(V + 63) // 64 * 64)[0]
-            return torch.log_softmax(pred[:, :V].float(), dim=-1), tuple(new_cache)
+            logits, new_cache = self._step(st, ys, states, lambda i, q: ops.mha_src_step_fwd(q, ck["kv"][i], clip_of, ck["tlen"], Tmax=ck["Tmax"], H=H))
+            return torch.log_softmax(logits.float(), dim=-1), new_cache
 
     def score(self, ys: torch.Tensor, state, x: torch.Tensor):
         logp, cache = self.forward_one_step(ys.unsqueeze(0), None, x.unsqueeze(0), cache=None if state is None else [c.unsqueeze(0) for c in state])
@@ -297,10 +279,16 @@ class DecoderScorer:
         return self.forward_one_step(ys, None, xs, cache=states)
 
 
-def _lin_kv(st, mem, name: str, rows: int, D: int):
-    from .lrs_model import _lin
-
-    return _lin(st, mem, name, rows, D, 2 * D)
+def _fresh_store(model, scorer=None):
+    """What every inference entry point does first: join the side stream (a TrainStep may have left the tail of its optimiser step there)
+    and bring the bf16 shadows up to date; a decoder scorer then drops the source keys / values it projected with the old weights."""
+    st = model.store()
+    model._side.join()
+    if not st.shadow_fresh:
+        st.refresh_shadows()
+        if scorer is not None:
+            scorer._mem = None
+    return st
 
 
 class CTCPrefixScorer:
@@ -316,10 +304,7 @@ class CTCPrefixScorer:
     def ctc_log_softmax(self, x: torch.Tensor) -> torch.Tensor:
         """`CTC.log_softmax` (ctc.py:163-170): x [T, adim] -> fp32 [T, odim]."""
         m = self.model
-        st = m.store()
-        m._side.join()                # (a TrainStep may have left the tail of its optimiser step on the side stream)
-        if not st.shadow_fresh:
-            st.refresh_shadows()
+        st = _fresh_store(m)
         T = x.size(0)
         with torch.no_grad():
             logits = ops.linear_fwd(x.to(BF16).contiguous(), st.s16("ctc.ctc_lo.weight"), st.p32("ctc.ctc_lo.bias"), rows=T, K=m.adim, N=m.odim,
@@ -346,13 +331,19 @@ class CTCPrefixScorer:
             s_prev = torch.zeros(n, dtype=logp.dtype, device=logp.device)
         else:
             r_prev, s_prev = state
+        return self._score_partial(y, ids, r_prev, s_prev, V, r_prev[:, T - 1],
+                                   lambda r, last, ids_c, out_len: self._prefix(logp, r, last, ids_c, out_len))
+
+    def _score_partial(self, y, ids, r_prev, s_prev, V: int, end, prefix):
+        """The part both searches share.  prefix(r_prev, last label, ids, labels in the prefix) -> (r_new, psi) is the recursion; end [n, 2]
+        is r_prev at the last frame of each hypothesis' clip, which gives <eos> its score."""
         ids_c = None if ids is None else ids.contiguous()
-        r_new, psi = self._prefix(logp, r_prev.contiguous(), y[:, -1].contiguous(), ids_c, y.shape[1] - 1)
+        r_new, psi = prefix(r_prev.contiguous(), y[:, -1].contiguous(), ids_c, y.shape[1] - 1)
         if ids_c is None:
             full = psi.clone()
         else:
-            full = torch.full((n, V), LOGZERO, dtype=logp.dtype, device=logp.device).scatter_(1, ids_c, psi)
-        full[:, self.eos] = torch.logaddexp(r_prev[:, T - 1, 0], r_prev[:, T - 1, 1])
+            full = torch.full((y.shape[0], V), LOGZERO, dtype=psi.dtype, device=psi.device).scatter_(1, ids_c, psi)
+        full[:, self.eos] = torch.logaddexp(end[:, 0], end[:, 1])
         full[:, self.blank] = LOGZERO
         return full - s_prev.unsqueeze(1), (r_new, full, ids_c)
 
@@ -382,16 +373,9 @@ class CTCPrefixScorer:
             s_prev = torch.zeros(n, dtype=logp.dtype, device=logp.device)
         else:
             r_prev, s_prev = state
-        ids_c = None if ids is None else ids.contiguous()
-        r_new, psi = self._prefix_clips(logp, tlen, r_prev.contiguous(), y[:, -1].contiguous(), ids_c, clip_of, y.shape[1] - 1)
-        if ids_c is None:
-            full = psi.clone()
-        else:
-            full = torch.full((n, V), LOGZERO, dtype=logp.dtype, device=logp.device).scatter_(1, ids_c, psi)
         end = r_prev[torch.arange(n, device=logp.device), tlen.long()[cl] - 1]                                  # [n, 2]: the clip's last frame
-        full[:, self.eos] = torch.logaddexp(end[:, 0], end[:, 1])
-        full[:, self.blank] = LOGZERO
-        return full - s_prev.unsqueeze(1), (r_new, full, ids_c)
+        return self._score_partial(y, ids, r_prev, s_prev, V, end,
+                                   lambda r, last, ids_c, out_len: self._prefix_clips(logp, tlen, r, last, ids_c, clip_of, out_len))
 
     def select_states(self, pending, prev: torch.Tensor, tok: torch.Tensor):
         """State of the extensions (prev[i], tok[i])."""

@@ -128,6 +128,37 @@ def test_ctc_prefix_clips_kernel_matches_restatement_per_clip(dev, tlens, V, per
         last = (j if ids is None else ids[torch.arange(n), j]).long()
 
 
+@pytest.mark.parametrize("T,V,n,S", [(1, 41, 2, None), (9, 41, 3, 7), (9, 41, 3, None)])
+def test_ctc_prefix_clips_one_clip_equals_the_single_clip_entry_point(dev, T, V, n, S):
+    """svsr_ctc_prefix_score launches the kernel without its two tables (every hypothesis in clip 0, Tmax frames); the same rows as one clip
+    padded to T + 5 frames with NaN, through clip_of and tlen, must give the same bits, and -1e10 in the padding of the new state."""
+    from oracle import lrs_oracle as O
+    from syncvsr_amd import ops
+
+    g = torch.Generator().manual_seed(1000 * T + V + n)
+    Tmax, eos = T + 5, V - 1
+    logp = torch.full((1, Tmax, V), float("nan"))
+    logp[0, :T] = torch.log_softmax(2.0 * torch.randn(T, V, generator=g), dim=-1)
+    r_prev = torch.full((n, Tmax, 2), float("nan"))
+    r_prev[:, :T, 0] = O.CTC_LOGZERO
+    r_prev[:, :T, 1] = torch.cumsum(logp[0, :T, 0], 0)
+    last = torch.randint(1, V - 1, (n,), generator=g)
+    ids = None if S is None else torch.stack([torch.randperm(V, generator=g)[:S] for _ in range(n)])
+    if ids is not None:
+        ids[0, 0] = last[0]                                  # (with S = None every row meets its own last label among the V candidates)
+    ids_d = None if ids is None else ids.to(dev)
+    tl = torch.tensor([T], dtype=torch.int32, device=dev)
+    clip_of = torch.zeros(n, dtype=torch.int32, device=dev)
+    for out_len in (0, 1, 3):
+        r_one, psi_one = ops.ctc_prefix_score(logp[0, :T].to(dev).contiguous(), r_prev[:, :T].to(dev).contiguous(), last.to(dev), ids_d, out_len, 0, eos)
+        r_pad, psi_pad = ops.ctc_prefix_score_clips(logp.to(dev), tl, r_prev.to(dev), last.to(dev), ids_d, clip_of, out_len, 0, eos)
+        torch.cuda.synchronize()
+        assert r_one.shape == (n, S or V, T, 2) and r_pad.shape == (n, S or V, Tmax, 2)
+        assert torch.equal(psi_one, psi_pad), out_len
+        assert torch.equal(r_one, r_pad[:, :, :T]), out_len
+        assert bool((r_pad[:, :, T:] == O.CTC_LOGZERO).all()), out_len
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # the searches
 # ----------------------------------------------------------------------------------------------------------------------
