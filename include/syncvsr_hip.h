@@ -495,7 +495,8 @@ int svsr_ctc_grad(const float* logits, int ld, const int64_t* labels, int Lmax, 
  * of each prefix; ids int64 [n][S] = candidate labels per hypothesis (null: all V labels, S = V); out_len = labels in the
  * prefixes without <sos>.  Writes r_new fp32 [n][S][T][2] (state of every extension) and psi fp32 [n][S] (log prefix
  * probability; eos -> total probability of the prefix, blank -> -1e10).  A candidate outside [0, V) is an impossible extension: its
- * r_new and psi are -1e10 and logp is not read for it.  Defined in lrs_search.hip: the kernel of svsr_ctc_prefix_score_clips with one
+ * r_new and psi are -1e10 and logp is not read for it.  Ids and last labels are compared as the int64 values they are (2^32 + 5 is not
+ * label 5; a last label outside [0, V) equals no candidate).  Defined in lrs_search.hip: the kernel of svsr_ctc_prefix_score_clips with one
  * clip of T frames. */
 int svsr_ctc_prefix_score(const float* logp, int ldp, const float* r_prev, const int64_t* last, const int64_t* ids, float* r_new, float* psi, int T, int V, int n, int S, int out_len, int blank, int eos, hipStream_t stream);
 

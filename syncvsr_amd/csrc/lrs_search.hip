@@ -169,7 +169,9 @@ __global__ __launch_bounds__(BS_THREADS) void k_beam_select_merge(BeamPlanes p, 
 //   psi    = logsumexp(r_n[start-1], phi[t-1] + logp[t][c] for t in [start, T)),   start = max(#labels in the prefix, 1)
 // eos gets logaddexp(r_n_prev[T-1], r_b_prev[T-1]), blank gets LOGZERO.  r_new [n][S][Tmax][2] is the state of each extension.
 // Hypothesis h belongs to clip c = clip_of[h] (null: clip 0) and walks the Tc = tlen[c] (null: Tmax) frames of logp[c]; frames
-// Tc .. Tmax - 1 of the new state are LOGZERO and nothing reads the padding of logp or r_prev.
+// Tc .. Tmax - 1 of the new state are LOGZERO and nothing reads the padding of logp or r_prev.  Candidate ids and last labels are compared
+// as int64, before any narrowing: an id outside [0, V) (2^32 + 5 included) is an impossible extension, and a last label outside [0, V)
+// matches no candidate.
 // ---------------------------------------------------------------------------------------------------------------------
 #define CTC_LOGZERO (-1.0e10f)
 __device__ __forceinline__ float lae(float a, float b) {
@@ -187,17 +189,18 @@ __global__ __launch_bounds__(256) void k_ctc_prefix_score_clips(const float* __r
     const int h = (int)(idx / S), j = (int)(idx - (long)h * S);
     float* rn_out = r_new + idx * Tmax * 2;
     const int clip = clip_of != nullptr ? clip_of[h] : 0;
-    const int c = ids != nullptr ? (int)ids[(long)h * S + j] : j;
+    const long id = ids != nullptr ? ids[(long)h * S + j] : (long)j;           // ranged as the 64-bit value it is: 2^32 + 5 is not label 5
+    const int c = (int)id;
     int T = (clip >= 0 && clip < C) ? (tlen != nullptr ? tlen[clip] : Tmax) : 0;
     T = T > Tmax ? Tmax : T;
-    if (T < 1 || c < 0 || c >= V) {                        // no clip / no such label: an impossible extension, never a stray read
+    if (T < 1 || id < 0 || id >= (long)V) {                // no clip / no such label: an impossible extension, never a stray read
         for (int t = 0; t < Tmax; ++t) { rn_out[2 * t] = CTC_LOGZERO; rn_out[2 * t + 1] = CTC_LOGZERO; }
         psi[idx] = CTC_LOGZERO;
         return;
     }
     const float* lp = logp + (long)clip * Tmax * ldp;
     const float* rp = r_prev + (long)h * Tmax * 2;
-    const bool same = c == (int)last[h];
+    const bool same = id == last[h];                       // (64-bit too: a last label outside [0, V) equals no candidate)
     const int start = out_len > 1 ? out_len : 1;
     for (int t = 0; t < start - 1 && t < T; ++t) { rn_out[2 * t] = CTC_LOGZERO; rn_out[2 * t + 1] = CTC_LOGZERO; }
     float rn = (out_len == 0) ? lp[c] : CTC_LOGZERO, rb = CTC_LOGZERO;          // r[start-1]

@@ -1874,14 +1874,16 @@ def ctc_prefix_score_clips(logp: torch.Tensor, tlen: torch.Tensor, r_prev: torch
 
 
 def mha_src_step_fwd(q: torch.Tensor, kv: torch.Tensor, clip_of: torch.Tensor, tlen: torch.Tensor, *, Tmax: int, H: int,
-                     scale: float = 0.125) -> torch.Tensor:
+                     scale: float = 0.125, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """q bf16 [n, >= H * 64], kv bf16 [C * Tmax, >= 2 * H * 64] (k | v per row), clip_of int32 [n], tlen int32 [C] -> ctx bf16 [n, H * 64]: row r
-    over the tlen[clip_of[r]] source frames of its clip (svsr_mha_src_step_fwd)."""
+    over the tlen[clip_of[r]] source frames of its clip (svsr_mha_src_step_fwd).  out: bf16 [n, H * 64] of any row pitch (a column slice of
+    a wider tensor) to write instead of a new tensor."""
     n, C = q.shape[0], tlen.numel()
     assert q.dtype == BF16 and q.dim() == 2 and q.stride(1) == 1 and kv.dtype == BF16 and kv.dim() == 2 and kv.stride(1) == 1
     assert kv.shape[0] == C * Tmax and clip_of.dtype == torch.int32 and clip_of.is_contiguous() and clip_of.numel() == n
     assert tlen.dtype == torch.int32 and tlen.is_contiguous()
-    ctx = torch.empty((n, H * 64), dtype=BF16, device=q.device)
+    ctx = torch.empty((n, H * 64), dtype=BF16, device=q.device) if out is None else out
+    assert ctx.dtype == BF16 and ctx.shape == (n, H * 64) and ctx.stride(1) == 1
     _call("svsr_mha_src_step_fwd", _p(q), q.stride(0), _p(kv), kv.stride(0), _p(clip_of), _p(tlen), C, int(Tmax), n, H, float(scale), _p(ctx),
           ctx.stride(0), _stream(), label="k_mha_src_step", flops=4.0 * n * Tmax * H * 64, nbytes=256.0 * n * H * Tmax)
     return ctx

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import search_cases as SC
 from golden_cases import build_lrs_infer_case
 
 pytestmark = pytest.mark.gpu
@@ -60,6 +61,45 @@ def test_beam_select_kernel_equals_its_torch_statement(dev, rows, V, beam):
     ties = sum(int((t[row_lo_c : row_lo_c + k][1:] == t[row_lo_c : row_lo_c + k][:-1]).sum()) for row_lo_c, k in zip(out_off, w_count))
     print(f"rows {rows[:4]}.. V {V} beam {beam}: {o} winners, {ties} exact ties among neighbours, {int((t < -1e8).sum())} LOGZERO winners")
     assert ties > 0
+
+
+
+def _bits(t):
+    return t.view(torch.int32) if t.is_floating_point() else t
+
+
+def _same_but_nan(got, want):
+    """NaN where the reference has NaN, and the reference's bits everywhere else"""
+    nan = torch.isnan(want)
+    return torch.equal(torch.isnan(got), nan) and torch.equal(_bits(got[~nan]), _bits(want[~nan]))
+
+
+@pytest.mark.parametrize("name", list(SC.BEAM_EDGE_CASES))
+def test_beam_select_kernel_at_its_documented_edges(dev, name):
+    """tests/search_cases.py BEAM_EDGE_CASES against `beam_select_reference` (tests/test_search_cases_cpu.py checks the reference's own order
+    on the same inputs): 1, 2 and 4 planes (the fourth with a negative weight); a row pitch wider than V whose extra columns hold NaN and
+    +inf; NaN (above everything, by index), +inf and -inf among the totals of one plane; the 40 winners tied across two slice boundaries,
+    all inside the last partial slice, and all inside slice 0 beside a clip without rows.  Indices exact, totals and values bit for bit
+    where not NaN, two launches bit for bit."""
+    from syncvsr_amd import ops
+
+    planes, weights, run, rows, V, beam, (w_prev, w_tok, w_total, w_vals, w_count) = SC.beam_edge_case(name)
+    row_lo, out_off, o = SC.beam_layout(rows, V, beam)
+    i32 = dict(dtype=torch.int32, device=dev)
+    d_planes, d_run = [p.to(dev) for p in planes], run.to(dev)
+    assert all(p.stride(0) == planes[0].shape[1] for p in d_planes)
+    clip_of = torch.tensor([c for c, r in enumerate(rows) for _ in range(r)], **i32)
+    got = [ops.beam_select(d_planes, weights, d_run, clip_of, torch.tensor(row_lo, **i32), torch.tensor(out_off, **i32), beam=beam, V=V,
+                           max_rows=max(rows), out_rows=o) for _ in range(2)]
+    torch.cuda.synchronize()
+    prev, tok, total, vals, clip_out, count = [t.cpu() for t in got[0]]
+    assert count.tolist() == w_count
+    assert torch.equal(prev, w_prev) and torch.equal(tok, w_tok)
+    assert _same_but_nan(total, w_total) and _same_but_nan(vals, w_vals)
+    assert torch.equal(clip_out, clip_of.cpu()[w_prev])
+    assert all(torch.equal(_bits(a), _bits(b)) for a, b in zip(got[0], got[1]))              # run to run
+    print(f"{name}: rows {rows} V {V} pitch {planes[0].shape[1]} beam {beam} planes {len(planes)}: {o} winners, {int(torch.isnan(w_total).sum())} NaN, "
+          f"{int(torch.isinf(w_total).sum())} inf")
 
 
 def test_beam_select_rejects_what_it_cannot_rank(dev):
@@ -157,6 +197,200 @@ def test_ctc_prefix_clips_one_clip_equals_the_single_clip_entry_point(dev, T, V,
         assert torch.equal(psi_one, psi_pad), out_len
         assert torch.equal(r_one, r_pad[:, :, :T]), out_len
         assert bool((r_pad[:, :, T:] == O.CTC_LOGZERO).all()), out_len
+
+
+
+def _ctc_clip_inputs(g, tlens, V, clip_of, Tmax=None, out_len=0):
+    """logp [C, Tmax, V] and r_prev [n, Tmax, 2] with NaN wherever a clip has no frame (and in every row without a clip); the state of a live
+    row is finite in both columns — so the "same label" branch (phi = r_b) differs from the other (phi = logaddexp(r_n, r_b)) — and -1e10
+    before frame out_len - 1, as a prefix of out_len labels leaves it."""
+    from oracle import lrs_oracle as O
+
+    C, Tmax = len(tlens), Tmax or max(tlens)
+    logp = torch.full((C, Tmax, V), float("nan"))
+    for c, T in enumerate(tlens):
+        logp[c, :T] = torch.log_softmax(2.0 * torch.randn(T, V, generator=g), dim=-1)
+    r_prev = torch.full((len(clip_of), Tmax, 2), float("nan"))
+    for r, c in enumerate(clip_of):
+        if 0 <= c < C:
+            r_prev[r, : tlens[c]] = -5.0 * torch.rand(tlens[c], 2, generator=g) - 0.1 * torch.arange(tlens[c]).view(-1, 1)
+            r_prev[r, : min(max(out_len - 1, 0), tlens[c])] = O.CTC_LOGZERO
+    return logp, r_prev
+
+
+def _ctc_row_matches_oracle(r_new_r, psi_r, logp_c, r_prev_r, last_r, ids_r, out_len, eos, T, where):
+    """one hypothesis (r_new_r [S, Tmax, 2], psi_r [S]) under the criteria of test_ctc_prefix_clips_kernel_matches_restatement_per_clip"""
+    from oracle import lrs_oracle as O
+
+    r_ref, psi_ref = O.ctc_prefix_score(logp_c[:T].double(), r_prev_r[None, :T].double(), torch.tensor([int(last_r)]), None if ids_r is None else ids_r[None],
+                                        out_len, 0, eos)
+    live = psi_ref[0] > -1e9
+    assert torch.equal(live, psi_r > -1e9), where
+    np.testing.assert_allclose(psi_r.numpy()[live.numpy()], psi_ref[0].numpy()[live.numpy()], atol=2e-4, rtol=1e-5, err_msg=str(where))
+    rl = r_ref[0] > -1e9
+    np.testing.assert_allclose(r_new_r[:, :T].numpy()[rl.numpy()], r_ref[0].numpy()[rl.numpy()], atol=5e-4, rtol=1e-5, err_msg=str(where))
+    assert bool((r_new_r[:, :T][~rl] < -1e9).all()) and bool((r_new_r[:, T:] == O.CTC_LOGZERO).all()), where
+    return psi_ref[0]
+
+
+@pytest.mark.parametrize("S", [None, 7])
+def test_ctc_prefix_clips_rows_without_frames_and_a_length_above_tmax(dev, S):
+    """Clips of 9, 0 and 5 frames, two rows each, one row of clip -1 and one of clip C: the rows of the empty clip and the two stray rows are
+    -1e10 throughout (their logp and r_prev are NaN), the others match the oracle; the same launch with tlen[0] = Tmax + 3 gives the same bits."""
+    from oracle import lrs_oracle as O
+    from syncvsr_amd import ops
+
+    tlens, V, eos = (9, 0, 5), 41, 40
+    clip_of = [0, 0, 1, 1, 2, 2, -1, 3]
+    n, Tmax = len(clip_of), 9
+    for out_len in (0, 2):
+        g = torch.Generator().manual_seed(500 + out_len + (S or 0))
+        logp, r_prev = _ctc_clip_inputs(g, tlens, V, clip_of, out_len=out_len)
+        last = torch.randint(1, V - 1, (n,), generator=g)
+        ids = None if S is None else torch.stack([torch.randperm(V, generator=g)[:S] for _ in range(n)])
+        if ids is not None:
+            ids[:, 0] = last
+            ids[0, 1], ids[4, 1] = eos, 0
+        ids_d = None if ids is None else ids.to(dev)
+        out = []
+        for t0 in (Tmax, Tmax + 3):
+            tl = torch.tensor([t0, 0, 5], dtype=torch.int32, device=dev)
+            out.append(ops.ctc_prefix_score_clips(logp.to(dev), tl, r_prev.to(dev), last.to(dev), ids_d, torch.tensor(clip_of, dtype=torch.int32, device=dev),
+                                                  out_len, 0, eos))
+        torch.cuda.synchronize()
+        assert torch.equal(out[0][0], out[1][0]) and torch.equal(out[0][1], out[1][1]), "tlen = Tmax + 3 must behave as Tmax"
+        r_new, psi = out[1][0].cpu(), out[1][1].cpu()
+        assert r_new.shape == (n, S or V, Tmax, 2)
+        for r, c in enumerate(clip_of):
+            if not 0 <= c < 3 or tlens[c] == 0:
+                assert bool((r_new[r] == O.CTC_LOGZERO).all()) and bool((psi[r] == O.CTC_LOGZERO).all()), (out_len, r)
+            else:
+                _ctc_row_matches_oracle(r_new[r], psi[r], logp[c], r_prev[r], last[r], None if ids is None else ids[r], out_len, eos, tlens[c], (out_len, r))
+
+
+def test_ctc_prefix_clips_candidate_ids_and_last_labels_outside_the_vocabulary(dev):
+    """-1, V, 2^31 and 2^32 + 5 as candidates are impossible extensions (-1e10, nothing read), whatever their low 32 bits say; the other
+    columns keep the bits of a launch with valid ids in those places.  A last label of 2^32 + 7 is not label 7: the row scores candidate 7
+    as any other label (the oracle with last = -1)."""
+    from oracle import lrs_oracle as O
+    from syncvsr_amd import ops
+
+    tlens, V, eos, S = (9, 5), 41, 40, 7
+    clip_of = [0, 0, 1, 1]
+    n = len(clip_of)
+    for out_len in (0, 2):
+        g = torch.Generator().manual_seed(600 + out_len)
+        logp, r_prev = _ctc_clip_inputs(g, tlens, V, clip_of, out_len=out_len)
+        last = torch.randint(1, V - 1, (n,), generator=g)
+        ids = torch.stack([torch.randperm(V, generator=g)[:S] for _ in range(n)])
+        ids[1, 4] = last[1]                                    # a true "same label" pair stays one
+        ids[2, 5] = 7
+        last[2] = 2 ** 32 + 7
+        bad = ids.clone()
+        bad[:, :4] = torch.tensor([-1, V, 2 ** 31, 2 ** 32 + 5])
+        tl = torch.tensor(tlens, dtype=torch.int32, device=dev)
+        cl = torch.tensor(clip_of, dtype=torch.int32, device=dev)
+        r_ok, psi_ok = ops.ctc_prefix_score_clips(logp.to(dev), tl, r_prev.to(dev), last.to(dev), ids.to(dev), cl, out_len, 0, eos)
+        r_bad, psi_bad = ops.ctc_prefix_score_clips(logp.to(dev), tl, r_prev.to(dev), last.to(dev), bad.to(dev), cl, out_len, 0, eos)
+        torch.cuda.synchronize()
+        r_ok, psi_ok, r_bad, psi_bad = r_ok.cpu(), psi_ok.cpu(), r_bad.cpu(), psi_bad.cpu()
+        for j in range(4):
+            assert bool((psi_bad[:, j] == O.CTC_LOGZERO).all()) and bool((r_bad[:, j] == O.CTC_LOGZERO).all()), (out_len, int(bad[0, j]))
+        assert torch.equal(_bits(psi_bad[:, 4:]), _bits(psi_ok[:, 4:])) and torch.equal(_bits(r_bad[:, 4:]), _bits(r_ok[:, 4:]))
+        ref_last = last.clone()
+        ref_last[2] = -1
+        for r, c in enumerate(clip_of):
+            psi_ref = _ctc_row_matches_oracle(r_ok[r], psi_ok[r], logp[c], r_prev[r], ref_last[r], ids[r], out_len, eos, tlens[c], (out_len, r))
+            if r == 2:                                         # the inputs can tell the two branches apart at candidate 7
+                other = O.ctc_prefix_score(logp[c, : tlens[c]].double(), r_prev[r : r + 1, : tlens[c]].double(), torch.tensor([7]), ids[r : r + 1], out_len, 0, eos)[1][0]
+                assert abs(float(other[5] - psi_ref[5])) > 1e-2
+
+
+@pytest.mark.parametrize("T,out_len", [(5, 4), (5, 5), (1, 0), (1, 1)])
+@pytest.mark.parametrize("S", [None, 7])
+def test_ctc_prefix_clips_prefix_as_long_as_the_clip(dev, T, out_len, S):
+    """out_len = T - 1 and T: the frame loop runs once or not at all.  Against the oracle; with out_len = T every label but eos is -1e10 and
+    eos is logaddexp of r_prev at the last frame."""
+    from oracle import lrs_oracle as O
+    from syncvsr_amd import ops
+
+    V, eos, n, Tmax = 41, 40, 3, T + 2
+    g = torch.Generator().manual_seed(700 + 10 * T + out_len + (S or 0))
+    logp, r_prev = _ctc_clip_inputs(g, (T,), V, [0] * n, Tmax=Tmax, out_len=out_len)
+    last = torch.randint(1, V - 1, (n,), generator=g)
+    ids = None if S is None else torch.stack([torch.randperm(V - 1, generator=g)[:S] for _ in range(n)])
+    if ids is not None:
+        ids[:, 0] = last
+        ids[0, 1], ids[1, 2] = eos, 0
+    r_new, psi = ops.ctc_prefix_score_clips(logp.to(dev), torch.tensor([T], dtype=torch.int32, device=dev), r_prev.to(dev), last.to(dev),
+                                            None if ids is None else ids.to(dev), torch.zeros(n, dtype=torch.int32, device=dev), out_len, 0, eos)
+    torch.cuda.synchronize()
+    r_new, psi = r_new.cpu(), psi.cpu()
+    assert bool(torch.isfinite(r_new).all()) and bool(torch.isfinite(psi).all())
+    for r in range(n):
+        _ctc_row_matches_oracle(r_new[r], psi[r], logp[0], r_prev[r], last[r], None if ids is None else ids[r], out_len, eos, T, (T, out_len, r))
+        if out_len == T:
+            lab = torch.arange(V) if ids is None else ids[r]
+            assert bool((psi[r][lab != eos] == O.CTC_LOGZERO).all())
+            want = float(torch.logaddexp(r_prev[r, T - 1, 0].double(), r_prev[r, T - 1, 1].double()))
+            assert bool(((psi[r][lab == eos] - want).abs() <= 2e-4 + 1e-5 * abs(want)).all())
+    assert out_len != T or S is not None or int((psi > -1e9).sum()) == n                       # (every row met eos among the V candidates)
+
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# svsr_mha_src_step_fwd
+# ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(SC.SRC_STEP_SHAPES))
+def test_mha_src_step_kernel_equals_its_fp64_statement(dev, name):
+    """tests/search_cases.py SRC_STEP_SHAPES: clips of 1 to 150 frames (one to three chunks of 64 keys, partial last chunks of 1, 2 and 22
+    keys), peak keys at the first and last frame and on both sides of the first chunk boundary, rows without a clip, a clip without frames, a
+    length above Tmax, 45 waves (the last workgroup holds one), q a column slice of a [n, 3D] tensor, kv rows of 2D + 8 with NaN in every
+    frame and column that is not the clip's.  Elementwise |got - want| <= 2^-8 |want| + 2^-10 A against the fp64 statement (A = sum_k p_k
+    |v_k|): two half-ulps of the bf16 result, and the fp32 error of scores and exp; tests/test_search_cases_cpu.py shows an fp32 restatement
+    of the kernel at 0.68 / 0.71 of this bound (t150 / t130) and two wrong ones hundreds of times above it.  Rows without keys are exact
+    zeros.  Written into a column slice of a wider tensor, the same bits arrive and the columns beside them keep theirs."""
+    from syncvsr_amd import ops
+
+    case, want, A = SC.src_step_shape(name)
+    H, Tmax, D, n = case["H"], case["Tmax"], case["H"] * 64, len(case["clip_of"])
+    q = case["q_wide"].to(dev)[:, D : 2 * D]
+    kv = case["kv"].to(dev)
+    assert q.stride(0) == 3 * D and kv.stride(0) == 2 * D + 8
+    clip_of = torch.tensor(case["clip_of"], dtype=torch.int32, device=dev)
+    tlen = torch.tensor(case["tlens"], dtype=torch.int32, device=dev)
+    got = ops.mha_src_step_fwd(q, kv, clip_of, tlen, Tmax=Tmax, H=H, scale=case["scale"])
+    wide = torch.full((n, D + 24), 7.0, dtype=torch.bfloat16, device=dev)
+    ret = ops.mha_src_step_fwd(q, kv, clip_of, tlen, Tmax=Tmax, H=H, scale=case["scale"], out=wide[:, 8 : 8 + D])
+    torch.cuda.synchronize()
+    assert got.shape == (n, D) and got.dtype == torch.bfloat16 and ret.data_ptr() == wide[:, 8:].data_ptr()
+    got, wide = got.cpu(), wide.cpu()
+    assert bool(torch.isfinite(got.float()).all())
+    for r in SC.src_step_dead_rows(case):
+        assert not got[r].any(), r
+    ratio = SC.src_step_ratio(got, want, A)
+    print(f"{name}: H {H} Tmax {Tmax} rows {n}: max error / bound = {ratio:.3f}")
+    assert ratio <= 1.0
+    assert torch.equal(_bits(wide[:, 8 : 8 + D].contiguous()), _bits(got))
+    assert bool((wide[:, :8] == 7.0).all()) and bool((wide[:, 8 + D :] == 7.0).all())
+
+
+def test_mha_src_step_rejects_pitches_and_alignment_it_cannot_load(dev):
+    from syncvsr_amd import _lib, ops
+
+    H, D, Tmax, n = 1, 64, 4, 2
+    i32 = dict(dtype=torch.int32, device=dev)
+    clip_of, tlen = torch.zeros(n, **i32), torch.tensor([Tmax], **i32)
+    bf = dict(dtype=torch.bfloat16, device=dev)
+    q, kv = torch.zeros(n, 3 * D, **bf), torch.zeros(Tmax, 2 * D, **bf)
+    ops.mha_src_step_fwd(q[:, :D], kv, clip_of, tlen, Tmax=Tmax, H=H)                       # (the well-formed call is taken)
+    with pytest.raises(_lib.SvsrError):
+        ops.mha_src_step_fwd(torch.zeros(n, 3 * D + 4, **bf)[:, :D], kv, clip_of, tlen, Tmax=Tmax, H=H)        # q_pitch % 8 != 0
+    with pytest.raises(_lib.SvsrError):
+        ops.mha_src_step_fwd(q[:, :D], torch.zeros(Tmax, 2 * D - 8, **bf), clip_of, tlen, Tmax=Tmax, H=H)       # kv_pitch < 2 * H * 64
+    with pytest.raises(_lib.SvsrError):
+        ops.mha_src_step_fwd(q[:, 4 : 4 + D], kv, clip_of, tlen, Tmax=Tmax, H=H)                                # q 8 bytes off a 16-byte boundary
+    torch.cuda.synchronize()
 
 
 # ----------------------------------------------------------------------------------------------------------------------

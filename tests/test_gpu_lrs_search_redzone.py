@@ -3,7 +3,8 @@ processes under the two allocators of tests/conftest.py (see tests/test_gpu_redz
 tensor: a stray STORE fails the test that made it) and SVSR_TAILFLUSH=1 (every tensor ends against an unmapped page: a READ behind it ends
 the child in the test that made it).  All three entry points reach their operands through computed indices (row -> clip -> frame block,
 flat index -> (row, token), output offsets), at shapes that are no multiples of the 64-lane waves, the 256-thread workgroups or the
-slices: 41 and 5,049 units, 1 to 40 rows per clip, clips of 1, 5, 9, 37 frames."""
+slices: 41 and 5,049 units, 1 to 40 rows per clip, clips of 1, 5, 9, 37 frames; source attention over clips of 1 to 150 frames (partial last
+chunks of keys, a length above Tmax, rows without a clip), plane pitches wider than V, candidate ids far outside the vocabulary."""
 import os
 import subprocess
 import sys
@@ -14,7 +15,7 @@ pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 FILE = os.path.join(HERE, "test_gpu_lrs_search_clips.py")
-KERNEL_TESTS = "beam_select or ctc_prefix_clips or decoder_step or tiny_model"
+KERNEL_TESTS = "beam_select or ctc_prefix_clips or mha_src_step or decoder_step or tiny_model"
 
 
 def _run(env_key: str):
