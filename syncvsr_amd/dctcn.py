@@ -22,12 +22,11 @@ from __future__ import annotations
 from typing import Any, Optional
 
 import torch
-import torch.nn as nn
 
 from . import ops
 from .config import Config
 from .dctcn_init import (SE_REDUCTION, TCN, dctcn_buffer_specs, dctcn_dims, dctcn_init_state_dict, dctcn_layers, dctcn_param_specs)
-from .model import _attach, _frontend_forward, _get, _ParamStore, _SideStream
+from .model import _frontend_forward, _ParamStore, _StoreModule
 
 BF16 = torch.bfloat16
 
@@ -77,7 +76,7 @@ def _unsupported(config: Config) -> list[str]:
     return why
 
 
-class DCTCNLightningModule(nn.Module):
+class DCTCNLightningModule(_StoreModule):
     def __init__(self, config: Config, seed: Optional[int] = None):
         super().__init__()
         if not isinstance(config, Config):
@@ -88,6 +87,7 @@ class DCTCNLightningModule(nn.Module):
             raise NotImplementedError("; ".join(why))
         self.dims = dctcn_dims(config)
         self.audio_alignment, self.vq_groups, self.audio_vocab_size = self.dims["A"], self.dims["G"], self.dims["V"]
+        self.codec = "vq"                    # pre-tokenised vq-wav2vec tokens: attach_audio_codec refuses the wav2vec2 tokeniser
         optim = config.get("optim", Config())
         w = optim.get("loss_audio_weight", optim.get("lambda_audio"))         # the module reads the first, the shipped yaml holds the second
         if w is None:
@@ -96,23 +96,11 @@ class DCTCNLightningModule(nn.Module):
         self.mixup_alpha = float(optim.get("mixup_alpha", 0.0))
         self.label_smoothing = float(config.get_path("train.label_smoothing", 0.0))
         self.use_boundary = bool(config.model.dctcn.use_boundary)
-        self._specs = dctcn_param_specs(config)
-        self._bspecs = dctcn_buffer_specs(config)
-        sd = dctcn_init_state_dict(config, seed=0 if seed is None else seed)
-        for name, shape, kind in self._specs:
-            t = sd[name]
-            if kind == "conv" and len(shape) == 4:
-                t = t.contiguous(memory_format=torch.channels_last)
-            _attach(self, name, t, True)
-        for name, shape, kind in self._bspecs:
-            _attach(self, name, sd[name], False)
+        self._attach_state(dctcn_param_specs(config), dctcn_buffer_specs(config), dctcn_init_state_dict(config, seed=0 if seed is None else seed))
         self.stem_name, self.trunk_name = "model.frontend3D", "model.trunk"
         self.stem_act = self.trunk_act = ops.ACT_SWISH                        # tcn/model.py:118-119, tcn/models/resnet.py with relu_type swish
-        self._side = _SideStream()
-        self._store: Optional[_ParamStore] = None
         self._prep: Optional[dict] = None
         self._last: dict[str, Any] = {}
-        self.register_load_state_dict_post_hook(lambda module, incompatible: module.mark_params_dirty())
         self.eval()
 
     # ------------------------------------------------------------------------------------------------
@@ -127,13 +115,11 @@ class DCTCNLightningModule(nn.Module):
         """Call after changing parameters or buffers in place: the bf16 shadows, the tap-major convolution weights and the folded BatchNorm
         coefficients are rebuilt at the next forward (load_state_dict and .to(device) do this themselves)."""
         self._prep = None
-        if self._store is not None:
-            self._store.shadow_fresh = False
+        super().mark_params_dirty()
 
     def store(self) -> _ParamStore:
-        dev = _get(self, self._specs[0][0]).device
-        if self._store is None or self._store.device != dev or not self._store.owns(self):
-            self._store = _ParamStore(self, dev)
+        old = self._store
+        if super().store() is not old:
             self._prep = None
         return self._store
 

@@ -22,7 +22,7 @@ import torch.distributed as dist
 
 from . import ops
 from .config import Config
-from .model import TransformerLightningModule, _xt_skips
+from .model import TransformerLightningModule, _StoreModule, _xt_skips
 from .shape_cache import ShapeLRU, shape_key
 
 
@@ -158,6 +158,9 @@ class TrainStep:
         gradient accumulation over windows of N micro-steps (class docstring).  Eager and native; under native ONE recorded list per batch
         shape serves the first, middle and last micro-steps (the zero-fill and the optimiser tail are op groups a replay leaves out), and
         with max_shapes > 1 the micro-batches of a window may differ in shape."""
+        if not isinstance(model, _StoreModule) or type(model)._loss_weights is _StoreModule._loss_weights:
+            raise TypeError(f"TrainStep drives a model._StoreModule with a training step, one that states its _loss_weights "
+                            f"(TransformerLightningModule, lrs_model.E2E), got {type(model).__name__}")
         self.model = model
         self.is_lrw = isinstance(model, TransformerLightningModule)
         if self.is_lrw:            # LRW/video/config/*.yaml: optim.optimizer / optim.scheduler / train.gradient_clip_val
@@ -178,7 +181,7 @@ class TrainStep:
             raise NotImplementedError("accumulate > 1 with use_graph=True: a captured HIP graph holds the whole step, optimiser included, and "
                                       "cannot leave the zero-fill or the optimiser out of a replay (use native=True or the eager step)")
         self.window = AccumWindow(accum)
-        if accum > 1 or getattr(model, "_loss_scale", 1.0) != 1.0:
+        if accum > 1 or model._loss_scale != 1.0:
             model.set_loss_scale(1.0 / accum)          # the seeds of the backward: written in place, outside any recorded region
         self.lr = float(opt.lr)
         self.betas = (float(opt.betas[0]), float(opt.betas[1]))
@@ -194,13 +197,12 @@ class TrainStep:
         self.dp = GradReducer(model, process_group, bucket_mb, always_reduce, grad_comm_dtype) if data_parallel and (self.world > 1 or always_reduce) else None
         if not data_parallel:
             model.grad_ready_hook = None
-        if hasattr(model, "accumulate_into_grads"):
-            model.accumulate_into_grads(False)
+        model.accumulate_into_grads(False)
         self.use_graph = use_graph
         self.native = bool(native)
         if self.native and use_graph:
             raise ValueError("native=True and use_graph=True are two ways of replaying a step: pick one")
-        if self.native and not self.is_lrw and getattr(model, "length_norm", False):
+        if self.native and not self.is_lrw and model.length_norm:
             raise NotImplementedError("native=True: transformer_length_normalized_loss needs a torch kernel inside the step (use native=False)")
         if int(max_shapes) < 1:
             raise ValueError("max_shapes must be >= 1")
@@ -215,7 +217,7 @@ class TrainStep:
         self._rec: Optional[ops.StepRecorder] = None
         self.fused_encoder_fallbacks = 0        # times _watch_fused_encoder switched the encoder to the launch chain
         self.host_ms: list[float] = []          # host time of the last steps' enqueue (bench.py reports the median)
-        if use_graph and getattr(model, "layer_drop_p", 0.0) > 0.0:
+        if use_graph and model.layer_drop_p > 0.0:
             raise NotImplementedError("layer_dropout skips whole encoder blocks at random: the launch sequence differs from step to "
                                       "step and cannot be replayed from one captured HIP graph (use use_graph=False)")
         # Weight-gradient launches only feed the flat gradient buffer, so in EAGER mode they run on a side stream next to the
@@ -345,7 +347,7 @@ class TrainStep:
         """The first-touch map of this model's gradient buffer (ops.GradCoverage), or None where the whole-buffer fill stays: models that declare
         no spans (model.grad_store_spans: the x-transformers encoder with its layer drop), ops.GRAD_STORE off (tests: the all-add reference).  Used by the steps of
         accumulate = 1 only: a window's micro-steps share one recorded list, whose frozen modes cannot tell the first micro-step from the rest."""
-        if not ops.GRAD_STORE or not hasattr(self.model, "grad_store_spans"):
+        if not ops.GRAD_STORE:
             return None
         key, cov = self.__dict__.get("_cover", (None, None))
         if key != st.grad.data_ptr():
@@ -440,8 +442,7 @@ class TrainStep:
         if model._side.stream is None:
             model._side.stream = torch.cuda.Stream()
         model.direct_constants(static[0].device)
-        if getattr(model, "_drop_word", None) is None and (model.drop_p > 0.0 or model.attn_drop_p > 0.0 or getattr(model, "emb_drop_p", 0.0) > 0.0
-                                                           or getattr(model, "_codec_samples", lambda: False)()):
+        if model._drop_word is None and (model.drop_p > 0.0 or model.attn_drop_p > 0.0 or model.emb_drop_p > 0.0 or model._codec_samples()):
             model._advance_dropout(static[0].device)      # creates the seed word outside the recorded region ...
             ops.word_add(model._drop_word, -1)             # ... and leaves its value where the first forward expects it
         rec = ops.StepRecorder()
@@ -460,7 +461,7 @@ class TrainStep:
 
     def _layer_drop(self) -> bool:
         """Layer drop is on: the recorded lists hold every encoder block as an op group (model._xt_encoder_forward / _backward)."""
-        return self.is_lrw and getattr(self.model, "layer_drop_p", 0.0) > 0.0
+        return self.is_lrw and self.model.layer_drop_p > 0.0
 
     def _count(self, key, i: int) -> None:
         self._counts.setdefault(key, [0, 0])[i] += 1
@@ -692,11 +693,10 @@ class TrainStep:
               # compute-unit count the splits are planned for is one of them and is a fixed 256, not the device's): a resumed run is
               # bit-identical when these agree
               "reduction_plan": torch.tensor(ops.reduction_plan_params(), dtype=torch.int64)}
-        if hasattr(self.model, "rng_state"):        # dropout seed word + layer-drop generator: a resumed run draws the same masks / skips
-            rs = self.model.rng_state()
-            sd["dropout_word"] = torch.tensor([rs["dropout_word"]], dtype=torch.int64)
-            if "layer_rng" in rs:
-                sd["layer_rng"] = _rng_state_to_tensor(rs["layer_rng"])
+        rs = self.model.rng_state()                 # dropout seed word + layer-drop generator: a resumed run draws the same masks / skips
+        sd["dropout_word"] = torch.tensor([rs["dropout_word"]], dtype=torch.int64)
+        if "layer_rng" in rs:
+            sd["layer_rng"] = _rng_state_to_tensor(rs["layer_rng"])
         # saved inside a window: its position and the gradient accumulated so far, so that a resumed run finishes the window (at a window
         # boundary neither key is written)
         win = self.window.state_dict()
@@ -726,7 +726,7 @@ class TrainStep:
                 raise ValueError("a checkpoint saved inside a window carries the accumulated gradient (accum_grad) of this parameter layout")
             st.grad.copy_(sd["accum_grad"])
         self.opt_state[1] = 0                    # (word 1 counts the skipped steps of THIS run; older checkpoints kept a float there)
-        if "dropout_word" in sd and hasattr(self.model, "load_rng_state"):
+        if "dropout_word" in sd:            # (checkpoints of LRS runs written before E2E had an rng_state carry none)
             rs = {"dropout_word": int(sd["dropout_word"].reshape(-1)[0])}
             if "layer_rng" in sd:
                 try:
@@ -746,7 +746,7 @@ class TrainStep:
         raw = self.opt_state.cpu()
         if self.is_lrw and ops.check_enc_clusters(reset=False):
             self._watch_fused_encoder()
-        if not self.is_lrw and hasattr(self.model, "check_targets"):
+        if not self.is_lrw:
             self.model.check_targets()          # a label outside [1, odim) reached svsr_lrs_targets: raises with the cause
         f = raw.view(torch.float32)
         return {"step": int(raw[0]), "lr": float(f[2]), "grad_norm": float(f[3]), "skipped_steps": int(raw[1]),
@@ -890,8 +890,8 @@ class GradReducer:
         if seg.is_cuda:
             if fence:
                 self.comm_stream.wait_stream(torch.cuda.current_stream())     # the segment's producers are enqueued there ...
-                side = getattr(self.model, "_side", None)
-                if side is not None and side.stream is not None and (side.enabled or side.enabled_small):
+                side = self.model._side
+                if side.stream is not None and (side.enabled or side.enabled_small):
                     self.comm_stream.wait_stream(side.stream)                 # ... and, for weight gradients, on the model's side stream
             with torch.cuda.stream(self.comm_stream):
                 if self.measure and self._bucket_events:

@@ -30,6 +30,7 @@ from typing import Any, NamedTuple, Optional
 import torch
 
 from . import ops
+from .model import _require_device
 
 LOGZERO = -1.0e10          # ctc_prefix_score.py:33
 BF16 = torch.bfloat16
@@ -236,8 +237,7 @@ class DecoderScorer:
         if xs.dim() != 3 or xs.size(-1) != m.ddim:
             raise ValueError(f"xs is {tuple(xs.shape)}, the decoder expects [clips, frames, ddim = {m.ddim}] (the reference feeds the encoder "
                              "output to the decoder directly at inference, lightning.py:114-119, which needs adim == ddim)")
-        if xs.device.type != "cuda":
-            raise RuntimeError("syncvsr_amd runs on an MI355X HIP device only; there is no CPU fallback (use oracle/ for checking)")
+        _require_device(xs)
         st = _fresh_store(m, self)
         C, Tmax, D = xs.shape
         tlen = torch.as_tensor(lengths, dtype=torch.int32).to(xs.device).contiguous()

@@ -17,13 +17,13 @@ import math
 from typing import Any, Optional
 
 import torch
-import torch.nn as nn
 
 from . import ops
 from .config import Config
 from .lrs_init import LRS_ODIM, lrs_audio_dims, lrs_buffer_specs, lrs_init_state_dict, lrs_param_specs
 from . import model as _model_mod
-from .model import BF16, _Holder, _SideStream, _ParamStore, _attach, _defer_list, _frontend_backward, _frontend_forward, _get, _bn_stats, _ready
+from .model import (BF16, _Holder, _NoAutogradCtx, _ParamStore, _StoreModule, _begin_backward, _bn_stats, _defer_list, _frontend_backward, _frontend_forward,
+                    _get, _ready, _require_device)
 
 LN_EPS = 1e-12          # transformer/layer_norm.py:19
 
@@ -125,7 +125,7 @@ class _CtcFacade(_Holder):
         return self.log_softmax(hs_pad).argmax(dim=-1)
 
 
-class E2E(nn.Module):
+class E2E(_StoreModule):
     def __init__(self, odim: int = LRS_ODIM, args: Any = None, ignore_id: int = -1, seed: Optional[int] = None):
         super().__init__()
         from .lrs_init import default_lrs_args
@@ -172,24 +172,12 @@ class E2E(nn.Module):
         attn_p = args.transformer_attn_dropout_rate
         self.attn_drop_p = self.drop_p if attn_p is None else float(attn_p)
         self._sites = lrs_sites(self.elayers, self.dlayers)
-        self.dropout_seed = 0                     # base seed; the device-side word advances by one per training forward
-        self._drop_word: Optional[torch.Tensor] = None
         self.audio_alignment, self.vq_groups, self.audio_vocab_size = lrs_audio_dims(args)
         self.codec = "vq" if self.audio_alignment == 4 else "wav2vec2"
 
-        self._specs = lrs_param_specs(args, self.odim)
-        self._bspecs = lrs_buffer_specs(args, self.odim)
-        sd = lrs_init_state_dict(args, self.odim, seed=0 if seed is None else seed)
-        for name, shape, kind in self._specs:
-            t = sd[name]
-            if kind == "conv" and len(shape) == 4:
-                t = t.contiguous(memory_format=torch.channels_last)
-            _attach(self, name, t, True)
-        for name, shape, kind in self._bspecs:
-            _attach(self, name, sd[name], False)
-        self._store: Optional[_ParamStore] = None
-        self.register_load_state_dict_post_hook(lambda module, incompatible: module.mark_params_dirty())
-        self.register_load_state_dict_pre_hook(lambda module, *a, **k: module._side.join())       # (an AdamW range may still be writing the flat buffer on the side stream)
+        # (the dropout seed starts at 0 whatever `seed` is; the device-side word advances by one per training forward)
+        self._attach_state(lrs_param_specs(args, self.odim), lrs_buffer_specs(args, self.odim),
+                           lrs_init_state_dict(args, self.odim, seed=0 if seed is None else seed), dropout_seed=0)
         from .lrs_init import lrs_frontend_names
 
         self.stem_name, self.trunk_name = lrs_frontend_names(args)
@@ -197,9 +185,6 @@ class E2E(nn.Module):
             self.stem_act, self.trunk_act = ops.ACT_GELU, ops.ACT_RELU
         else:
             self.stem_act = self.trunk_act = ops.ACT_SWISH       # backbones/conv3d_extractor.py:34, modules/resnet.py:76-78
-        self.use_tr = True
-        self._side = _SideStream()
-        self.grad_ready_hook = None
         self._pos_cache: dict[tuple[str, int, str], torch.Tensor] = {}
         import weakref
 
@@ -265,46 +250,8 @@ class E2E(nn.Module):
             one("proj_decoder.weight")
         return out
 
-    def configure_optimizers(self):
-        """LRS/video/lightning.py:89-96 — the two parameter groups (decay on ndim >= 2)."""
-        do_decay = [p for p in self.parameters() if p.requires_grad and p.ndim >= 2]
-        no_decay = [p for p in self.parameters() if p.requires_grad and p.ndim < 2]
-        return [{"params": do_decay}, {"params": no_decay, "weight_decay": 0.0}]
-
-    def mark_params_dirty(self) -> None:
-        if self._store is not None:
-            self._store.shadow_fresh = False
-
-    def store(self) -> _ParamStore:
-        dev = _get(self, self._specs[0][0]).device
-        if self._store is None or self._store.device != dev or not self._store.owns(self):
-            self._store = _ParamStore(self, dev)
-        return self._store
-
-    def state_dict(self, *args, **kwargs):
-        self._side.join()             # (a TrainStep may have left the tail of its optimiser step on the side stream)
-        return super().state_dict(*args, **kwargs)
-
     # ------------------------------------------------------------------------------------------------
-    # wav2vec2 audio tokeniser (e2e_asr_transformer.py:145-157,167-180)
-    def attach_audio_codec(self, codec, sample_in_training: bool = True) -> "E2E":
-        """Registers the frozen tokeniser (audio_codec.Wav2Vec2Codec) as `self.wav2vec`, the reference's attribute: state_dict() gains its
-        `wav2vec.*` buffers, and forward / prepare_batch / train_step_direct then take float waveforms [B, 1, L] or [B, L] in the `audios`
-        slot — 8000 zeros are appended to every row and the tokens are computed inside the step.  In training mode the tokens are
-        argmax(logits + Gumbel noise) (the reference's frozen quantiser runs its gumbel_softmax branch under Lightning's model.train()),
-        keyed by the dropout seed word; sample_in_training=False keeps the eval-mode argmax.  The codec holds buffers only: it stays out of
-        parameters(), the parameter store, the optimiser, clipping and the gradient / BatchNorm-statistics collectives."""
-        from .audio_codec import Wav2Vec2Codec
-
-        if not isinstance(codec, Wav2Vec2Codec):
-            raise TypeError("attach_audio_codec takes a syncvsr_amd.audio_codec.Wav2Vec2Codec")
-        if self.codec != "wav2vec2":
-            raise ValueError(f"this model was built for the {self.codec!r} codec (args.codec): the wav2vec2 tokeniser gives 640-way tokens, A = 2")
-        codec.to(_get(self, self._specs[0][0]).device)
-        self.wav2vec = codec
-        self.codec_sample_in_training = bool(sample_in_training)
-        return self
-
+    # wav2vec2 audio tokeniser (e2e_asr_transformer.py:145-157,167-180): attach_audio_codec
     def _codec_samples(self) -> bool:
         """The tokeniser of this training step draws Gumbel noise (and so needs the seed word to advance every step)."""
         return self.training and self._modules.get("wav2vec") is not None and getattr(self, "codec_sample_in_training", False)
@@ -315,22 +262,8 @@ class E2E(nn.Module):
 
         if audios.device.type != "cuda":
             raise RuntimeError("audio waveforms must be on the MI355X device: the tokeniser has no CPU path")
-        seed = None
-        if self._codec_samples():
-            if self._drop_word is None or self._drop_word.device != audios.device:
-                self._drop_word = torch.tensor([self.dropout_seed], dtype=torch.int32, device=audios.device)
-            seed = self._drop_word
+        seed = self._seed_word(audios.device) if self._codec_samples() else None
         return self._modules["wav2vec"](audios, pad=LRS_PAD, sample=seed is not None, seed_word=seed, keep=T * self.audio_alignment)
-
-    def _advance_dropout(self, dev: torch.device) -> None:
-        if self._drop_word is None or self._drop_word.device != dev:
-            self._drop_word = torch.tensor([self.dropout_seed], dtype=torch.int32, device=dev)
-        ops.word_add(self._drop_word, 1)          # a device op (a library launch: recorded by a native step list): replays keep drawing fresh masks
-
-    def reseed_dropout(self, seed: int) -> None:
-        self.dropout_seed = int(seed)
-        if self._drop_word is not None:          # in place: a captured graph holds this word's address
-            self._drop_word.fill_(self.dropout_seed)
 
     def _d(self, site: str, attn: bool = False):
         """(seed word, site id, p) for ops.*(drop=...) or None when dropout is off (eval mode / p = 0)."""
@@ -391,8 +324,7 @@ class E2E(nn.Module):
                resnet_feats: bool = False) -> torch.Tensor:
         """`self.encoder(xs, masks)[0]` of the reference (what its inference path calls, LRS/video/lightning.py:100-101,113-116):
         x [B,T,1,H,W] -> fp32 [B,T,adim]; forward only (no autograd), honours train/eval mode for BatchNorm and dropout."""
-        if x.device.type != "cuda":
-            raise RuntimeError("syncvsr_amd runs on an MI355X HIP device only; there is no CPU fallback (use oracle/ for checking)")
+        _require_device(x)
         st = self.store()
         if not st.shadow_fresh:
             st.refresh_shadows()
@@ -412,8 +344,7 @@ class E2E(nn.Module):
         return res[2].float().view(B, T, self.adim)
 
     def forward(self, x: torch.Tensor, lengths: torch.Tensor, audios: torch.Tensor, label):
-        if x.device.type != "cuda":
-            raise RuntimeError("syncvsr_amd runs on an MI355X HIP device only; there is no CPU fallback (use oracle/ for checking)")
+        _require_device(x)
         if x.dim() != 5 or x.size(2) != 1:
             raise ValueError("x must be [B, T, 1, H, W]")
         st = self.store()
@@ -463,28 +394,8 @@ class E2E(nn.Module):
         return (x.float().contiguous(), lengths.to(device=x.device, dtype=torch.int32).contiguous(),
                 audios if audios.is_floating_point() else audios[:, : T * A].contiguous(), tg.labels, tg.ys_in, tg.ys_out)
 
-    def direct_constants(self, dev) -> None:
-        """d loss / d {loss_ctc, loss_att, loss_audio} as device scalars (made once, outside any recorded region)."""
-        if getattr(self, "_g_consts", None) is None or self._g_consts[0].device != dev:
-            self._g_consts = tuple(torch.full((), w, dtype=torch.float32, device=dev) for w in (self.mtlalpha, 1.0 - self.mtlalpha, self.audio_weight))
-            if getattr(self, "_loss_scale", 1.0) != 1.0:
-                self.set_loss_scale(self._loss_scale)
-
-    def set_loss_scale(self, scale: float = 1.0) -> None:
-        """Gradient accumulation (engine.TrainStep(accumulate=N) drives this with 1 / N): the seeds of the hand-written backward become
-        d (scale * loss) / d {loss_ctc, loss_att, loss_audio} — what `(loss * scale).backward()` hands the backward, in fp32: fp32(scale) times
-        the fp32 CTC, attention and audio weights.  Written IN PLACE and outside any recorded region (a recorded step list reads the
-        scalars by address).  The losses a step returns stay unscaled."""
-        self._loss_scale = float(scale)
-        if getattr(self, "_g_consts", None) is not None:
-            one = torch.tensor(self._loss_scale, dtype=torch.float32)
-            for g, w in zip(self._g_consts, (self.mtlalpha, 1.0 - self.mtlalpha, self.audio_weight)):
-                g.copy_(one * torch.tensor(w, dtype=torch.float32))
-
-    def loss_seeds(self, dev) -> tuple:
-        """(loss_ctc, loss_att, loss_audio) seeds: the device scalars train_step_direct hands its backward."""
-        self.direct_constants(dev)
-        return self._g_consts
+    def _loss_weights(self) -> tuple[float, ...]:
+        return (self.mtlalpha, 1.0 - self.mtlalpha, self.audio_weight)          # d loss / d {loss_ctc, loss_att, loss_audio}
 
     def grad_store_spans(self, offsets: dict, phys: dict) -> list:
         """[lo, hi) element ranges of the flat gradient buffer whose first writer in a backward pass is a weight-gradient launch with a store
@@ -499,13 +410,6 @@ class E2E(nn.Module):
                 spans.append((o, o + numel))
         return spans
 
-    def accumulate_into_grads(self, on: bool = True) -> None:
-        """The "do not zero" switch of the backward (as model.TransformerLightningModule.accumulate_into_grads): off, every backward() zeroes
-        the flat gradient buffer before it writes; on, the following backward() calls ADD into it — `(loss / N).backward()` per micro-batch
-        with the switch off for the first and on for the others, then optimizer.step().  engine.TrainStep sets it per micro-step and
-        leaves it off."""
-        self._keep_grads = bool(on)
-
     def train_step_direct(self, x, ilen, tokens, labels, ys_in, ys_out):
         """forward + backward of the loss WITHOUT autograd (inputs as prepare_batch returns them): every device operation is a library call,
         so the step can be recorded into a native step list.  -> (loss, loss_ctc, loss_att, loss_audio, acc) as forward()."""
@@ -513,12 +417,7 @@ class E2E(nn.Module):
             raise NotImplementedError("transformer_length_normalized_loss divides by a device value with a torch kernel: use the autograd path")
         st = self.store()
         self.direct_constants(x.device)
-
-        class _Ctx:
-            def mark_non_differentiable(self, *a):
-                pass
-
-        ctx = _Ctx()
+        ctx = _NoAutogradCtx()
         if tokens.is_floating_point():                 # waveforms (prepare_batch with a codec attached): tokenised in the step
             tokens = self._tokenize(tokens, x.size(1))
         tg = LrsTargets(labels, ys_in, ys_out)
@@ -912,14 +811,7 @@ class _LrsFunction(torch.autograd.Function):
         R = B * T
         A, G, V = model.audio_alignment, model.vq_groups, model.audio_vocab_size
         dev = th["h"].device
-        if not getattr(model, "_keep_grads", False):       # (accumulate_into_grads: the backward adds into the buffer)
-            st.zero_grad()
-        st.rebind_grads()
-
-        def scalar(g):
-            return (g if g is not None else torch.zeros((), device=dev)).float().contiguous()
-
-        g_ctc, g_att, g_audio = scalar(g_ctc), scalar(g_att), scalar(g_audio)
+        g_ctc, g_att, g_audio = _begin_backward(model, st, dev, g_ctc, g_att, g_audio)
         h = th["h"]
         dh = ops.zeros((R, D), BF16, dev)
         # decoder first: its parameters sit at the end of the flat gradient buffer

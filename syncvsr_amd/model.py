@@ -90,7 +90,192 @@ def _get(root: nn.Module, name: str) -> torch.Tensor:
     return obj
 
 
-class TransformerLightningModule(nn.Module):
+def _require_device(t: torch.Tensor) -> None:
+    if t.device.type != "cuda":
+        raise RuntimeError("syncvsr_amd runs on an MI355X HIP device only; there is no CPU fallback (use oracle/ for checking)")
+
+
+class _NoAutogradCtx:
+    """The `ctx` of an autograd Function whose forward / backward a train_step_direct calls by hand."""
+
+    def mark_non_differentiable(self, *a):
+        pass
+
+
+class _StoreModule(nn.Module):
+    """What the model modules share: parameters and buffers attached under the reference's state-dict names and kept in one flat
+    _ParamStore, the side stream, the device seed word of the counter-based dropout, the device scalars that seed the hand-written backward
+    and its "do not zero" switch.  A model calls _attach_state() from its __init__ and supplies `_fwd_rank(name)` and
+    `_transposed_entries(offsets)` (see _ParamStore), `_loss_weights()` if it trains, and `grad_store_spans` if its backward has
+    store-mode writers.  This class registers no module, parameter or buffer of its own."""
+
+    layer_drop_p = 0.0          # plain defaults of what engine.TrainStep reads from every model
+    emb_drop_p = 0.0
+    length_norm = False
+
+    def _attach_state(self, specs, bspecs, sd: dict, dropout_seed: int = 0) -> None:
+        self._specs, self._bspecs = specs, bspecs
+        for name, shape, kind in specs:
+            t = sd[name]
+            if kind == "conv" and len(shape) == 4:
+                t = t.contiguous(memory_format=torch.channels_last)      # physical [Co][kh][kw][Ci]
+            _attach(self, name, t, True)
+        for name, shape, kind in bspecs:
+            _attach(self, name, sd[name], False)
+        self._store: Optional[_ParamStore] = None
+        self._side = _SideStream()  # second stream for the weight-gradient launches (._side.enabled = False serialises)
+        self.grad_ready_hook = None  # called as hook(lo, hi) when flat gradient range [lo, hi) is final (DDP buckets)
+        self.use_tr = True          # ds_read_b64_tr_b16 fragments in the weight-gradient kernels
+        # Dropout masks are counter based (csrc/common.h): element i of site s is kept iff hash(seed, s, i) >= p * 2^32; the seed is a
+        # device word advanced once per training forward.
+        self.dropout_seed = int(dropout_seed)
+        self._drop_word: Optional[torch.Tensor] = None
+        self._keep_grads = False    # accumulate_into_grads
+        self._loss_scale = 1.0      # set_loss_scale
+        self._g_consts: Optional[tuple] = None
+        self.register_load_state_dict_post_hook(lambda module, incompatible: module.mark_params_dirty())
+        # (PRE hook: the copies of load_state_dict into the flat buffer must not race with an AdamW range still running on the side stream)
+        self.register_load_state_dict_pre_hook(lambda module, *a, **k: module._side.join())
+
+    def store(self) -> "_ParamStore":
+        dev = _get(self, self._specs[0][0]).device
+        if self._store is None or self._store.device != dev or not self._store.owns(self):
+            self._store = _ParamStore(self, dev)
+        return self._store
+
+    def mark_params_dirty(self) -> None:
+        """Call after changing parameters outside engine.TrainStep (load_state_dict does it): the bf16 shadows are re-cast."""
+        if self._store is not None:
+            self._store.shadow_fresh = False
+
+    def state_dict(self, *args, **kwargs):
+        self._side.join()             # (a TrainStep may have left the tail of its optimiser step on the side stream)
+        return super().state_dict(*args, **kwargs)
+
+    def configure_optimizers(self):
+        """LRW/video/src/lightning.py:216-223, LRS/video/lightning.py:89-96 — the two parameter groups (decay on ndim >= 2); the fused HIP
+        optimiser lives in engine.TrainStep."""
+        do_decay = [p for p in self.parameters() if p.requires_grad and p.ndim >= 2]
+        no_decay = [p for p in self.parameters() if p.requires_grad and p.ndim < 2]
+        return [{"params": do_decay}, {"params": no_decay, "weight_decay": 0.0}]
+
+    def attach_audio_codec(self, codec, sample_in_training: bool = True):
+        """Registers the frozen wav2vec2 tokeniser (audio_codec.Wav2Vec2Codec) as `self.wav2vec`, the reference's attribute: state_dict()
+        gains its `wav2vec.*` buffers.  The word-level model then has forward_audios (its forward / training_step still take pre-computed
+        tokens); the sentence-level model's forward / prepare_batch / train_step_direct take float waveforms [B, 1, L] or [B, L] in the
+        `audios` slot — 8000 zeros are appended to every row and the tokens are computed inside the step.  In training mode the tokens are
+        argmax(logits + Gumbel noise) (the reference's frozen quantiser runs its gumbel_softmax branch under Lightning's model.train()),
+        keyed by the dropout seed word; sample_in_training=False keeps the eval-mode argmax.  The codec holds buffers only: it stays out of
+        parameters(), the parameter store, the optimiser, clipping and the gradient / BatchNorm-statistics collectives."""
+        from .audio_codec import Wav2Vec2Codec
+
+        if not isinstance(codec, Wav2Vec2Codec):
+            raise TypeError("attach_audio_codec takes a syncvsr_amd.audio_codec.Wav2Vec2Codec")
+        if self.codec != "wav2vec2":
+            raise ValueError(f"this model was built for the {self.codec!r} codec (model.wav2vec.path of the word-level config, args.codec of the "
+                             f"sentence-level one): the wav2vec2 tokeniser gives 640-way tokens, A = 2")
+        codec.to(_get(self, self._specs[0][0]).device)
+        self.wav2vec = codec
+        self.codec_sample_in_training = bool(sample_in_training)
+        return self
+
+    def _codec_samples(self) -> bool:
+        """The tokeniser of this training step draws Gumbel noise (and so needs the seed word to advance every step)."""
+        return False
+
+    def check_targets(self) -> None:
+        """Raises if a batch prepared since the last check held a target the device kernels had to replace (models with such targets)."""
+
+    # -- dropout seed word ---------------------------------------------------------------------------
+    def _seed_word(self, dev: torch.device) -> torch.Tensor:
+        if self._drop_word is None or self._drop_word.device != dev:
+            self._drop_word = torch.tensor([self.dropout_seed], dtype=torch.int32, device=dev)
+        return self._drop_word
+
+    def _advance_dropout(self, dev: torch.device) -> None:
+        ops.word_add(self._seed_word(dev), 1)     # a device op (a library launch): graph / step-list replays keep drawing fresh masks
+
+    def reseed_dropout(self, seed: int) -> None:
+        self.dropout_seed = int(seed)
+        if self._drop_word is not None:          # in place: a captured graph / recorded step list holds this word's address
+            self._drop_word.fill_(self.dropout_seed)
+        if hasattr(self, "_layer_rng"):          # the layer-drop draws follow the seed too (per-rank / per-run reseeding)
+            self._layer_rng.seed(self.dropout_seed)
+
+    def rng_state(self) -> dict:
+        """Everything random about the next training forward, for bit-exact resume: the dropout seed word (the device counter the
+        masks are hashed from) and the python generator behind layer_dropout.  engine.TrainStep.state_dict stores it."""
+        word = self.dropout_seed if self._drop_word is None else int(self._drop_word.item())
+        out = {"dropout_word": word}
+        if hasattr(self, "_layer_rng"):
+            out["layer_rng"] = self._layer_rng.getstate()
+        return out
+
+    def load_rng_state(self, state: dict) -> None:
+        self.dropout_seed = int(state["dropout_word"])
+        if self._drop_word is not None:
+            self._drop_word.fill_(self.dropout_seed)
+        if "layer_rng" in state and hasattr(self, "_layer_rng"):
+            self._layer_rng.setstate(state["layer_rng"])
+
+    # -- seeds of the hand-written backward ----------------------------------------------------------
+    def _loss_weights(self) -> tuple[float, ...]:
+        """d (total loss) / d (each loss the model's autograd node returns), in the node's output order."""
+        raise NotImplementedError(f"{type(self).__name__} has no training step")
+
+    def direct_constants(self, dev) -> None:
+        """The loss weights as device scalars (made once per device, outside any recorded region), times the loss scale of set_loss_scale()."""
+        if self._g_consts is None or self._g_consts[0].device != dev:
+            self._g_consts = tuple(torch.full((), w, dtype=torch.float32, device=dev) for w in self._loss_weights())
+            if self._loss_scale != 1.0:
+                self.set_loss_scale(self._loss_scale)
+
+    def set_loss_scale(self, scale: float = 1.0) -> None:
+        """Gradient accumulation (engine.TrainStep(accumulate=N) drives this with 1 / N): the seeds of the hand-written backward become
+        d (scale * total loss) / d (each loss) — what `(loss * scale).backward()` hands the backward, in fp32: fp32(scale) * fp32(weight).
+        The device scalars are written IN PLACE and outside any recorded region: a recorded step list reads them by address, so the scale
+        needs no re-recording.  The losses a step returns stay unscaled."""
+        self._loss_scale = float(scale)
+        if self._g_consts is not None:
+            one = torch.tensor(self._loss_scale, dtype=torch.float32)
+            for g, w in zip(self._g_consts, self._loss_weights()):
+                g.copy_(one * torch.tensor(w, dtype=torch.float32))
+
+    def loss_seeds(self, dev) -> tuple:
+        """One seed per loss of _loss_weights(): the device scalars train_step_direct hands its backward."""
+        self.direct_constants(dev)
+        return self._g_consts
+
+    def accumulate_into_grads(self, on: bool = True) -> None:
+        """The "do not zero" switch of the backward.  Off (the default): every backward() zeroes the flat gradient buffer (the storage behind
+        every p.grad) before it writes, so `loss.backward(); optimizer.step()` needs no zero_grad().  On: the following backward() calls ADD
+        into the buffer.  Hand-rolled accumulation over N micro-batches with a foreign optimiser:
+
+            model.accumulate_into_grads(False); (model(*b0)["loss_total"] / N).backward()      # zeroes, then writes
+            model.accumulate_into_grads(True)
+            for b in rest: (model(*b)["loss_total"] / N).backward()                             # adds
+            optimizer.step(); model.accumulate_into_grads(False)
+
+        (optimizer.zero_grad() only drops the p.grad views; the buffer is zeroed by the first backward.)  engine.TrainStep sets this
+        per micro-step and leaves it off."""
+        self._keep_grads = bool(on)
+
+    def grad_store_spans(self, offsets: dict, phys: dict) -> list:
+        """[lo, hi) element ranges of the flat gradient buffer whose first writer in a backward pass is a store-mode weight-gradient launch
+        (ops.GradCoverage).  None declared: engine.TrainStep keeps the whole-buffer zero-fill."""
+        return []
+
+
+def _begin_backward(model: _StoreModule, st: "_ParamStore", dev: torch.device, *grads) -> tuple:
+    """The first lines of a hand-written backward: the zero-fill (unless accumulate_into_grads), the p.grad views, and the incoming
+    gradients as contiguous fp32 scalars (None: zero)."""
+    if not model._keep_grads:
+        st.zero_grad()
+    st.rebind_grads()
+    return tuple((g if g is not None else torch.zeros((), device=dev)).float().contiguous() for g in grads)
+
+
+class TransformerLightningModule(_StoreModule):
     """HIP-native twin of the reference LightningModule (word-level LRW model with the SyncVSR audio head)."""
 
     def __init__(self, config: Config, seed: Optional[int] = None):
@@ -118,10 +303,7 @@ class TransformerLightningModule(nn.Module):
         self.codec, self.audio_alignment, self.vq_groups, self.audio_vocab_size = audio_codec_dims(config.model.wav2vec.path)
         self.dim = hidden_dim(config)
         self.dim_p = pad64(self.dim)            # row pitch of the encoder's activations (pad columns are zero)
-        self.dropout_seed = 0 if seed is None else int(seed)
-        self._drop_word: Optional[torch.Tensor] = None
-        # Dropout masks are counter based (csrc/common.h): element i of site s is kept iff hash(seed, s, i) >= p * 2^32; the seed is a
-        # device word advanced once per training forward.
+        seed = 0 if seed is None else int(seed)
         from .dropout import lrw_sites, lrw_xt_sites
 
         self.emb_drop_p = float(bert.get("emb_dropout", 0.0))          # read directly by the module (lightning.py:45)
@@ -133,7 +315,6 @@ class TransformerLightningModule(nn.Module):
             # missing keys take BertConfig(**config.model.bert)'s defaults, 0.1 each (lightning.py:92)
             self.drop_p = float(bert.get("hidden_dropout_prob", 0.1))
             self.attn_drop_p = float(bert.get("attention_probs_dropout_prob", 0.1))
-            self.layer_drop_p = 0.0
             self._sites = lrw_sites(self.layers)
             if self.dim % 512 or self.dim // self.heads != 64:
                 raise NotImplementedError("encoder width must be a multiple of 512 with 64-wide heads")
@@ -155,63 +336,27 @@ class TransformerLightningModule(nn.Module):
             self._sites = lrw_xt_sites(self.layers)
             import random
 
-            self._layer_rng = random.Random(self.dropout_seed)
+            self._layer_rng = random.Random(seed)
             self.layer_skip_override: Optional[set[int]] = None     # tests: the set of `encoder.layers.{n}` indices to skip
             self._rot_tab: dict[tuple[int, str], torch.Tensor] = {}
 
-        self._specs = param_specs(config)
-        self._bspecs = buffer_specs(config)
+        self._attach_state(param_specs(config), buffer_specs(config), init_state_dict(config, seed=seed), dropout_seed=seed)
         self._phys = {n: phys_shape(config, n, shp) for n, shp, _ in self._specs}
-        sd = init_state_dict(config, seed=0 if seed is None else seed)
-        for name, shape, kind in self._specs:
-            t = sd[name]
-            if kind == "conv" and len(shape) == 4:
-                t = t.contiguous(memory_format=torch.channels_last)      # physical [Co][kh][kw][Ci]
-            _attach(self, name, t, True)
-        for name, shape, kind in self._bspecs:
-            _attach(self, name, sd[name], False)
         from .augment import CutMix
 
         self.cutmix = CutMix(self.word_labels).eval()          # lightning.py:85-88
-        self._store: Optional[_ParamStore] = None
-        self.register_load_state_dict_post_hook(lambda module, incompatible: module.mark_params_dirty())
-        # (PRE hook: the copies of load_state_dict into the flat buffer must not race with an AdamW range still running on the side stream)
-        self.register_load_state_dict_pre_hook(lambda module, *a, **k: module._side.join())
         self.stem_name, self.trunk_name = "stem3d", "resnet"
         self.stem_act, self.trunk_act = ops.ACT_GELU, ops.ACT_RELU          # lightning.py:52, timm BasicBlock
-        self.use_tr = True          # ds_read_b64_tr_b16 fragments in the weight-gradient kernels
-        self._side = _SideStream()  # second stream for the trunk's weight-gradient launches (._side.enabled = False serialises)
-        self.grad_ready_hook = None  # called as hook(lo, hi) when flat gradient range [lo, hi) is final (DDP buckets)
 
     # ------------------------------------------------------------------------------------------------
     # reference-compatible helpers
     # ------------------------------------------------------------------------------------------------
-    def configure_optimizers(self):
-        """lightning.py:216-223 — returns the two parameter groups; the fused HIP optimiser lives in engine.TrainStep."""
-        do_decay = [p for p in self.parameters() if p.requires_grad and p.ndim >= 2]
-        no_decay = [p for p in self.parameters() if p.requires_grad and p.ndim < 2]
-        return [{"params": do_decay}, {"params": no_decay, "weight_decay": 0.0}]
-
     def training_step(self, batch, idx: int = 0) -> torch.Tensor:
         """lightning.py:194-202: (CutMix) -> forward -> loss_total."""
         self.is_train = True
         if self.config.train.use_cutmix:
             batch = self.cutmix(*batch)
         return self(*batch)["loss_total"]
-
-    def attach_audio_codec(self, codec, sample_in_training: bool = True) -> "TransformerLightningModule":
-        """Registers the frozen wav2vec2 tokeniser (audio_codec.Wav2Vec2Codec) as `self.wav2vec` (lightning.py:58-67) for forward_audios;
-        its buffers join state_dict() under `wav2vec.*`.  forward / training_step still take pre-computed tokens."""
-        from .audio_codec import Wav2Vec2Codec
-
-        if not isinstance(codec, Wav2Vec2Codec):
-            raise TypeError("attach_audio_codec takes a syncvsr_amd.audio_codec.Wav2Vec2Codec")
-        if self.codec != "wav2vec2":
-            raise ValueError(f"this model was built for the {self.codec!r} codec (model.wav2vec.path): the wav2vec2 tokeniser gives 640-way tokens")
-        codec.to(_get(self, self._specs[0][0]).device)
-        self.wav2vec = codec
-        self.codec_sample_in_training = bool(sample_in_training)
-        return self
 
     def forward_audios(self, audios: torch.Tensor) -> torch.Tensor:
         """lightning.py:121-131 for the wav2vec2 codec: float waveforms [B, L] (or [B, 1, L]) -> int64 tokens [B, F, 2] (no padding appended).
@@ -221,40 +366,8 @@ class TransformerLightningModule(nn.Module):
             raise ValueError("forward_audios needs a wav2vec2 tokeniser: call attach_audio_codec(Wav2Vec2Codec...) first")
         if audios.device.type != "cuda":
             raise RuntimeError("audio waveforms must be on the MI355X device: the tokeniser has no CPU path")
-        seed = None
-        if self.training and self.codec_sample_in_training:
-            if self._drop_word is None or self._drop_word.device != audios.device:
-                self._drop_word = torch.tensor([self.dropout_seed], dtype=torch.int32, device=audios.device)
-            seed = self._drop_word
+        seed = self._seed_word(audios.device) if self.training and self.codec_sample_in_training else None
         return codec(audios, sample=seed is not None, seed_word=seed)
-
-    def _advance_dropout(self, dev: torch.device) -> None:
-        if self._drop_word is None or self._drop_word.device != dev:
-            self._drop_word = torch.tensor([self.dropout_seed], dtype=torch.int32, device=dev)
-        ops.word_add(self._drop_word, 1)          # a device op: graph / step-list replays keep drawing fresh masks
-
-    def reseed_dropout(self, seed: int) -> None:
-        self.dropout_seed = int(seed)
-        if self._drop_word is not None:          # in place: a captured graph / recorded step list holds this word's address
-            self._drop_word.fill_(self.dropout_seed)
-        if hasattr(self, "_layer_rng"):          # the layer-drop draws follow the seed too (per-rank / per-run reseeding)
-            self._layer_rng.seed(self.dropout_seed)
-
-    def rng_state(self) -> dict:
-        """Everything random about the next training forward, for bit-exact resume: the dropout seed word (the device counter the
-        masks are hashed from) and the python generator behind layer_dropout.  engine.TrainStep.state_dict stores it."""
-        word = self.dropout_seed if self._drop_word is None else int(self._drop_word.item())
-        out = {"dropout_word": word}
-        if hasattr(self, "_layer_rng"):
-            out["layer_rng"] = self._layer_rng.getstate()
-        return out
-
-    def load_rng_state(self, state: dict) -> None:
-        self.dropout_seed = int(state["dropout_word"])
-        if self._drop_word is not None:
-            self._drop_word.fill_(self.dropout_seed)
-        if "layer_rng" in state and hasattr(self, "_layer_rng"):
-            self._layer_rng.setstate(state["layer_rng"])
 
     def _d(self, site: str, kind: str = "hidden"):
         """(seed word, site id, p) for ops.*(drop=...) or None when dropout is off (eval mode / p = 0)."""
@@ -262,15 +375,6 @@ class TransformerLightningModule(nn.Module):
         if not self.training or p <= 0.0:
             return None
         return (self._drop_word, self._sites[site], p)
-
-    def state_dict(self, *args, **kwargs):
-        self._side.join()             # (a TrainStep may have left the tail of its optimiser step on the side stream)
-        return super().state_dict(*args, **kwargs)
-
-    def mark_params_dirty(self) -> None:
-        """Call after changing parameters outside engine.TrainStep (load_state_dict does it): the bf16 shadows are re-cast."""
-        if self._store is not None:
-            self._store.shadow_fresh = False
 
     @staticmethod
     def _fwd_rank(name: str) -> int:
@@ -313,12 +417,6 @@ class TransformerLightningModule(nn.Module):
             out.append((n, offsets[n][0], offsets[n][2][0], self.dim_p))
         return out
 
-    def store(self) -> "_ParamStore":
-        dev = self.cls_token.device
-        if self._store is None or self._store.device != dev or not self._store.owns(self):
-            self._store = _ParamStore(self, dev)
-        return self._store
-
     # ------------------------------------------------------------------------------------------------
     def forward_videos(self, videos: torch.Tensor) -> torch.Tensor:
         """lightning.py:112-119: [B,1,T,H,W] -> fp32 [B,T,512] (no autograd; use forward() for training)."""
@@ -330,8 +428,7 @@ class TransformerLightningModule(nn.Module):
         return feats.float().view(videos.size(0), -1, 512)
 
     def forward(self, videos: torch.Tensor, audio_tokens: torch.Tensor, labels: torch.Tensor, word_mask: torch.Tensor) -> dict[str, torch.Tensor]:
-        if videos.device.type != "cuda":
-            raise RuntimeError("syncvsr_amd runs on an MI355X HIP device only; there is no CPU fallback (use oracle/ for checking)")
+        _require_device(videos)
         st = self.store()
         T = videos.size(2)
         A = self.audio_alignment
@@ -372,44 +469,8 @@ class TransformerLightningModule(nn.Module):
             wm = word_mask.to(device=videos.device, dtype=torch.float32).contiguous()
         return (videos.float().contiguous(), audio_tokens[:, : T * A].contiguous(), (labels.long() if hard else labels.float()).contiguous(), wm)
 
-    def direct_constants(self, dev) -> None:
-        """The two loss weights d loss_total / d loss_{category, audio} as device scalars (made once, outside any recorded region), times
-        the loss scale of set_loss_scale()."""
-        if getattr(self, "_g_one", None) is None or self._g_one.device != dev:
-            self._g_one = torch.ones((), dtype=torch.float32, device=dev)
-            self._g_lam = torch.full((), self.lambda_audio, dtype=torch.float32, device=dev)
-            if getattr(self, "_loss_scale", 1.0) != 1.0:
-                self.set_loss_scale(self._loss_scale)
-
-    def set_loss_scale(self, scale: float = 1.0) -> None:
-        """Gradient accumulation (engine.TrainStep(accumulate=N) drives this with 1 / N): the seeds of the hand-written backward become
-        d (scale * loss_total) / d loss_{category, audio} — what `(loss_total * scale).backward()` hands the backward, in fp32: scale and
-        fp32(scale) * fp32(lambda_audio).  The device scalars are written IN PLACE and outside any recorded region: a recorded step list
-        reads them by address, so the scale needs no re-recording.  The losses a step returns stay unscaled."""
-        self._loss_scale = float(scale)
-        if getattr(self, "_g_one", None) is not None:
-            one = torch.tensor(self._loss_scale, dtype=torch.float32)
-            self._g_one.copy_(one)
-            self._g_lam.copy_(one * torch.tensor(self.lambda_audio, dtype=torch.float32))
-
-    def loss_seeds(self, dev) -> tuple:
-        """(loss_category seed, loss_audio seed): the device scalars train_step_direct hands its backward."""
-        self.direct_constants(dev)
-        return self._g_one, self._g_lam
-
-    def accumulate_into_grads(self, on: bool = True) -> None:
-        """The "do not zero" switch of the backward.  Off (the default): every backward() zeroes the flat gradient buffer (the storage behind
-        every p.grad) before it writes, so `loss.backward(); optimizer.step()` needs no zero_grad().  On: the following backward() calls ADD
-        into the buffer.  Hand-rolled accumulation over N micro-batches with a foreign optimiser:
-
-            model.accumulate_into_grads(False); (model(*b0)["loss_total"] / N).backward()      # zeroes, then writes
-            model.accumulate_into_grads(True)
-            for b in rest: (model(*b)["loss_total"] / N).backward()                             # adds
-            optimizer.step(); model.accumulate_into_grads(False)
-
-        (optimizer.zero_grad() only drops the p.grad views; the buffer is zeroed by the first backward.)  engine.TrainStep sets this
-        per micro-step and leaves it off."""
-        self._keep_grads = bool(on)
+    def _loss_weights(self) -> tuple[float, ...]:
+        return (1.0, self.lambda_audio)          # d loss_total / d loss_{category, audio}
 
     def grad_store_spans(self, offsets: dict, phys: dict) -> list:
         """[lo, hi) element ranges of the flat gradient buffer whose first writer in a backward pass is a weight-gradient launch with a store
@@ -442,16 +503,10 @@ class TransformerLightningModule(nn.Module):
         """forward + backward of loss_total WITHOUT autograd: the same tape functions `forward()` + `loss_total.backward()` run,
         called directly, with loss_total and the two loss weights formed on the device.  Inputs as prepare_batch returns them.
         Every device operation in here is a library call, so the whole step can be recorded into a native step list."""
-        if videos.device.type != "cuda":
-            raise RuntimeError("syncvsr_amd runs on an MI355X HIP device only; there is no CPU fallback (use oracle/ for checking)")
+        _require_device(videos)
         st = self.store()
         self.direct_constants(videos.device)
-
-        class _Ctx:
-            def mark_non_differentiable(self, *a):
-                pass
-
-        ctx = _Ctx()
+        ctx = _NoAutogradCtx()
         self._metrics_on_side = True          # what only the caller reads (accuracy, loss_total) is computed on the side stream: joined when the backward ends
         try:
             loss_category, loss_audio, acc = _LrwFunction.forward(ctx, self.cls_token, self, st, videos, audio_tokens, labels, True,
@@ -464,7 +519,7 @@ class TransformerLightningModule(nn.Module):
             loss_total = box["t"]
         else:
             loss_total = ops.lincomb2(loss_category, loss_audio, self.lambda_audio)
-        _LrwFunction.backward(ctx, self._g_one, self._g_lam, None)
+        _LrwFunction.backward(ctx, *self._g_consts, None)
         return {"loss_total": loss_total, "loss_category": loss_category, "loss_audio": loss_audio, "accuracy_top1": acc[0],
                 "accuracy_top5": acc[1]}
 
@@ -1269,11 +1324,7 @@ class _LrwFunction(torch.autograd.Function):
         B, T, D, S, A, G, V, C = th["dims"]
         dev = th["h"].device
         use_tr = model.use_tr
-        if not getattr(model, "_keep_grads", False):       # (accumulate_into_grads: the backward adds into the buffer)
-            st.zero_grad()
-        st.rebind_grads()
-        g_cat = (g_cat if g_cat is not None else torch.zeros((), device=dev)).float().contiguous()
-        g_audio = (g_audio if g_audio is not None else torch.zeros((), device=dev)).float().contiguous()
+        g_cat, g_audio = _begin_backward(model, st, dev, g_cat, g_audio)
         NA = A * G * V
         Cp = (C + 63) // 64 * 64
         dlc = torch.empty((B, Cp), dtype=BF16, device=dev)          # (svsr_ce_bwd writes the pad columns C .. Cp - 1 as zeros)

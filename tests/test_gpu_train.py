@@ -394,6 +394,45 @@ def test_checkpoint_resume_lrw_with_dropout():
 
 
 @pytest.mark.gpu
+def test_checkpoint_resume_lrs_with_dropout():
+    """TrainStep.state_dict() carries E2E's dropout seed word too: a resumed LRS run continues the masks where the interrupted run stopped
+    (the word is an integer: exact), and its losses follow the uninterrupted run within the bound of test_checkpoint_resume_lrs."""
+    if not torch.cuda.is_available():
+        pytest.skip("needs an MI355X")
+    from golden_cases import build_lrs_case
+    from syncvsr_amd.engine import TrainStep, lrs_train_config
+    from syncvsr_amd.lrs_model import E2E
+
+    dev = torch.device("cuda:0")
+    args, odim, sd, batch, training, gold = build_lrs_case("lrs_tiny_b3", load_golden=False)
+    args.dropout_rate = 0.1
+    args.transformer_attn_dropout_rate = 0.1
+    tcfg = lrs_train_config(optimizer__lr=5e-4, scheduler__num_warmup_steps=1, scheduler__num_training_steps=10)
+    gb = [t.to(dev) for t in batch]
+
+    def fresh(state):
+        m = E2E(odim, args)
+        m.load_state_dict(state)
+        m.to(dev).train()
+        return m, TrainStep(m, tcfg, use_graph=False)
+
+    m1, ts1 = fresh(sd)
+    ref = [ts1.step(*gb)[0].item() for _ in range(4)]
+    m2, ts2 = fresh(sd)
+    first = [ts2.step(*gb)[0].item() for _ in range(2)]
+    ckpt_model = {k: v.detach().cpu().clone() for k, v in m2.state_dict().items()}
+    ckpt_opt = {k: v.cpu() for k, v in ts2.state_dict().items()}
+    assert int(ckpt_opt["dropout_word"]) == m2.dropout_seed + 2
+    m3, ts3 = fresh(ckpt_model)
+    ts3.load_state_dict({k: v.to(dev) for k, v in ckpt_opt.items()})
+    resumed = [ts3.step(*gb)[0].item() for _ in range(2)]
+    print("uninterrupted", ref, "resumed", first + resumed)
+    assert m3.rng_state()["dropout_word"] == m1.rng_state()["dropout_word"]
+    for a, b in zip(first + resumed, ref):
+        assert abs(a - b) <= 2e-4 * abs(b), (first + resumed, ref)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("case", ["lrs_tiny", "lrs_tiny_b3"])
 def test_lrs_native_step_list_equals_eager_steps(case):
     """The sentence-level model under engine.TrainStep(native=True): decoder / CTC targets are prepared ahead of the recorded region
