@@ -215,6 +215,7 @@ class TrainStep:
         self._key: Optional[tuple] = None              # shape key of the list stepped last (max_shapes > 1)
         self._counts: dict = {}                        # shape key -> [times recorded, times replayed]
         self._rec: Optional[ops.StepRecorder] = None
+        self._cover: tuple = (None, None)              # (data pointer of the gradient buffer, its ops.GradCoverage or None): _coverage
         self.fused_encoder_fallbacks = 0        # times _watch_fused_encoder switched the encoder to the launch chain
         self.host_ms: list[float] = []          # host time of the last steps' enqueue (bench.py reports the median)
         if use_graph and model.layer_drop_p > 0.0:
@@ -294,7 +295,7 @@ class TrainStep:
         where it joins the "tail" group."""
         model = self.model
         rec = ops.active_recorder()
-        st.__dict__.pop("sumsq_tail_done", None)
+        self._forget_early_sumsq(st)
         model._early_sumsq = self.opt_state if self.dp is None and (plan["optimise"] or rec is not None) else None
         if plan["zero"] or rec is not None:
             with ops.window_group("zero"):
@@ -311,8 +312,7 @@ class TrainStep:
             return False
         model = self.model
         st = model.store()
-        model._early_sumsq = None
-        st.__dict__.pop("sumsq_tail_done", None)
+        self._forget_early_sumsq(st)
         model.accumulate_into_grads(False)
         if self.dp is not None:
             self.dp.begin_step()
@@ -321,6 +321,12 @@ class TrainStep:
         self._optimizer(st)
         return True
 
+    def _forget_early_sumsq(self, st) -> None:
+        """Drops the early-sum-of-squares handshake with the model's backward (model._early_sumsq, st.sumsq_tail_done): it is valid only
+        for the step that set it, and a step that aborted between its backward and its optimiser must not leave it behind."""
+        self.model._early_sumsq = None
+        st.sumsq_tail_done = False
+
     def _zero_grads_early(self, st) -> None:
         """The flat gradient buffer's zero-fill — the whole buffer, or with a first-touch map (_coverage) only the ranges no store-mode writer
         covers (LRW: 1.3 of 128 MB; the covered spans' first writers store) — is issued when the step BEGINS, on the side stream (behind the previous step's optimiser, which is the
@@ -328,9 +334,7 @@ class TrainStep:
         runs, long before the backward's main-stream writers): the fill (whole buffer: 128 MB LRW / 1 GB LRS) leaves the main stream, where it sat in front
         of the backward (17 / 140 us).  The backward's own zero_grad() then finds `grad_clean` set and does nothing."""
         model = self.model
-        # (a step that aborted between its backward and its optimiser — an exception in the training loop — must not leave its handshake
-        # behind: the flag is only valid for the step that set it)
-        st.__dict__.pop("sumsq_tail_done", None)
+        self._forget_early_sumsq(st)
         # no collective between the backward and the clip: the model may sum the squares of every gradient but the last while that one is
         # computed (set per step: two TrainSteps may drive one model, each with its own optimiser state)
         model._early_sumsq = self.opt_state if self.dp is None else None
@@ -349,7 +353,7 @@ class TrainStep:
         accumulate = 1 only: a window's micro-steps share one recorded list, whose frozen modes cannot tell the first micro-step from the rest."""
         if not ops.GRAD_STORE:
             return None
-        key, cov = self.__dict__.get("_cover", (None, None))
+        key, cov = self._cover
         if key != st.grad.data_ptr():
             spans = self.model.grad_store_spans(st.offsets, st.phys)
             cov = ops.GradCoverage(st.grad, spans) if spans else None
@@ -363,7 +367,8 @@ class TrainStep:
         HBM-bound pass runs beside the next step's stem / trunk forward.  The model joins the side stream before its encoder runs and
         before state_dict(); the step counter advances behind the last range."""
         model = self.model
-        model._early_sumsq = None        # (a backward outside a step must not write this optimiser's state)
+        early_done = st.sumsq_tail_done  # the backward already summed the squares of everything behind the stem weight
+        self._forget_early_sumsq(st)     # (a backward outside a step must not write this optimiser's state)
         stale = ops.end_grad_coverage()
         if stale:
             raise RuntimeError(f"{len(stale)} gradient ranges planned as first-touch stores had no writer in this step (first: elements "
@@ -372,7 +377,7 @@ class TrainStep:
         if st.sumsq_head:
             # two ranges, always the same two (one association whatever ran early): [head, n) -> partial sums 0..1022 — already summed on the
             # side stream beside the stem's weight gradient when the model could (model._early_sumsq) — and the stem weight -> partial 1023
-            if not st.__dict__.pop("sumsq_tail_done", False):
+            if not early_done:
                 ops.grad_sumsq_parts(st.grad, st.sumsq_head, st.numel - st.sumsq_head, self.opt_state, 0, ops.SUMSQ_PARTS - 1)
             ops.grad_sumsq_parts(st.grad, 0, st.sumsq_head, self.opt_state, ops.SUMSQ_PARTS - 1, 1)
         else:
@@ -594,8 +599,7 @@ class TrainStep:
         except BaseException:
             # an aborted step must not leave its early-sum-of-squares handshake pointing at this optimiser's state (a later stand-alone
             # backward would write partial sums into it and the next optimiser step would trust them)
-            self.model._early_sumsq = None
-            self.model.store().__dict__.pop("sumsq_tail_done", None)
+            self._forget_early_sumsq(self.model.store())
             ops.end_grad_coverage()      # (and the next backward outside a step adds, as it always did)
             if self.window.n > 1:          # the window is abandoned (class docstring): the next step() starts a new one and zero-fills
                 self.window.abort()

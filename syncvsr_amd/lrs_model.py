@@ -21,9 +21,8 @@ import torch
 from . import ops
 from .config import Config
 from .lrs_init import LRS_ODIM, lrs_audio_dims, lrs_buffer_specs, lrs_init_state_dict, lrs_param_specs
-from . import model as _model_mod
-from .model import (BF16, _Holder, _NoAutogradCtx, _ParamStore, _StoreModule, _begin_backward, _bn_stats, _defer_list, _frontend_backward, _frontend_forward,
-                    _get, _ready, _require_device)
+from .model import (BF16, _Holder, _NoAutogradCtx, _ParamStore, _StoreModule, _begin_backward, _bn_stats, _defer_list, _flush_lin_wgrads, _frontend_backward,
+                    _frontend_forward, _get, _lin_wgrad, _ready, _require_device)
 
 LN_EPS = 1e-12          # transformer/layer_norm.py:19
 
@@ -444,30 +443,12 @@ def _lin_bwd(model, st: _ParamStore, name: str, x, dy, rows: int, K: int, N: int
     dy_pitch = dy_pitch or N
     gw = st.grad[st.offsets[f"{name}.weight"][0] :][: N * K]
     gb = st.grad[st.offsets[f"{name}.bias"][0] :][:N] if bias else None          # column sums of dy, fused into the wgrad launch
-    # weight gradients only feed the flat gradient buffer: optionally on the side stream, next to the data-gradient GEMM
-    if "lin_wgrad" not in _model_mod._ABLATE:       # (timing experiments only, see model._ABLATE)
-        group = model.__dict__.get("_wg_group")
-        if group is not None and model.use_tr:      # a decoder layer's weight gradients: collected, one grouped launch per layer (_flush_wg_group)
-            group.append(dict(x=x, dy=dy, dw=gw, db=gb, rows=rows, K=K, N=N, x_pitch=K, dy_pitch=dy_pitch))
-        else:
-            model._side.run(lambda: ops.linear_wgrad(x, dy, gw, rows=rows, K=K, N=N, x_pitch=K, dy_pitch=dy_pitch, use_tr=model.use_tr, db=gb),
-                            x, dy, small=True)
+    # weight gradients only feed the flat gradient buffer: optionally on the side stream, next to the data-gradient GEMM; a decoder layer's
+    # are collected for one grouped launch per layer
+    _lin_wgrad(model, x, dy, gw, gb, rows, K, N, K, dy_pitch)
     if not need_dx:
         return None
     return ops.linear_dgrad(dy, st.t16(tkey or f"{name}.weight"), rows=rows, N=N, K=K, dy_pitch=dy_pitch, addend=addend, out=out, drop=drop)
-
-
-def _flush_wg_group(model) -> None:
-    """The weight gradients a decoder layer's backward collected, as ONE launch over a device table of problems (ops.linear_wgrad_group, the
-    launch the word-level encoder uses): at ~800 target rows each of the layer's eight contractions is a 13-chunk K loop — 22 us of latency
-    apiece as a launch of its own, 48 of them per step on the weight-gradient stream.  (Problems the grouped kernel does not take — the
-    source-attention key / value projection over the 2,560 encoder rows — go out on their own inside that call.)"""
-    group = model.__dict__.get("_wg_group")
-    model._wg_group = None
-    if not group:
-        return
-    keep = [t for q in group for t in (q["x"], q["dy"])]
-    model._side.run(lambda: ops.linear_wgrad_group(group), *keep, small=True)
 
 
 def _ln(st: _ParamStore, x, name: str):
@@ -511,7 +492,7 @@ def _ffn_bwd(model, st, t: dict, dy, p: str, R: int, D: int, U: int, alpha: floa
     """x' = x + alpha * dropout(FFN(LN(x))); dy = grad of x' -> grad of x.  branch: (alpha, drop) of the branch in front (see _ln_bwd)."""
     dys = _branch_grad(dy, alpha, t["do"])
     gs = 1.0 / (1.0 - t["dh"][2]) if t["dh"] is not None else 1.0           # dropped hidden units are the zeros of the saved h
-    if U % 64 == 0 and model.use_tr:
+    if U % 64 == 0:
         # (round 6) relu' / the dropout mask and the bias gradient's partial rows in the epilogue of w_2's data gradient: one launch fewer
         # per feed-forward block in the main stream's chain, two passes over [R, U] fewer
         _lin_bwd(model, st, f"{p}.w_2", t["h"], dys, R, U, D, need_dx=False)
@@ -667,7 +648,6 @@ def _decoder_bwd(model: E2E, st: _ParamStore, tape: dict, tg: LrsTargets, dpred,
     to = tape["dec_out"]
     L, Vp, V = to["L"], to["Vp"], model.odim
     R = B * L
-    model._wg_group = None      # (a backward that aborted inside a layer must not leave its half-filled group: the launches below would join it and be dropped)
     dtn = _lin_bwd(model, st, "decoder.output_layer", to["tn"], dpred, R, D, V, dy_pitch=Vp)
     # (every LayerNorm backward below also writes the gradient of the residual branch that follows it: _ln_bwd's `branch`)
     dx = _ln_bwd(model, st, dtn, to["x"], "decoder.after_norm", to["m"], to["r"],
@@ -696,7 +676,7 @@ def _decoder_bwd(model: E2E, st: _ParamStore, tape: dict, tg: LrsTargets, dpred,
         dt1 = _lin_bwd(model, st, f"{p}.self_attn.linear_q", tsf["tn"], dqkv, R, D, 3 * D, tkey=f"{p}.self_attn.qkv")
         nxt = tape[f"decoder.decoders.{i - 1}"]["ff"]["do"] if i > 0 else tape["dec_embed_drop"]
         dx = _ln_bwd(model, st, dt1, tsf["x"], f"{p}.norm1", tsf["m"], tsf["r"], addend=dx1, branch=(1.0, nxt))
-        _flush_wg_group(model)
+        _flush_lin_wgrads(model)
         _ready(model, st, f"{p}.self_attn.linear_q.weight")
     ops.embed_pos_bwd(tg.ys_in, _branch_grad(dx, 1.0, tape["dec_embed_drop"]), st.g32("decoder.embed.0.weight"), D, math.sqrt(D))
     _ready(model, st, "decoder.embed.0.weight")

@@ -125,13 +125,17 @@ class _StoreModule(nn.Module):
         self._store: Optional[_ParamStore] = None
         self._side = _SideStream()  # second stream for the weight-gradient launches (._side.enabled = False serialises)
         self.grad_ready_hook = None  # called as hook(lo, hi) when flat gradient range [lo, hi) is final (DDP buckets)
-        self.use_tr = True          # ds_read_b64_tr_b16 fragments in the weight-gradient kernels
         # Dropout masks are counter based (csrc/common.h): element i of site s is kept iff hash(seed, s, i) >= p * 2^32; the seed is a
         # device word advanced once per training forward.
         self.dropout_seed = int(dropout_seed)
         self._drop_word: Optional[torch.Tensor] = None
         self._keep_grads = False    # accumulate_into_grads
         self._loss_scale = 1.0      # set_loss_scale
+        # state of one hand-written backward pass (_begin_backward drops what an aborted pass left in the first two)
+        self._wg_group: Optional[list] = None   # linear weight gradients awaiting one grouped launch: a backward sets [], _lin_wgrad appends, _flush_lin_wgrads issues
+        self._deferred: list = []               # postponed parameter-gradient reductions: ops.add_ln_bwd / bias_act_bwd append (_defer_list), _flush_deferred issues
+        self._early_sumsq = None                # engine.TrainStep: its optimiser state when no collective follows the backward; read by _frontend_backward
+        self._metrics_on_side = False           # train_step_direct sets it around its forward; read by _LrwFunction.forward
         self._g_consts: Optional[tuple] = None
         self.register_load_state_dict_post_hook(lambda module, incompatible: module.mark_params_dirty())
         # (PRE hook: the copies of load_state_dict into the flat buffer must not race with an AdamW range still running on the side stream)
@@ -268,7 +272,10 @@ class _StoreModule(nn.Module):
 
 def _begin_backward(model: _StoreModule, st: "_ParamStore", dev: torch.device, *grads) -> tuple:
     """The first lines of a hand-written backward: the zero-fill (unless accumulate_into_grads), the p.grad views, and the incoming
-    gradients as contiguous fp32 scalars (None: zero)."""
+    gradients as contiguous fp32 scalars (None: zero).  What a backward that aborted on a host exception left collected or postponed is
+    dropped, not issued: its closures hold that pass's tensors and would add into this pass's gradients."""
+    model._wg_group = None
+    model._deferred.clear()
     if not model._keep_grads:
         st.zero_grad()
     st.rebind_grads()
@@ -547,6 +554,8 @@ class _ParamStore:
         self.offsets: dict[str, tuple[int, int, tuple[int, ...]]] = {}
         self._side = getattr(model, "_side", None)      # a TrainStep may leave the tail of its optimiser step there: whoever reads or rewrites flat / w16 from the main stream joins it first
         self._vc: dict = {}        # cached views of the flat buffers (p32 / g32 / s16 / t16)
+        self.grad_clean = False         # engine.TrainStep zero-filled `grad` when its step began: set there, consumed by zero_grad
+        self.sumsq_tail_done = False    # the squares behind the stem weight are summed already: set by _frontend_backward, consumed by TrainStep._optimizer
         off = 0
         phys = getattr(model, "_phys", {})
         self.phys: dict[str, tuple[int, ...]] = {n: tuple(phys.get(n, s)) for n, s, _ in specs}
@@ -693,7 +702,7 @@ class _ParamStore:
         ops.transpose_shadows(self.flat, self.w16, self.w16t, self.table, self.n_entries)
 
     def zero_grad(self) -> None:
-        if self.__dict__.get("grad_clean", False):       # engine.TrainStep zeroed the buffer on the side stream when the step began
+        if self.grad_clean:       # engine.TrainStep zeroed the buffer on the side stream when the step began
             self.grad_clean = False
             return
         ops.memset(self.grad, 0)
@@ -770,7 +779,6 @@ def _frontend_forward(model, st: "_ParamStore", tape: dict, videos: torch.Tensor
 
 
 def _frontend_backward(model, st: "_ParamStore", tape: dict, dfeats: torch.Tensor) -> None:
-    use_tr = model.use_tr
     act = model.trunk_act
     dx = ops.avgpool_bwd(dfeats, tape["trunk_out_shape"])
     # ReLU trunk: the launch that produces the gradient of a BatchNorm+ReLU output also masks it and takes the first pass of that
@@ -793,7 +801,7 @@ def _frontend_backward(model, st: "_ParamStore", tape: dict, dfeats: torch.Tenso
             dc2, dres = ops.bn_act_bwd(dx, t2["y"], t2["c"], t2["mean"], t2["rstd"], st.p32(f"{t2['bn']}.weight"), ws2["coef"],
                                        st.g32(f"{t2['bn']}.weight"), st.g32(f"{t2['bn']}.bias"), act, True,
                                        beta=st.p32(f"{t2['bn']}.bias"), res=t2["res"])
-        _conv_wgrad(model, st, f"{prefix}.conv2", t2, dc2, use_tr)
+        _conv_wgrad(model, st, f"{prefix}.conv2", t2, dc2)
         t1 = tape[f"{prefix}.conv1"]
         ws1 = st.bn[t1["bn"]]
         w2t = st.t16(f"{prefix}.conv2.weight").view(planes, 3, 3, planes)
@@ -807,7 +815,7 @@ def _frontend_backward(model, st: "_ParamStore", tape: dict, dfeats: torch.Tenso
             do1 = ops.conv2d_dgrad(dc2, w2t, 3, 1, 1, t2["x"].shape[1:3])
             dc1, _ = ops.bn_act_bwd(do1, t1["y"], t1["c"], t1["mean"], t1["rstd"], st.p32(f"{t1['bn']}.weight"), ws1["coef"],
                                     st.g32(f"{t1['bn']}.weight"), st.g32(f"{t1['bn']}.bias"), act, False, beta=st.p32(f"{t1['bn']}.bias"))
-        _conv_wgrad(model, st, f"{prefix}.conv1", t1, dc1, use_tr)
+        _conv_wgrad(model, st, f"{prefix}.conv1", t1, dc1)
         in_hw = t1["x"].shape[1:3]
         w1t = st.t16(f"{prefix}.conv1.weight").view(inp, 3, 3, planes)
         tp = tape[f"{blocks[bi - 1][0]}.conv2"] if fused and bi > 0 else None       # the block below: its output is this block's input
@@ -819,7 +827,7 @@ def _frontend_backward(model, st: "_ParamStore", tape: dict, dfeats: torch.Tenso
             wsd = st.bn[td["bn"]]
             dcd, _ = ops.bn_act_bwd(dres, None, td["c"], td["mean"], td["rstd"], st.p32(f"{td['bn']}.weight"), wsd["coef"],
                                     st.g32(f"{td['bn']}.weight"), st.g32(f"{td['bn']}.bias"), 0, False)
-            _conv_wgrad(model, st, f"{prefix}.downsample.0", td, dcd, use_tr)
+            _conv_wgrad(model, st, f"{prefix}.downsample.0", td, dcd)
             wdt = st.t16(f"{prefix}.downsample.0.weight").view(inp, 1, 1, planes)
             # the 1x1 branch first (pixels its stride skips are written as zeros), the 3x3 branch adds to it: the launch that completes
             # the block's input gradient is the one with the taps that reach every pixel
@@ -838,7 +846,7 @@ def _frontend_backward(model, st: "_ParamStore", tape: dict, dfeats: torch.Tenso
         rec["stem"] = (dx.clone(), False)
     sc, sb = model.stem_name + ".0", model.stem_name + ".1"
     ws = st.bn[sb]
-    fused = ts.get("xwin") is not None and use_tr and ops.stem_bwd_wgrad_ok(ts["videos"])
+    fused = ts.get("xwin") is not None and ops.stem_bwd_wgrad_ok(ts["videos"])
     dconv = ops.stem_bn_gelu_pool_bwd(dx, ts["amax"], ts["c"], ts["mean"], ts["rstd"], st.p32(f"{sb}.weight"), st.p32(f"{sb}.bias"),
                                       ws["coef"], st.g32(f"{sb}.weight"), st.g32(f"{sb}.bias"), model.stem_act, xwin=ts.get("xwin"),
                                       want_dx=not fused)
@@ -849,7 +857,7 @@ def _frontend_backward(model, st: "_ParamStore", tape: dict, dfeats: torch.Tenso
         # alone it is 223 us against 105 + 134 (928 frames) and the sentence-level step gains 0.2 ms.
         _flush_deferred(model)
         model._side.join()
-        early = getattr(model, "_early_sumsq", None)      # the optimiser's device state, set by engine.TrainStep when no collective follows
+        early = model._early_sumsq      # the optimiser's device state, set by engine.TrainStep when no collective follows
         if early is not None and st.sumsq_head:
             # every gradient but the stem convolution's is final: their sum of squares (the global-norm clip's) runs beside that last pass
             # (part of the optimiser tail: under gradient accumulation a recorded list leaves it out of every micro-step but the last)
@@ -858,7 +866,7 @@ def _frontend_backward(model, st: "_ParamStore", tape: dict, dfeats: torch.Tenso
             st.sumsq_tail_done = True
         ops.stem_bwd_wgrad(ts["videos"], dconv, ts["amax"], ts["c"], ts["mean"], ts["rstd"], ws["coef"], st.g32(f"{sc}.weight"))
     else:
-        ops.stem_conv_wgrad(ts["videos"], dconv, st.g32(f"{sc}.weight"), use_tr)
+        ops.stem_conv_wgrad(ts["videos"], dconv, st.g32(f"{sc}.weight"))
     _flush_deferred(model)
     model._side.join()
     _ready(model, st, None)
@@ -869,49 +877,42 @@ def _frontend_backward(model, st: "_ParamStore", tape: dict, dfeats: torch.Tenso
 _ABLATE: frozenset = frozenset()
 
 
-def _conv_wgrad(model, st: "_ParamStore", conv: str, t: dict, dc: torch.Tensor, use_tr: bool) -> None:
+def _conv_wgrad(model, st: "_ParamStore", conv: str, t: dict, dc: torch.Tensor) -> None:
     if "conv_wgrad" in _ABLATE:
         return
-    model._side.run(lambda: ops.conv2d_wgrad(t["x"], dc, st.g32(f"{conv}.weight"), t["k"], t["stride"], t["pad"], use_tr), dc)
+    model._side.run(lambda: ops.conv2d_wgrad(t["x"], dc, st.g32(f"{conv}.weight"), t["k"], t["stride"], t["pad"]), dc)
 
 
 def _lin_wgrad(model, x, dy, gw, gb, rows: int, K: int, N: int, x_pitch: int, dy_pitch: int) -> None:
-    """Weight (+ bias) gradient of an encoder linear layer, handed to the side stream (a function call, so that the deferred
-    launch sees THIS layer's tensors and not the loop variables of a later one)."""
+    """Weight (+ bias) gradient of a linear layer of either training model, handed to the side stream (a function call, so that the
+    deferred launch sees THIS layer's tensors and not the loop variables of a later one)."""
     if "lin_wgrad" in _ABLATE:
         return
-    group = getattr(model, "_wg_group", None)
-    if group is not None:          # collected: one grouped launch at the end of the encoder's backward (_flush_lin_wgrads)
+    group = model._wg_group
+    if group is not None:          # collected: one grouped launch per flush (_flush_lin_wgrads: a word-level encoder layer, a decoder layer)
         group.append(dict(x=x, dy=dy, dw=gw, db=gb, rows=rows, K=K, N=N, x_pitch=x_pitch, dy_pitch=dy_pitch))
         return
     model._side.run(lambda: ops.linear_wgrad(x, dy, gw, rows=rows, K=K, N=N, x_pitch=x_pitch, dy_pitch=dy_pitch, db=gb), x, dy, small=True)
 
 
 def _flush_lin_wgrads(model) -> None:
-    """The collected linear weight gradients of this backward pass as one launch (ops.linear_wgrad_group), on the side stream when
-    the trunk's weight gradients go there: nothing downstream reads them before the optimiser."""
+    """The linear weight gradients collected so far as ONE launch over a device table of problems (ops.linear_wgrad_group; problems the
+    grouped kernel does not take go out on their own inside that call), on the side stream when weight gradients go there: nothing
+    downstream reads them before the optimiser.  At ~800 rows each contraction is a 13-chunk K loop, 22 us of latency as a launch of its own."""
     group, model._wg_group = model._wg_group, None
     if not group:
         return
     keep = [t for q in group for t in (q["x"], q["dy"])]
-    if model._side.enabled:
-        model._side.run(lambda: ops.linear_wgrad_group(group), *keep)
-    else:
-        ops.linear_wgrad_group(group)
+    model._side.run(lambda: ops.linear_wgrad_group(group), *keep, small=True)
 
 
 def _defer_list(model) -> Optional[list]:
     """The list ops.add_ln_bwd / ops.bias_act_bwd append their postponed reductions to (None: reduce in line)."""
-    if not (model._side.enabled or model._side.enabled_small):
-        return None
-    d = model.__dict__.get("_deferred")
-    if d is None:
-        d = model.__dict__["_deferred"] = []
-    return d
+    return model._deferred if model._side.enabled or model._side.enabled_small else None
 
 
 def _flush_deferred(model) -> None:
-    d = model.__dict__.get("_deferred")
+    d = model._deferred
     if d:
         fns, keep = [f for f, _ in d], [k for _, k in d]
         d.clear()
@@ -1046,7 +1047,7 @@ def _encoder_layers_backward_fused(model: TransformerLightningModule, st: _Param
         gqb = st.grad[st.offsets[f"{p}.attention.self.query.bias"][0]:][: 3 * D]
         _lin_wgrad(model, t["x"], q["dqkv"], gq, gqb, R, D, 3 * D, D, 3 * D)
         _flush_deferred(model)
-        if getattr(model, "_wg_group", None) is None:
+        if model._wg_group is None:
             _ready(model, st, f"{p}.attention.self.query.weight")
         elif i > 0:
             _flush_lin_wgrads(model)
@@ -1058,7 +1059,6 @@ def _encoder_layers_backward_fused(model: TransformerLightningModule, st: _Param
 def _encoder_backward(model: TransformerLightningModule, st: _ParamStore, tape: dict, dh: torch.Tensor, B: int, T: int) -> torch.Tensor:
     D, S, H, I = model.dim, T + 1, model.heads, model.inter
     R = B * S
-    use_tr = model.use_tr
     dx = dh
     # parameter-gradient reductions of the row passes (LayerNorm gamma / beta, the intermediate bias): nothing downstream waits for them, so
     # they leave the chain of dependent launches and run on the side stream, one hand-over per layer (_flush_deferred, from _ready)
@@ -1094,7 +1094,7 @@ def _encoder_backward(model: TransformerLightningModule, st: _ParamStore, tape: 
         _lin_wgrad(model, t["x"], dqkv, gq, gqb, R, D, 3 * D, D, 3 * D)
         dx = ops.linear_dgrad(dqkv, st.t16(f"{p}.qkv"), rows=R, N=3 * D, K=D, dy_pitch=3 * D, addend=ds1)
         _flush_deferred(model)
-        if getattr(model, "_wg_group", None) is None:
+        if model._wg_group is None:
             _ready(model, st, f"{p}.attention.self.query.weight")
         elif i > 0:
             # the weight gradients collected so far as one launch on the side stream NOW: the encoder's backward is a chain of small
@@ -1102,7 +1102,7 @@ def _encoder_backward(model: TransformerLightningModule, st: _ParamStore, tape: 
             _flush_lin_wgrads(model)
             model._wg_group = []
             _ready(model, st, f"{p}.attention.self.query.weight")
-    if getattr(model, "_wg_group", None) is not None:
+    if model._wg_group is not None:
         # the remaining linear weight gradients of the encoder (and the heads) in one launch; their flat-buffer range is final from here
         _flush_lin_wgrads(model)
         _ready(model, st, "encoder.encoder.layer.0.attention.self.query.weight")
@@ -1268,7 +1268,7 @@ class _LrwFunction(torch.autograd.Function):
         lab_prob = None if hard else labels.float().contiguous()
         # (round 6) inside TrainStep the word head (classifier, its loss, the metric — and in the backward its loss gradient and data gradient) is a
         # branch of its own between the two encoder launches, of 1-8 workgroups per launch: it runs on the side stream beside the audio head
-        side_heads = bool(getattr(model, "_metrics_on_side", False) and model._side.enabled and need_grad
+        side_heads = bool(model._metrics_on_side and model._side.enabled and need_grad
                           and model.encoder_type == "huggingface")       # (the heads' weight gradients then follow on the side stream too)
         hb: dict = {}
 
@@ -1299,7 +1299,7 @@ class _LrwFunction(torch.autograd.Function):
             loss_a, lse_a = ops.ce_fwd(logits_a, V, tok, None, B * T * A * G, V, 0.0)
         if side_heads:
             acc = hb["acc"]
-        elif getattr(model, "_metrics_on_side", False) and model._side.enabled:
+        elif model._metrics_on_side and model._side.enabled:
             # (round 6) inside TrainStep the metric is read when the step is over: its two launches leave the main stream's chain (the
             # side stream is joined at the end of the backward)
             box: dict = {}
@@ -1323,7 +1323,6 @@ class _LrwFunction(torch.autograd.Function):
         th = tape["head"]
         B, T, D, S, A, G, V, C = th["dims"]
         dev = th["h"].device
-        use_tr = model.use_tr
         g_cat, g_audio = _begin_backward(model, st, dev, g_cat, g_audio)
         NA = A * G * V
         Cp = (C + 63) // 64 * 64
@@ -1357,8 +1356,7 @@ class _LrwFunction(torch.autograd.Function):
             if grouped:
                 model._wg_group.append(q)
             else:
-                ops.linear_wgrad(q["x"], q["dy"], q["dw"], rows=q["rows"], K=q["K"], N=q["N"], x_pitch=q["x_pitch"], dy_pitch=q["dy_pitch"], seq=q["seq"],
-                                 use_tr=use_tr, db=q["db"])
+                ops.linear_wgrad(q["x"], q["dy"], q["dw"], rows=q["rows"], K=q["K"], N=q["N"], x_pitch=q["x_pitch"], dy_pitch=q["dy_pitch"], seq=q["seq"], db=q["db"])
         ops.linear_dgrad(dla, st.t16("audio_projection.weight"), rows=B * T, N=NA, K=D, dy_pitch=NA, out=dh, seq=(S, 1, T))
         if side_heads:
             model._side.join()

@@ -638,8 +638,8 @@ def conv_plan(mode: int, N: int, H: int, W: int, Co_out: int, k: int, stride: in
     return pl
 
 
-def rows_plan(Nimg: int, P: int, src0: int, dst0: int, Co_out: int, Ci: Optional[int] = None) -> Plan:
-    """Plan of a dense layer over rows grouped in Nimg sequences (svsr_rows_plan); Ci is accepted for the callers' convenience and unused."""
+def rows_plan(Nimg: int, P: int, src0: int, dst0: int, Co_out: int) -> Plan:
+    """Plan of a dense layer over rows grouped in Nimg sequences (svsr_rows_plan)."""
     key = ("rows", Nimg, P, src0, dst0, Co_out)
     pl = _PLAN_CACHE.get(key)
     if pl is None:
@@ -934,7 +934,7 @@ def linear_fwd(x: torch.Tensor, w16: torch.Tensor, bias: Optional[torch.Tensor],
         out = torch.empty((rows, out_pitch), dtype=torch.float32 if out_f32 else BF16, device=x.device)
     pre = torch.empty_like(out) if gelu else None
     if seq is None:
-        plan, geo = rows_plan(rows, 1, 0, 0, N, None if (gelu or out_f32 or out_pitch % 8) else K), dict(Nimg=rows, in_pix=1, out_pix=1)
+        plan, geo = rows_plan(rows, 1, 0, 0, N), dict(Nimg=rows, in_pix=1, out_pix=1)
     else:
         S, s0, n = seq
         plan, geo = rows_plan(rows // n, n, s0, 0, N), dict(Nimg=rows // n, in_pix=S, out_pix=n)
@@ -952,7 +952,7 @@ def linear_dgrad(dy: torch.Tensor, w16t: torch.Tensor, *, rows: int, N: int, K: 
     if seq is None:
         if out is None:
             out = torch.empty((rows, K), dtype=BF16, device=dy.device)
-        plan, geo = rows_plan(rows, 1, 0, 0, K, Np), dict(Nimg=rows, in_pix=1, out_pix=1)
+        plan, geo = rows_plan(rows, 1, 0, 0, K), dict(Nimg=rows, in_pix=1, out_pix=1)
     else:
         S, s0, n = seq
         assert out is not None
@@ -1003,9 +1003,8 @@ def linear_dgrad_relu(dy: torch.Tensor, w16t: torch.Tensor, *, rows: int, N: int
 
 
 def linear_wgrad(x: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor, *, rows: int, K: int, N: int, x_pitch: int, dy_pitch: int,
-                 seq: Optional[tuple[int, int, int]] = None, use_tr: bool = True, db: Optional[torch.Tensor] = None, mode: Optional[int] = None) -> None:
-    """dw fp32 [N][K] += dy[rows, N]^T @ x[rows, K];  db fp32 [N] += column sums of dy (bias gradient), if given.
-    (`use_tr` is accepted for the callers' sake: the generic kernel always builds its fragments with transpose reads.)"""
+                 seq: Optional[tuple[int, int, int]] = None, db: Optional[torch.Tensor] = None, mode: Optional[int] = None) -> None:
+    """dw fp32 [N][K] += dy[rows, N]^T @ x[rows, K];  db fp32 [N] += column sums of dy (bias gradient), if given."""
     if seq is None:
         plan, geo = wgrad_rows_plan(rows, 1, 0, 0, K, N, db is not None), dict(Nimg=rows, in_pix=1, out_pix=1)
     else:
