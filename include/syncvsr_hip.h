@@ -595,10 +595,25 @@ int svsr_tcn_norm_pool_fwd(const void* x, int64_t x_pitch, int B, int T, int C, 
  *
  * svsr_mha_src_step_fwd: source attention of one query row per hypothesis: q bf16 [n] rows of q_pitch (H * 64 read), kv bf16
  * [C * Tmax] rows of kv_pitch = k | v (2 * H * 64 read) projected once per clip; row r attends to rows clip_of[r] * Tmax + [0, tlen[clip]);
- * softmax in fp32 (scores * scale); ctx bf16 [n] rows of ctx_pitch.  One wave per (row, head); it gathers tlen * 256 bytes. */
+ * softmax in fp32 (scores * scale); ctx bf16 [n] rows of ctx_pitch.  One wave per (row, head); it gathers tlen * 256 bytes.
+ *
+ * svsr_ctc_align: CTC forced alignment (Viterbi) of B clips, what `CTC.forced_align_batch` (ctc.py:246-328) computes, one workgroup per
+ * clip.  logp fp32 log-probabilities [B][Tmax][ldp] (ldp >= V; columns >= V and rows >= tlen[b] are never read), tlen int32 [B], labels
+ * int64 [B][Lmax] padded with -1 at the tail (as for svsr_ctc_fwd; anything else in front of the tail is a label).  States
+ * ext = [blank, y1, blank, ..., yL, blank]; d[0][0] = logp[0][blank], d[0][1] = logp[0][y1];
+ * d[t][s] = best(d[t-1][s], d[t-1][s-1], d[t-1][s-2]) + logp[t][ext[s]] with s-2 only for odd s >= 3 with ext[s] != ext[s-2], the
+ * candidates compared in that order with strict > (the first maximum wins), one fp32 add per cell; the end state is the larger of
+ * d[tlen-1][S-2] and d[tlen-1][S-1], S-2 on a tie.  Outputs: frames int32 [B][Tmax] the token of every frame (blank for blank states, -1
+ * for t >= tlen[b]); spans int32 [B][Lmax][2] first and last frame of every label's state (-1, -1 for l >= L_b); score fp32 [B] the d of
+ * the end state.  bp: workspace of B * Tmax * (2 Lmax + 1) bytes (one back-pointer per cell).  A clip without a path — tlen < L + (adjacent
+ * equal labels), tlen <= 0, L = 0, a label outside [0, V) (as the 64-bit value it is) or equal to blank, a best path of -inf — gets score
+ * -inf and frames = spans = -1, and nothing of logp is read through such a label.  No atomics; the result is a pure function of the inputs
+ * and equals the reference's, value for value.  Bounds (SVSR_ERR_ARG): 2 Lmax + 1 <= 2048 and 12 (2 Lmax + 1) + 2 Tmax <= 65536 bytes of
+ * LDS.  A chain of tlen dependent steps per clip: latency, not throughput. */
 int svsr_beam_select_slices(int V, int beam, int max_rows);
 int svsr_beam_select(const float* s0, const float* s1, const float* s2, const float* s3, float w0, float w1, float w2, float w3, int nplanes, int64_t ldv, const float* run, const int* clip_of, const int* row_lo, const int* out_off, int n, int C, int V, int beam, int max_rows, int out_rows, void* cand, int64_t* prev, int64_t* tok, float* total, float* vals, int* clip_out, int* count, hipStream_t stream);
 int svsr_ctc_prefix_score_clips(const float* logp, int ldp, const float* r_prev, const int64_t* last, const int64_t* ids, const int* clip_of, const int* tlen, float* r_new, float* psi, int C, int Tmax, int V, int n, int S, int out_len, int blank, int eos, hipStream_t stream);
+int svsr_ctc_align(const float* logp, int ldp, const int* tlen, const int64_t* labels, int Lmax, int B, int Tmax, int V, int blank, unsigned char* bp, int* frames, int* spans, float* score, hipStream_t stream);
 int svsr_mha_src_step_fwd(const void* q, int64_t q_pitch, const void* kv, int64_t kv_pitch, const int* clip_of, const int* tlen, int C, int Tmax, int n, int H, float scale, void* ctx, int64_t ctx_pitch, hipStream_t stream);
 
 /* ---- native step enqueuer (steplist.hip; host code, launches nothing of its own) -----------------------------------

@@ -3,6 +3,7 @@
 //     sum of the scorers' planes, the running score, and the per-clip top `beam` (the torch statement: lrs_infer.beam_select_reference)
 //   * k_ctc_prefix_score_clips: the CTC prefix recursion of both searches, every hypothesis walking the frames of ITS clip
 //   * k_mha_src_step: source attention of one query row per hypothesis against the keys / values of its clip
+//   * k_ctc_align: CTC forced alignment (Viterbi over the CTC lattice) of a batch of clips, the back end of lrs_align.align_clips
 // No float atomics and no order that depends on arrival anywhere: every output is a pure function of the inputs.
 #include "common.h"
 
@@ -223,6 +224,155 @@ __global__ __launch_bounds__(256) void k_ctc_prefix_score_clips(const float* __r
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// CTC forced alignment: the Viterbi member of the lattice family (k_ctc_lattice sums the paths, this keeps the best one).  What the
+// reference's CTC.forced_align_batch computes with a numpy loop over frames (ctc.py:246-328), for one clip per workgroup:
+//   ext = [blank, y1, blank, ..., yL, blank], S = 2L + 1;   d[0][0] = lp[0][blank], d[0][1] = lp[0][y1], -inf elsewhere
+//   d[t][s] = best(d[t-1][s], d[t-1][s-1], d[t-1][s-2]) + lp[t][ext[s]]      s-2 only for odd s >= 3 with ext[s] != ext[s-2]
+//   end: the larger of d[T-1][S-2] and d[T-1][S-1] (S-2 on a tie), then the back-pointers down to frame 0.
+// The results are EQUAL to the reference's, not close: best() compares in that order with strict > (the first maximum wins, argmax's rule; a
+// missing candidate is the reference's -inf, which strict > never selects, and all -inf selects "stay"), and a cell is ONE fp32 add of the
+// selected candidate and the emission.  States are strided over the 256 threads (up to CA_PER each, in registers: S <= 2048), prev / cur
+// rows in LDS, one barrier per frame, one back-pointer byte (0, 1, 2 states back) per cell in bp [B][Tmax][2 Lmax + 1].  The emissions are
+// a gather of S values per frame: the loads of frame t + 1 are issued before the barrier of frame t.  Then one thread walks the
+// back-pointers and leaves the state of every frame in LDS, and all threads write frames and spans (each word has one writer).
+// This is a chain of T dependent steps per clip — latency, not throughput.
+// The transcript is everything in front of the run of -1 at the tail of labels[b]; a clip with a label outside [0, V) (compared as the
+// int64 it is) or equal to blank, with no label or no frame, or whose best path is -inf (too few frames, emissions at -inf) is
+// infeasible: score -inf, frames and spans -1, and nothing of logp is read through such a label.
+// ---------------------------------------------------------------------------------------------------------------------
+#define CA_THREADS 256
+#define CA_PER 8
+#define CA_MAX_S (CA_THREADS * CA_PER)
+#define CA_MAX_LDS 65536
+
+__device__ __forceinline__ void ctc_align_none(int* fr, int* sp, float* sc, int Tmax, int Lmax) {
+    for (int t = threadIdx.x; t < Tmax; t += CA_THREADS) fr[t] = -1;
+    for (int i = threadIdx.x; i < 2 * Lmax; i += CA_THREADS) sp[i] = -1;
+    if (threadIdx.x == 0) *sc = -INFINITY;
+}
+
+__global__ __launch_bounds__(CA_THREADS) void k_ctc_align(const float* __restrict__ logp, int ldp, const int* __restrict__ tlen,
+                                                          const long* __restrict__ labels, int Lmax, int Tmax, int V, int blank,
+                                                          unsigned char* bp, int* __restrict__ frames, int* __restrict__ spans,
+                                                          float* __restrict__ score) {
+    extern __shared__ float sm[];             // prev[Smax], cur[Smax], ext (int)[Smax], path (u16)[Tmax]
+    __shared__ int s_red[8];
+    __shared__ int s_end;
+    const int Smax = 2 * Lmax + 1;
+    float* prev = sm;
+    float* cur = sm + Smax;
+    int* ext = reinterpret_cast<int*>(sm + 2 * Smax);
+    unsigned short* path = reinterpret_cast<unsigned short*>(sm + 3 * Smax);
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const long* lab = labels + (long)b * Lmax;
+    int* fr = frames + (long)b * Tmax;
+    int* sp = spans + (long)b * Lmax * 2;
+
+    int L = 0, hole = Lmax;                   // labels in front of the -1 tail; the first entry that is no label of this vocabulary
+    for (int l = tid; l < Lmax; l += CA_THREADS) {
+        const long v = lab[l];
+        if (v != -1) L = l + 1;
+        if ((v < 0 || v >= (long)V || v == (long)blank) && l < hole) hole = l;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const int oL = __shfl_xor(L, o, 64), oh = __shfl_xor(hole, o, 64);
+        L = oL > L ? oL : L;
+        hole = oh < hole ? oh : hole;
+    }
+    if ((tid & 63) == 0) { s_red[tid >> 6] = L; s_red[4 + (tid >> 6)] = hole; }
+    __syncthreads();
+    L = max(max(s_red[0], s_red[1]), max(s_red[2], s_red[3]));
+    hole = min(min(s_red[4], s_red[5]), min(s_red[6], s_red[7]));
+    const bool bad = hole < L;                // (a -1 in front of a label included: the padding is the tail only)
+    int T = tlen[b];
+    T = T > Tmax ? Tmax : T;
+    if (bad || L < 1 || T < 1) {              // (the same for every thread of the workgroup)
+        ctc_align_none(fr, sp, score + b, Tmax, Lmax);
+        return;
+    }
+    const int S = 2 * L + 1, nk = (S + CA_THREADS - 1) / CA_THREADS;
+    const float* lpb = logp + (long)b * Tmax * ldp;
+    unsigned char* bpb = bp + (long)b * Tmax * Smax;
+
+    int col[CA_PER];                          // ext of this thread's states, and whether they may be entered from two states back
+    bool skip[CA_PER];
+    float e[CA_PER];                          // their emissions at the frame about to be computed
+#pragma unroll
+    for (int k = 0; k < CA_PER; ++k) {
+        const int s = tid + k * CA_THREADS;
+        col[k] = blank; skip[k] = false; e[k] = 0.f;
+        if (k < nk && s < S) {
+            if (s & 1) {
+                col[k] = (int)lab[s >> 1];
+                skip[k] = s >= 3 && lab[s >> 1] != lab[(s >> 1) - 1];
+            }
+            ext[s] = col[k];
+            prev[s] = s == 0 ? lpb[blank] : (s == 1 ? lpb[col[k]] : -INFINITY);
+            if (T > 1) e[k] = lpb[(long)ldp + col[k]];
+        }
+    }
+    __syncthreads();
+    for (int t = 1; t < T; ++t) {
+        float en[CA_PER];
+#pragma unroll
+        for (int k = 0; k < CA_PER; ++k) {    // the gather of frame t + 1: in flight across this frame's barrier
+            const int s = tid + k * CA_THREADS;
+            en[k] = 0.f;
+            if (k < nk && s < S && t + 1 < T) en[k] = lpb[(long)(t + 1) * ldp + col[k]];
+        }
+#pragma unroll
+        for (int k = 0; k < CA_PER; ++k) {
+            const int s = tid + k * CA_THREADS;
+            if (k < nk && s < S) {
+                float best = prev[s];
+                unsigned char back = 0;
+                if (s >= 1) { const float c = prev[s - 1]; if (c > best) { best = c; back = 1; } }
+                if (skip[k]) { const float c = prev[s - 2]; if (c > best) { best = c; back = 2; } }
+                cur[s] = best + e[k];
+                bpb[(long)t * Smax + s] = back;
+            }
+        }
+        __syncthreads();
+        float* tmp = prev; prev = cur; cur = tmp;
+#pragma unroll
+        for (int k = 0; k < CA_PER; ++k) e[k] = en[k];
+    }
+    if (tid == 0) {
+        int s = prev[S - 1] > prev[S - 2] ? S - 1 : S - 2;
+        const float sc = prev[s];
+        const bool ok = sc > -INFINITY;      // (false for NaN too)
+        score[b] = ok ? sc : -INFINITY;
+        s_end = ok ? s : -1;
+        if (ok) {
+            for (int t = T - 1; t >= 1; --t) {
+                path[t] = (unsigned short)s;
+                s -= bpb[(long)t * Smax + s];
+            }
+            path[0] = (unsigned short)s;
+        }
+    }
+    __syncthreads();
+    if (s_end < 0) {
+        ctc_align_none(fr, sp, score + b, Tmax, Lmax);
+        return;
+    }
+    for (int t = tid; t < Tmax; t += CA_THREADS) {
+        int tok = -1;
+        if (t < T) {
+            const int st = path[t];
+            tok = ext[st];
+            if (st & 1) {                     // every label state is visited: each of its two words has exactly one writer
+                if (t == 0 || path[t - 1] != st) sp[st - 1] = t;          // spans[l][0], l = st >> 1
+                if (t == T - 1 || path[t + 1] != st) sp[st] = t;           // spans[l][1]
+            }
+        }
+        fr[t] = tok;
+    }
+    for (int i = 2 * L + tid; i < 2 * Lmax; i += CA_THREADS) sp[i] = -1;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Source attention of a beam step: one wave per (hypothesis r, head h).  The query is row r of q; the keys / values are rows
 // clip_of[r] * Tmax + [0, tlen[clip]) of kv (k | v per row, projected once per clip and layer).  Structure of k_mha_table (lrs_lm.hip):
 // keys in chunks of 64, lane l owns key c * 64 + l for the scores, online softmax in fp32, then lane l owns channel l of the weighted
@@ -353,6 +503,20 @@ int svsr_ctc_prefix_score(const float* logp, int ldp, const float* r_prev, const
     if (T < 1 || V < 2 || n < 1 || S < 1 || (ids == nullptr && S != V) || ldp < V || out_len < 0 || blank < 0 || blank >= V || eos < 0 || eos >= V)
         return SVSR_ERR_ARG;
     return ctc_prefix_launch(logp, ldp, r_prev, last, ids, nullptr, nullptr, r_new, psi, 1, T, V, n, S, out_len, blank, eos, stream);
+}
+
+// one workgroup per clip; dynamic LDS: prev | cur | ext rows of 2 Lmax + 1 words and the state of every frame (16 bits)
+int svsr_ctc_align(const float* logp, int ldp, const int* tlen, const int64_t* labels, int Lmax, int B, int Tmax, int V, int blank, unsigned char* bp,
+                   int* frames, int* spans, float* score, hipStream_t stream) {
+    if (B < 1 || Tmax < 1 || Lmax < 1 || V < 2 || ldp < V || blank < 0 || blank >= V || logp == nullptr || tlen == nullptr || labels == nullptr ||
+        bp == nullptr || frames == nullptr || spans == nullptr || score == nullptr)
+        return SVSR_ERR_ARG;
+    if (2L * Lmax + 1 > CA_MAX_S) return SVSR_ERR_ARG;                          // CA_PER states per thread
+    const size_t lds = (size_t)3 * (2 * Lmax + 1) * sizeof(float) + (((size_t)Tmax * 2 + 3) & ~(size_t)3);
+    if (lds > CA_MAX_LDS) return SVSR_ERR_ARG;
+    hipLaunchKernelGGL(k_ctc_align, dim3(B), dim3(CA_THREADS), lds, stream, logp, ldp, tlen, (const long*)labels, Lmax, Tmax, V, blank, bp, frames, spans,
+                       score);
+    return svsr_check_launch();
 }
 
 int svsr_mha_src_step_fwd(const void* q, int64_t q_pitch, const void* kv, int64_t kv_pitch, const int* clip_of, const int* tlen, int C, int Tmax, int n,

@@ -109,7 +109,7 @@ class _DecoderFacade(_Holder):
 
 
 class _CtcFacade(_Holder):
-    """`E2E.ctc` inference helpers (ctc.py:154-181) on hs_pad [B, T, adim]."""
+    """`E2E.ctc` inference helpers (ctc.py:154-181) on hs_pad [B, T, adim], and forced alignment (ctc.py:181-328)."""
 
     def log_softmax(self, hs_pad: torch.Tensor) -> torch.Tensor:
         from .lrs_infer import CTCPrefixScorer
@@ -122,6 +122,45 @@ class _CtcFacade(_Holder):
 
     def argmax(self, hs_pad: torch.Tensor) -> torch.Tensor:
         return self.log_softmax(hs_pad).argmax(dim=-1)
+
+    def forced_align_batch(self, hs_pad: torch.Tensor, ys_pad: torch.Tensor, ilens, blank_id: int = 0) -> list:
+        """`CTC.forced_align_batch` (ctc.py:246-328): hs_pad [Tmax, B, odim] ACTIVATIONS (the reference applies log_softmax to them directly,
+        its ctc_lo call is commented out, ctc.py:267-269), ys_pad int64 [B, Lmax] padded with ignore_id, ilens [B] -> a list of B numpy int64
+        arrays, the token of each of the ilens[b] frames on the best CTC path (svsr_ctc_align).  Where the reference returns a junk path —
+        a clip with fewer frames than its transcript needs, an empty transcript, an id outside [0, odim) or equal to blank_id, an
+        ignore_id in front of a live token, ilens outside [1, Tmax] — this raises ValueError before anything is launched."""
+        from .lrs_align import align_logp, check_targets
+
+        m = self._owner()
+        if hs_pad.dim() != 3 or hs_pad.size(2) != m.odim:
+            raise ValueError(f"hs_pad must be [Tmax, B, {m.odim}] activations, got {tuple(hs_pad.shape)}")
+        Tmax, B = hs_pad.shape[:2]
+        labels, lens = check_targets(ys_pad, ilens, B, Tmax, m.odim, blank_id, m.ignore_id)
+        _require_device(hs_pad)
+        logp = torch.log_softmax(hs_pad.detach().float(), dim=-1).transpose(0, 1).contiguous()
+        frames, _, _ = align_logp(logp, lens, labels, blank_id)
+        host = frames.cpu().numpy()
+        return [host[b, : lens[b]].astype("int64") for b in range(B)]
+
+    def forced_align(self, h: torch.Tensor, y, blank_id: int = 0) -> list:
+        """`CTC.forced_align` (ctc.py:181-244) as what it is meant to be: h [T, adim] or [1, T, adim] encoder output, y the ids -> the token
+        of each frame, a list of T ints.  It is `forced_align_batch` on the one clip after ctc_lo.  (The reference's own loop reads
+        logdelta[t-1, s-1] with s-1 = -1 for state 0, which numpy takes as the LAST state: most of its outputs do not spell y.  INTEGRATION.md.)"""
+        from .lrs_align import align_logp, check_targets
+        from .lrs_infer import CTCPrefixScorer
+
+        m = self._owner()
+        if h.dim() == 3 and h.size(0) == 1:
+            h = h[0]
+        if h.dim() != 2 or h.size(1) != m.adim:
+            raise ValueError(f"h must be [T, {m.adim}] or [1, T, {m.adim}], got {tuple(h.shape)}")
+        T = h.size(0)
+        ys = torch.as_tensor(y, dtype=torch.int64).reshape(1, -1)
+        labels, lens = check_targets(ys, [T], 1, T, m.odim, blank_id, m.ignore_id)
+        _require_device(h)
+        logp = CTCPrefixScorer(m, m.eos).ctc_log_softmax(h.detach())
+        frames, _, _ = align_logp(logp.unsqueeze(0), lens, labels, blank_id)
+        return [int(v) for v in frames[0].tolist()]
 
 
 class E2E(_StoreModule):

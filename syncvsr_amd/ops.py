@@ -1872,6 +1872,29 @@ def ctc_prefix_score_clips(logp: torch.Tensor, tlen: torch.Tensor, r_prev: torch
     return r_new, psi
 
 
+CTC_ALIGN_MAX_LABELS = 1023      # 2 L + 1 states <= 2048 (csrc/lrs_search.hip CA_MAX_S)
+
+
+def ctc_align(logp: torch.Tensor, tlen: torch.Tensor, labels: torch.Tensor, blank: int = 0,
+              V: Optional[int] = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """logp fp32 [B, Tmax, ldp] log-probabilities (V <= ldp: the first V columns are the vocabulary, default all), tlen int32 [B], labels
+    int64 [B, Lmax] padded with -1 at the tail -> (frames int32 [B, Tmax], spans int32 [B, Lmax, 2], score fp32 [B]): the best CTC path of
+    every clip.  A clip without a path has score -inf and -1 everywhere.  See svsr_ctc_align."""
+    B, Tmax, ldp = logp.shape
+    V = ldp if V is None else int(V)
+    assert logp.dtype == torch.float32 and logp.is_contiguous() and tlen.dtype == torch.int32 and tlen.is_contiguous() and tlen.numel() == B
+    assert labels.dtype == torch.int64 and labels.is_contiguous() and labels.dim() == 2 and labels.shape[0] == B
+    Lmax = labels.shape[1]
+    dev = logp.device
+    bp = torch.empty((B, Tmax, 2 * Lmax + 1), dtype=torch.uint8, device=dev)
+    frames = torch.empty((B, Tmax), dtype=torch.int32, device=dev)
+    spans = torch.empty((B, Lmax, 2), dtype=torch.int32, device=dev)
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    _call("svsr_ctc_align", _p(logp), ldp, _p(tlen), _p(labels), Lmax, B, Tmax, V, int(blank), _p(bp), _p(frames), _p(spans), _p(score), _stream(),
+          label="k_ctc_align")
+    return frames, spans, score
+
+
 def mha_src_step_fwd(q: torch.Tensor, kv: torch.Tensor, clip_of: torch.Tensor, tlen: torch.Tensor, *, Tmax: int, H: int,
                      scale: float = 0.125, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """q bf16 [n, >= H * 64], kv bf16 [C * Tmax, >= 2 * H * 64] (k | v per row), clip_of int32 [n], tlen int32 [C] -> ctx bf16 [n, H * 64]: row r
