@@ -609,11 +609,34 @@ int svsr_tcn_norm_pool_fwd(const void* x, int64_t x_pitch, int B, int T, int C, 
  * equal labels), tlen <= 0, L = 0, a label outside [0, V) (as the 64-bit value it is) or equal to blank, a best path of -inf — gets score
  * -inf and frames = spans = -1, and nothing of logp is read through such a label.  No atomics; the result is a pure function of the inputs
  * and equals the reference's, value for value.  Bounds (SVSR_ERR_ARG): 2 Lmax + 1 <= 2048 and 12 (2 Lmax + 1) + 2 Tmax <= 65536 bytes of
- * LDS.  A chain of tlen dependent steps per clip: latency, not throughput. */
+ * LDS.  A chain of tlen dependent steps per clip: latency, not throughput.
+ *
+ * svsr_ctc_frame_best + svsr_ctc_collapse: CTC best-path (greedy) decoding of C clips, what `CTC.argmax` (ctc.py:172) and the host
+ * `groupby` that follows it compute, from the LOGITS of ctc_lo: no [C][Tmax][V] log-softmax is ever stored.
+ * svsr_ctc_frame_best: logits fp32 [C * Tmax][ldp] (ldp >= V; what svsr_linear_fwd writes with an fp32 output of that pitch), tlen int32
+ * [C].  Row (c, t) with t < tlen[c]: best int32 = the column of the largest logit, the lowest column on a tie, the first NaN if there is
+ * one (torch.argmax's rule); best_logp fp32 = logits[best] - logsumexp(logits[0 .. V)), the logsumexp in fp32 around the row maximum (NaN
+ * for a row that holds a NaN or nothing but -inf).  Rows t >= tlen[c] get best = -1 and best_logp = 0.  Columns >= V and rows t >= tlen[c]
+ * are never read.  One wave per row, one pass carrying (max, column, rescaled sum), 16-byte loads where the rows are 16-byte aligned (logits
+ * aligned and ldp % 4 == 0; single loads otherwise), a fixed butterfly over the 64 lanes: no atomics, a pure function of the inputs.
+ * HBM-bound by construction: it reads rows * V * 4 bytes once and writes 8 bytes per row, about 1.25 exp per element and no contraction.
+ * Bounds (SVSR_ERR_ARG): V >= 1, ldp >= V, C >= 1, Tmax >= 1, C * Tmax < 2^31.
+ * svsr_ctc_collapse: best / best_logp [C][Tmax] as written above (any int32 winners), blank any id.  A run is a maximal stretch of equal
+ * best over frames 0 .. tlen[c] - 1; every run whose value is not blank is one token, in frame order: tokens int64 [C][Lcap] its id, spans
+ * int32 [C][Lcap][2] its first and last frame, token_logp fp32 [C][Lcap] the fp32 sum of best_logp over the run in frame order divided by
+ * the run length (one correctly rounded division).  ntok int32 [C] = the number of tokens (0: an all-blank clip is an empty transcript);
+ * rows l >= ntok[c] hold tokens -1, spans (-1, -1), token_logp 0.  score fp32 [C] = the fp32 sum of best_logp over the clip's frames in
+ * frame order, the log-probability of the best path.  tlen[c] <= 0: ntok = 0, score = 0.  Lcap is the row capacity of the three token
+ * outputs (Tmax always suffices); no row l >= Lcap is written, ntok counts them all the same.  One workgroup per clip, token positions
+ * from a flag per frame and a workgroup prefix sum: no atomics, nothing depends on arrival.  Bounds (SVSR_ERR_ARG): Tmax <= 4096 (the
+ * clip's winners and log-probabilities live in 8 Tmax bytes of LDS), Lcap >= 1, C >= 1.  A few short dependent chains per clip: latency,
+ * not throughput. */
 int svsr_beam_select_slices(int V, int beam, int max_rows);
 int svsr_beam_select(const float* s0, const float* s1, const float* s2, const float* s3, float w0, float w1, float w2, float w3, int nplanes, int64_t ldv, const float* run, const int* clip_of, const int* row_lo, const int* out_off, int n, int C, int V, int beam, int max_rows, int out_rows, void* cand, int64_t* prev, int64_t* tok, float* total, float* vals, int* clip_out, int* count, hipStream_t stream);
 int svsr_ctc_prefix_score_clips(const float* logp, int ldp, const float* r_prev, const int64_t* last, const int64_t* ids, const int* clip_of, const int* tlen, float* r_new, float* psi, int C, int Tmax, int V, int n, int S, int out_len, int blank, int eos, hipStream_t stream);
 int svsr_ctc_align(const float* logp, int ldp, const int* tlen, const int64_t* labels, int Lmax, int B, int Tmax, int V, int blank, unsigned char* bp, int* frames, int* spans, float* score, hipStream_t stream);
+int svsr_ctc_frame_best(const float* logits, int64_t ldp, const int* tlen, int C, int Tmax, int V, int* best, float* best_logp, hipStream_t stream);
+int svsr_ctc_collapse(const int* best, const float* best_logp, const int* tlen, int C, int Tmax, int Lcap, int blank, int64_t* tokens, int* spans, float* token_logp, int* ntok, float* score, hipStream_t stream);
 int svsr_mha_src_step_fwd(const void* q, int64_t q_pitch, const void* kv, int64_t kv_pitch, const int* clip_of, const int* tlen, int C, int Tmax, int n, int H, float scale, void* ctx, int64_t ctx_pitch, hipStream_t stream);
 
 /* ---- native step enqueuer (steplist.hip; host code, launches nothing of its own) -----------------------------------

@@ -4,6 +4,7 @@
 //   * k_ctc_prefix_score_clips: the CTC prefix recursion of both searches, every hypothesis walking the frames of ITS clip
 //   * k_mha_src_step: source attention of one query row per hypothesis against the keys / values of its clip
 //   * k_ctc_align: CTC forced alignment (Viterbi over the CTC lattice) of a batch of clips, the back end of lrs_align.align_clips
+//   * k_ctc_frame_best / k_ctc_collapse: CTC best-path (greedy) decoding of a batch of clips, the back end of lrs_align.greedy_clips
 // No float atomics and no order that depends on arrival anywhere: every output is a pure function of the inputs.
 #include "common.h"
 
@@ -373,6 +374,169 @@ __global__ __launch_bounds__(CA_THREADS) void k_ctc_align(const float* __restric
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// CTC best-path (greedy) decoding, two launches.  What `CTC.argmax` (ctc.py:172) and the host `groupby` behind it compute, without the
+// [C][Tmax][V] log-softmax in between.
+// k_ctc_frame_best: one wave per row (c, t) of the fp32 LOGITS, one pass.  A lane walks its columns in rising order and carries
+//   m   the largest value so far (strict >: the first maximum wins; NaN never wins here)     idx   its column
+//   s   sum of exp(x - m) over what it has seen, rescaled whenever m rises                   nan   its first NaN column
+// 16-byte loads over the whole groups of four columns below V when the rows are 16-byte aligned (four loads in flight per lane), single
+// loads for the V % 4 columns behind them and for unaligned rows: no column >= V and no row t >= tlen[c] is ever read.  The 64 triples
+// are merged by a fixed xor butterfly — the larger m, on equal m the lower column, s rescaled to the common m — so every lane ends with
+// the same bits whatever the launch, and nothing is accumulated through memory.  best = the first NaN's column if the row has one
+// (torch.argmax's rule), else idx; best_logp = x[best] - logsumexp(x) = -log(s) (NaN for a row with a NaN or of -inf only).
+// HBM-bound by construction: rows * V * 4 bytes read once, 8 written per row.
+// ---------------------------------------------------------------------------------------------------------------------
+#define CG_NONE 0x7fffffff
+
+struct FrameBest {
+    float m, s;
+    int idx, nan;
+};
+
+__device__ __forceinline__ void fb_take4(FrameBest& a, const f32x4 x, int j) {
+    float mc = a.m;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (x[k] > mc) { mc = x[k]; a.idx = j + k; }
+        if (x[k] != x[k]) a.nan = min(a.nan, j + k);
+    }
+    if (mc > -INFINITY)                                    // (all -inf so far: s stays 0 and exp(-inf - -inf) is never formed)
+        a.s = a.s * __expf(a.m - mc) + ((__expf(x[0] - mc) + __expf(x[1] - mc)) + (__expf(x[2] - mc) + __expf(x[3] - mc)));
+    a.m = mc;
+}
+
+__device__ __forceinline__ void fb_take1(FrameBest& a, float x, int j) {
+    float mc = a.m;
+    if (x > mc) { mc = x; a.idx = j; }
+    if (x != x) a.nan = min(a.nan, j);
+    if (mc > -INFINITY) a.s = a.s * __expf(a.m - mc) + __expf(x - mc);
+    a.m = mc;
+}
+
+__device__ __forceinline__ void fb_merge(float& m, float& sum, int& idx, int& nan, float bm, float bs, int bi, int bn) {
+    const bool tb = bm > m || (bm == m && bi < idx);
+    const float nm = tb ? bm : m;
+    sum = nm > -INFINITY ? sum * __expf(m - nm) + bs * __expf(bm - nm) : 0.f;
+    m = nm;
+    idx = tb ? bi : idx;
+    nan = min(nan, bn);
+}
+
+__global__ __launch_bounds__(64) void k_ctc_frame_best(const float* __restrict__ logits, long ldp, const int* __restrict__ tlen, int Tmax, int V,
+                                                       int vec, int* __restrict__ best, float* __restrict__ best_logp) {
+    const int row = (int)blockIdx.x, lane = threadIdx.x;  // (rows < 2^31: the launcher checks)
+    const int c = row / Tmax, t = row - c * Tmax;
+    if (t >= tlen[c]) {                                    // (the same for the whole wave) padding: nothing of the row is read
+        if (lane == 0) { best[row] = -1; best_logp[row] = 0.f; }
+        return;
+    }
+    const float* x = logits + (long)row * ldp;
+    FrameBest a = {-INFINITY, 0.f, CG_NONE, CG_NONE};
+    int done = 0;                                          // columns [0, done) go through 16-byte loads
+    if (vec) {
+        const f32x4* xv = reinterpret_cast<const f32x4*>(x);
+        const int nq = V >> 2;
+        done = nq << 2;
+        int q = lane;
+        for (; q + 192 < nq; q += 256) {
+            const f32x4 v0 = xv[q], v1 = xv[q + 64], v2 = xv[q + 128], v3 = xv[q + 192];
+            fb_take4(a, v0, q * 4);
+            fb_take4(a, v1, (q + 64) * 4);
+            fb_take4(a, v2, (q + 128) * 4);
+            fb_take4(a, v3, (q + 192) * 4);
+        }
+        for (; q < nq; q += 64) fb_take4(a, xv[q], q * 4);
+    }
+    for (int j = done + lane; j < V; j += 64) fb_take1(a, x[j], j);
+    float m = a.m, sum = a.s;
+    int idx = a.idx, nan = a.nan;
+#pragma unroll
+    for (int o = 1; o <= 32; o <<= 1)
+        fb_merge(m, sum, idx, nan, __shfl_xor(m, o, 64), __shfl_xor(sum, o, 64), __shfl_xor(idx, o, 64), __shfl_xor(nan, o, 64));
+    if (lane == 0) {
+        const bool isnan_row = nan != CG_NONE;
+        best[row] = isnan_row ? nan : (idx == CG_NONE ? 0 : idx);             // (every column -inf: all equal, the first wins)
+        best_logp[row] = (isnan_row || !(m > -INFINITY)) ? __builtin_nanf("") : -logf(sum);     // (a row of -inf has no softmax: NaN, as torch)
+    }
+}
+
+// k_ctc_collapse: one workgroup per clip.  The winners and their log-probabilities of the clip's T = tlen[c] frames go to LDS; frame t starts
+// a token when best[t] != blank and (t == 0 or best[t] != best[t-1]).  A thread owns a stretch of consecutive frames; the token number of
+// a start is the exclusive prefix sum of the flags (per-thread counts, a wave scan, four wave totals through LDS: positions follow from
+// the frames alone, never from arrival).  The thread that owns a start walks its run to the end: the fp32 sum of best_logp in frame order
+// over the run length (a correctly rounded division) is token_logp.  Thread 0 adds up the clip's score, also in frame order.  Rows behind
+// ntok are filled: tokens -1, spans (-1, -1), token_logp 0.  Nothing is written at or behind row Lcap.  Short dependent chains on a few
+// KB: latency, not throughput.
+// dynamic LDS: winners (int)[Tmax] | log-probabilities [Tmax] | wave totals (int)[4]
+#define CG_THREADS 256
+#define CG_MAX_T 4096
+
+__global__ __launch_bounds__(CG_THREADS) void k_ctc_collapse(const int* __restrict__ best, const float* __restrict__ best_logp,
+                                                             const int* __restrict__ tlen, int Tmax, int Lcap, int blank, long* __restrict__ tokens,
+                                                             int* __restrict__ spans, float* __restrict__ token_logp, int* __restrict__ ntok,
+                                                             float* __restrict__ score) {
+    extern __shared__ __attribute__((aligned(16))) int cg_sm[];
+    int* sb = cg_sm;
+    float* sl = reinterpret_cast<float*>(cg_sm + Tmax);
+    int* wtot = cg_sm + 2 * Tmax;
+    const int c = blockIdx.x, tid = threadIdx.x;
+    int T = tlen[c];
+    T = T > Tmax ? Tmax : (T < 0 ? 0 : T);
+    long* tk = tokens + (long)c * Lcap;
+    int* sp = spans + (long)c * Lcap * 2;
+    float* tl = token_logp + (long)c * Lcap;
+    for (int t = tid; t < T; t += CG_THREADS) {
+        sb[t] = best[(long)c * Tmax + t];
+        sl[t] = best_logp[(long)c * Tmax + t];
+    }
+    __syncthreads();
+    const int per = (T + CG_THREADS - 1) / CG_THREADS;
+    const int t0 = min(tid * per, T), t1 = min(t0 + per, T);
+    int cnt = 0;
+    for (int t = t0; t < t1; ++t) cnt += (sb[t] != blank && (t == 0 || sb[t] != sb[t - 1])) ? 1 : 0;
+    int inc = cnt;                                         // inclusive scan of the counts within the wave
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int up = __shfl_up(inc, o, 64);
+        if ((tid & 63) >= o) inc += up;
+    }
+    if ((tid & 63) == 63) wtot[tid >> 6] = inc;
+    __syncthreads();
+    int l = inc - cnt, total = 0;
+#pragma unroll
+    for (int w = 0; w < CG_THREADS / 64; ++w) {
+        if (w < (tid >> 6)) l += wtot[w];
+        total += wtot[w];
+    }
+    for (int t = t0; t < t1; ++t) {
+        const int v = sb[t];
+        if (v == blank || (t > 0 && v == sb[t - 1])) continue;
+        float sum = sl[t];
+        int e = t;
+        while (e + 1 < T && sb[e + 1] == v) { ++e; sum += sl[e]; }
+        if (l < Lcap) {
+            tk[l] = (long)v;
+            sp[2 * l] = t;
+            sp[2 * l + 1] = e;
+            tl[l] = __fdiv_rn(sum, (float)(e - t + 1));
+        }
+        ++l;
+    }
+    for (int i = total + tid; i < Lcap; i += CG_THREADS) {
+        tk[i] = -1;
+        sp[2 * i] = -1;
+        sp[2 * i + 1] = -1;
+        tl[i] = 0.f;
+    }
+    if (tid == 0) {
+        float sc = 0.f;
+        for (int t = 0; t < T; ++t) sc += sl[t];
+        score[c] = sc;
+        ntok[c] = total;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Source attention of a beam step: one wave per (hypothesis r, head h).  The query is row r of q; the keys / values are rows
 // clip_of[r] * Tmax + [0, tlen[clip]) of kv (k | v per row, projected once per clip and layer).  Structure of k_mha_table (lrs_lm.hip):
 // keys in chunks of 64, lane l owns key c * 64 + l for the scores, online softmax in fp32, then lane l owns channel l of the weighted
@@ -516,6 +680,29 @@ int svsr_ctc_align(const float* logp, int ldp, const int* tlen, const int64_t* l
     if (lds > CA_MAX_LDS) return SVSR_ERR_ARG;
     hipLaunchKernelGGL(k_ctc_align, dim3(B), dim3(CA_THREADS), lds, stream, logp, ldp, tlen, (const long*)labels, Lmax, Tmax, V, blank, bp, frames, spans,
                        score);
+    return svsr_check_launch();
+}
+
+// one wave per row; 16-byte loads when every row starts on a 16-byte boundary
+int svsr_ctc_frame_best(const float* logits, int64_t ldp, const int* tlen, int C, int Tmax, int V, int* best, float* best_logp, hipStream_t stream) {
+    if (C < 1 || Tmax < 1 || V < 1 || ldp < (int64_t)V || logits == nullptr || tlen == nullptr || best == nullptr || best_logp == nullptr)
+        return SVSR_ERR_ARG;
+    const long rows = (long)C * Tmax;
+    if (rows > 0x7fffffffL) return SVSR_ERR_ARG;
+    const int vec = ((uintptr_t)logits & 15) == 0 && ldp % 4 == 0;
+    hipLaunchKernelGGL(k_ctc_frame_best, dim3((unsigned)rows), dim3(64), 0, stream, logits, (long)ldp, tlen, Tmax, V, vec, best, best_logp);
+    return svsr_check_launch();
+}
+
+// one workgroup per clip; dynamic LDS: the clip's winners and log-probabilities, 8 Tmax + 16 bytes
+int svsr_ctc_collapse(const int* best, const float* best_logp, const int* tlen, int C, int Tmax, int Lcap, int blank, int64_t* tokens, int* spans,
+                      float* token_logp, int* ntok, float* score, hipStream_t stream) {
+    if (C < 1 || Tmax < 1 || Tmax > CG_MAX_T || Lcap < 1 || best == nullptr || best_logp == nullptr || tlen == nullptr || tokens == nullptr ||
+        spans == nullptr || token_logp == nullptr || ntok == nullptr || score == nullptr)
+        return SVSR_ERR_ARG;
+    const size_t lds = (size_t)2 * Tmax * sizeof(float) + 4 * sizeof(int);
+    hipLaunchKernelGGL(k_ctc_collapse, dim3(C), dim3(CG_THREADS), lds, stream, best, best_logp, tlen, Tmax, Lcap, blank, (long*)tokens, spans,
+                       token_logp, ntok, score);
     return svsr_check_launch();
 }
 

@@ -301,15 +301,18 @@ class CTCPrefixScorer:
         self.model, self.eos = model, int(eos)
         self.logp: Optional[torch.Tensor] = None
 
-    def ctc_log_softmax(self, x: torch.Tensor) -> torch.Tensor:
-        """`CTC.log_softmax` (ctc.py:163-170): x [T, adim] -> fp32 [T, odim]."""
+    def ctc_logits(self, x: torch.Tensor) -> torch.Tensor:
+        """ctc_lo alone: x [T, adim] -> fp32 LOGITS [T, odim rounded up to 64] (the first odim columns are the units; the rest is padding)."""
         m = self.model
         st = _fresh_store(m)
         T = x.size(0)
         with torch.no_grad():
-            logits = ops.linear_fwd(x.to(BF16).contiguous(), st.s16("ctc.ctc_lo.weight"), st.p32("ctc.ctc_lo.bias"), rows=T, K=m.adim, N=m.odim,
-                                    x_pitch=m.adim, out_f32=True, out_pitch=(m.odim + 63) // 64 * 64)[0]
-        return torch.log_softmax(logits[:, : m.odim].float(), dim=-1).contiguous()
+            return ops.linear_fwd(x.to(BF16).contiguous(), st.s16("ctc.ctc_lo.weight"), st.p32("ctc.ctc_lo.bias"), rows=T, K=m.adim, N=m.odim,
+                                  x_pitch=m.adim, out_f32=True, out_pitch=(m.odim + 63) // 64 * 64)[0]
+
+    def ctc_log_softmax(self, x: torch.Tensor) -> torch.Tensor:
+        """`CTC.log_softmax` (ctc.py:163-170): x [T, adim] -> fp32 [T, odim]."""
+        return torch.log_softmax(self.ctc_logits(x)[:, : self.model.odim].float(), dim=-1).contiguous()
 
     def batch_init_state(self, x: torch.Tensor):
         self.logp = self.ctc_log_softmax(x)

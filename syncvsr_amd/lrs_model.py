@@ -109,7 +109,7 @@ class _DecoderFacade(_Holder):
 
 
 class _CtcFacade(_Holder):
-    """`E2E.ctc` inference helpers (ctc.py:154-181) on hs_pad [B, T, adim], and forced alignment (ctc.py:181-328)."""
+    """`E2E.ctc` inference helpers (ctc.py:154-181) on hs_pad [B, T, adim], greedy decoding, and forced alignment (ctc.py:181-328)."""
 
     def log_softmax(self, hs_pad: torch.Tensor) -> torch.Tensor:
         from .lrs_infer import CTCPrefixScorer
@@ -122,6 +122,14 @@ class _CtcFacade(_Holder):
 
     def argmax(self, hs_pad: torch.Tensor) -> torch.Tensor:
         return self.log_softmax(hs_pad).argmax(dim=-1)
+
+    def greedy_batch(self, hs_pad: torch.Tensor, ilens, blank_id: int = 0) -> list:
+        """Best-path decoding, `argmax` (ctc.py:172) with the collapse every caller of it applies: hs_pad [B, T, adim] encoder outputs, ilens
+        [B] -> a list of B numpy int64 arrays, the transcript of each clip (runs of a frame-wise winner merged, blank_id dropped; possibly
+        empty).  `lrs_align.greedy_features` on the same arguments also gives frames, spans and confidences."""
+        from .lrs_align import greedy_features
+
+        return [p.tokens for p in greedy_features(self._owner(), hs_pad, ilens, blank_id)]
 
     def forced_align_batch(self, hs_pad: torch.Tensor, ys_pad: torch.Tensor, ilens, blank_id: int = 0) -> list:
         """`CTC.forced_align_batch` (ctc.py:246-328): hs_pad [Tmax, B, odim] ACTIVATIONS (the reference applies log_softmax to them directly,

@@ -1895,6 +1895,43 @@ def ctc_align(logp: torch.Tensor, tlen: torch.Tensor, labels: torch.Tensor, blan
     return frames, spans, score
 
 
+CTC_GREEDY_MAX_FRAMES = 4096     # Tmax of svsr_ctc_collapse: a clip's winners and log-probabilities in LDS (csrc/lrs_search.hip CG_MAX_T)
+
+
+def ctc_frame_best(logits: torch.Tensor, tlen: torch.Tensor, *, Tmax: int, V: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """logits fp32 [C * Tmax, ldp >= V] (the fp32 output of `linear_fwd` for ctc_lo), tlen int32 [C] -> (best int32 [C, Tmax] the column of
+    the largest logit of every live frame, -1 behind tlen; best_logp fp32 [C, Tmax] its log-probability, 0 behind tlen).  Columns >= V and
+    frames behind tlen are never read.  See svsr_ctc_frame_best."""
+    C = tlen.numel()
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[0] == C * Tmax
+    assert tlen.dtype == torch.int32 and tlen.is_contiguous()
+    best = torch.empty((C, Tmax), dtype=torch.int32, device=logits.device)
+    best_logp = torch.empty((C, Tmax), dtype=torch.float32, device=logits.device)
+    _call("svsr_ctc_frame_best", _p(logits), logits.stride(0), _p(tlen), C, int(Tmax), int(V), _p(best), _p(best_logp), _stream(),
+          label="k_ctc_frame_best", nbytes=4.0 * C * Tmax * V)
+    return best, best_logp
+
+
+def ctc_collapse(best: torch.Tensor, best_logp: torch.Tensor, tlen: torch.Tensor, blank: int = 0, Lcap: Optional[int] = None):
+    """best int32 [C, Tmax], best_logp fp32 [C, Tmax], tlen int32 [C] -> (tokens int64 [C, Lcap], spans int32 [C, Lcap, 2], token_logp fp32
+    [C, Lcap], ntok int32 [C], score fp32 [C]): runs merged, blanks dropped; rows behind ntok hold -1 / (-1, -1) / 0.  Lcap defaults to Tmax
+    (a clip has no more tokens than frames).  Tmax <= CTC_GREEDY_MAX_FRAMES.  See svsr_ctc_collapse."""
+    C, Tmax = best.shape
+    Lcap = Tmax if Lcap is None else int(Lcap)
+    assert best.dtype == torch.int32 and best.is_contiguous() and best_logp.dtype == torch.float32 and best_logp.is_contiguous()
+    assert best_logp.shape == best.shape and tlen.dtype == torch.int32 and tlen.is_contiguous() and tlen.numel() == C
+    dev = best.device
+    rows = max(Lcap, 0)
+    tokens = torch.empty((C, rows), dtype=torch.int64, device=dev)
+    spans = torch.empty((C, rows, 2), dtype=torch.int32, device=dev)
+    token_logp = torch.empty((C, rows), dtype=torch.float32, device=dev)
+    ntok = torch.empty(C, dtype=torch.int32, device=dev)
+    score = torch.empty(C, dtype=torch.float32, device=dev)
+    _call("svsr_ctc_collapse", _p(best), _p(best_logp), _p(tlen), C, Tmax, Lcap, int(blank), _p(tokens), _p(spans), _p(token_logp), _p(ntok),
+          _p(score), _stream(), label="k_ctc_collapse")
+    return tokens, spans, token_logp, ntok, score
+
+
 def mha_src_step_fwd(q: torch.Tensor, kv: torch.Tensor, clip_of: torch.Tensor, tlen: torch.Tensor, *, Tmax: int, H: int,
                      scale: float = 0.125, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """q bf16 [n, >= H * 64], kv bf16 [C * Tmax, >= 2 * H * 64] (k | v per row), clip_of int32 [n], tlen int32 [C] -> ctx bf16 [n, H * 64]: row r
