@@ -1,6 +1,8 @@
 """Clips per second of the LRS beam search at the shipped model size (beam 40, CTC weight 0.1, 5,049 units): `BatchBeamSearch.forward` clip
-after clip (the only path before the multi-clip search; `forward` and everything it calls are unchanged by it) beside
-`BatchBeamSearch.forward_clips` over the same clips C at a time, C = 1, 8, 32, 64, with and without the transformer language model.
+after clip beside `BatchBeamSearch.forward_clips` over the same clips C at a time, C = 1, 8, 32, 64, with and without the transformer
+language model.  `forward` is a one-clip group of the multi-clip search, so the "forward, clip after clip" row (`seq`) times the same code
+path as the `forward_clips` C = 1 row and the two should agree within their spread; run on a checkout from before the searches were merged,
+the first row times the separate single-clip loop the package had then.
 
     python scripts/beam_bench.py [--clips 64] [--groups 1,8,32,64] [--reps 3] [--lm 0,1] [--out profiles/round9_beam_clips.json]
 

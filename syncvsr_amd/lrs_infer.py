@@ -17,10 +17,12 @@ batch_score` (transformer/decoder.py:153-220), `CTCPrefixScorer` (scorers/ctc.py
 
 The search itself is device-agnostic host logic over torch tensors; the two neural scorers need the HIP library.
 
-`BatchBeamSearch.forward_clips(xs [C, Tmax, D], lengths)` / `decode_clips` decode C clips in ONE lock-step search (the reference decodes its
-test list clip after clip): rows stay grouped by clip, the scorers are clip-aware (`batch_init_state_clips`, `batch_score_clips` /
-`batch_score_partial_clips`; any other scorer is wrapped in `PerClipScorers`), the selection of a position is one HIP entry point for all
-clips (svsr_beam_select; CPU tensors: its torch statement `beam_select_reference`), and the host synchronises once per position.
+There is ONE search.  `BatchBeamSearch.forward_clips(xs [C, Tmax, D], lengths)` / `decode_clips` decode C clips in lock step (the reference
+decodes its test list clip after clip), and `forward(x [T, D])` is that search with one clip: rows stay grouped by clip, the scorers are
+clip-aware (`batch_init_state_clips`, `batch_score_clips` / `batch_score_partial_clips`; a scorer that speaks the reference's single-clip
+protocol only, and for CPU tensors one that speaks both, is wrapped in `PerClipScorers`), the selection of a position is one HIP entry
+point for all clips (svsr_beam_select; anything but fp32 CUDA tensors: its torch statement `beam_select_reference`), and the host
+synchronises once per position.
 """
 from __future__ import annotations
 
@@ -71,16 +73,10 @@ class LengthBonus:
     def __init__(self, n_vocab: int):
         self.n = int(n_vocab)
 
-    def batch_init_state(self, x):
-        return None
-
-    def batch_score(self, ys, states, xs):
-        return torch.ones((ys.shape[0], self.n), dtype=xs.dtype, device=xs.device), None
-
     def select_states(self, states, prev, tok):
         return None
 
-    # -- clip-aware protocol (BatchBeamSearch.forward_clips): the bonus does not look at the clip
+    # -- clip-aware protocol: the bonus does not look at the clip
     def batch_init_state_clips(self, xs, lengths):
         self._like = xs
         return None
@@ -338,7 +334,7 @@ class CTCPrefixScorer:
                                    lambda r, last, ids_c, out_len: self._prefix(logp, r, last, ids_c, out_len))
 
     def _score_partial(self, y, ids, r_prev, s_prev, V: int, end, prefix):
-        """The part both searches share.  prefix(r_prev, last label, ids, labels in the prefix) -> (r_new, psi) is the recursion; end [n, 2]
+        """The part both protocols share.  prefix(r_prev, last label, ids, labels in the prefix) -> (r_new, psi) is the recursion; end [n, 2]
         is r_prev at the last frame of each hypothesis' clip, which gives <eos> its score."""
         ids_c = None if ids is None else ids.contiguous()
         r_new, psi = prefix(r_prev.contiguous(), y[:, -1].contiguous(), ids_c, y.shape[1] - 1)
@@ -350,7 +346,7 @@ class CTCPrefixScorer:
         full[:, self.blank] = LOGZERO
         return full - s_prev.unsqueeze(1), (r_new, full, ids_c)
 
-    # -- clip-aware protocol (BatchBeamSearch.forward_clips) ---------------------------------------
+    # -- clip-aware protocol -------------------------------------------------------------------------
     def batch_init_state_clips(self, xs: torch.Tensor, lengths):
         """xs [C, Tmax, adim]: the posteriors of every clip in one GEMM + one log-softmax -> self.logp_clips fp32 [C, Tmax, odim]."""
         C, Tmax = xs.shape[:2]
@@ -392,9 +388,8 @@ class CTCPrefixScorer:
         return r_new[prev, j].contiguous(), full[prev, tok].contiguous()
 
 
-
 # ----------------------------------------------------------------------------------------------------
-# multi-clip search: the adapter for single-clip scorers, and the torch statement of the selection step
+# the adapter for single-clip scorers, and the torch statement of the selection step
 # ----------------------------------------------------------------------------------------------------
 def _ranges(clip_of) -> dict:
     """{clip: (first row, end row)} of a non-decreasing row -> clip map (host side)."""
@@ -432,25 +427,28 @@ class _ClipStates:
 
 class PerClipScorers:
     """Adapter: any scorer that speaks the single-clip protocol (`batch_init_state(x)`, `batch_score(ys, states, xs)` or
-    `batch_score_partial(y, ids, state, x)`, `select_states`) as a clip-aware scorer of `BatchBeamSearch.forward_clips`.  Rows are split by
-    clip, the wrapped scorer is called once per clip with that clip's unpadded encoder output, and the answers are concatenated: correct
-    for every scorer, and as slow as one search per clip for this scorer's share of a step.  The single-clip protocol lets a scorer keep
-    data of its clip on itself (CTCPrefixScorer.logp), so every clip gets its own shallow copy of the wrapped scorer."""
+    `batch_score_partial(y, ids, state, x)`, `select_states`) as a clip-aware scorer of `BatchBeamSearch`.  Rows are split by clip, the
+    wrapped scorer is called once per clip with that clip's unpadded encoder output, and the answers are concatenated: correct for every
+    scorer, and as slow as one search per clip for this scorer's share of a step.  The single-clip protocol lets a scorer keep data of its
+    clip on itself (CTCPrefixScorer.logp), so every clip gets its own shallow copy of the wrapped scorer: attributes that
+    `batch_init_state` sets land on the copy.  `copies=False` (one clip only) hands the clip to the wrapped scorer itself, which is what
+    the reference's search does and how `BatchBeamSearch.forward` wraps."""
 
-    def __init__(self, scorer):
-        self.scorer = scorer
+    def __init__(self, scorer, copies: bool = True):
+        self.scorer, self.copies = scorer, copies
         self._per: dict = {}
-        if hasattr(scorer, "batch_score_partial"):
+        if hasattr(scorer, "batch_score_partial"):           # (the attribute marks a partial scorer for BatchBeamSearch's constructor)
             self.batch_score_partial_clips = self._batch_score_partial_clips
-            self.batch_score_partial = None                  # (marks a partial scorer for BatchBeamSearch's constructor)
 
     def batch_init_state_clips(self, xs: torch.Tensor, lengths):
         import copy
 
+        if not self.copies and len(lengths) != 1:
+            raise ValueError("PerClipScorers(copies=False) serves one clip")
         self._per = {}
         per = {}
         for c, T in enumerate(int(v) for v in lengths):
-            d = copy.copy(self.scorer)
+            d = copy.copy(self.scorer) if self.copies else self.scorer
             x = xs[c, :T]
             self._per[c] = (d, x)
             per[c] = (c, c + 1, d.batch_init_state(x))
@@ -479,7 +477,7 @@ class PerClipScorers:
 
 
 def beam_select_reference(planes, weights, run: torch.Tensor, row_lo, beam: int, V: int):
-    """The torch statement of the selection step of a multi-clip search — what svsr_beam_select computes, and the path of CPU tensors.
+    """The torch statement of the selection step — what svsr_beam_select computes, and the path of everything but fp32 CUDA tensors.
     planes [n, >= V] with their weights, in order; run [n]; row_lo: host list [C + 1] of the clips' row ranges.  weighted = zeros;
     weighted += w_k * s_k for every plane; weighted += run[:, None]; per clip the min(beam, rows * V) best (row, token), higher first,
     ties to the lower (row, token) -> (prev [m] global rows, tok [m], total [m], vals [P, m]: each plane at the winners, count: list [C])."""
@@ -519,7 +517,8 @@ class BatchBeamSearch:
             if weights.get(k, 0) == 0 or v is None:          # beam_search.py:73-76
                 continue
             self.scorers[k] = v
-            (self.part_scorers if hasattr(v, "batch_score_partial") else self.full_scorers)[k] = v
+            partial = hasattr(v, "batch_score_partial") or hasattr(v, "batch_score_partial_clips")
+            (self.part_scorers if partial else self.full_scorers)[k] = v
         self.sos, self.eos, self.token_list = int(sos), int(eos), token_list
         self.beam_size, self.n_vocab = int(beam_size), int(vocab_size)
         self.pre_beam_size = int(pre_beam_ratio * beam_size)
@@ -527,33 +526,6 @@ class BatchBeamSearch:
             raise KeyError(f"{pre_beam_score_key} is not found in {self.full_scorers}")
         self.pre_beam_score_key = pre_beam_score_key
         self.do_pre_beam = pre_beam_score_key is not None and self.pre_beam_size < self.n_vocab and len(self.part_scorers) > 0
-
-    # one step: running = dict(yseq [n, L], score [n], scores {k: [n]}, states {k: batched state})
-    def _search(self, run: dict, x: torch.Tensor) -> dict:
-        yseq = run["yseq"]
-        n, V = yseq.shape[0], self.n_vocab
-        xs = x.unsqueeze(0).expand(n, *x.shape)
-        weighted = torch.zeros((n, V), dtype=x.dtype, device=x.device)
-        sc, st = {}, {}
-        for k, d in self.full_scorers.items():
-            sc[k], st[k] = d.batch_score(yseq, run["states"][k], xs)
-            weighted += self.weights[k] * sc[k].to(x.dtype)
-        part_ids = None
-        if self.do_pre_beam:
-            pre = weighted if self.pre_beam_score_key == "full" else sc[self.pre_beam_score_key]
-            part_ids = torch.topk(pre, self.pre_beam_size, dim=-1)[1]
-        for k, d in self.part_scorers.items():
-            sc[k], st[k] = d.batch_score_partial(yseq, part_ids, run["states"][k], x)
-            weighted += self.weights[k] * sc[k].to(x.dtype)
-        weighted += run["score"].to(x.dtype).unsqueeze(1)
-        top = weighted.view(-1).topk(min(self.beam_size, n * V))[1]
-        prev, tok = torch.div(top, V, rounding_mode="trunc"), top % V
-        return dict(
-            yseq=torch.cat((yseq[prev], tok.unsqueeze(1)), dim=1),
-            score=weighted[prev, tok],
-            scores={k: run["scores"][k][prev] + sc[k][prev, tok].to(x.dtype) for k in self.scorers},
-            states={k: self.scorers[k].select_states(st[k], prev, tok) for k in self.scorers},
-        )
 
     @staticmethod
     def _take(states, keep: torch.Tensor):
@@ -564,42 +536,17 @@ class BatchBeamSearch:
         return states[keep]
 
     def forward(self, x: torch.Tensor, maxlenratio: float = 0.0, minlenratio: float = 0.0) -> list:
-        """x: encoder output of ONE clip [T, D] -> ended hypotheses, best first (beam_search.py:333-405)."""
-        if maxlenratio == 0:
-            maxlen = x.shape[0]
-        elif maxlenratio < 0:
-            maxlen = -1 * int(maxlenratio)
-        else:
-            maxlen = max(1, int(maxlenratio * x.size(0)))
-        run = dict(yseq=torch.tensor([[self.sos]], dtype=torch.int64, device=x.device), score=torch.zeros(1, dtype=x.dtype, device=x.device),
-                   scores={k: torch.zeros(1, dtype=x.dtype, device=x.device) for k in self.scorers},
-                   states={k: d.batch_init_state(x) for k, d in self.scorers.items()})
-        ended: list[Hypothesis] = []
-        for i in range(maxlen):
-            run = self._search(run, x)
-            n = run["yseq"].shape[0]
-            if i == maxlen - 1:          # batch_beam_search.py:318-334: close every running hypothesis at the length limit
-                run["yseq"] = torch.cat((run["yseq"], torch.full((n, 1), self.eos, dtype=torch.int64, device=x.device)), dim=1)
-            is_eos = run["yseq"][:, -1] == self.eos
-            scores_cpu = run["score"].tolist()
-            for b in torch.nonzero(is_eos).view(-1).tolist():
-                ended.append(Hypothesis(yseq=run["yseq"][b], score=scores_cpu[b], scores={k: float(v[b]) for k, v in run["scores"].items()}))
-            keep = torch.nonzero(~is_eos).view(-1)
-            run = dict(yseq=run["yseq"][keep], score=run["score"][keep], scores={k: v[keep] for k, v in run["scores"].items()},
-                       states={k: self._take(v, keep) for k, v in run["states"].items()})
-            if maxlenratio == 0.0 and end_detect([dict(score=h.score, yseq=h.yseq) for h in ended], i):
-                break
-            if keep.numel() == 0:
-                break
-        nbest = sorted(ended, key=lambda h: h.score, reverse=True)
-        if not nbest:                      # beam_search.py:383-392
-            return [] if minlenratio < 0.1 else self.forward(x, maxlenratio, max(0.0, minlenratio - 0.1))
-        return nbest
+        """x: encoder output of ONE clip [T, D] -> ended hypotheses, best first (beam_search.py:333-405): the search below with one clip."""
+        if x.dim() != 2:
+            raise ValueError(f"x must be the encoder output of one clip [frames, D], got {tuple(x.shape)}")
+        if x.shape[0] == 0:
+            return []
+        return self._forward_group(x.unsqueeze(0), [x.shape[0]], maxlenratio, minlenratio, copies=False)[0]
 
     __call__ = forward
 
     # ------------------------------------------------------------------------------------------------
-    # multi-clip search: C clips advance through ONE search in lock step
+    # the search: C clips advance in lock step
     # ------------------------------------------------------------------------------------------------
     # Device bytes the CTC scorer's pending state [rows, candidates, Tmax, 2] fp32 of one step may take.  A batch whose C * beam rows
     # would exceed it is decoded in groups of consecutive clips that fit (full-vocabulary partial scoring, ctc_weight == 1.0, at beam 40
@@ -613,24 +560,26 @@ class BatchBeamSearch:
         cand = self.pre_beam_size if self.do_pre_beam else self.n_vocab
         return max(1, int(self.clip_workspace_bytes) // (self.beam_size * cand * int(Tmax) * 2 * 4))
 
-    def _clip_scorers(self) -> dict:
+    def _clip_scorers(self, dev, copies: bool = True) -> dict:
+        """The scorers as the search speaks to them.  The clip-aware methods of this package's scorers are HIP launches, while their
+        single-clip protocol is the reference's and runs wherever its hooks do (a subclass that restates `CTCPrefixScorer._prefix` in torch
+        scores CPU tensors): a scorer that speaks both is driven clip-aware for device tensors and through `PerClipScorers` otherwise."""
         out = {}
         for k, d in self.scorers.items():
-            if isinstance(d, PerClipScorers):
-                out[k] = d
-            elif hasattr(d, "batch_init_state_clips") and hasattr(d, "batch_score_partial_clips" if k in self.part_scorers else "batch_score_clips"):
+            single = hasattr(d, "batch_init_state") and hasattr(d, "batch_score_partial" if k in self.part_scorers else "batch_score")
+            clips = hasattr(d, "batch_init_state_clips") and hasattr(d, "batch_score_partial_clips" if k in self.part_scorers else "batch_score_clips")
+            if isinstance(d, PerClipScorers) or (clips and (dev.type == "cuda" or not single)):
                 out[k] = d
             else:
-                out[k] = PerClipScorers(d)
+                out[k] = PerClipScorers(d, copies)
         return out
 
     def _select(self, planes, weights, run_score, clip_of, rows, meta):
         """-> (prev, tok, total, vals [P, m], clip_of of the winners).  rows: host list of rows per clip; meta: int32 device tensor
-        row_lo [C + 1] | out_off [C] (made where the host last synchronised), None on CPU."""
+        row_lo [C + 1] | out_off [C] (made where the host last synchronised), None on CPU.  The kernel adds fp32 planes; every other
+        dtype, and CPU tensors, take the torch statement."""
         V, beam = self.n_vocab, self.beam_size
-        if run_score.device.type == "cuda":
-            if run_score.dtype != torch.float32:
-                raise NotImplementedError(f"the selection kernel of a multi-clip search adds fp32 planes; the encoder outputs are {run_score.dtype}")
+        if run_score.device.type == "cuda" and run_score.dtype == torch.float32:
             C = len(rows)
             prev, tok, total, vals, clip_out, _ = ops.beam_select(
                 [s.to(torch.float32) for s in planes], weights, run_score.contiguous(), clip_of, meta[: C + 1], meta[C + 1 :], beam=beam, V=V,
@@ -643,7 +592,8 @@ class BatchBeamSearch:
         return prev, tok, total, vals, clip_of[prev]
 
     def _search_clips(self, run: dict, scorers: dict, rows: list, dtype) -> dict:
-        """One position of every live clip: `_search` with clip-aware scorers and the per-clip selection."""
+        """One position of every live clip (batch_beam_search.py:180-275): run = dict(yseq [n, L], score [n], scores {k: [n]}, states
+        {k: batched state}, clip_of [n], meta); full scorers, the pre-beam, partial scorers, then the per-clip selection."""
         yseq, clip_of = run["yseq"], run["clip_of"]
         sc, st = {}, {}
         for k in self.full_scorers:
@@ -659,7 +609,7 @@ class BatchBeamSearch:
             part_ids = torch.topk(pre, self.pre_beam_size, dim=-1)[1]          # per row: the clips do not meet here
         for k in self.part_scorers:
             sc[k], st[k] = scorers[k].batch_score_partial_clips(yseq, part_ids, run["states"][k], clip_of)
-        order = list(self.full_scorers) + list(self.part_scorers)              # the order `_search` adds the planes up in
+        order = list(self.full_scorers) + list(self.part_scorers)              # the order the planes are added up in
         prev, tok, total, vals, new_clip = self._select([sc[k].to(dtype) for k in order], [self.weights[k] for k in order], run["score"], clip_of,
                                                         rows, run["meta"])
         return dict(
@@ -672,8 +622,8 @@ class BatchBeamSearch:
 
     def forward_clips(self, xs: torch.Tensor, lengths, maxlenratio: float = 0.0, minlenratio: float = 0.0) -> list:
         """xs: padded encoder outputs of C clips [C, Tmax, D], lengths [C] (int tensor or list) -> per clip the ended hypotheses, best
-        first: element c is what `forward(xs[c, :lengths[c]])` returns.  All clips start together, so every live hypothesis has the same
-        prefix length at every position; each clip keeps its own length limit, end detection and ended list, and a clip that has finished
+        first: element c is what `forward(xs[c, :lengths[c]])`, the same search with that clip alone, returns.  All clips start
+        together, so every live hypothesis has the same prefix length at every position; each clip keeps its own length limit, end detection and ended list, and a clip that has finished
         simply stops contributing rows.  One host synchronisation per position for all clips together.  Scorers without the clip-aware
         methods are wrapped in `PerClipScorers`.  Batches beyond `clips_per_group(Tmax)` clips are decoded in groups of consecutive
         clips (`clip_workspace_bytes`)."""
@@ -692,7 +642,7 @@ class BatchBeamSearch:
             out += self._forward_group(xs[g0 : g0 + G, : max(ls)], ls, maxlenratio, minlenratio)
         return out
 
-    def _forward_group(self, xs: torch.Tensor, lens: list, maxlenratio: float, minlenratio: float) -> list:
+    def _forward_group(self, xs: torch.Tensor, lens: list, maxlenratio: float, minlenratio: float, copies: bool = True) -> list:
         C, dev, dt = xs.shape[0], xs.device, xs.dtype
         V, beam = self.n_vocab, self.beam_size
         if maxlenratio == 0:
@@ -701,7 +651,7 @@ class BatchBeamSearch:
             maxlen = [-1 * int(maxlenratio)] * C
         else:
             maxlen = [max(1, int(maxlenratio * t)) for t in lens]
-        scorers = self._clip_scorers()
+        scorers = self._clip_scorers(dev, copies)
         rows = [1 if maxlen[c] > 0 else 0 for c in range(C)]                      # live hypotheses per clip (host bookkeeping)
         first = [c for c in range(C) if rows[c]]
         run = dict(yseq=torch.full((len(first), 1), self.sos, dtype=torch.int64, device=dev), score=torch.zeros(len(first), dtype=dt, device=dev),
@@ -709,15 +659,13 @@ class BatchBeamSearch:
                    states={k: d.batch_init_state_clips(xs, lens) for k, d in scorers.items()},
                    clip_of=torch.tensor(first, dtype=torch.int32, device=dev), meta=self._meta(rows, dev))
         ended: list[list] = [[] for _ in range(C)]
-        wide = torch.float64 if dt == torch.float64 else torch.float32          # one read-back row type that holds tokens and scores exactly
+        wide = torch.float64 if dt == torch.float64 else torch.float32          # holds tokens (< 2^24) and narrower scores exactly
         i = 0
         while sum(rows) > 0:
             run = self._search_clips(run, scorers, rows, dt)
             rows = [min(beam, r * V) for r in rows]
             names = list(run["scores"])
             host = torch.stack([run["yseq"][:, -1].to(wide), run["score"].to(wide)] + [run["scores"][k].to(wide) for k in names]).cpu()
-            if dt not in (torch.float32, torch.float64):
-                host = host.to(dt)
             last, score, parts = host[0].tolist(), host[1].tolist(), [h.tolist() for h in host[2:]]
             keep, b = [], 0
             for c in range(C):
@@ -746,7 +694,7 @@ class BatchBeamSearch:
         for c in range(C):
             nbest = sorted(ended[c], key=lambda h: h.score, reverse=True)
             if not nbest and minlenratio >= 0.1:                 # beam_search.py:383-392
-                nbest = self._forward_group(xs[c : c + 1, : lens[c]], lens[c : c + 1], maxlenratio, max(0.0, minlenratio - 0.1))[0]
+                nbest = self._forward_group(xs[c : c + 1, : lens[c]], lens[c : c + 1], maxlenratio, max(0.0, minlenratio - 0.1), copies)[0]
             out.append(nbest)
         return out
 

@@ -1,7 +1,8 @@
 """Seeded cases and plain references of the beam-search kernel tests (tests/test_gpu_lrs_search_clips.py, tests/test_search_cases_cpu.py):
 source attention of one query row per hypothesis (csrc/lrs_search.hip k_mha_src_step) with its fp64 statement, an fp32 restatement of the
-kernel's chunked online softmax and two deliberately wrong variants of it, and the selection planes of svsr_beam_select at its edges.
-Everything here is CPU torch; the GPU tests copy the inputs over and compare."""
+kernel's chunked online softmax and two deliberately wrong variants of it, the selection planes of svsr_beam_select at its edges, and the
+statement of the search itself: the single-clip loop `BatchBeamSearch.forward` ran before it became a one-clip group of the multi-clip search.
+Everything here is plain torch; the GPU tests copy the inputs over and compare."""
 from __future__ import annotations
 
 import functools
@@ -267,3 +268,82 @@ def beam_edge_case(name: str):
     planes, weights, run, rows, V, beam = BEAM_EDGE_CASES[name]()
     row_lo, _, _ = beam_layout(rows, V, beam)
     return planes, weights, run, rows, V, beam, beam_select_reference(planes, weights, run, row_lo, beam, V)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the search
+# ----------------------------------------------------------------------------------------------------------------------
+def _take(states, keep: torch.Tensor):
+    if states is None:
+        return None
+    if isinstance(states, tuple):
+        return tuple(s[keep] for s in states)
+    return states[keep]
+
+
+def _single_clip_step(search, run: dict, x: torch.Tensor) -> dict:
+    """One position: running = dict(yseq [n, L], score [n], scores {k: [n]}, states {k: batched state})."""
+    yseq = run["yseq"]
+    n, V = yseq.shape[0], search.n_vocab
+    xs = x.unsqueeze(0).expand(n, *x.shape)
+    weighted = torch.zeros((n, V), dtype=x.dtype, device=x.device)
+    sc, st = {}, {}
+    for k, d in search.full_scorers.items():
+        sc[k], st[k] = d.batch_score(yseq, run["states"][k], xs)
+        weighted += search.weights[k] * sc[k].to(x.dtype)
+    part_ids = None
+    if search.do_pre_beam:
+        pre = weighted if search.pre_beam_score_key == "full" else sc[search.pre_beam_score_key]
+        part_ids = torch.topk(pre, search.pre_beam_size, dim=-1)[1]
+    for k, d in search.part_scorers.items():
+        sc[k], st[k] = d.batch_score_partial(yseq, part_ids, run["states"][k], x)
+        weighted += search.weights[k] * sc[k].to(x.dtype)
+    weighted += run["score"].to(x.dtype).unsqueeze(1)
+    top = weighted.view(-1).topk(min(search.beam_size, n * V))[1]
+    prev, tok = torch.div(top, V, rounding_mode="trunc"), top % V
+    return dict(
+        yseq=torch.cat((yseq[prev], tok.unsqueeze(1)), dim=1),
+        score=weighted[prev, tok],
+        scores={k: run["scores"][k][prev] + sc[k][prev, tok].to(x.dtype) for k in search.scorers},
+        states={k: search.scorers[k].select_states(st[k], prev, tok) for k in search.scorers},
+    )
+
+
+def single_clip_search(search, x: torch.Tensor, maxlenratio: float = 0.0, minlenratio: float = 0.0) -> list:
+    """The statement of `BatchBeamSearch.forward`: x, the encoder output of ONE clip [T, D] -> ended hypotheses, best first
+    (beam_search.py:333-405).  This is the loop `forward` ran while the package had a search per entry point, moved here as it was: `search`
+    gives its weights, scorers and settings only, and the scorers are spoken to in the reference's single-clip protocol (`batch_init_state(x)`,
+    `batch_score(ys, states, xs)` / `batch_score_partial(y, ids, state, x)`, `select_states`), torch.topk selects, and nothing of the
+    multi-clip search runs."""
+    from syncvsr_amd.lrs_infer import Hypothesis, end_detect
+
+    if maxlenratio == 0:
+        maxlen = x.shape[0]
+    elif maxlenratio < 0:
+        maxlen = -1 * int(maxlenratio)
+    else:
+        maxlen = max(1, int(maxlenratio * x.size(0)))
+    run = dict(yseq=torch.tensor([[search.sos]], dtype=torch.int64, device=x.device), score=torch.zeros(1, dtype=x.dtype, device=x.device),
+               scores={k: torch.zeros(1, dtype=x.dtype, device=x.device) for k in search.scorers},
+               states={k: d.batch_init_state(x) for k, d in search.scorers.items()})
+    ended: list = []
+    for i in range(maxlen):
+        run = _single_clip_step(search, run, x)
+        n = run["yseq"].shape[0]
+        if i == maxlen - 1:          # batch_beam_search.py:318-334: close every running hypothesis at the length limit
+            run["yseq"] = torch.cat((run["yseq"], torch.full((n, 1), search.eos, dtype=torch.int64, device=x.device)), dim=1)
+        is_eos = run["yseq"][:, -1] == search.eos
+        scores_cpu = run["score"].tolist()
+        for b in torch.nonzero(is_eos).view(-1).tolist():
+            ended.append(Hypothesis(yseq=run["yseq"][b], score=scores_cpu[b], scores={k: float(v[b]) for k, v in run["scores"].items()}))
+        keep = torch.nonzero(~is_eos).view(-1)
+        run = dict(yseq=run["yseq"][keep], score=run["score"][keep], scores={k: v[keep] for k, v in run["scores"].items()},
+                   states={k: _take(v, keep) for k, v in run["states"].items()})
+        if maxlenratio == 0.0 and end_detect([dict(score=h.score, yseq=h.yseq) for h in ended], i):
+            break
+        if keep.numel() == 0:
+            break
+    nbest = sorted(ended, key=lambda h: h.score, reverse=True)
+    if not nbest:                      # beam_search.py:383-392
+        return [] if minlenratio < 0.1 else single_clip_search(search, x, maxlenratio, max(0.0, minlenratio - 0.1))
+    return nbest

@@ -1,6 +1,6 @@
-"""Multi-clip beam search on the GPU (-m gpu): the three entry points of csrc/lrs_search.hip against their statements, the clip-aware
-decoder step against the single-clip one, and `BatchBeamSearch.forward_clips` under the criteria tests/test_gpu_lrs_infer.py and
-tests/test_gpu_lrs_lm.py apply to `forward`, per clip."""
+"""The beam search on the GPU (-m gpu): the three entry points of csrc/lrs_search.hip against their statements, the clip-aware
+decoder step against the single-clip one, `BatchBeamSearch.forward_clips` under the criteria tests/test_gpu_lrs_infer.py and
+tests/test_gpu_lrs_lm.py apply to `forward`, per clip, and `forward` as the one-clip group of the same search that it is."""
 import numpy as np
 import pytest
 import torch
@@ -481,7 +481,8 @@ def _rescore(sd, args, odim, enc, yseq, ctcw, maxlen, lm_ref=None, lmw=0.0):
 
 
 def _reference_search(sd64, args, odim, x64, beam, ctcw, lm_ref=None, lmw=0.0):
-    """The single-clip search under the fp64 scorers (tests/test_lrs_infer_cpu.py ties it to the reference's own n-best)."""
+    """The single-clip statement of the search (tests/search_cases.py) under the fp64 scorers (tests/test_lrs_search_clips_cpu.py ties it to
+    the reference's own n-best)."""
     from oracle import lrs_oracle as O
     from syncvsr_amd.lrs_infer import get_beam_search_decoder
 
@@ -492,7 +493,7 @@ def _reference_search(sd64, args, odim, x64, beam, ctcw, lm_ref=None, lmw=0.0):
     m.odim = odim
     bs = get_beam_search_decoder(m, [f"t{i}" for i in range(odim)], ctc_weight=ctcw, beam_size=beam,
                                  scorers=dict(decoder=O.OracleDecoderScorer(sd64, args), ctc=O.make_oracle_ctc_scorer(sd64, odim - 1)))
-    return bs.forward(x64)
+    return SC.single_clip_search(bs, x64)
 
 
 def _check_clip(nbest, ref, sd64, args, odim, x64, beam, ctcw, where, margin=0.05, lm_ref=None, lmw=0.0):
@@ -651,9 +652,76 @@ def test_forward_clips_with_the_language_model(dev, tiny):
                 ref = BatchBeamSearch(beam_size=beam, vocab_size=odim, weights={"decoder": 1 - ctcw, "ctc": ctcw, "lm": lmw, "length_bonus": 0},
                                       scorers=dict(decoder=O.OracleDecoderScorer(sd64, args), ctc=O.make_oracle_ctc_scorer(sd64, odim - 1), lm=lm_ref,
                                                    length_bonus=LengthBonus(odim)), sos=odim - 1, eos=odim - 1, pre_beam_score_key="decoder")
-                _check_clip(got[c], ref.forward(clips[c].double()), sd64, args, odim, clips[c].double(), beam, ctcw, f"lm run{r} clip{c}",
+                _check_clip(got[c], SC.single_clip_search(ref, clips[c].double()), sd64, args, odim, clips[c].double(), beam, ctcw, f"lm run{r} clip{c}",
                             lm_ref=lm_ref, lmw=lmw)
                 assert "lm" in got[c][0].scores
         assert ran >= 1
     finally:
         LMPool.__init__ = inner
+
+
+def _to(v, dev):
+    if isinstance(v, torch.Tensor):
+        return v.to(dev)
+    return type(v)(_to(e, dev) for e in v) if isinstance(v, (list, tuple)) else v
+
+
+class _HostScorer:
+    """A CPU scorer of the single-clip protocol behind device tensors: arguments go to the host, scores and states come back to `dev`."""
+
+    def __init__(self, inner, dev):
+        self.inner, self.dev = inner, dev
+
+    def batch_init_state(self, x):
+        return _to(self.inner.batch_init_state(x.cpu()), self.dev)
+
+    def batch_score(self, ys, states, xs):
+        return _to(self.inner.batch_score(ys.cpu(), _to(states, "cpu"), xs.cpu()), self.dev)
+
+    def select_states(self, states, prev, tok):
+        return _to(self.inner.select_states(_to(states, "cpu"), prev.cpu(), tok.cpu()), self.dev)
+
+
+class _HostPartialScorer(_HostScorer):
+    def batch_score_partial(self, y, ids, state, x):
+        return _to(self.inner.batch_score_partial(y.cpu(), _to(ids, "cpu"), _to(state, "cpu"), x.cpu()), self.dev)
+
+
+def test_forward_equals_a_one_clip_forward_clips(dev, tiny):
+    """`forward(x)` and `forward_clips(x[None], [T])[0]` are the same launches on the same inputs: equal hypotheses, bit-equal scores.  And
+    an encoder output that is not fp32 (fp64 on the device, the oracle's scorers behind PerClipScorers) is selected by the torch statement
+    instead of being refused, and gives what the single-clip statement of the search gives, to 1e-9."""
+    from oracle import lrs_oracle as O
+    from syncvsr_amd.lrs_infer import PerClipScorers, get_beam_search_decoder
+
+    model, args, odim, sd, clip, runs, gold = tiny
+    sd64 = {k: v.double() if v.is_floating_point() else v for k, v in sd.items()}
+    tokens = [f"t{i}" for i in range(odim)]
+    x = torch.from_numpy(gold["enc_feat"]).to(dev)
+    T = x.shape[0]
+    for beam in (4, 5):
+        bs = get_beam_search_decoder(model, tokens, ctc_weight=0.1, beam_size=beam)
+        one, group = bs(x), bs.forward_clips(x.unsqueeze(0), [T])[0]
+        assert one and len(one) == len(group)
+        for a, b in zip(one, group):
+            assert a.yseq.tolist() == b.yseq.tolist()
+            assert a.score == b.score and a.scores == b.scores, (beam, a.asdict(), b.asdict())      # floats compared exactly: the same bits
+
+        class _M:
+            pass
+
+        m = _M()
+        m.odim = odim
+        raw = dict(decoder=_HostScorer(O.OracleDecoderScorer(sd64, args), dev), ctc=_HostPartialScorer(O.make_oracle_ctc_scorer(sd64, odim - 1), dev))
+        statement = get_beam_search_decoder(m, tokens, ctc_weight=0.1, beam_size=beam, scorers=raw)
+        wrapped = get_beam_search_decoder(m, tokens, ctc_weight=0.1, beam_size=beam, scorers={k: PerClipScorers(v) for k, v in raw.items()})
+        assert list(wrapped.part_scorers) == ["ctc"]
+        x64 = x.double()
+        want = SC.single_clip_search(statement, x64)
+        assert want
+        for got in (wrapped.forward(x64), statement.forward(x64), wrapped.forward_clips(x64.unsqueeze(0), [T])[0]):
+            assert len(got) == len(want)
+            for g, w in zip(got, want):
+                assert g.yseq.is_cuda and g.yseq.tolist() == w.yseq.tolist()
+                assert abs(g.score - w.score) <= 1e-9 and set(g.scores) == set(w.scores)
+                assert all(abs(g.scores[k] - w.scores[k]) <= 1e-9 for k in w.scores), (beam, g.asdict(), w.asdict())

@@ -1,13 +1,15 @@
-"""Multi-clip beam search on CPU: `BatchBeamSearch.forward_clips` (syncvsr_amd/lrs_infer.py) driven by the oracle's fp64 scorers through
-`PerClipScorers` must return, for every clip of a padded batch, exactly what `forward` returns for that clip alone — and for the golden
-clip what the reference's own search returned (tests/golden/lrs_infer_tiny.npz).  fp64 and the same scorer calls: there is no rounding
-excuse, the bound is 1e-9.  Also here: the torch statement of the selection step against a brute-force stable sort on planes with exact
+"""The beam search on CPU: `BatchBeamSearch.forward_clips` (syncvsr_amd/lrs_infer.py) driven by the oracle's fp64 scorers through
+`PerClipScorers` must return, for every clip of a padded batch, exactly what the single-clip statement of the search
+(tests/search_cases.py single_clip_search: the reference's loop over the raw scorers) returns for that clip alone — and for the golden
+clip what the reference's own search returned (tests/golden/lrs_infer_tiny.npz); `forward` is a one-clip group of the same search and
+must equal the statement too.  fp64 and the same scorer calls: there is no rounding excuse, the bound is 1e-9.  Also here: the torch statement of the selection step against a brute-force stable sort on planes with exact
 ties, the row order after a finished clip's rows are dropped, and the grouping of a batch under the workspace bound."""
 import numpy as np
 import pytest
 import torch
 
 from golden_cases import build_lrs_infer_case
+from search_cases import single_clip_search
 
 
 def _clips(gold):
@@ -25,7 +27,8 @@ def _clips(gold):
 
 
 def _searches(sd, args, odim, beam, ctcw):
-    """(single-clip search over the raw oracle scorers, multi-clip search over the same scorers behind PerClipScorers)"""
+    """(search over the raw oracle scorers: what single_clip_search speaks to, and what `forward` wraps itself; search over the same scorers
+    already behind PerClipScorers)"""
     from oracle import lrs_oracle as O
     from syncvsr_amd.lrs_infer import PerClipScorers, get_beam_search_decoder
 
@@ -77,7 +80,7 @@ def test_forward_clips_equals_forward_per_clip_and_the_reference_nbest(case):
         got = many.forward_clips(xs, torch.tensor(lens))
         assert len(got) == len(clips)
         for c, x in enumerate(clips):
-            _same_nbest(got[c], one.forward(x), (r, c))
+            _same_nbest(got[c], single_clip_search(one, x), (r, c))
         # the golden clip: the reference's own n-best, as tests/test_lrs_infer_cpu.py asserts it
         nbest = got[0]
         assert len(nbest) == int(gold[f"run{r}.n_ended"])
@@ -100,6 +103,7 @@ def test_forward_clips_equals_forward_per_clip_and_the_reference_nbest(case):
 
 
 def test_one_clip_equals_forward_and_groups_under_the_workspace_bound_change_nothing(case):
+    """(`forward` as it was: the single-clip statement)"""
     args, odim, sd, runs, gold = case
     clips, xs, lens = _clips(gold)
     beam, ctcw = runs[0]
@@ -107,7 +111,7 @@ def test_one_clip_equals_forward_and_groups_under_the_workspace_bound_change_not
     for c in (0, 3):
         got = many.forward_clips(clips[c].unsqueeze(0), [lens[c]])
         assert len(got) == 1
-        _same_nbest(got[0], one.forward(clips[c]), c)
+        _same_nbest(got[0], single_clip_search(one, clips[c]), c)
     whole = many.forward_clips(xs, lens)
     # the documented bound: rows * candidates * Tmax * 2 fp32 of the CTC scorer's pending state per group
     per_clip = beam * many.pre_beam_size * max(lens) * 8
@@ -125,7 +129,78 @@ def test_one_clip_equals_forward_and_groups_under_the_workspace_bound_change_not
     got = full.forward_clips(xs[:2], lens[:2])
     ref, _ = _searches(sd, args, odim, 3, 1.0)
     for c in range(2):
-        _same_nbest(got[c], ref.forward(clips[c]), ("ctc only", c))
+        _same_nbest(got[c], single_clip_search(ref, clips[c]), ("ctc only", c))
+
+
+def test_forward_is_the_statement(case):
+    """`forward(x)` is a one-clip group of the multi-clip search; single_clip_search is the loop it used to be.  Every run of the fixture,
+    every clip, the three kinds of length limit (the clip's frames with end detection, a fixed count, a ratio), 1e-9."""
+    args, odim, sd, runs, gold = case
+    clips, xs, lens = _clips(gold)
+    for r, (beam, ctcw) in enumerate(runs):
+        search, _ = _searches(sd, args, odim, beam, ctcw)
+        for c, x in enumerate(clips):
+            for ratio in (0.0, -3, 0.5):
+                want = single_clip_search(search, x, ratio)
+                assert want, "the statement itself must find hypotheses here"
+                if ratio:                                        # a length limit closes whatever is still running: <eos> twice where it had ended
+                    assert max(len(h.yseq) for h in want) == (3 if ratio < 0 else max(1, int(0.5 * lens[c]))) + 2
+                _same_nbest(search.forward(x, ratio), want, (r, c, ratio))
+    assert type(search).__call__ is type(search).forward
+    # a limit of no position at all (-1 * int(-0.5) == 0): nothing ends, the minlenratio retry runs (0.3 -> 0.2 -> 0.1, which
+    # is 0.0999... in floating point and below the 0.1 that retries) and gives up
+    calls = []
+    inner = search._forward_group
+
+    def spy(xs, lens, maxlenratio, minlenratio, *a, **k):
+        calls.append(minlenratio)
+        return inner(xs, lens, maxlenratio, minlenratio, *a, **k)
+
+    search._forward_group = spy
+    assert single_clip_search(search, clips[0], -0.5, 0.3) == [] and search.forward(clips[0], -0.5, 0.3) == []
+    assert [round(m, 6) for m in calls] == [0.3, 0.2, 0.1], calls
+    # no frame: no hypothesis, and no scorer is asked
+    touched = []
+    search.scorers["decoder"].batch_init_state = lambda x: touched.append(x)
+    assert search.forward(clips[0][:0]) == [] and not touched and len(calls) == 3
+    with pytest.raises(ValueError, match="one clip"):
+        search.forward(xs)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16, torch.float32])
+def test_forward_reads_tokens_back_exactly_whatever_the_score_dtype(dtype):
+    """The shipped vocabulary: 5,049 units, <eos> = 5048, which bf16 rounds to 5056, and 5046 / 5047, which fp16 rounds to 5048.  A scripted
+    scorer lets every path go on with 5046 or 5047, end on <eos> from the third position on, and do nothing else at the fifth.  Its scores
+    and their sums are multiples of 1/16 below 4 in magnitude, exact in every dtype here; 5047 costs a power of two that depends on the
+    position and <eos> the only odd sixteenth, so no two candidates of a position tie.  `forward` must end the hypotheses the statement ends."""
+    from syncvsr_amd.lrs_infer import BatchBeamSearch
+
+    V, eos, a, b = 5049, 5048, 5046, 5047
+
+    class Scripted:
+        def batch_init_state(self, x):
+            return None
+
+        def batch_score(self, ys, states, xs):
+            n, L = ys.shape
+            sc = torch.full((n, V), -30.0, dtype=xs.dtype)
+            if L < 5:
+                sc[:, a], sc[:, b] = -0.5, -0.5 - 0.125 * 2 ** (L - 1)
+            if L >= 3:
+                sc[:, eos] = -0.0625
+            return sc, None
+
+        def select_states(self, states, prev, tok):
+            return None
+
+    bs = BatchBeamSearch(beam_size=3, vocab_size=V, weights=dict(s=1.0), scorers=dict(s=Scripted()), sos=eos, eos=eos)
+    x = torch.zeros(12, 2, dtype=dtype)
+    want = single_clip_search(bs, x)
+    assert want[0].yseq.tolist() == [eos, a, a, eos] and want[0].score == -1.0625
+    assert all(len(h.yseq) <= 6 and h.yseq.tolist().count(eos) == 2 for h in want)                 # nothing ran to the length limit
+    assert any(b in h.yseq.tolist() for h in want)
+    _same_nbest(bs.forward(x), want, dtype)
+    _same_nbest(bs.forward_clips(torch.stack((x, x)), [12, 7])[0], want, (dtype, "two clips"))
 
 
 def test_unsupported_use_raises(case):
@@ -229,7 +304,7 @@ def test_row_order_after_a_finished_clip_is_dropped():
     out = bs.forward_clips(xs, [8, 8, 8])
     single = BatchBeamSearch(beam_size=2, vocab_size=V, weights=dict(s=1.0), scorers=dict(s=Scripted()), sos=eos, eos=eos)
     for c in range(3):
-        _same_nbest(out[c], single.forward(xs[c]), c)
+        _same_nbest(out[c], single_clip_search(single, xs[c]), c)
     assert calls[0] == ([1, 1, 1], [0, 1, 2]) and calls[1] == ([2, 2, 2], [0, 0, 1, 1, 2, 2])
     assert ([2, 0, 2], [0, 0, 2, 2]) in calls                  # clip 1 gone: its neighbours' rows close up, in clip order
     assert out[1] and all(len(h.yseq) == 3 for h in out[1]) and all(len(h.yseq) > 3 for h in out[0] + out[2])
