@@ -437,6 +437,46 @@ int svsr_lincomb3_ratio(const float* a, float wa, const float* b, float wb, cons
  * H x W with bilinear sampling (align_corners = False, no antialias; a window of exactly H x W is a plain crop). */
 int svsr_clip_prep(const void* src_u8, const int* params, float* dst, int B, int T, int Hs, int Ws, int H, int W, float mean, float std, hipStream_t stream);
 
+/* Device-side input pipeline of the LRS path (csrc/lrs_prep.hip), what the reference runs per sample in dataloader workers
+ * (LRS/video/datamodule/transforms.py:89-135, av_dataset.py:30-41) and pads on the host (data_module.py:12-43).
+ *
+ * svsr_lrs_clip_prep: VideoTransform("train") (x / 255 -> RandomResizedCrop(96) -> RandomHorizontalFlip -> Grayscale -> Normalize(0.421,
+ * 0.165)) and the val / test pipelines (Resize(96) | CenterCrop(96)) over a batch of clips of DIFFERENT lengths in one launch.
+ * src_u8: packed uint8 frames [total_frames][Hs][Ws], one channel (AVDataset decodes with TJPF_GRAY, so Grayscale() is the identity);
+ * off: device int32 [B + 1], clip b holds frames off[b] .. off[b + 1] - 1; params: device int32 [B][5] = {top, left, h, w, flip} as in
+ * svsr_clip_prep; dst: fp32 [B][Tpad][1][H][W], the layout E2E.forward takes.  Frame t < T_b = off[b + 1] - off[b] of clip b is
+ * Normalize(flip(resize(window(x / 255)))) with svsr_clip_prep's sampling formulas (the same formulas, not bit-identical results: the compiler contracts them differently in the two
+ * kernels, measured difference at most 9.5e-7): bilinear, align_corners = False, NO
+ * antialias, a window of exactly H x W is a plain crop.  (torchvision's resize of a tensor antialiases only when it shrinks.  The LRS crops
+ * are stored at 96 x 96 and RandomResizedCrop(96) never draws a window larger than the stored frame, so it only enlarges and antialias
+ * never acts; a larger stored frame with a window above H x W is sampled WITHOUT antialias here, which is then not what torchvision
+ * computes.)  Frames T_b .. Tpad - 1 are written as 0.0 — what collate_pad pads the normalised clips with — and so is any frame that
+ * would lie outside [0, total_frames); a window is clamped into the stored frame: nothing outside src is read whatever off and params hold.
+ * tmask: device uint8 [B][Tpad] or null; a real frame with tmask != 0 is written as (0 - mean) / std, a frame zeroed in front of Normalize
+ * (AdaptiveTimeMask(10, 25), transforms.py:101, commented out in the reference: null by default).  Every element of dst is written: no
+ * zero-fill beside the launch.  Grid: one workgroup per (clip, frame, block of 32 rows) up to 16384, the rest in a stride loop; 16-byte
+ * stores where W % 4 == 0 and dst is 16-byte aligned.  max_blocks > 0 caps the grid instead (a test aid: the result does not depend on it).
+ * Moves total_frames * Hs * Ws bytes in (the window's share of them) and B * Tpad * H * W * 4 bytes out: HBM-bound on the write.
+ *
+ * svsr_wave_prep: AudioTransform (AddNoise = torchaudio.functional.add_noise at a drawn SNR, then F.layer_norm(x, x.shape, eps = 1e-8)).
+ * wave: fp32 [B][Spad], or int16 [B][Spad] with wave_i16 != 0 (a sample counts as v / 32768, pydub_to_np's scale); len: device int32 [B] real
+ * samples per clip (clamped to [0, Spad]); noise: device fp32 noise bank [Nn] or null; nstart: device int32 [B], clip b mixes noise[nstart[b]
+ * .. nstart[b] + len[b]); snr_db: device fp32 [B]; out: fp32 [B][Spad].  Per clip over its real samples
+ *     Ex = sum x^2, En = sum n^2, scale = sqrt(Ex / En) * 10^(-snr_db / 20), y = x + scale * n,
+ *     out = (y - mean(y)) / sqrt(var_biased(y) + eps),            samples >= len: 0.0
+ * scale is DEFINED as 0 — the noise-free normalisation, no NaN — where Ex == 0 or En == 0, where noise is null (the val / test transform
+ * without snr_target) and where the clip's noise segment would leave the bank (nothing outside it is read).  snr_db = 999999, the
+ * reference's "clean" level, underflows the power to 0: scale is an exact 0 and the output is bit-identical to noise = null.  A clip of
+ * length 0 is all padding.  Reductions: the first launch writes, per 4096 samples of a clip, one row of the five sums {x, n, x^2, n^2, x n}
+ * in DOUBLE into ws (caller-owned, svsr_wave_prep_ws_bytes(B, Spad) bytes, 8-byte aligned); the second adds a clip's rows in index order,
+ * derives scale, mean and variance from them in double (sum y = Sx + scale Sn, sum y^2 = Sxx + 2 scale Sxn + scale^2 Snn: a DC offset
+ * costs the variance no digits that matter) and writes out, each element evaluated in double and rounded once.  No atomics, a fixed
+ * order, a partition that depends on the lengths alone: bit-identical from run to run and under any max_blocks (as above: a test aid,
+ * 0 = one workgroup per 4096 samples up to 16384).  Bounds (SVSR_ERR_ARG): B >= 1, 1 <= Spad <= 2^30, eps >= 0, ws large enough. */
+int svsr_lrs_clip_prep(const void* src_u8, int64_t total_frames, const int* off, const int* params, const void* tmask, float* dst, int B, int Tpad, int Hs, int Ws, int H, int W, float mean, float std, int max_blocks, hipStream_t stream);
+int64_t svsr_wave_prep_ws_bytes(int B, int Spad);
+int svsr_wave_prep(const void* wave, int wave_i16, const int* len, const float* noise, int64_t Nn, const int* nstart, const float* snr_db, float* out, int B, int Spad, float eps, void* ws, int64_t ws_bytes, int max_blocks, hipStream_t stream);
+
 /* ---- LRS (E2E: Conformer encoder + CTC / attention decoder) -----------------------------------------------------
  * Multi-head attention with 64-wide heads (mha.hip).  q rows [B*Lq] with pitch q_pitch (head h at column h*64), k/v rows
  * [B*Lk] with pitch kv_pitch; klen[b] = number of valid keys (null: all), causal != 0 masks j > i.  With pe != null the

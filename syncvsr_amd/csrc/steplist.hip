@@ -85,6 +85,7 @@ const std::unordered_map<std::string, Entry>& registry() {
         SVSR_REG(svsr_beam_select), SVSR_REG(svsr_ctc_prefix_score_clips), SVSR_REG(svsr_mha_src_step_fwd), SVSR_REG(svsr_ctc_align),
         SVSR_REG(svsr_ctc_frame_best), SVSR_REG(svsr_ctc_collapse),
         SVSR_REG(svsr_tconv_fwd), SVSR_REG(svsr_tcn_se_fwd), SVSR_REG(svsr_tcn_norm_pool_fwd),
+        SVSR_REG(svsr_lrs_clip_prep), SVSR_REG(svsr_wave_prep),
     };
     return r;
 }

@@ -1523,6 +1523,40 @@ def clip_prep(frames_u8: torch.Tensor, params: torch.Tensor, H: int, W: int, mea
     return out
 
 
+def lrs_clip_prep(src_u8: torch.Tensor, off: torch.Tensor, params: torch.Tensor, Tpad: int, H: int, W: int, mean: float = 0.421,
+                  std: float = 0.165, tmask: Optional[torch.Tensor] = None, max_blocks: int = 0) -> torch.Tensor:
+    """Packed uint8 frames [sum T_b, Hs, Ws] + int32 frame offsets [B + 1] + int32 params [B, 5] = (top, left, h, w, flip) -> fp32
+    [B, Tpad, 1, H, W] with frames behind a clip's length 0.0 (svsr_lrs_clip_prep).  tmask: uint8 [B, Tpad], a marked real frame is written as
+    (0 - mean) / std.  max_blocks > 0: a grid cap for tests (the result does not depend on it)."""
+    B = off.numel() - 1
+    assert src_u8.dtype == torch.uint8 and src_u8.dim() == 3 and src_u8.is_contiguous()
+    assert off.dtype == torch.int32 and off.is_contiguous() and B >= 1 and params.dtype == torch.int32 and params.shape == (B, 5) and params.is_contiguous()
+    assert tmask is None or (tmask.dtype == torch.uint8 and tmask.shape == (B, Tpad) and tmask.is_contiguous())
+    out = torch.empty((B, Tpad, 1, H, W), dtype=torch.float32, device=src_u8.device)
+    _call("svsr_lrs_clip_prep", _p(src_u8), src_u8.shape[0], _p(off), _p(params), _p(tmask), _p(out), B, int(Tpad), src_u8.shape[1], src_u8.shape[2],
+          int(H), int(W), float(mean), float(std), int(max_blocks), _stream(), label="k_lrs_clip_prep", nbytes=float(src_u8.numel() + 4 * out.numel()))
+    return out
+
+
+def wave_prep(wave: torch.Tensor, lengths: torch.Tensor, noise: Optional[torch.Tensor] = None, nstart: Optional[torch.Tensor] = None,
+              snr_db: Optional[torch.Tensor] = None, eps: float = 1e-8, max_blocks: int = 0) -> torch.Tensor:
+    """wave fp32 or int16 [B, Spad] (int16 counts as v / 32768), lengths int32 [B] -> fp32 [B, Spad]: per clip over its real samples,
+    noise[nstart[b] : nstart[b] + len] mixed in at snr_db[b] (torchaudio's add_noise; noise=None: no mix), then the layer norm over the
+    waveform; samples behind the length are 0.0 (svsr_wave_prep: two launches, partial sums in the per-stream scratch)."""
+    B, Spad = wave.shape
+    assert wave.dtype in (torch.float32, torch.int16) and wave.is_contiguous() and lengths.dtype == torch.int32 and lengths.numel() == B and lengths.is_contiguous()
+    if noise is not None:
+        assert noise.dtype == torch.float32 and noise.dim() == 1 and noise.is_contiguous()
+        assert nstart.dtype == torch.int32 and nstart.numel() == B and nstart.is_contiguous() and snr_db.dtype == torch.float32 and snr_db.numel() == B and snr_db.is_contiguous()
+    out = torch.empty((B, Spad), dtype=torch.float32, device=wave.device)
+    ws_bytes = _query("svsr_wave_prep_ws_bytes", B, Spad)[0]
+    ws = scratch((ws_bytes + 3) // 4)
+    _call("svsr_wave_prep", _p(wave), int(wave.dtype == torch.int16), _p(lengths), _p(noise), 0 if noise is None else noise.numel(),
+          _p(nstart) if noise is not None else None, _p(snr_db) if noise is not None else None, _p(out), B, Spad, float(eps), _p(ws), ws_bytes,
+          int(max_blocks), _stream(), label="k_wave_prep", nbytes=float(wave.numel() * wave.element_size() * 2 + 4 * out.numel()))
+    return out
+
+
 def cast_bf16(src: torch.Tensor, dst: torch.Tensor) -> None:
     _call("svsr_cast_bf16", _p(src), _p(dst), src.numel(), _stream())
 
