@@ -679,6 +679,23 @@ int svsr_ctc_frame_best(const float* logits, int64_t ldp, const int* tlen, int C
 int svsr_ctc_collapse(const int* best, const float* best_logp, const int* tlen, int C, int Tmax, int Lcap, int blank, int64_t* tokens, int* spans, float* token_logp, int* ntok, float* score, hipStream_t stream);
 int svsr_mha_src_step_fwd(const void* q, int64_t q_pitch, const void* kv, int64_t kv_pitch, const int* clip_of, const int* tlen, int C, int Tmax, int n, int H, float scale, void* ctx, int64_t ctx_pitch, hipStream_t stream);
 
+/* ---- scoring of decoded transcripts (lrs_eval.hip) -----------------------------------------------------------------
+ * svsr_edit_distance: Levenshtein distance of N (hypothesis, reference) pairs and its split into substitutions, deletions and insertions:
+ * what the reference's test_step asks of torchaudio.functional.edit_distance (LRS/video/lightning.py:17-20,127), for a whole batch, an
+ * n-best list or a validation step at once.  hyp int64 [N] rows of ldh ids, ref int64 [N] rows of ldr ids (row strides in ids), hyp_len /
+ * ref_len int32 [N]; out int32 [N][4] = distance, substitutions, deletions, insertions.  Ids are compared on all 64 bits and may be
+ * anything (token ids, interned words, code points).  A length is cut to [0, min(row stride, 1024)] and nothing behind it is read.
+ * Definition: a cell holds (cost, S, D, I); cell(0,0) is all zero; cell(i,0) is i insertions (hypothesis ids with nothing to match);
+ * cell(0,j) is j deletions; for i, j >= 1 the candidates are, in priority order, (1) the diagonal cell(i-1,j-1) plus one substitution unless
+ * hyp[i-1] == ref[j-1], (2) a deletion from cell(i,j-1), (3) an insertion from cell(i-1,j); the smallest cost wins, a tie goes to the earlier
+ * candidate, and the counts travel with the chosen predecessor.  out is cell(hyp_len, ref_len).  So cost is the textbook distance,
+ * S + D + I == cost and hyp_len == ref_len - D + I, with no back-pointer matrix and nothing that depends on arrival: integer arithmetic, no
+ * atomics, no LDS.  One wave per pair: lane l keeps K = ceil(ref_len / 64) consecutive columns (ids and the cells above) in registers, the
+ * lanes sweep the rows skewed by one row per lane and hand the strip's last cell and the row's hypothesis id one lane up, so a pair takes
+ * hyp_len + (ref_len - 1) / K <= hyp_len + 63 steps of K cells.  Bounds (SVSR_ERR_ARG): N >= 1, ldh, ldr >= 0.  A dependent chain per pair:
+ * latency, not throughput. */
+int svsr_edit_distance(const int64_t* hyp, int64_t ldh, const int* hyp_len, const int64_t* ref, int64_t ldr, const int* ref_len, int N, int* out, hipStream_t stream);
+
 /* ---- native step enqueuer (steplist.hip; host code, launches nothing of its own) -----------------------------------
  * Stands where the reference's per-step host loop stands (pl.Trainer.fit -> training_step, LRW/video/src/train.py:23-45,
  * lightning.py:194-202): ONE host call per optimisation step instead of one per launch.  A list records, once, the launch

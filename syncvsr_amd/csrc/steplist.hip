@@ -83,7 +83,7 @@ const std::unordered_map<std::string, Entry>& registry() {
         SVSR_REG(svsr_igemm_wgrad_v2), SVSR_REG(svsr_igemm_wgrad_group_v2), SVSR_REG(svsr_conv3x3_wgrad_v2), SVSR_REG(svsr_fill_ranges),
         SVSR_REG(svsr_mha_table_fwd), SVSR_REG(svsr_lm_embed_fwd),
         SVSR_REG(svsr_beam_select), SVSR_REG(svsr_ctc_prefix_score_clips), SVSR_REG(svsr_mha_src_step_fwd), SVSR_REG(svsr_ctc_align),
-        SVSR_REG(svsr_ctc_frame_best), SVSR_REG(svsr_ctc_collapse),
+        SVSR_REG(svsr_ctc_frame_best), SVSR_REG(svsr_ctc_collapse), SVSR_REG(svsr_edit_distance),
         SVSR_REG(svsr_tconv_fwd), SVSR_REG(svsr_tcn_se_fwd), SVSR_REG(svsr_tcn_norm_pool_fwd),
         SVSR_REG(svsr_lrs_clip_prep), SVSR_REG(svsr_wave_prep),
     };

@@ -1966,6 +1966,41 @@ def ctc_collapse(best: torch.Tensor, best_logp: torch.Tensor, tlen: torch.Tensor
     return tokens, spans, token_logp, ntok, score
 
 
+EDIT_MAX_LEN = 1024              # ids per side of svsr_edit_distance: 64 lanes x 16 columns in registers (csrc/lrs_eval.hip ED_MAX_LEN)
+
+
+def _id_rows(t: torch.Tensor, name: str) -> int:
+    """Row stride (in ids) of the int64 rows `t` as svsr_edit_distance takes it.  The kernel cuts a row's length to its stride, so a stride
+    wider than the row must lie inside the tensor's storage for the last row too."""
+    n, w = t.shape
+    if w == 0:
+        return 0
+    ld = t.stride(0) if n > 1 else w
+    assert t.stride(1) == 1 and ld >= w, f"{name}: rows of unit stride, one after the other"
+    if ld > w:
+        assert t.storage_offset() + n * ld <= t.untyped_storage().nbytes() // 8, f"{name}: the last row's stride runs past the storage"
+    return ld
+
+
+def edit_distance(hyp: torch.Tensor, hyp_len: torch.Tensor, ref: torch.Tensor, ref_len: torch.Tensor) -> torch.Tensor:
+    """hyp int64 [N, Lh], hyp_len int32 [N], ref int64 [N, Lr], ref_len int32 [N] -> int32 [N, 4] = (distance, substitutions, deletions,
+    insertions) of every pair; hyp_len == ref_len - deletions + insertions.  Rows may be views of wider rows (unit stride along a row);
+    nothing behind a row's length is read.  Lh, Lr <= EDIT_MAX_LEN (ValueError, before any launch).  See svsr_edit_distance."""
+    assert hyp.dtype == torch.int64 and hyp.dim() == 2 and ref.dtype == torch.int64 and ref.dim() == 2 and ref.shape[0] == hyp.shape[0]
+    N = hyp.shape[0]
+    assert hyp_len.dtype == torch.int32 and hyp_len.is_contiguous() and hyp_len.numel() == N
+    assert ref_len.dtype == torch.int32 and ref_len.is_contiguous() and ref_len.numel() == N
+    if hyp.shape[1] > EDIT_MAX_LEN or ref.shape[1] > EDIT_MAX_LEN:
+        raise ValueError(f"sequences of more than {EDIT_MAX_LEN} ids are not supported, got rows of {hyp.shape[1]} and {ref.shape[1]}")
+    ldh, ldr = _id_rows(hyp, "hyp"), _id_rows(ref, "ref")
+    out = torch.empty((N, 4), dtype=torch.int32, device=hyp.device)
+    if N == 0:
+        return out
+    _call("svsr_edit_distance", _p(hyp) if ldh else None, ldh, _p(hyp_len), _p(ref) if ldr else None, ldr, _p(ref_len), N, _p(out), _stream(),
+          label="k_edit_distance")
+    return out
+
+
 def mha_src_step_fwd(q: torch.Tensor, kv: torch.Tensor, clip_of: torch.Tensor, tlen: torch.Tensor, *, Tmax: int, H: int,
                      scale: float = 0.125, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """q bf16 [n, >= H * 64], kv bf16 [C * Tmax, >= 2 * H * 64] (k | v per row), clip_of int32 [n], tlen int32 [C] -> ctx bf16 [n, H * 64]: row r
