@@ -359,6 +359,33 @@ int svsr_w2v_conv0(const float* wave, int B, int L_in, int pad, const float* w, 
 int svsr_w2v_norm_gelu(void* x, int B, int F, int rows, const float* gamma, const float* beta, float eps, float* stats, int F0, int mode, hipStream_t stream);
 int svsr_w2v_quantize(const void* feat, int R, int F, int keep, const float* gamma, const float* beta, float eps, const void* w, const float* bias, const unsigned* seed, unsigned site, int64_t* tok, float* logits_out, hipStream_t stream);
 
+/* ---- the vq-wav2vec k-means audio tokeniser (vq_codec.hip) ---------------------------------------------------------------
+ * Replaces forward_audios of the `vq` codec (LRW lightning.py:121-131): fairseq ConvFeatureExtractionModel (8 Conv1d of 512 channels without
+ * bias, kernels 10,8,4,4,4,1,1,1, strides 5,4,2,2,2,1,1,1, each followed by GroupNorm(1, 512) + ReLU; log(|x| + 1) at the end) and
+ * KmeansVectorQuantizer (grouped 1x1 projection, GroupNorm(2, 512), nearest of 320 centroids per group).  Activations: channels-last bf16 rows
+ * [B][rows][512].  Every GroupNorm takes its statistics over all frames of a clip: producers store per-(clip, block) partial {sum, sum of
+ * squares} pairs, consumers add them in block order in double.  svsr_vq_part_floats(B, F, kind): floats of such a partial buffer for clips of
+ *   F frames: kind 0 = [B][ceil(F / 64)][2] (svsr_vq_conv0_*, svsr_vq_gn_*), kind 1 = [B][2][ceil(F / 32)][2] (svsr_vq_project / svsr_vq_assign).
+ * svsr_vq_conv0_stats: layer 0 (w fp32 [512][10]) in fp32 over wave fp32 [B][L_in] followed by `pad` zeros per row, F0 = (L_in + pad - 10) / 5 + 1
+ *   frames; stores only the partial sums (kind 0) of the F0 x 512 pre-norm values.
+ * svsr_vq_conv0_apply: the same convolution again, then relu(GroupNorm(1, 512) * gamma + beta) into out [B][out_rows][512] (out_rows >= F0).
+ * Layers 1-7 are svsr_igemm_fwd over svsr_rows_plan(B, F_out, 0, 0, 512): a stride-s kernel-k convolution reads the contiguous k*512 values of
+ *   source row t when rows overlap with pitch s*512 (Ci = k*512, in_pitch = s*512, in_pix = rows / s), followed by
+ * svsr_vq_gn_partial: partial sums (kind 0) of the F valid rows of every clip of x [B][rows][512], and
+ * svsr_vq_gn_relu: in place over those rows relu(GroupNorm(1, 512) * gamma + beta), mode 1: log(. + 1) on top.  Rows F .. rows - 1 are not touched.
+ * svsr_vq_project: x bf16 [B * F][512], w bf16 [512][256] (output channel o of group o / 256 reads input channels (o / 256) * 256 ..) ->
+ *   ze fp32 [B * F][512] and the partial sums (kind 1) of each group's F x 256 values.
+ * svsr_vq_assign: z = GroupNorm(2, 512)(ze) * gamma + beta, score[v] = e2[g][v] - 2 z_g . emb[g][v] (emb bf16 [2][320][256], e2 fp32 [2][320]),
+ *   tok int64 [B][keep][2] = per-group argmin of frames t < keep, ties to the lowest index, in the layout svsr_linear_ce_fwd / svsr_ce_fwd read
+ *   (no + 320 offset).  A row with a NaN score in either group gets token 0 in both.  scores_out (fp32 [B * F][2][320], optional): the scores. */
+int64_t svsr_vq_part_floats(int B, int F, int kind);
+int svsr_vq_conv0_stats(const float* wave, int B, int L_in, int pad, const float* w, float* part, hipStream_t stream);
+int svsr_vq_conv0_apply(const float* wave, int B, int L_in, int pad, const float* w, const float* gamma, const float* beta, float eps, const float* part, void* out, int out_rows, hipStream_t stream);
+int svsr_vq_gn_partial(const void* x, int B, int F, int rows, float* part, hipStream_t stream);
+int svsr_vq_gn_relu(void* x, int B, int F, int rows, const float* gamma, const float* beta, float eps, const float* part, int mode, hipStream_t stream);
+int svsr_vq_project(const void* x, int B, int F, const void* w, float* ze, float* part, hipStream_t stream);
+int svsr_vq_assign(const float* ze, int B, int F, int keep, const float* gamma, const float* beta, float eps, const float* part, const void* emb, const float* e2, int64_t* tok, float* scores_out, hipStream_t stream);
+
 /* top-1 / top-5 accuracy (lightning.py:177-183); out2 = {top1, top5}; rows2: [B][2] float workspace. */
 int svsr_topk_acc(const float* logits, const int64_t* labels, const float* soft_labels, int B, int C, float* out2, float* rows2, hipStream_t stream);
 

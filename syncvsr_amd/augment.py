@@ -52,17 +52,35 @@ def make_plan(batch_size: int, frames: int, token_steps: int, generator: Optiona
 
 
 class CutMix(torch.nn.Module):
-    """Drop-in for the reference's ``CutMix(num_labels, wav2vec=None)`` on pre-tokenised audio."""
+    """Drop-in for the reference's ``CutMix(num_labels, wav2vec=None)``.  wav2vec: an audio_codec.VqWav2VecCodec; float waveforms in the
+    `audios` slot are then tokenised first (augment.py:38-40) and the tokens spliced as pre-tokenised audio is.  The codec is BORROWED: it
+    is kept in a plain tuple, not as a sub-module, so this module's ``state_dict()`` and ``.to()`` leave it alone — whoever owns it (the
+    model it is attached to, or the caller of a stand-alone CutMix) moves it to the device and lists its buffers, once."""
 
     def __init__(self, num_labels: int, wav2vec=None) -> None:
         super().__init__()
-        if wav2vec is not None:
-            raise NotImplementedError("on-the-fly wav2vec tokenisation is outside the hot path; pass audio tokens")
         self.num_labels = num_labels
+        self.set_codec(wav2vec)
         self.generator: Optional[torch.Generator] = None     # None = torch's global CPU generator, as the reference uses
+
+    def set_codec(self, wav2vec) -> None:
+        """None, or the vq tokeniser (class docstring).  As attach_audio_codec: TypeError for what is no codec, ValueError for the wrong kind."""
+        from .audio_codec import VqWav2VecCodec, Wav2Vec2Codec
+
+        if isinstance(wav2vec, Wav2Vec2Codec):
+            raise ValueError("CutMix belongs to the word-level models, whose codec is 'vq': it tokenises with a VqWav2VecCodec, not the wav2vec2 tokeniser")
+        if wav2vec is not None and not isinstance(wav2vec, VqWav2VecCodec):
+            raise TypeError("CutMix(wav2vec=...) takes a syncvsr_amd.audio_codec.VqWav2VecCodec or None")
+        self._codec = (wav2vec,)
+
+    @property
+    def wav2vec(self):
+        return self._codec[0]
 
     def forward(self, videos: torch.Tensor, audios: torch.Tensor, labels: torch.Tensor, word_mask: torch.Tensor):
         B, _, T = videos.shape[:3]
+        if self.wav2vec is not None and audios.is_floating_point():
+            audios = self.wav2vec(audios)
         plan = make_plan(B, T, audios.shape[1], self.generator)
         dev = videos.device
         fsrc = plan.frame_src.to(dev, non_blocking=True)

@@ -13,9 +13,9 @@ second-stage branches with ``Swish(out1 + res)`` in the epilogue (svsr_tconv_fwd
 scale / shift applied to the fp32 accumulator; the bf16 weights are never scaled.
 
 Reference defects resolved here: ``self.vq_groups`` is never set there (2, as TransformerLightningModule); the module reads
-``config.optim.loss_audio_weight`` while the yaml has ``optim.lambda_audio`` (either is accepted); fairseq's codec is not loaded — audio
-tokens arrive pre-tokenised, and ``load_state_dict`` ignores ``wav2vec.*`` keys (as inference.py's strict=False does) while staying strict
-about everything else.
+``config.optim.loss_audio_weight`` while the yaml has ``optim.lambda_audio`` (either is accepted); fairseq is not imported — audio tokens
+arrive pre-tokenised or, after ``attach_audio_codec(audio_codec.VqWav2VecCodec...)``, as float waveforms tokenised on the device; without
+that codec ``load_state_dict`` ignores ``wav2vec.*`` keys (as inference.py's strict=False does) while staying strict about everything else.
 """
 from __future__ import annotations
 
@@ -87,7 +87,7 @@ class DCTCNLightningModule(_StoreModule):
             raise NotImplementedError("; ".join(why))
         self.dims = dctcn_dims(config)
         self.audio_alignment, self.vq_groups, self.audio_vocab_size = self.dims["A"], self.dims["G"], self.dims["V"]
-        self.codec = "vq"                    # pre-tokenised vq-wav2vec tokens: attach_audio_codec refuses the wav2vec2 tokeniser
+        self.codec = "vq"                    # vq-wav2vec tokens, pre-computed or from an attached audio_codec.VqWav2VecCodec
         optim = config.get("optim", Config())
         w = optim.get("loss_audio_weight", optim.get("lambda_audio"))         # the module reads the first, the shipped yaml holds the second
         if w is None:
@@ -104,6 +104,8 @@ class DCTCNLightningModule(_StoreModule):
         self.eval()
 
     # ------------------------------------------------------------------------------------------------
+    takes_vq_waveforms = True
+
     @staticmethod
     def _fwd_rank(name: str) -> int:
         return 0 if name.startswith("model.frontend3D") else 1 if name.startswith("model.trunk") else 2
@@ -124,8 +126,11 @@ class DCTCNLightningModule(_StoreModule):
         return self._store
 
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
-        """`wav2vec.*` keys (the frozen codec of a reference checkpoint) are ignored; everything else is checked as `strict` says."""
-        kept = {k: v for k, v in state_dict.items() if not k.startswith("wav2vec.")}
+        """Without an attached codec `wav2vec.*` keys (the frozen codec of a reference checkpoint) are ignored — with one they are its buffers
+        (the aggregator and prediction heads, which it does not hold, still are); everything else is checked as `strict` says."""
+        codec = self._modules.get("wav2vec")
+        own = () if codec is None else tuple("wav2vec." + k for k in codec.state_dict())
+        kept = {k: v for k, v in state_dict.items() if not k.startswith("wav2vec.") or k in own}
         return super().load_state_dict(kept, strict=strict, assign=assign)
 
     # ------------------------------------------------------------------------------------------------
@@ -258,11 +263,13 @@ class DCTCNLightningModule(_StoreModule):
 
     def forward(self, videos: torch.Tensor, audios: torch.Tensor, labels: torch.Tensor, word_mask: torch.Tensor,
                 attention_mask: torch.Tensor) -> dict[str, torch.Tensor]:
-        """lightning.py:255-312 in eval mode (lam = 0).  audios: pre-computed vq-wav2vec tokens int64 [B, >= A*T, 2]."""
+        """lightning.py:255-312 in eval mode (lam = 0).  audios: pre-computed vq-wav2vec tokens int64 [B, >= A*T, 2], or, with the tokeniser
+        attached (attach_audio_codec), float waveforms [B, L] / [B, 1, L] on the device."""
         B, _, T = videos.shape[:3]
         A, G, V = self.audio_alignment, self.vq_groups, self.audio_vocab_size
+        audios = self._tokenize_waveforms(audios, T * A)
         if audios.dtype != torch.int64 or audios.dim() != 3 or audios.size(2) != G:
-            raise ValueError("pass pre-computed audio tokens int64 [B, >= A*T, 2] in the `audios` slot (the fairseq codec is not loaded)")
+            raise ValueError("pass pre-computed audio tokens int64 [B, >= A*T, 2] in the `audios` slot (no audio tokeniser is attached)")
         if audios.size(1) < T * A:
             raise ValueError(f"audio tokens have {audios.size(1)} steps, need >= {T * A}")
         st, h, logits_c = self._run(videos, word_mask, attention_mask)

@@ -594,6 +594,10 @@ class TrainStep:
         With use_graph / native the batch shapes are fixed by the first call (later batches are copied into the static buffers).
         With accumulate = N > 1 this is one micro-step of a window (class docstring); the optimiser runs in every N-th call."""
         self._watch_fused_encoder()
+        if self.is_lrw:
+            # float waveforms (vq codec attached): the tokeniser draws nothing, so it runs as eager launches in FRONT of the recorded /
+            # replayed / captured step, which sees tokens as it always did; its device forms thereby exist before a step is recorded
+            batch = (batch[0], self.model._tokenize_waveforms(batch[1], batch[0].size(2) * self.model.audio_alignment), *batch[2:])
         try:
             out = self._step(*batch)
         except BaseException:

@@ -163,25 +163,46 @@ class _StoreModule(nn.Module):
         no_decay = [p for p in self.parameters() if p.requires_grad and p.ndim < 2]
         return [{"params": do_decay}, {"params": no_decay, "weight_decay": 0.0}]
 
-    def attach_audio_codec(self, codec, sample_in_training: bool = True):
-        """Registers the frozen wav2vec2 tokeniser (audio_codec.Wav2Vec2Codec) as `self.wav2vec`, the reference's attribute: state_dict()
-        gains its `wav2vec.*` buffers.  The word-level model then has forward_audios (its forward / training_step still take pre-computed
-        tokens); the sentence-level model's forward / prepare_batch / train_step_direct take float waveforms [B, 1, L] or [B, L] in the
-        `audios` slot — 8000 zeros are appended to every row and the tokens are computed inside the step.  In training mode the tokens are
-        argmax(logits + Gumbel noise) (the reference's frozen quantiser runs its gumbel_softmax branch under Lightning's model.train()),
-        keyed by the dropout seed word; sample_in_training=False keeps the eval-mode argmax.  The codec holds buffers only: it stays out of
-        parameters(), the parameter store, the optimiser, clipping and the gradient / BatchNorm-statistics collectives."""
-        from .audio_codec import Wav2Vec2Codec
+    takes_vq_waveforms = False          # the word-level models set it: their `audios` slot takes waveforms once a VqWav2VecCodec is attached
 
-        if not isinstance(codec, Wav2Vec2Codec):
-            raise TypeError("attach_audio_codec takes a syncvsr_amd.audio_codec.Wav2Vec2Codec")
-        if self.codec != "wav2vec2":
+    def attach_audio_codec(self, codec, sample_in_training: bool = True):
+        """Registers the frozen audio tokeniser of this model's codec — audio_codec.Wav2Vec2Codec for `wav2vec2`, audio_codec.VqWav2VecCodec
+        for `vq` — as `self.wav2vec`, the reference's attribute: state_dict() gains its `wav2vec.*` buffers.  With the wav2vec2 codec the
+        word-level model then has forward_audios (its forward / training_step still take pre-computed tokens); the sentence-level model's
+        forward / prepare_batch / train_step_direct take float waveforms [B, 1, L] or [B, L] in the `audios` slot — 8000 zeros are appended
+        to every row and the tokens are computed inside the step.  In training mode the tokens are argmax(logits + Gumbel noise) (the
+        reference's frozen quantiser runs its gumbel_softmax branch under Lightning's model.train()), keyed by the dropout seed word;
+        sample_in_training=False keeps the eval-mode argmax.  With the vq codec (deterministic: nothing is drawn) the word-level models take
+        float waveforms in the `audios` slot wherever the reference calls forward_audios; they are tokenised first and cropped to T * A
+        frames (_tokenize_waveforms).  The codec holds buffers only: it stays out of parameters(), the parameter store, the optimiser,
+        clipping and the gradient / BatchNorm-statistics collectives."""
+        from .audio_codec import VqWav2VecCodec, Wav2Vec2Codec
+
+        if not isinstance(codec, (Wav2Vec2Codec, VqWav2VecCodec)):
+            raise TypeError("attach_audio_codec takes a syncvsr_amd.audio_codec.Wav2Vec2Codec or VqWav2VecCodec")
+        if isinstance(codec, Wav2Vec2Codec) and self.codec != "wav2vec2":
             raise ValueError(f"this model was built for the {self.codec!r} codec (model.wav2vec.path of the word-level config, args.codec of the "
                              f"sentence-level one): the wav2vec2 tokeniser gives 640-way tokens, A = 2")
+        if isinstance(codec, VqWav2VecCodec) and not self.takes_vq_waveforms:
+            raise ValueError("the sentence-level model tokenises waveforms with the wav2vec2 codec only; pass pre-computed vq tokens")
+        if isinstance(codec, VqWav2VecCodec) and self.codec != "vq":
+            raise ValueError(f"this model was built for the {self.codec!r} codec (model.wav2vec.path of the word-level config, args.codec of the "
+                             f"sentence-level one): the vq-wav2vec tokeniser gives 320-way tokens, A = 4")
         codec.to(_get(self, self._specs[0][0]).device)
         self.wav2vec = codec
+        if isinstance(codec, VqWav2VecCodec) and getattr(self, "cutmix", None) is not None:
+            self.cutmix.set_codec(codec)        # lightning.py:85-88: CutMix(num_labels, wav2vec=self.wav2vec)
         self.codec_sample_in_training = bool(sample_in_training)
         return self
+
+    def _tokenize_waveforms(self, audios: torch.Tensor, frames: int) -> torch.Tensor:
+        """Float waveforms [B, L] / [B, 1, L] in the `audios` slot of a model with the vq tokeniser attached -> its tokens of the first
+        `frames` audio frames, int64 [B, frames, 2] (lightning.py:121-131, then the crop [:, :T*A] of forward).  Anything else — tokens, or
+        float audio without that codec — is returned as it came and meets the checks it always met."""
+        codec = self._modules.get("wav2vec")
+        if codec is None or self.codec != "vq" or not torch.is_tensor(audios) or not audios.is_floating_point():
+            return audios
+        return codec(audios, keep=int(frames))
 
     def _codec_samples(self) -> bool:
         """The tokeniser of this training step draws Gumbel noise (and so needs the seed word to advance every step)."""
@@ -351,13 +372,15 @@ class TransformerLightningModule(_StoreModule):
         self._phys = {n: phys_shape(config, n, shp) for n, shp, _ in self._specs}
         from .augment import CutMix
 
-        self.cutmix = CutMix(self.word_labels).eval()          # lightning.py:85-88
+        self.cutmix = CutMix(self.word_labels).eval()          # lightning.py:85-88 (attach_audio_codec hands it the vq tokeniser)
         self.stem_name, self.trunk_name = "stem3d", "resnet"
         self.stem_act, self.trunk_act = ops.ACT_GELU, ops.ACT_RELU          # lightning.py:52, timm BasicBlock
 
     # ------------------------------------------------------------------------------------------------
     # reference-compatible helpers
     # ------------------------------------------------------------------------------------------------
+    takes_vq_waveforms = True
+
     def training_step(self, batch, idx: int = 0) -> torch.Tensor:
         """lightning.py:194-202: (CutMix) -> forward -> loss_total."""
         self.is_train = True
@@ -365,14 +388,28 @@ class TransformerLightningModule(_StoreModule):
             batch = self.cutmix(*batch)
         return self(*batch)["loss_total"]
 
+    def validation_step(self, batch, idx: int = 0) -> dict:
+        """lightning.py:204-208: forward in evaluation mode (float waveforms are tokenised by the attached vq codec) -> the `val/` metrics."""
+        self.is_train = False
+        return {f"val/{k}": v for k, v in self(*batch).items()}
+
+    def test_step(self, batch, idx: int = 0) -> dict:
+        """lightning.py:210-214."""
+        self.is_train = False
+        return {f"test/{k}": v for k, v in self(*batch).items()}
+
     def forward_audios(self, audios: torch.Tensor) -> torch.Tensor:
-        """lightning.py:121-131 for the wav2vec2 codec: float waveforms [B, L] (or [B, 1, L]) -> int64 tokens [B, F, 2] (no padding appended).
-        In training mode (with sample_in_training) the tokens are argmax(logits + Gumbel noise) keyed by the current dropout seed word."""
+        """lightning.py:121-131: float waveforms [B, L] (or [B, 1, L]) -> int64 tokens [B, F, 2] (no padding appended).  wav2vec2 codec: in
+        training mode (with sample_in_training) the tokens are argmax(logits + Gumbel noise) keyed by the current dropout seed word; the vq
+        codec is deterministic."""
         codec = self._modules.get("wav2vec")
         if codec is None:
-            raise ValueError("forward_audios needs a wav2vec2 tokeniser: call attach_audio_codec(Wav2Vec2Codec...) first")
+            kind = "VqWav2VecCodec" if self.codec == "vq" else "Wav2Vec2Codec"
+            raise ValueError(f"forward_audios needs the {self.codec} tokeniser: call attach_audio_codec({kind}...) first")
         if audios.device.type != "cuda":
             raise RuntimeError("audio waveforms must be on the MI355X device: the tokeniser has no CPU path")
+        if self.codec == "vq":
+            return codec(audios)
         seed = self._seed_word(audios.device) if self.training and self.codec_sample_in_training else None
         return codec(audios, sample=seed is not None, seed_word=seed)
 
@@ -439,6 +476,7 @@ class TransformerLightningModule(_StoreModule):
         st = self.store()
         T = videos.size(2)
         A = self.audio_alignment
+        audio_tokens = self._tokenize_waveforms(audio_tokens, T * A)
         audio_tokens = audio_tokens[:, : T * A].contiguous()
         if audio_tokens.size(1) != T * A:
             raise ValueError(f"audio_tokens has {audio_tokens.size(1)} steps, need >= {T * A}")
@@ -466,6 +504,7 @@ class TransformerLightningModule(_StoreModule):
         (inside the recorded region every one of them must be a no-op, so that no torch kernel is needed at replay)."""
         T = videos.size(2)
         A = self.audio_alignment
+        audio_tokens = self._tokenize_waveforms(audio_tokens, T * A)
         if audio_tokens.size(1) < T * A:
             raise ValueError(f"audio_tokens has {audio_tokens.size(1)} steps, need >= {T * A}")
         hard = labels.dtype in (torch.int64, torch.int32)

@@ -1809,6 +1809,53 @@ def w2v_quantize(feat: torch.Tensor, R: int, F: int, keep: int, gamma, beta, eps
           _stream(), label="k_w2v_quantize", flops=2.0 * R * 512 * 640)
 
 
+# vq-wav2vec k-means audio tokeniser (csrc/vq_codec.hip)
+
+def vq_part_floats(B: int, F: int, kind: int) -> int:
+    """Floats of a GroupNorm partial-sum buffer for B clips of F frames: kind 0 layers 0-7, kind 1 the projection (svsr_vq_part_floats)."""
+    n = int(_lib.load().svsr_vq_part_floats(B, F, kind))
+    if n < 0:
+        _lib.check(-n, "svsr_vq_part_floats")
+    return n
+
+
+def vq_conv0_stats(wave: torch.Tensor, B: int, L_in: int, pad: int, w: torch.Tensor, part: torch.Tensor) -> None:
+    """Layer 0 of the feature extractor, statistics only: wave fp32 [B][L_in] (+ pad zeros) -> partial sums of its GroupNorm (svsr_vq_conv0_stats)."""
+    F0 = (L_in + pad - 10) // 5 + 1
+    _call("svsr_vq_conv0_stats", _p(wave), B, L_in, pad, _p(w), _p(part), _stream(), label="k_vq_conv0<stats>", flops=2.0 * B * F0 * 512 * 10)
+
+
+def vq_conv0_apply(wave: torch.Tensor, B: int, L_in: int, pad: int, w: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float,
+                   part: torch.Tensor, out: torch.Tensor, out_rows: int) -> None:
+    """Layer 0 again + GroupNorm(1, 512) + ReLU -> out bf16 [B][out_rows][512] (svsr_vq_conv0_apply)."""
+    F0 = (L_in + pad - 10) // 5 + 1
+    _call("svsr_vq_conv0_apply", _p(wave), B, L_in, pad, _p(w), _p(gamma), _p(beta), float(eps), _p(part), _p(out), out_rows, _stream(),
+          label="k_vq_conv0<apply>", flops=2.0 * B * F0 * 512 * 10)
+
+
+def vq_gn_partial(x: torch.Tensor, B: int, F: int, rows: int, part: torch.Tensor) -> None:
+    """Partial sums of the F valid rows of every clip of x bf16 [B][rows][512] (svsr_vq_gn_partial)."""
+    _call("svsr_vq_gn_partial", _p(x), B, F, rows, _p(part), _stream(), label="k_vq_gn_partial")
+
+
+def vq_gn_relu(x: torch.Tensor, B: int, F: int, rows: int, gamma: torch.Tensor, beta: torch.Tensor, eps: float, part: torch.Tensor,
+               log: bool = False) -> None:
+    """In place over the valid rows: relu(GroupNorm(1, 512)), with log: log(. + 1) on top (svsr_vq_gn_relu)."""
+    _call("svsr_vq_gn_relu", _p(x), B, F, rows, _p(gamma), _p(beta), float(eps), _p(part), 1 if log else 0, _stream(), label="k_vq_gn_relu")
+
+
+def vq_project(x: torch.Tensor, B: int, F: int, w16: torch.Tensor, ze: torch.Tensor, part: torch.Tensor) -> None:
+    """The quantiser's grouped projection: x bf16 [B * F][512] -> ze fp32 [B * F][512] + its GroupNorm partial sums (svsr_vq_project)."""
+    _call("svsr_vq_project", _p(x), B, F, _p(w16), _p(ze), _p(part), _stream(), label="k_vq_project", flops=2.0 * B * F * 512 * 256)
+
+
+def vq_assign(ze: torch.Tensor, B: int, F: int, keep: int, gamma: torch.Tensor, beta: torch.Tensor, eps: float, part: torch.Tensor,
+              emb16: torch.Tensor, e2: torch.Tensor, tok: torch.Tensor, scores_out: Optional[torch.Tensor] = None) -> None:
+    """GroupNorm(2, 512) + nearest centroid per group -> tok int64 [B][keep][2] (svsr_vq_assign)."""
+    _call("svsr_vq_assign", _p(ze), B, F, keep, _p(gamma), _p(beta), float(eps), _p(part), _p(emb16), _p(e2), _p(tok), _p(scores_out), _stream(),
+          label="k_vq_assign", flops=2.0 * B * F * 512 * 320)
+
+
 # --------------------------------------------------------------------------------------------------
 # Transformer language-model scorer (csrc/lrs_lm.hip)
 # --------------------------------------------------------------------------------------------------
