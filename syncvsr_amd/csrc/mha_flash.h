@@ -318,6 +318,12 @@ __global__ __launch_bounds__(512) void k_mhaf_bwd_q(const MhafArgs p) {
         const bf16_t* qrow = a.q + ((long)b * a.Lq + qi) * a.q_pitch + h * MHA_DH + half * 8;
         const bf16_t* drow = a.dctx + ((long)b * a.Lq + qi) * a.dctx_pitch + h * MHA_DH + half * 8;
         const bf16_t* crow = p.ctx + ((long)b * a.Lq + qi) * p.ctx_in_pitch + h * MHA_DH + half * 8;
+        // D_i = dctx_i . ctx_i is the diagonal of ctx dctx^T, taken from the same MFMA chain (same operand layout, same order of additions)
+        // that makes dP^T = V dctx^T below: where a query has ONE live key, ctx_i is that key's V row bit for bit, so dP - D is exactly
+        // zero, as it is in the per-tile kernels, and not a few ulp of it
+        f32x16 dd;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dd[r] = 0.f;
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
             const bf16x8 f = ld_frag(qrow + kk * 16);
@@ -328,10 +334,11 @@ __global__ __launch_bounds__(512) void k_mhaf_bwd_q(const MhafArgs p) {
                 qu[kk] = f; qv[kk] = f;
             }
             dct[kk] = ld_frag(drow + kk * 16);
-            const bf16x8 c = ld_frag(crow + kk * 16);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) dsum = __builtin_fmaf(bf2f((bf16_t)dct[kk][e]), bf2f((bf16_t)c[e]), dsum);
+            dd = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ld_frag(crow + kk * 16), dct[kk], dd, 0, 0, 0);
         }
+#pragma unroll
+        for (int e = 0; e < 16; ++e)
+            if (mf_row(e, half) == il) dsum = dd[e];          // (one lane of the pair holds row il of column il)
         dsum += __shfl_xor(dsum, 32, 64);
         if (live) lse = p.lse[(long)bh * a.Lq + i];
     }
