@@ -504,6 +504,32 @@ int svsr_lrs_clip_prep(const void* src_u8, int64_t total_frames, const int* off,
 int64_t svsr_wave_prep_ws_bytes(int B, int Spad);
 int svsr_wave_prep(const void* wave, int wave_i16, const int* len, const float* noise, int64_t Nn, const int* nstart, const float* snr_db, float* out, int B, int Spad, float eps, void* ws, int64_t ws_bytes, int max_blocks, hipStream_t stream);
 
+/* Device-side training inputs of the LRW path (csrc/lrw_prep.hip): the reference's per-clip chain x / 255 -> RandomHorizontalFlip ->
+ * RandomResizedCrop | Identity -> Grayscale -> TimeMask -> Normalize (LRW/video/src/data.py:157-164) and the frame splice of its sequential
+ * CutMix (LRW/video/src/augment.py:27-118) in two launches per batch.  src_u8: uint8 clips [B][T][Hs][Ws]; params: device int32 [B][5] =
+ * {top, left, h, w, flip} as in svsr_clip_prep, sampled by the SAME device function (csrc/clip_sample.h): x_s[t], frame t of clip s in front
+ * of Normalize, is what svsr_clip_prep samples, and a frame that is neither masked nor spliced has svsr_clip_prep's bits.
+ *
+ * svsr_lrw_clip_sums: frame_sums fp32 [B][T], the sum of x_s[t] over the frame's H * W pixels.  One workgroup per (clip, frame) up to 16384,
+ * the rest in a stride loop; thread i of 256 adds pixels i, i + 256, ... in index order, the 64 lanes in a butterfly, the 4 waves in wave
+ * order: the partition depends on H * W alone.  No atomics; bit-identical from run to run and under any max_blocks (> 0 caps the grid: a
+ * test aid).  Reads the windows' share of B * T * Hs * Ws bytes, writes B * T * 4.
+ *
+ * svsr_lrw_clip_mix: dst fp32 [B][1][T][H][W], dst[b][0][t] = Normalize(TimeMask(x_s))[t] with s = frame_src[b][t] — the ORIGINAL clip that
+ * frame t of sample b comes from once the reference's in-place chain is resolved (augment.make_plan); crop, flip and mask are clip s's.
+ * frame_src: device int32 [B][T], clamped into [0, B).  runs: device int32 [B][n_mask][2] = (start, length) of clip s's masked runs in the
+ * order TimeMask draws them, clamped into [0, T] (a length of 0 masks nothing); n_mask = 0: no mask, runs may be null.  The fill of run j is
+ * the mean over all T * H * W values of the clip AS MASKED SO FAR, derived per workgroup from the clip's T frame sums:
+ *     S = sum_t fs[t];   per run: m = S / (T H W), for t in the run: S += H W m - cur[t], cur[t] = H W m
+ * (fp32, a fixed order) and a masked frame is written as the constant (fill - mean) / std; with replace_with_zero the fill is 0 and
+ * frame_sums may be null.  Any other frame is sampled and normalised as svsr_clip_prep does.  Nothing outside src_u8 is read whatever
+ * params, frame_src and runs hold.  One workgroup per (sample, frame, block of 32 rows) up to 16384, the rest in a stride loop; 16-byte
+ * stores where W % 4 == 0 and dst is 16-byte aligned; max_blocks as above.  Every element of dst is written once.  Together the two
+ * launches read the clips twice (uint8) and write B * T * H * W * 4 bytes: HBM-bound on the write.
+ * Bounds (SVSR_ERR_ARG): B, T, Hs, Ws, H, W >= 1, T <= 256, Hs * Ws, H * W and B * T <= 2^24, std > 0, 0 <= n_mask <= 65536, max_blocks >= 0. */
+int svsr_lrw_clip_sums(const void* src_u8, const int* params, float* frame_sums, int B, int T, int Hs, int Ws, int H, int W, int max_blocks, hipStream_t stream);
+int svsr_lrw_clip_mix(const void* src_u8, const int* params, const int* frame_src, const int* runs, const float* frame_sums, float* dst, int B, int T, int Hs, int Ws, int H, int W, int n_mask, int replace_with_zero, float mean, float std, int max_blocks, hipStream_t stream);
+
 /* ---- LRS (E2E: Conformer encoder + CTC / attention decoder) -----------------------------------------------------
  * Multi-head attention with 64-wide heads (mha.hip).  q rows [B*Lq] with pitch q_pitch (head h at column h*64), k/v rows
  * [B*Lk] with pitch kv_pitch; klen[b] = number of valid keys (null: all), causal != 0 masks j > i.  With pe != null the

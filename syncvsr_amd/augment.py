@@ -84,20 +84,27 @@ class CutMix(torch.nn.Module):
         plan = make_plan(B, T, audios.shape[1], self.generator)
         dev = videos.device
         fsrc = plan.frame_src.to(dev, non_blocking=True)
-        tsrc = plan.token_src.to(dev, non_blocking=True)
         tidx = torch.arange(T, device=dev).unsqueeze(0).expand(B, T)
         mixed_videos = videos[fsrc, :, tidx].permute(0, 2, 1, 3, 4).contiguous()          # [B, 1, T, H, W]
-        aidx = torch.arange(audios.shape[1], device=dev).unsqueeze(0).expand(B, -1)
-        mixed_audios = audios[tsrc, aidx].contiguous()
-        mix = plan.mix.to(dev)
-        tgt = plan.target_ids.to(dev)
-        one_hot = F.one_hot(labels, self.num_labels)
-        # integer one-hots promoted by the float mix rate, as in augment.py:111-113; untouched samples stay integer there,
-        # the concatenation makes the batch float — here everything is float32 from the start
-        mixed_labels = (1.0 - mix).unsqueeze(1) * one_hot.float() + mix.unsqueeze(1) * one_hot[tgt].float()
-        wm = word_mask.float()
-        mixed_word_mask = (1.0 - mix).view(B, *([1] * (wm.dim() - 1))) * wm + mix.view(B, *([1] * (wm.dim() - 1))) * wm[tgt]
-        return mixed_videos, mixed_audios, mixed_labels, mixed_word_mask
+        return (mixed_videos, *mix_small_tensors(plan, audios, labels, word_mask, self.num_labels, dev))
+
+
+def mix_small_tensors(plan: CutMixPlan, audios: torch.Tensor, labels: torch.Tensor, word_mask: torch.Tensor, num_labels: int, dev):
+    """What CutMix mixes besides the clips, for a resolved plan: audio tokens gathered by `token_src`, labels as [B, num_labels]
+    probabilities, float word masks (augment.py:104-116).  Shared by CutMix.forward and DeviceLRWPipeline."""
+    B = audios.shape[0]
+    tsrc = plan.token_src.to(dev, non_blocking=True)
+    aidx = torch.arange(audios.shape[1], device=dev).unsqueeze(0).expand(B, -1)
+    mixed_audios = audios[tsrc, aidx].contiguous()
+    mix = plan.mix.to(dev)
+    tgt = plan.target_ids.to(dev)
+    one_hot = F.one_hot(labels, num_labels)
+    # integer one-hots promoted by the float mix rate, as in augment.py:111-113; untouched samples stay integer there,
+    # the concatenation makes the batch float — here everything is float32 from the start
+    mixed_labels = (1.0 - mix).unsqueeze(1) * one_hot.float() + mix.unsqueeze(1) * one_hot[tgt].float()
+    wm = word_mask.float()
+    mixed_word_mask = (1.0 - mix).view(B, *([1] * (wm.dim() - 1))) * wm + mix.view(B, *([1] * (wm.dim() - 1))) * wm[tgt]
+    return mixed_audios, mixed_labels, mixed_word_mask
 
 
 def draw_time_runs(n_frames: int, max_run, n_mask: int) -> list[tuple[int, int]]:
@@ -196,3 +203,108 @@ class DeviceClipPipeline:
         identity = self.train and not self.use_rrc          # nn.Identity: output size = stored size
         H, W = (Hs, Ws) if identity else (self.size, self.size)
         return ops.clip_prep(frames_u8.contiguous(), params.to(frames_u8.device, non_blocking=True), H, W, self.mean, self.std)
+
+
+class DeviceLRWPipeline:
+    """The word-level training inputs on the device in two launches per batch: what the reference spreads over its dataset transform
+    (LRW/video/src/data.py:157-164: x / 255 -> RandomHorizontalFlip -> RandomResizedCrop | Identity -> Grayscale -> TimeMask -> Normalize,
+    per clip in the loader workers) and its sequential CutMix (augment.py:27-118, per batch in the training step), from the stored uint8
+    crops [B, T, Hs, Ws] and a few host-drawn integers.  svsr_lrw_clip_sums writes the per-frame sums that TimeMask's clip means are made
+    of; svsr_lrw_clip_mix writes the batch, every frame sampled from the clip that CutMix's in-place chain finally takes it from, with that
+    clip's crop, flip and mask (csrc/lrw_prep.hip).  No per-clip launches and no second pass over the fp32 clips.
+
+    `__call__(frames_u8, audios, labels, word_mask)` returns `(videos, audios, labels, word_mask)` as CutMix.forward does: with use_cutmix
+    the audio tokens are spliced, the labels are [B, num_labels] probabilities and the word mask is float; without it the three pass
+    through.  The batch is ALREADY mixed: hand it to `model(*batch)` or `engine.TrainStep.step(*batch)`, not to `model.training_step`,
+    which applies CutMix itself when `train.use_cutmix` is on.
+
+    Draws, all on the host, in this order per batch (`plan`):
+      1. `DeviceClipPipeline.draw`: window and flip of every clip, from the numpy generator seeded with `seed`;
+      2. `draw_time_runs` per clip in batch order, from Python's `random` (two calls per mask, as the reference's dataset makes them);
+      3. `make_plan`, from `self.generator`, or torch's global CPU generator when that is None (as CutMix).
+    A stage that is off draws nothing.  train=False, or use_timemask and use_cutmix both off, is `DeviceClipPipeline.__call__` — one
+    svsr_clip_prep launch; the sums launch is also left out when no clip has a run of positive length, and with replace_with_zero.
+
+    codec: a VqWav2VecCodec; float waveforms in the `audios` slot are then tokenised first, as `CutMix(wav2vec=)` does.  It is BORROWED
+    (kept in a plain tuple): whoever owns it moves it to the device."""
+
+    def __init__(self, size: int, num_labels: int, train: bool = True, use_rrc: bool = True, use_timemask: bool = True, use_cutmix: bool = True,
+                 timemask_T: float = 0.6 * 25, n_mask: int = 1, replace_with_zero: bool = False, use_val_resize: bool = False,
+                 mean: float = 0.421, std: float = 0.165, seed: int = 0, codec=None):
+        from .audio_codec import VqWav2VecCodec, Wav2Vec2Codec
+
+        if isinstance(codec, Wav2Vec2Codec):
+            raise ValueError("DeviceLRWPipeline belongs to the word-level models, whose codec is 'vq': it tokenises with a VqWav2VecCodec, not the wav2vec2 tokeniser")
+        if codec is not None and not isinstance(codec, VqWav2VecCodec):
+            raise TypeError("DeviceLRWPipeline(codec=...) takes a syncvsr_amd.audio_codec.VqWav2VecCodec or None")
+        if int(n_mask) < 0:
+            raise ValueError("n_mask must be >= 0")
+        self._codec = (codec,)
+        self.clips = DeviceClipPipeline(size, train, use_rrc=use_rrc, use_val_resize=use_val_resize, mean=mean, std=std, seed=seed)
+        self.size, self.num_labels, self.train = int(size), int(num_labels), bool(train)
+        self.use_timemask, self.use_cutmix = bool(train and use_timemask and int(n_mask) > 0), bool(train and use_cutmix)
+        # (an integral float bound, the reference's 0.6 * 25, draws what the integer draws; `random` refuses floats from Python 3.12 on)
+        self.timemask_T = int(timemask_T) if float(timemask_T).is_integer() else timemask_T
+        self.n_mask, self.replace_with_zero = int(n_mask), bool(replace_with_zero)
+        self.mean, self.std = float(mean), float(std)
+        self.generator: Optional[torch.Generator] = None     # None = torch's global CPU generator, as CutMix
+
+    @property
+    def codec(self):
+        return self._codec[0]
+
+    def plan(self, B: int, T: int, Hs: int, Ws: int, token_steps: int) -> dict:
+        """Every host decision of one batch, drawn in the documented order: {"params": int32 [B, 5] = (top, left, h, w, flip), "runs": int32
+        [B, n_mask, 2] = (start, length) per clip as drawn (None without the time mask), "cutmix": the CutMixPlan (None without CutMix)}."""
+        params = self.clips.draw(B, Hs, Ws)
+        runs = None
+        if self.use_timemask:
+            runs = torch.tensor([draw_time_runs(T, self.timemask_T, self.n_mask) for _ in range(B)], dtype=torch.int32).reshape(B, self.n_mask, 2)
+        cut = make_plan(B, T, token_steps, self.generator) if self.use_cutmix else None
+        return {"params": params, "runs": runs, "cutmix": cut}
+
+    def __call__(self, frames_u8: torch.Tensor, audios: torch.Tensor, labels: torch.Tensor, word_mask: torch.Tensor, plan: Optional[dict] = None):
+        from . import ops
+
+        if frames_u8.dim() != 4 or frames_u8.dtype != torch.uint8:
+            raise ValueError("frames_u8 must be uint8 [B, T, Hs, Ws]")
+        B, T, Hs, Ws = frames_u8.shape
+        if self.codec is not None and audios.is_floating_point():
+            audios = self.codec(audios)
+        if plan is None:
+            plan = self.plan(B, T, Hs, Ws, audios.shape[1])
+        params, runs, cut = plan["params"], plan.get("runs"), plan.get("cutmix")
+        if not (self.use_timemask or self.use_cutmix) or (runs is None and cut is None):
+            return self.clips(frames_u8, params), audios, labels, word_mask
+        if T > ops.LRW_CLIP_MAX_FRAMES:
+            raise ValueError(f"clips of {T} frames: the LRW clip kernels take at most {ops.LRW_CLIP_MAX_FRAMES}")
+        if params.dtype != torch.int32 or params.shape != (B, 5):
+            raise ValueError(f"params must be int32 [B, 5] = {(B, 5)}")
+        top, left, h, w = (params[:, i] for i in range(4))
+        if bool(((top < 0) | (left < 0) | (h < 1) | (w < 1) | (top + h > Hs) | (left + w > Ws)).any()):
+            raise ValueError("crop window outside the stored frame")
+        if cut is not None and (cut.frame_src.shape != (B, T) or int(cut.frame_src.min()) < 0 or int(cut.frame_src.max()) >= B):
+            raise ValueError("frame_src must be [B, T] with entries in [0, B)")
+        if runs is not None:
+            if runs.dim() != 3 or runs.shape[0] != B or runs.shape[2] != 2:
+                raise ValueError("runs must be [B, n_mask, 2]")
+            start, length = runs[..., 0].long(), runs[..., 1].long()
+            if bool(((start < 0) | (length < 0) | (start + length > T)).any()):
+                raise ValueError("time-mask run outside the clip")
+            if not bool((length > 0).any()):
+                runs = None                              # nothing is masked: no sums, no run table
+        dev = frames_u8.device
+        identity = self.clips.train and not self.clips.use_rrc          # nn.Identity: output size = stored size
+        H, W = (Hs, Ws) if identity else (self.size, self.size)
+        fsrc = torch.arange(B, dtype=torch.int32).unsqueeze(1).repeat(1, T) if cut is None else cut.frame_src.to(torch.int32)
+        # every drawn integer in ONE small upload: params | frame_src | runs
+        parts = [params.reshape(-1), fsrc.reshape(-1)] + ([runs.to(torch.int32).reshape(-1)] if runs is not None else [])
+        meta = torch.cat(parts).to(dev, non_blocking=True)
+        par_d, fsrc_d = meta[: 5 * B].view(B, 5), meta[5 * B: 5 * B + B * T].view(B, T)
+        runs_d = meta[5 * B + B * T:].view(B, -1, 2) if runs is not None else None
+        frames_u8 = frames_u8.contiguous()
+        sums = ops.lrw_clip_sums(frames_u8, par_d, H, W) if runs_d is not None and not self.replace_with_zero else None
+        videos = ops.lrw_clip_mix(frames_u8, par_d, fsrc_d, H, W, runs_d, sums, self.replace_with_zero, self.mean, self.std)
+        if cut is None:
+            return videos, audios, labels, word_mask
+        return (videos, *mix_small_tensors(cut, audios, labels, word_mask, self.num_labels, dev))

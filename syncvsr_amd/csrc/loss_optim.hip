@@ -6,6 +6,7 @@
 //   * global-norm clip + AdamW + cosine schedule + bf16 shadow refresh (lightning.py:216-223)
 //   * fp32 -> bf16 shadow casts / transposes of the weights the MFMA kernels consume
 #include "common.h"
+#include "clip_sample.h"
 
 // one wave per row; logits may be bf16 or f32; V <= 64*CE_MAXPER
 #define CE_MAXPER 16
@@ -366,7 +367,8 @@ __global__ __launch_bounds__(256) void k_video_cast(const float* __restrict__ sr
 // H x W with bilinear sampling (align_corners = False, no antialias), horizontal flip, x / 255, (x - mean) / std — the chain
 // x/255 -> RandomHorizontalFlip -> RandomResizedCrop | CenterCrop -> Normalize of reference LRW/video/src/data.py:150,157-171
 // in one pass; the random decisions are made on the host and arrive as params [B][5] = {top, left, h, w, flip}.
-// A window of exactly H x W is a plain crop (the sampling weights degenerate to 1 / 0).
+// A window of exactly H x W is a plain crop (the sampling weights degenerate to 1 / 0).  The sampling itself is csrc/clip_sample.h, shared
+// with the LRW pipeline kernels (csrc/lrw_prep.hip) so that all of them give a pixel the same bits.
 // ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_clip_prep(const unsigned char* __restrict__ src, const int* __restrict__ params,
                                                    float* __restrict__ dst, int B, int T, int Hs, int Ws, int H, int W, float mean,
@@ -378,28 +380,9 @@ __global__ __launch_bounds__(256) void k_clip_prep(const unsigned char* __restri
         const int y = (int)(r % H);
         r /= H;
         const int t = (int)(r % T), b = (int)(r / T);
-        int top = params[b * 5 + 0], left = params[b * 5 + 1], ch = params[b * 5 + 2], cw = params[b * 5 + 3];
-        const int flip = params[b * 5 + 4];
-        // the window is clamped into the stored frame: no read outside it whatever the host drew
-        top = top < 0 ? 0 : (top > Hs - 1 ? Hs - 1 : top);
-        left = left < 0 ? 0 : (left > Ws - 1 ? Ws - 1 : left);
-        ch = ch < 1 ? 1 : (ch > Hs - top ? Hs - top : ch);
-        cw = cw < 1 ? 1 : (cw > Ws - left ? Ws - left : cw);
-        const int xo = flip ? W - 1 - x : x;
-        // source coordinates inside the window (pixel centres), clamped to the window like torch's upsample_bilinear2d
-        float fy = ((float)y + 0.5f) * ((float)ch / (float)H) - 0.5f;
-        float fx = ((float)xo + 0.5f) * ((float)cw / (float)W) - 0.5f;
-        fy = fmaxf(fy, 0.f); fx = fmaxf(fx, 0.f);
-        int y0 = (int)fy, x0 = (int)fx;
-        if (y0 > ch - 1) y0 = ch - 1;
-        if (x0 > cw - 1) x0 = cw - 1;
-        const int y1 = y0 + 1 < ch ? y0 + 1 : ch - 1, x1 = x0 + 1 < cw ? x0 + 1 : cw - 1;
-        const float wy = fy - (float)y0, wx = fx - (float)x0;
+        const ClipWindow w = clip_window(params, b, Hs, Ws);
         const unsigned char* f = src + ((long)b * T + t) * Hs * Ws;
-        const float v00 = f[(top + y0) * Ws + left + x0], v01 = f[(top + y0) * Ws + left + x1];
-        const float v10 = f[(top + y1) * Ws + left + x0], v11 = f[(top + y1) * Ws + left + x1];
-        const float v = (1.f - wy) * ((1.f - wx) * v00 + wx * v01) + wy * ((1.f - wx) * v10 + wx * v11);
-        dst[idx] = (v * (1.0f / 255.0f) - mean) * inv_std;
+        dst[idx] = clip_normalize(clip_sample(f, w, Ws, y, x, H, W), mean, inv_std);
     }
 }
 

@@ -1538,6 +1538,61 @@ def lrs_clip_prep(src_u8: torch.Tensor, off: torch.Tensor, params: torch.Tensor,
     return out
 
 
+LRW_CLIP_MAX_FRAMES = 256          # LW_MAXT of csrc/lrw_prep.hip
+
+
+def _lrw_clip_check(frames_u8: torch.Tensor, params: torch.Tensor, H: int, W: int) -> tuple[int, int, int, int]:
+    """The argument errors the two LRW clip kernels share, raised before any launch."""
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or not frames_u8.is_contiguous():
+        raise ValueError("frames_u8 must be a contiguous uint8 tensor [B, T, Hs, Ws]")
+    B, T, Hs, Ws = frames_u8.shape
+    if params.dtype != torch.int32 or params.shape != (B, 5) or not params.is_contiguous():
+        raise ValueError(f"params must be a contiguous int32 tensor [B, 5] = {(B, 5)}")
+    if T > LRW_CLIP_MAX_FRAMES:
+        raise ValueError(f"clips of {T} frames: the LRW clip kernels take at most {LRW_CLIP_MAX_FRAMES}")
+    if B < 1 or T < 1 or min(Hs, Ws, int(H), int(W)) < 1:
+        raise ValueError("empty batch, clip or frame")
+    return B, T, Hs, Ws
+
+
+def lrw_clip_sums(frames_u8: torch.Tensor, params: torch.Tensor, H: int, W: int, max_blocks: int = 0) -> torch.Tensor:
+    """uint8 clips [B, T, Hs, Ws] + int32 params [B, 5] = (top, left, h, w, flip) -> fp32 [B, T]: the sum over each frame of what clip_prep
+    samples in front of Normalize (svsr_lrw_clip_sums; a fixed reduction order, independent of the grid).  max_blocks > 0: a grid cap for
+    tests (the result does not depend on it)."""
+    B, T, Hs, Ws = _lrw_clip_check(frames_u8, params, H, W)
+    out = torch.empty((B, T), dtype=torch.float32, device=frames_u8.device)
+    _call("svsr_lrw_clip_sums", _p(frames_u8), _p(params), _p(out), B, T, Hs, Ws, int(H), int(W), int(max_blocks), _stream(),
+          label="k_lrw_clip_sums", nbytes=float(frames_u8.numel() + 4 * out.numel()))
+    return out
+
+
+def lrw_clip_mix(frames_u8: torch.Tensor, params: torch.Tensor, frame_src: torch.Tensor, H: int, W: int, runs: Optional[torch.Tensor] = None,
+                 frame_sums: Optional[torch.Tensor] = None, replace_with_zero: bool = False, mean: float = 0.421, std: float = 0.165,
+                 max_blocks: int = 0) -> torch.Tensor:
+    """uint8 clips [B, T, Hs, Ws] + int32 params [B, 5] + int32 frame_src [B, T] (augment.make_plan's map) -> fp32 [B, 1, T, H, W]
+    (svsr_lrw_clip_mix): out[b, 0, t] is frame t of clip s = frame_src[b, t] with clip s's crop, flip and time mask, normalised.  runs: int32
+    [B, n_mask, 2] = (start, length) per clip in TimeMask's order, or None; a masked frame is the clip's mean as masked so far, derived from
+    frame_sums = lrw_clip_sums(...) (or 0 with replace_with_zero, which needs no sums).  max_blocks as in lrw_clip_sums."""
+    B, T, Hs, Ws = _lrw_clip_check(frames_u8, params, H, W)
+    if frame_src.dtype != torch.int32 or frame_src.shape != (B, T) or not frame_src.is_contiguous():
+        raise ValueError(f"frame_src must be a contiguous int32 tensor [B, T] = {(B, T)}")
+    n_mask = 0
+    if runs is not None:
+        if runs.dtype != torch.int32 or runs.dim() != 3 or runs.shape[0] != B or runs.shape[2] != 2 or not runs.is_contiguous():
+            raise ValueError("runs must be a contiguous int32 tensor [B, n_mask, 2]")
+        n_mask = runs.shape[1]
+    if n_mask > 0 and not replace_with_zero:
+        if frame_sums is None:
+            raise ValueError("mean-filled runs need frame_sums (ops.lrw_clip_sums)")
+        if frame_sums.dtype != torch.float32 or frame_sums.shape != (B, T) or not frame_sums.is_contiguous():
+            raise ValueError(f"frame_sums must be a contiguous fp32 tensor [B, T] = {(B, T)}")
+    out = torch.empty((B, 1, T, H, W), dtype=torch.float32, device=frames_u8.device)
+    _call("svsr_lrw_clip_mix", _p(frames_u8), _p(params), _p(frame_src), _p(runs) if n_mask else None, _p(frame_sums) if n_mask else None, _p(out),
+          B, T, Hs, Ws, int(H), int(W), n_mask, int(bool(replace_with_zero)), float(mean), float(std), int(max_blocks), _stream(),
+          label="k_lrw_clip_mix", nbytes=float(frames_u8.numel() + 4 * out.numel()))
+    return out
+
+
 def wave_prep(wave: torch.Tensor, lengths: torch.Tensor, noise: Optional[torch.Tensor] = None, nstart: Optional[torch.Tensor] = None,
               snr_db: Optional[torch.Tensor] = None, eps: float = 1e-8, max_blocks: int = 0) -> torch.Tensor:
     """wave fp32 or int16 [B, Spad] (int16 counts as v / 32768), lengths int32 [B] -> fp32 [B, Spad]: per clip over its real samples,
