@@ -576,10 +576,13 @@ int svsr_glu_dwconv_bwd_parts(const void* dc, const void* u, const float* w, voi
 
 /* CTC loss as the reference calls it (ctc.py:44-74,83-151): log_softmax over V, torch.nn.CTCLoss(reduction="sum",
  * zero_infinity=True), blank 0, divided by the batch size.  logits fp32 [B*T][ld]; labels int64 [B][Lmax] padded with -1
- * at the tail; ilen int32 [B].  Workspaces: lse [B*T], ab [B][T][2*Lmax+1], nll [B].  *loss = sum_b nll_b / B. */
+ * at the tail; ilen int32 [B].  Workspaces: lse [B*T], ab [B][T][2*Lmax+1], nll [B].  *loss = sum_b nll_b / B.
+ * ilen is not trusted: an item with ilen[b] < 1 or ilen[b] > T contributes 0 to the loss (B still divides), gets zero rows from
+ * svsr_ctc_grad, and no logit, lse or ab row is read or written for it. */
 int svsr_ctc_fwd(const float* logits, int ld, const int64_t* labels, int Lmax, const int* ilen, int B, int T, int V, float* lse, float* ab, float* nll, float* loss, hipStream_t stream);
 
-/* dlogits [B*T][ldo] bf16 = gout/B * (softmax - label occupancy) for t < ilen[b], 0 elsewhere (and for infeasible targets). */
+/* dlogits [B*T][ldo] bf16 = gout/B * (softmax - label occupancy) for t < ilen[b], 0 elsewhere (and for infeasible targets and
+ * items whose ilen[b] is outside [1, T]); all ldo columns of every row are written (columns V.. with 0). */
 int svsr_ctc_grad(const float* logits, int ld, const int64_t* labels, int Lmax, const int* ilen, int B, int T, int V, const float* lse, const float* ab, const float* nll, const float* gout, void* dlogits, int ldo, hipStream_t stream);
 
 /* CTC prefix scores of beam-search extensions (espnet/nets/ctc_prefix_score.py:11-165 `CTCPrefixScoreTH.__call__`, driven by

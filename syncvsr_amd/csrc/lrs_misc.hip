@@ -226,6 +226,9 @@ __global__ __launch_bounds__(256) void k_row_lse(const float* __restrict__ z, in
 // ---------------------------------------------------------------------------------------------------------------------
 // CTC: one block per batch item walks the lattice (alpha forward, beta backward) in log space.
 // ext[s] = blank for even s, y[s/2] for odd s;  S = 2*len+1.  ab [B][T][Smax] workspace: alpha, then posterior occupancy.
+// An item whose ilen[b] is outside [1, T] is no item (torch.nn.CTCLoss gives 0 for ilen = 0 under zero_infinity and refuses ilen > T): its nll
+// is 0, its gradient rows are zeros, and neither kernel reads or writes a logit, lse or ab row for it — frame 0 of an empty item is not its own,
+// and frames past T belong to the next item or to nobody.
 // ---------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float lae(float a, float b) {       // log(exp(a) + exp(b)) with -inf handling
     if (a == -INFINITY) return b;
@@ -250,6 +253,10 @@ __global__ __launch_bounds__(256) void k_ctc_lattice(const float* __restrict__ z
     }
     __syncthreads();
     const int len = s_len, S = 2 * len + 1, Tb = ilen[b];
+    if (Tb < 1 || Tb > T) {                              // (the whole workgroup: nothing below is reached)
+        if (tid == 0) nll_out[b] = 0.f;
+        return;
+    }
     for (int s = tid; s < Smax; s += 256) ext[s] = (s & 1) && s < S ? (int)labels[(long)b * Lmax + (s >> 1)] : 0;
     __syncthreads();
     const float* zb = z + (long)b * T * ld;
@@ -313,7 +320,7 @@ __global__ __launch_bounds__(256) void k_ctc_lattice(const float* __restrict__ z
     }
 }
 
-// dlogits[b,t,v] = g/B * (softmax[v] - sum_{s: ext s = v} occ[t][s]) for t < ilen[b] (and a feasible target), else 0
+// dlogits[b,t,v] = g/B * (softmax[v] - sum_{s: ext s = v} occ[t][s]) for t < ilen[b] (a feasible target, 1 <= ilen[b] <= T), else 0
 __global__ __launch_bounds__(256) void k_ctc_grad(const float* __restrict__ z, int ld, const float* __restrict__ lse,
                                                   const long* __restrict__ labels, int Lmax, const int* __restrict__ ilen,
                                                   const float* __restrict__ ab, const float* __restrict__ nll, int B, int T, int V, int Smax,
@@ -321,7 +328,8 @@ __global__ __launch_bounds__(256) void k_ctc_grad(const float* __restrict__ z, i
     extern __shared__ float sAcc[];          // [V] occupancy per class, then [Smax] staged (class, occupancy) pairs
     const int row = blockIdx.x, b = row / T, t = row - b * T;
     bf16_t* o = dz + (long)row * ldo;
-    const bool live = t < ilen[b] && nll[b] != 0.f;
+    const int Tb = ilen[b];
+    const bool live = Tb >= 1 && Tb <= T && t < Tb && nll[b] != 0.f;
     if (!live) {
         for (int v = threadIdx.x; v < ldo; v += 256) o[v] = 0;
         return;
@@ -610,7 +618,9 @@ int svsr_glu_dwconv_bwd(const void* dc, const void* u, const float* w, void* du,
 }
 
 /* logits fp32 [B*T][ld]; labels int64 [B][Lmax] padded with -1; ilen int32 [B]; ab workspace fp32 [B][T][2*Lmax+1];
- * lse [B*T], nll [B] scratch; *loss = sum_b nll_b / B (fixed order).  Then svsr_ctc_grad writes dlogits (bf16, pitch ldo). */
+ * lse [B*T], nll [B] scratch; *loss = sum_b nll_b / B (fixed order).  Then svsr_ctc_grad writes dlogits (bf16, pitch ldo).
+ * Any ilen is safe: an item with ilen[b] < 1 or ilen[b] > T adds 0 to the loss (it still counts in B), gets zero gradient rows and
+ * touches no memory outside its own rows. */
 int svsr_ctc_fwd(const float* logits, int ld, const int64_t* labels, int Lmax, const int* ilen, int B, int T, int V, float* lse,
                  float* ab, float* nll, float* loss, hipStream_t stream) {
     if (Lmax < 1 || T < 1 || V < 2) return SVSR_ERR_ARG;

@@ -1709,9 +1709,10 @@ def mha_bwd(dctx, q, q_pitch: int, k, v, kv_pitch: int, probs, *, B: int, H: int
     return dq_ac, dq_bd, dpe
 
 
-def glu_dwconv_fwd(u, w, bias, want_stats: bool, B: int, T: int, D: int, K: int):
-    """-> (c [B*T, D] bf16, BatchNorm1d partials (buffer, rows) or None)"""
-    c = torch.empty((B * T, D), dtype=BF16, device=u.device)
+def glu_dwconv_fwd(u, w, bias, want_stats: bool, B: int, T: int, D: int, K: int, out: Optional[torch.Tensor] = None):
+    """-> (c [B*T, D] bf16, BatchNorm1d partials (buffer, rows) or None); out: a contiguous [B*T, D] bf16 buffer of the caller's for c"""
+    c = torch.empty((B * T, D), dtype=BF16, device=u.device) if out is None else out
+    assert c.shape == (B * T, D) and c.dtype == BF16 and c.is_contiguous()
     stats = st = None
     if want_stats:
         rows = _query("svsr_glu_dwconv_fwd_stat_rows", B, T)[0]
@@ -1724,10 +1725,12 @@ def glu_dwconv_fwd(u, w, bias, want_stats: bool, B: int, T: int, D: int, K: int)
 DW_SPLITS = 96        # workgroups per 64-channel block of svsr_glu_dwconv_bwd: one (clip, 32-frame tile) each at B = 16, T <= 192 (16 splits left a quarter of the CUs idle with several tiles in a row each)
 
 
-def glu_dwconv_bwd(dc, u, w, dw, dbias, B: int, T: int, D: int, K: int, reduce_later: bool = False):
+def glu_dwconv_bwd(dc, u, w, dw, dbias, B: int, T: int, D: int, K: int, reduce_later: bool = False, out: Optional[torch.Tensor] = None):
     """-> du; reduce_later: -> (du, (fn, keep)) — fn() issues the fixed-order sum of the partial rows into dw / dbias on the stream current when
-    it is called (parameter gradients: the model hands fn to its side stream), keep = the partial rows."""
-    du = torch.empty_like(u)
+    it is called (parameter gradients: the model hands fn to its side stream), keep = the partial rows.  out: a contiguous [B*T, 2D] bf16
+    buffer of the caller's for du."""
+    du = torch.empty_like(u) if out is None else out
+    assert du.shape == (B * T, 2 * D) and du.dtype == BF16 and du.is_contiguous()
     part = torch.empty(DW_SPLITS * D * (K + 1), dtype=torch.float32, device=u.device)
 
     def launch(parts: int) -> None:
@@ -1772,9 +1775,11 @@ def ctc_fwd(logits, ld: int, labels, ilen, B: int, T: int, V: int):
     return loss, (lse, ab, nll)
 
 
-def ctc_grad(logits, ld: int, labels, ilen, B: int, T: int, V: int, state, gout, ldo: int) -> torch.Tensor:
+def ctc_grad(logits, ld: int, labels, ilen, B: int, T: int, V: int, state, gout, ldo: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """-> dlogits [B*T, ldo] bf16 (every column written, V.. with zeros); out: a contiguous buffer of the caller's for it"""
     lse, ab, nll = state
-    dz = torch.empty((B * T, ldo), dtype=BF16, device=logits.device)
+    dz = torch.empty((B * T, ldo), dtype=BF16, device=logits.device) if out is None else out
+    assert dz.shape == (B * T, ldo) and dz.dtype == BF16 and dz.is_contiguous()
     _call("svsr_ctc_grad", _p(logits), ld, _p(labels), labels.shape[1], _p(ilen), B, T, V, _p(lse), _p(ab), _p(nll), _p(gout), _p(dz), ldo,
           _stream())
     return dz
@@ -1818,8 +1823,11 @@ def ls_loss_fwd(logits, ld: int, target, R: int, V: int, smoothing: float, inv_d
     return loss, lse, counts
 
 
-def ls_loss_bwd(logits, ld: int, target, R: int, V: int, smoothing: float, inv_denom: float, lse, gout, ldo: int) -> torch.Tensor:
-    dz = torch.empty((R, ldo), dtype=BF16, device=logits.device)
+def ls_loss_bwd(logits, ld: int, target, R: int, V: int, smoothing: float, inv_denom: float, lse, gout, ldo: int,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """-> dlogits [R, ldo] bf16 (every column written, V.. with zeros); out: a contiguous buffer of the caller's for it"""
+    dz = torch.empty((R, ldo), dtype=BF16, device=logits.device) if out is None else out
+    assert dz.shape == (R, ldo) and dz.dtype == BF16 and dz.is_contiguous()
     _call("svsr_ls_loss_bwd", _p(logits), ld, _p(target), R, V, float(smoothing), float(inv_denom), _p(lse), _p(gout), _p(dz), ldo, _stream())
     return dz
 
