@@ -202,7 +202,9 @@ int svsr_conv3x3_wgrad_v2(const void* x, const void* dy, float* dw, int Nimg, in
 /* ---- 3-D stem (stem.hip) --------------------------------------------------------------------------------------
  * svsr_stem_conv_fwd replaces stem3d[0] = nn.Conv3d(1,64,(5,7,7),(1,2,2),(2,3,3),bias=False) (lightning.py:50).
  * vid fp32 [B][1][T][H][W]; w fp32 [64][1][5][7][7]; out bf16 [B*T][H/2][W/2][64]; stats [rows][2][64] with rows =
- * svsr_stem_conv_fwd_stat_rows(B, T, H, W). */
+ * svsr_stem_conv_fwd_stat_rows(B, T, H, W).  H and W even and >= 8.  ws: svsr_stem_conv_fwd_ws_bytes(B, T, H, W) bytes (non-zero where
+ * W % 8 == 0) for the DMA-fed kernel; NULL or too small: the direct kernel, at any even W.  A shape whose tile does not fit the LDS of
+ * the kernel chosen (W >= 1394 direct, W >= 1392 DMA-fed) returns SVSR_ERR_ARG before anything is launched. */
 int svsr_stem_conv_fwd_stat_rows(int B, int T, int H, int W);
 int64_t svsr_stem_conv_fwd_ws_bytes(int B, int T, int H, int W);
 int svsr_stem_conv_fwd(const float* vid, const float* w, void* out, float* stats, int B, int T, int H, int W, void* ws, int64_t ws_bytes, hipStream_t stream);
@@ -216,7 +218,7 @@ int svsr_stem_conv_wgrad(const float* vid, const void* dy, float* dw, int B, int
  * stem3d[0].weight): the gradient of the convolution output is made tile by tile in LDS and contracted at once, never written.  Call
  * svsr_stem_bn_act_pool_bwd first with dx = NULL and xwin / gpool given (it then runs its reduce pass and the finalisation only and
  * leaves gpool and coef); x = the convolution output, amax / mean / rstd as there.  dw bit-identical to the two-launch form.
- * svsr_stem_bwd_wgrad_ok: 1 when the shape is covered (else use the two launches). */
+ * svsr_stem_bwd_wgrad_ok: 1 when the shape is covered (W % 4 == 0 and W <= 96; else use the two launches). */
 int svsr_stem_bwd_wgrad_ok(int B, int T, int H, int W);
 int svsr_stem_bwd_wgrad(const float* vid, const void* gpool, const void* amax, const void* x, const float* mean, const float* rstd, const float* coef, float* dw, int B, int T, int H, int W, float* part, int64_t part_floats, hipStream_t stream);
 
@@ -242,7 +244,8 @@ int svsr_bn_act_bwd(const void* dy, const void* y, const void* x, const float* m
 
 /* stem3d[1..3]: BatchNorm3d -> activation -> MaxPool3d((1,3,3),(1,2,2),(0,1,1)) fused; act 1 = exact nn.GELU()
  * (LRW lightning.py:51-53), act 2 = Swish (LRS backbones/conv3d_extractor.py:30-36).
- * x [N][Hc][Wc][C] -> y [N][Hp][Wp][C], amax uint8 [N][Hp][Wp][C] = window-local argmax (first max wins). */
+ * x [N][Hc][Wc][C] -> y [N][Hp][Wp][C], amax uint8 [N][Hp][Wp][C] = window-local argmax (first max wins).
+ * Hp = (Hc - 1) / 2 + 1 and Wp = (Wc - 1) / 2 + 1: anything else is SVSR_ERR_ARG, in the forward and in every form of the backward. */
 int svsr_stem_bn_act_pool_fwd(const void* x, void* y, void* amax, const float* mean, const float* rstd, const float* gamma, const float* beta, int N, int Hc, int Wc, int Hp, int Wp, int C, int act, void* xwin, hipStream_t stream);
 
 /* backward of the fused stem pass: dx = gradient of the stem conv output; slots: workspace of

@@ -796,6 +796,7 @@ int svsr_bn_bwd_from_stats(const void* g, const void* x, const float* mean, cons
 int svsr_stem_bn_act_pool_fwd(const void* x, void* y, void* amax, const float* mean, const float* rstd, const float* gamma,
                               const float* beta, int N, int Hc, int Wc, int Hp, int Wp, int C, int act, void* xwin, hipStream_t stream) {
     if (!chan_ok(C) || (act != SVSR_ACT_GELU && act != SVSR_ACT_SWISH)) return SVSR_ERR_ARG;
+    if (N < 1 || Hc < 1 || Wc < 1 || Hp != (Hc - 1) / 2 + 1 || Wp != (Wc - 1) / 2 + 1) return SVSR_ERR_ARG;      // the kernels index with both sizes
     StemRowIter it;
     if (!stem_iter(it, C, Wp, Hp)) return SVSR_ERR_ARG;
     const dim3 grid((Hp + it.rpb - 1) / it.rpb, N);
@@ -827,6 +828,7 @@ int svsr_stem_bn_act_pool_bwd(const void* dpool, const void* amax, const void* x
                               const float* gamma, const float* beta, float* slots, float* coef, float* dgamma, float* dbeta,
                               void* dx, int N, int Hc, int Wc, int Hp, int Wp, int C, int act, const void* xwin, void* gpool, hipStream_t stream) {
     if (!chan_ok(C) || (act != SVSR_ACT_GELU && act != SVSR_ACT_SWISH)) return SVSR_ERR_ARG;
+    if (N < 1 || Hc < 1 || Wc < 1 || Hp != (Hc - 1) / 2 + 1 || Wp != (Wc - 1) / 2 + 1) return SVSR_ERR_ARG;      // every form, not the gather forms alone
     StemRowIter it;
     if (!stem_iter(it, C, Wc, Hc)) return SVSR_ERR_ARG;
     const size_t lds_b = (size_t)(STEM_BR / 2 + 1) * Wp * C * 3;

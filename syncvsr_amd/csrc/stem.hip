@@ -895,9 +895,9 @@ int svsr_stem_conv_fwd(const float* vid, const float* w, void* out, float* stats
         bf16_t* wpack = vid16 + (int64_t)B * T * H * (W + 8);
         const long rows = (long)B * T * H;
         const int vid_blocks = (int)((rows * ((W + 8) / 8) + 255) / 256), w_blocks = (STEM_C * STEM_WPITCH + 255) / 256;
-        hipLaunchKernelGGL(k_stem_prep, dim3(vid_blocks + w_blocks), dim3(256), 0, stream, vid, w, vid16, wpack, rows, W, vid_blocks);
         const size_t lds_d = (size_t)STEM_W_CHUNKS * 16 + ((size_t)5 * a.rows_in_max * ((W + 8) / 8) + 63) / 64 * 64 * 16;
-        if (lds_d > 160 * 1024) return SVSR_ERR_ARG;
+        if (lds_d > 160 * 1024) return SVSR_ERR_ARG;      // (before the prep launch: a refusal launches nothing)
+        hipLaunchKernelGGL(k_stem_prep, dim3(vid_blocks + w_blocks), dim3(256), 0, stream, vid, w, vid16, wpack, rows, W, vid_blocks);
         static size_t lds_dma = 0;
         if (lds_d > lds_dma) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_stem_conv_fwd_dma), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_d);
@@ -993,18 +993,19 @@ int svsr_stem_bwd_wgrad(const float* vid, const void* gpool, const void* amax, c
     if (part == nullptr || part_floats < (int64_t)grid * STEM_C * 245) return SVSR_ERR_ARG;
     a.vid = vid; a.x = (const bf16_t*)x; a.gpool = (const bf16_t*)gpool; a.amax = (const unsigned char*)amax;
     a.mean = mean; a.rstd = rstd; a.coef = coef; a.part = part;
-    // prefetch-register variants: 88-wide clips need 6 + 6 pieces per thread, the general form holds 8 + 8
-    const int v = (SW_RB * a.WoP * 8 <= 6 * 256) ? ((5 * (2 * SW_RB + 5) * (W / 4) <= 6 * 256) ? 0 : 1) : 2;
-    const void* fn = v == 0 ? reinterpret_cast<const void*>(k_stem_bwd_wgrad<6, 6>)
-                   : v == 1 ? reinterpret_cast<const void*>(k_stem_bwd_wgrad<6, 8>) : reinterpret_cast<const void*>(k_stem_bwd_wgrad<8, 8>);
-    static size_t lds_set[3] = {0, 0, 0};
+    // prefetch-register variants: 88-wide clips need 6 + 6 pieces per thread, W = 96 needs 8 pieces of input rows.  The accepted shapes
+    // (PW / 2 <= 32, so WoP <= 48) never hold more than 6 pieces of the x tile: an <8, 8> form was unreachable and is gone
+    // (tests/test_stem_restatement_cpu.py enumerates the shapes)
+    if (SW_RB * a.WoP * 8 > 6 * 256) return SVSR_ERR_ARG;
+    const int v = (5 * (2 * SW_RB + 5) * (W / 4) <= 6 * 256) ? 0 : 1;
+    const void* fn = v == 0 ? reinterpret_cast<const void*>(k_stem_bwd_wgrad<6, 6>) : reinterpret_cast<const void*>(k_stem_bwd_wgrad<6, 8>);
+    static size_t lds_set[2] = {0, 0};
     if (lds > lds_set[v]) {
         (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         lds_set[v] = lds;
     }
     if (v == 0) hipLaunchKernelGGL((k_stem_bwd_wgrad<6, 6>), dim3(grid), dim3(256), lds, stream, a);
-    else if (v == 1) hipLaunchKernelGGL((k_stem_bwd_wgrad<6, 8>), dim3(grid), dim3(256), lds, stream, a);
-    else hipLaunchKernelGGL((k_stem_bwd_wgrad<8, 8>), dim3(grid), dim3(256), lds, stream, a);
+    else hipLaunchKernelGGL((k_stem_bwd_wgrad<6, 8>), dim3(grid), dim3(256), lds, stream, a);
     const int rc = svsr_check_launch();
     if (rc != SVSR_OK) return rc;
     return svsr_colsum_rows(part, grid, STEM_C * 245, dw, STEM_C * 245, nullptr, 0, 1, 1.0f, stream);

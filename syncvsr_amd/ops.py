@@ -1019,17 +1019,20 @@ def linear_wgrad(x: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor, *, rows: i
 _STEM_WS: dict = {}
 
 
-def stem_conv_fwd(videos: torch.Tensor, w: torch.Tensor, want_stats: bool = False):
-    """-> (out [B*T,H/2,W/2,64] bf16, BatchNorm partials (buffer, rows) or None)"""
+def stem_conv_fwd(videos: torch.Tensor, w: torch.Tensor, want_stats: bool = False, use_ws: bool = True, out: Optional[torch.Tensor] = None):
+    """-> (out [B*T,H/2,W/2,64] bf16, BatchNorm partials (buffer, rows) or None).  use_ws=False withholds the workspace of the DMA-fed
+    kernel: the direct kernel then runs at any W (what a C-ABI caller without a workspace gets).  out: a contiguous tensor to write into."""
     B, C, T, H, W = videos.shape
     assert C == 1 and videos.dtype == torch.float32 and videos.is_contiguous()
-    out = torch.empty((B * T, H // 2, W // 2, 64), dtype=BF16, device=videos.device)
+    if out is None:
+        out = torch.empty((B * T, H // 2, W // 2, 64), dtype=BF16, device=videos.device)
+    assert out.shape == (B * T, H // 2, W // 2, 64) and out.dtype == BF16 and out.is_contiguous()
     stats = st = None
     if want_stats:
         rows = _query("svsr_stem_conv_fwd_stat_rows", B, T, H, W)[0]
         stats = scratch(rows * 2 * 64)
         st = (stats, rows)
-    nws = _query("svsr_stem_conv_fwd_ws_bytes", B, T, H, W)[0]
+    nws = _query("svsr_stem_conv_fwd_ws_bytes", B, T, H, W)[0] if use_ws else 0
     ws = None
     if nws:         # bf16 copy of the clip + packed weights for the DMA-fed kernel: one grow-only buffer per device and stream (`stats`
         key = (videos.device, _stream())        # lives in the shared scratch; variable-length LRS batches must not pile up one buffer per shape)
@@ -1053,25 +1056,29 @@ def stem_conv_wgrad(videos: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor, us
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_SWISH = 0, 1, 1, 2     # ReLU/GELU share code 1: ReLU in the BN passes, GELU in the stem pass
 
 
-def stem_bn_gelu_pool_fwd(x: torch.Tensor, mean, rstd, gamma, beta, act: int = ACT_GELU, want_win: bool = False):
+def stem_bn_gelu_pool_fwd(x: torch.Tensor, mean, rstd, gamma, beta, act: int = ACT_GELU, want_win: bool = False, out: Optional[torch.Tensor] = None):
     """-> (y, amax) or, with want_win, (y, amax, xwin): xwin = the convolution output at every window's arg-max, for
-    stem_bn_gelu_pool_bwd(xwin=...) (reduce pass over pooled-size tensors, apply pass without activation derivatives)."""
+    stem_bn_gelu_pool_bwd(xwin=...) (reduce pass over pooled-size tensors, apply pass without activation derivatives).
+    out: a contiguous tensor to write y into."""
     N, Hc, Wc, C = x.shape
     Hp, Wp = (Hc - 1) // 2 + 1, (Wc - 1) // 2 + 1
-    y = torch.empty((N, Hp, Wp, C), dtype=BF16, device=x.device)
+    y = torch.empty((N, Hp, Wp, C), dtype=BF16, device=x.device) if out is None else out
+    assert y.shape == (N, Hp, Wp, C) and y.dtype == BF16 and y.is_contiguous()
     amax = torch.empty((N, Hp, Wp, C), dtype=torch.uint8, device=x.device)
     xwin = torch.empty((N, Hp, Wp, C), dtype=BF16, device=x.device) if want_win else None
     _call("svsr_stem_bn_act_pool_fwd", _p(x), _p(y), _p(amax), _p(mean), _p(rstd), _p(gamma), _p(beta), N, Hc, Wc, Hp, Wp, C, act, _p(xwin), _stream())
     return (y, amax, xwin) if want_win else (y, amax)
 
 
-def stem_bn_gelu_pool_bwd(dpool, amax, x, mean, rstd, gamma, beta, coef, dgamma, dbeta, act: int = ACT_GELU, xwin=None, want_dx: bool = True):
+def stem_bn_gelu_pool_bwd(dpool, amax, x, mean, rstd, gamma, beta, coef, dgamma, dbeta, act: int = ACT_GELU, xwin=None, want_dx: bool = True,
+                          out: Optional[torch.Tensor] = None):
     """-> dx (gradient of the stem convolution's output); with want_dx=False (needs xwin) -> gpool, and `coef` is left filled: the inputs of
-    stem_bwd_wgrad, which makes dx tile by tile inside the weight-gradient pass instead of writing it."""
+    stem_bwd_wgrad, which makes dx tile by tile inside the weight-gradient pass instead of writing it.  out: a contiguous tensor to write dx into."""
     N, Hc, Wc, C = x.shape
     _, Hp, Wp, _ = dpool.shape
     assert want_dx or xwin is not None
-    dx = torch.empty_like(x) if want_dx else None
+    dx = (torch.empty_like(x) if out is None else out) if want_dx else None
+    assert dx is None or (dx.shape == x.shape and dx.dtype == x.dtype and dx.is_contiguous())
     slots = scratch(_query("svsr_stem_bn_act_pool_bwd_rows", N, Hc, Wc, C)[0] * 2 * C)
     gpool = torch.empty_like(dpool) if xwin is not None else None
     _call("svsr_stem_bn_act_pool_bwd", _p(dpool), _p(amax), _p(x), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(slots), _p(coef),

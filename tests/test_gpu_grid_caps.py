@@ -44,7 +44,9 @@ svsr_colsum_rows / _multi (runtime)                  | ceil(n/CL) blocks, CL = 2
                                                      |   lanes walk the rows, no cap         |   and single-row tails        |   shape classes: tests/test_gpu_kernels.py::test_colsum_rows_multi_equals_separate_launches
 svsr_rmsnorm_bwd (xt)                                | ceil(R/16) blocks, ceil(R/32) from    | R >= 4096 (rows-per-block     | tests/test_gpu_xt.py::test_rmsnorm_forward_backward[513-576-4100]
                                                      |   R = 4096 on; rows walked in a loop  |   switch; no cap)             |
-persistent GEMM-class kernels (stem, conv3x3_c64,    | one workgroup per CU-slot, tile loop  | more tiles than workgroups    | tests/test_gpu_bench_shapes.py, tests/test_gpu_kernels.py (out of scope here:
+svsr_stem_conv_fwd, svsr_stem_conv_wgrad,            | ceil(Ho*Wo/128)*B*T tiles, cap 768;   | B*T > 768 one-tile frames;    | tests/test_gpu_stem_edges.py (5 x 157 frames of 12 x 8: 785 tiles, 1,570 row groups;
+  svsr_stem_bwd_wgrad (stem)                         |   ceil(Ho/4)*B*T row groups, cap 512  |   B*T*ceil(Ho/4) > 512        |   exact integer / impulse cases, every workgroup's partial row)
+persistent GEMM-class kernels (conv3x3_c64,          | one workgroup per CU-slot, tile loop  | more tiles than workgroups    | tests/test_gpu_bench_shapes.py, tests/test_gpu_kernels.py (out of scope here:
   wgrad3x3, igemm_p8)                                |                                       |                               |   the contraction kernels have their own shape tests)
 the other launches of xt and runtime; w2v_codec,     | ceil(n/block) or one block per item:  | -                             | nothing to cross
   audio_head, lrs_lm, lrs_search, dctcn, enc_fused,  |   no cap, no stride loop              |                               |
