@@ -145,10 +145,15 @@ int svsr_igemm_fwd(const void* in, const void* wt, void* out, void* out_pre, con
 int svsr_wgrad_plan(int Nimg, int H, int W, int Ci, int Co, int k, int stride, int pad, int* words, int cap_words, int* meta, int64_t* part_floats);
 int svsr_wgrad_rows_plan(int Nimg, int P, int src0, int dst0, int Ci, int Co, int has_bias, int* words, int cap_words, int* meta, int64_t* part_floats);
 int svsr_igemm_wgrad(const void* x, const void* dyp, float* dw, float* dbias, const int* plan_dev, const int* meta, int Nimg, int in_pix, int Ci, int in_pitch, int Co, int out_pix, int out_pitch, int wt_taps, float* part, int64_t part_floats, hipStream_t stream);
+/* svsr_wgrad_rows_plan_tile: svsr_wgrad_rows_plan with the tile edge given (bc = 64 or 128; anything else is -SVSR_ERR_ARG) and no K split:
+ * meta = {bc, ring depth (3 / 2), 1, all chunks, tasks, 1, P, 0}, *part_floats = 0.  For the problems of a grouped launch, which fills the
+ * chip with many problems at once and so needs neither the narrow tile nor the split that svsr_wgrad_rows_plan picks for one problem alone. */
+int svsr_wgrad_rows_plan_tile(int Nimg, int P, int src0, int dst0, int Ci, int Co, int has_bias, int bc, int* words, int cap_words, int* meta, int64_t* part_floats);
 /* svsr_igemm_wgrad_group: n independent svsr_igemm_wgrad problems in ONE launch — the weight gradients of the encoder's and the heads'
  * nn.Linear layers (reference lightning.py:82,92,107: 26 short contractions of a backward pass; as launches of their own each is 7-17 us
- * of latency for ~1 us of work).  Every problem must carry a plan without K split on 64-wide tiles (meta[0..2] = {64, 3, 1}); anything
- * else returns SVSR_ERR_ARG.  table_dev: caller-owned device buffer of >= svsr_igemm_wgrad_group_bytes(n) bytes.  Results are identical
+ * of latency for ~1 us of work).  Every problem must carry a plain plan without K split, and all problems of a launch the same tile:
+ * meta[0..2] = {64, 3, 1} or {128, 2, 1} (svsr_wgrad_rows_plan_tile); anything else — a mix of the two, a split or unit-list plan, n < 1,
+ * n > 256 — returns SVSR_ERR_ARG before anything is launched.  table_dev: caller-owned device buffer of >= svsr_igemm_wgrad_group_bytes(n) bytes.  Results are identical
  * to n separate svsr_igemm_wgrad calls (same workgroup code, one writer per element). */
 int64_t svsr_igemm_wgrad_group_bytes(int n);
 int svsr_igemm_wgrad_group(const svsr_wgrad_problem* problems, int n, void* table_dev, int64_t table_bytes, hipStream_t stream);

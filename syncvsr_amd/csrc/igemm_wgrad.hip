@@ -331,8 +331,11 @@ __global__ __launch_bounds__(256) void k_igemm_wgrad(const WgradArgs p) {
 
 // GROUPED launch: one grid over the tiles of several independent weight-gradient problems (the encoder's and the heads' linear layers:
 // 26 contractions of 15 K chunks each, 7-17 us apiece as launches of their own — latency, not work).  table[i] = the problem's arguments
-// and the first tile it owns; every workgroup finds its problem with a scan over the (wave-uniform) table and runs the ordinary body.
+// and the first tile it owns; every workgroup finds its problem with a binary search over the (wave-uniform) table and runs the ordinary body.
 // No K split inside a group (splits = 1: each tile adds its result to dW directly, one writer per element), so nothing needs a slab.
+// Two instantiations: <64,3>, the tile svsr_wgrad_rows_plan gives a short contraction on its own, and <128,2> for plans made with
+// svsr_wgrad_rows_plan_tile — a group that fills the chip by itself (all six encoder layers: 1,152 tiles of 128 x 128) stages half the
+// bytes per FLOP on the wide tile.  One launch runs one of them: a group is homogeneous in its tile.
 struct WgradGroupEntry { WgradArgs a; int tile_begin; int pad_; };
 
 // The table reaches the device as kernel arguments of a writer kernel (16 entries a launch), not as a host-to-device copy: a launch is
@@ -350,9 +353,13 @@ __global__ __launch_bounds__(256) void k_wgrad_group_table(const WgradGroupChunk
 template <int BC, int NS>
 __global__ __launch_bounds__(256) void k_igemm_wgrad_group(const WgradGroupEntry* __restrict__ table, int n) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    int idx = 0;
-    for (int i = 1; i < n; ++i)
-        if ((int)blockIdx.x >= table[i].tile_begin) idx = i;
+    // the last entry whose first tile is not above this workgroup's (tile_begin increases strictly: every problem owns >= 1 tile): a binary
+    // search, log2(n) dependent scalar loads where a scan over a 24-entry table was 24 in the prologue of a 15-chunk loop
+    int idx = 0, hi = n;
+    while (hi - idx > 1) {
+        const int mid = (idx + hi) >> 1;
+        if ((int)blockIdx.x >= table[mid].tile_begin) idx = mid; else hi = mid;
+    }
     const WgradArgs p = table[idx].a;
     const int task = (int)blockIdx.x - table[idx].tile_begin;
     const int co_tiles = (p.Co + BC - 1) / BC, ci_tiles = (p.Ci + BC - 1) / BC;
@@ -617,8 +624,9 @@ static WgradUnits wgrad_units(const std::vector<long>& tap_chunks, int co_tiles,
 // meta: {tile edge, ring depth, K splits, chunks per split, tasks, taps, max positions of a tap, 0}
 // format 2 (unit list; meta[7] > 0): {tile edge, ring depth, slab slots, units, tasks, taps, max positions, word offset of the unit table};
 // the task table {first slot, slots} x tasks follows the units.
+// force_bc (64 / 128; 0 = chosen here): the plain plan of that tile without K split, whatever the shape (svsr_wgrad_rows_plan_tile)
 static int wplan_emit(const std::vector<std::vector<int>>& taps_pos, const std::vector<int>& tws, int Nimg, int Co, int Ci, int wt_taps,
-                      int has_bias, int* words, int cap_words, int* meta, int64_t* part_floats) {
+                      int has_bias, int* words, int cap_words, int* meta, int64_t* part_floats, int force_bc = 0) {
     const int ntaps = (int)taps_pos.size();
     int nwords = WPLAN_HDR + ntaps * WPLAN_TAP_WORDS;
     const int pos_word0 = nwords;
@@ -627,9 +635,14 @@ static int wplan_emit(const std::vector<std::vector<int>>& taps_pos, const std::
     if (maxP < 1 || maxP > WG_MAXP || (long)Nimg * maxP >= (1L << 24)) return -SVSR_ERR_ARG;
     const bool im = wgrad_imgmajor(Nimg);
     const long chunks = im ? maxP * (long)((Nimg + 63) / 64) : ((long)Nimg * maxP + 63) / 64;
-    const WgradLaunch pl = wgrad_launch(chunks, Co, Ci, ntaps, wt_taps, has_bias != 0);
+    WgradLaunch pl = wgrad_launch(chunks, Co, Ci, ntaps, wt_taps, has_bias != 0);
+    if (force_bc != 0) {
+        pl.bc = force_bc; pl.ns = force_bc == 128 ? 2 : 3;
+        pl.tasks = ((Co + pl.bc - 1) / pl.bc) * ((Ci + pl.bc - 1) / pl.bc) * ntaps;
+        pl.splits = 1; pl.chunks_per_split = (int)chunks;
+    }
     // unit lists for the long contractions (the short ones — LRW's 960-row linears — have no K split to balance and ride the grouped launch)
-    const bool use_units = svsr_tune_get(SVSR_TUNE_WG_UNITS) != 0 && chunks > svsr_tune_get(SVSR_TUNE_WG_SHORT_K);
+    const bool use_units = force_bc == 0 && svsr_tune_get(SVSR_TUNE_WG_UNITS) != 0 && chunks > svsr_tune_get(SVSR_TUNE_WG_SHORT_K);
     WgradUnits wu;
     const int units_word0 = nwords;
     if (use_units) {
@@ -709,6 +722,19 @@ static int launch_wgrad_units(const WgradArgs& a, const int* plan_dev, const int
     return svsr_check_launch();
 }
 
+template <int BC, int NS>
+static int launch_wgrad_group(const WgradGroupEntry* table_dev, int n, int tiles, int maxP, hipStream_t stream) {
+    const size_t lds_max = (size_t)NS * 2 * 64 * BC * sizeof(bf16_t) + (size_t)WG_MAXP * 2 * sizeof(int);
+    static bool attr_set = false;          // (one per instantiation)
+    if (!attr_set) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_igemm_wgrad_group<BC, NS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
+        attr_set = true;
+    }
+    const size_t lds = (size_t)NS * 2 * 64 * BC * sizeof(bf16_t) + (((size_t)maxP * 2 * sizeof(int) + 127) & ~(size_t)127);
+    hipLaunchKernelGGL((k_igemm_wgrad_group<BC, NS>), dim3(tiles), dim3(256), lds, stream, table_dev, n);
+    return svsr_check_launch();
+}
+
 extern "C" {
 
 /* svsr_wgrad_plan (host): plan of the weight gradient of a k x k / stride / pad convolution over Nimg images [H][W] -> [Ho][Wo]
@@ -746,6 +772,17 @@ int svsr_wgrad_rows_plan(int Nimg, int P, int src0, int dst0, int Ci, int Co, in
     std::vector<std::vector<int>> tp(1);
     for (int j = 0; j < P; ++j) { tp[0].push_back(src0 + j); tp[0].push_back(dst0 + j); }
     return wplan_emit(tp, std::vector<int>{0}, Nimg, Co, Ci, 1, has_bias, words, cap_words, meta, part_floats);
+}
+
+/* svsr_wgrad_rows_plan_tile (host): the same rows with the tile edge given (bc = 64 or 128) and no K split — the ordinary words and meta
+ * {bc, ring depth, 1, all chunks, tasks, 1, P, 0} of wg_body<64,3> / wg_body<128,2>, for a caller that fills the chip with MANY problems
+ * (svsr_igemm_wgrad_group_v2) and so needs neither the narrow tile nor the split svsr_wgrad_rows_plan picks for one problem alone. */
+int svsr_wgrad_rows_plan_tile(int Nimg, int P, int src0, int dst0, int Ci, int Co, int has_bias, int bc, int* words, int cap_words, int* meta,
+                              int64_t* part_floats) {
+    if (Nimg < 1 || P < 1 || Ci < 1 || Co < 1 || (bc != 64 && bc != 128)) return -SVSR_ERR_ARG;
+    std::vector<std::vector<int>> tp(1);
+    for (int j = 0; j < P; ++j) { tp[0].push_back(src0 + j); tp[0].push_back(dst0 + j); }
+    return wplan_emit(tp, std::vector<int>{0}, Nimg, Co, Ci, 1, has_bias, words, cap_words, meta, part_floats, bc);
 }
 
 int svsr_colsum_rows(const float* ws, int nrows, int64_t ld, float* out0, int64_t n0, float* out1, int64_t n1, int accumulate, float scale,
@@ -791,8 +828,9 @@ int svsr_igemm_wgrad_v2(const void* x, const void* dyp, float* dw, float* dbias,
 }
 
 /* svsr_igemm_wgrad_group: n independent svsr_igemm_wgrad problems (each described like a call of its own: plan_dev + meta of
- * svsr_wgrad_*plan) in ONE launch.  Every problem must have a plan without K split on 64-wide tiles (meta = {64, 3, 1, ...}: the short
- * contractions this exists for) — anything else returns SVSR_ERR_ARG and the caller launches it alone.  table_dev: caller-owned device
+ * svsr_wgrad_*plan) in ONE launch.  Every problem must have a plain plan without K split, and all of them the same tile: meta = {64, 3, 1, ...}
+ * (what svsr_wgrad_rows_plan gives the short contractions this exists for) or {128, 2, 1, ...} (svsr_wgrad_rows_plan_tile) — anything else,
+ * a mix of the two included, returns SVSR_ERR_ARG before anything is launched.  table_dev: caller-owned device
  * buffer of at least svsr_igemm_wgrad_group_bytes(n) bytes (the problem table is written there on `stream`, by a kernel that carries it as arguments, ahead of the contraction: graph- and replay-safe). */
 int64_t svsr_igemm_wgrad_group_bytes(int n) { return n < 1 ? 0 : (int64_t)n * (int64_t)sizeof(WgradGroupEntry); }
 
@@ -810,7 +848,8 @@ int svsr_igemm_wgrad_group_v2(const svsr_wgrad_problem* problems, const int* mod
         if (q.plan_dev == nullptr || q.meta == nullptr || q.Ci < 1 || q.Co < 1 || q.in_pitch % 8 != 0 || q.out_pitch % 8 != 0 || q.Ci % 8 != 0 || q.Nimg < 1 ||
             q.x == nullptr || q.dy == nullptr || q.dw == nullptr)
             return SVSR_ERR_ARG;
-        if (q.meta[0] != 64 || q.meta[1] != 3 || q.meta[2] != 1) return SVSR_ERR_ARG;
+        const bool wide = q.meta[0] == 128 && q.meta[1] == 2;
+        if ((!wide && (q.meta[0] != 64 || q.meta[1] != 3)) || q.meta[2] != 1 || q.meta[7] != 0 || q.meta[0] != problems[0].meta[0]) return SVSR_ERR_ARG;
         WgradArgs& a = tab[i].a;
         a.x = (const bf16_t*)q.x; a.dy = (const bf16_t*)q.dy; a.dw = q.dw; a.db = q.dbias; a.part = nullptr; a.plan = q.plan_dev;
         a.splits = 1; a.chunks_per_split = q.meta[3];
@@ -830,16 +869,8 @@ int svsr_igemm_wgrad_group_v2(const svsr_wgrad_problem* problems, const int* mod
         hipLaunchKernelGGL(k_wgrad_group_table, dim3(1), dim3(256), 0, stream, chunk, (int)(cnt * sizeof(WgradGroupEntry) / 8),
                            reinterpret_cast<long long*>(static_cast<WgradGroupEntry*>(table_dev) + i0));
     }
-    constexpr int BC = 64, NS = 3;
-    const size_t lds_max = (size_t)NS * 2 * 64 * BC * sizeof(bf16_t) + (size_t)WG_MAXP * 2 * sizeof(int);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_igemm_wgrad_group<BC, NS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
-        attr_set = true;
-    }
-    const size_t lds = (size_t)NS * 2 * 64 * BC * sizeof(bf16_t) + (((size_t)maxP * 2 * sizeof(int) + 127) & ~(size_t)127);
-    hipLaunchKernelGGL((k_igemm_wgrad_group<BC, NS>), dim3(tiles), dim3(256), lds, stream, (const WgradGroupEntry*)table_dev, n);
-    return svsr_check_launch();
+    return problems[0].meta[0] == 128 ? launch_wgrad_group<128, 2>((const WgradGroupEntry*)table_dev, n, tiles, maxP, stream)
+                                      : launch_wgrad_group<64, 3>((const WgradGroupEntry*)table_dev, n, tiles, maxP, stream);
 }
 
 }  // extern "C"

@@ -810,6 +810,7 @@ class GradReducer:
         self.comm_stream: Optional[torch.cuda.Stream] = None
         self.top = 0
         self.launched: list[tuple[int, int]] = []
+        self._fenced_at = -1                  # ops.enqueue_seq() at the comm stream's last fence of this step
         self.sync = True                      # begin_step(sync=False): the reducer sits out a micro-step
         self.collectives = 0                  # gradient all-reduces issued so far (tests count them per micro-step)
         model.grad_ready_hook = self.on_ready
@@ -877,6 +878,7 @@ class GradReducer:
         st = self._st = self.model.store()         # (store() re-validates ~300 tensors: once per step, not once per hook call)
         self.top = st.decay_end
         self.launched = []
+        self._fenced_at = -1
         if self.measure:
             self._bucket_events.append([])
             if len(self._bucket_events) > 64:
@@ -896,11 +898,15 @@ class GradReducer:
         self.collectives += 1
         backend = self._backend
         if seg.is_cuda:
-            if fence:
+            # (nothing enqueued since the last fence — gradient-ready notifications that follow each other directly, as behind the encoder's one
+            # grouped weight-gradient launch: the comm stream already waits for these producers.  Inside a HIP graph capture a second
+            # event record / wait pair behind the same node gave a graph whose replay ran out of order)
+            if fence and ops.enqueue_seq() != self._fenced_at:
                 self.comm_stream.wait_stream(torch.cuda.current_stream())     # the segment's producers are enqueued there ...
                 side = self.model._side
                 if side.stream is not None and (side.enabled or side.enabled_small):
                     self.comm_stream.wait_stream(side.stream)                 # ... and, for weight gradients, on the model's side stream
+                self._fenced_at = ops.enqueue_seq()
             with torch.cuda.stream(self.comm_stream):
                 if self.measure and self._bucket_events:
                     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

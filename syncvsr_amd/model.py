@@ -934,15 +934,16 @@ def _lin_wgrad(model, x, dy, gw, gb, rows: int, K: int, N: int, x_pitch: int, dy
     model._side.run(lambda: ops.linear_wgrad(x, dy, gw, rows=rows, K=K, N=N, x_pitch=x_pitch, dy_pitch=dy_pitch, db=gb), x, dy, small=True)
 
 
-def _flush_lin_wgrads(model) -> None:
+def _flush_lin_wgrads(model, tile: Optional[int] = None) -> None:
     """The linear weight gradients collected so far as ONE launch over a device table of problems (ops.linear_wgrad_group; problems the
     grouped kernel does not take go out on their own inside that call), on the side stream when weight gradients go there: nothing
-    downstream reads them before the optimiser.  At ~800 rows each contraction is a 13-chunk K loop, 22 us of latency as a launch of its own."""
+    downstream reads them before the optimiser.  At ~800 rows each contraction is a 13-chunk K loop, 22 us of latency as a launch of its own.
+    tile: ops.linear_wgrad_group's (a forced tile edge for a group large enough to fill the chip by itself)."""
     group, model._wg_group = model._wg_group, None
     if not group:
         return
     keep = [t for q in group for t in (q["x"], q["dy"])]
-    model._side.run(lambda: ops.linear_wgrad_group(group), *keep, small=True)
+    model._side.run(lambda: ops.linear_wgrad_group(group, tile=tile), *keep, small=True)
 
 
 def _defer_list(model) -> Optional[list]:
@@ -1039,8 +1040,11 @@ def _encoder_forward_fused(model: TransformerLightningModule, st: _ParamStore, t
 def _encoder_layers_backward_fused(model: TransformerLightningModule, st: _ParamStore, tape: dict, dh: torch.Tensor, B: int, S: int,
                                    defer: Optional[list]) -> torch.Tensor:
     """The backward of all encoder layers in one launch (ops.enc_bwd, csrc/enc_fused.hip k_enc_bwd), then the parameter gradients it leaves
-    to the weight-gradient launches — the same calls, in the same order, as the per-layer path below makes.  Returns the gradient of the
-    first layer's input."""
+    to the weight-gradient launches.  Every operand of every layer's contractions exists when that launch returns, so with a collector
+    (model._wg_group) all of them — attention.output.dense included, unsplit — go out as ONE grouped launch on ops.ENC_WGRAD_TILE-wide tiles
+    and the LayerNorm parameter sums as one svsr_colsum_rows_multi launch, followed by the layers' gradient-ready notifications in the order
+    the per-layer path below gives them (what was collected before, the heads' linears, is flushed first, as a group of its own).  Without a
+    collector: the same calls, in the same order, as the per-layer path.  Returns the gradient of the first layer's input."""
     D, H, I, Lc = model.dim, model.heads, model.inter, model.layers
     R = B * S
     dev = dh.device
@@ -1066,13 +1070,21 @@ def _encoder_layers_backward_fused(model: TransformerLightningModule, st: _Param
     ops.enc_bwd(dh, recs, B, S, model._drop_word if on else None, model.drop_p if hidden_drop else 0.0,
                 model.attn_drop_p if t0["dpr"] is not None else 0.0)
 
+    merged = model._wg_group is not None
+    ln_sums: list = []         # merged: the 2 x layers LayerNorm parameter sums, one svsr_colsum_rows_multi launch behind the loop
+
     def ln_grads(rows, name):
         gw, gb = st.g32(f"{name}.weight"), st.g32(f"{name}.bias")
-        if defer is None:
+        if merged:
+            ln_sums.append((ops._deferred_colsum(rows, B, 2 * D, gw, D, gb, D), rows))
+        elif defer is None:
             ops.colsum_rows(rows, B, 2 * D, gw, D, gb, D)
         else:
             defer.append((lambda: ops.colsum_rows(rows, B, 2 * D, gw, D, gb, D), rows))
 
+    if merged:
+        _flush_lin_wgrads(model)
+        model._wg_group = []
     for i in reversed(range(Lc)):
         p = f"encoder.encoder.layer.{i}"
         t, q = tape[p], recs[i]
@@ -1085,13 +1097,19 @@ def _encoder_layers_backward_fused(model: TransformerLightningModule, st: _Param
         gq = st.grad[st.offsets[f"{p}.attention.self.query.weight"][0]:][: 3 * D * D]
         gqb = st.grad[st.offsets[f"{p}.attention.self.query.bias"][0]:][: 3 * D]
         _lin_wgrad(model, t["x"], q["dqkv"], gq, gqb, R, D, 3 * D, D, 3 * D)
-        _flush_deferred(model)
-        if model._wg_group is None:
+        if not merged:
+            _flush_deferred(model)
             _ready(model, st, f"{p}.attention.self.query.weight")
-        elif i > 0:
-            _flush_lin_wgrads(model)
-            model._wg_group = []
-            _ready(model, st, f"{p}.attention.self.query.weight")
+    if merged:
+        if defer is None:
+            ops.run_deferred([f for f, _ in ln_sums])
+        else:
+            defer.extend(ln_sums)
+            _flush_deferred(model)
+        _flush_lin_wgrads(model, tile=ops.ENC_WGRAD_TILE)
+        model._wg_group = []          # (empty: the caller's closing flush issues nothing and notifies layer 0)
+        for i in reversed(range(1, Lc)):
+            _ready(model, st, f"encoder.encoder.layer.{i}.attention.self.query.weight")
     return recs[0]["dx"]
 
 

@@ -333,15 +333,18 @@ class StepRecorder:
 
     def run(self) -> None:
         """Re-issues the recorded step: segment by segment, each followed by its host callbacks."""
+        global _ENQUEUED
         failed = ctypes.c_int(-1)
         run, h, cbs = self.lib.svsr_steplist_run, self.handle, self.callbacks
         if len(cbs) == 0:
             rc = run(h, -1, ctypes.byref(failed))
+            _ENQUEUED += 1
             if rc != 0:
                 _lib.check(rc, f"svsr_steplist_run (op {failed.value})")
             return
         for k in range(self.segments):
             rc = run(h, k, ctypes.byref(failed))
+            _ENQUEUED += 1
             if rc != 0:
                 _lib.check(rc, f"svsr_steplist_run (op {failed.value})")
             for fn in cbs.get(k, ()):
@@ -591,7 +594,18 @@ def lincomb3_ratio(a, wa: float, b, wb: float, c, wc: float, num=None, den=None)
     return out0, out1
 
 
+_ENQUEUED = 0      # counts what has been handed to the device: library calls and replayed step-list segments (enqueue_seq)
+
+
+def enqueue_seq() -> int:
+    """A number that grows with every library call and every replayed step-list segment: two equal readings mean that nothing was enqueued
+    in between (engine.GradReducer: a second cross-stream fence behind the same producers is left out)."""
+    return _ENQUEUED
+
+
 def _call(name: str, *args, label: Optional[str] = None, flops: float = 0.0, nbytes: float = 0.0) -> None:
+    global _ENQUEUED
+    _ENQUEUED += 1
     if _REC is not None and _REC.append_only:          # (a group the recording step skips: appended, not executed)
         _REC.call(name, args)
         return
@@ -683,6 +697,15 @@ def wgrad_rows_plan(Nimg: int, P: int, src0: int, dst0: int, Ci: int, Co: int, h
     return pl
 
 
+def wgrad_rows_plan_tile(Nimg: int, P: int, src0: int, dst0: int, Ci: int, Co: int, has_bias: bool, bc: int) -> WPlan:
+    """The same rows on bc-wide tiles (64 / 128) without K split (svsr_wgrad_rows_plan_tile): a problem of a grouped launch."""
+    key = ("wrows_tile", Nimg, P, src0, dst0, Ci, Co, bool(has_bias), bc)
+    pl = _PLAN_CACHE.get(key)
+    if pl is None:
+        pl = _PLAN_CACHE[key] = WPlan("svsr_wgrad_rows_plan_tile", Nimg, P, src0, dst0, Ci, Co, int(has_bias), bc)
+    return pl
+
+
 # --------------------------------------------------------------------------------------------------
 # implicit GEMM
 # --------------------------------------------------------------------------------------------------
@@ -741,32 +764,39 @@ def _group_table(nbytes: int, device) -> torch.Tensor:
     return t
 
 
-def linear_wgrad_group(problems: Sequence[dict]) -> None:
-    """problems: keyword arguments of linear_wgrad calls (x, dy, dw, rows, K, N, x_pitch, dy_pitch, seq, db).  Those whose plan has no K
-    split on 64-wide tiles go out as one svsr_igemm_wgrad_group launch; the others (none at the LRW shapes) as launches of their own."""
-    grouped, keep, modes = [], [], []
+def linear_wgrad_group(problems: Sequence[dict], tile: Optional[int] = None) -> None:
+    """problems: keyword arguments of linear_wgrad calls (x, dy, dw, rows, K, N, x_pitch, dy_pitch, seq, db).  tile=None: those whose plan has
+    no K split on 64-wide tiles go out as one svsr_igemm_wgrad_group launch; the others (the encoder's attention.output.dense at the LRW shapes)
+    as launches of their own.  tile=64 / 128: EVERY problem rides a grouped launch, planned unsplit on tiles of that edge
+    (svsr_wgrad_rows_plan_tile) — for a caller whose problems fill the chip together (all encoder layers at once); with tile=128 the problems
+    narrower than a tile (K or N below 128) form a second, 64-wide group of the same call."""
+    if tile not in (None, 64, 128):
+        raise ValueError(f"linear_wgrad_group: tile must be None, 64 or 128, not {tile!r}")
+    groups: dict = {}          # tile edge -> (problem records, plans, modes, flops)
     for q in problems:
         rows, K, N, seq, db = q["rows"], q["K"], q["N"], q.get("seq"), q.get("db")
-        if seq is None:
-            plan, geo = wgrad_rows_plan(rows, 1, 0, 0, K, N, db is not None), (rows, 1, 1)
+        rp = (rows, 1, 0, 0) if seq is None else (rows // seq[2], seq[2], seq[1], 0)
+        geo = (rows, 1, 1) if seq is None else (rows // seq[2], seq[0], seq[2])
+        if tile is None:
+            plan = wgrad_rows_plan(*rp, K, N, db is not None)
+            if not (plan.bc == 64 and int(plan.meta[1]) == 3 and plan.splits == 1):
+                linear_wgrad(q["x"], q["dy"], q["dw"], rows=rows, K=K, N=N, x_pitch=q["x_pitch"], dy_pitch=q["dy_pitch"], seq=seq, db=db)
+                continue
         else:
-            S, s0, n = seq
-            plan, geo = wgrad_rows_plan(rows // n, n, s0, 0, K, N, db is not None), (rows // n, S, n)
-        if not (plan.bc == 64 and int(plan.meta[1]) == 3 and plan.splits == 1):
-            linear_wgrad(q["x"], q["dy"], q["dw"], rows=rows, K=K, N=N, x_pitch=q["x_pitch"], dy_pitch=q["dy_pitch"], seq=seq, db=db)
-            continue
-        grouped.append(_WgradProblem(_p(q["x"]), _p(q["dy"]), _p(q["dw"]), _p(db), plan.words.data_ptr(), ctypes.addressof(plan.meta),
-                                     geo[0], geo[1], K, q["x_pitch"], N, geo[2], q["dy_pitch"], 1))
-        keep.append(plan)
-        modes.append(_grad_add(q["dw"], N * K) | 2)
-    if not grouped:
-        return
-    arr = (_WgradProblem * len(grouped))(*grouped)
-    nbytes = int(_lib.load().svsr_igemm_wgrad_group_bytes(len(grouped)))
-    table = _group_table(nbytes, problems[0]["x"].device)
-    flops = sum(2.0 * q["rows"] * q["K"] * q["N"] for q in problems)
-    _call("svsr_igemm_wgrad_group_v2", arr, (ctypes.c_int * len(modes))(*modes), len(grouped), _p(table), nbytes, _stream(),
-          label="k_igemm_wgrad_group<64,3>", flops=flops)
+            plan = wgrad_rows_plan_tile(*rp, K, N, db is not None, tile if K >= tile and N >= tile else 64)
+        g = groups.setdefault(plan.bc, ([], [], [], [0.0]))
+        g[0].append(_WgradProblem(_p(q["x"]), _p(q["dy"]), _p(q["dw"]), _p(db), plan.words.data_ptr(), ctypes.addressof(plan.meta),
+                                  geo[0], geo[1], K, q["x_pitch"], N, geo[2], q["dy_pitch"], 1))
+        g[1].append(plan)
+        g[2].append(_grad_add(q["dw"], N * K) | 2)
+        g[3][0] += 2.0 * rows * K * N
+    for bc in sorted(groups, reverse=True):
+        grouped, _, modes, flops = groups[bc]
+        arr = (_WgradProblem * len(grouped))(*grouped)
+        nbytes = int(_lib.load().svsr_igemm_wgrad_group_bytes(len(grouped)))
+        table = _group_table(nbytes, problems[0]["x"].device)
+        _call("svsr_igemm_wgrad_group_v2", arr, (ctypes.c_int * len(modes))(*modes), len(grouped), _p(table), nbytes, _stream(),
+              label=f"k_igemm_wgrad_group<{bc},{2 if bc == 128 else 3}>", flops=flops[0])
 
 
 def conv_out_size(n: int, k: int, stride: int, pad: int) -> int:
@@ -1337,6 +1367,10 @@ class _EncBwdLayer(ctypes.Structure):
 
 
 ENC_BWD_FUSED = os.environ.get("SVSR_ENC_BWD_FUSED", "1") != "0"     # the whole encoder backward as one launch (False: 13 launches per layer)
+# tile edge of the ONE grouped weight-gradient launch behind the fused backward (linear_wgrad_group(tile=...)).  Six layers are 1,152 tiles of
+# 128 x 128 = 2.25 rounds of two workgroups per CU, at half the staged bytes per FLOP of the 4,608 tiles of 64 x 64 (six rounds of three):
+# measured at the benchmark's shapes the wide launch is the faster one; 64 is the other supported value
+ENC_WGRAD_TILE = 128
 _ENC_BWD_WS: dict = {}
 
 
