@@ -676,6 +676,50 @@ int svsr_tconv_fwd(const void* x, int64_t x_pitch, int B, int T, int n_in, int d
 int svsr_tcn_se_fwd(const void* x, int64_t x_pitch, int B, int T, int n_in, int R, int nb, const void* w1, const void* w2, float* gate, hipStream_t stream);
 int svsr_tcn_norm_pool_fwd(const void* x, int64_t x_pitch, int B, int T, int C, const float* scale, const float* shift, const float* mask, void* h, void* pooled, hipStream_t stream);
 
+/* ---- backward of the dense temporal back-end (dctcn.hip; DCTCNLightningModule.loss_and_backend_grads) ------------------------
+ * The statistics mode of the forward: running-statistic BatchNorm, no dropout.  Gradient rows are channels-last bf16 [B*T][pitch]; parameter
+ * gradients and per-channel sums are fp32.  No atomics: one writer per element and launch, every sum in one fixed order (two runs: same bits).
+ *
+ * svsr_tconv_fwd_save: svsr_tconv_fwd (same arguments, same output bits) that also stores the fp32 accumulator of every written element:
+ * acc[b*T + t][i * co + c] for branch i, acc_pitch >= nb * co.  The backward recomputes z = scale * acc + shift from it with the forward's fma;
+ * nothing is recovered by dividing by scale and no activation is inverted.
+ *
+ * svsr_tconv_epi_bwd: the epilogue's backward over C channels (a multiple of 64) of `rows` rows.  z = scale[c] * acc + shift[c], y = act(z);
+ * with res: u = y + res, du = dy * res_act'(u), dres = bf16(du); without: du = dy.  g = du * act'(z); dacc = bf16(g * scale[c]).
+ * sums fp32 [4][C] = per channel the sums over the rows of g, g * acc, du * min(z, 0) (PReLU slope gradient; 0 otherwise) and du (0 without
+ * res): first per block of 64 rows into part (fp32, 4 * C * ceil(rows / 64)), then folded in block order.  dy, dacc, dres, res are passed
+ * at their first channel, with their pitches.  The host turns the sums into d bn.weight, d bn.bias, d conv.bias with O(C) operations.
+ *
+ * svsr_tconv_dgrad: data gradient of nb (1..3) branches in one launch, on MFMA with the forward's staged slab.  `branches` is a HOST table of
+ * nb x 4 64-bit words {k, wt, gate, dy_off}: wt bf16 [n_out][k][co] with wt[ci][j][c] = w[c][k-1-j][ci] (transposed, taps flipped); gate fp32
+ * [B][n_out] or 0; dy_off the first channel of the branch's dacc in a dy row.
+ *   dxg_i[b][t][ci] = sum_j sum_c dy[b][t + (j - (k-1)/2) d][dy_off + c] * wt[ci][j][c]      (rows outside the clip contribute zero)
+ *   out[b*T + t][ci] = bf16(addend + cadd[b][ci] * cadd_scale + sum_i (gate_i ? gate_i[b][ci] : 1) * dxg_i)     (one write; addend, cadd optional;
+ *   addend may be out itself)
+ *   gpart[i][b][tile][ci] = sum over the 32-row time tile of x[b][t][ci] * dxg_i   (gated branches only; x bf16 rows of x_pitch)
+ * Same shape domain as svsr_tconv_fwd with co and n_out exchanged for n_in and co; anything else SVSR_ERR_ARG.
+ *
+ * svsr_tconv_wgrad: one branch's weight gradient dw[c][ci][j] (the parameter's own [co][n_valid][k] layout, ci < n_valid <= n_in)
+ *   = (add ? dw : 0) + sum_{b,t} dy[b][t][c] * bf16(x * gate)[b][t + (j - (k-1)/2) d][ci], fp32 on MFMA over the rows; gate fp32 [B][n_in] or
+ * null; the rows are split `splits` ways (1 .. ceil(B * ceil(T/32) / 2)), part fp32 [splits][co][k][n_in] is folded in split order.
+ *
+ * svsr_tcn_se_bwd: from the gate partials of svsr_tconv_dgrad through sigmoid(W2 swish(W1 m)): dm fp32 [B][n_in] (gradient of the time mean,
+ * summed over the branches; dm / T belongs to every row: svsr_tconv_dgrad's cadd) and the weight gradients, written (or added, `add`) to the
+ * 2 * nb fp32 pointers of the HOST table dw = {dW1_0 .. , dW2_0 ..} ([R][n_in] and [n_in][R]); sums over clips in clip order.  work: fp32
+ * scratch of nb*B*n_in + 2*nb*B*R + B*n_in floats.  n_in up to (64 KiB - 8 R) / 24 channels.
+ *
+ * svsr_tcn_norm_pool_bwd: g = dh[b][t][c] + dpooled[b][c] * mask[b][t] / (sum_t mask + 1e-6); dx = bf16(g * scale[c]) (rows of dx_pitch);
+ * sums fp32 [2][C] = the sums over all rows of g and g * x (x: the forward's input), per clip into part (fp32 [B][2][C]) then in clip order.
+ *
+ * svsr_tcn_fold: out[i] = (add ? out[i] : 0) + sum_r part[r * n + i], r ascending. */
+int svsr_tconv_fwd_save(const void* x, int64_t x_pitch, int B, int T, int n_in, int d, int nb, const int64_t* branches, int co, int act, void* out, int64_t out_pitch, const void* res, int64_t res_pitch, int res_act, float* acc, int64_t acc_pitch, hipStream_t stream);
+int svsr_tconv_epi_bwd(const void* dy, int64_t dy_pitch, const float* acc, int64_t acc_pitch, int64_t rows, int C, int act, const float* scale, const float* shift, const float* slope, const void* res, int64_t res_pitch, int res_act, void* dacc, int64_t dacc_pitch, void* dres, int64_t dres_pitch, float* part, float* sums, hipStream_t stream);
+int svsr_tconv_dgrad(const void* dy, int64_t dy_pitch, int B, int T, int co, int d, int nb, const int64_t* branches, int n_out, const void* x, int64_t x_pitch, const void* addend, int64_t add_pitch, const float* cadd, float cadd_scale, void* out, int64_t out_pitch, float* gpart, hipStream_t stream);
+int svsr_tconv_wgrad(const void* x, int64_t x_pitch, const float* gate, const void* dy, int64_t dy_pitch, int B, int T, int n_in, int co, int k, int d, int splits, float* part, float* dw, int n_valid, int add, hipStream_t stream);
+int svsr_tcn_se_bwd(const void* x, int64_t x_pitch, int B, int T, int n_in, int R, int nb, const void* w1, const void* w2, const float* gate, const float* gpart, float* work, float* dm, const int64_t* dw, int add, hipStream_t stream);
+int svsr_tcn_norm_pool_bwd(const void* dh, const void* dpooled, const void* x, int64_t x_pitch, int B, int T, int C, const float* scale, const float* mask, void* dx, int64_t dx_pitch, float* part, float* sums, hipStream_t stream);
+int svsr_tcn_fold(const float* part, int rows, int64_t n, float* out, int add, hipStream_t stream);
+
 /* ---- multi-clip beam search (lrs_search.hip; BatchBeamSearch.forward_clips of syncvsr_amd/lrs_infer.py) -----------------
  * C clips advance through one search in lock step.  The n live hypotheses are rows grouped by clip: clip_of int32 [n] is non-decreasing,
  * clip c owns rows row_lo[c] .. row_lo[c + 1] - 1 (row_lo int32 [C + 1]; an empty range: the clip has finished).

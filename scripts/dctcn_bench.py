@@ -4,6 +4,7 @@ out) at B = 96 and B = 32, T = 29, 96 x 96.
 
     python scripts/dctcn_bench.py [--batches 96,32] [--rounds 7] [--iters 50] [--out profiles/dctcn_eval.json]
     rocprofv3 --kernel-trace --stats -d <dir> -- python scripts/dctcn_bench.py --profile-only        # kernel table, in a run of its own
+    python scripts/dctcn_bench.py --backward [--profile-only]      # forward + backward of the back-end and heads against eager bf16 autograd
 
 Times are wall-clock between device synchronisations (host dispatch included), the two implementations ALTERNATING round by round after
 warm-up of every shape; per implementation the median over rounds of the mean of `--iters` calls, and the minimum.  The convolution
@@ -56,7 +57,7 @@ class EagerDCTCN:
                 h = F.silu(o + r)
         return h.mean((2, 3)).view(B, T, 512)
 
-    def backend(self, feats, word_mask, attention_mask):
+    def backend(self, feats, word_mask, attention_mask, want_hidden: bool = False):
         W, dm = self.W, self.dims
         x = feats
         if dm["in_size"] == 513:
@@ -93,7 +94,29 @@ class EagerDCTCN:
         h = self.bn(x, f"{TCN}.norm5")
         am = attention_mask.to(h.dtype)
         pooled = (h * am.unsqueeze(1)).sum(2) / (am.sum(1, keepdim=True) + 1e-6)
-        return F.linear(pooled, W["video_classifier.weight"], W["video_classifier.bias"]).float()
+        logits = F.linear(pooled, W["video_classifier.weight"], W["video_classifier.bias"]).float()
+        if not want_hidden:
+            return logits
+        return logits, h
+
+    def backend_params(self) -> list:
+        """Leaves of the backward leg: every floating-point tensor of the temporal network and the heads that is a parameter."""
+        return [v for k, v in self.W.items() if k.startswith((TCN, "video_classifier", "audio_projection")) and v.is_floating_point()
+                and "running_" not in k]
+
+    def loss_and_grads(self, feats, word_mask, attention_mask, tokens, labels, lam: float):
+        """bf16 autograd of the same modules: both cross-entropies of lightning.py:280-312 (lam = 0), gradients of every back-end parameter."""
+        params = self.backend_params()
+        for p in params:
+            p.requires_grad_(True)
+            p.grad = None
+        logits, h = self.backend(feats, word_mask, attention_mask, want_hidden=True)
+        B, C, T = h.shape
+        la = F.linear(h.transpose(1, 2), self.W["audio_projection.weight"], self.W["audio_projection.bias"])
+        A, V = self.dims["A"], self.dims["V"]
+        loss = F.cross_entropy(logits, labels) + lam * F.cross_entropy(la.reshape(-1, V).float(), tokens[:, : T * A].reshape(-1))
+        loss.backward()
+        return loss
 
 
 def _time(fn, iters: int) -> float:
@@ -105,6 +128,69 @@ def _time(fn, iters: int) -> float:
     return (time.perf_counter() - t0) * 1e3 / iters
 
 
+def backward_leg(a) -> None:
+    """Features in, all gradients out; same alternating / median protocol as the forward.  Merges "timing" into profiles/dctcn_backward.json
+    (the file also holds the bf16 floor of the tests)."""
+    from syncvsr_amd import ops
+    from syncvsr_amd.dctcn import DCTCNLightningModule
+    from syncvsr_amd.dctcn_init import dctcn_dims, dctcn_init_state_dict, dctcn_synthetic_batch, default_dctcn_config
+
+    dev = torch.device("cuda:0")
+    cfg = default_dctcn_config()
+    sd = dctcn_init_state_dict(cfg, seed=0)
+    model = DCTCNLightningModule(cfg)
+    model.load_state_dict(sd)
+    model.to(dev).eval()
+    eager = EagerDCTCN(sd, dctcn_dims(cfg), dev)
+    lam, T, rows = model.lambda_audio, a.frames, []
+    for B in [int(v) for v in a.batches.split(",")]:
+        videos, tokens, labels, wm, am = [t.to(dev) for t in dctcn_synthetic_batch(cfg, B, T, seed=B)]
+        labels = labels.long()
+        with torch.no_grad():
+            feats16 = eager.frontend(videos).contiguous()
+        feats_hip = feats16.reshape(B * T, 512).contiguous()
+        fns = {
+            "hip_backward": lambda: model.loss_and_backend_grads_from_features(feats_hip, B, T, tokens, labels, wm, am),
+            "eager_backward": lambda: eager.loss_and_grads(feats16, wm, am, tokens, labels, lam),
+            "hip_forward_only": lambda: model._losses((B, T), tokens, labels, wm, am, None, feats_hip),
+        }
+        for fn in fns.values():
+            _time(fn, 3)
+        if a.profile_only:
+            continue
+        g_hip = dict(model.named_parameters())["audio_projection.weight"].grad.float().flatten()
+        g_ref = eager.W["audio_projection.weight"].grad.float().flatten()
+        cos = float(torch.dot(g_hip, g_ref) / (g_hip.norm() * g_ref.norm()))
+        samples = {k: [] for k in fns}
+        for _ in range(a.rounds):
+            for k, fn in fns.items():
+                samples[k].append(_time(fn, a.iters))
+        ops.start_event_timing()
+        fns["hip_backward"]()
+        torch.cuda.synchronize()
+        ev = ops.stop_event_timing()
+        row = dict(B=B, T=T, cos_grad_audio_projection=round(cos, 5))
+        for k, v in samples.items():
+            row[f"{k}_ms_median"], row[f"{k}_ms_min"] = round(statistics.median(v), 4), round(min(v), 4)
+        row["eager_over_hip"] = round(row["eager_backward_ms_median"] / row["hip_backward_ms_median"], 3)
+        row["event_ms_by_label"] = {k: (v.get("launches"), round(v.get("ms", 0.0), 3)) for k, v in sorted(ev.items()) if v.get("ms")}
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    if a.profile_only:
+        return
+    path = os.path.join(ROOT, "profiles", "dctcn_backward.json") if a.out.endswith("dctcn_eval.json") else a.out
+    doc = {}
+    if os.path.exists(path):
+        with open(path) as f:
+            doc = json.load(f)
+    doc["timing"] = dict(what="DC-TCN back-end + heads, forward and backward: features in, all gradients out; HIP vs torch eager bf16 autograd of the "
+                              "same modules, same process, alternating rounds (event_ms_by_label: device events around host calls, not kernel times)",
+                         device=torch.cuda.get_device_name(0), rounds=a.rounds, iters=a.iters, rows=rows)
+    with open(path, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", default="96,32")
@@ -114,7 +200,11 @@ def main() -> None:
     ap.add_argument("--peak-tflops", type=float, default=2500.0, help="dense bf16 peak of the device (MI355X: 2.5 PFLOP/s)")
     ap.add_argument("--profile-only", action="store_true", help="a few untimed forwards per shape (for a rocprofv3 run of its own)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dctcn_eval.json"))
+    ap.add_argument("--backward", action="store_true", help="the backward leg instead: features in, all back-end gradients out, HIP "
+                    "(loss_and_backend_grads_from_features) against bf16 autograd of the eager modules -> profiles/dctcn_backward.json")
     a = ap.parse_args()
+    if a.backward:
+        return backward_leg(a)
     from syncvsr_amd import ops
     from syncvsr_amd.dctcn import DCTCNLightningModule
     from syncvsr_amd.dctcn_init import dctcn_dims, dctcn_init_state_dict, dctcn_synthetic_batch, default_dctcn_config

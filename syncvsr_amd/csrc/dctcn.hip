@@ -33,6 +33,9 @@ struct TArgs {
     const bf16_t* res;
     long x_pitch, out_pitch, res_pitch;
     int B, T, n_in, d, act, res_act, n_tt, slots;
+    float* save;              // k_tconv<true>: the fp32 accumulators, [B*T][save_pitch], branch i at channels [i * co, (i + 1) * co)
+    long save_pitch;
+    int co;
 };
 
 // 16-byte piece s (0..7) of 128-byte LDS row `row`: XOR swizzle on the row PAIR, so the 16 rows of a ds_read_b128 lane group (consecutive
@@ -42,6 +45,9 @@ __device__ __forceinline__ int tc_off(int row, int s) { return row * 128 + ((s ^
 // One workgroup (4 waves): TC_SLOTS slots x 64 output channels of ONE branch; wave w owns slot w >> 1 and 32 of the channels.
 // Per 64-channel chunk of the input: the rows [t0 - halo, t0 + 32 + halo) of each slot (zeros outside the clip), times the branch's gate,
 // are staged ONCE and serve all k taps (a tap is a row offset into the slab); the chunk of the weights [64 co][k][64 ci] beside it.
+// SAVE: the accumulator of every written element is stored too (svsr_tconv_fwd_save: the backward recomputes z = scale * acc + shift from it
+// with the same fma); the bf16 outputs are the same bits either way.
+template <bool SAVE>
 __global__ __launch_bounds__(256) void k_tconv(TArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     unsigned char* slab = smem_raw;
@@ -112,6 +118,7 @@ __global__ __launch_bounds__(256) void k_tconv(TArgs a) {
         if (t < a.T) {
             const long row = (long)b * a.T + t;
             float v = __builtin_fmaf(acc[i], sc, sh);
+            if (SAVE) a.save[row * a.save_pitch + (long)blockIdx.z * a.co + co] = acc[i];
             if (a.act == SVSR_ACT_SWISH) v = swish(v);
             else if (a.act == TC_ACT_PRELU) v = v >= 0.f ? v : v * slope;
             else if (a.act == SVSR_ACT_RELU) v = fmaxf(v, 0.f);
@@ -125,8 +132,10 @@ __global__ __launch_bounds__(256) void k_tconv(TArgs a) {
 }
 
 // branches: HOST table of nb x 8 64-bit words {k, w, gate, scale, shift, slope, out_off, res_off} (read during the call only)
-extern "C" int svsr_tconv_fwd(const void* x, int64_t x_pitch, int B, int T, int n_in, int d, int nb, const int64_t* branches, int co, int act,
-                              void* out, int64_t out_pitch, const void* res, int64_t res_pitch, int res_act, hipStream_t stream) {
+static int tconv_launch(const void* x, int64_t x_pitch, int B, int T, int n_in, int d, int nb, const int64_t* branches, int co, int act,
+                        void* out, int64_t out_pitch, const void* res, int64_t res_pitch, int res_act, float* save, int64_t save_pitch, bool saving,
+                        hipStream_t stream) {
+    if (saving && (save == nullptr || save_pitch < (int64_t)nb * co)) return SVSR_ERR_ARG;
     if (x == nullptr || out == nullptr || branches == nullptr) return SVSR_ERR_ARG;
     if (B < 1 || T < 1 || d < 1 || n_in < 64 || n_in % 64 != 0 || x_pitch < n_in || x_pitch % 8 != 0 || ((uintptr_t)x & 15) != 0) return SVSR_ERR_ARG;
     if (nb < 1 || nb > 3 || co < TC_BN || co % TC_BN != 0 || out_pitch < co) return SVSR_ERR_ARG;
@@ -161,12 +170,28 @@ extern "C" int svsr_tconv_fwd(const void* x, int64_t x_pitch, int B, int T, int 
     a.x = (const bf16_t*)x; a.out = (bf16_t*)out; a.res = (const bf16_t*)res;
     a.x_pitch = x_pitch; a.out_pitch = out_pitch; a.res_pitch = res_pitch;
     a.B = B; a.T = T; a.n_in = n_in; a.d = d; a.act = act; a.res_act = res_act; a.n_tt = (int)n_tt; a.slots = (int)slots;
+    a.save = save; a.save_pitch = save_pitch; a.co = co;
     const size_t lds = TC_SLAB_BYTES + (size_t)kmax * TC_BN * TC_BK * 2;
+    const dim3 grid((unsigned)((slots + TC_SLOTS - 1) / TC_SLOTS), (unsigned)(co / TC_BN), (unsigned)nb);
     // per call: the attribute belongs to the current device's copy of the kernel, and setting it costs a table lookup
-    const hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void*>(k_tconv), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const void* fn = saving ? reinterpret_cast<const void*>(k_tconv<true>) : reinterpret_cast<const void*>(k_tconv<false>);
+    const hipError_t ae = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (ae != hipSuccess) return (int)ae;
-    hipLaunchKernelGGL(k_tconv, dim3((unsigned)((slots + TC_SLOTS - 1) / TC_SLOTS), (unsigned)(co / TC_BN), (unsigned)nb), dim3(256), lds, stream, a);
+    if (saving) hipLaunchKernelGGL(k_tconv<true>, grid, dim3(256), lds, stream, a);
+    else hipLaunchKernelGGL(k_tconv<false>, grid, dim3(256), lds, stream, a);
     return svsr_check_launch();
+}
+
+extern "C" int svsr_tconv_fwd(const void* x, int64_t x_pitch, int B, int T, int n_in, int d, int nb, const int64_t* branches, int co, int act,
+                              void* out, int64_t out_pitch, const void* res, int64_t res_pitch, int res_act, hipStream_t stream) {
+    return tconv_launch(x, x_pitch, B, T, n_in, d, nb, branches, co, act, out, out_pitch, res, res_pitch, res_act, nullptr, 0, false, stream);
+}
+
+// svsr_tconv_fwd that also stores every fp32 accumulator: acc[b*T + t][i * co + c] for branch i (acc_pitch >= nb * co)
+extern "C" int svsr_tconv_fwd_save(const void* x, int64_t x_pitch, int B, int T, int n_in, int d, int nb, const int64_t* branches, int co, int act,
+                                   void* out, int64_t out_pitch, const void* res, int64_t res_pitch, int res_act, float* acc, int64_t acc_pitch,
+                                   hipStream_t stream) {
+    return tconv_launch(x, x_pitch, B, T, n_in, d, nb, branches, co, act, out, out_pitch, res, res_pitch, res_act, acc, acc_pitch, true, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -311,4 +336,606 @@ extern "C" int svsr_tcn_norm_pool_fwd(const void* x, int64_t x_pitch, int B, int
     hipLaunchKernelGGL(k_tcn_norm_pool, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const bf16_t*)x, (long)x_pitch, B, T, C, scale, shift,
                        mask, (bf16_t*)h, (bf16_t*)pooled);
     return svsr_check_launch();
+}
+
+// =====================================================================================================================
+// Backward of the back-end in the statistics mode the forward runs (running-statistic BatchNorm, no dropout).  Gradient rows are bf16,
+// parameter gradients and per-channel sums fp32.  No atomics: every element has one writer per launch, every sum one fixed order.
+// =====================================================================================================================
+
+// out[i] = (add ? out[i] : 0) + sum_r part[r * n + i], r ascending
+__global__ __launch_bounds__(256) void k_tcn_fold(const float* __restrict__ part, int rows, long n, float* __restrict__ out, int add) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float s = 0.f;
+    for (int r = 0; r < rows; ++r) s += part[(long)r * n + i];
+    out[i] = add ? out[i] + s : s;
+}
+
+extern "C" int svsr_tcn_fold(const float* part, int rows, int64_t n, float* out, int add, hipStream_t stream) {
+    if (part == nullptr || out == nullptr || rows < 1 || n < 1 || n > (1L << 38)) return SVSR_ERR_ARG;
+    hipLaunchKernelGGL(k_tcn_fold, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, part, rows, (long)n, out, add);
+    return svsr_check_launch();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Epilogue backward.  With z = scale * acc + shift (the forward's fma on the stored accumulator), y = act(z) and, with a residual,
+// u = y + res and the output res_act(u):   du = dy * res_act'(u) (dy without a residual), g = du * act'(z),
+//   dacc = bf16(g * scale), dres = bf16(du), and per channel the sums of g, g * acc, du * min(z, 0) (the PReLU slope) and du,
+// first per block of EB_ROWS rows (part [blocks][4][C]), then folded in block order by svsr_tcn_fold.
+// ---------------------------------------------------------------------------------------------------------------------
+#define EB_ROWS 64
+struct EArgs {
+    const bf16_t* dy; const float* acc; const float* scale; const float* shift; const float* slope; const bf16_t* res;
+    bf16_t* dacc; bf16_t* dres; float* part;
+    long dy_pitch, acc_pitch, res_pitch, dacc_pitch, dres_pitch, rows;
+    int C, act, res_act;
+};
+
+__global__ __launch_bounds__(256) void k_tconv_epi_bwd(EArgs a) {
+    __shared__ float red[4][4][64];
+    const int tid = threadIdx.x, cl = tid & 63, rl = tid >> 6;
+    const int c = blockIdx.y * 64 + cl;
+    const float sc = a.scale[c], sh = a.shift[c];
+    const float slope = a.act == TC_ACT_PRELU ? a.slope[c] : 0.f;
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    const long r0 = (long)blockIdx.x * EB_ROWS;
+    for (int i = rl; i < EB_ROWS; i += 4) {
+        const long row = r0 + i;
+        if (row >= a.rows) break;
+        const float ac = a.acc[row * a.acc_pitch + c];
+        const float z = __builtin_fmaf(ac, sc, sh);
+        float du = bf2f(a.dy[row * a.dy_pitch + c]);
+        if (a.res != nullptr) {
+            float y = z;
+            if (a.act == SVSR_ACT_SWISH) y = swish(z);
+            else if (a.act == TC_ACT_PRELU) y = z >= 0.f ? z : z * slope;
+            else if (a.act == SVSR_ACT_RELU) y = fmaxf(z, 0.f);
+            const float u = y + bf2f(a.res[row * a.res_pitch + c]);
+            if (a.res_act == SVSR_ACT_SWISH) du *= swish_grad(u);
+            a.dres[row * a.dres_pitch + c] = f2bf(du);
+            s3 += du;
+        }
+        float g = du;
+        if (a.act == SVSR_ACT_SWISH) g = du * swish_grad(z);
+        else if (a.act == TC_ACT_PRELU) { g = z >= 0.f ? du : du * slope; s2 += du * fminf(z, 0.f); }
+        else if (a.act == SVSR_ACT_RELU) g = z > 0.f ? du : 0.f;
+        a.dacc[row * a.dacc_pitch + c] = f2bf(g * sc);
+        s0 += g;
+        s1 = __builtin_fmaf(g, ac, s1);
+    }
+    red[0][rl][cl] = s0; red[1][rl][cl] = s1; red[2][rl][cl] = s2; red[3][rl][cl] = s3;
+    __syncthreads();
+    // thread (stat = rl, channel = cl): the four row lanes in order
+    const float t = ((red[rl][0][cl] + red[rl][1][cl]) + red[rl][2][cl]) + red[rl][3][cl];
+    a.part[((long)blockIdx.x * 4 + rl) * a.C + c] = t;
+}
+
+extern "C" int svsr_tconv_epi_bwd(const void* dy, int64_t dy_pitch, const float* acc, int64_t acc_pitch, int64_t rows, int C, int act,
+                                  const float* scale, const float* shift, const float* slope, const void* res, int64_t res_pitch, int res_act,
+                                  void* dacc, int64_t dacc_pitch, void* dres, int64_t dres_pitch, float* part, float* sums, hipStream_t stream) {
+    if (dy == nullptr || acc == nullptr || scale == nullptr || shift == nullptr || dacc == nullptr || part == nullptr || sums == nullptr) return SVSR_ERR_ARG;
+    if (rows < 1 || rows > (1L << 30) || C < 64 || C % 64 != 0 || C / 64 > 65535 || dy_pitch < C || acc_pitch < C || dacc_pitch < C) return SVSR_ERR_ARG;
+    if (act != SVSR_ACT_NONE && act != SVSR_ACT_RELU && act != SVSR_ACT_SWISH && act != TC_ACT_PRELU) return SVSR_ERR_ARG;
+    if (act == TC_ACT_PRELU && slope == nullptr) return SVSR_ERR_ARG;
+    if (res_act != SVSR_ACT_NONE && res_act != SVSR_ACT_SWISH) return SVSR_ERR_ARG;
+    if (res != nullptr && (dres == nullptr || res_pitch < C || dres_pitch < C)) return SVSR_ERR_ARG;
+    EArgs a;
+    a.dy = (const bf16_t*)dy; a.acc = acc; a.scale = scale; a.shift = shift; a.slope = slope; a.res = (const bf16_t*)res;
+    a.dacc = (bf16_t*)dacc; a.dres = (bf16_t*)dres; a.part = part;
+    a.dy_pitch = dy_pitch; a.acc_pitch = acc_pitch; a.res_pitch = res_pitch; a.dacc_pitch = dacc_pitch; a.dres_pitch = dres_pitch; a.rows = rows;
+    a.C = C; a.act = act; a.res_act = res_act;
+    const long blocks = (rows + EB_ROWS - 1) / EB_ROWS;
+    hipLaunchKernelGGL(k_tconv_epi_bwd, dim3((unsigned)blocks, (unsigned)(C / 64)), dim3(256), 0, stream, a);
+    int rc = svsr_check_launch();
+    if (rc != SVSR_OK) return rc;
+    return svsr_tcn_fold(part, (int)blocks, 4L * C, sums, 0, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Data gradient of the multi-branch (gated) temporal convolution: the forward's slab scheme with the roles exchanged.  The staged rows are
+// the nb branches' dacc (co channels each, at dy_off), the weights are the transposed, tap-flipped shadows wt [n_out][k][co]
+// (wt[ci][j][c] = w[c][k - 1 - j][ci]), so tap j is again the row offset (j - (k - 1) / 2) * d.  One workgroup: TC_SLOTS slots x 64 input
+// channels, the branches one after the other:
+//   dxg_j = conv(dacc_j, wt_j);   gpart[j][b][tile][ci] = sum_t x[b][t][ci] * dxg_j[b][t][ci]   (gated branches; t ascending per lane, the two
+//   lane halves added low + high);   out = bf16(addend + cadd[b][ci] * cadd_scale + sum_j gate_j[b][ci] * dxg_j)     — one write for all branches
+// ---------------------------------------------------------------------------------------------------------------------
+struct DBranch { const bf16_t* wt; const float* gate; int k, dy_off; };
+struct DArgs {
+    DBranch br[3];
+    const bf16_t* dy; const bf16_t* x; const bf16_t* addend; const float* cadd; bf16_t* out; float* gpart;
+    long dy_pitch, x_pitch, add_pitch, out_pitch;
+    float cadd_scale;
+    int B, T, co, n_out, d, nb, n_tt, slots;
+};
+
+__global__ __launch_bounds__(256) void k_tconv_dgrad(DArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    unsigned char* slab = smem_raw;
+    unsigned char* wts = smem_raw + TC_SLAB_BYTES;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n0 = blockIdx.y * TC_BN;
+    const int my_slot = wave >> 1, nh = wave & 1, r = lane & 31, h = lane >> 5;
+    const long gsw = (long)blockIdx.x * TC_SLOTS + my_slot;
+    const bool valid = gsw < a.slots;
+    const int wb = valid ? (int)(gsw / a.n_tt) : 0;
+    const int wtt = valid ? (int)(gsw - (long)wb * a.n_tt) : 0;
+    const int t0 = wtt * TC_TILE;
+    const int ci = n0 + nh * 32 + r;
+    f32x16 tot;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) tot[i] = 0.f;
+    for (int j = 0; j < a.nb; ++j) {
+        const DBranch br = a.br[j];
+        const int k = br.k, halo = (k - 1) * a.d / 2;
+        f32x16 acc;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+        for (int c0 = 0; c0 < a.co; c0 += TC_BK) {
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < TC_SLOTS * TC_ROWS * 8 / 256; ++i) {
+                const int p = tid + i * 256;
+                const int s = p & 7, row = (p >> 3) & (TC_ROWS - 1), sl = p >> 9;
+                const long gs = (long)blockIdx.x * TC_SLOTS + sl;
+                u32x4 v = {0u, 0u, 0u, 0u};
+                if (gs < a.slots && row >= TC_HALO - halo && row < TC_HALO + TC_TILE + halo) {
+                    const int b = (int)(gs / a.n_tt);
+                    const int t = (int)(gs - (long)b * a.n_tt) * TC_TILE - TC_HALO + row;
+                    if (t >= 0 && t < a.T) v = *reinterpret_cast<const u32x4*>(a.dy + ((long)b * a.T + t) * a.dy_pitch + br.dy_off + c0 + s * 8);
+                }
+                *reinterpret_cast<u32x4*>(slab + tc_off(sl * TC_ROWS + row, s)) = v;
+            }
+            for (int p = tid; p < k * TC_BN * 8; p += 256) {
+                const int s = p & 7, cc = (p >> 3) & (TC_BN - 1), jj = p >> 9;
+                const u32x4 v = *reinterpret_cast<const u32x4*>(br.wt + ((long)(n0 + cc) * k + jj) * a.co + c0 + s * 8);
+                *reinterpret_cast<u32x4*>(wts + tc_off(jj * TC_BN + cc, s)) = v;
+            }
+            __syncthreads();
+            for (int jj = 0; jj < k; ++jj) {
+                const int arow = my_slot * TC_ROWS + TC_HALO + r + (jj - (k - 1) / 2) * a.d;
+                const int brow = jj * TC_BN + nh * 32 + r;
+#pragma unroll
+                for (int kk = 0; kk < TC_BK / 16; ++kk) {
+                    const bf16x8 af = *reinterpret_cast<const bf16x8*>(slab + tc_off(arow, 2 * kk + h));
+                    const bf16x8 bfr = *reinterpret_cast<const bf16x8*>(wts + tc_off(brow, 2 * kk + h));
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bfr, acc, 0, 0, 0);
+                }
+            }
+        }
+        if (br.gate != nullptr) {
+            const float gt = valid ? br.gate[(long)wb * a.n_out + ci] : 0.f;
+            float gp = 0.f;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int t = t0 + (i & 3) + 8 * (i >> 2) + 4 * h;
+                if (valid && t < a.T) gp = __builtin_fmaf(bf2f(a.x[((long)wb * a.T + t) * a.x_pitch + ci]), acc[i], gp);
+                tot[i] = __builtin_fmaf(gt, acc[i], tot[i]);
+            }
+            const float other = __shfl_xor(gp, 32);
+            if (valid && h == 0) a.gpart[(((long)j * a.B + wb) * a.n_tt + wtt) * a.n_out + ci] = gp + other;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) tot[i] += acc[i];
+        }
+    }
+    if (!valid) return;
+    const float ca = a.cadd != nullptr ? a.cadd[(long)wb * a.n_out + ci] * a.cadd_scale : 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int t = t0 + (i & 3) + 8 * (i >> 2) + 4 * h;
+        if (t < a.T) {
+            const long row = (long)wb * a.T + t;
+            float v = tot[i] + ca;
+            if (a.addend != nullptr) v += bf2f(a.addend[row * a.add_pitch + ci]);
+            a.out[row * a.out_pitch + ci] = f2bf(v);
+        }
+    }
+}
+
+// branches: HOST table of nb x 4 64-bit words {k, wt, gate, dy_off}
+extern "C" int svsr_tconv_dgrad(const void* dy, int64_t dy_pitch, int B, int T, int co, int d, int nb, const int64_t* branches, int n_out,
+                                const void* x, int64_t x_pitch, const void* addend, int64_t add_pitch, const float* cadd, float cadd_scale,
+                                void* out, int64_t out_pitch, float* gpart, hipStream_t stream) {
+    if (dy == nullptr || out == nullptr || branches == nullptr) return SVSR_ERR_ARG;
+    if (B < 1 || T < 1 || d < 1 || co < 64 || co % 64 != 0 || dy_pitch % 8 != 0 || ((uintptr_t)dy & 15) != 0) return SVSR_ERR_ARG;
+    if (nb < 1 || nb > 3 || n_out < TC_BN || n_out % TC_BN != 0 || out_pitch < n_out) return SVSR_ERR_ARG;
+    if (addend != nullptr && add_pitch < n_out) return SVSR_ERR_ARG;
+    DArgs a;
+    int kmax = 1;
+    bool gated = false;
+    for (int i = 0; i < 3; ++i) {
+        const int64_t* e = branches + 4 * (i < nb ? i : 0);
+        DBranch& br = a.br[i];
+        br.k = (int)e[0];
+        br.wt = (const bf16_t*)(uintptr_t)e[1];
+        br.gate = (const float*)(uintptr_t)e[2];
+        br.dy_off = (int)e[3];
+        if (e[0] < 1 || e[0] > TC_MAXK || e[0] % 2 == 0) return SVSR_ERR_ARG;
+        if ((e[0] - 1) * (int64_t)d / 2 > TC_HALO) return SVSR_ERR_ARG;
+        if (br.wt == nullptr || ((uintptr_t)br.wt & 15) != 0) return SVSR_ERR_ARG;
+        if (e[3] < 0 || e[3] % 8 != 0 || e[3] + co > dy_pitch) return SVSR_ERR_ARG;
+        if (br.gate != nullptr) gated = true;
+        if (br.k > kmax) kmax = br.k;
+    }
+    if (gated && (x == nullptr || gpart == nullptr || x_pitch < n_out)) return SVSR_ERR_ARG;
+    const long n_tt = (T + TC_TILE - 1) / TC_TILE;
+    const long slots = (long)B * n_tt;
+    if (slots > (1L << 30) || n_out / TC_BN > 65535) return SVSR_ERR_ARG;
+    a.dy = (const bf16_t*)dy; a.x = (const bf16_t*)x; a.addend = (const bf16_t*)addend; a.cadd = cadd; a.out = (bf16_t*)out; a.gpart = gpart;
+    a.dy_pitch = dy_pitch; a.x_pitch = x_pitch; a.add_pitch = add_pitch; a.out_pitch = out_pitch; a.cadd_scale = cadd_scale;
+    a.B = B; a.T = T; a.co = co; a.n_out = n_out; a.d = d; a.nb = nb; a.n_tt = (int)n_tt; a.slots = (int)slots;
+    const size_t lds = TC_SLAB_BYTES + (size_t)kmax * TC_BN * TC_BK * 2;
+    const hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void*>(k_tconv_dgrad), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (ae != hipSuccess) return (int)ae;
+    hipLaunchKernelGGL(k_tconv_dgrad, dim3((unsigned)((slots + TC_SLOTS - 1) / TC_SLOTS), (unsigned)(n_out / TC_BN)), dim3(256), lds, stream, a);
+    return svsr_check_launch();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Weight gradient of one branch: dW[c][j][ci] = sum_{b,t} dacc[b][t][c] * bf16(x * gate)[b][t + (j - (K-1)/2) d][ci], fp32 on MFMA over the rows.
+// One workgroup: 64 output channels x 64 input channels x all K taps; wave w owns the output-channel half w >> 1 and the input-channel half
+// w & 1, K accumulators.  Per pair of slots the gated rows are staged as the forward stages them (one slab serves the K taps), the dacc tile
+// beside them; the MFMA's K dimension is time, so a lane gathers its 8 consecutive rows of one channel with 2-byte LDS reads.  Split s of S
+// takes the slot pairs s, s + S, ... and writes part[s][co][K][n_in]; k_tconv_wgrad_fold adds the splits in order and writes the parameter's
+// own [co][n_valid][K] layout.
+// ---------------------------------------------------------------------------------------------------------------------
+struct WArgs {
+    const bf16_t* x; const bf16_t* dy; const float* gate; float* part;
+    long x_pitch, dy_pitch;
+    int B, T, n_in, co, d, n_tt, slots, S;
+};
+
+__device__ __forceinline__ bf16x8 tc_gather8(const unsigned char* base, int row0, int ch) {
+    u32x4 v;
+    unsigned w[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const unsigned lo = *reinterpret_cast<const unsigned short*>(base + tc_off(row0 + 2 * q, ch >> 3) + (ch & 7) * 2);
+        const unsigned hi = *reinterpret_cast<const unsigned short*>(base + tc_off(row0 + 2 * q + 1, ch >> 3) + (ch & 7) * 2);
+        w[q] = lo | (hi << 16);
+    }
+    v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
+    return __builtin_bit_cast(bf16x8, v);
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void k_tconv_wgrad(WArgs a) {
+    __shared__ __attribute__((aligned(16))) unsigned char slab[TC_SLAB_BYTES];
+    __shared__ __attribute__((aligned(16))) unsigned char dyt[TC_SLOTS * TC_TILE * 128];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int halo = (K - 1) * a.d / 2;
+    const int ci0 = blockIdx.y * 64, co0 = blockIdx.z * 64;
+    const int mh = wave >> 1, nh = wave & 1, r = lane & 31, h = lane >> 5;
+    f32x16 acc[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[j][i] = 0.f;
+    const int npairs = (a.slots + TC_SLOTS - 1) / TC_SLOTS;
+    for (int pr = blockIdx.x; pr < npairs; pr += a.S) {
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < TC_SLOTS * TC_ROWS * 8 / 256; ++i) {
+            const int p = tid + i * 256;
+            const int s = p & 7, row = (p >> 3) & (TC_ROWS - 1), sl = p >> 9;
+            const long gs = (long)pr * TC_SLOTS + sl;
+            u32x4 v = {0u, 0u, 0u, 0u};
+            if (gs < a.slots && row >= TC_HALO - halo && row < TC_HALO + TC_TILE + halo) {
+                const int b = (int)(gs / a.n_tt);
+                const int t = (int)(gs - (long)b * a.n_tt) * TC_TILE - TC_HALO + row;
+                if (t >= 0 && t < a.T) {
+                    v = *reinterpret_cast<const u32x4*>(a.x + ((long)b * a.T + t) * a.x_pitch + ci0 + s * 8);
+                    if (a.gate != nullptr) {
+                        const float4* gp = reinterpret_cast<const float4*>(a.gate + (long)b * a.n_in + ci0 + s * 8);
+                        const float4 g0 = gp[0], g1 = gp[1];
+                        float f[8];
+                        unpack8(v, f);
+                        f[0] *= g0.x; f[1] *= g0.y; f[2] *= g0.z; f[3] *= g0.w;
+                        f[4] *= g1.x; f[5] *= g1.y; f[6] *= g1.z; f[7] *= g1.w;
+                        v = pack8(f);
+                    }
+                }
+            }
+            *reinterpret_cast<u32x4*>(slab + tc_off(sl * TC_ROWS + row, s)) = v;
+        }
+#pragma unroll
+        for (int i = 0; i < TC_SLOTS * TC_TILE * 8 / 256; ++i) {
+            const int p = tid + i * 256;
+            const int s = p & 7, row = (p >> 3) & (TC_TILE - 1), sl = p >> 8;
+            const long gs = (long)pr * TC_SLOTS + sl;
+            u32x4 v = {0u, 0u, 0u, 0u};
+            if (gs < a.slots) {
+                const int b = (int)(gs / a.n_tt);
+                const int t = (int)(gs - (long)b * a.n_tt) * TC_TILE + row;
+                if (t < a.T) v = *reinterpret_cast<const u32x4*>(a.dy + ((long)b * a.T + t) * a.dy_pitch + co0 + s * 8);
+            }
+            *reinterpret_cast<u32x4*>(dyt + tc_off(sl * TC_TILE + row, s)) = v;
+        }
+        __syncthreads();
+#pragma unroll 1
+        for (int sl = 0; sl < TC_SLOTS; ++sl)
+#pragma unroll 1
+            for (int kk = 0; kk < TC_TILE / 16; ++kk) {
+                const bf16x8 af = tc_gather8(dyt, sl * TC_TILE + 16 * kk + 8 * h, mh * 32 + r);
+#pragma unroll
+                for (int j = 0; j < K; ++j) {
+                    const bf16x8 bfr = tc_gather8(slab, sl * TC_ROWS + TC_HALO + 16 * kk + 8 * h + (j - (K - 1) / 2) * a.d, nh * 32 + r);
+                    acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bfr, acc[j], 0, 0, 0);
+                }
+            }
+    }
+    // lane = input channel, registers = output channels
+    const int ci = ci0 + nh * 32 + r;
+#pragma unroll
+    for (int j = 0; j < K; ++j)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int c = co0 + mh * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+            a.part[(((long)blockIdx.x * a.co + c) * K + j) * a.n_in + ci] = acc[j][i];
+        }
+}
+
+__global__ __launch_bounds__(256) void k_tconv_wgrad_fold(const float* __restrict__ part, int S, int co, int K, int n_in, int n_valid,
+                                                          float* __restrict__ dw, int add) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    const long n = (long)co * n_valid * K;
+    if (i >= n) return;
+    const int j = (int)(i % K);
+    const long q = i / K;
+    const int ci = (int)(q % n_valid);
+    const int c = (int)(q / n_valid);
+    const long stride = (long)co * K * n_in;
+    const float* p = part + ((long)c * K + j) * n_in + ci;
+    float s = 0.f;
+    for (int sp = 0; sp < S; ++sp) s += p[sp * stride];
+    dw[i] = add ? dw[i] + s : s;
+}
+
+extern "C" int svsr_tconv_wgrad(const void* x, int64_t x_pitch, const float* gate, const void* dy, int64_t dy_pitch, int B, int T, int n_in, int co,
+                                int k, int d, int splits, float* part, float* dw, int n_valid, int add, hipStream_t stream) {
+    if (x == nullptr || dy == nullptr || part == nullptr || dw == nullptr) return SVSR_ERR_ARG;
+    if (B < 1 || T < 1 || d < 1 || n_in < 64 || n_in % 64 != 0 || x_pitch < n_in || x_pitch % 8 != 0 || ((uintptr_t)x & 15) != 0) return SVSR_ERR_ARG;
+    if (co < 64 || co % 64 != 0 || dy_pitch < co || dy_pitch % 8 != 0 || ((uintptr_t)dy & 15) != 0) return SVSR_ERR_ARG;
+    if (k < 1 || k > TC_MAXK || k % 2 == 0 || (k - 1) * (int64_t)d / 2 > TC_HALO) return SVSR_ERR_ARG;
+    if (gate != nullptr && ((uintptr_t)gate & 15) != 0) return SVSR_ERR_ARG;
+    if (n_valid < 1 || n_valid > n_in) return SVSR_ERR_ARG;
+    const long n_tt = (T + TC_TILE - 1) / TC_TILE;
+    const long slots = (long)B * n_tt;
+    const long npairs = (slots + TC_SLOTS - 1) / TC_SLOTS;
+    if (slots > (1L << 30) || splits < 1 || splits > npairs || splits > 65535 || n_in / 64 > 65535 || co / 64 > 65535) return SVSR_ERR_ARG;
+    WArgs a;
+    a.x = (const bf16_t*)x; a.dy = (const bf16_t*)dy; a.gate = gate; a.part = part; a.x_pitch = x_pitch; a.dy_pitch = dy_pitch;
+    a.B = B; a.T = T; a.n_in = n_in; a.co = co; a.d = d; a.n_tt = (int)n_tt; a.slots = (int)slots; a.S = splits;
+    const dim3 grid((unsigned)splits, (unsigned)(n_in / 64), (unsigned)(co / 64));
+    if (k == 1) hipLaunchKernelGGL(k_tconv_wgrad<1>, grid, dim3(256), 0, stream, a);
+    else if (k == 3) hipLaunchKernelGGL(k_tconv_wgrad<3>, grid, dim3(256), 0, stream, a);
+    else if (k == 5) hipLaunchKernelGGL(k_tconv_wgrad<5>, grid, dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(k_tconv_wgrad<7>, grid, dim3(256), 0, stream, a);
+    int rc = svsr_check_launch();
+    if (rc != SVSR_OK) return rc;
+    const long n = (long)co * n_valid * k;
+    hipLaunchKernelGGL(k_tconv_wgrad_fold, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const float*)part, splits, co, k, n_in, n_valid, dw, add);
+    return svsr_check_launch();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Squeeze-and-excitation backward, SE_CLIPS clips per workgroup as k_tcn_se: the time mean m and a1 = W1 m are recomputed, the gate is the
+// forward's.  dgate = sum over time tiles of gpart (ascending); da2 = dgate * gate * (1 - gate); dhid = W2^T da2; da1 = dhid * swish'(a1);
+// dm += W1^T da1 over the branches in order.  Written per clip: da2 [nb][B][n_in], da1 and hid [nb][B][R], mean and dm [B][n_in] — the
+// weight gradients dW2 = sum_b da2 (x) hid, dW1 = sum_b da1 (x) m are k_tcn_se_wgrad's (b ascending).
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_tcn_se_bwd(const bf16_t* __restrict__ x, long x_pitch, int B, int T, int n_in, int R, int nb, int n_tt,
+                                                    const bf16_t* __restrict__ w1, const bf16_t* __restrict__ w2, const float* __restrict__ gate,
+                                                    const float* __restrict__ gpart, float* __restrict__ da2_o, float* __restrict__ da1_o,
+                                                    float* __restrict__ hid_o, float* __restrict__ mean_o, float* __restrict__ dm_o) {
+    extern __shared__ float se_sm[];
+    float* mean = se_sm;                               // [SE_CLIPS][n_in]
+    float* da2 = mean + SE_CLIPS * n_in;               // [SE_CLIPS][n_in]
+    float* dm = da2 + SE_CLIPS * n_in;                 // [SE_CLIPS][n_in]
+    float* a1 = dm + SE_CLIPS * n_in;                  // [SE_CLIPS][R]
+    float* da1 = a1 + SE_CLIPS * R;                    // [SE_CLIPS][R]
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int b0 = blockIdx.x * SE_CLIPS;
+    const int pieces = n_in >> 3;
+    const float inv_t = 1.0f / (float)T;
+    for (int p = tid; p < SE_CLIPS * pieces; p += 256) {
+        const int cl = p / pieces, pc = p - cl * pieces;
+        float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (b0 + cl < B) {
+            const bf16_t* xp = x + (long)(b0 + cl) * T * x_pitch + pc * 8;
+            for (int t = 0; t < T; ++t) {
+                float f[8];
+                unpack8(*reinterpret_cast<const u32x4*>(xp + (long)t * x_pitch), f);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) s[i] += f[i];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            mean[cl * n_in + pc * 8 + i] = s[i] * inv_t;
+            dm[cl * n_in + pc * 8 + i] = 0.f;
+        }
+    }
+    for (int br = 0; br < nb; ++br) {
+        __syncthreads();
+        const bf16_t* w1b = w1 + (long)br * R * n_in;
+        const bf16_t* w2b = w2 + (long)br * n_in * R;
+        for (int j = wave; j < R; j += 4) {             // a1 = W1 m, exactly as the forward sums it
+            float d[SE_CLIPS];
+#pragma unroll
+            for (int cl = 0; cl < SE_CLIPS; ++cl) d[cl] = 0.f;
+            for (int pc = lane; pc < pieces; pc += 64) {
+                float f[8];
+                unpack8(*reinterpret_cast<const u32x4*>(w1b + (long)j * n_in + pc * 8), f);
+#pragma unroll
+                for (int cl = 0; cl < SE_CLIPS; ++cl)
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) d[cl] = __builtin_fmaf(f[i], mean[cl * n_in + pc * 8 + i], d[cl]);
+            }
+#pragma unroll
+            for (int cl = 0; cl < SE_CLIPS; ++cl) {
+                const float v = wave_sum(d[cl]);
+                if (lane == 0) a1[cl * R + j] = v;
+            }
+        }
+        for (int p = tid; p < SE_CLIPS * n_in; p += 256) {
+            const int cl = p / n_in, c = p - cl * n_in;
+            float v = 0.f;
+            if (b0 + cl < B) {
+                const long base = ((long)br * B + b0 + cl);
+                float dg = 0.f;
+                for (int tt = 0; tt < n_tt; ++tt) dg += gpart[(base * n_tt + tt) * n_in + c];
+                const float g = gate[base * n_in + c];
+                v = dg * g * (1.0f - g);
+                da2_o[base * n_in + c] = v;
+            }
+            da2[p] = v;
+        }
+        __syncthreads();
+        for (int j = wave; j < R; j += 4) {             // dhid[j] = sum_c W2[c][j] da2[c]
+            float d[SE_CLIPS];
+#pragma unroll
+            for (int cl = 0; cl < SE_CLIPS; ++cl) d[cl] = 0.f;
+            for (int c = lane; c < n_in; c += 64) {
+                const float w = bf2f(w2b[(long)c * R + j]);
+#pragma unroll
+                for (int cl = 0; cl < SE_CLIPS; ++cl) d[cl] = __builtin_fmaf(w, da2[cl * n_in + c], d[cl]);
+            }
+#pragma unroll
+            for (int cl = 0; cl < SE_CLIPS; ++cl) {
+                const float v = wave_sum(d[cl]);
+                if (lane == 0) {
+                    const float z = a1[cl * R + j];
+                    const float g1 = v * swish_grad(z);
+                    da1[cl * R + j] = g1;
+                    if (b0 + cl < B) {
+                        da1_o[((long)br * B + b0 + cl) * R + j] = g1;
+                        hid_o[((long)br * B + b0 + cl) * R + j] = swish(z);
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        for (int p = tid; p < SE_CLIPS * n_in; p += 256) {       // dm[c] += sum_j W1[j][c] da1[j]
+            const int cl = p / n_in, c = p - cl * n_in;
+            float s = 0.f;
+            for (int j = 0; j < R; ++j) s = __builtin_fmaf(bf2f(w1b[(long)j * n_in + c]), da1[cl * R + j], s);
+            dm[p] += s;
+        }
+    }
+    __syncthreads();
+    for (int p = tid; p < SE_CLIPS * n_in; p += 256) {
+        const int cl = p / n_in, c = p - cl * n_in;
+        if (b0 + cl < B) {
+            mean_o[(long)(b0 + cl) * n_in + c] = mean[p];
+            dm_o[(long)(b0 + cl) * n_in + c] = dm[p];
+        }
+    }
+}
+
+struct SEW { float* dw1[3]; float* dw2[3]; };
+// blockIdx.y = branch, blockIdx.z = 0: dW1 [R][n_in], 1: dW2 [n_in][R]
+__global__ __launch_bounds__(256) void k_tcn_se_wgrad(const float* __restrict__ da2, const float* __restrict__ da1, const float* __restrict__ hid,
+                                                      const float* __restrict__ mean, int B, int n_in, int R, SEW o, int add) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)n_in * R) return;
+    const int br = blockIdx.y;
+    float s = 0.f;
+    float* dst;
+    if (blockIdx.z == 0) {
+        const int j = (int)(i / n_in), c = (int)(i - (long)j * n_in);
+        for (int b = 0; b < B; ++b) s = __builtin_fmaf(da1[((long)br * B + b) * R + j], mean[(long)b * n_in + c], s);
+        dst = o.dw1[br] + i;
+    } else {
+        const int c = (int)(i / R), j = (int)(i - (long)c * R);
+        for (int b = 0; b < B; ++b) s = __builtin_fmaf(da2[((long)br * B + b) * n_in + c], hid[((long)br * B + b) * R + j], s);
+        dst = o.dw2[br] + i;
+    }
+    *dst = add ? *dst + s : s;
+}
+
+// work: fp32 scratch of nb*B*n_in + 2*nb*B*R + B*n_in floats; dm fp32 [B][n_in]; dw: HOST table of 2 x nb pointers {dW1_0.., dW2_0..}
+extern "C" int svsr_tcn_se_bwd(const void* x, int64_t x_pitch, int B, int T, int n_in, int R, int nb, const void* w1, const void* w2, const float* gate,
+                               const float* gpart, float* work, float* dm, const int64_t* dw, int add, hipStream_t stream) {
+    if (x == nullptr || w1 == nullptr || w2 == nullptr || gate == nullptr || gpart == nullptr || work == nullptr || dm == nullptr || dw == nullptr) return SVSR_ERR_ARG;
+    if (B < 1 || T < 1 || n_in < 64 || n_in % 64 != 0 || x_pitch < n_in || x_pitch % 8 != 0 || nb < 1 || nb > 3) return SVSR_ERR_ARG;
+    if (R < 4 || R % 4 != 0 || R > n_in) return SVSR_ERR_ARG;
+    if ((((uintptr_t)x | (uintptr_t)w1) & 15) != 0) return SVSR_ERR_ARG;
+    const size_t lds = (size_t)SE_CLIPS * (3 * n_in + 2 * R) * sizeof(float);
+    if (lds > 64 * 1024) return SVSR_ERR_ARG;
+    SEW o;
+    for (int i = 0; i < 3; ++i) {
+        o.dw1[i] = (float*)(uintptr_t)dw[i < nb ? i : 0];
+        o.dw2[i] = (float*)(uintptr_t)dw[nb + (i < nb ? i : 0)];
+        if (o.dw1[i] == nullptr || o.dw2[i] == nullptr) return SVSR_ERR_ARG;
+    }
+    const int n_tt = (T + TC_TILE - 1) / TC_TILE;
+    float* da2 = work;
+    float* da1 = da2 + (long)nb * B * n_in;
+    float* hid = da1 + (long)nb * B * R;
+    float* mean = hid + (long)nb * B * R;
+    hipLaunchKernelGGL(k_tcn_se_bwd, dim3((unsigned)((B + SE_CLIPS - 1) / SE_CLIPS)), dim3(256), lds, stream, (const bf16_t*)x, (long)x_pitch, B, T, n_in, R,
+                       nb, n_tt, (const bf16_t*)w1, (const bf16_t*)w2, gate, gpart, da2, da1, hid, mean, dm);
+    int rc = svsr_check_launch();
+    if (rc != SVSR_OK) return rc;
+    const long n = (long)n_in * R;
+    hipLaunchKernelGGL(k_tcn_se_wgrad, dim3((unsigned)((n + 255) / 256), (unsigned)nb, 2u), dim3(256), 0, stream, (const float*)da2, (const float*)da1,
+                       (const float*)hid, (const float*)mean, B, n_in, R, o, add);
+    return svsr_check_launch();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// norm5 + masked mean backward: g[b][t][c] = dh[b][t][c] + dpooled[b][c] * mask[b][t] / (sum_t mask + 1e-6);  dx = bf16(g * scale[c]);
+// part[b][0][c] = sum_t g, part[b][1][c] = sum_t g * x (t ascending), folded over the clips in order into sums [2][C].
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_tcn_norm_pool_bwd(const bf16_t* __restrict__ dh, const bf16_t* __restrict__ dpooled, const bf16_t* __restrict__ x,
+                                                           long x_pitch, int B, int T, int C, const float* __restrict__ scale,
+                                                           const float* __restrict__ mask, bf16_t* __restrict__ dx, long dx_pitch, float* __restrict__ part) {
+    const int pieces = C >> 3;
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= (long)B * pieces) return;
+    const int b = (int)(p / pieces), c0 = (int)(p - (long)b * pieces) * 8;
+    float sc[8], dp[8], s0[8], s1[8];
+    unpack8(*reinterpret_cast<const u32x4*>(dpooled + (long)b * C + c0), dp);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { sc[i] = scale[c0 + i]; s0[i] = 0.f; s1[i] = 0.f; }
+    float msum = 0.f;
+    for (int t = 0; t < T; ++t) msum += mask[(long)b * T + t];
+    const float inv = 1.0f / (msum + 1e-6f);
+    for (int t = 0; t < T; ++t) {
+        const long row = (long)b * T + t;
+        float g[8], xv[8];
+        unpack8(*reinterpret_cast<const u32x4*>(dh + row * C + c0), g);
+        unpack8(*reinterpret_cast<const u32x4*>(x + row * x_pitch + c0), xv);
+        const float m = mask[row] * inv;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            g[i] = __builtin_fmaf(dp[i], m, g[i]);
+            s0[i] += g[i];
+            s1[i] = __builtin_fmaf(g[i], xv[i], s1[i]);
+            g[i] *= sc[i];
+        }
+        *reinterpret_cast<u32x4*>(dx + row * dx_pitch + c0) = pack8(g);
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        part[((long)b * 2) * C + c0 + i] = s0[i];
+        part[((long)b * 2 + 1) * C + c0 + i] = s1[i];
+    }
+}
+
+extern "C" int svsr_tcn_norm_pool_bwd(const void* dh, const void* dpooled, const void* x, int64_t x_pitch, int B, int T, int C, const float* scale,
+                                      const float* mask, void* dx, int64_t dx_pitch, float* part, float* sums, hipStream_t stream) {
+    if (dh == nullptr || dpooled == nullptr || x == nullptr || scale == nullptr || mask == nullptr || dx == nullptr || part == nullptr || sums == nullptr)
+        return SVSR_ERR_ARG;
+    if (B < 1 || T < 1 || C < 8 || C % 8 != 0 || x_pitch < C || x_pitch % 8 != 0 || dx_pitch < C || dx_pitch % 8 != 0) return SVSR_ERR_ARG;
+    if ((((uintptr_t)dh | (uintptr_t)dpooled | (uintptr_t)x | (uintptr_t)dx) & 15) != 0) return SVSR_ERR_ARG;
+    const long n = (long)B * (C >> 3);
+    if (n > (1L << 36)) return SVSR_ERR_ARG;
+    hipLaunchKernelGGL(k_tcn_norm_pool_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const bf16_t*)dh, (const bf16_t*)dpooled,
+                       (const bf16_t*)x, (long)x_pitch, B, T, C, scale, mask, (bf16_t*)dx, (long)dx_pitch, part);
+    int rc = svsr_check_launch();
+    if (rc != SVSR_OK) return rc;
+    return svsr_tcn_fold(part, B, 2L * C, sums, 0, stream);
 }

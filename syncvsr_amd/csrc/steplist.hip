@@ -85,6 +85,8 @@ const std::unordered_map<std::string, Entry>& registry() {
         SVSR_REG(svsr_beam_select), SVSR_REG(svsr_ctc_prefix_score_clips), SVSR_REG(svsr_mha_src_step_fwd), SVSR_REG(svsr_ctc_align),
         SVSR_REG(svsr_ctc_frame_best), SVSR_REG(svsr_ctc_collapse), SVSR_REG(svsr_edit_distance),
         SVSR_REG(svsr_tconv_fwd), SVSR_REG(svsr_tcn_se_fwd), SVSR_REG(svsr_tcn_norm_pool_fwd),
+        SVSR_REG(svsr_tconv_fwd_save), SVSR_REG(svsr_tconv_epi_bwd), SVSR_REG(svsr_tconv_dgrad), SVSR_REG(svsr_tconv_wgrad), SVSR_REG(svsr_tcn_se_bwd),
+        SVSR_REG(svsr_tcn_norm_pool_bwd), SVSR_REG(svsr_tcn_fold),
         SVSR_REG(svsr_lrs_clip_prep), SVSR_REG(svsr_wave_prep),
         SVSR_REG(svsr_lrw_clip_sums), SVSR_REG(svsr_lrw_clip_mix),
         SVSR_REG(svsr_vq_conv0_stats), SVSR_REG(svsr_vq_conv0_apply), SVSR_REG(svsr_vq_gn_partial), SVSR_REG(svsr_vq_gn_relu), SVSR_REG(svsr_vq_project),

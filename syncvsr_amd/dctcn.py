@@ -3,8 +3,10 @@
 followed by the densely connected temporal convolution network (``tcn/models/densetcn.py``) with squeeze-and-excitation gates, the masked-mean
 consensus and the two heads.
 
-EVAL / INFERENCE PATH ONLY (``validation_step`` / ``test_step`` / ``inference.py``): a forward in training mode raises NotImplementedError
-(mixup, dropout, batch-statistic BatchNorm1d and the backward are not built), it never runs a wrong forward silently.
+EVAL / INFERENCE PATH (``validation_step`` / ``test_step`` / ``inference.py``) and, in the same statistics mode, the gradients of the temporal
+network and the two heads (``loss_and_backend_grads``: fine-tuning with the front-end and the BatchNorm statistics frozen).  A forward in
+training mode raises NotImplementedError (mixup, dropout, batch-statistic BatchNorm1d and the front-end backward are not built): it never
+runs a wrong forward silently.
 
 Back-end layout (csrc/dctcn.hip): channels-last bf16 rows; ONE [B*T, reduced + layers * growth] buffer per dense block is the feature
 stack (a layer reads a channel prefix through the row pitch and writes its channels at an offset: no ``torch.cat``).  Per layer: one launch
@@ -191,9 +193,21 @@ class DCTCNLightningModule(_StoreModule):
         return P
 
     # ------------------------------------------------------------------------------------------------
-    def _backend(self, st: _ParamStore, feats: torch.Tensor, word_mask: Optional[torch.Tensor], B: int, T: int, keep: Optional[dict] = None):
-        """feats bf16 [B*T, 512] -> the last block's feature stack bf16 [B*T, C] (before norm5)."""
+    @staticmethod
+    def _tconv(tape: Optional[dict], key, x, *, co, branches, **kw):
+        """ops.tconv_fwd; with a tape the same kernel's saving instantiation: the fp32 accumulators are kept under tape["acc"][key]."""
+        if tape is None:
+            return ops.tconv_fwd(x, co=co, branches=branches, **kw)
+        acc = torch.empty((x.shape[0], len(branches) * co), dtype=torch.float32, device=x.device)
+        tape["acc"][key] = acc
+        return ops.tconv_fwd_save(x, co=co, branches=branches, acc=acc, **kw)
+
+    def _backend(self, st: _ParamStore, feats: torch.Tensor, word_mask: Optional[torch.Tensor], B: int, T: int, keep: Optional[dict] = None,
+                 tape: Optional[dict] = None):
+        """feats bf16 [B*T, 512] -> the last block's feature stack bf16 [B*T, C] (before norm5).  tape: what the backward reads is kept."""
         P, dm, dev = self._prepare(st), self.dims, feats.device
+        if tape is not None:
+            tape.update(acc={}, layers=[], stacks=[])
         R = dm["reduced"]
         if self.use_boundary:
             if word_mask is None:
@@ -205,7 +219,10 @@ class DCTCNLightningModule(_StoreModule):
             x0 = feats
         width = lambda bi: R + dm["blocks"][bi] * dm["growth"][bi]          # noqa: E731
         stack = torch.empty((B * T, width(0)), dtype=BF16, device=dev)
-        ops.tconv_fwd(x0, B=B, T=T, n_in=x0.shape[1], d=1, branches=[P["t0"]], co=R, act=ops.ACT_PRELU, out=stack)
+        self._tconv(tape, "t0", x0, B=B, T=T, n_in=x0.shape[1], d=1, branches=[P["t0"]], co=R, act=ops.ACT_PRELU, out=stack)
+        if tape is not None:
+            tape["x0"] = x0
+            tape["stacks"].append(stack)
         if keep is not None:
             keep["transition0"] = stack[:, :R].float().view(B, T, R)
         nlayers = len(P["layers"])
@@ -213,40 +230,57 @@ class DCTCNLightningModule(_StoreModule):
             n_in, g, gb, d, bi = L["n_in"], L["g"], L["gb"], L["d"], L["bi"]
             gates = ops.tcn_se_fwd(stack, L["se_w1"], L["se_w2"], B=B, T=T, n_in=n_in)
             out0 = torch.empty((B * T, g), dtype=BF16, device=dev)
-            ops.tconv_fwd(stack, B=B, T=T, n_in=n_in, d=d, branches=[dict(br, gate=gates[j]) for j, br in enumerate(L["stage0"])], co=gb,
-                          act=ops.ACT_SWISH, out=out0)
+            self._tconv(tape, (i, 0), stack, B=B, T=T, n_in=n_in, d=d, branches=[dict(br, gate=gates[j]) for j, br in enumerate(L["stage0"])], co=gb,
+                        act=ops.ACT_SWISH, out=out0)
             res = torch.empty((B * T, g), dtype=BF16, device=dev)
             ops.tconv_fwd(stack, B=B, T=T, n_in=n_in, d=1, branches=[L["down"]], co=g, act=ops.ACT_NONE, out=res)
-            ops.tconv_fwd(out0, B=B, T=T, n_in=g, d=d, branches=L["stage1"], co=gb, act=ops.ACT_SWISH, out=stack, res=res, res_act=ops.ACT_SWISH)
+            self._tconv(tape, (i, 1), out0, B=B, T=T, n_in=g, d=d, branches=L["stage1"], co=gb, act=ops.ACT_SWISH, out=stack, res=res,
+                        res_act=ops.ACT_SWISH)
+            if tape is not None:
+                tape["layers"].append(dict(stack=stack, gates=gates, out0=out0, res=res))
             if i + 1 == nlayers or P["layers"][i + 1]["bi"] != bi:
                 if keep is not None:
                     keep[f"denseblock{bi + 1}"] = stack.float().view(B, T, -1)
                 if bi in P["trans"]:
                     tr = P["trans"][bi]
                     nxt = torch.empty((B * T, width(bi + 1)), dtype=BF16, device=dev)
-                    ops.tconv_fwd(stack, B=B, T=T, n_in=tr["n_in"], d=1, branches=[tr], co=R, act=ops.ACT_SWISH, out=nxt)
+                    self._tconv(tape, ("tr", bi), stack, B=B, T=T, n_in=tr["n_in"], d=1, branches=[tr], co=R, act=ops.ACT_SWISH, out=nxt)
                     stack = nxt
+                    if tape is not None:
+                        tape["stacks"].append(stack)
         return stack
 
-    def _run(self, videos: torch.Tensor, word_mask, attention_mask, keep: Optional[dict] = None):
+    def _run(self, videos: torch.Tensor, word_mask, attention_mask, keep: Optional[dict] = None, tape: Optional[dict] = None,
+             feats: Optional[torch.Tensor] = None):
+        """feats (bf16 [B*T, 512], with videos = the (B, T) pair): the front-end is skipped (loss_and_backend_grads_from_features)."""
         if self.training:
             raise NotImplementedError("DCTCNLightningModule: only the eval / inference path is built (no mixup, dropout, batch-statistic "
                                       "BatchNorm1d or backward yet): call .eval() first")
-        if videos.device.type != "cuda":
+        src = videos if feats is None else feats
+        if src.device.type != "cuda":
             raise RuntimeError("syncvsr_amd runs on an MI355X HIP device only; there is no CPU fallback")
-        if videos.dim() != 5 or videos.size(1) != 1:
-            raise ValueError("videos must be [B, 1, T, H, W]")
+        if feats is None:
+            if videos.dim() != 5 or videos.size(1) != 1:
+                raise ValueError("videos must be [B, 1, T, H, W]")
+            B, _, T = videos.shape[:3]
+        else:
+            B, T = videos
+            if feats.dtype != BF16 or tuple(feats.shape) != (B * T, 512) or not feats.is_contiguous():
+                raise ValueError("features must be a contiguous bf16 [B*T, 512] tensor")
         st = self.store()
         self._prepare(st)
-        B, _, T = videos.shape[:3]
         C = self.dims["out_size"]
         with torch.no_grad():
-            feats = _frontend_forward(self, st, {}, videos.float().contiguous(), False)
-            stack = self._backend(st, feats, word_mask, B, T, keep)
+            if feats is None:
+                feats = _frontend_forward(self, st, {}, videos.float().contiguous(), False)
+            stack = self._backend(st, feats, word_mask, B, T, keep, tape)
             if attention_mask is None:
-                attention_mask = torch.ones((B, T), dtype=torch.float32, device=videos.device)
+                attention_mask = torch.ones((B, T), dtype=torch.float32, device=src.device)
             scale, shift = self._prep["norm5"]
-            h, pooled = ops.tcn_norm_pool_fwd(stack, scale, shift, attention_mask.to(torch.float32).contiguous(), B=B, T=T, C=C)
+            mask = attention_mask.to(torch.float32).contiguous()
+            h, pooled = ops.tcn_norm_pool_fwd(stack, scale, shift, mask, B=B, T=T, C=C)
+            if tape is not None:
+                tape.update(mask=mask, pooled=pooled, B=B, T=T)
             logits_c, _ = ops.linear_fwd(pooled, st.s16("video_classifier.weight"), st.p32("video_classifier.bias"), rows=B, K=C,
                                          N=self.dims["classes"], x_pitch=C, out_f32=True)
         return st, h, logits_c
@@ -265,26 +299,220 @@ class DCTCNLightningModule(_StoreModule):
                 attention_mask: torch.Tensor) -> dict[str, torch.Tensor]:
         """lightning.py:255-312 in eval mode (lam = 0).  audios: pre-computed vq-wav2vec tokens int64 [B, >= A*T, 2], or, with the tokeniser
         attached (attach_audio_codec), float waveforms [B, L] / [B, 1, L] on the device."""
-        B, _, T = videos.shape[:3]
+        return self._losses(videos, audios, labels, word_mask, attention_mask, None)
+
+    def _losses(self, videos, audios, labels, word_mask, attention_mask, tape: Optional[dict], feats=None) -> dict[str, torch.Tensor]:
+        """The eval forward; with a tape (loss_and_backend_grads) the same launches keep what the backward reads."""
+        B, T = (videos.shape[0], videos.shape[2]) if feats is None else videos
         A, G, V = self.audio_alignment, self.vq_groups, self.audio_vocab_size
         audios = self._tokenize_waveforms(audios, T * A)
         if audios.dtype != torch.int64 or audios.dim() != 3 or audios.size(2) != G:
             raise ValueError("pass pre-computed audio tokens int64 [B, >= A*T, 2] in the `audios` slot (no audio tokeniser is attached)")
         if audios.size(1) < T * A:
             raise ValueError(f"audio tokens have {audios.size(1)} steps, need >= {T * A}")
-        st, h, logits_c = self._run(videos, word_mask, attention_mask)
+        st, h, logits_c = self._run(videos, word_mask, attention_mask, None, tape, feats)
         C, NA = self.dims["out_size"], A * G * V
         with torch.no_grad():
             lab = labels.long().contiguous()
-            loss_c, _ = ops.ce_fwd(logits_c, self.dims["classes"], lab, None, B, self.dims["classes"], self.label_smoothing)
+            loss_c, lse_c = ops.ce_fwd(logits_c, self.dims["classes"], lab, None, B, self.dims["classes"], self.label_smoothing)
             tok = audios[:, : T * A].contiguous().reshape(-1)
             # (the logits are stored: svsr_linear_ce_ok takes K up to 576, the shipped width is 1664)
             logits_a, _ = ops.linear_fwd(h, st.s16("audio_projection.weight"), st.p32("audio_projection.bias"), rows=B * T, K=C, N=NA, x_pitch=C)
-            loss_a, _ = ops.ce_fwd(logits_a, V, tok, None, B * T * A * G, V, 0.0)
+            loss_a, lse_a = ops.ce_fwd(logits_a, V, tok, None, B * T * A * G, V, 0.0)
             acc = ops.topk_acc(logits_c, lab, None)
             loss_total = ops.lincomb2(loss_c, loss_a, self.lambda_audio)
         self._last = dict(last_hidden_states=h, logits_category=logits_c, logits_audio=logits_a)
+        if tape is not None:
+            tape.update(st=st, h=h, logits_c=logits_c, logits_a=logits_a, lab=lab, tok=tok, lse_c=lse_c, lse_a=lse_a)
         return {"loss_total": loss_total, "loss_category": loss_c, "loss_audio": loss_a, "accuracy_top1": acc[0], "accuracy_top5": acc[1]}
+
+    # ------------------------------------------------------------------------------------------------
+    # backward of the back-end and the two heads (statistics mode of the eval forward: running-statistic BatchNorm, no dropout, lam = 0)
+    # ------------------------------------------------------------------------------------------------
+    def backend_parameters(self) -> list:
+        """The nn.Parameters loss_and_backend_grads fills: everything but the front-end, in state-dict order."""
+        return [p for n, p in self.named_parameters() if self._fwd_rank(n) == 2]
+
+    def _prepare_bwd(self, st: _ParamStore) -> dict:
+        """Transposed, tap-flipped shadows for the data gradients and the per-stage BatchNorm vectors (rebuilt with _prepare's)."""
+        P = self._prepare(st)
+        if "bwd" in P:
+            return P["bwd"]
+        ks, dev = self.dims["ks"], st.device
+        wt = lambda name: ops.tconv_wt(st.s16(name).view(st.offsets[name][2]))          # noqa: E731
+        Q: dict[str, Any] = dict(layers=[], trans={})
+        t0 = f"{TCN}.transition0.conv.weight"
+        w = torch.zeros((self.in_pad, 1, self.dims["reduced"]), dtype=BF16, device=dev)
+        w[: self.dims["in_size"]] = wt(t0)
+        Q["t0_wt"] = w
+        layers, trans = dctcn_layers(self.config)
+        for (p, n_in, g, d, bi), L in zip(layers, P["layers"]):
+            q: dict[str, Any] = dict(p=p, down_wt=wt(f"{p}.downsample.weight"))
+            for stage in (0, 1):
+                q[f"wt{stage}"] = [wt(f"{p}.cbcr{stage}_{i}.net.0.weight") for i in range(len(ks))]
+                q[f"scale{stage}"] = torch.cat([br["scale"] for br in L[f"stage{stage}"]]).contiguous()
+                q[f"shift{stage}"] = torch.cat([br["shift"] for br in L[f"stage{stage}"]]).contiguous()
+            Q["layers"].append(q)
+        for name, n, bi in trans:
+            Q["trans"][bi] = dict(name=name, wt=wt(f"{name}.conv.weight"))
+
+        def head_t(name):                    # [N, K] -> [K, N padded to 64] for ops.linear_dgrad
+            N, K = st.offsets[name][2]
+            out = torch.zeros((K, (N + 63) // 64 * 64), dtype=BF16, device=dev)
+            out[:, :N] = st.s16(name).view(N, K).t()
+            return out
+        Q["wc_t"], Q["wa_t"] = head_t("video_classifier.weight"), head_t("audio_projection.weight")
+        P["bwd"] = Q
+        return Q
+
+    def _grad_of(self, st: _ParamStore, name: str, accumulate: bool):
+        """-> (the fp32 gradient buffer of `name` in the parameter's own layout, add?).  The buffer is the store's; a .grad that is None or a
+        foreign tensor is replaced by it (a foreign one's values are carried over when accumulating)."""
+        p = st._params[name]
+        view = st._view(st.grad, name)
+        if accumulate and p.grad is None:
+            view.zero_()          # nothing to add to: every tensor of one call then shares one flag (the SE launch writes six of them)
+        elif accumulate and p.grad.data_ptr() != view.data_ptr():
+            view.copy_(p.grad)
+        p.grad = view
+        return view, accumulate
+
+    @staticmethod
+    def _put(dst: torch.Tensor, add: bool, val: torch.Tensor) -> None:
+        if add:
+            dst.add_(val.view(dst.shape))
+        else:
+            dst.copy_(val.view(dst.shape))
+
+    def _bn_grads(self, st, accumulate, sums, bn: str, bias: Optional[str], lo: int = 0, hi: Optional[int] = None) -> None:
+        s0, s1 = sums[0, lo:hi], sums[1, lo:hi]
+        dw, db, dcb = ops.bn_conv_param_grads(s0, s1, st.p32(f"{bn}.weight"), st.buffers[f"{bn}.running_mean"], st.buffers[f"{bn}.running_var"],
+                                             None if bias is None else st.p32(bias))
+        self._put(*self._grad_of(st, f"{bn}.weight", accumulate), dw)
+        self._put(*self._grad_of(st, f"{bn}.bias", accumulate), db)
+        if bias is not None:
+            self._put(*self._grad_of(st, bias, accumulate), dcb)
+
+    def loss_and_backend_grads(self, videos: torch.Tensor, audios: torch.Tensor, labels: torch.Tensor, word_mask: torch.Tensor,
+                               attention_mask: torch.Tensor, loss_scale: float = 1.0, accumulate: bool = False,
+                               want_input_grad: bool = False) -> dict[str, torch.Tensor]:
+        """The eval forward (the same launches: the metrics are forward()'s bits) followed by the hand-written backward of the temporal network
+        and the two heads: afterwards every parameter of backend_parameters() has .grad = d(loss_total * loss_scale)/d(param) in fp32
+        (accumulate=True adds to an existing .grad).  The front-end and every BatchNorm running statistic are frozen and untouched.  With
+        want_input_grad the dict also carries "grad_features": bf16 [B*T, 512], the gradient of the front-end features."""
+        tape: dict[str, Any] = {}
+        out = self._losses(videos, audios, labels, word_mask, attention_mask, tape)
+        with torch.no_grad():
+            gf = self._backward(tape, float(loss_scale), bool(accumulate), bool(want_input_grad))
+        if want_input_grad:
+            out["grad_features"] = gf
+        return out
+
+    def loss_and_backend_grads_from_features(self, feats: torch.Tensor, B: int, T: int, audios: torch.Tensor, labels: torch.Tensor,
+                                             word_mask: torch.Tensor, attention_mask: torch.Tensor, loss_scale: float = 1.0,
+                                             accumulate: bool = False, want_input_grad: bool = False) -> dict[str, torch.Tensor]:
+        """loss_and_backend_grads from pre-computed front-end features (bf16 [B*T, 512]) instead of videos: the frozen front-end need not
+        run again for a clip whose features are cached (and what scripts/dctcn_bench.py --backward times)."""
+        tape: dict[str, Any] = {}
+        out = self._losses((int(B), int(T)), audios, labels, word_mask, attention_mask, tape, feats)
+        with torch.no_grad():
+            gf = self._backward(tape, float(loss_scale), bool(accumulate), bool(want_input_grad))
+        if want_input_grad:
+            out["grad_features"] = gf
+        return out
+
+    def _backward(self, tape: dict, loss_scale: float, accumulate: bool, want_input_grad: bool):
+        st: _ParamStore = tape["st"]
+        P, Q, dm = self._prepare(st), self._prepare_bwd(st), self.dims
+        B, T, dev = tape["B"], tape["T"], st.device
+        rows, C, R, ks = B * T, dm["out_size"], dm["reduced"], dm["ks"]
+        A, G, V, NC = self.audio_alignment, self.vq_groups, self.audio_vocab_size, dm["classes"]
+        NA, NCp = A * G * V, (NC + 63) // 64 * 64
+        grad = lambda name: self._grad_of(st, name, accumulate)          # noqa: E731
+        # heads: the cross-entropy and linear kernels the transformer model's heads run
+        g_c = torch.full((), loss_scale, dtype=torch.float32, device=dev)
+        g_a = torch.full((), loss_scale * self.lambda_audio, dtype=torch.float32, device=dev)
+        dlc = torch.empty((B, NCp), dtype=BF16, device=dev)
+        ops.ce_bwd(tape["logits_c"], NC, tape["lab"], None, B, NC, self.label_smoothing, tape["lse_c"], g_c, dlc, NCp)
+        dla = torch.empty((rows, NA), dtype=BF16, device=dev)
+        ops.ce_bwd(tape["logits_a"], V, tape["tok"], None, rows * A * G, V, 0.0, tape["lse_a"], g_a, dla, V)
+        for wname, bname, x, dy, n_rows, N, pitch in (("audio_projection.weight", "audio_projection.bias", tape["h"], dla, rows, NA, NA),
+                                                     ("video_classifier.weight", "video_classifier.bias", tape["pooled"], dlc, B, NC, NCp)):
+            (gw, addw), (gb, addb) = grad(wname), grad(bname)
+            if not addw:
+                gw.zero_()
+            if not addb:
+                gb.zero_()
+            ops.linear_wgrad(x, dy, gw, rows=n_rows, K=C, N=N, x_pitch=C, dy_pitch=pitch, db=gb)          # (adds)
+        dh = ops.linear_dgrad(dla, Q["wa_t"], rows=rows, N=NA, K=C, dy_pitch=NA)
+        dpooled = ops.linear_dgrad(dlc, Q["wc_t"], rows=B, N=NC, K=C, dy_pitch=NCp)
+        # norm5 + masked mean
+        stacks = tape["stacks"]
+        scale5, _ = P["norm5"]
+        dS = torch.empty_like(stacks[-1])
+        _, sums = ops.tcn_norm_pool_bwd(dh, dpooled, stacks[-1], scale5, tape["mask"], B=B, T=T, C=C, out=dS)
+        self._bn_grads(st, accumulate, sums, f"{TCN}.norm5", None)
+        # dense blocks, last to first; dS: the gradient of the current block's feature stack
+        for i in range(len(P["layers"]) - 1, -1, -1):
+            L, q, t = P["layers"][i], Q["layers"][i], tape["layers"][i]
+            n_in, g, gb, d, bi, p = L["n_in"], L["g"], L["gb"], L["d"], L["bi"], q["p"]
+            stack = t["stack"]
+            # second stage: Swish(out1 + res) sends its gradient to out1's convolutions and to the downsample branch
+            dacc1, dres, sums = ops.tconv_epi_bwd(dS[:, n_in: n_in + g], tape["acc"][(i, 1)], q["scale1"], q["shift1"], rows=rows, C=g,
+                                                  act=ops.ACT_SWISH, res=t["res"], res_act=ops.ACT_SWISH)
+            self._put(*grad(f"{p}.downsample.bias"), sums[3])
+            for j, k in enumerate(ks):
+                c = f"{p}.cbcr1_{j}.net"
+                self._bn_grads(st, accumulate, sums, f"{c}.1", f"{c}.0.bias", j * gb, (j + 1) * gb)
+                gw, add = grad(f"{c}.0.weight")
+                ops.tconv_wgrad(t["out0"], dacc1[:, j * gb: (j + 1) * gb], gw, B=B, T=T, n_in=g, co=gb, k=k, d=d, add=add)
+            dout0 = torch.empty((rows, g), dtype=BF16, device=dev)
+            ops.tconv_dgrad(dacc1, B=B, T=T, co=gb, d=d, n_out=g, out=dout0,
+                            branches=[dict(k=k, wt=q["wt1"][j], dy_off=j * gb) for j, k in enumerate(ks)])
+            # first stage (gated)
+            dacc0, _, sums = ops.tconv_epi_bwd(dout0, tape["acc"][(i, 0)], q["scale0"], q["shift0"], rows=rows, C=g, act=ops.ACT_SWISH)
+            for j, k in enumerate(ks):
+                c = f"{p}.cbcr0_{j}.net"
+                self._bn_grads(st, accumulate, sums, f"{c}.1", f"{c}.0.bias", j * gb, (j + 1) * gb)
+                gw, add = grad(f"{c}.0.weight")
+                ops.tconv_wgrad(stack, dacc0[:, j * gb: (j + 1) * gb], gw, B=B, T=T, n_in=n_in, co=gb, k=k, d=d, gate=t["gates"][j], add=add)
+            gpart = ops.tconv_dgrad(dacc0, B=B, T=T, co=gb, d=d, n_out=n_in, out=dS, x=stack, addend=dS,
+                                    branches=[dict(k=k, wt=q["wt0"][j], dy_off=j * gb, gate=t["gates"][j]) for j, k in enumerate(ks)])
+            g1 = [grad(f"{p}.cbcr0_se_{j}.fc.0.weight") for j in range(len(ks))]
+            g2 = [grad(f"{p}.cbcr0_se_{j}.fc.2.weight") for j in range(len(ks))]
+            add = g1[0][1]
+            dmean = ops.tcn_se_bwd(stack, L["se_w1"], L["se_w2"], t["gates"], gpart, [a for a, _ in g1], [a for a, _ in g2], B=B, T=T, n_in=n_in,
+                                   add=add)
+            # downsample branch; the time mean's gradient (constant over a clip's rows) rides in the same write
+            gw, add = grad(f"{p}.downsample.weight")
+            ops.tconv_wgrad(stack, dres, gw, B=B, T=T, n_in=n_in, co=g, k=1, d=1, add=add)
+            ops.tconv_dgrad(dres, B=B, T=T, co=g, d=1, n_out=n_in, out=dS, addend=dS, cadd=dmean, cadd_scale=1.0 / T,
+                            branches=[dict(k=1, wt=q["down_wt"], dy_off=0)])
+            if i == 0 or P["layers"][i - 1]["bi"] != bi:          # the block's input: a transition's output
+                if bi == 0:
+                    break
+                tr, x = Q["trans"][bi - 1], stacks[bi - 1]
+                n = P["trans"][bi - 1]["n_in"]
+                dacc, _, sums = ops.tconv_epi_bwd(dS[:, :R], tape["acc"][("tr", bi - 1)], P["trans"][bi - 1]["scale"], P["trans"][bi - 1]["shift"],
+                                                  rows=rows, C=R, act=ops.ACT_SWISH)
+                self._bn_grads(st, accumulate, sums, f"{tr['name']}.norm", None)
+                gw, add = grad(f"{tr['name']}.conv.weight")
+                ops.tconv_wgrad(x, dacc, gw, B=B, T=T, n_in=n, co=R, k=1, d=1, add=add)
+                dS = torch.empty_like(x)
+                ops.tconv_dgrad(dacc, B=B, T=T, co=R, d=1, n_out=n, out=dS, branches=[dict(k=1, wt=tr["wt"], dy_off=0)])
+        # transition0 (PReLU)
+        p = f"{TCN}.transition0"
+        dacc, _, sums = ops.tconv_epi_bwd(dS[:, :R], tape["acc"]["t0"], P["t0"]["scale"], P["t0"]["shift"], rows=rows, C=R, act=ops.ACT_PRELU,
+                                          slope=P["t0"]["slope"])
+        self._bn_grads(st, accumulate, sums, f"{p}.norm", None)
+        self._put(*grad(f"{p}.prelu.weight"), sums[2])
+        gw, add = grad(f"{p}.conv.weight")
+        ops.tconv_wgrad(tape["x0"], dacc, gw, B=B, T=T, n_in=self.in_pad, co=R, k=1, d=1, add=add)
+        if not want_input_grad:
+            return None
+        dx0 = torch.empty((rows, self.in_pad), dtype=BF16, device=dev)
+        ops.tconv_dgrad(dacc, B=B, T=T, co=R, d=1, n_out=self.in_pad, out=dx0, branches=[dict(k=1, wt=Q["t0_wt"], dy_off=0)])
+        return dx0[:, :512].contiguous()          # (the boundary column's own gradient is discarded)
 
     def validation_step(self, batch: dict, idx: int = 0) -> dict:
         return {f"val/{k}": v for k, v in self(**batch).items()}

@@ -2238,3 +2238,184 @@ def tcn_norm_pool_fwd(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor,
     pooled = torch.empty((B, C), dtype=BF16, device=x.device)
     _call("svsr_tcn_norm_pool_fwd", _p(x), x.stride(0), B, T, C, _p(scale), _p(shift), _p(mask), _p(h), _p(pooled), _stream(), label="k_tcn_norm_pool")
     return h, pooled
+
+
+# -- backward of the back-end (statistics mode of the forward: running-statistic BatchNorm, no dropout) ------------------------------
+def tconv_fwd_save(x: torch.Tensor, *, B: int, T: int, n_in: int, d: int, branches: Sequence[dict], co: int, act: int, out: torch.Tensor,
+                   acc: torch.Tensor, res: Optional[torch.Tensor] = None, res_act: int = ACT_NONE) -> torch.Tensor:
+    """tconv_fwd (same output bits) that also stores the fp32 accumulators: acc fp32 [B*T, >= nb * co], branch i at channels [i * co, (i + 1) * co)
+    (svsr_tconv_fwd_save)."""
+    assert x.dtype == BF16 and x.dim() == 2 and x.stride(1) == 1 and x.shape[0] >= B * T and x.shape[1] >= n_in
+    assert out.dtype == BF16 and out.dim() == 2 and out.stride(1) == 1 and out.shape[0] >= B * T
+    assert acc.dtype == torch.float32 and acc.dim() == 2 and acc.stride(1) == 1 and acc.shape[0] >= B * T and acc.shape[1] >= len(branches) * co
+    if res is not None:
+        assert res.dtype == BF16 and res.dim() == 2 and res.stride(1) == 1 and res.shape[0] >= B * T
+    rows = []
+    flops = 0.0
+    for br in branches:
+        w, k = br["w"], int(br["k"])
+        assert w.dtype == BF16 and w.is_contiguous() and tuple(w.shape) == (co, k, n_in), (tuple(w.shape), (co, k, n_in))
+        g = br.get("gate")
+        assert g is None or (g.dtype == torch.float32 and g.is_contiguous() and tuple(g.shape) == (B, n_in))
+        off, roff = int(br["out_off"]), int(br.get("res_off", 0))
+        assert 0 <= off and off + co <= out.shape[1] and (res is None or (0 <= roff and roff + co <= res.shape[1]))
+        rows.append((k, _p(w), _p(g) or 0, _p(br["scale"]), _p(br["shift"]), _p(br.get("slope")) or 0, off, roff))
+        flops += 2.0 * B * T * n_in * k * co
+    tab = torch.tensor(rows, dtype=torch.int64)
+    _call("svsr_tconv_fwd_save", _p(x), x.stride(0), B, T, n_in, int(d), len(branches), tab.data_ptr(), co, int(act), _p(out), out.stride(0), _p(res),
+          0 if res is None else res.stride(0), int(res_act), _p(acc), acc.stride(0), _stream(), label="k_tconv<save>", flops=flops)
+    return out
+
+
+def _rows_view(t: torch.Tensor, rows: int, width: int, dtype) -> None:
+    if not (t.dtype == dtype and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] >= rows and t.shape[1] >= width):
+        raise ValueError(f"expected a {dtype} [>= {rows}, >= {width}] row tensor with unit channel stride, got {tuple(t.shape)} {t.dtype}")
+
+
+def tconv_epi_bwd(dy: torch.Tensor, acc: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, *, rows: int, C: int, act: int,
+                  slope: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None, res_act: int = ACT_NONE,
+                  dacc: Optional[torch.Tensor] = None, dres: Optional[torch.Tensor] = None):
+    """Epilogue backward (svsr_tconv_epi_bwd).  dy bf16 [rows, C] (a channel slice of a wider row tensor is fine), acc fp32 [rows, C], scale /
+    shift fp32 [C] -> (dacc bf16 [rows, C], dres bf16 [rows, C] or None, sums fp32 [4, C] = sum g, sum g * acc, sum du * min(z, 0), sum du)."""
+    if C < 64 or C % 64:
+        raise ValueError("tconv_epi_bwd: the channel count must be a multiple of 64")
+    _rows_view(dy, rows, C, BF16)
+    _rows_view(acc, rows, C, torch.float32)
+    for t in (scale, shift, slope):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == C)
+    dev = dy.device
+    if dacc is None:
+        dacc = torch.empty((rows, C), dtype=BF16, device=dev)
+    _rows_view(dacc, rows, C, BF16)
+    if res is not None:
+        _rows_view(res, rows, C, BF16)
+        if dres is None:
+            dres = torch.empty((rows, C), dtype=BF16, device=dev)
+        _rows_view(dres, rows, C, BF16)
+    part = torch.empty(((rows + 63) // 64) * 4 * C, dtype=torch.float32, device=dev)
+    sums = torch.empty((4, C), dtype=torch.float32, device=dev)
+    _call("svsr_tconv_epi_bwd", _p(dy), dy.stride(0), _p(acc), acc.stride(0), rows, C, int(act), _p(scale), _p(shift), _p(slope), _p(res),
+          0 if res is None else res.stride(0), int(res_act), _p(dacc), dacc.stride(0), _p(dres) if res is not None else None,
+          0 if res is None else dres.stride(0), _p(part), _p(sums), _stream(), label="k_tconv_epi_bwd")
+    return dacc, (dres if res is not None else None), sums
+
+
+def tconv_dgrad(dy: torch.Tensor, *, B: int, T: int, co: int, d: int, branches: Sequence[dict], n_out: int, out: torch.Tensor,
+                x: Optional[torch.Tensor] = None, addend: Optional[torch.Tensor] = None, cadd: Optional[torch.Tensor] = None,
+                cadd_scale: float = 1.0) -> Optional[torch.Tensor]:
+    """Data gradient of up to three branches in one launch (svsr_tconv_dgrad).  Each branch: k, wt (bf16 [n_out, k, co], transposed and tap-flipped:
+    tconv_wt), dy_off, optionally gate (fp32 [B, n_out]).  out bf16 [B*T, >= n_out] = addend + cadd[b] * cadd_scale + sum gate_i * dxg_i.
+    -> the gate partials fp32 [nb, B, tiles, n_out] if any branch is gated (x, the forward's input rows, is required then), else None."""
+    rows = B * T
+    for br in branches:
+        if not tconv_ok(co, n_out, int(br["k"]), int(d)):
+            raise ValueError("tconv_dgrad: outside the shape domain of svsr_tconv_fwd (channels a multiple of 64, odd k <= 7, (k - 1) d / 2 <= 16)")
+    _rows_view(out, rows, n_out, BF16)
+    gated = any(br.get("gate") is not None for br in branches)
+    if gated:
+        if x is None:
+            raise ValueError("tconv_dgrad: gated branches need x, the rows the forward multiplied")
+        _rows_view(x, rows, n_out, BF16)
+    if addend is not None:
+        _rows_view(addend, rows, n_out, BF16)
+    assert dy.dtype == BF16 and dy.dim() == 2 and dy.stride(1) == 1 and dy.shape[0] >= rows
+    assert cadd is None or (cadd.dtype == torch.float32 and cadd.is_contiguous() and tuple(cadd.shape) == (B, n_out))
+    tab_rows, flops = [], 0.0
+    for br in branches:
+        k, wt, off = int(br["k"]), br["wt"], int(br["dy_off"])
+        assert wt.dtype == BF16 and wt.is_contiguous() and tuple(wt.shape) == (n_out, k, co), (tuple(wt.shape), (n_out, k, co))
+        assert 0 <= off and off + co <= dy.shape[1]
+        g = br.get("gate")
+        assert g is None or (g.dtype == torch.float32 and g.is_contiguous() and tuple(g.shape) == (B, n_out))
+        tab_rows.append((k, _p(wt), _p(g) or 0, off))
+        flops += 2.0 * rows * n_out * k * co
+    tab = torch.tensor(tab_rows, dtype=torch.int64)
+    gpart = torch.empty((len(branches), B, (T + 31) // 32, n_out), dtype=torch.float32, device=dy.device) if gated else None
+    _call("svsr_tconv_dgrad", _p(dy), dy.stride(0), B, T, co, int(d), len(branches), tab.data_ptr(), n_out, _p(x), 0 if x is None else x.stride(0),
+          _p(addend), 0 if addend is None else addend.stride(0), _p(cadd), float(cadd_scale), _p(out), out.stride(0), _p(gpart), _stream(),
+          label="k_tconv_dgrad", flops=flops)
+    return gpart
+
+
+def tconv_wt(w16: torch.Tensor) -> torch.Tensor:
+    """bf16 Conv1d weight in the parameter's layout [co, ci, k] -> the data-gradient shadow [ci, k, co] with the taps flipped."""
+    return w16.permute(1, 2, 0).flip(1).contiguous()
+
+
+def tconv_wgrad_splits(B: int, T: int, n_in: int, co: int) -> int:
+    """Row splits of svsr_tconv_wgrad: enough workgroups for ~2 per compute unit of a 256-CU device, at most 8 and at most the slot pairs
+    (a fixed function of the shape: the summation order does not depend on the device)."""
+    pairs = (B * ((T + 31) // 32) + 1) // 2
+    return max(1, min(pairs, 8, -(-512 // ((n_in // 64) * (co // 64)))))
+
+
+def tconv_wgrad(x: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor, *, B: int, T: int, n_in: int, co: int, k: int, d: int,
+                gate: Optional[torch.Tensor] = None, add: bool = False, splits: Optional[int] = None) -> None:
+    """dw fp32 [co, n_valid <= n_in, k] (contiguous, the parameter's layout) = (add ? dw : 0) + sum_rows dy^T (x) shifted bf16(x * gate)
+    (svsr_tconv_wgrad).  x bf16 [B*T, >= n_in], dy bf16 [B*T, >= co] (the branch's channel slice)."""
+    if not tconv_ok(n_in, co, int(k), int(d)):
+        raise ValueError("tconv_wgrad: outside the shape domain of svsr_tconv_fwd (channels a multiple of 64, odd k <= 7, (k - 1) d / 2 <= 16)")
+    rows = B * T
+    _rows_view(x, rows, n_in, BF16)
+    _rows_view(dy, rows, co, BF16)
+    if not (dw.dtype == torch.float32 and dw.is_contiguous() and dw.dim() == 3 and dw.shape[0] == co and dw.shape[2] == k and 1 <= dw.shape[1] <= n_in):
+        raise ValueError(f"tconv_wgrad: dw must be a contiguous fp32 [co, <= n_in, k] tensor, got {tuple(dw.shape)}")
+    assert gate is None or (gate.dtype == torch.float32 and gate.is_contiguous() and tuple(gate.shape) == (B, n_in))
+    S = tconv_wgrad_splits(B, T, n_in, co) if splits is None else int(splits)
+    part = torch.empty(S * co * k * n_in, dtype=torch.float32, device=x.device)
+    _call("svsr_tconv_wgrad", _p(x), x.stride(0), _p(gate), _p(dy), dy.stride(0), B, T, n_in, co, int(k), int(d), S, _p(part), _p(dw), dw.shape[1],
+          int(bool(add)), _stream(), label=f"k_tconv_wgrad<{k}>", flops=2.0 * rows * n_in * k * co)
+
+
+def tcn_se_bwd(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, gate: torch.Tensor, gpart: torch.Tensor, dw1: Sequence[torch.Tensor],
+               dw2: Sequence[torch.Tensor], *, B: int, T: int, n_in: int, add: bool = False) -> torch.Tensor:
+    """Squeeze-and-excitation backward (svsr_tcn_se_bwd): gate partials of tconv_dgrad -> dm fp32 [B, n_in] (gradient of the time mean over
+    all branches) and the weight gradients dw1[i] fp32 [R, n_in], dw2[i] fp32 [n_in, R] written (add: added to)."""
+    nb, R = w1.shape[0], w1.shape[1]
+    _rows_view(x, B * T, n_in, BF16)
+    assert w1.dtype == BF16 and w1.is_contiguous() and tuple(w1.shape) == (nb, R, n_in)
+    assert w2.dtype == BF16 and w2.is_contiguous() and tuple(w2.shape) == (nb, n_in, R)
+    assert gate.dtype == torch.float32 and gate.is_contiguous() and tuple(gate.shape) == (nb, B, n_in)
+    assert gpart.dtype == torch.float32 and gpart.is_contiguous() and tuple(gpart.shape) == (nb, B, (T + 31) // 32, n_in)
+    if 2 * (3 * n_in + 2 * R) * 4 > 64 * 1024:
+        raise ValueError("tcn_se_bwd: n_in too wide for the workgroup's LDS (2 clips x (3 n_in + 2 R) floats <= 64 KiB)")
+    assert len(dw1) == nb and len(dw2) == nb
+    for a, b in zip(dw1, dw2):
+        assert a.dtype == torch.float32 and a.is_contiguous() and a.numel() == R * n_in and b.dtype == torch.float32 and b.is_contiguous() and b.numel() == R * n_in
+    dev = x.device
+    work = torch.empty(nb * B * n_in + 2 * nb * B * R + B * n_in, dtype=torch.float32, device=dev)
+    dm = torch.empty((B, n_in), dtype=torch.float32, device=dev)
+    tab = torch.tensor([_p(t) for t in dw1] + [_p(t) for t in dw2], dtype=torch.int64)
+    _call("svsr_tcn_se_bwd", _p(x), x.stride(0), B, T, n_in, R, nb, _p(w1), _p(w2), _p(gate), _p(gpart), _p(work), _p(dm), tab.data_ptr(),
+          int(bool(add)), _stream(), label="k_tcn_se_bwd")
+    return dm
+
+
+def tcn_norm_pool_bwd(dh: torch.Tensor, dpooled: torch.Tensor, x: torch.Tensor, scale: torch.Tensor, mask: torch.Tensor, *, B: int, T: int, C: int,
+                      out: torch.Tensor):
+    """norm5 + masked mean backward (svsr_tcn_norm_pool_bwd): dh bf16 [B*T, C], dpooled bf16 [B, C], x bf16 [B*T, >= C] (the forward's input)
+    -> out bf16 [B*T, >= C] channels [0, C) written, sums fp32 [2, C] = (sum g, sum g * x)."""
+    if C < 8 or C % 8:
+        raise ValueError("tcn_norm_pool_bwd: C must be a multiple of 8")
+    assert dh.dtype == BF16 and dh.is_contiguous() and tuple(dh.shape) == (B * T, C)
+    assert dpooled.dtype == BF16 and dpooled.is_contiguous() and tuple(dpooled.shape) == (B, C)
+    _rows_view(x, B * T, C, BF16)
+    _rows_view(out, B * T, C, BF16)
+    assert mask.dtype == torch.float32 and mask.is_contiguous() and mask.numel() == B * T
+    assert scale.dtype == torch.float32 and scale.is_contiguous() and scale.numel() == C
+    part = torch.empty(B * 2 * C, dtype=torch.float32, device=dh.device)
+    sums = torch.empty((2, C), dtype=torch.float32, device=dh.device)
+    _call("svsr_tcn_norm_pool_bwd", _p(dh), _p(dpooled), _p(x), x.stride(0), B, T, C, _p(scale), _p(mask), _p(out), out.stride(0), _p(part), _p(sums),
+          _stream(), label="k_tcn_norm_pool_bwd")
+    return out, sums
+
+
+def bn_conv_param_grads(sum_g: torch.Tensor, sum_g_acc: torch.Tensor, weight: torch.Tensor, running_mean: torch.Tensor, running_var: torch.Tensor,
+                        conv_bias: Optional[torch.Tensor], eps: float = BN_EPS):
+    """The O(C) chain rule of y = BatchNorm1d(eval)(acc + conv_bias) from the per-channel sums of g = dL/dy and g * acc:
+    -> (d bn.weight, d bn.bias, d conv.bias or None).  scale = weight * r is never divided by: a BatchNorm weight of 0 is exact."""
+    r = torch.rsqrt(running_var + eps)
+    off = -running_mean if conv_bias is None else conv_bias - running_mean
+    d_weight = r * (sum_g_acc + off * sum_g)
+    d_cbias = None if conv_bias is None else sum_g * (weight * r)
+    return d_weight, sum_g, d_cbias
