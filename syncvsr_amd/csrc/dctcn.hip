@@ -42,6 +42,81 @@ struct TArgs {
 // rows, one logical piece) land on 16 distinct (half bank row, 16-byte slot) positions
 __device__ __forceinline__ int tc_off(int row, int s) { return row * 128 + ((s ^ ((row >> 1) & 7)) << 4); }
 
+// The three staging / tap helpers below are shared by k_tconv, k_tconv_dgrad and (the first) k_tconv_wgrad<K>.  None of them synchronises:
+// every caller puts one __syncthreads() in front of the staging (the previous chunk's fragments are read) and one behind it.
+
+// Slab of one 64-channel chunk: the rows [t0 - halo, t0 + 32 + halo) of the TC_SLOTS slots from global slot gs0 on, channels
+// [c, c + 64) of src (row pitch `pitch`), zeros outside the clip, outside the halo and for slots >= slots; with a gate (fp32 rows of
+// gate_pitch, one per clip) the rows are bf16(x * gate[b]).  All TC_SLOTS * TC_ROWS LDS rows are written.
+__device__ __forceinline__ void tc_stage_rows(unsigned char* slab, const bf16_t* src, long pitch, int c, const float* gate, int gate_pitch, int halo,
+                                              int T, int n_tt, int slots, long gs0, int tid) {
+#pragma unroll
+    for (int i = 0; i < TC_SLOTS * TC_ROWS * 8 / 256; ++i) {
+        const int p = tid + i * 256;
+        const int s = p & 7, row = (p >> 3) & (TC_ROWS - 1), sl = p >> 9;
+        const long gs = gs0 + sl;
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (gs < slots && row >= TC_HALO - halo && row < TC_HALO + TC_TILE + halo) {
+            const int b = (int)(gs / n_tt);
+            const int t = (int)(gs - (long)b * n_tt) * TC_TILE - TC_HALO + row;
+            if (t >= 0 && t < T) {
+                v = *reinterpret_cast<const u32x4*>(src + ((long)b * T + t) * pitch + c + s * 8);
+                if (gate != nullptr) {
+                    const float4* gp = reinterpret_cast<const float4*>(gate + (long)b * gate_pitch + c + s * 8);
+                    const float4 g0 = gp[0], g1 = gp[1];
+                    float f[8];
+                    unpack8(v, f);
+                    f[0] *= g0.x; f[1] *= g0.y; f[2] *= g0.z; f[3] *= g0.w;
+                    f[4] *= g1.x; f[5] *= g1.y; f[6] *= g1.z; f[7] *= g1.w;
+                    v = pack8(f);
+                }
+            }
+        }
+        *reinterpret_cast<u32x4*>(slab + tc_off(sl * TC_ROWS + row, s)) = v;
+    }
+}
+
+// Weight chunk [64 rows from row0][k][64 channels from c0] of w [rows][k][ld] -> wts, LDS row j * 64 + row
+__device__ __forceinline__ void tc_stage_weights(unsigned char* wts, const bf16_t* w, int row0, int k, int ld, int c0, int tid) {
+    for (int p = tid; p < k * TC_BN * 8; p += 256) {
+        const int s = p & 7, co = (p >> 3) & (TC_BN - 1), j = p >> 9;
+        const u32x4 v = *reinterpret_cast<const u32x4*>(w + ((long)(row0 + co) * k + j) * ld + c0 + s * 8);
+        *reinterpret_cast<u32x4*>(wts + tc_off(j * TC_BN + co, s)) = v;
+    }
+}
+
+// acc += the k taps of one staged chunk: tap j is the slab row offset (j - (k - 1) / 2) * d, four MFMAs over the 64 channels
+__device__ __forceinline__ void tc_taps(f32x16& acc, const unsigned char* slab, const unsigned char* wts, int k, int d, int my_slot, int nh, int r, int h) {
+    for (int j = 0; j < k; ++j) {
+        const int arow = my_slot * TC_ROWS + TC_HALO + r + (j - (k - 1) / 2) * d;
+        const int brow = j * TC_BN + nh * 32 + r;
+#pragma unroll
+        for (int kk = 0; kk < TC_BK / 16; ++kk) {
+            const bf16x8 af = *reinterpret_cast<const bf16x8*>(slab + tc_off(arow, 2 * kk + h));
+            const bf16x8 bfr = *reinterpret_cast<const bf16x8*>(wts + tc_off(brow, 2 * kk + h));
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bfr, acc, 0, 0, 0);
+        }
+    }
+}
+
+// Host side of the same scheme.  Taps: odd k <= TC_MAXK whose reach fits the staged halo
+static bool tc_taps_ok(int64_t k, int d) { return k >= 1 && k <= TC_MAXK && k % 2 != 0 && (k - 1) * (int64_t)d / 2 <= TC_HALO; }
+
+// Time tiles per clip and (clip, tile) slots of B clips of T rows; false: more slots than the kernels index
+static bool tc_geometry(int B, int T, int* n_tt, int* slots) {
+    const long tt = (T + TC_TILE - 1) / TC_TILE, n = (long)B * tt;
+    if (n > (1L << 30)) return false;
+    *n_tt = (int)tt; *slots = (int)n;
+    return true;
+}
+
+// Dynamic LDS of a slab and a kmax-tap weight chunk, announced to kernel fn.  Per call: the attribute belongs to the current device's copy of
+// the kernel, and setting it costs a table lookup
+static hipError_t tc_dynamic_lds(const void* fn, int kmax, size_t* lds) {
+    *lds = TC_SLAB_BYTES + (size_t)kmax * TC_BN * TC_BK * 2;
+    return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds);
+}
+
 // One workgroup (4 waves): TC_SLOTS slots x 64 output channels of ONE branch; wave w owns slot w >> 1 and 32 of the channels.
 // Per 64-channel chunk of the input: the rows [t0 - halo, t0 + 32 + halo) of each slot (zeros outside the clip), times the branch's gate,
 // are staged ONCE and serve all k taps (a tap is a row offset into the slab); the chunk of the weights [64 co][k][64 ci] beside it.
@@ -63,46 +138,10 @@ __global__ __launch_bounds__(256) void k_tconv(TArgs a) {
     const int my_slot = wave >> 1, nh = wave & 1, r = lane & 31, h = lane >> 5;
     for (int c0 = 0; c0 < a.n_in; c0 += TC_BK) {
         __syncthreads();                                   // the previous chunk's fragments are read
-#pragma unroll
-        for (int i = 0; i < TC_SLOTS * TC_ROWS * 8 / 256; ++i) {
-            const int p = tid + i * 256;
-            const int s = p & 7, row = (p >> 3) & (TC_ROWS - 1), sl = p >> 9;
-            const long gs = (long)blockIdx.x * TC_SLOTS + sl;
-            u32x4 v = {0u, 0u, 0u, 0u};
-            if (gs < a.slots && row >= TC_HALO - halo && row < TC_HALO + TC_TILE + halo) {
-                const int b = (int)(gs / a.n_tt);
-                const int t = (int)(gs - (long)b * a.n_tt) * TC_TILE - TC_HALO + row;
-                if (t >= 0 && t < a.T) {
-                    v = *reinterpret_cast<const u32x4*>(a.x + ((long)b * a.T + t) * a.x_pitch + c0 + s * 8);
-                    if (br.gate != nullptr) {
-                        const float4* gp = reinterpret_cast<const float4*>(br.gate + (long)b * a.n_in + c0 + s * 8);
-                        const float4 g0 = gp[0], g1 = gp[1];
-                        float f[8];
-                        unpack8(v, f);
-                        f[0] *= g0.x; f[1] *= g0.y; f[2] *= g0.z; f[3] *= g0.w;
-                        f[4] *= g1.x; f[5] *= g1.y; f[6] *= g1.z; f[7] *= g1.w;
-                        v = pack8(f);
-                    }
-                }
-            }
-            *reinterpret_cast<u32x4*>(slab + tc_off(sl * TC_ROWS + row, s)) = v;
-        }
-        for (int p = tid; p < k * TC_BN * 8; p += 256) {
-            const int s = p & 7, co = (p >> 3) & (TC_BN - 1), j = p >> 9;
-            const u32x4 v = *reinterpret_cast<const u32x4*>(br.w + ((long)(co0 + co) * k + j) * a.n_in + c0 + s * 8);
-            *reinterpret_cast<u32x4*>(wts + tc_off(j * TC_BN + co, s)) = v;
-        }
+        tc_stage_rows(slab, a.x, a.x_pitch, c0, br.gate, a.n_in, halo, a.T, a.n_tt, a.slots, (long)blockIdx.x * TC_SLOTS, tid);
+        tc_stage_weights(wts, br.w, co0, k, a.n_in, c0, tid);
         __syncthreads();
-        for (int j = 0; j < k; ++j) {
-            const int arow = my_slot * TC_ROWS + TC_HALO + r + (j - (k - 1) / 2) * a.d;
-            const int brow = j * TC_BN + nh * 32 + r;
-#pragma unroll
-            for (int kk = 0; kk < TC_BK / 16; ++kk) {
-                const bf16x8 af = *reinterpret_cast<const bf16x8*>(slab + tc_off(arow, 2 * kk + h));
-                const bf16x8 bfr = *reinterpret_cast<const bf16x8*>(wts + tc_off(brow, 2 * kk + h));
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bfr, acc, 0, 0, 0);
-            }
-        }
+        tc_taps(acc, slab, wts, k, a.d, my_slot, nh, r, h);
     }
     // epilogue: lane = output channel, registers = time rows
     const long gs = (long)blockIdx.x * TC_SLOTS + my_slot;
@@ -155,8 +194,7 @@ static int tconv_launch(const void* x, int64_t x_pitch, int B, int T, int n_in, 
         br.slope = (const float*)(uintptr_t)e[5];
         br.out_off = (int)e[6];
         br.res_off = (int)e[7];
-        if (e[0] < 1 || e[0] > TC_MAXK || e[0] % 2 == 0) return SVSR_ERR_ARG;
-        if ((e[0] - 1) * (int64_t)d / 2 > TC_HALO) return SVSR_ERR_ARG;
+        if (!tc_taps_ok(e[0], d)) return SVSR_ERR_ARG;
         if (br.w == nullptr || ((uintptr_t)br.w & 15) != 0 || br.scale == nullptr || br.shift == nullptr) return SVSR_ERR_ARG;
         if (br.gate != nullptr && ((uintptr_t)br.gate & 15) != 0) return SVSR_ERR_ARG;
         if (act == TC_ACT_PRELU && br.slope == nullptr) return SVSR_ERR_ARG;
@@ -164,18 +202,14 @@ static int tconv_launch(const void* x, int64_t x_pitch, int B, int T, int n_in, 
         if (res != nullptr && (e[7] < 0 || e[7] + co > res_pitch)) return SVSR_ERR_ARG;
         if (br.k > kmax) kmax = br.k;
     }
-    const long n_tt = (T + TC_TILE - 1) / TC_TILE;
-    const long slots = (long)B * n_tt;
-    if (slots > (1L << 30) || co / TC_BN > 65535) return SVSR_ERR_ARG;
+    if (!tc_geometry(B, T, &a.n_tt, &a.slots) || co / TC_BN > 65535) return SVSR_ERR_ARG;
     a.x = (const bf16_t*)x; a.out = (bf16_t*)out; a.res = (const bf16_t*)res;
     a.x_pitch = x_pitch; a.out_pitch = out_pitch; a.res_pitch = res_pitch;
-    a.B = B; a.T = T; a.n_in = n_in; a.d = d; a.act = act; a.res_act = res_act; a.n_tt = (int)n_tt; a.slots = (int)slots;
+    a.B = B; a.T = T; a.n_in = n_in; a.d = d; a.act = act; a.res_act = res_act;
     a.save = save; a.save_pitch = save_pitch; a.co = co;
-    const size_t lds = TC_SLAB_BYTES + (size_t)kmax * TC_BN * TC_BK * 2;
-    const dim3 grid((unsigned)((slots + TC_SLOTS - 1) / TC_SLOTS), (unsigned)(co / TC_BN), (unsigned)nb);
-    // per call: the attribute belongs to the current device's copy of the kernel, and setting it costs a table lookup
-    const void* fn = saving ? reinterpret_cast<const void*>(k_tconv<true>) : reinterpret_cast<const void*>(k_tconv<false>);
-    const hipError_t ae = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const dim3 grid((unsigned)((a.slots + TC_SLOTS - 1) / TC_SLOTS), (unsigned)(co / TC_BN), (unsigned)nb);
+    size_t lds;
+    const hipError_t ae = tc_dynamic_lds(saving ? reinterpret_cast<const void*>(k_tconv<true>) : reinterpret_cast<const void*>(k_tconv<false>), kmax, &lds);
     if (ae != hipSuccess) return (int)ae;
     if (saving) hipLaunchKernelGGL(k_tconv<true>, grid, dim3(256), lds, stream, a);
     else hipLaunchKernelGGL(k_tconv<false>, grid, dim3(256), lds, stream, a);
@@ -473,35 +507,10 @@ __global__ __launch_bounds__(256) void k_tconv_dgrad(DArgs a) {
         for (int i = 0; i < 16; ++i) acc[i] = 0.f;
         for (int c0 = 0; c0 < a.co; c0 += TC_BK) {
             __syncthreads();
-#pragma unroll
-            for (int i = 0; i < TC_SLOTS * TC_ROWS * 8 / 256; ++i) {
-                const int p = tid + i * 256;
-                const int s = p & 7, row = (p >> 3) & (TC_ROWS - 1), sl = p >> 9;
-                const long gs = (long)blockIdx.x * TC_SLOTS + sl;
-                u32x4 v = {0u, 0u, 0u, 0u};
-                if (gs < a.slots && row >= TC_HALO - halo && row < TC_HALO + TC_TILE + halo) {
-                    const int b = (int)(gs / a.n_tt);
-                    const int t = (int)(gs - (long)b * a.n_tt) * TC_TILE - TC_HALO + row;
-                    if (t >= 0 && t < a.T) v = *reinterpret_cast<const u32x4*>(a.dy + ((long)b * a.T + t) * a.dy_pitch + br.dy_off + c0 + s * 8);
-                }
-                *reinterpret_cast<u32x4*>(slab + tc_off(sl * TC_ROWS + row, s)) = v;
-            }
-            for (int p = tid; p < k * TC_BN * 8; p += 256) {
-                const int s = p & 7, cc = (p >> 3) & (TC_BN - 1), jj = p >> 9;
-                const u32x4 v = *reinterpret_cast<const u32x4*>(br.wt + ((long)(n0 + cc) * k + jj) * a.co + c0 + s * 8);
-                *reinterpret_cast<u32x4*>(wts + tc_off(jj * TC_BN + cc, s)) = v;
-            }
+            tc_stage_rows(slab, a.dy, a.dy_pitch, br.dy_off + c0, nullptr, 0, halo, a.T, a.n_tt, a.slots, (long)blockIdx.x * TC_SLOTS, tid);
+            tc_stage_weights(wts, br.wt, n0, k, a.co, c0, tid);
             __syncthreads();
-            for (int jj = 0; jj < k; ++jj) {
-                const int arow = my_slot * TC_ROWS + TC_HALO + r + (jj - (k - 1) / 2) * a.d;
-                const int brow = jj * TC_BN + nh * 32 + r;
-#pragma unroll
-                for (int kk = 0; kk < TC_BK / 16; ++kk) {
-                    const bf16x8 af = *reinterpret_cast<const bf16x8*>(slab + tc_off(arow, 2 * kk + h));
-                    const bf16x8 bfr = *reinterpret_cast<const bf16x8*>(wts + tc_off(brow, 2 * kk + h));
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bfr, acc, 0, 0, 0);
-                }
-            }
+            tc_taps(acc, slab, wts, k, a.d, my_slot, nh, r, h);
         }
         if (br.gate != nullptr) {
             const float gt = valid ? br.gate[(long)wb * a.n_out + ci] : 0.f;
@@ -551,24 +560,21 @@ extern "C" int svsr_tconv_dgrad(const void* dy, int64_t dy_pitch, int B, int T, 
         br.wt = (const bf16_t*)(uintptr_t)e[1];
         br.gate = (const float*)(uintptr_t)e[2];
         br.dy_off = (int)e[3];
-        if (e[0] < 1 || e[0] > TC_MAXK || e[0] % 2 == 0) return SVSR_ERR_ARG;
-        if ((e[0] - 1) * (int64_t)d / 2 > TC_HALO) return SVSR_ERR_ARG;
+        if (!tc_taps_ok(e[0], d)) return SVSR_ERR_ARG;
         if (br.wt == nullptr || ((uintptr_t)br.wt & 15) != 0) return SVSR_ERR_ARG;
         if (e[3] < 0 || e[3] % 8 != 0 || e[3] + co > dy_pitch) return SVSR_ERR_ARG;
         if (br.gate != nullptr) gated = true;
         if (br.k > kmax) kmax = br.k;
     }
     if (gated && (x == nullptr || gpart == nullptr || x_pitch < n_out)) return SVSR_ERR_ARG;
-    const long n_tt = (T + TC_TILE - 1) / TC_TILE;
-    const long slots = (long)B * n_tt;
-    if (slots > (1L << 30) || n_out / TC_BN > 65535) return SVSR_ERR_ARG;
+    if (!tc_geometry(B, T, &a.n_tt, &a.slots) || n_out / TC_BN > 65535) return SVSR_ERR_ARG;
     a.dy = (const bf16_t*)dy; a.x = (const bf16_t*)x; a.addend = (const bf16_t*)addend; a.cadd = cadd; a.out = (bf16_t*)out; a.gpart = gpart;
     a.dy_pitch = dy_pitch; a.x_pitch = x_pitch; a.add_pitch = add_pitch; a.out_pitch = out_pitch; a.cadd_scale = cadd_scale;
-    a.B = B; a.T = T; a.co = co; a.n_out = n_out; a.d = d; a.nb = nb; a.n_tt = (int)n_tt; a.slots = (int)slots;
-    const size_t lds = TC_SLAB_BYTES + (size_t)kmax * TC_BN * TC_BK * 2;
-    const hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void*>(k_tconv_dgrad), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    a.B = B; a.T = T; a.co = co; a.n_out = n_out; a.d = d; a.nb = nb;
+    size_t lds;
+    const hipError_t ae = tc_dynamic_lds(reinterpret_cast<const void*>(k_tconv_dgrad), kmax, &lds);
     if (ae != hipSuccess) return (int)ae;
-    hipLaunchKernelGGL(k_tconv_dgrad, dim3((unsigned)((slots + TC_SLOTS - 1) / TC_SLOTS), (unsigned)(n_out / TC_BN)), dim3(256), lds, stream, a);
+    hipLaunchKernelGGL(k_tconv_dgrad, dim3((unsigned)((a.slots + TC_SLOTS - 1) / TC_SLOTS), (unsigned)(n_out / TC_BN)), dim3(256), lds, stream, a);
     return svsr_check_launch();
 }
 
@@ -615,30 +621,7 @@ __global__ __launch_bounds__(256) void k_tconv_wgrad(WArgs a) {
     const int npairs = (a.slots + TC_SLOTS - 1) / TC_SLOTS;
     for (int pr = blockIdx.x; pr < npairs; pr += a.S) {
         __syncthreads();
-#pragma unroll
-        for (int i = 0; i < TC_SLOTS * TC_ROWS * 8 / 256; ++i) {
-            const int p = tid + i * 256;
-            const int s = p & 7, row = (p >> 3) & (TC_ROWS - 1), sl = p >> 9;
-            const long gs = (long)pr * TC_SLOTS + sl;
-            u32x4 v = {0u, 0u, 0u, 0u};
-            if (gs < a.slots && row >= TC_HALO - halo && row < TC_HALO + TC_TILE + halo) {
-                const int b = (int)(gs / a.n_tt);
-                const int t = (int)(gs - (long)b * a.n_tt) * TC_TILE - TC_HALO + row;
-                if (t >= 0 && t < a.T) {
-                    v = *reinterpret_cast<const u32x4*>(a.x + ((long)b * a.T + t) * a.x_pitch + ci0 + s * 8);
-                    if (a.gate != nullptr) {
-                        const float4* gp = reinterpret_cast<const float4*>(a.gate + (long)b * a.n_in + ci0 + s * 8);
-                        const float4 g0 = gp[0], g1 = gp[1];
-                        float f[8];
-                        unpack8(v, f);
-                        f[0] *= g0.x; f[1] *= g0.y; f[2] *= g0.z; f[3] *= g0.w;
-                        f[4] *= g1.x; f[5] *= g1.y; f[6] *= g1.z; f[7] *= g1.w;
-                        v = pack8(f);
-                    }
-                }
-            }
-            *reinterpret_cast<u32x4*>(slab + tc_off(sl * TC_ROWS + row, s)) = v;
-        }
+        tc_stage_rows(slab, a.x, a.x_pitch, ci0, a.gate, a.n_in, halo, a.T, a.n_tt, a.slots, (long)pr * TC_SLOTS, tid);
 #pragma unroll
         for (int i = 0; i < TC_SLOTS * TC_TILE * 8 / 256; ++i) {
             const int p = tid + i * 256;
@@ -697,16 +680,14 @@ extern "C" int svsr_tconv_wgrad(const void* x, int64_t x_pitch, const float* gat
     if (x == nullptr || dy == nullptr || part == nullptr || dw == nullptr) return SVSR_ERR_ARG;
     if (B < 1 || T < 1 || d < 1 || n_in < 64 || n_in % 64 != 0 || x_pitch < n_in || x_pitch % 8 != 0 || ((uintptr_t)x & 15) != 0) return SVSR_ERR_ARG;
     if (co < 64 || co % 64 != 0 || dy_pitch < co || dy_pitch % 8 != 0 || ((uintptr_t)dy & 15) != 0) return SVSR_ERR_ARG;
-    if (k < 1 || k > TC_MAXK || k % 2 == 0 || (k - 1) * (int64_t)d / 2 > TC_HALO) return SVSR_ERR_ARG;
+    if (!tc_taps_ok(k, d)) return SVSR_ERR_ARG;
     if (gate != nullptr && ((uintptr_t)gate & 15) != 0) return SVSR_ERR_ARG;
     if (n_valid < 1 || n_valid > n_in) return SVSR_ERR_ARG;
-    const long n_tt = (T + TC_TILE - 1) / TC_TILE;
-    const long slots = (long)B * n_tt;
-    const long npairs = (slots + TC_SLOTS - 1) / TC_SLOTS;
-    if (slots > (1L << 30) || splits < 1 || splits > npairs || splits > 65535 || n_in / 64 > 65535 || co / 64 > 65535) return SVSR_ERR_ARG;
     WArgs a;
+    if (!tc_geometry(B, T, &a.n_tt, &a.slots)) return SVSR_ERR_ARG;
+    if (splits < 1 || splits > (a.slots + TC_SLOTS - 1) / TC_SLOTS || splits > 65535 || n_in / 64 > 65535 || co / 64 > 65535) return SVSR_ERR_ARG;
     a.x = (const bf16_t*)x; a.dy = (const bf16_t*)dy; a.gate = gate; a.part = part; a.x_pitch = x_pitch; a.dy_pitch = dy_pitch;
-    a.B = B; a.T = T; a.n_in = n_in; a.co = co; a.d = d; a.n_tt = (int)n_tt; a.slots = (int)slots; a.S = splits;
+    a.B = B; a.T = T; a.n_in = n_in; a.co = co; a.d = d; a.S = splits;
     const dim3 grid((unsigned)splits, (unsigned)(n_in / 64), (unsigned)(co / 64));
     if (k == 1) hipLaunchKernelGGL(k_tconv_wgrad<1>, grid, dim3(256), 0, stream, a);
     else if (k == 3) hipLaunchKernelGGL(k_tconv_wgrad<3>, grid, dim3(256), 0, stream, a);

@@ -113,7 +113,7 @@ class DCTCNLightningModule(_StoreModule):
         return 0 if name.startswith("model.frontend3D") else 1 if name.startswith("model.trunk") else 2
 
     def _transposed_entries(self, offsets) -> list:
-        return []                    # no backward: no transposed shadows beyond the front-end's own
+        return []                    # none in the store: the back-end's backward builds its transposed, tap-flipped shadows itself (_prepare_bwd)
 
     def mark_params_dirty(self) -> None:
         """Call after changing parameters or buffers in place: the bf16 shadows, the tap-major convolution weights and the folded BatchNorm
@@ -200,7 +200,7 @@ class DCTCNLightningModule(_StoreModule):
             return ops.tconv_fwd(x, co=co, branches=branches, **kw)
         acc = torch.empty((x.shape[0], len(branches) * co), dtype=torch.float32, device=x.device)
         tape["acc"][key] = acc
-        return ops.tconv_fwd_save(x, co=co, branches=branches, acc=acc, **kw)
+        return ops.tconv_fwd(x, co=co, branches=branches, acc=acc, **kw)
 
     def _backend(self, st: _ParamStore, feats: torch.Tensor, word_mask: Optional[torch.Tensor], B: int, T: int, keep: Optional[dict] = None,
                  tape: Optional[dict] = None):
@@ -393,6 +393,15 @@ class DCTCNLightningModule(_StoreModule):
         if bias is not None:
             self._put(*self._grad_of(st, bias, accumulate), dcb)
 
+    def _loss_and_grads(self, videos, audios, labels, word_mask, attention_mask, loss_scale, accumulate, want_input_grad, feats=None):
+        tape: dict[str, Any] = {}
+        out = self._losses(videos, audios, labels, word_mask, attention_mask, tape, feats)
+        with torch.no_grad():
+            gf = self._backward(tape, float(loss_scale), bool(accumulate), bool(want_input_grad))
+        if want_input_grad:
+            out["grad_features"] = gf
+        return out
+
     def loss_and_backend_grads(self, videos: torch.Tensor, audios: torch.Tensor, labels: torch.Tensor, word_mask: torch.Tensor,
                                attention_mask: torch.Tensor, loss_scale: float = 1.0, accumulate: bool = False,
                                want_input_grad: bool = False) -> dict[str, torch.Tensor]:
@@ -400,26 +409,27 @@ class DCTCNLightningModule(_StoreModule):
         and the two heads: afterwards every parameter of backend_parameters() has .grad = d(loss_total * loss_scale)/d(param) in fp32
         (accumulate=True adds to an existing .grad).  The front-end and every BatchNorm running statistic are frozen and untouched.  With
         want_input_grad the dict also carries "grad_features": bf16 [B*T, 512], the gradient of the front-end features."""
-        tape: dict[str, Any] = {}
-        out = self._losses(videos, audios, labels, word_mask, attention_mask, tape)
-        with torch.no_grad():
-            gf = self._backward(tape, float(loss_scale), bool(accumulate), bool(want_input_grad))
-        if want_input_grad:
-            out["grad_features"] = gf
-        return out
+        return self._loss_and_grads(videos, audios, labels, word_mask, attention_mask, loss_scale, accumulate, want_input_grad)
 
     def loss_and_backend_grads_from_features(self, feats: torch.Tensor, B: int, T: int, audios: torch.Tensor, labels: torch.Tensor,
                                              word_mask: torch.Tensor, attention_mask: torch.Tensor, loss_scale: float = 1.0,
                                              accumulate: bool = False, want_input_grad: bool = False) -> dict[str, torch.Tensor]:
         """loss_and_backend_grads from pre-computed front-end features (bf16 [B*T, 512]) instead of videos: the frozen front-end need not
         run again for a clip whose features are cached (and what scripts/dctcn_bench.py --backward times)."""
-        tape: dict[str, Any] = {}
-        out = self._losses((int(B), int(T)), audios, labels, word_mask, attention_mask, tape, feats)
-        with torch.no_grad():
-            gf = self._backward(tape, float(loss_scale), bool(accumulate), bool(want_input_grad))
-        if want_input_grad:
-            out["grad_features"] = gf
-        return out
+        return self._loss_and_grads((int(B), int(T)), audios, labels, word_mask, attention_mask, loss_scale, accumulate, want_input_grad, feats)
+
+    def _stage_bwd(self, st: _ParamStore, accumulate: bool, dy, acc, scale, shift, x, convs, *, B: int, T: int, n_in: int, co: int, d: int,
+                   gates=None, **epi):
+        """Backward of one convolution stage short of its data gradient: the epilogue backward over all branches (epi: act, slope, res, res_act
+        of ops.tconv_epi_bwd), then per branch j — convs[j] = (k, conv weight, BatchNorm, conv bias or None), channels [j * co, (j + 1) * co) —
+        the BatchNorm / bias gradients and the weight gradient over the stage's input rows x.  -> (dacc, dres, sums)"""
+        dacc, dres, sums = ops.tconv_epi_bwd(dy, acc, scale, shift, rows=B * T, C=len(convs) * co, **epi)
+        for j, (k, weight, bn, bias) in enumerate(convs):
+            self._bn_grads(st, accumulate, sums, bn, bias, j * co, (j + 1) * co)
+            gw, add = self._grad_of(st, weight, accumulate)
+            ops.tconv_wgrad(x, dacc[:, j * co: (j + 1) * co], gw, B=B, T=T, n_in=n_in, co=co, k=k, d=d, gate=None if gates is None else gates[j],
+                            add=add)
+        return dacc, dres, sums
 
     def _backward(self, tape: dict, loss_scale: float, accumulate: bool, want_input_grad: bool):
         st: _ParamStore = tape["st"]
@@ -457,25 +467,17 @@ class DCTCNLightningModule(_StoreModule):
             L, q, t = P["layers"][i], Q["layers"][i], tape["layers"][i]
             n_in, g, gb, d, bi, p = L["n_in"], L["g"], L["gb"], L["d"], L["bi"], q["p"]
             stack = t["stack"]
+            convs = lambda stage: [(k, f"{p}.cbcr{stage}_{j}.net.0.weight", f"{p}.cbcr{stage}_{j}.net.1", f"{p}.cbcr{stage}_{j}.net.0.bias") for j, k in enumerate(ks)]  # noqa: E731
             # second stage: Swish(out1 + res) sends its gradient to out1's convolutions and to the downsample branch
-            dacc1, dres, sums = ops.tconv_epi_bwd(dS[:, n_in: n_in + g], tape["acc"][(i, 1)], q["scale1"], q["shift1"], rows=rows, C=g,
-                                                  act=ops.ACT_SWISH, res=t["res"], res_act=ops.ACT_SWISH)
+            dacc1, dres, sums = self._stage_bwd(st, accumulate, dS[:, n_in: n_in + g], tape["acc"][(i, 1)], q["scale1"], q["shift1"], t["out0"],
+                                                convs(1), B=B, T=T, n_in=g, co=gb, d=d, act=ops.ACT_SWISH, res=t["res"], res_act=ops.ACT_SWISH)
             self._put(*grad(f"{p}.downsample.bias"), sums[3])
-            for j, k in enumerate(ks):
-                c = f"{p}.cbcr1_{j}.net"
-                self._bn_grads(st, accumulate, sums, f"{c}.1", f"{c}.0.bias", j * gb, (j + 1) * gb)
-                gw, add = grad(f"{c}.0.weight")
-                ops.tconv_wgrad(t["out0"], dacc1[:, j * gb: (j + 1) * gb], gw, B=B, T=T, n_in=g, co=gb, k=k, d=d, add=add)
             dout0 = torch.empty((rows, g), dtype=BF16, device=dev)
             ops.tconv_dgrad(dacc1, B=B, T=T, co=gb, d=d, n_out=g, out=dout0,
                             branches=[dict(k=k, wt=q["wt1"][j], dy_off=j * gb) for j, k in enumerate(ks)])
             # first stage (gated)
-            dacc0, _, sums = ops.tconv_epi_bwd(dout0, tape["acc"][(i, 0)], q["scale0"], q["shift0"], rows=rows, C=g, act=ops.ACT_SWISH)
-            for j, k in enumerate(ks):
-                c = f"{p}.cbcr0_{j}.net"
-                self._bn_grads(st, accumulate, sums, f"{c}.1", f"{c}.0.bias", j * gb, (j + 1) * gb)
-                gw, add = grad(f"{c}.0.weight")
-                ops.tconv_wgrad(stack, dacc0[:, j * gb: (j + 1) * gb], gw, B=B, T=T, n_in=n_in, co=gb, k=k, d=d, gate=t["gates"][j], add=add)
+            dacc0, _, _ = self._stage_bwd(st, accumulate, dout0, tape["acc"][(i, 0)], q["scale0"], q["shift0"], stack, convs(0), B=B, T=T,
+                                          n_in=n_in, co=gb, d=d, gates=t["gates"], act=ops.ACT_SWISH)
             gpart = ops.tconv_dgrad(dacc0, B=B, T=T, co=gb, d=d, n_out=n_in, out=dS, x=stack, addend=dS,
                                     branches=[dict(k=k, wt=q["wt0"][j], dy_off=j * gb, gate=t["gates"][j]) for j, k in enumerate(ks)])
             g1 = [grad(f"{p}.cbcr0_se_{j}.fc.0.weight") for j in range(len(ks))]
@@ -491,23 +493,18 @@ class DCTCNLightningModule(_StoreModule):
             if i == 0 or P["layers"][i - 1]["bi"] != bi:          # the block's input: a transition's output
                 if bi == 0:
                     break
-                tr, x = Q["trans"][bi - 1], stacks[bi - 1]
-                n = P["trans"][bi - 1]["n_in"]
-                dacc, _, sums = ops.tconv_epi_bwd(dS[:, :R], tape["acc"][("tr", bi - 1)], P["trans"][bi - 1]["scale"], P["trans"][bi - 1]["shift"],
-                                                  rows=rows, C=R, act=ops.ACT_SWISH)
-                self._bn_grads(st, accumulate, sums, f"{tr['name']}.norm", None)
-                gw, add = grad(f"{tr['name']}.conv.weight")
-                ops.tconv_wgrad(x, dacc, gw, B=B, T=T, n_in=n, co=R, k=1, d=1, add=add)
+                tr, x, ptr = Q["trans"][bi - 1], stacks[bi - 1], P["trans"][bi - 1]
+                dacc, _, _ = self._stage_bwd(st, accumulate, dS[:, :R], tape["acc"][("tr", bi - 1)], ptr["scale"], ptr["shift"], x,
+                                             [(1, f"{tr['name']}.conv.weight", f"{tr['name']}.norm", None)], B=B, T=T, n_in=ptr["n_in"], co=R, d=1,
+                                             act=ops.ACT_SWISH)
                 dS = torch.empty_like(x)
-                ops.tconv_dgrad(dacc, B=B, T=T, co=R, d=1, n_out=n, out=dS, branches=[dict(k=1, wt=tr["wt"], dy_off=0)])
+                ops.tconv_dgrad(dacc, B=B, T=T, co=R, d=1, n_out=ptr["n_in"], out=dS, branches=[dict(k=1, wt=tr["wt"], dy_off=0)])
         # transition0 (PReLU)
         p = f"{TCN}.transition0"
-        dacc, _, sums = ops.tconv_epi_bwd(dS[:, :R], tape["acc"]["t0"], P["t0"]["scale"], P["t0"]["shift"], rows=rows, C=R, act=ops.ACT_PRELU,
-                                          slope=P["t0"]["slope"])
-        self._bn_grads(st, accumulate, sums, f"{p}.norm", None)
+        dacc, _, sums = self._stage_bwd(st, accumulate, dS[:, :R], tape["acc"]["t0"], P["t0"]["scale"], P["t0"]["shift"], tape["x0"],
+                                        [(1, f"{p}.conv.weight", f"{p}.norm", None)], B=B, T=T, n_in=self.in_pad, co=R, d=1, act=ops.ACT_PRELU,
+                                        slope=P["t0"]["slope"])
         self._put(*grad(f"{p}.prelu.weight"), sums[2])
-        gw, add = grad(f"{p}.conv.weight")
-        ops.tconv_wgrad(tape["x0"], dacc, gw, B=B, T=T, n_in=self.in_pad, co=R, k=1, d=1, add=add)
         if not want_input_grad:
             return None
         dx0 = torch.empty((rows, self.in_pad), dtype=BF16, device=dev)

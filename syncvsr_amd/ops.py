@@ -2175,96 +2175,9 @@ ACT_PRELU = 3
 TCONV_MAX_HALO = 16      # (k - 1) * d / 2 rows of the same clip on either side of a time tile (csrc/dctcn.hip TC_HALO)
 
 
-_TCONV_TABLES: list = []
-
-
 def tconv_ok(n_in: int, co: int, k: int, d: int) -> bool:
     """The shapes svsr_tconv_fwd takes (anything else is SVSR_ERR_ARG there)."""
     return n_in >= 64 and n_in % 64 == 0 and co >= 64 and co % 64 == 0 and k in (1, 3, 5, 7) and d >= 1 and (k - 1) * d // 2 <= TCONV_MAX_HALO
-
-
-def tconv_fwd(x: torch.Tensor, *, B: int, T: int, n_in: int, d: int, branches: Sequence[dict], co: int, act: int, out: torch.Tensor,
-              res: Optional[torch.Tensor] = None, res_act: int = ACT_NONE) -> torch.Tensor:
-    """Up to three dilated temporal convolutions of the rows x bf16 [B*T, pitch >= n_in] in one launch (svsr_tconv_fwd).  Each branch is a dict
-    k, w (bf16 [co, k, n_in]), scale / shift (fp32 [co]), out_off, and optionally gate (fp32 [B, n_in]), slope (fp32 [co], PReLU), res_off.
-    out bf16 [B*T, pitch]: channels [out_off, out_off + co) of every row are written, nothing else."""
-    assert x.dtype == BF16 and x.dim() == 2 and x.stride(1) == 1 and x.shape[0] >= B * T and x.shape[1] >= n_in
-    assert out.dtype == BF16 and out.dim() == 2 and out.stride(1) == 1 and out.shape[0] >= B * T
-    if res is not None:
-        assert res.dtype == BF16 and res.dim() == 2 and res.stride(1) == 1 and res.shape[0] >= B * T
-    rows = []
-    flops = 0.0
-    for i, br in enumerate(branches):
-        w, k = br["w"], int(br["k"])
-        assert w.dtype == BF16 and w.is_contiguous() and tuple(w.shape) == (co, k, n_in), (tuple(w.shape), (co, k, n_in))
-        for n in ("scale", "shift", "slope"):
-            t = br.get(n)
-            assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == co)
-        g = br.get("gate")
-        assert g is None or (g.dtype == torch.float32 and g.is_contiguous() and tuple(g.shape) == (B, n_in))
-        off, roff = int(br["out_off"]), int(br.get("res_off", 0))
-        assert 0 <= off and off + co <= out.shape[1] and (res is None or (0 <= roff and roff + co <= res.shape[1]))
-        rows.append((k, _p(w), _p(g) or 0, _p(br["scale"]), _p(br["shift"]), _p(br.get("slope")) or 0, off, roff))
-        flops += 2.0 * B * T * n_in * k * co
-    tab = torch.tensor(rows, dtype=torch.int64)          # host table, read during the call only
-    if _REC is not None:
-        _TCONV_TABLES.append(tab)                       # a recorded step list re-reads it at every replay: keep it alive
-    _call("svsr_tconv_fwd", _p(x), x.stride(0), B, T, n_in, int(d), len(branches), tab.data_ptr(), co, int(act), _p(out), out.stride(0), _p(res),
-          0 if res is None else res.stride(0), int(res_act), _stream(), label="k_tconv", flops=flops)
-    return out
-
-
-def tcn_se_fwd(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, *, B: int, T: int, n_in: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """x bf16 [B*T, pitch >= n_in], w1 bf16 [nb, R, n_in], w2 bf16 [nb, n_in, R] -> gate fp32 [nb, B, n_in] = sigmoid(W2 swish(W1 mean_t x))
-    (svsr_tcn_se_fwd): the time mean once, the nb gates of a layer in one launch."""
-    nb, R = w1.shape[0], w1.shape[1]
-    assert x.dtype == BF16 and x.dim() == 2 and x.stride(1) == 1 and x.shape[0] >= B * T and x.shape[1] >= n_in
-    assert w1.dtype == BF16 and w1.is_contiguous() and tuple(w1.shape) == (nb, R, n_in)
-    assert w2.dtype == BF16 and w2.is_contiguous() and tuple(w2.shape) == (nb, n_in, R)
-    gate = torch.empty((nb, B, n_in), dtype=torch.float32, device=x.device) if out is None else out
-    assert gate.dtype == torch.float32 and gate.is_contiguous() and tuple(gate.shape) == (nb, B, n_in)
-    _call("svsr_tcn_se_fwd", _p(x), x.stride(0), B, T, n_in, R, nb, _p(w1), _p(w2), _p(gate), _stream(), label="k_tcn_se")
-    return gate
-
-
-def tcn_norm_pool_fwd(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, mask: torch.Tensor, *, B: int, T: int, C: int):
-    """x bf16 [B*T, pitch >= C], mask fp32 [B, T] -> (h bf16 [B*T, C] = x * scale + shift, pooled bf16 [B, C] = masked mean of h over time)
-    (svsr_tcn_norm_pool_fwd)."""
-    assert x.dtype == BF16 and x.dim() == 2 and x.stride(1) == 1 and x.shape[0] >= B * T and x.shape[1] >= C
-    assert mask.dtype == torch.float32 and mask.is_contiguous() and mask.numel() == B * T
-    for t in (scale, shift):
-        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == C
-    h = torch.empty((B * T, C), dtype=BF16, device=x.device)
-    pooled = torch.empty((B, C), dtype=BF16, device=x.device)
-    _call("svsr_tcn_norm_pool_fwd", _p(x), x.stride(0), B, T, C, _p(scale), _p(shift), _p(mask), _p(h), _p(pooled), _stream(), label="k_tcn_norm_pool")
-    return h, pooled
-
-
-# -- backward of the back-end (statistics mode of the forward: running-statistic BatchNorm, no dropout) ------------------------------
-def tconv_fwd_save(x: torch.Tensor, *, B: int, T: int, n_in: int, d: int, branches: Sequence[dict], co: int, act: int, out: torch.Tensor,
-                   acc: torch.Tensor, res: Optional[torch.Tensor] = None, res_act: int = ACT_NONE) -> torch.Tensor:
-    """tconv_fwd (same output bits) that also stores the fp32 accumulators: acc fp32 [B*T, >= nb * co], branch i at channels [i * co, (i + 1) * co)
-    (svsr_tconv_fwd_save)."""
-    assert x.dtype == BF16 and x.dim() == 2 and x.stride(1) == 1 and x.shape[0] >= B * T and x.shape[1] >= n_in
-    assert out.dtype == BF16 and out.dim() == 2 and out.stride(1) == 1 and out.shape[0] >= B * T
-    assert acc.dtype == torch.float32 and acc.dim() == 2 and acc.stride(1) == 1 and acc.shape[0] >= B * T and acc.shape[1] >= len(branches) * co
-    if res is not None:
-        assert res.dtype == BF16 and res.dim() == 2 and res.stride(1) == 1 and res.shape[0] >= B * T
-    rows = []
-    flops = 0.0
-    for br in branches:
-        w, k = br["w"], int(br["k"])
-        assert w.dtype == BF16 and w.is_contiguous() and tuple(w.shape) == (co, k, n_in), (tuple(w.shape), (co, k, n_in))
-        g = br.get("gate")
-        assert g is None or (g.dtype == torch.float32 and g.is_contiguous() and tuple(g.shape) == (B, n_in))
-        off, roff = int(br["out_off"]), int(br.get("res_off", 0))
-        assert 0 <= off and off + co <= out.shape[1] and (res is None or (0 <= roff and roff + co <= res.shape[1]))
-        rows.append((k, _p(w), _p(g) or 0, _p(br["scale"]), _p(br["shift"]), _p(br.get("slope")) or 0, off, roff))
-        flops += 2.0 * B * T * n_in * k * co
-    tab = torch.tensor(rows, dtype=torch.int64)
-    _call("svsr_tconv_fwd_save", _p(x), x.stride(0), B, T, n_in, int(d), len(branches), tab.data_ptr(), co, int(act), _p(out), out.stride(0), _p(res),
-          0 if res is None else res.stride(0), int(res_act), _p(acc), acc.stride(0), _stream(), label="k_tconv<save>", flops=flops)
-    return out
 
 
 def _rows_view(t: torch.Tensor, rows: int, width: int, dtype) -> None:
@@ -2272,6 +2185,86 @@ def _rows_view(t: torch.Tensor, rows: int, width: int, dtype) -> None:
         raise ValueError(f"expected a {dtype} [>= {rows}, >= {width}] row tensor with unit channel stride, got {tuple(t.shape)} {t.dtype}")
 
 
+def _packed(t: Optional[torch.Tensor], dtype, shape=None, numel: Optional[int] = None, optional: bool = False) -> None:
+    """A contiguous tensor of `dtype` with exactly `shape`, or (shape None) exactly `numel` elements; optional: None passes."""
+    if t is None and optional:
+        return
+    if not (t.dtype == dtype and t.is_contiguous() and (tuple(t.shape) == tuple(shape) if shape is not None else t.numel() == numel)):
+        raise ValueError(f"expected a contiguous {dtype} tensor of {'shape ' + str(tuple(shape)) if shape is not None else str(numel) + ' elements'}, "
+                         f"got {tuple(t.shape)} {t.dtype}")
+
+
+def _host_table(rows) -> torch.Tensor:
+    """The host int64 table a launch reads during the call: the caller holds the result until the call has returned.  A recorded step list
+    re-reads it at every replay, so inside a recording the recorder owns it too (StepRecorder.keep)."""
+    tab = torch.tensor(rows, dtype=torch.int64)
+    if _REC is not None:
+        _REC.keep.append(tab)
+    return tab
+
+
+def tconv_fwd(x: torch.Tensor, *, B: int, T: int, n_in: int, d: int, branches: Sequence[dict], co: int, act: int, out: torch.Tensor,
+              res: Optional[torch.Tensor] = None, res_act: int = ACT_NONE, acc: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Up to three dilated temporal convolutions of the rows x bf16 [B*T, pitch >= n_in] in one launch (svsr_tconv_fwd).  Each branch is a dict
+    k, w (bf16 [co, k, n_in]), scale / shift (fp32 [co]), out_off, and optionally gate (fp32 [B, n_in]), slope (fp32 [co], PReLU), res_off.
+    out bf16 [B*T, pitch]: channels [out_off, out_off + co) of every row are written, nothing else.  With acc (fp32 [B*T, >= nb * co]) the
+    kernel's saving instantiation runs (svsr_tconv_fwd_save): the same output bits, and the fp32 accumulators of branch i at channels
+    [i * co, (i + 1) * co) of acc — what the backward of the back-end reads."""
+    _rows_view(x, B * T, n_in, BF16)
+    _rows_view(out, B * T, 0, BF16)
+    if acc is not None:
+        _rows_view(acc, B * T, len(branches) * co, torch.float32)
+    if res is not None:
+        _rows_view(res, B * T, 0, BF16)
+    rows = []
+    for br in branches:
+        w, k, g = br["w"], int(br["k"]), br.get("gate")
+        _packed(w, BF16, (co, k, n_in))
+        for n in ("scale", "shift", "slope"):
+            _packed(br.get(n), torch.float32, numel=co, optional=True)
+        _packed(g, torch.float32, (B, n_in), optional=True)
+        off, roff = int(br["out_off"]), int(br.get("res_off", 0))
+        if not (0 <= off and off + co <= out.shape[1] and (res is None or (0 <= roff and roff + co <= res.shape[1]))):
+            raise ValueError(f"tconv_fwd: channels [{off}, {off + co}) / [{roff}, {roff + co}) lie outside the output / residual rows")
+        rows.append((k, _p(w), _p(g) or 0, _p(br["scale"]), _p(br["shift"]), _p(br.get("slope")) or 0, off, roff))
+    flops = sum(2.0 * B * T * n_in * r[0] * co for r in rows)
+    tab = _host_table(rows)
+    head = (_p(x), x.stride(0), B, T, n_in, int(d), len(branches), tab.data_ptr(), co, int(act), _p(out), out.stride(0), _p(res),
+            0 if res is None else res.stride(0), int(res_act))
+    if acc is None:
+        _call("svsr_tconv_fwd", *head, _stream(), label="k_tconv", flops=flops)
+    else:
+        _call("svsr_tconv_fwd_save", *head, _p(acc), acc.stride(0), _stream(), label="k_tconv<save>", flops=flops)
+    return out
+
+
+def tcn_se_fwd(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, *, B: int, T: int, n_in: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x bf16 [B*T, pitch >= n_in], w1 bf16 [nb, R, n_in], w2 bf16 [nb, n_in, R] -> gate fp32 [nb, B, n_in] = sigmoid(W2 swish(W1 mean_t x))
+    (svsr_tcn_se_fwd): the time mean once, the nb gates of a layer in one launch."""
+    nb, R = w1.shape[0], w1.shape[1]
+    _rows_view(x, B * T, n_in, BF16)
+    _packed(w1, BF16, (nb, R, n_in))
+    _packed(w2, BF16, (nb, n_in, R))
+    gate = torch.empty((nb, B, n_in), dtype=torch.float32, device=x.device) if out is None else out
+    _packed(gate, torch.float32, (nb, B, n_in))
+    _call("svsr_tcn_se_fwd", _p(x), x.stride(0), B, T, n_in, R, nb, _p(w1), _p(w2), _p(gate), _stream(), label="k_tcn_se")
+    return gate
+
+
+def tcn_norm_pool_fwd(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, mask: torch.Tensor, *, B: int, T: int, C: int):
+    """x bf16 [B*T, pitch >= C], mask fp32 [B, T] -> (h bf16 [B*T, C] = x * scale + shift, pooled bf16 [B, C] = masked mean of h over time)
+    (svsr_tcn_norm_pool_fwd)."""
+    _rows_view(x, B * T, C, BF16)
+    _packed(mask, torch.float32, numel=B * T)
+    for t in (scale, shift):
+        _packed(t, torch.float32, numel=C)
+    h = torch.empty((B * T, C), dtype=BF16, device=x.device)
+    pooled = torch.empty((B, C), dtype=BF16, device=x.device)
+    _call("svsr_tcn_norm_pool_fwd", _p(x), x.stride(0), B, T, C, _p(scale), _p(shift), _p(mask), _p(h), _p(pooled), _stream(), label="k_tcn_norm_pool")
+    return h, pooled
+
+
+# -- backward of the back-end (statistics mode of the forward: running-statistic BatchNorm, no dropout) ------------------------------
 def tconv_epi_bwd(dy: torch.Tensor, acc: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, *, rows: int, C: int, act: int,
                   slope: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None, res_act: int = ACT_NONE,
                   dacc: Optional[torch.Tensor] = None, dres: Optional[torch.Tensor] = None):
@@ -2282,7 +2275,7 @@ def tconv_epi_bwd(dy: torch.Tensor, acc: torch.Tensor, scale: torch.Tensor, shif
     _rows_view(dy, rows, C, BF16)
     _rows_view(acc, rows, C, torch.float32)
     for t in (scale, shift, slope):
-        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == C)
+        _packed(t, torch.float32, numel=C, optional=True)
     dev = dy.device
     if dacc is None:
         dacc = torch.empty((rows, C), dtype=BF16, device=dev)
@@ -2318,22 +2311,21 @@ def tconv_dgrad(dy: torch.Tensor, *, B: int, T: int, co: int, d: int, branches: 
         _rows_view(x, rows, n_out, BF16)
     if addend is not None:
         _rows_view(addend, rows, n_out, BF16)
-    assert dy.dtype == BF16 and dy.dim() == 2 and dy.stride(1) == 1 and dy.shape[0] >= rows
-    assert cadd is None or (cadd.dtype == torch.float32 and cadd.is_contiguous() and tuple(cadd.shape) == (B, n_out))
-    tab_rows, flops = [], 0.0
+    _rows_view(dy, rows, 0, BF16)
+    _packed(cadd, torch.float32, (B, n_out), optional=True)
+    tab_rows = []
     for br in branches:
-        k, wt, off = int(br["k"]), br["wt"], int(br["dy_off"])
-        assert wt.dtype == BF16 and wt.is_contiguous() and tuple(wt.shape) == (n_out, k, co), (tuple(wt.shape), (n_out, k, co))
-        assert 0 <= off and off + co <= dy.shape[1]
-        g = br.get("gate")
-        assert g is None or (g.dtype == torch.float32 and g.is_contiguous() and tuple(g.shape) == (B, n_out))
+        k, wt, off, g = int(br["k"]), br["wt"], int(br["dy_off"]), br.get("gate")
+        _packed(wt, BF16, (n_out, k, co))
+        if not (0 <= off and off + co <= dy.shape[1]):
+            raise ValueError(f"tconv_dgrad: channels [{off}, {off + co}) lie outside the gradient rows")
+        _packed(g, torch.float32, (B, n_out), optional=True)
         tab_rows.append((k, _p(wt), _p(g) or 0, off))
-        flops += 2.0 * rows * n_out * k * co
-    tab = torch.tensor(tab_rows, dtype=torch.int64)
     gpart = torch.empty((len(branches), B, (T + 31) // 32, n_out), dtype=torch.float32, device=dy.device) if gated else None
-    _call("svsr_tconv_dgrad", _p(dy), dy.stride(0), B, T, co, int(d), len(branches), tab.data_ptr(), n_out, _p(x), 0 if x is None else x.stride(0),
-          _p(addend), 0 if addend is None else addend.stride(0), _p(cadd), float(cadd_scale), _p(out), out.stride(0), _p(gpart), _stream(),
-          label="k_tconv_dgrad", flops=flops)
+    tab = _host_table(tab_rows)
+    _call("svsr_tconv_dgrad", _p(dy), dy.stride(0), B, T, co, int(d), len(branches), tab.data_ptr(), n_out, _p(x),
+          0 if x is None else x.stride(0), _p(addend), 0 if addend is None else addend.stride(0), _p(cadd), float(cadd_scale), _p(out), out.stride(0),
+          _p(gpart), _stream(), label="k_tconv_dgrad", flops=sum(2.0 * rows * n_out * r[0] * co for r in tab_rows))
     return gpart
 
 
@@ -2360,7 +2352,7 @@ def tconv_wgrad(x: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor, *, B: int, 
     _rows_view(dy, rows, co, BF16)
     if not (dw.dtype == torch.float32 and dw.is_contiguous() and dw.dim() == 3 and dw.shape[0] == co and dw.shape[2] == k and 1 <= dw.shape[1] <= n_in):
         raise ValueError(f"tconv_wgrad: dw must be a contiguous fp32 [co, <= n_in, k] tensor, got {tuple(dw.shape)}")
-    assert gate is None or (gate.dtype == torch.float32 and gate.is_contiguous() and tuple(gate.shape) == (B, n_in))
+    _packed(gate, torch.float32, (B, n_in), optional=True)
     S = tconv_wgrad_splits(B, T, n_in, co) if splits is None else int(splits)
     part = torch.empty(S * co * k * n_in, dtype=torch.float32, device=x.device)
     _call("svsr_tconv_wgrad", _p(x), x.stride(0), _p(gate), _p(dy), dy.stride(0), B, T, n_in, co, int(k), int(d), S, _p(part), _p(dw), dw.shape[1],
@@ -2373,19 +2365,20 @@ def tcn_se_bwd(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, gate: torch.
     all branches) and the weight gradients dw1[i] fp32 [R, n_in], dw2[i] fp32 [n_in, R] written (add: added to)."""
     nb, R = w1.shape[0], w1.shape[1]
     _rows_view(x, B * T, n_in, BF16)
-    assert w1.dtype == BF16 and w1.is_contiguous() and tuple(w1.shape) == (nb, R, n_in)
-    assert w2.dtype == BF16 and w2.is_contiguous() and tuple(w2.shape) == (nb, n_in, R)
-    assert gate.dtype == torch.float32 and gate.is_contiguous() and tuple(gate.shape) == (nb, B, n_in)
-    assert gpart.dtype == torch.float32 and gpart.is_contiguous() and tuple(gpart.shape) == (nb, B, (T + 31) // 32, n_in)
+    _packed(w1, BF16, (nb, R, n_in))
+    _packed(w2, BF16, (nb, n_in, R))
+    _packed(gate, torch.float32, (nb, B, n_in))
+    _packed(gpart, torch.float32, (nb, B, (T + 31) // 32, n_in))
     if 2 * (3 * n_in + 2 * R) * 4 > 64 * 1024:
         raise ValueError("tcn_se_bwd: n_in too wide for the workgroup's LDS (2 clips x (3 n_in + 2 R) floats <= 64 KiB)")
-    assert len(dw1) == nb and len(dw2) == nb
-    for a, b in zip(dw1, dw2):
-        assert a.dtype == torch.float32 and a.is_contiguous() and a.numel() == R * n_in and b.dtype == torch.float32 and b.is_contiguous() and b.numel() == R * n_in
+    if not (len(dw1) == nb and len(dw2) == nb):
+        raise ValueError(f"tcn_se_bwd: one dw1 and one dw2 per branch ({nb}), got {len(dw1)} and {len(dw2)}")
+    for t in (*dw1, *dw2):
+        _packed(t, torch.float32, numel=R * n_in)
     dev = x.device
     work = torch.empty(nb * B * n_in + 2 * nb * B * R + B * n_in, dtype=torch.float32, device=dev)
     dm = torch.empty((B, n_in), dtype=torch.float32, device=dev)
-    tab = torch.tensor([_p(t) for t in dw1] + [_p(t) for t in dw2], dtype=torch.int64)
+    tab = _host_table([_p(t) for t in dw1] + [_p(t) for t in dw2])
     _call("svsr_tcn_se_bwd", _p(x), x.stride(0), B, T, n_in, R, nb, _p(w1), _p(w2), _p(gate), _p(gpart), _p(work), _p(dm), tab.data_ptr(),
           int(bool(add)), _stream(), label="k_tcn_se_bwd")
     return dm
@@ -2397,12 +2390,12 @@ def tcn_norm_pool_bwd(dh: torch.Tensor, dpooled: torch.Tensor, x: torch.Tensor, 
     -> out bf16 [B*T, >= C] channels [0, C) written, sums fp32 [2, C] = (sum g, sum g * x)."""
     if C < 8 or C % 8:
         raise ValueError("tcn_norm_pool_bwd: C must be a multiple of 8")
-    assert dh.dtype == BF16 and dh.is_contiguous() and tuple(dh.shape) == (B * T, C)
-    assert dpooled.dtype == BF16 and dpooled.is_contiguous() and tuple(dpooled.shape) == (B, C)
+    _packed(dh, BF16, (B * T, C))
+    _packed(dpooled, BF16, (B, C))
     _rows_view(x, B * T, C, BF16)
     _rows_view(out, B * T, C, BF16)
-    assert mask.dtype == torch.float32 and mask.is_contiguous() and mask.numel() == B * T
-    assert scale.dtype == torch.float32 and scale.is_contiguous() and scale.numel() == C
+    _packed(mask, torch.float32, numel=B * T)
+    _packed(scale, torch.float32, numel=C)
     part = torch.empty(B * 2 * C, dtype=torch.float32, device=dh.device)
     sums = torch.empty((2, C), dtype=torch.float32, device=dh.device)
     _call("svsr_tcn_norm_pool_bwd", _p(dh), _p(dpooled), _p(x), x.stride(0), B, T, C, _p(scale), _p(mask), _p(out), out.stride(0), _p(part), _p(sums),

@@ -1,5 +1,9 @@
-"""CPU half of the DC-TCN backward: the C ABI of the new entry points, the Python-side shape refusals, the O(C) chain rule from the
-per-channel sums to the BatchNorm / bias gradients, and the bf16 noise floor recorded in profiles/dctcn_backward.json."""
+"""CPU half of the DC-TCN backward: the C ABI of the new entry points, the Python-side shape refusals, who owns the host tables, the O(C)
+chain rule from the per-channel sums to the BatchNorm / bias gradients, and the bf16 noise floor recorded in profiles/dctcn_backward.json."""
+import gc
+import types
+import weakref
+
 import pytest
 import torch
 
@@ -58,6 +62,66 @@ def test_python_side_shape_refusals():
     assert ops.tconv_wgrad_splits(96, 29, 512, 128) == ops.tconv_wgrad_splits(96, 29, 512, 128) <= 8
     assert ops.tconv_wgrad_splits(1, 1, 64, 64) == 1
     assert f32 is torch.float32
+
+
+def _table_passing_calls(ops):
+    """The four wrappers that hand a host table to the library, on CPU tensors of the smallest legal shapes: (name, index of the table among the
+    C arguments, call)."""
+    bf = torch.bfloat16
+    B, T, n, R = 1, 1, 64, 4
+    x, out, one = torch.zeros(B * T, n, dtype=bf), torch.zeros(B * T, n, dtype=bf), torch.ones(n)
+    fbr = [dict(k=1, w=torch.zeros(n, 1, n, dtype=bf), scale=one, shift=one, out_off=0)]
+    dbr = [dict(k=1, wt=torch.zeros(n, 1, n, dtype=bf), dy_off=0, gate=torch.ones(B, n))]
+    w1, w2 = torch.zeros(1, R, n, dtype=bf), torch.zeros(1, n, R, dtype=bf)
+    return [("svsr_tconv_fwd", 7, lambda: ops.tconv_fwd(x, B=B, T=T, n_in=n, d=1, branches=fbr, co=n, act=0, out=out)),
+            ("svsr_tconv_fwd_save", 7, lambda: ops.tconv_fwd(x, B=B, T=T, n_in=n, d=1, branches=fbr, co=n, act=0, out=out, acc=torch.zeros(B * T, n))),
+            ("svsr_tconv_dgrad", 7, lambda: ops.tconv_dgrad(x, B=B, T=T, co=n, d=1, branches=dbr, n_out=n, out=out, x=x)),
+            ("svsr_tcn_se_bwd", 13, lambda: ops.tcn_se_bwd(x, w1, w2, torch.ones(1, B, n), torch.zeros(1, B, 1, n), [torch.zeros(R, n)],
+                                                           [torch.zeros(n, R)], B=B, T=T, n_in=n))]
+
+
+def test_host_tables_belong_to_the_recorder_and_to_nobody_outside_a_recording(monkeypatch):
+    """A recorded step list re-reads a launch's host table at every replay: inside a recording every table-passing wrapper hands its table to
+    the recorder (StepRecorder.keep); outside one the module retains none (there is no module-level list of them any more)."""
+    from syncvsr_amd import ops
+
+    calls, made = [], []
+    real_tensor = torch.tensor
+
+    def spy(*a, **k):                                       # every host table is a torch.tensor(..., dtype=int64)
+        t = real_tensor(*a, **k)
+        if t.dtype == torch.int64:
+            made.append(weakref.ref(t))
+        return t
+
+    def fake_call(name, *args, **kw):
+        alive = [r() for r in made if r() is not None]
+        calls.append((name, args, [t for t in alive if t.data_ptr() == args[_IDX[name]]]))
+
+    cases = _table_passing_calls(ops)
+    _IDX = {name: idx for name, idx, _ in cases}
+    monkeypatch.setattr(ops, "_call", fake_call)
+    monkeypatch.setattr(ops, "STREAM_OVERRIDE", 0)
+    monkeypatch.setattr(torch, "tensor", spy)
+    stub = types.SimpleNamespace(keep=[], append_only=False)
+    monkeypatch.setattr(ops, "_REC", stub)
+    for name, idx, fn in cases:
+        fn()
+        got, args, tabs = calls[-1]
+        assert got == name and len(tabs) == 1, (name, got, len(tabs))
+        assert any(t is tabs[0] for t in stub.keep), f"{name}: the table it passed is not in the recorder's keep list"
+        assert args[idx] == tabs[0].data_ptr() and tabs[0].dtype == torch.int64 and not tabs[0].is_cuda
+    assert len(stub.keep) == len(cases)
+    # outside a recording: the table the call read is gone once the wrapper has returned
+    monkeypatch.setattr(ops, "_REC", None)
+    del made[:], calls[:], tabs
+    for name, idx, fn in cases:
+        fn()
+        assert calls[-1][0] == name and len(calls[-1][2]) == 1
+    del calls[:]
+    gc.collect()
+    assert len(made) == len(cases) and all(r() is None for r in made), "a host table outlived its call outside a recording"
+    assert not hasattr(ops, "_TCONV_TABLES") and not hasattr(ops, "tconv_fwd_save")
 
 
 def test_host_chain_rule_matches_autograd_with_a_zero_batchnorm_weight():

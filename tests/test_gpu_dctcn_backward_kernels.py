@@ -248,7 +248,7 @@ def test_norm_pool_backward_and_saved_accumulators():
     br = [dict(k=k, w=w, scale=sc, shift=sh, out_off=0)]
     o1 = ops.tconv_fwd(xs, B=B, T=T, n_in=n_in, d=d, branches=br, co=co, act=2, out=torch.empty(B * T, co, dtype=BF, device=DEV))
     accb = torch.full((B * T + 1, co + 8), SENT, device=DEV)
-    o2 = ops.tconv_fwd_save(xs, B=B, T=T, n_in=n_in, d=d, branches=br, co=co, act=2, out=torch.empty(B * T, co, dtype=BF, device=DEV), acc=accb)
+    o2 = ops.tconv_fwd(xs, B=B, T=T, n_in=n_in, d=d, branches=br, co=co, act=2, out=torch.empty(B * T, co, dtype=BF, device=DEV), acc=accb)
     assert torch.equal(o1.view(torch.int16), o2.view(torch.int16))
     z = accb[: B * T, :co] * sc + sh
     assert _rel_err((z * torch.sigmoid(z)).cpu(), o1.float().cpu()) < LINEAR_BOUND
@@ -295,3 +295,64 @@ def test_out_of_domain_arguments_return_err_arg_and_write_nothing():
     assert lib.svsr_tcn_fold(f.data_ptr(), 1, 0, f.data_ptr(), 0, None) == 1001
     torch.cuda.synchronize()
     assert bool((out.float() == SENT).all()) and bool((f == SENT).all())
+
+
+def _table_passing_sequence(ops, t, B, T, n_in, co):
+    """svsr_tconv_fwd_save -> svsr_tconv_dgrad (gated) -> svsr_tcn_se_bwd on the tensors of t, each launch with a host table.
+    -> (gate partials, dm): what the wrappers allocate themselves."""
+    ops.tconv_fwd(t["x"], B=B, T=T, n_in=n_in, d=2, co=co, act=2, out=t["y"], acc=t["acc"],
+                  branches=[dict(k=3, w=t["w"], gate=t["gate"][0], scale=t["scale"], shift=t["shift"], out_off=0)])
+    gp = ops.tconv_dgrad(t["dy"], B=B, T=T, co=co, d=2, n_out=n_in, out=t["dx"], x=t["x"], branches=[dict(k=3, wt=t["wt"], dy_off=0, gate=t["gate"][0])])
+    dm = ops.tcn_se_bwd(t["x"], t["w1"], t["w2"], t["gate"], gp, [t["dw1"]], [t["dw2"]], B=B, T=T, n_in=n_in)
+    return gp, dm
+
+
+def test_recorded_replay_owns_its_host_tables():
+    """A step list records the three table-passing launches; every Python reference to what the wrappers made is dropped, host memory is
+    churned and the inputs are refilled in place: the replay equals an eager run on the new inputs bit for bit (the recorder keeps the tables)."""
+    import gc
+
+    from syncvsr_amd import ops
+
+    B, T, n_in, co, Rr = 2, 5, 128, 64, 8
+    inputs = dict(x=(B * T, n_in), dy=(B * T, co), w=(co, 3, n_in), wt=(n_in, 3, co), w1=(1, Rr, n_in), w2=(1, n_in, Rr))
+
+    def fill(t, seed):
+        for i, (n, shape) in enumerate(inputs.items()):
+            t[n].copy_((_r(*shape, seed=seed + i) * (0.1 if n[0] == "w" else 1.0)).to(BF))
+        t["gate"].copy_(torch.sigmoid(_r(1, B, n_in, seed=seed + 10)))
+        t["scale"].copy_(1 + 0.1 * _r(co, seed=seed + 11))
+        t["shift"].copy_(0.1 * _r(co, seed=seed + 12))
+
+    def tensors():
+        t = {n: torch.empty(shape, dtype=BF, device=DEV) for n, shape in inputs.items()}
+        t.update(gate=torch.empty(1, B, n_in, device=DEV), scale=torch.empty(co, device=DEV), shift=torch.empty(co, device=DEV))
+        t.update(y=torch.full((B * T, co), SENT, dtype=BF, device=DEV), acc=torch.full((B * T, co), SENT, device=DEV),
+                 dx=torch.full((B * T, n_in), SENT, dtype=BF, device=DEV), dw1=torch.full((Rr, n_in), SENT, device=DEV),
+                 dw2=torch.full((n_in, Rr), SENT, device=DEV))
+        return t
+
+    outs = ("y", "acc", "dx", "dw1", "dw2")
+    t = tensors()
+    fill(t, 1000)
+    rec = ops.StepRecorder()
+    with ops.recording(rec):
+        gp, dm = _table_passing_sequence(ops, t, B, T, n_in, co)
+    torch.cuda.synchronize()
+    first = [t[n].clone() for n in outs]
+    gc.collect()
+    churn = [torch.zeros(n, dtype=torch.int64) for n in (2, 4, 8, 16, 2, 4, 8, 16)]          # zeros: a table read from re-used memory is refused, not followed
+    del churn
+    fill(t, 2000)
+    rec.run()
+    torch.cuda.synchronize()
+    e = tensors()
+    fill(e, 2000)
+    egp, edm = _table_passing_sequence(ops, e, B, T, n_in, co)
+    torch.cuda.synchronize()
+    for n, before in zip(outs, first):
+        view = torch.int16 if t[n].dtype == BF else torch.int32
+        assert torch.equal(t[n].view(view), e[n].view(view)), f"{n}: the replay differs from an eager run on the same inputs"
+        assert not torch.equal(t[n].view(view), before.view(view)), f"{n}: the replay did not see the refilled inputs"
+    assert torch.equal(gp.view(torch.int32), egp.view(torch.int32)) and torch.equal(dm.view(torch.int32), edm.view(torch.int32))
+    assert sum(1 for k in rec.keep if torch.is_tensor(k) and k.dtype == torch.int64 and not k.is_cuda) == 3
