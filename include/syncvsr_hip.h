@@ -720,6 +720,34 @@ int svsr_tcn_se_bwd(const void* x, int64_t x_pitch, int B, int T, int n_in, int 
 int svsr_tcn_norm_pool_bwd(const void* dh, const void* dpooled, const void* x, int64_t x_pitch, int B, int T, int C, const float* scale, const float* mask, void* dx, int64_t dx_pitch, float* part, float* sums, hipStream_t stream);
 int svsr_tcn_fold(const float* part, int rows, int64_t n, float* out, int add, hipStream_t stream);
 
+/* ---- batch-statistic stages of the dense temporal back-end (dctcn.hip; loss_and_backend_grads(train_stats=True)) --------------
+ * The reference's TemporalConvLayer is Conv1d(padding = (k-1)d) -> BatchNorm1d -> symmetric chomp -> activation: in training mode a
+ * branch's statistics run over T + (k-1)d positions a clip.  A stage is convolution -> statistics -> apply on the EXTENDED axis: with
+ * h_i = (k_i - 1) d / 2 <= hmax <= 16 a clip owns T + 2 hmax rows, time t is row t + hmax, branch i owns rows [hmax - h_i, hmax + h_i + T).
+ * `h` is a HOST table of nb ints (the h_i); C = nb * co; channels [i * co, (i + 1) * co) are branch i's.
+ *
+ * svsr_tconv_fwd_ext: svsr_tconv_fwd's convolution (same table; k, w, gate are read) at every own row of every branch: fp32 accumulators
+ *   acc [B * (T + 2 hmax)][acc_pitch], no activation row.  Rows outside a branch's extent are neither written nor read by anything.
+ * svsr_tcn_colstats: stats fp32 [2][C] = per channel (mean, sum (x - mean)^2) over the B * (T + 2 h_i) own rows of x (fp32, or bf16 with
+ *   is_bf16): per clip a mean and the squares against it, clips merged in order with Chan's update.  part: fp32 scratch [B][2][C].
+ * svsr_tconv_apply: k_tconv's epilogue on the T interior rows: z = fma(acc, scale, shift), activation, dropout (drop_p > 0: element
+ *   row * C + c kept iff drop_keep(drop_key, p * 2^32, .), kept values times 1 / (1 - p); B * T * C <= 2^32 with drop_p > 0, the index being a
+ *   32-bit counter), + res, res_act -> out bf16 [B * T][out_pitch].
+ * svsr_tconv_epi_bwd_bs: pass 1 of the backward, svsr_tconv_epi_bwd's sums [4][C] and dres over the interior rows with the mask in the chain
+ *   (no dacc).  part: fp32 scratch [ceil(B T / 64)][4][C].
+ * svsr_tconv_bn_bwd: pass 2, dacc bf16 [B * (T + 2 hmax)][dacc_pitch] = scale * (g - ca - xhat * cb) on a branch's own rows (g recomputed on
+ *   interior rows, 0 on chomped ones; xhat = (acc - mean) * invstd), zeros on the others.
+ * svsr_tconv_dgrad_ext / svsr_tconv_wgrad_ext: svsr_tconv_dgrad / svsr_tconv_wgrad over such gradient rows (hmax = 0: the same launch).
+ * svsr_tcn_norm_pool_bwd_bs: svsr_tcn_norm_pool_bwd's dx with norm5's batch statistics in the chain (no sums). */
+int svsr_tconv_fwd_ext(const void* x, int64_t x_pitch, int B, int T, int n_in, int d, int nb, const int64_t* branches, int co, int hmax, float* acc, int64_t acc_pitch, hipStream_t stream);
+int svsr_tcn_colstats(const void* x, int64_t pitch, int is_bf16, int B, int T, int C, int co, int hmax, int nb, const int* h, float* part, float* stats, hipStream_t stream);
+int svsr_tconv_apply(const float* acc, int64_t acc_pitch, int B, int T, int C, int co, int hmax, int nb, const int* h, int act, const float* scale, const float* shift, const float* slope, const void* res, int64_t res_pitch, int res_act, unsigned drop_key, float drop_p, void* out, int64_t out_pitch, hipStream_t stream);
+int svsr_tconv_epi_bwd_bs(const void* dy, int64_t dy_pitch, const float* acc, int64_t acc_pitch, int B, int T, int C, int co, int hmax, int nb, const int* h, int act, const float* scale, const float* shift, const float* slope, const void* res, int64_t res_pitch, int res_act, unsigned drop_key, float drop_p, void* dres, int64_t dres_pitch, float* part, float* sums, hipStream_t stream);
+int svsr_tconv_bn_bwd(const void* dy, int64_t dy_pitch, const float* acc, int64_t acc_pitch, int B, int T, int C, int co, int hmax, int nb, const int* h, int act, const float* scale, const float* shift, const float* slope, const void* res, int64_t res_pitch, int res_act, unsigned drop_key, float drop_p, const float* mean, const float* invstd, const float* ca, const float* cb, void* dacc, int64_t dacc_pitch, hipStream_t stream);
+int svsr_tconv_dgrad_ext(const void* dy, int64_t dy_pitch, int B, int T, int co, int d, int nb, const int64_t* branches, int n_out, const void* x, int64_t x_pitch, const void* addend, int64_t add_pitch, const float* cadd, float cadd_scale, void* out, int64_t out_pitch, float* gpart, int hmax, hipStream_t stream);
+int svsr_tconv_wgrad_ext(const void* x, int64_t x_pitch, const float* gate, const void* dy, int64_t dy_pitch, int B, int T, int n_in, int co, int k, int d, int splits, float* part, float* dw, int n_valid, int add, int hmax, hipStream_t stream);
+int svsr_tcn_norm_pool_bwd_bs(const void* dh, const void* dpooled, const void* x, int64_t x_pitch, int B, int T, int C, const float* scale, const float* mean, const float* invstd, const float* ca, const float* cb, const float* mask, void* dx, int64_t dx_pitch, hipStream_t stream);
+
 /* ---- multi-clip beam search (lrs_search.hip; BatchBeamSearch.forward_clips of syncvsr_amd/lrs_infer.py) -----------------
  * C clips advance through one search in lock step.  The n live hypotheses are rows grouped by clip: clip_of int32 [n] is non-decreasing,
  * clip c owns rows row_lo[c] .. row_lo[c + 1] - 1 (row_lo int32 [C + 1]; an empty range: the clip has finished).

@@ -5,6 +5,7 @@ out) at B = 96 and B = 32, T = 29, 96 x 96.
     python scripts/dctcn_bench.py [--batches 96,32] [--rounds 7] [--iters 50] [--out profiles/dctcn_eval.json]
     rocprofv3 --kernel-trace --stats -d <dir> -- python scripts/dctcn_bench.py --profile-only        # kernel table, in a run of its own
     python scripts/dctcn_bench.py --backward [--profile-only]      # forward + backward of the back-end and heads against eager bf16 autograd
+    python scripts/dctcn_bench.py --train [--batches 96]           # the same in the training arithmetic (batch statistics, dropout) -> profiles/dctcn_train.json
 
 Times are wall-clock between device synchronisations (host dispatch included), the two implementations ALTERNATING round by round after
 warm-up of every shape; per implementation the median over rounds of the mean of `--iters` calls, and the minimum.  The convolution
@@ -36,9 +37,12 @@ class EagerDCTCN:
     def __init__(self, sd: dict, dims: dict, dev):
         self.W = {k: (v.to(dev).to(torch.bfloat16) if v.is_floating_point() else v.to(dev)) for k, v in sd.items()}
         self.dims = dims
+        self.train, self.p_drop = False, 0.0          # --train: batch-statistic BatchNorm1d in the back-end, dropout0 / dropout1
 
     def bn(self, x, p):
         W = self.W
+        if self.train and p.startswith(TCN):
+            return F.batch_norm(x, W[f"{p}.running_mean"], W[f"{p}.running_var"], W[f"{p}.weight"], W[f"{p}.bias"], True, 0.1, 1e-5)
         return F.batch_norm(x, W[f"{p}.running_mean"], W[f"{p}.running_var"], W[f"{p}.weight"], W[f"{p}.bias"], False, 0.0, 1e-5)
 
     def frontend(self, videos):
@@ -79,14 +83,14 @@ class EagerDCTCN:
                     c = F.conv1d(xc * y.unsqueeze(2), W[f"{p}.cbcr0_{ki}.net.0.weight"], W[f"{p}.cbcr0_{ki}.net.0.bias"], padding=(k - 1) * d, dilation=d)
                     c = self.bn(c, f"{p}.cbcr0_{ki}.net.1")
                     outs.append(F.silu(c[:, :, (k - 1) * d // 2: c.size(2) - (k - 1) * d // 2].contiguous()))
-                o0 = torch.cat(outs, 1)
+                o0 = F.dropout(torch.cat(outs, 1), self.p_drop, self.train)
                 outs = []
                 for ki, k in enumerate(ks):
                     c = F.conv1d(o0, W[f"{p}.cbcr1_{ki}.net.0.weight"], W[f"{p}.cbcr1_{ki}.net.0.bias"], padding=(k - 1) * d, dilation=d)
                     c = self.bn(c, f"{p}.cbcr1_{ki}.net.1")
                     outs.append(F.silu(c[:, :, (k - 1) * d // 2: c.size(2) - (k - 1) * d // 2].contiguous()))
                 res = F.conv1d(xc, W[f"{p}.downsample.weight"], W[f"{p}.downsample.bias"])
-                feats_list.append(F.silu(torch.cat(outs, 1) + res))
+                feats_list.append(F.silu(F.dropout(torch.cat(outs, 1), self.p_drop, self.train) + res))
             x = torch.cat(feats_list, 1)
             if bi != len(dm["blocks"]) - 1:
                 p = f"{TCN}.transition{bi + 1}"
@@ -142,6 +146,8 @@ def backward_leg(a) -> None:
     model.load_state_dict(sd)
     model.to(dev).eval()
     eager = EagerDCTCN(sd, dctcn_dims(cfg), dev)
+    if a.train:
+        eager.train, eager.p_drop = True, float(cfg.model.dctcn.densetcn_options.dropout)
     lam, T, rows = model.lambda_audio, a.frames, []
     for B in [int(v) for v in a.batches.split(",")]:
         videos, tokens, labels, wm, am = [t.to(dev) for t in dctcn_synthetic_batch(cfg, B, T, seed=B)]
@@ -154,6 +160,10 @@ def backward_leg(a) -> None:
             "eager_backward": lambda: eager.loss_and_grads(feats16, wm, am, tokens, labels, lam),
             "hip_forward_only": lambda: model._losses((B, T), tokens, labels, wm, am, None, feats_hip),
         }
+        if a.train:          # the training arithmetic beside this project's own eval-statistics backward (hip_backward) and eager .train() autograd
+            fns["hip_train"] = lambda: model.loss_and_backend_grads_from_features(feats_hip, B, T, tokens, labels, wm, am, train_stats=True,
+                                                                                  dropout_seed=1)
+            del fns["hip_forward_only"]
         for fn in fns.values():
             _time(fn, 3)
         if a.profile_only:
@@ -166,24 +176,28 @@ def backward_leg(a) -> None:
             for k, fn in fns.items():
                 samples[k].append(_time(fn, a.iters))
         ops.start_event_timing()
-        fns["hip_backward"]()
+        fns["hip_train" if a.train else "hip_backward"]()
         torch.cuda.synchronize()
         ev = ops.stop_event_timing()
-        row = dict(B=B, T=T, cos_grad_audio_projection=round(cos, 5))
+        row = dict(B=B, T=T)
+        if not a.train:          # (with --train the two sides draw unrelated dropout masks: their gradients are not comparable)
+            row["cos_grad_audio_projection"] = round(cos, 5)
         for k, v in samples.items():
             row[f"{k}_ms_median"], row[f"{k}_ms_min"] = round(statistics.median(v), 4), round(min(v), 4)
-        row["eager_over_hip"] = round(row["eager_backward_ms_median"] / row["hip_backward_ms_median"], 3)
+        row["eager_over_hip"] = round(row["eager_backward_ms_median"] / row["hip_train_ms_median" if a.train else "hip_backward_ms_median"], 3)
+        if a.train:
+            row["train_over_eval_stats"] = round(row["hip_train_ms_median"] / row["hip_backward_ms_median"], 3)
         row["event_ms_by_label"] = {k: (v.get("launches"), round(v.get("ms", 0.0), 3)) for k, v in sorted(ev.items()) if v.get("ms")}
         rows.append(row)
         print(json.dumps(row), flush=True)
     if a.profile_only:
         return
-    path = os.path.join(ROOT, "profiles", "dctcn_backward.json") if a.out.endswith("dctcn_eval.json") else a.out
+    path = os.path.join(ROOT, "profiles", "dctcn_train.json" if a.train else "dctcn_backward.json") if a.out.endswith("dctcn_eval.json") else a.out
     doc = {}
     if os.path.exists(path):
         with open(path) as f:
             doc = json.load(f)
-    doc["timing"] = dict(what="DC-TCN back-end + heads, forward and backward: features in, all gradients out; HIP vs torch eager bf16 autograd of the "
+    doc["timing"] = dict(mode="train_stats=True, dropout on; eager in .train()" if a.train else "eval statistics", what="DC-TCN back-end + heads, forward and backward: features in, all gradients out; HIP vs torch eager bf16 autograd of the "
                               "same modules, same process, alternating rounds (event_ms_by_label: device events around host calls, not kernel times)",
                          device=torch.cuda.get_device_name(0), rounds=a.rounds, iters=a.iters, rows=rows)
     with open(path, "w") as f:
@@ -202,7 +216,11 @@ def main() -> None:
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dctcn_eval.json"))
     ap.add_argument("--backward", action="store_true", help="the backward leg instead: features in, all back-end gradients out, HIP "
                     "(loss_and_backend_grads_from_features) against bf16 autograd of the eager modules -> profiles/dctcn_backward.json")
+    ap.add_argument("--train", action="store_true", help="with --backward semantics, the training arithmetic: loss_and_backend_grads_from_features("
+                    "train_stats=True, dropout_seed=...) beside eager bf16 autograd in .train() and the eval-statistics backward -> profiles/dctcn_train.json")
     a = ap.parse_args()
+    if a.train:
+        return backward_leg(a)
     if a.backward:
         return backward_leg(a)
     from syncvsr_amd import ops

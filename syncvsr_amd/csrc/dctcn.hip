@@ -17,6 +17,9 @@
 #define TC_MAXK 7
 #define TC_SLAB_BYTES (TC_SLOTS * TC_ROWS * TC_BK * 2)
 #define TC_ACT_PRELU 3
+#define TC_PLAIN 0           // k_tconv<MODE>: the eval forward; TC_SAVE: that and the fp32 accumulators; TC_EXT: the accumulators of the
+#define TC_SAVE 1            // extended axis alone (batch-statistic stages)
+#define TC_EXT 2
 
 struct TBranch {
     const bf16_t* w;          // [co][k][n_in]
@@ -36,6 +39,7 @@ struct TArgs {
     float* save;              // k_tconv<true>: the fp32 accumulators, [B*T][save_pitch], branch i at channels [i * co, (i + 1) * co)
     long save_pitch;
     int co;
+    int T_src, shift;         // tc_stage_rows' source axis: T and 0, or (k_tconv<TC_EXT>) the clip's own T under the extended axis a.T, and hmax
 };
 
 // 16-byte piece s (0..7) of 128-byte LDS row `row`: XOR swizzle on the row PAIR, so the 16 rows of a ds_read_b128 lane group (consecutive
@@ -48,8 +52,12 @@ __device__ __forceinline__ int tc_off(int row, int s) { return row * 128 + ((s ^
 // Slab of one 64-channel chunk: the rows [t0 - halo, t0 + 32 + halo) of the TC_SLOTS slots from global slot gs0 on, channels
 // [c, c + 64) of src (row pitch `pitch`), zeros outside the clip, outside the halo and for slots >= slots; with a gate (fp32 rows of
 // gate_pitch, one per clip) the rows are bf16(x * gate[b]).  All TC_SLOTS * TC_ROWS LDS rows are written.
+// The tiles count time on the launch's own axis (n_tt tiles a clip); the source holds T_src rows a clip and its row of tile time t is
+// t_src = t - shift, zeros outside [0, T_src).  shift 0 with T_src = the launch's T is the plain case; the batch-statistic stages run the
+// forward and the weight gradient on the extended axis of T + 2 * hmax rows over T-row inputs (shift = hmax) and the data gradient on the
+// T-row axis over extended gradient rows (shift = -hmax).
 __device__ __forceinline__ void tc_stage_rows(unsigned char* slab, const bf16_t* src, long pitch, int c, const float* gate, int gate_pitch, int halo,
-                                              int T, int n_tt, int slots, long gs0, int tid) {
+                                              int T_src, int shift, int n_tt, int slots, long gs0, int tid) {
 #pragma unroll
     for (int i = 0; i < TC_SLOTS * TC_ROWS * 8 / 256; ++i) {
         const int p = tid + i * 256;
@@ -58,9 +66,9 @@ __device__ __forceinline__ void tc_stage_rows(unsigned char* slab, const bf16_t*
         u32x4 v = {0u, 0u, 0u, 0u};
         if (gs < slots && row >= TC_HALO - halo && row < TC_HALO + TC_TILE + halo) {
             const int b = (int)(gs / n_tt);
-            const int t = (int)(gs - (long)b * n_tt) * TC_TILE - TC_HALO + row;
-            if (t >= 0 && t < T) {
-                v = *reinterpret_cast<const u32x4*>(src + ((long)b * T + t) * pitch + c + s * 8);
+            const int t = (int)(gs - (long)b * n_tt) * TC_TILE - TC_HALO + row - shift;
+            if (t >= 0 && t < T_src) {
+                v = *reinterpret_cast<const u32x4*>(src + ((long)b * T_src + t) * pitch + c + s * 8);
                 if (gate != nullptr) {
                     const float4* gp = reinterpret_cast<const float4*>(gate + (long)b * gate_pitch + c + s * 8);
                     const float4 g0 = gp[0], g1 = gp[1];
@@ -122,7 +130,7 @@ static hipError_t tc_dynamic_lds(const void* fn, int kmax, size_t* lds) {
 // are staged ONCE and serve all k taps (a tap is a row offset into the slab); the chunk of the weights [64 co][k][64 ci] beside it.
 // SAVE: the accumulator of every written element is stored too (svsr_tconv_fwd_save: the backward recomputes z = scale * acc + shift from it
 // with the same fma); the bf16 outputs are the same bits either way.
-template <bool SAVE>
+template <int MODE>
 __global__ __launch_bounds__(256) void k_tconv(TArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     unsigned char* slab = smem_raw;
@@ -131,6 +139,17 @@ __global__ __launch_bounds__(256) void k_tconv(TArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int k = br.k, halo = (k - 1) * a.d / 2;
     const int co0 = blockIdx.y * TC_BN;
+    // TC_EXT: the branch's own rows of the extended axis are [lo, hi); a workgroup whose slots all lie outside them has nothing to store
+    const int lo = a.shift - halo, hi = a.shift + a.T_src + halo;
+    if (MODE == TC_EXT) {
+        bool any = false;
+        for (int s = 0; s < TC_SLOTS; ++s) {
+            const long gs = (long)blockIdx.x * TC_SLOTS + s;
+            const int t0 = (int)(gs % a.n_tt) * TC_TILE;
+            any = any || (gs < a.slots && t0 < hi && t0 + TC_TILE > lo);
+        }
+        if (!any) return;                                  // (uniform over the workgroup, before the first barrier)
+    }
     f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
@@ -138,7 +157,7 @@ __global__ __launch_bounds__(256) void k_tconv(TArgs a) {
     const int my_slot = wave >> 1, nh = wave & 1, r = lane & 31, h = lane >> 5;
     for (int c0 = 0; c0 < a.n_in; c0 += TC_BK) {
         __syncthreads();                                   // the previous chunk's fragments are read
-        tc_stage_rows(slab, a.x, a.x_pitch, c0, br.gate, a.n_in, halo, a.T, a.n_tt, a.slots, (long)blockIdx.x * TC_SLOTS, tid);
+        tc_stage_rows(slab, a.x, a.x_pitch, c0, br.gate, a.n_in, halo, a.T_src, a.shift, a.n_tt, a.slots, (long)blockIdx.x * TC_SLOTS, tid);
         tc_stage_weights(wts, br.w, co0, k, a.n_in, c0, tid);
         __syncthreads();
         tc_taps(acc, slab, wts, k, a.d, my_slot, nh, r, h);
@@ -149,6 +168,14 @@ __global__ __launch_bounds__(256) void k_tconv(TArgs a) {
     const int b = (int)(gs / a.n_tt);
     const int t0 = (int)(gs - (long)b * a.n_tt) * TC_TILE;
     const int co = co0 + nh * 32 + r;
+    if (MODE == TC_EXT) {                                  // accumulators only: the statistics come first (svsr_tcn_colstats, svsr_tconv_apply)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int t = t0 + (i & 3) + 8 * (i >> 2) + 4 * h;
+            if (t >= lo && t < hi) a.save[((long)b * a.T + t) * a.save_pitch + (long)blockIdx.z * a.co + co] = acc[i];
+        }
+        return;
+    }
     const float sc = br.scale[co], sh = br.shift[co];
     const float slope = (a.act == TC_ACT_PRELU) ? br.slope[co] : 0.f;
 #pragma unroll
@@ -157,7 +184,7 @@ __global__ __launch_bounds__(256) void k_tconv(TArgs a) {
         if (t < a.T) {
             const long row = (long)b * a.T + t;
             float v = __builtin_fmaf(acc[i], sc, sh);
-            if (SAVE) a.save[row * a.save_pitch + (long)blockIdx.z * a.co + co] = acc[i];
+            if (MODE == TC_SAVE) a.save[row * a.save_pitch + (long)blockIdx.z * a.co + co] = acc[i];
             if (a.act == SVSR_ACT_SWISH) v = swish(v);
             else if (a.act == TC_ACT_PRELU) v = v >= 0.f ? v : v * slope;
             else if (a.act == SVSR_ACT_RELU) v = fmaxf(v, 0.f);
@@ -206,13 +233,13 @@ static int tconv_launch(const void* x, int64_t x_pitch, int B, int T, int n_in, 
     a.x = (const bf16_t*)x; a.out = (bf16_t*)out; a.res = (const bf16_t*)res;
     a.x_pitch = x_pitch; a.out_pitch = out_pitch; a.res_pitch = res_pitch;
     a.B = B; a.T = T; a.n_in = n_in; a.d = d; a.act = act; a.res_act = res_act;
-    a.save = save; a.save_pitch = save_pitch; a.co = co;
+    a.save = save; a.save_pitch = save_pitch; a.co = co; a.T_src = T; a.shift = 0;
     const dim3 grid((unsigned)((a.slots + TC_SLOTS - 1) / TC_SLOTS), (unsigned)(co / TC_BN), (unsigned)nb);
     size_t lds;
-    const hipError_t ae = tc_dynamic_lds(saving ? reinterpret_cast<const void*>(k_tconv<true>) : reinterpret_cast<const void*>(k_tconv<false>), kmax, &lds);
+    const hipError_t ae = tc_dynamic_lds(saving ? reinterpret_cast<const void*>(k_tconv<TC_SAVE>) : reinterpret_cast<const void*>(k_tconv<TC_PLAIN>), kmax, &lds);
     if (ae != hipSuccess) return (int)ae;
-    if (saving) hipLaunchKernelGGL(k_tconv<true>, grid, dim3(256), lds, stream, a);
-    else hipLaunchKernelGGL(k_tconv<false>, grid, dim3(256), lds, stream, a);
+    if (saving) hipLaunchKernelGGL(k_tconv<TC_SAVE>, grid, dim3(256), lds, stream, a);
+    else hipLaunchKernelGGL(k_tconv<TC_PLAIN>, grid, dim3(256), lds, stream, a);
     return svsr_check_launch();
 }
 
@@ -481,6 +508,7 @@ struct DArgs {
     long dy_pitch, x_pitch, add_pitch, out_pitch;
     float cadd_scale;
     int B, T, co, n_out, d, nb, n_tt, slots;
+    int T_src, shift;         // the gradient rows' axis: T and 0, or (svsr_tconv_dgrad_ext) T + 2 * hmax and -hmax
 };
 
 __global__ __launch_bounds__(256) void k_tconv_dgrad(DArgs a) {
@@ -507,7 +535,7 @@ __global__ __launch_bounds__(256) void k_tconv_dgrad(DArgs a) {
         for (int i = 0; i < 16; ++i) acc[i] = 0.f;
         for (int c0 = 0; c0 < a.co; c0 += TC_BK) {
             __syncthreads();
-            tc_stage_rows(slab, a.dy, a.dy_pitch, br.dy_off + c0, nullptr, 0, halo, a.T, a.n_tt, a.slots, (long)blockIdx.x * TC_SLOTS, tid);
+            tc_stage_rows(slab, a.dy, a.dy_pitch, br.dy_off + c0, nullptr, 0, halo, a.T_src, a.shift, a.n_tt, a.slots, (long)blockIdx.x * TC_SLOTS, tid);
             tc_stage_weights(wts, br.wt, n0, k, a.co, c0, tid);
             __syncthreads();
             tc_taps(acc, slab, wts, k, a.d, my_slot, nh, r, h);
@@ -543,10 +571,12 @@ __global__ __launch_bounds__(256) void k_tconv_dgrad(DArgs a) {
 }
 
 // branches: HOST table of nb x 4 64-bit words {k, wt, gate, dy_off}
-extern "C" int svsr_tconv_dgrad(const void* dy, int64_t dy_pitch, int B, int T, int co, int d, int nb, const int64_t* branches, int n_out,
-                                const void* x, int64_t x_pitch, const void* addend, int64_t add_pitch, const float* cadd, float cadd_scale,
-                                void* out, int64_t out_pitch, float* gpart, hipStream_t stream) {
+// hmax: dy holds T + 2 * hmax rows a clip, the row of time t at t + hmax (0: the plain T-row gradient)
+static int tconv_dgrad_launch(const void* dy, int64_t dy_pitch, int B, int T, int co, int d, int nb, const int64_t* branches, int n_out,
+                              const void* x, int64_t x_pitch, const void* addend, int64_t add_pitch, const float* cadd, float cadd_scale,
+                              void* out, int64_t out_pitch, float* gpart, int hmax, hipStream_t stream) {
     if (dy == nullptr || out == nullptr || branches == nullptr) return SVSR_ERR_ARG;
+    if (hmax < 0 || hmax > TC_HALO) return SVSR_ERR_ARG;
     if (B < 1 || T < 1 || d < 1 || co < 64 || co % 64 != 0 || dy_pitch % 8 != 0 || ((uintptr_t)dy & 15) != 0) return SVSR_ERR_ARG;
     if (nb < 1 || nb > 3 || n_out < TC_BN || n_out % TC_BN != 0 || out_pitch < n_out) return SVSR_ERR_ARG;
     if (addend != nullptr && add_pitch < n_out) return SVSR_ERR_ARG;
@@ -561,6 +591,7 @@ extern "C" int svsr_tconv_dgrad(const void* dy, int64_t dy_pitch, int B, int T, 
         br.gate = (const float*)(uintptr_t)e[2];
         br.dy_off = (int)e[3];
         if (!tc_taps_ok(e[0], d)) return SVSR_ERR_ARG;
+        if (hmax > 0 && (e[0] - 1) * (int64_t)d / 2 > hmax) return SVSR_ERR_ARG;          // (the branch reads rows [t - h, t + h] of the extended axis)
         if (br.wt == nullptr || ((uintptr_t)br.wt & 15) != 0) return SVSR_ERR_ARG;
         if (e[3] < 0 || e[3] % 8 != 0 || e[3] + co > dy_pitch) return SVSR_ERR_ARG;
         if (br.gate != nullptr) gated = true;
@@ -570,12 +601,27 @@ extern "C" int svsr_tconv_dgrad(const void* dy, int64_t dy_pitch, int B, int T, 
     if (!tc_geometry(B, T, &a.n_tt, &a.slots) || n_out / TC_BN > 65535) return SVSR_ERR_ARG;
     a.dy = (const bf16_t*)dy; a.x = (const bf16_t*)x; a.addend = (const bf16_t*)addend; a.cadd = cadd; a.out = (bf16_t*)out; a.gpart = gpart;
     a.dy_pitch = dy_pitch; a.x_pitch = x_pitch; a.add_pitch = add_pitch; a.out_pitch = out_pitch; a.cadd_scale = cadd_scale;
-    a.B = B; a.T = T; a.co = co; a.n_out = n_out; a.d = d; a.nb = nb;
+    a.B = B; a.T = T; a.co = co; a.n_out = n_out; a.d = d; a.nb = nb; a.T_src = T + 2 * hmax; a.shift = -hmax;
     size_t lds;
     const hipError_t ae = tc_dynamic_lds(reinterpret_cast<const void*>(k_tconv_dgrad), kmax, &lds);
     if (ae != hipSuccess) return (int)ae;
     hipLaunchKernelGGL(k_tconv_dgrad, dim3((unsigned)((a.slots + TC_SLOTS - 1) / TC_SLOTS), (unsigned)(n_out / TC_BN)), dim3(256), lds, stream, a);
     return svsr_check_launch();
+}
+
+extern "C" int svsr_tconv_dgrad(const void* dy, int64_t dy_pitch, int B, int T, int co, int d, int nb, const int64_t* branches, int n_out,
+                                const void* x, int64_t x_pitch, const void* addend, int64_t add_pitch, const float* cadd, float cadd_scale,
+                                void* out, int64_t out_pitch, float* gpart, hipStream_t stream) {
+    return tconv_dgrad_launch(dy, dy_pitch, B, T, co, d, nb, branches, n_out, x, x_pitch, addend, add_pitch, cadd, cadd_scale, out, out_pitch, gpart, 0,
+                              stream);
+}
+
+// svsr_tconv_dgrad over the gradient of the extended accumulators (svsr_tconv_bn_bwd): dy bf16 [B * (T + 2 * hmax)][dy_pitch]
+extern "C" int svsr_tconv_dgrad_ext(const void* dy, int64_t dy_pitch, int B, int T, int co, int d, int nb, const int64_t* branches, int n_out,
+                                    const void* x, int64_t x_pitch, const void* addend, int64_t add_pitch, const float* cadd, float cadd_scale,
+                                    void* out, int64_t out_pitch, float* gpart, int hmax, hipStream_t stream) {
+    return tconv_dgrad_launch(dy, dy_pitch, B, T, co, d, nb, branches, n_out, x, x_pitch, addend, add_pitch, cadd, cadd_scale, out, out_pitch, gpart,
+                              hmax, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -590,6 +636,7 @@ struct WArgs {
     const bf16_t* x; const bf16_t* dy; const float* gate; float* part;
     long x_pitch, dy_pitch;
     int B, T, n_in, co, d, n_tt, slots, S;
+    int T_x, shift;           // x's own rows a clip under the launch's axis T: T and 0, or (svsr_tconv_wgrad_ext) T - 2 * hmax and hmax
 };
 
 __device__ __forceinline__ bf16x8 tc_gather8(const unsigned char* base, int row0, int ch) {
@@ -621,7 +668,7 @@ __global__ __launch_bounds__(256) void k_tconv_wgrad(WArgs a) {
     const int npairs = (a.slots + TC_SLOTS - 1) / TC_SLOTS;
     for (int pr = blockIdx.x; pr < npairs; pr += a.S) {
         __syncthreads();
-        tc_stage_rows(slab, a.x, a.x_pitch, ci0, a.gate, a.n_in, halo, a.T, a.n_tt, a.slots, (long)pr * TC_SLOTS, tid);
+        tc_stage_rows(slab, a.x, a.x_pitch, ci0, a.gate, a.n_in, halo, a.T_x, a.shift, a.n_tt, a.slots, (long)pr * TC_SLOTS, tid);
 #pragma unroll
         for (int i = 0; i < TC_SLOTS * TC_TILE * 8 / 256; ++i) {
             const int p = tid + i * 256;
@@ -675,19 +722,21 @@ __global__ __launch_bounds__(256) void k_tconv_wgrad_fold(const float* __restric
     dw[i] = add ? dw[i] + s : s;
 }
 
-extern "C" int svsr_tconv_wgrad(const void* x, int64_t x_pitch, const float* gate, const void* dy, int64_t dy_pitch, int B, int T, int n_in, int co,
-                                int k, int d, int splits, float* part, float* dw, int n_valid, int add, hipStream_t stream) {
+// hmax: dy holds T + 2 * hmax rows a clip (the gradient of the extended accumulators) and the sum runs over all of them; x keeps T rows
+static int tconv_wgrad_launch(const void* x, int64_t x_pitch, const float* gate, const void* dy, int64_t dy_pitch, int B, int T, int n_in, int co,
+                              int k, int d, int splits, float* part, float* dw, int n_valid, int add, int hmax, hipStream_t stream) {
     if (x == nullptr || dy == nullptr || part == nullptr || dw == nullptr) return SVSR_ERR_ARG;
+    if (hmax < 0 || hmax > TC_HALO || (hmax > 0 && (k - 1) * (int64_t)d / 2 > hmax)) return SVSR_ERR_ARG;
     if (B < 1 || T < 1 || d < 1 || n_in < 64 || n_in % 64 != 0 || x_pitch < n_in || x_pitch % 8 != 0 || ((uintptr_t)x & 15) != 0) return SVSR_ERR_ARG;
     if (co < 64 || co % 64 != 0 || dy_pitch < co || dy_pitch % 8 != 0 || ((uintptr_t)dy & 15) != 0) return SVSR_ERR_ARG;
     if (!tc_taps_ok(k, d)) return SVSR_ERR_ARG;
     if (gate != nullptr && ((uintptr_t)gate & 15) != 0) return SVSR_ERR_ARG;
     if (n_valid < 1 || n_valid > n_in) return SVSR_ERR_ARG;
     WArgs a;
-    if (!tc_geometry(B, T, &a.n_tt, &a.slots)) return SVSR_ERR_ARG;
+    if (!tc_geometry(B, T + 2 * hmax, &a.n_tt, &a.slots)) return SVSR_ERR_ARG;
     if (splits < 1 || splits > (a.slots + TC_SLOTS - 1) / TC_SLOTS || splits > 65535 || n_in / 64 > 65535 || co / 64 > 65535) return SVSR_ERR_ARG;
     a.x = (const bf16_t*)x; a.dy = (const bf16_t*)dy; a.gate = gate; a.part = part; a.x_pitch = x_pitch; a.dy_pitch = dy_pitch;
-    a.B = B; a.T = T; a.n_in = n_in; a.co = co; a.d = d; a.S = splits;
+    a.B = B; a.T = T + 2 * hmax; a.n_in = n_in; a.co = co; a.d = d; a.S = splits; a.T_x = T; a.shift = hmax;
     const dim3 grid((unsigned)splits, (unsigned)(n_in / 64), (unsigned)(co / 64));
     if (k == 1) hipLaunchKernelGGL(k_tconv_wgrad<1>, grid, dim3(256), 0, stream, a);
     else if (k == 3) hipLaunchKernelGGL(k_tconv_wgrad<3>, grid, dim3(256), 0, stream, a);
@@ -698,6 +747,17 @@ extern "C" int svsr_tconv_wgrad(const void* x, int64_t x_pitch, const float* gat
     const long n = (long)co * n_valid * k;
     hipLaunchKernelGGL(k_tconv_wgrad_fold, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const float*)part, splits, co, k, n_in, n_valid, dw, add);
     return svsr_check_launch();
+}
+
+extern "C" int svsr_tconv_wgrad(const void* x, int64_t x_pitch, const float* gate, const void* dy, int64_t dy_pitch, int B, int T, int n_in, int co,
+                                int k, int d, int splits, float* part, float* dw, int n_valid, int add, hipStream_t stream) {
+    return tconv_wgrad_launch(x, x_pitch, gate, dy, dy_pitch, B, T, n_in, co, k, d, splits, part, dw, n_valid, add, 0, stream);
+}
+
+// svsr_tconv_wgrad over dy bf16 [B * (T + 2 * hmax)][dy_pitch]; splits <= the slot pairs of the extended axis
+extern "C" int svsr_tconv_wgrad_ext(const void* x, int64_t x_pitch, const float* gate, const void* dy, int64_t dy_pitch, int B, int T, int n_in, int co,
+                                    int k, int d, int splits, float* part, float* dw, int n_valid, int add, int hmax, hipStream_t stream) {
+    return tconv_wgrad_launch(x, x_pitch, gate, dy, dy_pitch, B, T, n_in, co, k, d, splits, part, dw, n_valid, add, hmax, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -919,4 +979,368 @@ extern "C" int svsr_tcn_norm_pool_bwd(const void* dh, const void* dpooled, const
     int rc = svsr_check_launch();
     if (rc != SVSR_OK) return rc;
     return svsr_tcn_fold(part, B, 2L * C, sums, 0, stream);
+}
+
+// =====================================================================================================================
+// Batch-statistic stages (loss_and_backend_grads(train_stats=True)).  The reference's TemporalConvLayer is Conv1d(padding = (k - 1) d) ->
+// BatchNorm1d -> symmetric chomp -> activation: in training mode the statistics of a branch are taken over T + (k - 1) d positions a clip,
+// of which (k - 1) d are chomped off afterwards.  So a stage is convolution -> statistics -> apply, on the EXTENDED axis: with
+// h_i = (k_i - 1) d / 2 and hmax >= every h_i of the launch, a clip owns T_ext = T + 2 * hmax rows, the row of time t is t + hmax, and branch
+// i's positions are the rows [hmax - h_i, hmax + h_i + T).  Rows of a branch's channels outside its own extent are never written by the
+// forward and never read by anything; their gradient rows are written as zeros, so the data and weight gradients need no extent of their own.
+// A 64-channel block never straddles two branches (co is a multiple of 64): the extent is uniform per workgroup.
+// =====================================================================================================================
+struct XGeo { int T, T_ext, hmax, co, h[3]; };
+
+static bool xgeo_make(XGeo* g, int T, int hmax, int co, int nb, const int* h) {
+    if (T < 1 || hmax < 0 || hmax > TC_HALO || co < 64 || co % 64 != 0 || nb < 1 || nb > 3) return false;
+    g->T = T; g->T_ext = T + 2 * hmax; g->hmax = hmax; g->co = co;
+    for (int i = 0; i < 3; ++i) {
+        g->h[i] = h[i < nb ? i : 0];
+        if (g->h[i] < 0 || g->h[i] > hmax) return false;
+    }
+    return true;
+}
+
+// svsr_tconv_fwd's convolution on the extended axis: the fp32 accumulators alone, acc[(b * T_ext + u)][i * co + c] for branch i and its own
+// rows u.  branches: svsr_tconv_fwd's table; k, w and gate are read.
+extern "C" int svsr_tconv_fwd_ext(const void* x, int64_t x_pitch, int B, int T, int n_in, int d, int nb, const int64_t* branches, int co, int hmax,
+                                  float* acc, int64_t acc_pitch, hipStream_t stream) {
+    if (x == nullptr || acc == nullptr || branches == nullptr) return SVSR_ERR_ARG;
+    if (B < 1 || T < 1 || d < 1 || n_in < 64 || n_in % 64 != 0 || x_pitch < n_in || x_pitch % 8 != 0 || ((uintptr_t)x & 15) != 0) return SVSR_ERR_ARG;
+    if (nb < 1 || nb > 3 || co < TC_BN || co % TC_BN != 0 || acc_pitch < (int64_t)nb * co || hmax < 0 || hmax > TC_HALO) return SVSR_ERR_ARG;
+    TArgs a;
+    int kmax = 1;
+    for (int i = 0; i < 3; ++i) {
+        const int64_t* e = branches + 8 * (i < nb ? i : 0);
+        TBranch& br = a.br[i];
+        br.k = (int)e[0];
+        br.w = (const bf16_t*)(uintptr_t)e[1];
+        br.gate = (const float*)(uintptr_t)e[2];
+        br.scale = nullptr; br.shift = nullptr; br.slope = nullptr; br.out_off = 0; br.res_off = 0;
+        if (!tc_taps_ok(e[0], d) || (e[0] - 1) * (int64_t)d / 2 > hmax) return SVSR_ERR_ARG;
+        if (br.w == nullptr || ((uintptr_t)br.w & 15) != 0) return SVSR_ERR_ARG;
+        if (br.gate != nullptr && ((uintptr_t)br.gate & 15) != 0) return SVSR_ERR_ARG;
+        if (br.k > kmax) kmax = br.k;
+    }
+    if (!tc_geometry(B, T + 2 * hmax, &a.n_tt, &a.slots) || co / TC_BN > 65535) return SVSR_ERR_ARG;
+    a.x = (const bf16_t*)x; a.out = nullptr; a.res = nullptr;
+    a.x_pitch = x_pitch; a.out_pitch = 0; a.res_pitch = 0;
+    a.B = B; a.T = T + 2 * hmax; a.n_in = n_in; a.d = d; a.act = SVSR_ACT_NONE; a.res_act = SVSR_ACT_NONE;
+    a.save = acc; a.save_pitch = acc_pitch; a.co = co; a.T_src = T; a.shift = hmax;
+    const dim3 grid((unsigned)((a.slots + TC_SLOTS - 1) / TC_SLOTS), (unsigned)(co / TC_BN), (unsigned)nb);
+    size_t lds;
+    const hipError_t ae = tc_dynamic_lds(reinterpret_cast<const void*>(k_tconv<TC_EXT>), kmax, &lds);
+    if (ae != hipSuccess) return (int)ae;
+    hipLaunchKernelGGL(k_tconv<TC_EXT>, grid, dim3(256), lds, stream, a);
+    return svsr_check_launch();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Column statistics: per channel the mean and the CENTRED second moment sum (x - mean)^2 over the channel's own rows of every clip.
+// One workgroup per (clip, 64 channels): the clip's mean first (four row lanes, added in order), then the squares against it; the clips are
+// merged in ascending order with Chan's update (equal counts).  No atomics, no E[x^2] - mean^2.  TIn float: the extended accumulators;
+// bf16_t: a [B*T][C] activation stack (norm5; hmax = 0).
+// ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float cs_ld(const float* p) { return *p; }
+__device__ __forceinline__ float cs_ld(const bf16_t* p) { return bf2f(*p); }
+
+template <typename TIn>
+__global__ __launch_bounds__(256) void k_tcn_colstats(const TIn* __restrict__ x, long pitch, int C, XGeo g, float* __restrict__ part) {
+    __shared__ float red[4][64];
+    const int tid = threadIdx.x, cl = tid & 63, rl = tid >> 6;
+    const int b = blockIdx.x, c = blockIdx.y * 64 + cl;
+    const int h = g.h[(blockIdx.y * 64) / g.co];
+    const int n = g.T + 2 * h;
+    const TIn* base = x + ((long)b * g.T_ext + g.hmax - h) * pitch + c;
+    float s = 0.f;
+    for (int i = rl; i < n; i += 4) s += cs_ld(base + (long)i * pitch);
+    red[rl][cl] = s;
+    __syncthreads();
+    const float m = (((red[0][cl] + red[1][cl]) + red[2][cl]) + red[3][cl]) / (float)n;
+    float q = 0.f;
+    for (int i = rl; i < n; i += 4) {
+        const float dl = cs_ld(base + (long)i * pitch) - m;
+        q = __builtin_fmaf(dl, dl, q);
+    }
+    __syncthreads();                                       // every thread has read the sums
+    red[rl][cl] = q;
+    __syncthreads();
+    if (rl == 0) {
+        part[((long)b * 2) * C + c] = m;
+        part[((long)b * 2 + 1) * C + c] = ((red[0][cl] + red[1][cl]) + red[2][cl]) + red[3][cl];
+    }
+}
+
+__global__ __launch_bounds__(256) void k_tcn_colstats_merge(const float* __restrict__ part, int B, int C, XGeo g, float* __restrict__ stats) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    const float n = (float)(g.T + 2 * g.h[c / g.co]);
+    float mean = part[c], m2 = part[C + c];
+    for (int b = 1; b < B; ++b) {
+        const float na = n * (float)b, tot = na + n;
+        const float dl = part[((long)b * 2) * C + c] - mean;
+        mean = __builtin_fmaf(dl, n / tot, mean);
+        m2 = (m2 + part[((long)b * 2 + 1) * C + c]) + dl * dl * (na * n / tot);
+    }
+    stats[c] = mean;
+    stats[C + c] = m2;
+}
+
+// x: fp32 (is_bf16 0) or bf16 rows [B * (T + 2 * hmax)][pitch]; channels [i * co, (i + 1) * co) belong to branch i with half reach h[i];
+// part: fp32 scratch [B][2][C]; stats fp32 [2][C] = (mean, sum (x - mean)^2) over B * (T + 2 * h[i]) rows
+extern "C" int svsr_tcn_colstats(const void* x, int64_t pitch, int is_bf16, int B, int T, int C, int co, int hmax, int nb, const int* h, float* part,
+                                 float* stats, hipStream_t stream) {
+    XGeo g;
+    if (x == nullptr || h == nullptr || part == nullptr || stats == nullptr || B < 1 || B > 65535 * 32) return SVSR_ERR_ARG;
+    if (!xgeo_make(&g, T, hmax, co, nb, h) || C != nb * co || pitch < C || C / 64 > 65535) return SVSR_ERR_ARG;
+    const dim3 grid((unsigned)B, (unsigned)(C / 64));
+    if (is_bf16) hipLaunchKernelGGL(k_tcn_colstats<bf16_t>, grid, dim3(256), 0, stream, (const bf16_t*)x, (long)pitch, C, g, part);
+    else hipLaunchKernelGGL(k_tcn_colstats<float>, grid, dim3(256), 0, stream, (const float*)x, (long)pitch, C, g, part);
+    int rc = svsr_check_launch();
+    if (rc != SVSR_OK) return rc;
+    hipLaunchKernelGGL(k_tcn_colstats_merge, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream, (const float*)part, B, C, g, stats);
+    return svsr_check_launch();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The epilogue of a batch-statistic stage and its backward.  k_tconv's epilogue continued: z = fma(acc, scale, shift), y = act(z), then
+// dropout (element row * C + c of the stage's [B*T][C] output: y * m with m = 1 / (1 - p) where kept, 0 where dropped), then + res and
+// res_act.  Backward: du = dy * res_act'(u) (dy without a residual), dd = du * m, g = dd * act'(z).
+// ---------------------------------------------------------------------------------------------------------------------
+struct PArgs {
+    const float* acc; const float* scale; const float* shift; const float* slope; const bf16_t* res; const bf16_t* dy;
+    const float* mean; const float* invstd; const float* ca; const float* cb;
+    bf16_t* out; bf16_t* dres; bf16_t* dacc; float* part;
+    long acc_pitch, res_pitch, dy_pitch, out_pitch, dres_pitch, dacc_pitch, rows;
+    XGeo g;
+    int C, act, res_act, drop;
+    unsigned key, thresh;
+    float dscale;
+};
+
+__device__ __forceinline__ float pa_mult(const PArgs& a, long row, int c) {
+    if (!a.drop) return 1.f;
+    return drop_keep(a.key, a.thresh, (unsigned)(row * a.C + c)) ? a.dscale : 0.f;
+}
+
+__device__ __forceinline__ float pa_act(int act, float z, float slope) {
+    if (act == SVSR_ACT_SWISH) return swish(z);
+    if (act == TC_ACT_PRELU) return z >= 0.f ? z : z * slope;
+    if (act == SVSR_ACT_RELU) return fmaxf(z, 0.f);
+    return z;
+}
+
+// -> g; du (the residual branch's gradient) and z by reference
+__device__ __forceinline__ float pa_grad(const PArgs& a, long row, int c, float ac, float sc, float sh, float slope, float& du, float& z, float& dd) {
+    z = __builtin_fmaf(ac, sc, sh);
+    du = bf2f(a.dy[row * a.dy_pitch + c]);
+    const float m = pa_mult(a, row, c);
+    if (a.res != nullptr) {
+        float y = pa_act(a.act, z, slope);
+        if (a.drop) y *= m;
+        const float u = y + bf2f(a.res[row * a.res_pitch + c]);
+        if (a.res_act == SVSR_ACT_SWISH) du *= swish_grad(u);
+    }
+    dd = a.drop ? du * m : du;
+    float g = dd;
+    if (a.act == SVSR_ACT_SWISH) g = dd * swish_grad(z);
+    else if (a.act == TC_ACT_PRELU) g = z >= 0.f ? dd : dd * slope;
+    else if (a.act == SVSR_ACT_RELU) g = z > 0.f ? dd : 0.f;
+    return g;
+}
+
+__global__ __launch_bounds__(256) void k_tconv_apply(PArgs a) {
+    const int tid = threadIdx.x, cl = tid & 63, rl = tid >> 6;
+    const int c = blockIdx.y * 64 + cl;
+    const float sc = a.scale[c], sh = a.shift[c];
+    const float slope = a.act == TC_ACT_PRELU ? a.slope[c] : 0.f;
+    const long r0 = (long)blockIdx.x * EB_ROWS;
+    for (int i = rl; i < EB_ROWS; i += 4) {
+        const long row = r0 + i;
+        if (row >= a.rows) break;
+        const long b = row / a.g.T;
+        const long er = b * a.g.T_ext + a.g.hmax + (row - b * a.g.T);
+        float v = pa_act(a.act, __builtin_fmaf(a.acc[er * a.acc_pitch + c], sc, sh), slope);
+        if (a.drop) v *= pa_mult(a, row, c);
+        if (a.res != nullptr) {
+            v += bf2f(a.res[row * a.res_pitch + c]);
+            if (a.res_act == SVSR_ACT_SWISH) v = swish(v);
+        }
+        a.out[row * a.out_pitch + c] = f2bf(v);
+    }
+}
+
+// Pass 1 of the backward: per channel the sums of g, g * acc, dd * min(z, 0) (the PReLU slope) and du over the T interior rows, and dres = du
+__global__ __launch_bounds__(256) void k_tconv_epi_bwd_bs(PArgs a) {
+    __shared__ float red[4][4][64];
+    const int tid = threadIdx.x, cl = tid & 63, rl = tid >> 6;
+    const int c = blockIdx.y * 64 + cl;
+    const float sc = a.scale[c], sh = a.shift[c];
+    const float slope = a.act == TC_ACT_PRELU ? a.slope[c] : 0.f;
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    const long r0 = (long)blockIdx.x * EB_ROWS;
+    for (int i = rl; i < EB_ROWS; i += 4) {
+        const long row = r0 + i;
+        if (row >= a.rows) break;
+        const long b = row / a.g.T;
+        const long er = b * a.g.T_ext + a.g.hmax + (row - b * a.g.T);
+        const float ac = a.acc[er * a.acc_pitch + c];
+        float du, z, dd;
+        const float g = pa_grad(a, row, c, ac, sc, sh, slope, du, z, dd);
+        if (a.res != nullptr) {
+            a.dres[row * a.dres_pitch + c] = f2bf(du);
+            s3 += du;
+        }
+        if (a.act == TC_ACT_PRELU) s2 += dd * fminf(z, 0.f);
+        s0 += g;
+        s1 = __builtin_fmaf(g, ac, s1);
+    }
+    red[0][rl][cl] = s0; red[1][rl][cl] = s1; red[2][rl][cl] = s2; red[3][rl][cl] = s3;
+    __syncthreads();
+    const float t = ((red[rl][0][cl] + red[rl][1][cl]) + red[rl][2][cl]) + red[rl][3][cl];
+    a.part[((long)blockIdx.x * 4 + rl) * a.C + c] = t;
+}
+
+// Pass 2: the gradient of every extended accumulator, dacc = bf16(scale * (g - ca - xhat * cb)) on the branch's own rows (g recomputed on the
+// T interior rows, 0 on the chomped ones; xhat = (acc - mean) * invstd; ca = sum g / N, cb = sum g xhat / N from pass 1), zeros elsewhere.
+__global__ __launch_bounds__(256) void k_tconv_bn_bwd(PArgs a) {
+    const int tid = threadIdx.x, cl = tid & 63, rl = tid >> 6;
+    const int c = blockIdx.y * 64 + cl;
+    const int h = a.g.h[(blockIdx.y * 64) / a.g.co];
+    const float sc = a.scale[c], sh = a.shift[c], mean = a.mean[c], istd = a.invstd[c], ca = a.ca[c], cb = a.cb[c];
+    const float slope = a.act == TC_ACT_PRELU ? a.slope[c] : 0.f;
+    const long r0 = (long)blockIdx.x * EB_ROWS, erows = a.rows / a.g.T * a.g.T_ext;
+    for (int i = rl; i < EB_ROWS; i += 4) {
+        const long er = r0 + i;
+        if (er >= erows) break;
+        const long b = er / a.g.T_ext;
+        const int u = (int)(er - b * a.g.T_ext), t = u - a.g.hmax;
+        float v = 0.f;
+        if (t >= -h && t < a.g.T + h) {
+            const float ac = a.acc[er * a.acc_pitch + c];
+            float g = 0.f;
+            if (t >= 0 && t < a.g.T) {
+                float du, z, dd;
+                g = pa_grad(a, b * a.g.T + t, c, ac, sc, sh, slope, du, z, dd);
+            }
+            v = sc * ((g - ca) - (ac - mean) * istd * cb);
+        }
+        a.dacc[er * a.dacc_pitch + c] = f2bf(v);
+    }
+}
+
+static bool pa_fill(PArgs* a, const float* acc, int64_t acc_pitch, int B, int T, int C, int co, int hmax, int nb, const int* h, int act,
+                    const float* scale, const float* shift, const float* slope, const void* res, int64_t res_pitch, int res_act, unsigned drop_key,
+                    float drop_p) {
+    if (acc == nullptr || scale == nullptr || shift == nullptr || h == nullptr || B < 1 || (long)B * (T + 2L * TC_HALO) > (1L << 30)) return false;
+    if (!xgeo_make(&a->g, T, hmax, co, nb, h) || C != nb * co || C / 64 > 65535 || acc_pitch < C) return false;
+    if (act != SVSR_ACT_NONE && act != SVSR_ACT_RELU && act != SVSR_ACT_SWISH && act != TC_ACT_PRELU) return false;
+    if (act == TC_ACT_PRELU && slope == nullptr) return false;
+    if (res_act != SVSR_ACT_NONE && res_act != SVSR_ACT_SWISH) return false;
+    if (res != nullptr && res_pitch < C) return false;
+    if (!(drop_p >= 0.f && drop_p < 1.f)) return false;
+    if (drop_p > 0.f && (long)B * T * C > (1L << 32)) return false;          // the mask's element index row * C + c is a 32-bit counter
+    a->acc = acc; a->scale = scale; a->shift = shift; a->slope = slope; a->res = (const bf16_t*)res; a->dy = nullptr;
+    a->mean = nullptr; a->invstd = nullptr; a->ca = nullptr; a->cb = nullptr; a->out = nullptr; a->dres = nullptr; a->dacc = nullptr; a->part = nullptr;
+    a->acc_pitch = acc_pitch; a->res_pitch = res_pitch; a->dy_pitch = 0; a->out_pitch = 0; a->dres_pitch = 0; a->dacc_pitch = 0;
+    a->rows = (long)B * T; a->C = C; a->act = act; a->res_act = res_act;
+    a->drop = drop_p > 0.f; a->key = drop_key;
+    const double th = (double)drop_p * 4294967296.0;
+    a->thresh = th >= 4294967295.0 ? 4294967295u : (unsigned)th;
+    a->dscale = 1.0f / (1.0f - drop_p);
+    return true;
+}
+
+// acc fp32 [B * (T + 2 * hmax)][acc_pitch] (svsr_tconv_fwd_ext) -> out bf16 [B * T][out_pitch], channels [0, C) (C = nb * co).
+// drop_p > 0: dropout with the key drop_key (dropout.site_key), element index row * C + c.
+extern "C" int svsr_tconv_apply(const float* acc, int64_t acc_pitch, int B, int T, int C, int co, int hmax, int nb, const int* h, int act,
+                                const float* scale, const float* shift, const float* slope, const void* res, int64_t res_pitch, int res_act,
+                                unsigned drop_key, float drop_p, void* out, int64_t out_pitch, hipStream_t stream) {
+    PArgs a;
+    if (out == nullptr || out_pitch < C) return SVSR_ERR_ARG;
+    if (!pa_fill(&a, acc, acc_pitch, B, T, C, co, hmax, nb, h, act, scale, shift, slope, res, res_pitch, res_act, drop_key, drop_p)) return SVSR_ERR_ARG;
+    a.out = (bf16_t*)out; a.out_pitch = out_pitch;
+    hipLaunchKernelGGL(k_tconv_apply, dim3((unsigned)((a.rows + EB_ROWS - 1) / EB_ROWS), (unsigned)(C / 64)), dim3(256), 0, stream, a);
+    return svsr_check_launch();
+}
+
+// Pass 1.  part: fp32 scratch [ceil(B * T / 64)][4][C]; sums fp32 [4][C] as svsr_tconv_epi_bwd's; dres bf16 [B * T][dres_pitch] with a residual
+extern "C" int svsr_tconv_epi_bwd_bs(const void* dy, int64_t dy_pitch, const float* acc, int64_t acc_pitch, int B, int T, int C, int co, int hmax, int nb,
+                                     const int* h, int act, const float* scale, const float* shift, const float* slope, const void* res,
+                                     int64_t res_pitch, int res_act, unsigned drop_key, float drop_p, void* dres, int64_t dres_pitch, float* part,
+                                     float* sums, hipStream_t stream) {
+    PArgs a;
+    if (dy == nullptr || dy_pitch < C || part == nullptr || sums == nullptr) return SVSR_ERR_ARG;
+    if (res != nullptr && (dres == nullptr || dres_pitch < C)) return SVSR_ERR_ARG;
+    if (!pa_fill(&a, acc, acc_pitch, B, T, C, co, hmax, nb, h, act, scale, shift, slope, res, res_pitch, res_act, drop_key, drop_p)) return SVSR_ERR_ARG;
+    a.dy = (const bf16_t*)dy; a.dy_pitch = dy_pitch; a.dres = (bf16_t*)dres; a.dres_pitch = dres_pitch; a.part = part;
+    const long blocks = (a.rows + EB_ROWS - 1) / EB_ROWS;
+    hipLaunchKernelGGL(k_tconv_epi_bwd_bs, dim3((unsigned)blocks, (unsigned)(C / 64)), dim3(256), 0, stream, a);
+    int rc = svsr_check_launch();
+    if (rc != SVSR_OK) return rc;
+    return svsr_tcn_fold(part, (int)blocks, 4L * C, sums, 0, stream);
+}
+
+// Pass 2.  mean, invstd, ca, cb fp32 [C]; dacc bf16 [B * (T + 2 * hmax)][dacc_pitch]: every row of channels [0, C) is written
+extern "C" int svsr_tconv_bn_bwd(const void* dy, int64_t dy_pitch, const float* acc, int64_t acc_pitch, int B, int T, int C, int co, int hmax, int nb,
+                                 const int* h, int act, const float* scale, const float* shift, const float* slope, const void* res, int64_t res_pitch,
+                                 int res_act, unsigned drop_key, float drop_p, const float* mean, const float* invstd, const float* ca,
+                                 const float* cb, void* dacc, int64_t dacc_pitch, hipStream_t stream) {
+    PArgs a;
+    if (dy == nullptr || dy_pitch < C || mean == nullptr || invstd == nullptr || ca == nullptr || cb == nullptr || dacc == nullptr || dacc_pitch < C)
+        return SVSR_ERR_ARG;
+    if (!pa_fill(&a, acc, acc_pitch, B, T, C, co, hmax, nb, h, act, scale, shift, slope, res, res_pitch, res_act, drop_key, drop_p)) return SVSR_ERR_ARG;
+    a.dy = (const bf16_t*)dy; a.dy_pitch = dy_pitch; a.mean = mean; a.invstd = invstd; a.ca = ca; a.cb = cb;
+    a.dacc = (bf16_t*)dacc; a.dacc_pitch = dacc_pitch;
+    const long erows = (long)B * a.g.T_ext;
+    hipLaunchKernelGGL(k_tconv_bn_bwd, dim3((unsigned)((erows + EB_ROWS - 1) / EB_ROWS), (unsigned)(C / 64)), dim3(256), 0, stream, a);
+    return svsr_check_launch();
+}
+
+// norm5 under batch statistics: k_tcn_norm_pool_bwd's g with the statistics' chain rule, dx = bf16(scale * (g - ca - xhat * cb)),
+// xhat = (x - mean) * invstd (ca, cb from svsr_tcn_norm_pool_bwd's sums)
+__global__ __launch_bounds__(256) void k_tcn_norm_pool_bwd_bs(const bf16_t* __restrict__ dh, const bf16_t* __restrict__ dpooled, const bf16_t* __restrict__ x,
+                                                              long x_pitch, int B, int T, int C, const float* __restrict__ scale,
+                                                              const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                              const float* __restrict__ ca, const float* __restrict__ cb,
+                                                              const float* __restrict__ mask, bf16_t* __restrict__ dx, long dx_pitch) {
+    const int pieces = C >> 3;
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= (long)B * pieces) return;
+    const int b = (int)(p / pieces), c0 = (int)(p - (long)b * pieces) * 8;
+    float sc[8], dp[8], mu[8], is[8], a0[8], b0[8];
+    unpack8(*reinterpret_cast<const u32x4*>(dpooled + (long)b * C + c0), dp);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { sc[i] = scale[c0 + i]; mu[i] = mean[c0 + i]; is[i] = invstd[c0 + i]; a0[i] = ca[c0 + i]; b0[i] = cb[c0 + i]; }
+    float msum = 0.f;
+    for (int t = 0; t < T; ++t) msum += mask[(long)b * T + t];
+    const float inv = 1.0f / (msum + 1e-6f);
+    for (int t = 0; t < T; ++t) {
+        const long row = (long)b * T + t;
+        float g[8], xv[8];
+        unpack8(*reinterpret_cast<const u32x4*>(dh + row * C + c0), g);
+        unpack8(*reinterpret_cast<const u32x4*>(x + row * x_pitch + c0), xv);
+        const float m = mask[row] * inv;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            g[i] = __builtin_fmaf(dp[i], m, g[i]);
+            g[i] = sc[i] * ((g[i] - a0[i]) - (xv[i] - mu[i]) * is[i] * b0[i]);
+        }
+        *reinterpret_cast<u32x4*>(dx + row * dx_pitch + c0) = pack8(g);
+    }
+}
+
+extern "C" int svsr_tcn_norm_pool_bwd_bs(const void* dh, const void* dpooled, const void* x, int64_t x_pitch, int B, int T, int C, const float* scale,
+                                         const float* mean, const float* invstd, const float* ca, const float* cb, const float* mask, void* dx,
+                                         int64_t dx_pitch, hipStream_t stream) {
+    if (dh == nullptr || dpooled == nullptr || x == nullptr || scale == nullptr || mask == nullptr || dx == nullptr) return SVSR_ERR_ARG;
+    if (mean == nullptr || invstd == nullptr || ca == nullptr || cb == nullptr) return SVSR_ERR_ARG;
+    if (B < 1 || T < 1 || C < 8 || C % 8 != 0 || x_pitch < C || x_pitch % 8 != 0 || dx_pitch < C || dx_pitch % 8 != 0) return SVSR_ERR_ARG;
+    if ((((uintptr_t)dh | (uintptr_t)dpooled | (uintptr_t)x | (uintptr_t)dx) & 15) != 0) return SVSR_ERR_ARG;
+    const long n = (long)B * (C >> 3);
+    if (n > (1L << 36)) return SVSR_ERR_ARG;
+    hipLaunchKernelGGL(k_tcn_norm_pool_bwd_bs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const bf16_t*)dh, (const bf16_t*)dpooled,
+                       (const bf16_t*)x, (long)x_pitch, B, T, C, scale, mean, invstd, ca, cb, mask, (bf16_t*)dx, (long)dx_pitch);
+    return svsr_check_launch();
 }

@@ -87,6 +87,8 @@ const std::unordered_map<std::string, Entry>& registry() {
         SVSR_REG(svsr_tconv_fwd), SVSR_REG(svsr_tcn_se_fwd), SVSR_REG(svsr_tcn_norm_pool_fwd),
         SVSR_REG(svsr_tconv_fwd_save), SVSR_REG(svsr_tconv_epi_bwd), SVSR_REG(svsr_tconv_dgrad), SVSR_REG(svsr_tconv_wgrad), SVSR_REG(svsr_tcn_se_bwd),
         SVSR_REG(svsr_tcn_norm_pool_bwd), SVSR_REG(svsr_tcn_fold),
+        SVSR_REG(svsr_tconv_fwd_ext), SVSR_REG(svsr_tcn_colstats), SVSR_REG(svsr_tconv_apply), SVSR_REG(svsr_tconv_epi_bwd_bs), SVSR_REG(svsr_tconv_bn_bwd),
+        SVSR_REG(svsr_tconv_dgrad_ext), SVSR_REG(svsr_tconv_wgrad_ext), SVSR_REG(svsr_tcn_norm_pool_bwd_bs),
         SVSR_REG(svsr_lrs_clip_prep), SVSR_REG(svsr_wave_prep),
         SVSR_REG(svsr_lrw_clip_sums), SVSR_REG(svsr_lrw_clip_mix),
         SVSR_REG(svsr_vq_conv0_stats), SVSR_REG(svsr_vq_conv0_apply), SVSR_REG(svsr_vq_gn_partial), SVSR_REG(svsr_vq_gn_relu), SVSR_REG(svsr_vq_project),

@@ -4,9 +4,11 @@ followed by the densely connected temporal convolution network (``tcn/models/den
 consensus and the two heads.
 
 EVAL / INFERENCE PATH (``validation_step`` / ``test_step`` / ``inference.py``) and, in the same statistics mode, the gradients of the temporal
-network and the two heads (``loss_and_backend_grads``: fine-tuning with the front-end and the BatchNorm statistics frozen).  A forward in
-training mode raises NotImplementedError (mixup, dropout, batch-statistic BatchNorm1d and the front-end backward are not built): it never
-runs a wrong forward silently.
+network and the two heads (``loss_and_backend_grads``: fine-tuning with the front-end and the BatchNorm statistics frozen) — or, with
+``train_stats=True``, in the reference's training arithmetic for the back-end: batch-statistic BatchNorm1d (over the chomped positions of
+the full-padding convolutions too), dropout0 / dropout1, mixup; the front-end stays frozen in eval statistics.  A forward under ``.train()``
+raises NotImplementedError (the front-end backward, engine.TrainStep and the OneCycle schedule are not built): it never runs a wrong forward
+silently.
 
 Back-end layout (csrc/dctcn.hip): channels-last bf16 rows; ONE [B*T, reduced + layers * growth] buffer per dense block is the feature
 stack (a layer reads a channel prefix through the row pitch and writes its channels at an offset: no ``torch.cat``).  Per layer: one launch
@@ -25,7 +27,7 @@ from typing import Any, Optional
 
 import torch
 
-from . import ops
+from . import dropout, ops
 from .config import Config
 from .dctcn_init import (SE_REDUCTION, TCN, dctcn_buffer_specs, dctcn_dims, dctcn_init_state_dict, dctcn_layers, dctcn_param_specs)
 from .model import _frontend_forward, _ParamStore, _StoreModule
@@ -103,6 +105,7 @@ class DCTCNLightningModule(_StoreModule):
         self.stem_act = self.trunk_act = ops.ACT_SWISH                        # tcn/model.py:118-119, tcn/models/resnet.py with relu_type swish
         self._prep: Optional[dict] = None
         self._last: dict[str, Any] = {}
+        self._n_cache: dict = {}
         self.eval()
 
     # ------------------------------------------------------------------------------------------------
@@ -154,8 +157,12 @@ class DCTCNLightningModule(_StoreModule):
             return out
         return w.contiguous()
 
-    def _prepare(self, st: _ParamStore) -> dict:
+    def _prepare(self, st: _ParamStore, fold: bool = True) -> dict:
+        """fold=False (the batch-statistic path): the folded running-statistic coefficients are not needed; after a train_stats step they are
+        stale (P["folded"] False) and only a caller that reads them pays for folding them again (_refold)."""
         if self._prep is not None:
+            if fold and not self._prep["folded"]:
+                self._refold(st, self._prep)
             return self._prep
         st.refresh_shadows()
         st.shadow_fresh = True          # eval only: nothing but load_state_dict / mark_params_dirty changes a weight
@@ -189,8 +196,29 @@ class DCTCNLightningModule(_StoreModule):
             sc, sh = self._bn_affine(st, f"{name}.norm", None)
             P["trans"][bi] = dict(k=1, w=self._w16(st, f"{name}.conv.weight"), scale=sc, shift=sh, out_off=0, n_in=n)
         P["norm5"] = self._bn_affine(st, f"{TCN}.norm5", None)
+        P["folded"] = True
         self._prep = P
         return P
+
+    def _refold(self, st: _ParamStore, P: dict) -> None:
+        """The BatchNorm(eval) coefficients of _prepare again, from the current running statistics; weights and shadows are kept."""
+        ks = self.dims["ks"]
+        layers, trans = dctcn_layers(self.config)
+        P["t0"]["scale"], P["t0"]["shift"] = self._bn_affine(st, f"{TCN}.transition0.norm", None)
+        for (p, _, _, _, _), L in zip(layers, P["layers"]):
+            for stage in (0, 1):
+                for i in range(len(ks)):
+                    c = f"{p}.cbcr{stage}_{i}.net"
+                    L[f"stage{stage}"][i]["scale"], L[f"stage{stage}"][i]["shift"] = self._bn_affine(st, f"{c}.1", f"{c}.0.bias")
+        for name, _, bi in trans:
+            P["trans"][bi]["scale"], P["trans"][bi]["shift"] = self._bn_affine(st, f"{name}.norm", None)
+        P["norm5"] = self._bn_affine(st, f"{TCN}.norm5", None)
+        if "bwd" in P:
+            for q, L in zip(P["bwd"]["layers"], P["layers"]):
+                for stage in (0, 1):
+                    q[f"scale{stage}"] = torch.cat([br["scale"] for br in L[f"stage{stage}"]]).contiguous()
+                    q[f"shift{stage}"] = torch.cat([br["shift"] for br in L[f"stage{stage}"]]).contiguous()
+        P["folded"] = True
 
     # ------------------------------------------------------------------------------------------------
     @staticmethod
@@ -251,11 +279,12 @@ class DCTCNLightningModule(_StoreModule):
         return stack
 
     def _run(self, videos: torch.Tensor, word_mask, attention_mask, keep: Optional[dict] = None, tape: Optional[dict] = None,
-             feats: Optional[torch.Tensor] = None):
-        """feats (bf16 [B*T, 512], with videos = the (B, T) pair): the front-end is skipped (loss_and_backend_grads_from_features)."""
+             feats: Optional[torch.Tensor] = None, train: Optional[dict] = None):
+        """feats (bf16 [B*T, 512], with videos = the (B, T) pair): the front-end is skipped (loss_and_backend_grads_from_features).
+        train (loss_and_backend_grads(train_stats=True)): the back-end runs on batch statistics (_backend_bs); the front-end does not."""
         if self.training:
-            raise NotImplementedError("DCTCNLightningModule: only the eval / inference path is built (no mixup, dropout, batch-statistic "
-                                      "BatchNorm1d or backward yet): call .eval() first")
+            raise NotImplementedError("DCTCNLightningModule: a forward under .train() is not built (the front-end has no backward yet): call .eval() "
+                                      "first; the back-end trains through loss_and_backend_grads(train_stats=True)")
         src = videos if feats is None else feats
         if src.device.type != "cuda":
             raise RuntimeError("syncvsr_amd runs on an MI355X HIP device only; there is no CPU fallback")
@@ -268,15 +297,19 @@ class DCTCNLightningModule(_StoreModule):
             if feats.dtype != BF16 or tuple(feats.shape) != (B * T, 512) or not feats.is_contiguous():
                 raise ValueError("features must be a contiguous bf16 [B*T, 512] tensor")
         st = self.store()
-        self._prepare(st)
+        self._prepare(st, fold=train is None)
         C = self.dims["out_size"]
         with torch.no_grad():
             if feats is None:
                 feats = _frontend_forward(self, st, {}, videos.float().contiguous(), False)
-            stack = self._backend(st, feats, word_mask, B, T, keep, tape)
+            if train is None:
+                stack = self._backend(st, feats, word_mask, B, T, keep, tape)
+                scale, shift = self._prep["norm5"]
+            else:
+                stack = self._backend_bs(st, feats, word_mask, B, T, tape, train)
+                scale, shift = self._norm5_bs(st, stack, B, T, tape)
             if attention_mask is None:
                 attention_mask = torch.ones((B, T), dtype=torch.float32, device=src.device)
-            scale, shift = self._prep["norm5"]
             mask = attention_mask.to(torch.float32).contiguous()
             h, pooled = ops.tcn_norm_pool_fwd(stack, scale, shift, mask, B=B, T=T, C=C)
             if tape is not None:
@@ -301,7 +334,8 @@ class DCTCNLightningModule(_StoreModule):
         attached (attach_audio_codec), float waveforms [B, L] / [B, 1, L] on the device."""
         return self._losses(videos, audios, labels, word_mask, attention_mask, None)
 
-    def _losses(self, videos, audios, labels, word_mask, attention_mask, tape: Optional[dict], feats=None) -> dict[str, torch.Tensor]:
+    def _losses(self, videos, audios, labels, word_mask, attention_mask, tape: Optional[dict], feats=None,
+                train: Optional[dict] = None) -> dict[str, torch.Tensor]:
         """The eval forward; with a tape (loss_and_backend_grads) the same launches keep what the backward reads."""
         B, T = (videos.shape[0], videos.shape[2]) if feats is None else videos
         A, G, V = self.audio_alignment, self.vq_groups, self.audio_vocab_size
@@ -310,7 +344,8 @@ class DCTCNLightningModule(_StoreModule):
             raise ValueError("pass pre-computed audio tokens int64 [B, >= A*T, 2] in the `audios` slot (no audio tokeniser is attached)")
         if audios.size(1) < T * A:
             raise ValueError(f"audio tokens have {audios.size(1)} steps, need >= {T * A}")
-        st, h, logits_c = self._run(videos, word_mask, attention_mask, None, tape, feats)
+        st, h, logits_c = self._run(videos, word_mask, attention_mask, None, tape, feats, train)
+        lam = 0.0 if train is None else train["lam"]
         C, NA = self.dims["out_size"], A * G * V
         with torch.no_grad():
             lab = labels.long().contiguous()
@@ -319,6 +354,12 @@ class DCTCNLightningModule(_StoreModule):
             # (the logits are stored: svsr_linear_ce_ok takes K up to 576, the shipped width is 1664)
             logits_a, _ = ops.linear_fwd(h, st.s16("audio_projection.weight"), st.p32("audio_projection.bias"), rows=B * T, K=C, N=NA, x_pitch=C)
             loss_a, lse_a = ops.ce_fwd(logits_a, V, tok, None, B * T * A * G, V, 0.0)
+            if lam:          # mixup (lightning.py:278-298): both losses lerp towards the rolled targets' (the same kernels, called twice)
+                lab2, tok2 = lab.roll(1, 0).contiguous(), audios[:, : T * A].roll(1, 0).contiguous().reshape(-1)
+                loss_c = torch.lerp(loss_c, ops.ce_fwd(logits_c, self.dims["classes"], lab2, None, B, self.dims["classes"], self.label_smoothing)[0], lam)
+                loss_a = torch.lerp(loss_a, ops.ce_fwd(logits_a, V, tok2, None, B * T * A * G, V, 0.0)[0], lam)
+                if tape is not None:
+                    tape.update(lab2=lab2, tok2=tok2, lam=lam)
             acc = ops.topk_acc(logits_c, lab, None)
             loss_total = ops.lincomb2(loss_c, loss_a, self.lambda_audio)
         self._last = dict(last_hidden_states=h, logits_category=logits_c, logits_audio=logits_a)
@@ -333,9 +374,9 @@ class DCTCNLightningModule(_StoreModule):
         """The nn.Parameters loss_and_backend_grads fills: everything but the front-end, in state-dict order."""
         return [p for n, p in self.named_parameters() if self._fwd_rank(n) == 2]
 
-    def _prepare_bwd(self, st: _ParamStore) -> dict:
+    def _prepare_bwd(self, st: _ParamStore, fold: bool = True) -> dict:
         """Transposed, tap-flipped shadows for the data gradients and the per-stage BatchNorm vectors (rebuilt with _prepare's)."""
-        P = self._prepare(st)
+        P = self._prepare(st, fold)
         if "bwd" in P:
             return P["bwd"]
         ks, dev = self.dims["ks"], st.device
@@ -393,30 +434,59 @@ class DCTCNLightningModule(_StoreModule):
         if bias is not None:
             self._put(*self._grad_of(st, bias, accumulate), dcb)
 
-    def _loss_and_grads(self, videos, audios, labels, word_mask, attention_mask, loss_scale, accumulate, want_input_grad, feats=None):
+    def _loss_and_grads(self, videos, audios, labels, word_mask, attention_mask, loss_scale, accumulate, want_input_grad, feats=None,
+                        train_stats: bool = False, dropout_seed: Optional[int] = None, lam: float = 0.0):
         tape: dict[str, Any] = {}
-        out = self._losses(videos, audios, labels, word_mask, attention_mask, tape, feats)
+        train = None
+        if train_stats:
+            lam = float(lam)
+            if not 0.0 <= lam <= 1.0:
+                raise ValueError("lam must lie in [0, 1]")
+            p = float(self.config.model.dctcn.densetcn_options.get("dropout", 0.0)) if dropout_seed is not None else 0.0
+            train = dict(lam=lam, seed=None if dropout_seed is None else int(dropout_seed), p=p)
+            if lam and feats is None:
+                videos = torch.lerp(videos.float(), videos.float().roll(1, 0), lam)          # (word boundaries are not mixed)
+        elif dropout_seed is not None or float(lam) != 0.0:
+            raise ValueError("dropout_seed and lam belong to train_stats=True (the eval-statistics gradients have no dropout and no mixup)")
+        out = self._losses(videos, audios, labels, word_mask, attention_mask, tape, feats, train)
         with torch.no_grad():
-            gf = self._backward(tape, float(loss_scale), bool(accumulate), bool(want_input_grad))
+            if train is None:
+                gf = self._backward(tape, float(loss_scale), bool(accumulate), bool(want_input_grad))
+            else:
+                gf = self._backward_bs(tape, float(loss_scale), bool(accumulate), bool(want_input_grad))
+                self._update_running(tape)
         if want_input_grad:
             out["grad_features"] = gf
         return out
 
     def loss_and_backend_grads(self, videos: torch.Tensor, audios: torch.Tensor, labels: torch.Tensor, word_mask: torch.Tensor,
                                attention_mask: torch.Tensor, loss_scale: float = 1.0, accumulate: bool = False,
-                               want_input_grad: bool = False) -> dict[str, torch.Tensor]:
+                               want_input_grad: bool = False, train_stats: bool = False, dropout_seed: Optional[int] = None,
+                               lam: float = 0.0) -> dict[str, torch.Tensor]:
         """The eval forward (the same launches: the metrics are forward()'s bits) followed by the hand-written backward of the temporal network
         and the two heads: afterwards every parameter of backend_parameters() has .grad = d(loss_total * loss_scale)/d(param) in fp32
         (accumulate=True adds to an existing .grad).  The front-end and every BatchNorm running statistic are frozen and untouched.  With
-        want_input_grad the dict also carries "grad_features": bf16 [B*T, 512], the gradient of the front-end features."""
-        return self._loss_and_grads(videos, audios, labels, word_mask, attention_mask, loss_scale, accumulate, want_input_grad)
+        want_input_grad the dict also carries "grad_features": bf16 [B*T, 512], the gradient of the front-end features.
+
+        train_stats=True: the reference's TRAINING arithmetic for the back-end (the front-end stays frozen in eval statistics).  Every
+        BatchNorm1d uses batch statistics — for the cbcr* norms over all B * (T + (k - 1) d) positions of the full-padding convolution, the
+        chomped ones included, as the reference's Conv1d -> BatchNorm1d -> Chomp1d order has it; padded frames count (lengths=None) — and
+        running_mean / running_var / num_batches_tracked are updated afterwards (momentum 0.1, unbiased variance).  The gradients carry the
+        statistics' chain rule; a cbcr* conv bias cancels and its gradient is exact zeros.  dropout_seed: dropout0 / dropout1 of every dense
+        layer with p = densetcn_options.dropout and the counter-based mask of dropout.py (sites: dropout.dctcn_sites).  lam: mixup, drawn by
+        the caller: videos lerp towards videos.roll(1, 0), both losses towards the rolled targets' (lightning.py:264-299)."""
+        return self._loss_and_grads(videos, audios, labels, word_mask, attention_mask, loss_scale, accumulate, want_input_grad,
+                                    train_stats=train_stats, dropout_seed=dropout_seed, lam=lam)
 
     def loss_and_backend_grads_from_features(self, feats: torch.Tensor, B: int, T: int, audios: torch.Tensor, labels: torch.Tensor,
                                              word_mask: torch.Tensor, attention_mask: torch.Tensor, loss_scale: float = 1.0,
-                                             accumulate: bool = False, want_input_grad: bool = False) -> dict[str, torch.Tensor]:
+                                             accumulate: bool = False, want_input_grad: bool = False, train_stats: bool = False,
+                                             dropout_seed: Optional[int] = None, lam: float = 0.0) -> dict[str, torch.Tensor]:
         """loss_and_backend_grads from pre-computed front-end features (bf16 [B*T, 512]) instead of videos: the frozen front-end need not
-        run again for a clip whose features are cached (and what scripts/dctcn_bench.py --backward times)."""
-        return self._loss_and_grads((int(B), int(T)), audios, labels, word_mask, attention_mask, loss_scale, accumulate, want_input_grad, feats)
+        run again for a clip whose features are cached (and what scripts/dctcn_bench.py --backward times).  With lam the features are those
+        of already-mixed clips; the losses are mixed here."""
+        return self._loss_and_grads((int(B), int(T)), audios, labels, word_mask, attention_mask, loss_scale, accumulate, want_input_grad, feats,
+                                    train_stats=train_stats, dropout_seed=dropout_seed, lam=lam)
 
     def _stage_bwd(self, st: _ParamStore, accumulate: bool, dy, acc, scale, shift, x, convs, *, B: int, T: int, n_in: int, co: int, d: int,
                    gates=None, **epi):
@@ -431,11 +501,12 @@ class DCTCNLightningModule(_StoreModule):
                             add=add)
         return dacc, dres, sums
 
-    def _backward(self, tape: dict, loss_scale: float, accumulate: bool, want_input_grad: bool):
+    def _heads_backward(self, tape: dict, loss_scale: float, accumulate: bool):
+        """The two heads' parameter gradients -> (dh bf16 [B*T, C], dpooled bf16 [B, C]): the gradients of norm5's output and of the pooled row."""
         st: _ParamStore = tape["st"]
-        P, Q, dm = self._prepare(st), self._prepare_bwd(st), self.dims
+        Q, dm = self._prepare_bwd(st, fold="bs" not in tape), self.dims
         B, T, dev = tape["B"], tape["T"], st.device
-        rows, C, R, ks = B * T, dm["out_size"], dm["reduced"], dm["ks"]
+        rows, C = B * T, dm["out_size"]
         A, G, V, NC = self.audio_alignment, self.vq_groups, self.audio_vocab_size, dm["classes"]
         NA, NCp = A * G * V, (NC + 63) // 64 * 64
         grad = lambda name: self._grad_of(st, name, accumulate)          # noqa: E731
@@ -443,9 +514,20 @@ class DCTCNLightningModule(_StoreModule):
         g_c = torch.full((), loss_scale, dtype=torch.float32, device=dev)
         g_a = torch.full((), loss_scale * self.lambda_audio, dtype=torch.float32, device=dev)
         dlc = torch.empty((B, NCp), dtype=BF16, device=dev)
-        ops.ce_bwd(tape["logits_c"], NC, tape["lab"], None, B, NC, self.label_smoothing, tape["lse_c"], g_c, dlc, NCp)
         dla = torch.empty((rows, NA), dtype=BF16, device=dev)
-        ops.ce_bwd(tape["logits_a"], V, tape["tok"], None, rows * A * G, V, 0.0, tape["lse_a"], g_a, dla, V)
+        if "lab2" in tape:          # mixup: the two targets' gradients, weighted 1 - lam and lam, from the same kernel
+            lam = tape["lam"]
+            dlc2, dla2 = torch.zeros_like(dlc), torch.empty_like(dla)
+            dlc.zero_()
+            ops.ce_bwd(tape["logits_c"], NC, tape["lab"], None, B, NC, self.label_smoothing, tape["lse_c"], g_c * (1.0 - lam), dlc, NCp)
+            ops.ce_bwd(tape["logits_c"], NC, tape["lab2"], None, B, NC, self.label_smoothing, tape["lse_c"], g_c * lam, dlc2, NCp)
+            ops.ce_bwd(tape["logits_a"], V, tape["tok"], None, rows * A * G, V, 0.0, tape["lse_a"], g_a * (1.0 - lam), dla, V)
+            ops.ce_bwd(tape["logits_a"], V, tape["tok2"], None, rows * A * G, V, 0.0, tape["lse_a"], g_a * lam, dla2, V)
+            dlc.add_(dlc2)
+            dla.add_(dla2)
+        else:
+            ops.ce_bwd(tape["logits_c"], NC, tape["lab"], None, B, NC, self.label_smoothing, tape["lse_c"], g_c, dlc, NCp)
+            ops.ce_bwd(tape["logits_a"], V, tape["tok"], None, rows * A * G, V, 0.0, tape["lse_a"], g_a, dla, V)
         for wname, bname, x, dy, n_rows, N, pitch in (("audio_projection.weight", "audio_projection.bias", tape["h"], dla, rows, NA, NA),
                                                      ("video_classifier.weight", "video_classifier.bias", tape["pooled"], dlc, B, NC, NCp)):
             (gw, addw), (gb, addb) = grad(wname), grad(bname)
@@ -456,6 +538,15 @@ class DCTCNLightningModule(_StoreModule):
             ops.linear_wgrad(x, dy, gw, rows=n_rows, K=C, N=N, x_pitch=C, dy_pitch=pitch, db=gb)          # (adds)
         dh = ops.linear_dgrad(dla, Q["wa_t"], rows=rows, N=NA, K=C, dy_pitch=NA)
         dpooled = ops.linear_dgrad(dlc, Q["wc_t"], rows=B, N=NC, K=C, dy_pitch=NCp)
+        return dh, dpooled
+
+    def _backward(self, tape: dict, loss_scale: float, accumulate: bool, want_input_grad: bool):
+        st: _ParamStore = tape["st"]
+        P, Q, dm = self._prepare(st), self._prepare_bwd(st), self.dims
+        B, T, dev = tape["B"], tape["T"], st.device
+        rows, C, R, ks = B * T, dm["out_size"], dm["reduced"], dm["ks"]
+        grad = lambda name: self._grad_of(st, name, accumulate)          # noqa: E731
+        dh, dpooled = self._heads_backward(tape, loss_scale, accumulate)
         # norm5 + masked mean
         stacks = tape["stacks"]
         scale5, _ = P["norm5"]
@@ -510,6 +601,184 @@ class DCTCNLightningModule(_StoreModule):
         dx0 = torch.empty((rows, self.in_pad), dtype=BF16, device=dev)
         ops.tconv_dgrad(dacc, B=B, T=T, co=R, d=1, n_out=self.in_pad, out=dx0, branches=[dict(k=1, wt=Q["t0_wt"], dy_off=0)])
         return dx0[:, :512].contiguous()          # (the boundary column's own gradient is discarded)
+
+    # ------------------------------------------------------------------------------------------------
+    # the back-end in the reference's training arithmetic (loss_and_backend_grads(train_stats=True)): batch-statistic BatchNorm1d, dropout
+    # ------------------------------------------------------------------------------------------------
+    def _counts(self, B: int, T: int, hs: tuple, co: int, dev) -> torch.Tensor:
+        """fp32 [len(hs) * co]: the positions B * (T + 2 h) a channel's statistics run over; built once per shape (a host-to-device copy)."""
+        key = (B, T, hs, co, str(dev))
+        if key not in self._n_cache:
+            self._n_cache[key] = torch.tensor([float(B * (T + 2 * h)) for h in hs], dtype=torch.float32, device=dev).repeat_interleave(co)
+        return self._n_cache[key]
+
+    def _stage_bs(self, st: _ParamStore, tape: dict, key, x, norms, *, B: int, T: int, n_in: int, d: int, branches, co: int, act: int, out,
+                  slope=None, res=None, res_act: int = ops.ACT_NONE, drop=None) -> None:
+        """One convolution stage on batch statistics: convolution at every position BatchNorm1d sees (the chomped ones included) -> column
+        statistics -> scale / shift -> the epilogue over the T kept rows.  norms: per branch (BatchNorm, conv bias or None).  tape[key] keeps
+        what the backward and the running-statistic update read."""
+        acc, hmax, hs = ops.tconv_fwd_ext(x, B=B, T=T, n_in=n_in, d=d, branches=branches, co=co)
+        stats = ops.tcn_colstats(acc, B=B, T=T, co=co, hmax=hmax, hs=hs)
+        n = self._counts(B, T, tuple(hs), co, x.device)
+        weight = torch.cat([st.p32(f"{bn}.weight") for bn, _ in norms])
+        bias = torch.cat([st.p32(f"{bn}.bias") for bn, _ in norms])
+        scale, shift, mean, invstd, var_u = ops.bn_batch_affine(stats, n, weight, bias)
+        ops.tconv_apply(acc, scale, shift, B=B, T=T, co=co, hmax=hmax, hs=hs, act=act, out=out, slope=slope, res=res, res_act=res_act, drop=drop)
+        tape["bs"][key] = dict(acc=acc, hmax=hmax, hs=hs, scale=scale, shift=shift, mean=mean, invstd=invstd, n=n, var_u=var_u, norms=norms, co=co,
+                               drop=drop)
+
+    def _backend_bs(self, st: _ParamStore, feats: torch.Tensor, word_mask, B: int, T: int, tape: dict, train: dict):
+        """_backend on batch statistics, with dropout0 / dropout1 when train carries a seed.  The tape is always kept."""
+        P, dm, dev = self._prepare(st, fold=False), self.dims, feats.device
+        tape.update(bs={}, layers=[], stacks=[], train=train)
+        R, ks = dm["reduced"], dm["ks"]
+        sites = dropout.dctcn_sites(self.config)
+        layers, _ = dctcn_layers(self.config)
+        if self.use_boundary:
+            if word_mask is None:
+                raise ValueError("use_boundary: word_mask [B, T] is required")
+            x0 = torch.zeros((B * T, self.in_pad), dtype=BF16, device=dev)
+            x0[:, :512] = feats
+            x0[:, 512] = word_mask.reshape(B * T).to(BF16)
+        else:
+            x0 = feats
+        width = lambda bi: R + dm["blocks"][bi] * dm["growth"][bi]          # noqa: E731
+        stack = torch.empty((B * T, width(0)), dtype=BF16, device=dev)
+        p = f"{TCN}.transition0"
+        self._stage_bs(st, tape, "t0", x0, [(f"{p}.norm", None)], B=B, T=T, n_in=x0.shape[1], d=1, branches=[P["t0"]], co=R, act=ops.ACT_PRELU,
+                       slope=P["t0"]["slope"], out=stack)
+        tape["x0"] = x0
+        tape["stacks"].append(stack)
+        nlayers, li = len(P["layers"]), 0
+        for i, (L, (p, _, _, _, _)) in enumerate(zip(P["layers"], layers)):
+            n_in, g, gb, d, bi = L["n_in"], L["g"], L["gb"], L["d"], L["bi"]
+            li = li + 1 if i and P["layers"][i - 1]["bi"] == bi else 1
+            drop = [None, None]
+            if train["seed"] is not None and train["p"] > 0.0:
+                drop = [(dropout.site_key(train["seed"], sites[f"block{bi + 1}.layer{li}.drop{s}"]), train["p"]) for s in (0, 1)]
+            norms = lambda stage: [(f"{p}.cbcr{stage}_{j}.net.1", f"{p}.cbcr{stage}_{j}.net.0.bias") for j in range(len(ks))]  # noqa: E731
+            gates = ops.tcn_se_fwd(stack, L["se_w1"], L["se_w2"], B=B, T=T, n_in=n_in)
+            out0 = torch.empty((B * T, g), dtype=BF16, device=dev)
+            self._stage_bs(st, tape, (i, 0), stack, norms(0), B=B, T=T, n_in=n_in, d=d, co=gb, act=ops.ACT_SWISH, out=out0, drop=drop[0],
+                           branches=[dict(br, gate=gates[j]) for j, br in enumerate(L["stage0"])])
+            res = torch.empty((B * T, g), dtype=BF16, device=dev)
+            ops.tconv_fwd(stack, B=B, T=T, n_in=n_in, d=1, branches=[L["down"]], co=g, act=ops.ACT_NONE, out=res)
+            self._stage_bs(st, tape, (i, 1), out0, norms(1), B=B, T=T, n_in=g, d=d, co=gb, act=ops.ACT_SWISH, out=stack[:, n_in:], res=res,
+                           res_act=ops.ACT_SWISH, drop=drop[1], branches=L["stage1"])
+            tape["layers"].append(dict(stack=stack, gates=gates, out0=out0, res=res))
+            if (i + 1 == nlayers or P["layers"][i + 1]["bi"] != bi) and bi in P["trans"]:
+                tr = P["trans"][bi]
+                name = [t for t in dctcn_layers(self.config)[1] if t[2] == bi][0][0]
+                nxt = torch.empty((B * T, width(bi + 1)), dtype=BF16, device=dev)
+                self._stage_bs(st, tape, ("tr", bi), stack, [(f"{name}.norm", None)], B=B, T=T, n_in=tr["n_in"], d=1, branches=[tr], co=R,
+                               act=ops.ACT_SWISH, out=nxt)
+                stack = nxt
+                tape["stacks"].append(stack)
+        return stack
+
+    def _norm5_bs(self, st: _ParamStore, stack: torch.Tensor, B: int, T: int, tape: dict):
+        """norm5 on batch statistics over the B * T rows of the bf16 stack -> (scale, shift) for svsr_tcn_norm_pool_fwd."""
+        C, bn = self.dims["out_size"], f"{TCN}.norm5"
+        stats = ops.tcn_colstats(stack, B=B, T=T, co=C)
+        n = self._counts(B, T, (0,), C, stack.device)
+        scale, shift, mean, invstd, var_u = ops.bn_batch_affine(stats, n, st.p32(f"{bn}.weight"), st.p32(f"{bn}.bias"))
+        tape["bs"]["norm5"] = dict(scale=scale, shift=shift, mean=mean, invstd=invstd, n=n, var_u=var_u, norms=[(bn, None)], co=C)
+        return scale, shift
+
+    def _update_running(self, tape: dict, momentum: float = 0.1) -> None:
+        """BatchNorm1d's buffer update of every back-end norm from the step's statistics (the conv bias belongs to the mean, the variance is
+        the unbiased one), then the folded eval coefficients are marked stale: the next eval forward folds them again, a training step does not.
+        (The buffers are views of the store's one flat vector; nothing else shadows them.)"""
+        st: _ParamStore = tape["st"]
+        for S in tape["bs"].values():
+            co = S["co"]
+            for j, (bn, bias) in enumerate(S["norms"]):
+                mean, var = S["mean"][j * co: (j + 1) * co], S["var_u"][j * co: (j + 1) * co]
+                if bias is not None:
+                    mean = mean + st.p32(bias)
+                st.buffers[f"{bn}.running_mean"].mul_(1.0 - momentum).add_(mean, alpha=momentum)
+                st.buffers[f"{bn}.running_var"].mul_(1.0 - momentum).add_(var, alpha=momentum)
+                st.buffers[f"{bn}.num_batches_tracked"].add_(1)
+        if self._prep is not None:
+            self._prep["folded"] = False
+
+    def _stage_bwd_bs(self, st: _ParamStore, accumulate: bool, dy, S: dict, x, weights, *, B: int, T: int, n_in: int, d: int, ks, gates=None,
+                      act: int, slope=None, res=None, res_act: int = ops.ACT_NONE):
+        """_stage_bwd under batch statistics: pass 1 (sums, dres), the O(C) chain rule, pass 2 (the gradient of every extended accumulator),
+        then per branch the BatchNorm gradients, the conv bias's exact zeros and the weight gradient over the extended rows.
+        -> (dacc bf16 [B * (T + 2 hmax), C], dres, sums)"""
+        co, geo = S["co"], dict(B=B, T=T, co=S["co"], hmax=S["hmax"], hs=S["hs"], act=act, slope=slope, res=res, res_act=res_act, drop=S["drop"])
+        dres, sums = ops.tconv_epi_bwd_bs(dy, S["acc"], S["scale"], S["shift"], **geo)
+        dw, db, ca, cb = ops.bn_batch_param_grads(sums[0], sums[1], S["mean"], S["invstd"], S["n"])
+        dacc = ops.tconv_bn_bwd(dy, S["acc"], S["scale"], S["shift"], S["mean"], S["invstd"], ca, cb, **geo)
+        for j, ((bn, bias), weight, k) in enumerate(zip(S["norms"], weights, ks)):
+            self._put(*self._grad_of(st, f"{bn}.weight", accumulate), dw[j * co: (j + 1) * co])
+            self._put(*self._grad_of(st, f"{bn}.bias", accumulate), db[j * co: (j + 1) * co])
+            if bias is not None:          # cancels under batch statistics: exact zeros (an accumulated .grad is left as it is)
+                gb, add = self._grad_of(st, bias, accumulate)
+                if not add:
+                    gb.zero_()
+            gw, add = self._grad_of(st, weight, accumulate)
+            ops.tconv_wgrad(x, dacc[:, j * co: (j + 1) * co], gw, B=B, T=T, n_in=n_in, co=co, k=k, d=d, gate=None if gates is None else gates[j],
+                            add=add, hmax=S["hmax"])
+        return dacc, dres, sums
+
+    def _backward_bs(self, tape: dict, loss_scale: float, accumulate: bool, want_input_grad: bool):
+        st: _ParamStore = tape["st"]
+        P, Q, dm, bs = self._prepare(st, fold=False), self._prepare_bwd(st, fold=False), self.dims, tape["bs"]
+        B, T, dev = tape["B"], tape["T"], st.device
+        rows, C, R, ks = B * T, dm["out_size"], dm["reduced"], dm["ks"]
+        grad = lambda name: self._grad_of(st, name, accumulate)          # noqa: E731
+        dh, dpooled = self._heads_backward(tape, loss_scale, accumulate)
+        # norm5 + masked mean: the sums first, then the data gradient with the statistics' chain rule (one rounding)
+        stacks, S5 = tape["stacks"], bs["norm5"]
+        dS = torch.empty_like(stacks[-1])
+        _, sums = ops.tcn_norm_pool_bwd(dh, dpooled, stacks[-1], S5["scale"], tape["mask"], B=B, T=T, C=C, out=dS)
+        dw, db, ca, cb = ops.bn_batch_param_grads(sums[0], sums[1], S5["mean"], S5["invstd"], S5["n"])
+        self._put(*grad(f"{TCN}.norm5.weight"), dw)
+        self._put(*grad(f"{TCN}.norm5.bias"), db)
+        ops.tcn_norm_pool_bwd_bs(dh, dpooled, stacks[-1], S5["scale"], S5["mean"], S5["invstd"], ca, cb, tape["mask"], B=B, T=T, C=C, out=dS)
+        for i in range(len(P["layers"]) - 1, -1, -1):
+            L, q, t = P["layers"][i], Q["layers"][i], tape["layers"][i]
+            n_in, g, gb, d, bi, p = L["n_in"], L["g"], L["gb"], L["d"], L["bi"], q["p"]
+            stack = t["stack"]
+            weights = lambda stage: [f"{p}.cbcr{stage}_{j}.net.0.weight" for j in range(len(ks))]          # noqa: E731
+            S1, S0 = bs[(i, 1)], bs[(i, 0)]
+            dacc1, dres, sums = self._stage_bwd_bs(st, accumulate, dS[:, n_in: n_in + g], S1, t["out0"], weights(1), B=B, T=T, n_in=g, d=d, ks=ks,
+                                                   act=ops.ACT_SWISH, res=t["res"], res_act=ops.ACT_SWISH)
+            self._put(*grad(f"{p}.downsample.bias"), sums[3])
+            dout0 = torch.empty((rows, g), dtype=BF16, device=dev)
+            ops.tconv_dgrad(dacc1, B=B, T=T, co=gb, d=d, n_out=g, out=dout0, hmax=S1["hmax"],
+                            branches=[dict(k=k, wt=q["wt1"][j], dy_off=j * gb) for j, k in enumerate(ks)])
+            dacc0, _, _ = self._stage_bwd_bs(st, accumulate, dout0, S0, stack, weights(0), B=B, T=T, n_in=n_in, d=d, ks=ks, gates=t["gates"],
+                                             act=ops.ACT_SWISH)
+            gpart = ops.tconv_dgrad(dacc0, B=B, T=T, co=gb, d=d, n_out=n_in, out=dS, x=stack, addend=dS, hmax=S0["hmax"],
+                                    branches=[dict(k=k, wt=q["wt0"][j], dy_off=j * gb, gate=t["gates"][j]) for j, k in enumerate(ks)])
+            g1 = [grad(f"{p}.cbcr0_se_{j}.fc.0.weight") for j in range(len(ks))]
+            g2 = [grad(f"{p}.cbcr0_se_{j}.fc.2.weight") for j in range(len(ks))]
+            dmean = ops.tcn_se_bwd(stack, L["se_w1"], L["se_w2"], t["gates"], gpart, [a for a, _ in g1], [a for a, _ in g2], B=B, T=T, n_in=n_in,
+                                   add=g1[0][1])
+            gw, add = grad(f"{p}.downsample.weight")
+            ops.tconv_wgrad(stack, dres, gw, B=B, T=T, n_in=n_in, co=g, k=1, d=1, add=add)
+            ops.tconv_dgrad(dres, B=B, T=T, co=g, d=1, n_out=n_in, out=dS, addend=dS, cadd=dmean, cadd_scale=1.0 / T,
+                            branches=[dict(k=1, wt=q["down_wt"], dy_off=0)])
+            if i == 0 or P["layers"][i - 1]["bi"] != bi:
+                if bi == 0:
+                    break
+                tr, x, ptr = Q["trans"][bi - 1], stacks[bi - 1], P["trans"][bi - 1]
+                dacc, _, _ = self._stage_bwd_bs(st, accumulate, dS[:, :R], bs[("tr", bi - 1)], x, [f"{tr['name']}.conv.weight"], B=B, T=T,
+                                                n_in=ptr["n_in"], d=1, ks=[1], act=ops.ACT_SWISH)
+                dS = torch.empty_like(x)
+                ops.tconv_dgrad(dacc, B=B, T=T, co=R, d=1, n_out=ptr["n_in"], out=dS, branches=[dict(k=1, wt=tr["wt"], dy_off=0)])
+        p = f"{TCN}.transition0"
+        dacc, _, sums = self._stage_bwd_bs(st, accumulate, dS[:, :R], bs["t0"], tape["x0"], [f"{p}.conv.weight"], B=B, T=T, n_in=self.in_pad, d=1,
+                                           ks=[1], act=ops.ACT_PRELU, slope=P["t0"]["slope"])
+        self._put(*grad(f"{p}.prelu.weight"), sums[2])
+        if not want_input_grad:
+            return None
+        dx0 = torch.empty((rows, self.in_pad), dtype=BF16, device=dev)
+        ops.tconv_dgrad(dacc, B=B, T=T, co=R, d=1, n_out=self.in_pad, out=dx0, branches=[dict(k=1, wt=Q["t0_wt"], dy_off=0)])
+        return dx0[:, :512].contiguous()
 
     def validation_step(self, batch: dict, idx: int = 0) -> dict:
         return {f"val/{k}": v for k, v in self(**batch).items()}

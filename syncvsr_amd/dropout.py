@@ -22,9 +22,14 @@ def _mix(h: np.ndarray) -> np.ndarray:
     return h
 
 
+def site_key(seed: int, site: int) -> int:
+    """The 32-bit key of (seed, site): what `drop_key` computes on the device."""
+    return int(_mix(np.array([(seed * 0x9E3779B9 + site * 0x7F4A7C15 + 0x165667B1) & 0xFFFFFFFF], dtype=np.uint64))[0])
+
+
 def keep_mask(seed: int, site: int, p: float, numel: int) -> np.ndarray:
     """bool [numel]: True where element i is kept."""
-    key = _mix(np.array([(seed * 0x9E3779B9 + site * 0x7F4A7C15 + 0x165667B1) & 0xFFFFFFFF], dtype=np.uint64))[0]
+    key = np.uint64(site_key(seed, site))
     idx = np.arange(numel, dtype=np.uint64)
     h = _mix((idx * np.uint64(2654435761) + key) & _M)
     thresh = min(int(p * 4294967296.0), 4294967295)
@@ -58,4 +63,12 @@ def lrs_sites(elayers: int, dlayers: int) -> dict[str, int]:
         names += [f"enc.{i}.{s}" for s in ("ffm.hidden", "ffm.out", "attn.probs", "attn.out", "conv.out", "ff.hidden", "ff.out")]
     for i in range(dlayers):
         names += [f"dec.{i}.{s}" for s in ("self.probs", "self.out", "src.probs", "src.out", "ff.hidden", "ff.out")]
+    return {n: k + 1 for k, n in enumerate(names)}
+
+
+def dctcn_sites(config) -> dict[str, int]:
+    """Sites of the DC-TCN back-end (tcn/models/densetcn.py:53-57,83,90): `dropout0` / `dropout1` of every dense layer, one site per
+    (layer, stage) in forward order.  The element index is row * growth + channel of the stage's concatenated [B*T, growth] output."""
+    blocks = [int(v) for v in config.model.dctcn.densetcn_options.block_config]
+    names = [f"block{bi + 1}.layer{li + 1}.drop{s}" for bi, nl in enumerate(blocks) for li in range(nl) for s in (0, 1)]
     return {n: k + 1 for k, n in enumerate(names)}

@@ -2295,11 +2295,13 @@ def tconv_epi_bwd(dy: torch.Tensor, acc: torch.Tensor, scale: torch.Tensor, shif
 
 def tconv_dgrad(dy: torch.Tensor, *, B: int, T: int, co: int, d: int, branches: Sequence[dict], n_out: int, out: torch.Tensor,
                 x: Optional[torch.Tensor] = None, addend: Optional[torch.Tensor] = None, cadd: Optional[torch.Tensor] = None,
-                cadd_scale: float = 1.0) -> Optional[torch.Tensor]:
+                cadd_scale: float = 1.0, hmax: Optional[int] = None) -> Optional[torch.Tensor]:
     """Data gradient of up to three branches in one launch (svsr_tconv_dgrad).  Each branch: k, wt (bf16 [n_out, k, co], transposed and tap-flipped:
     tconv_wt), dy_off, optionally gate (fp32 [B, n_out]).  out bf16 [B*T, >= n_out] = addend + cadd[b] * cadd_scale + sum gate_i * dxg_i.
-    -> the gate partials fp32 [nb, B, tiles, n_out] if any branch is gated (x, the forward's input rows, is required then), else None."""
-    rows = B * T
+    -> the gate partials fp32 [nb, B, tiles, n_out] if any branch is gated (x, the forward's input rows, is required then), else None.
+    hmax given (svsr_tconv_dgrad_ext; 0 is the plain launch through that entry): dy is the gradient of the extended accumulators, bf16
+    [B * (T + 2 * hmax), .] (tconv_bn_bwd)."""
+    rows, ext, hmax = B * T, hmax is not None, int(hmax or 0)
     for br in branches:
         if not tconv_ok(co, n_out, int(br["k"]), int(d)):
             raise ValueError("tconv_dgrad: outside the shape domain of svsr_tconv_fwd (channels a multiple of 64, odd k <= 7, (k - 1) d / 2 <= 16)")
@@ -2311,7 +2313,7 @@ def tconv_dgrad(dy: torch.Tensor, *, B: int, T: int, co: int, d: int, branches: 
         _rows_view(x, rows, n_out, BF16)
     if addend is not None:
         _rows_view(addend, rows, n_out, BF16)
-    _rows_view(dy, rows, 0, BF16)
+    _rows_view(dy, B * (T + 2 * hmax), 0, BF16)
     _packed(cadd, torch.float32, (B, n_out), optional=True)
     tab_rows = []
     for br in branches:
@@ -2323,9 +2325,13 @@ def tconv_dgrad(dy: torch.Tensor, *, B: int, T: int, co: int, d: int, branches: 
         tab_rows.append((k, _p(wt), _p(g) or 0, off))
     gpart = torch.empty((len(branches), B, (T + 31) // 32, n_out), dtype=torch.float32, device=dy.device) if gated else None
     tab = _host_table(tab_rows)
-    _call("svsr_tconv_dgrad", _p(dy), dy.stride(0), B, T, co, int(d), len(branches), tab.data_ptr(), n_out, _p(x),
-          0 if x is None else x.stride(0), _p(addend), 0 if addend is None else addend.stride(0), _p(cadd), float(cadd_scale), _p(out), out.stride(0),
-          _p(gpart), _stream(), label="k_tconv_dgrad", flops=sum(2.0 * rows * n_out * r[0] * co for r in tab_rows))
+    head = (_p(dy), dy.stride(0), B, T, co, int(d), len(branches), tab.data_ptr(), n_out, _p(x), 0 if x is None else x.stride(0), _p(addend),
+            0 if addend is None else addend.stride(0), _p(cadd), float(cadd_scale), _p(out), out.stride(0), _p(gpart))
+    flops = sum(2.0 * rows * n_out * r[0] * co for r in tab_rows)
+    if ext:
+        _call("svsr_tconv_dgrad_ext", *head, hmax, _stream(), label="k_tconv_dgrad", flops=flops)
+    else:
+        _call("svsr_tconv_dgrad", *head, _stream(), label="k_tconv_dgrad", flops=flops)
     return gpart
 
 
@@ -2342,21 +2348,25 @@ def tconv_wgrad_splits(B: int, T: int, n_in: int, co: int) -> int:
 
 
 def tconv_wgrad(x: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor, *, B: int, T: int, n_in: int, co: int, k: int, d: int,
-                gate: Optional[torch.Tensor] = None, add: bool = False, splits: Optional[int] = None) -> None:
+                gate: Optional[torch.Tensor] = None, add: bool = False, splits: Optional[int] = None, hmax: Optional[int] = None) -> None:
     """dw fp32 [co, n_valid <= n_in, k] (contiguous, the parameter's layout) = (add ? dw : 0) + sum_rows dy^T (x) shifted bf16(x * gate)
-    (svsr_tconv_wgrad).  x bf16 [B*T, >= n_in], dy bf16 [B*T, >= co] (the branch's channel slice)."""
+    (svsr_tconv_wgrad).  x bf16 [B*T, >= n_in], dy bf16 [B*T, >= co] (the branch's channel slice).  hmax given (svsr_tconv_wgrad_ext; 0 is the plain launch): dy is the
+    gradient of the extended accumulators, bf16 [B * (T + 2 * hmax), >= co], and the sum runs over all of its rows."""
     if not tconv_ok(n_in, co, int(k), int(d)):
         raise ValueError("tconv_wgrad: outside the shape domain of svsr_tconv_fwd (channels a multiple of 64, odd k <= 7, (k - 1) d / 2 <= 16)")
-    rows = B * T
+    rows, ext, hmax = B * T, hmax is not None, int(hmax or 0)
     _rows_view(x, rows, n_in, BF16)
-    _rows_view(dy, rows, co, BF16)
+    _rows_view(dy, B * (T + 2 * hmax), co, BF16)
     if not (dw.dtype == torch.float32 and dw.is_contiguous() and dw.dim() == 3 and dw.shape[0] == co and dw.shape[2] == k and 1 <= dw.shape[1] <= n_in):
         raise ValueError(f"tconv_wgrad: dw must be a contiguous fp32 [co, <= n_in, k] tensor, got {tuple(dw.shape)}")
     _packed(gate, torch.float32, (B, n_in), optional=True)
-    S = tconv_wgrad_splits(B, T, n_in, co) if splits is None else int(splits)
+    S = tconv_wgrad_splits(B, T + 2 * hmax, n_in, co) if splits is None else int(splits)
     part = torch.empty(S * co * k * n_in, dtype=torch.float32, device=x.device)
-    _call("svsr_tconv_wgrad", _p(x), x.stride(0), _p(gate), _p(dy), dy.stride(0), B, T, n_in, co, int(k), int(d), S, _p(part), _p(dw), dw.shape[1],
-          int(bool(add)), _stream(), label=f"k_tconv_wgrad<{k}>", flops=2.0 * rows * n_in * k * co)
+    head = (_p(x), x.stride(0), _p(gate), _p(dy), dy.stride(0), B, T, n_in, co, int(k), int(d), S, _p(part), _p(dw), dw.shape[1], int(bool(add)))
+    if ext:
+        _call("svsr_tconv_wgrad_ext", *head, hmax, _stream(), label=f"k_tconv_wgrad<{k}>", flops=2.0 * B * (T + 2 * hmax) * n_in * k * co)
+    else:
+        _call("svsr_tconv_wgrad", *head, _stream(), label=f"k_tconv_wgrad<{k}>", flops=2.0 * rows * n_in * k * co)
 
 
 def tcn_se_bwd(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, gate: torch.Tensor, gpart: torch.Tensor, dw1: Sequence[torch.Tensor],
@@ -2412,3 +2422,149 @@ def bn_conv_param_grads(sum_g: torch.Tensor, sum_g_acc: torch.Tensor, weight: to
     d_weight = r * (sum_g_acc + off * sum_g)
     d_cbias = None if conv_bias is None else sum_g * (weight * r)
     return d_weight, sum_g, d_cbias
+
+
+# -- batch-statistic stages of the back-end (loss_and_backend_grads(train_stats=True)) ---------------------------------------------
+# The extended axis: hs[i] = (k_i - 1) * d / 2 per branch, hmax >= max(hs); a clip owns T + 2 * hmax rows, time t is row t + hmax, branch i
+# (channels [i * co, (i + 1) * co)) owns the rows [hmax - hs[i], hmax + hs[i] + T): the positions the reference's BatchNorm1d sees before the chomp.
+def tconv_halos(ks: Sequence[int], d: int) -> list:
+    return [(int(k) - 1) * int(d) // 2 for k in ks]
+
+
+def _int_table(vals) -> torch.Tensor:
+    tab = torch.tensor([int(v) for v in vals], dtype=torch.int32)
+    if _REC is not None:
+        _REC.keep.append(tab)
+    return tab
+
+
+def _ext_geo(B: int, T: int, co: int, hmax: int, hs: Sequence[int]):
+    hs = [int(h) for h in hs]
+    if not (1 <= len(hs) <= 3 and 0 <= int(hmax) <= TCONV_MAX_HALO and all(0 <= h <= hmax for h in hs) and co >= 64 and co % 64 == 0):
+        raise ValueError(f"extended axis: one to three branches of a multiple of 64 channels with 0 <= h <= hmax <= {TCONV_MAX_HALO}, got {hs}, {hmax}, {co}")
+    return hs, len(hs) * co, B * (T + 2 * int(hmax))
+
+
+def tconv_fwd_ext(x: torch.Tensor, *, B: int, T: int, n_in: int, d: int, branches: Sequence[dict], co: int, hmax: Optional[int] = None,
+                  acc: Optional[torch.Tensor] = None):
+    """The convolutions of tconv_fwd at every position the reference's BatchNorm1d sees (svsr_tconv_fwd_ext): branches hold k, w and optionally
+    gate.  -> (acc fp32 [B * (T + 2 * hmax), nb * co], hmax, hs).  Rows of a branch's channels outside its own extent are not written."""
+    hs = tconv_halos([br["k"] for br in branches], d)
+    hmax = max(hs) if hmax is None else int(hmax)
+    hs, C, erows = _ext_geo(B, T, co, hmax, hs)
+    _rows_view(x, B * T, n_in, BF16)
+    if acc is None:
+        acc = torch.empty((erows, C), dtype=torch.float32, device=x.device)
+    _rows_view(acc, erows, C, torch.float32)
+    rows = []
+    for br in branches:
+        w, k, g = br["w"], int(br["k"]), br.get("gate")
+        if not tconv_ok(n_in, co, k, int(d)):
+            raise ValueError("tconv_fwd_ext: outside the shape domain of svsr_tconv_fwd")
+        _packed(w, BF16, (co, k, n_in))
+        _packed(g, torch.float32, (B, n_in), optional=True)
+        rows.append((k, _p(w), _p(g) or 0, 0, 0, 0, 0, 0))
+    tab = _host_table(rows)
+    _call("svsr_tconv_fwd_ext", _p(x), x.stride(0), B, T, n_in, int(d), len(branches), tab.data_ptr(), co, hmax, _p(acc), acc.stride(0), _stream(),
+          label="k_tconv<ext>", flops=sum(2.0 * B * (T + 2 * h) * n_in * r[0] * co for r, h in zip(rows, hs)))
+    return acc, hmax, hs
+
+
+def tcn_colstats(x: torch.Tensor, *, B: int, T: int, co: int, hmax: int = 0, hs: Sequence[int] = (0,)) -> torch.Tensor:
+    """Per channel (mean, sum (x - mean)^2) over the B * (T + 2 * hs[i]) own rows of every branch (svsr_tcn_colstats): x fp32 (the extended
+    accumulators) or bf16 (an activation stack: hmax = 0) [B * (T + 2 * hmax), >= nb * co] -> stats fp32 [2, nb * co]."""
+    hs, C, erows = _ext_geo(B, T, co, hmax, hs)
+    if x.dtype not in (torch.float32, BF16):
+        raise ValueError("tcn_colstats: fp32 or bf16 rows")
+    _rows_view(x, erows, C, x.dtype)
+    part = torch.empty(B * 2 * C, dtype=torch.float32, device=x.device)
+    stats = torch.empty((2, C), dtype=torch.float32, device=x.device)
+    tab = _int_table(hs)
+    _call("svsr_tcn_colstats", _p(x), x.stride(0), int(x.dtype == BF16), B, T, C, co, int(hmax), len(hs), tab.data_ptr(), _p(part), _p(stats), _stream(),
+          label="k_tcn_colstats")
+    return stats
+
+
+def _epi_args(acc, scale, shift, slope, res, B, T, co, hmax, hs, act, res_act, drop):
+    hs, C, erows = _ext_geo(B, T, co, hmax, hs)
+    _rows_view(acc, erows, C, torch.float32)
+    for t in (scale, shift):
+        _packed(t, torch.float32, numel=C)
+    _packed(slope, torch.float32, numel=C, optional=True)
+    if res is not None:
+        _rows_view(res, B * T, C, BF16)
+    key, p = (0, 0.0) if drop is None else (int(drop[0]) & 0xFFFFFFFF, float(drop[1]))
+    tab = _int_table(hs)
+    return C, erows, tab, (_p(acc), acc.stride(0), B, T, C, co, int(hmax), len(hs), tab.data_ptr(), int(act), _p(scale), _p(shift), _p(slope), _p(res),
+                           0 if res is None else res.stride(0), int(res_act), key, p)
+
+
+def tconv_apply(acc: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, *, B: int, T: int, co: int, hmax: int, hs: Sequence[int], act: int,
+                out: torch.Tensor, slope: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None, res_act: int = ACT_NONE,
+                drop: Optional[tuple] = None) -> torch.Tensor:
+    """The epilogue of a batch-statistic stage over the T interior rows (svsr_tconv_apply): out bf16 [B*T, >= C] channels [0, C) =
+    res_act(dropout(act(fma(acc, scale, shift))) + res).  drop = (key, p): dropout.site_key(seed, site) and the probability."""
+    C, _, tab, head = _epi_args(acc, scale, shift, slope, res, B, T, co, hmax, hs, act, res_act, drop)
+    _rows_view(out, B * T, C, BF16)
+    _call("svsr_tconv_apply", *head, _p(out), out.stride(0), _stream(), label="k_tconv_apply")
+    return out
+
+
+def tconv_epi_bwd_bs(dy: torch.Tensor, acc: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, *, B: int, T: int, co: int, hmax: int,
+                     hs: Sequence[int], act: int, slope: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None, res_act: int = ACT_NONE,
+                     drop: Optional[tuple] = None):
+    """Pass 1 of a batch-statistic stage's backward (svsr_tconv_epi_bwd_bs) -> (dres bf16 [B*T, C] or None, sums fp32 [4, C] as tconv_epi_bwd's)."""
+    C, _, tab, head = _epi_args(acc, scale, shift, slope, res, B, T, co, hmax, hs, act, res_act, drop)
+    _rows_view(dy, B * T, C, BF16)
+    dres = torch.empty((B * T, C), dtype=BF16, device=dy.device) if res is not None else None
+    part = torch.empty(((B * T + 63) // 64) * 4 * C, dtype=torch.float32, device=dy.device)
+    sums = torch.empty((4, C), dtype=torch.float32, device=dy.device)
+    _call("svsr_tconv_epi_bwd_bs", _p(dy), dy.stride(0), *head, _p(dres), 0 if dres is None else dres.stride(0), _p(part), _p(sums), _stream(),
+          label="k_tconv_epi_bwd_bs")
+    return dres, sums
+
+
+def tconv_bn_bwd(dy: torch.Tensor, acc: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, mean: torch.Tensor, invstd: torch.Tensor,
+                 ca: torch.Tensor, cb: torch.Tensor, *, B: int, T: int, co: int, hmax: int, hs: Sequence[int], act: int,
+                 slope: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None, res_act: int = ACT_NONE, drop: Optional[tuple] = None):
+    """Pass 2 (svsr_tconv_bn_bwd) -> dacc bf16 [B * (T + 2 * hmax), C]: scale * (g - ca - xhat * cb) on a branch's own rows, zeros elsewhere."""
+    C, erows, tab, head = _epi_args(acc, scale, shift, slope, res, B, T, co, hmax, hs, act, res_act, drop)
+    _rows_view(dy, B * T, C, BF16)
+    for t in (mean, invstd, ca, cb):
+        _packed(t, torch.float32, numel=C)
+    dacc = torch.empty((erows, C), dtype=BF16, device=dy.device)
+    _call("svsr_tconv_bn_bwd", _p(dy), dy.stride(0), *head, _p(mean), _p(invstd), _p(ca), _p(cb), _p(dacc), dacc.stride(0), _stream(),
+          label="k_tconv_bn_bwd")
+    return dacc
+
+
+def tcn_norm_pool_bwd_bs(dh: torch.Tensor, dpooled: torch.Tensor, x: torch.Tensor, scale: torch.Tensor, mean: torch.Tensor, invstd: torch.Tensor,
+                         ca: torch.Tensor, cb: torch.Tensor, mask: torch.Tensor, *, B: int, T: int, C: int, out: torch.Tensor) -> torch.Tensor:
+    """tcn_norm_pool_bwd's dx with norm5's batch statistics in the chain (svsr_tcn_norm_pool_bwd_bs): out = scale * (g - ca - xhat * cb)."""
+    if C < 8 or C % 8:
+        raise ValueError("tcn_norm_pool_bwd_bs: C must be a multiple of 8")
+    _packed(dh, BF16, (B * T, C))
+    _packed(dpooled, BF16, (B, C))
+    _rows_view(x, B * T, C, BF16)
+    _rows_view(out, B * T, C, BF16)
+    _packed(mask, torch.float32, numel=B * T)
+    for t in (scale, mean, invstd, ca, cb):
+        _packed(t, torch.float32, numel=C)
+    _call("svsr_tcn_norm_pool_bwd_bs", _p(dh), _p(dpooled), _p(x), x.stride(0), B, T, C, _p(scale), _p(mean), _p(invstd), _p(ca), _p(cb), _p(mask),
+          _p(out), out.stride(0), _stream(), label="k_tcn_norm_pool_bwd_bs")
+    return out
+
+
+def bn_batch_affine(stats: torch.Tensor, n: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float = BN_EPS):
+    """The O(C) step between tcn_colstats and the apply: stats [2, C] = (mean, sum (x - mean)^2) over n [C] positions ->
+    (scale = weight * invstd, shift = bias - mean * scale, mean, invstd, unbiased variance).  A conv bias cancels under batch statistics."""
+    mean, var = stats[0], stats[1] / n
+    invstd = torch.rsqrt(var + eps)
+    scale = weight * invstd
+    return scale.contiguous(), (bias - mean * scale).contiguous(), mean.contiguous(), invstd.contiguous(), stats[1] / (n - 1.0)
+
+
+def bn_batch_param_grads(sum_g: torch.Tensor, sum_g_x: torch.Tensor, mean: torch.Tensor, invstd: torch.Tensor, n: torch.Tensor):
+    """From pass 1's sums of g and g * x: -> (d bn.weight = sum g * xhat, d bn.bias = sum g, ca = sum g / n, cb = sum g * xhat / n)."""
+    d_weight = invstd * (sum_g_x - mean * sum_g)
+    return d_weight, sum_g, (sum_g / n).contiguous(), (d_weight / n).contiguous()
