@@ -203,6 +203,15 @@ int svsr_conv3x3_wgrad_plan(int Nimg, int H, int W, int Ci, int Co, int* splits,
 int svsr_conv3x3_wgrad(const void* x, const void* dy, float* dw, int Nimg, int H, int W, int Ci, int Co, float* part, int64_t part_floats, hipStream_t stream);
 /* the same with the store / add mode of dw (0 or SVSR_GRAD_ADD_DW) */
 int svsr_conv3x3_wgrad_v2(const void* x, const void* dy, float* dw, int Nimg, int H, int W, int Ci, int Co, float* part, int64_t part_floats, int mode, hipStream_t stream);
+/* The chained form.  defer != 0: the launch leaves its split-K slabs in `part` un-added (nothing is deferred where the plan has one split: dw
+ * is written directly); the caller hands them on as the PENDING slabs of a later svsr_conv3x3_wgrad_chain on the same stream, or to
+ * svsr_conv3x3_wgrad_reduce.  pend_part != NULL: pend_splits (>= 2, from svsr_conv3x3_wgrad_plan of that convolution) slabs per 64 x 64
+ * tile of an earlier deferred launch — any geometry, pend_Ci / pend_Co its channel counts — which this launch's workgroups add into
+ * pend_dw (pend_mode: that convolution's store / add mode) before their own work, in the order of the stand-alone reduce: the same bits.
+ * Stream order is the only synchronisation, so the pending slabs must not overlap the range [part, part + part_floats needed) this launch
+ * writes: SVSR_ERR_ARG, nothing launched (keep two slab sets and alternate).  pend_part == NULL and defer == 0: svsr_conv3x3_wgrad_v2. */
+int svsr_conv3x3_wgrad_chain(const void* x, const void* dy, float* dw, int Nimg, int H, int W, int Ci, int Co, float* part, int64_t part_floats, int mode, int defer, const float* pend_part, float* pend_dw, int pend_splits, int pend_Ci, int pend_Co, int pend_mode, hipStream_t stream);
+int svsr_conv3x3_wgrad_reduce(const float* part, float* dw, int splits, int Ci, int Co, int mode, hipStream_t stream);
 
 /* ---- 3-D stem (stem.hip) --------------------------------------------------------------------------------------
  * svsr_stem_conv_fwd replaces stem3d[0] = nn.Conv3d(1,64,(5,7,7),(1,2,2),(2,3,3),bias=False) (lightning.py:50).

@@ -81,6 +81,7 @@ const std::unordered_map<std::string, Entry>& registry() {
         SVSR_REG(svsr_ls_loss_bwd), SVSR_REG(svsr_scale_bf16), SVSR_REG(svsr_word_add), SVSR_REG(svsr_lincomb2), SVSR_REG(svsr_igemm_wgrad_group), SVSR_REG(svsr_enc_fwd), SVSR_REG(svsr_enc_bwd), SVSR_REG(svsr_lincomb3_ratio), SVSR_REG(svsr_add_ln_bwd_partials), SVSR_REG(svsr_add_ln_bwd_branch), SVSR_REG(svsr_bias_act_bwd_partials),
         SVSR_REG(svsr_memcpy_async), SVSR_REG(svsr_w2v_conv0), SVSR_REG(svsr_w2v_norm_gelu), SVSR_REG(svsr_w2v_quantize),
         SVSR_REG(svsr_igemm_wgrad_v2), SVSR_REG(svsr_igemm_wgrad_group_v2), SVSR_REG(svsr_conv3x3_wgrad_v2), SVSR_REG(svsr_fill_ranges),
+        SVSR_REG(svsr_conv3x3_wgrad_chain), SVSR_REG(svsr_conv3x3_wgrad_reduce),
         SVSR_REG(svsr_mha_table_fwd), SVSR_REG(svsr_lm_embed_fwd),
         SVSR_REG(svsr_beam_select), SVSR_REG(svsr_ctc_prefix_score_clips), SVSR_REG(svsr_mha_src_step_fwd), SVSR_REG(svsr_ctc_align),
         SVSR_REG(svsr_ctc_frame_best), SVSR_REG(svsr_ctc_collapse), SVSR_REG(svsr_edit_distance),

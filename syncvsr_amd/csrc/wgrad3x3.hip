@@ -48,6 +48,63 @@ struct Wgrad3Args {
 struct Wgrad3Multi { const bf16_t* x[4]; const bf16_t* dy[4]; float* dw[4]; };
 #define W3_TILE_FLOATS (9 * 64 * 64)
 
+#define W3_RED_BLOCKS (W3_TILE_FLOATS / 4 / 64)       // block-items of one task's reduce: 64 float4 groups each
+
+// The slabs of an EARLIER launch on the same stream that are still to be added into their dW (the chained form, svsr_conv3x3_wgrad_chain):
+// everything k_wgrad3_reduce is launched with.  Stream order alone makes the slabs visible to the launch that carries this — no flag, no
+// atomic.  items = W3_RED_BLOCKS * tasks * problems; 0: nothing pending.
+struct Wgrad3Pending { const float* part; float* dw[4]; int splits, Ci, ci_tiles, add, tasks, items; };
+
+// One block-item of the slab reduce, by 256 threads (t256 = 0 .. 255): float4 groups bx * 64 .. + 63 of a task's tiles, slabs added in split order
+// by four slot lanes, the lanes' sums added in lane order, then scattered into dW[co][t][ci] (add == 0: the first writer of dW this step stores
+// 0.f + sum without loading the destination).  Both k_wgrad3_reduce and the prologue of k_wgrad3x3_halo go through here, so a weight
+// gradient has the same bits whichever of them sums it.  Every thread of the workgroup must call it (one barrier inside); on == false: a
+// thread group without an item.
+__device__ __forceinline__ void w3_reduce_item(const float* __restrict__ src, float* dw, int bx, int task, int splits, int Ci, int ci_tiles, int add,
+                                               f32x4 (*sred)[64], int t256, bool on) {
+    const int gl = t256 & 63, sl = t256 >> 6;
+    const int g = bx * 64 + gl;
+    f32x4 a = {0.f, 0.f, 0.f, 0.f};
+    if (on) {
+        int s = sl;
+        // eight loads in flight per thread, added in the lane's split order (two in flight made a lane's 64 slabs a chain of 32 dependent round
+        // trips: 18 us alone, 30-130 us beside the main stream's HBM-bound passes)
+        for (; s + 28 < splits; s += 32) {
+            f32x4 v[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = reinterpret_cast<const f32x4*>(src + (long)(s + 4 * k) * W3_TILE_FLOATS)[g];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) a = a + v[k];
+        }
+        for (; s + 4 < splits; s += 8) {
+            const f32x4 v0 = reinterpret_cast<const f32x4*>(src + (long)s * W3_TILE_FLOATS)[g];
+            const f32x4 v1 = reinterpret_cast<const f32x4*>(src + (long)(s + 4) * W3_TILE_FLOATS)[g];
+            a = (a + v0) + v1;
+        }
+        for (; s < splits; s += 4) a = a + reinterpret_cast<const f32x4*>(src + (long)s * W3_TILE_FLOATS)[g];
+        sred[sl][gl] = a;
+    }
+    __syncthreads();
+    if (!on || sl != 0) return;
+    a = ((sred[0][gl] + sred[1][gl]) + sred[2][gl]) + sred[3][gl];
+    const int lane = g & 63, rq = (g >> 6) & 3, wave = (g >> 8) & 3, t = g >> 10;
+    const int cot = task / ci_tiles, cit = task - cot * ci_tiles;
+    const int ci = cit * 64 + (wave & 1) * 32 + (lane & 31);
+    const int co = cot * 64 + (wave >> 1) * 32 + 8 * rq + 4 * (lane >> 5);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float* d = dw + ((long)(co + k) * 9 + t) * Ci + ci;
+        *d = (add ? *d : 0.f) + a[k];
+    }
+}
+
+// dW[co][t][ci] += sum over the splits (in split order) of a task's tiles.  grid (9 * 16 blocks of 64 float4 groups, tasks, problems)
+__global__ __launch_bounds__(256) void k_wgrad3_reduce(const float* __restrict__ part, const Wgrad3Multi m, int splits, int Ci, int ci_tiles, int add) {
+    __shared__ f32x4 sred[4][64];
+    const float* src = part + ((long)blockIdx.z * gridDim.y + blockIdx.y) * splits * W3_TILE_FLOATS;
+    w3_reduce_item(src, m.dw[blockIdx.z], blockIdx.x, blockIdx.y, splits, Ci, ci_tiles, add, sred, threadIdx.x, true);
+}
+
 __device__ __forceinline__ bf16x8 w3_frag_T(const bf16_t* tile, int ch0, int pos0, int lane) {
     // MFMA 32x32x16 fragment: lane l <- channel ch0 + (l&31), positions pos0 + (l>>5)*8 .. +7, via two transpose reads
     const int gq = lane >> 4, s = lane & 15;
@@ -94,7 +151,7 @@ __device__ __forceinline__ long w3_pixel(const Wgrad3Args& p, int q) {
 // is still the padded stretch those pixels span (+ halo; pad rows are zeros), and a small LDS table maps position k of the chunk to its padded row
 // — ds_read_b64_tr_b16 takes a row address per lane, so the nine shifted fragments are gathered through that table instead of walked.
 template <int NW, bool DENSE>
-__global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_wgrad3x3_halo(const Wgrad3Args p, const Wgrad3Multi m) {
+__global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_wgrad3x3_halo(const Wgrad3Args p, const Wgrad3Multi m, const Wgrad3Pending pd) {
     constexpr int NT = NW * 64, RPP = NT / 8;                    // threads; tile rows staged per pass of all threads
     constexpr int YR = W3_CH / RPP, XRN = (DENSE ? W3D_MAXXR : W3_MAXXR) / RPP;        // dY / X rows per thread and chunk
     constexpr int TPW = NW == 4 ? 9 : 5;                         // taps per wave
@@ -208,6 +265,24 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_wgrad3x3_halo(cons
         // 384 KiB of fragment reads (1.2 KiB per MFMA: every X fragment feeds ONE MFMA) next to 1.2 us of MFMA time.)
         Staged g;
         if (c_begin < c_end) load_chunk(g, c_begin);
+        if (pd.items > 0) {
+            // The pending reduce (Wgrad3Pending), here: behind the first chunk's operand requests, so those rows fly underneath it, and ahead of the
+            // first barrier of the chunk loop, while the dY tile's LDS is still free for the four lane sums.  The launch's workgroups walk the
+            // block-items grid-stride, one per 256 threads, spread over as many workgroups as there are items before a second half is used.
+            const int half = __builtin_amdgcn_readfirstlane(tid >> 8);
+            f32x4 (*sred)[64] = reinterpret_cast<f32x4 (*)[64]>(smem_raw) + half * 4;
+            const int nblk = gridDim.x * gridDim.y * gridDim.z;
+            const int blk = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+            for (int it = blk; it < pd.items; it += nblk * (NT / 256)) {
+                const int item = it + half * nblk;
+                const bool on = item < pd.items;
+                const int tk = on ? item / W3_RED_BLOCKS : 0, bx = on ? item - tk * W3_RED_BLOCKS : 0;       // tk: problem * tasks + task
+                const int prob = tk / pd.tasks;
+                w3_reduce_item(pd.part + (long)tk * pd.splits * W3_TILE_FLOATS, pd.dw[prob], bx, tk - prob * pd.tasks, pd.splits, pd.Ci, pd.ci_tiles,
+                               pd.add, sred, tid & 255, on);
+                __syncthreads();                       // the lane sums are read: the next item, or the first chunk, may overwrite them
+            }
+        }
         for (int c = c_begin; c < c_end; ++c) {
             __syncthreads();                           // previous chunk's fragment reads are done
             store_chunk(g, c, sY, sX, sMap);
@@ -239,46 +314,6 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_wgrad3x3_halo(cons
             float* d = dwp + ((long)co * 9 + tap0 + t) * p.Ci + ci;
             *d = (p.add ? *d : 0.f) + acc[t][r];
         }
-    }
-}
-
-// dW[co][t][ci] += sum over the splits (in split order) of a task's tiles.  grid (9 * 16 blocks of 64 float4 groups, tasks, problems)
-// add == 0: the launch is the first writer of dW this step and stores 0.f + sum (no load of the destination)
-__global__ __launch_bounds__(256) void k_wgrad3_reduce(const float* __restrict__ part, const Wgrad3Multi m, int splits, int Ci, int ci_tiles, int add) {
-    __shared__ f32x4 sred[4][64];
-    const int gl = threadIdx.x & 63, sl = threadIdx.x >> 6;
-    const int g = blockIdx.x * 64 + gl;
-    const float* src = part + ((long)blockIdx.z * gridDim.y + blockIdx.y) * splits * W3_TILE_FLOATS;
-    f32x4 a = {0.f, 0.f, 0.f, 0.f};
-    int s = sl;
-    // eight loads in flight per thread, added in the lane's split order (two in flight made a lane's 64 slabs a chain of 32 dependent round
-    // trips: 18 us alone, 30-130 us beside the main stream's HBM-bound passes)
-    for (; s + 28 < splits; s += 32) {
-        f32x4 v[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = reinterpret_cast<const f32x4*>(src + (long)(s + 4 * k) * W3_TILE_FLOATS)[g];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) a = a + v[k];
-    }
-    for (; s + 4 < splits; s += 8) {
-        const f32x4 v0 = reinterpret_cast<const f32x4*>(src + (long)s * W3_TILE_FLOATS)[g];
-        const f32x4 v1 = reinterpret_cast<const f32x4*>(src + (long)(s + 4) * W3_TILE_FLOATS)[g];
-        a = (a + v0) + v1;
-    }
-    for (; s < splits; s += 4) a = a + reinterpret_cast<const f32x4*>(src + (long)s * W3_TILE_FLOATS)[g];
-    sred[sl][gl] = a;
-    __syncthreads();
-    if (sl != 0) return;
-    a = ((sred[0][gl] + sred[1][gl]) + sred[2][gl]) + sred[3][gl];
-    const int lane = g & 63, rq = (g >> 6) & 3, wave = (g >> 8) & 3, t = g >> 10;
-    const int cot = blockIdx.y / ci_tiles, cit = blockIdx.y - cot * ci_tiles;
-    const int ci = cit * 64 + (wave & 1) * 32 + (lane & 31);
-    const int co = cot * 64 + (wave >> 1) * 32 + 8 * rq + 4 * (lane >> 5);
-    float* dw = m.dw[blockIdx.z];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        float* d = dw + ((long)(co + k) * 9 + t) * Ci + ci;
-        *d = (add ? *d : 0.f) + a[k];
     }
 }
 
@@ -336,8 +371,22 @@ static int w3_fill_args(Wgrad3Args& a, int Nimg, int H, int W, int Ci, int Co) {
     return SVSR_OK;
 }
 
-static int w3_launch(const Wgrad3Args& a0, const Wgrad3Multi& m, int n, const W3Plan& pl, float* part, int64_t part_floats, hipStream_t stream) {
-    if (pl.splits > 1 && (part == nullptr || part_floats < (int64_t)n * pl.splits * pl.tasks * W3_TILE_FLOATS)) return SVSR_ERR_ARG;
+static int w3_launch_reduce(const float* part, const Wgrad3Multi& m, int n, int splits, int tasks, int Ci, int add, hipStream_t stream) {
+    hipLaunchKernelGGL(k_wgrad3_reduce, dim3(W3_RED_BLOCKS, tasks, n), dim3(256), 0, stream, part, m, splits, Ci, Ci >> 6, add);
+    return svsr_check_launch();
+}
+
+// pd: the slabs of an earlier launch the workgroups of this one add into their dW first (items == 0: none).  defer: this launch's own slabs
+// (splits > 1) stay in `part` for a later launch or svsr_conv3x3_wgrad_reduce; otherwise k_wgrad3_reduce follows.
+static int w3_launch(const Wgrad3Args& a0, const Wgrad3Multi& m, int n, const W3Plan& pl, float* part, int64_t part_floats, hipStream_t stream,
+                     const Wgrad3Pending& pd = Wgrad3Pending{}, bool defer = false) {
+    const int64_t own = pl.splits > 1 ? (int64_t)n * pl.splits * pl.tasks * W3_TILE_FLOATS : 0;
+    if (own && (part == nullptr || part_floats < own)) return SVSR_ERR_ARG;
+    if (pd.items > 0 && own) {            // the launch must not write where it still reads: the two slab sets are disjoint
+        const float* plo = pd.part;
+        const float* phi = pd.part + (int64_t)(pd.items / W3_RED_BLOCKS) * pd.splits * W3_TILE_FLOATS;
+        if (plo < part + own && part < phi) return SVSR_ERR_ARG;
+    }
     Wgrad3Args a = a0;
     a.total_chunks = pl.total_chunks; a.chunks_per_block = pl.chunks_per_block; a.splits = pl.splits; a.part = part;
     const bool w8 = svsr_tune_get(SVSR_TUNE_W3_WAVES) == 8;
@@ -351,14 +400,13 @@ static int w3_launch(const Wgrad3Args& a0, const Wgrad3Multi& m, int n, const W3
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_wgrad3x3_halo<8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         lds_set = lds;
     }
-    if (w8 && pl.dense) hipLaunchKernelGGL((k_wgrad3x3_halo<8, true>), dim3(pl.splits, pl.tasks, n), dim3(512), lds, stream, a, m);
-    else if (w8) hipLaunchKernelGGL((k_wgrad3x3_halo<8, false>), dim3(pl.splits, pl.tasks, n), dim3(512), lds, stream, a, m);
-    else if (pl.dense) hipLaunchKernelGGL((k_wgrad3x3_halo<4, true>), dim3(pl.splits, pl.tasks, n), dim3(256), lds, stream, a, m);
-    else hipLaunchKernelGGL((k_wgrad3x3_halo<4, false>), dim3(pl.splits, pl.tasks, n), dim3(256), lds, stream, a, m);
+    if (w8 && pl.dense) hipLaunchKernelGGL((k_wgrad3x3_halo<8, true>), dim3(pl.splits, pl.tasks, n), dim3(512), lds, stream, a, m, pd);
+    else if (w8) hipLaunchKernelGGL((k_wgrad3x3_halo<8, false>), dim3(pl.splits, pl.tasks, n), dim3(512), lds, stream, a, m, pd);
+    else if (pl.dense) hipLaunchKernelGGL((k_wgrad3x3_halo<4, true>), dim3(pl.splits, pl.tasks, n), dim3(256), lds, stream, a, m, pd);
+    else hipLaunchKernelGGL((k_wgrad3x3_halo<4, false>), dim3(pl.splits, pl.tasks, n), dim3(256), lds, stream, a, m, pd);
     int rc = svsr_check_launch();
-    if (rc != SVSR_OK || pl.splits <= 1) return rc;
-    hipLaunchKernelGGL(k_wgrad3_reduce, dim3(W3_TILE_FLOATS / 4 / 64, pl.tasks, n), dim3(256), 0, stream, (const float*)part, m, pl.splits, a.Ci, a.Ci >> 6, a.add);
-    return svsr_check_launch();
+    if (rc != SVSR_OK || pl.splits <= 1 || defer) return rc;
+    return w3_launch_reduce(part, m, n, pl.splits, pl.tasks, a.Ci, a.add, stream);
 }
 
 extern "C" int svsr_conv3x3_wgrad(const void* x, const void* dy, float* dw, int Nimg, int H, int W, int Ci, int Co, float* part,
@@ -369,12 +417,40 @@ extern "C" int svsr_conv3x3_wgrad(const void* x, const void* dy, float* dw, int 
 /* the same with the store / add mode of dw (include/syncvsr_hip.h SVSR_GRAD_ADD_DW) */
 extern "C" int svsr_conv3x3_wgrad_v2(const void* x, const void* dy, float* dw, int Nimg, int H, int W, int Ci, int Co, float* part,
                                      int64_t part_floats, int mode, hipStream_t stream) {
+    return svsr_conv3x3_wgrad_chain(x, dy, dw, Nimg, H, W, Ci, Co, part, part_floats, mode, 0, nullptr, nullptr, 0, 0, 0, 0, stream);
+}
+
+// the pending descriptor of a convolution with pend_splits slabs per task at pend_part; false: not a shape this file launches
+static bool w3_pending(Wgrad3Pending& pd, const float* pend_part, float* pend_dw, int pend_splits, int pend_Ci, int pend_Co, int pend_mode) {
+    if (pend_dw == nullptr || pend_splits < 2 || pend_Ci % 64 || pend_Co % 64 || pend_Ci <= 0 || pend_Co <= 0) return false;
+    if (pend_mode != 0 && pend_mode != SVSR_GRAD_ADD_DW) return false;
+    pd = Wgrad3Pending{};
+    pd.part = pend_part; pd.dw[0] = pend_dw; pd.splits = pend_splits; pd.Ci = pend_Ci; pd.ci_tiles = pend_Ci >> 6; pd.add = pend_mode != 0;
+    pd.tasks = (pend_Co / 64) * (pend_Ci / 64); pd.items = W3_RED_BLOCKS * pd.tasks;
+    return true;
+}
+
+/* the chained form (include/syncvsr_hip.h) */
+extern "C" int svsr_conv3x3_wgrad_chain(const void* x, const void* dy, float* dw, int Nimg, int H, int W, int Ci, int Co, float* part,
+                                        int64_t part_floats, int mode, int defer, const float* pend_part, float* pend_dw, int pend_splits,
+                                        int pend_Ci, int pend_Co, int pend_mode, hipStream_t stream) {
     if (mode != 0 && mode != SVSR_GRAD_ADD_DW) return SVSR_ERR_ARG;
     Wgrad3Args a;
     const int rc0 = w3_fill_args(a, Nimg, H, W, Ci, Co);
     if (rc0 != SVSR_OK) return rc0;
+    Wgrad3Pending pd{};
+    if (pend_part != nullptr && !w3_pending(pd, pend_part, pend_dw, pend_splits, pend_Ci, pend_Co, pend_mode)) return SVSR_ERR_ARG;
     a.x = (const bf16_t*)x; a.dy = (const bf16_t*)dy; a.dw = dw; a.add = mode != 0;
     Wgrad3Multi m{};
     m.x[0] = a.x; m.dy[0] = a.dy; m.dw[0] = dw;
-    return w3_launch(a, m, 1, w3_plan(Nimg, H, W, Ci, Co), part, part_floats, stream);
+    return w3_launch(a, m, 1, w3_plan(Nimg, H, W, Ci, Co), part, part_floats, stream, pd, defer != 0);
+}
+
+/* the stand-alone reduce of a deferred launch's slabs: the end of a chain */
+extern "C" int svsr_conv3x3_wgrad_reduce(const float* part, float* dw, int splits, int Ci, int Co, int mode, hipStream_t stream) {
+    Wgrad3Pending pd;
+    if (part == nullptr || !w3_pending(pd, part, dw, splits, Ci, Co, mode)) return SVSR_ERR_ARG;
+    Wgrad3Multi m{};
+    m.dw[0] = dw;
+    return w3_launch_reduce(part, m, 1, splits, pd.tasks, Ci, pd.add, stream);
 }

@@ -36,12 +36,13 @@ class _SideStream:
         # linear-layer weight gradients: neutral for the LRW encoder, a gain for the LRS linears (engine.TrainStep turns it on there)
         self.enabled_small = False
 
-    def run(self, fn, *keep, small: bool = False) -> None:
+    def run(self, fn, *keep, small: bool = False, behind_main: bool = True) -> None:
         """Issues fn on the side stream, behind what the main stream has issued so far: one cross-stream wait per call (an event record
         + wait: host time in eager mode; handing several functions over at once measured slower).  The tensors fn reads must not be
         written in place before join().  fn's launches go to the side stream through ops.STREAM_OVERRIDE, which is much cheaper on the
         host than entering a torch.cuda.stream() context per launch, but its allocations still come from the main stream's pool: no
-        tensor allocated inside fn may be freed before join() (keep it in `keep`, the tape or a result box)."""
+        tensor allocated inside fn may be freed before join() (keep it in `keep`, the tape or a result box).  behind_main=False: no
+        cross-stream wait — fn reads only what earlier launches of the side stream itself wrote."""
         if not (self.enabled or (small and self.enabled_small)):
             fn()
             return
@@ -51,7 +52,8 @@ class _SideStream:
             return
         if self.stream is None:
             self.stream = torch.cuda.Stream()
-        ops.stream_wait(self.stream, torch.cuda.current_stream())
+        if behind_main:
+            ops.stream_wait(self.stream, torch.cuda.current_stream())
         ops.STREAM_OVERRIDE = self.stream.cuda_stream
         self._issuing = True
         try:
@@ -131,9 +133,11 @@ class _StoreModule(nn.Module):
         self._drop_word: Optional[torch.Tensor] = None
         self._keep_grads = False    # accumulate_into_grads
         self._loss_scale = 1.0      # set_loss_scale
-        # state of one hand-written backward pass (_begin_backward drops what an aborted pass left in the first two)
+        # state of one hand-written backward pass (_begin_backward drops what an aborted pass left in the first four)
         self._wg_group: Optional[list] = None   # linear weight gradients awaiting one grouped launch: a backward sets [], _lin_wgrad appends, _flush_lin_wgrads issues
         self._deferred: list = []               # postponed parameter-gradient reductions: ops.add_ln_bwd / bias_act_bwd append (_defer_list), _flush_deferred issues
+        self._w3_pending: Optional[dict] = None # the trunk's last halo weight gradient, still slabs: _conv_wgrad hands it to the next halo launch, _flush_w3_chain ends the chain
+        self._ready_held: list = []             # gradient-ready notifications (offsets) waiting for the launch that carries _w3_pending: _ready appends, _release_ready issues
         self._early_sumsq = None                # engine.TrainStep: its optimiser state when no collective follows the backward; read by _frontend_backward
         self._metrics_on_side = False           # train_step_direct sets it around its forward; read by _LrwFunction.forward
         self._g_consts: Optional[tuple] = None
@@ -297,6 +301,8 @@ def _begin_backward(model: _StoreModule, st: "_ParamStore", dev: torch.device, *
     dropped, not issued: its closures hold that pass's tensors and would add into this pass's gradients."""
     model._wg_group = None
     model._deferred.clear()
+    model._w3_pending = None
+    model._ready_held.clear()
     if not model._keep_grads:
         st.zero_grad()
     st.rebind_grads()
@@ -880,6 +886,8 @@ def _frontend_backward(model, st: "_ParamStore", tape: dict, dfeats: torch.Tenso
         else:
             dx, dx_stats = ops.conv2d_dgrad(dc1, w1t, 3, stride, 1, in_hw, addend=dres), None
         _ready(model, st, f"{prefix}.conv1.weight")
+    # the chain ends here: its last reduce goes out right behind the last halo launch and runs beside the stem's light passes
+    _flush_w3_chain(model)
     ts = tape["stem"]
     if rec is not None:
         rec["stem"] = (dx.clone(), False)
@@ -919,7 +927,34 @@ _ABLATE: frozenset = frozenset()
 def _conv_wgrad(model, st: "_ParamStore", conv: str, t: dict, dc: torch.Tensor) -> None:
     if "conv_wgrad" in _ABLATE:
         return
+    if ops.halo_wgrad_ok(t["x"], dc, t["k"], t["stride"], t["pad"]):
+        # a link of the trunk's chain (ops.conv3x3_wgrad_chain): this launch adds the previous halo launch's slabs into that weight's gradient
+        # and leaves its own to the next one — a stand-alone reduce between two launches cannot become resident beside the main stream's
+        # persistent data-gradient kernels and held the side stream for their whole length
+        def link():
+            model._w3_pending = ops.conv3x3_wgrad_chain(t["x"], dc, st.g32(f"{conv}.weight"), model._w3_pending)
+        model._side.run(link, dc)
+        _release_ready(model)       # what waited for the carried sum is final behind this launch
+        return
     model._side.run(lambda: ops.conv2d_wgrad(t["x"], dc, st.g32(f"{conv}.weight"), t["k"], t["stride"], t["pad"]), dc)
+
+
+def _flush_w3_chain(model) -> None:
+    """Ends the chain of halo weight gradients: the last launch's slabs go through the stand-alone reduce, on the side stream."""
+    pending, model._w3_pending = model._w3_pending, None
+    if pending is not None:
+        # (its operands are the slabs the side stream's own last halo launch wrote: nothing of the main stream to wait for)
+        model._side.run(lambda: ops.conv3x3_wgrad_flush(pending), behind_main=False)
+    _release_ready(model)
+
+
+def _release_ready(model) -> None:
+    """Issues the gradient-ready notifications _ready held back, in their order."""
+    held, hook = model._ready_held, model.grad_ready_hook
+    if held and hook is not None:
+        for lo in held:
+            ops.host_callback(lambda lo=lo: hook(lo))
+    held.clear()
 
 
 def _lin_wgrad(model, x, dy, gw, gb, rows: int, K: int, N: int, x_pitch: int, dy_pitch: int) -> None:
@@ -965,6 +1000,11 @@ def _ready(model, st: "_ParamStore", name: Optional[str]) -> None:
     _flush_deferred(model)                    # postponed parameter-gradient reductions: to the side stream, once per layer
     if model.grad_ready_hook is not None:     # (the reducer's comm stream waits for the side stream itself: engine.GradReducer._reduce)
         hook, lo = model.grad_ready_hook, (0 if name is None else st.offsets[name][0])
+        if model._w3_pending is not None:
+            # a halo weight gradient above `lo` is still slabs: its sum is written by the launch that carries them (_conv_wgrad) or by the
+            # chain's flush, and the notification follows that launch — later than before, in the same order
+            model._ready_held.append(lo)
+            return
         ops.host_callback(lambda: hook(lo))   # a host-side step (collective): a segment boundary of a recorded step list
 
 

@@ -201,6 +201,7 @@ class StepRecorder:
         self.layer_groups = False
         self.skips: frozenset = frozenset()
         self.append_only = False
+        self.cur_group: Optional[int] = None      # the op group being recorded (group()), None outside every group
         # gradient accumulation (engine.TrainStep(accumulate=N > 1)): (zero group, tail group) — the zero-fill of the gradient buffer and the
         # optimiser tail as op groups numbered behind the layer-drop groups (ops.window_group); None: the list holds neither (N = 1)
         self.window: Optional[tuple] = None
@@ -251,10 +252,12 @@ class StepRecorder:
         recorded as always: the list issues them whatever is skipped."""
         _lib.check(self.lib.svsr_steplist_push_group(self.handle, int(n)), f"svsr_steplist_push_group({n})")
         self.append_only = n in self.skips
+        self.cur_group = int(n)
         try:
             yield
         finally:
             self.append_only = False
+            self.cur_group = None
             _lib.check(self.lib.svsr_steplist_push_group(self.handle, -1), "svsr_steplist_push_group(-1)")
 
     def passthrough(self, dst: torch.Tensor, src: torch.Tensor, group: int) -> None:
@@ -950,6 +953,59 @@ def halo_wgrad_ok(x: torch.Tensor, dy: torch.Tensor, k: int, stride: int, pad: i
     N, H, W, Ci = x.shape
     Co = dy.shape[-1]
     return HALO_WGRAD and k == 3 and stride == 1 and pad == 1 and W <= 29 and H * W >= 100 and Ci % 64 == 0 and Co % 64 == 0
+
+
+# The two slab sets of the chained halo weight gradient, per stream: launch i writes set i mod 2 while its workgroups add set (i - 1) mod 2
+# into the previous convolution's dW.  Not the per-stream scratch: other producers (the strided convolutions' weight gradients, the postponed
+# column sums) go through that between two launches of a chain.  Outgrown sets are kept alive like outgrown scratch.
+_W3_SETS: dict[tuple, torch.Tensor] = {}
+
+
+def _w3_set(which: int, nfloats: int) -> torch.Tensor:
+    key = (_stream(), which)
+    t = _W3_SETS.get(key)
+    if t is None or t.numel() < nfloats:
+        if t is not None:
+            _SCRATCH_KEEP.append(t)
+        t = _W3_SETS[key] = torch.empty(max(int(nfloats), 1 << 20), dtype=torch.float32, device="cuda")
+    return t
+
+
+def _w3_outside_groups(what: str) -> None:
+    if _REC is not None and _REC.cur_group is not None:
+        raise RuntimeError(f"{what} inside op group {_REC.cur_group} of a recorded step: a replay that skips the group would leave the chain's "
+                           "pending slabs un-added (flush the chain before the group)")
+
+
+def conv3x3_wgrad_chain(x: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor, pending: Optional[dict], mode: Optional[int] = None) -> Optional[dict]:
+    """The halo weight gradient of conv2d_wgrad (halo_wgrad_ok shapes) as a link of a chain on the current stream: the launch leaves its
+    split-K slabs un-added and returns them as a `pending` record; the NEXT call's launch — any geometry, any channel counts — adds them into
+    their dw in its prologue (same order of additions as the stand-alone reduce, same bits), and conv3x3_wgrad_flush ends the chain.  A dw is
+    final only behind the launch that carries its record.  -> the new record (None where the plan has one split: dw is written directly)."""
+    N, H, W, Ci = x.shape
+    Co = dy.shape[-1]
+    _w3_outside_groups("conv3x3_wgrad_chain")
+    if pending is not None and pending["stream"] != _stream():
+        raise RuntimeError("conv3x3_wgrad_chain: the pending slabs were written on another stream")
+    splits, nfl = _query("svsr_conv3x3_wgrad_plan", N, H, W, Ci, Co)
+    which = 0 if pending is None else 1 - pending["set"]
+    part = _w3_set(which, nfl) if nfl else None
+    add = _grad_add(dw, Co * 9 * Ci) if mode is None else mode & 1
+    pp = pending or dict(part=None, dw=None, splits=0, Ci=0, Co=0, add=0)
+    _call("svsr_conv3x3_wgrad_chain", _p(x), _p(dy), _p(dw), N, H, W, Ci, Co, _p(part), nfl, add, 1, _p(pp["part"]), _p(pp["dw"]), pp["splits"],
+          pp["Ci"], pp["Co"], pp["add"], _stream(), label="k_wgrad3x3_halo", flops=2.0 * N * H * W * Co * Ci * 9)
+    return dict(part=part, dw=dw, splits=splits, Ci=Ci, Co=Co, add=add, set=which, stream=_stream()) if splits > 1 else None
+
+
+def conv3x3_wgrad_flush(pending: Optional[dict]) -> None:
+    """Ends a chain: the stand-alone reduce of the last launch's slabs."""
+    if pending is None:
+        return
+    _w3_outside_groups("conv3x3_wgrad_flush")
+    if pending["stream"] != _stream():
+        raise RuntimeError("conv3x3_wgrad_flush: the pending slabs were written on another stream")
+    _call("svsr_conv3x3_wgrad_reduce", _p(pending["part"]), _p(pending["dw"]), pending["splits"], pending["Ci"], pending["Co"], pending["add"],
+          _stream(), label="k_wgrad3_reduce")
 
 
 def linear_fwd(x: torch.Tensor, w16: torch.Tensor, bias: Optional[torch.Tensor], *, rows: int, K: int, N: int, x_pitch: int,
