@@ -547,6 +547,38 @@ int svsr_wave_prep(const void* wave, int wave_i16, const int* len, const float* 
 int svsr_lrw_clip_sums(const void* src_u8, const int* params, float* frame_sums, int B, int T, int Hs, int Ws, int H, int W, int max_blocks, hipStream_t stream);
 int svsr_lrw_clip_mix(const void* src_u8, const int* params, const int* frame_src, const int* runs, const float* frame_sums, float* dst, int B, int T, int Hs, int Ws, int H, int W, int n_mask, int replace_with_zero, float mean, float std, int max_blocks, hipStream_t stream);
 
+/* Device-side training inputs of the DC-TCN word-level path (csrc/dctcn_prep.hip): the reference's LRWDatasetForDCTCN per clip
+ * (LRW/video/src/data.py:70-139: videos = 2 x / 255 - 1, _mask_frames, _trim_frames, then the transform chain, which divides by 255 a
+ * second time in front of Normalize) and the clip mixup of its module (lightning.py:264-270), in at most three launches per batch.
+ * src_u8: uint8 clips [B][T][Hs][Ws].
+ *
+ * svsr_dctcn_clip_sums: frame_sums uint32 [B][T], the exact integer sum of every STORED frame (Hs * Ws <= 2^24 keeps it in range).  One
+ * workgroup per frame up to 16384, the rest in a stride loop.  Needed only when some clip masks a run of positive length.
+ *
+ * svsr_dctcn_clip_mix: dst fp32 [B][1][T][H][W].  table: device int32 [B][9] = {top, left, h, w, flip, shift, trunc, mask_off, mask_len}
+ * per clip; the window as in svsr_clip_prep.  val(s, t), frame t of clip s in front of Normalize:
+ *     t >= trunc_s                                  0
+ *     ts = (t - shift_s) mod T in [mask_off_s, mask_off_s + mask_len_s)      m_s / 255, m_s = 2 S_s / (255 T Hs Ws) - 1, S_s the clip's T
+ *                                                   frame sums added in 64-bit integer (m_s in double, rounded once)
+ *     otherwise                                     (2 u / 255 - 1) / 255, u = stored frame ts sampled by csrc/clip_sample.h with clip s's
+ *                                                   window and flip
+ * dst[b][0][t] = (x - mean) / std with x = val(b, t) for lam == 0 and x = val(b, t) + lam (val(b', t) - val(b, t)), b' = (b - 1 + B) mod B,
+ * otherwise (torch.lerp(v, v.roll(1, 0), lam) for lam < 0.5).  frame_sums null: no frame is masked (every mask_len counts as 0).  trunc
+ * and mask_off are clamped into [0, T], mask_len into [0, T - mask_off], shift is reduced mod T: nothing outside src_u8 is read whatever the
+ * table holds.  Masked and trimmed frames are written without sampling.  One workgroup per (sample, frame, block of 32 rows) up to 16384,
+ * the rest in a stride loop; 16-byte stores where W % 4 == 0 and dst is 16-byte aligned.  Every element of dst is written once: the launch
+ * reads the clips once (twice with lam != 0) as uint8 and writes B * T * H * W * 4 bytes, HBM-bound on the write.
+ *
+ * svsr_dctcn_wave_trim: wave fp32 [B][L] -> out fp32 [B][L], table device int32 [B][2] = {ashift, azero}:
+ * out[b][i] = i < azero_b ? wave[b][(i - ashift_b) mod L] : 0; azero clamped into [0, L].  Out of place: out == wave is refused.
+ *
+ * No atomics; bit-identical from run to run and under any max_blocks (> 0 caps the grid: a test aid, 0 = the default grid).
+ * Bounds (SVSR_ERR_ARG): B, T, Hs, Ws, H, W >= 1, T <= 256, Hs * Ws, H * W and B * T <= 2^24, std > 0, 0 <= lam <= 0.5, 1 <= L <= 2^30,
+ * max_blocks >= 0, no null buffer but frame_sums of svsr_dctcn_clip_mix. */
+int svsr_dctcn_clip_sums(const void* src_u8, unsigned* frame_sums, int B, int T, int Hs, int Ws, int max_blocks, hipStream_t stream);
+int svsr_dctcn_clip_mix(const void* src_u8, const int* table, const unsigned* frame_sums, float* dst, int B, int T, int Hs, int Ws, int H, int W, float lam, float mean, float std, int max_blocks, hipStream_t stream);
+int svsr_dctcn_wave_trim(const float* wave, const int* table, float* out, int B, int L, int max_blocks, hipStream_t stream);
+
 /* ---- LRS (E2E: Conformer encoder + CTC / attention decoder) -----------------------------------------------------
  * Multi-head attention with 64-wide heads (mha.hip).  q rows [B*Lq] with pitch q_pitch (head h at column h*64), k/v rows
  * [B*Lk] with pitch kv_pitch; klen[b] = number of valid keys (null: all), causal != 0 masks j > i.  With pe != null the

@@ -308,3 +308,141 @@ class DeviceLRWPipeline:
         if cut is None:
             return videos, audios, labels, word_mask
         return (videos, *mix_small_tensors(cut, audios, labels, word_mask, self.num_labels, dev))
+
+
+class DeviceDCTCNPipeline:
+    """The DC-TCN training inputs on the device in at most three launches per batch: what the reference's LRWDatasetForDCTCN does per clip
+    in the loader workers (LRW/video/src/data.py:70-139) and the clip mixup of its module (lightning.py:264-270), from the stored uint8
+    crops [B, T, Hs, Ws], the fp32 waveforms [B, L] and a few host-drawn integers per clip (csrc/dctcn_prep.hip):
+      scaling        videos = 2 x / 255 - 1, and the transform chain divides by 255 a SECOND time in front of Normalize(mean, std) — a quirk a
+                     trained checkpoint depends on: every input lies in about [-2.575, -2.528];
+      _mask_frames   a run of randint(max_time_masks) frames becomes the mean of the whole stored clip;
+      _trim_frames   clip, waveform, word mask and attention mask are rolled in time by a drawn shift and zeroed behind a drawn length;
+      transform      RandomHorizontalFlip, RandomResizedCrop | Identity (train), CenterCrop | Resize (eval): DeviceClipPipeline.draw;
+      mixup          torch.lerp(videos, videos.roll(1, 0), lam) with the caller's lam (draw_lam).
+    svsr_dctcn_clip_sums writes the stored frames' integer sums (only when some clip masks a run of positive length), svsr_dctcn_clip_mix
+    the batch, svsr_dctcn_wave_trim the waveforms.  train=False is the reference's validation=True: no mask, no trim, no flip, and the
+    waveforms pass through — one launch.
+
+    `__call__(frames_u8, waves, labels, boundaries, lam)` returns the keyword arguments of DCTCNLightningModule.forward: videos fp32
+    [B, 1, T, H, W], audios fp32 [B, L], labels, word_mask and attention_mask int64 [B, T].  The videos are ALREADY mixed: hand the dict
+    to `loss_and_backend_grads(**batch, train_stats=True, lam=lam, videos_mixed=True)` with the same lam.
+
+    Draws, all on the host, per batch (`plan`): window and flip of every clip from the numpy generator seeded with `seed`
+    (DeviceClipPipeline.draw), then per clip in batch order from numpy's GLOBAL np.random, as the reference's dataset draws them:
+    length = randint(max_time_masks), offset = randint(T - length), truncated = randint(boundary, T),
+    off2 = randint(truncated - boundary + 1); shift = off2 - (T - boundary) // 2."""
+
+    def __init__(self, size: int, max_time_masks: int = 15, train: bool = True, use_rrc: bool = False, use_val_resize: bool = False,
+                 mean: float = 0.421, std: float = 0.165, seed: int = 0):
+        if train and int(max_time_masks) < 1:
+            raise ValueError("max_time_masks must be >= 1 (the reference draws randint(max_time_masks))")
+        self.clips = DeviceClipPipeline(size, train, use_rrc=use_rrc, use_val_resize=use_val_resize, mean=mean, std=std, seed=seed)
+        self.size, self.max_time_masks, self.train = int(size), int(max_time_masks), bool(train)
+        self.mean, self.std = float(mean), float(std)
+
+    @classmethod
+    def from_config(cls, config, train: bool, seed: int = 0) -> "DeviceDCTCNPipeline":
+        """From a dc-tcn configuration: data.input_size, data.max_time_masks (15 when absent), train.use_rrc and train.use_val_resize
+        (absent: off, as in the shipped dc-tcn-base.yaml).  train.use_timemask, the transform-level TimeMask on top of _mask_frames, is
+        not implemented."""
+        data, tr = config.get("data", {}), config.get("train", {})
+        if tr.get("use_timemask", False):
+            raise NotImplementedError("train.use_timemask: the transform-level TimeMask on top of the dataset's _mask_frames is not part of "
+                                      "DeviceDCTCNPipeline")
+        return cls(int(data["input_size"]), max_time_masks=int(data.get("max_time_masks", 15)), train=train, use_rrc=bool(tr.get("use_rrc", False)),
+                   use_val_resize=bool(tr.get("use_val_resize", False)), seed=seed)
+
+    @staticmethod
+    def draw_lam(alpha: float) -> float:
+        """The module's mixup weight (lightning.py:266), one draw per batch from numpy's global np.random: in [0, 0.5]."""
+        import numpy as np
+
+        return float(0.5 - abs(0.5 - np.random.beta(alpha, alpha)))
+
+    def plan(self, B: int, T: int, Hs: int, Ws: int, L: int, boundaries) -> dict:
+        """Every host decision of one batch: {"params": int32 [B, 5] = (top, left, h, w, flip), "time": int32 [B, 4] = (shift, trunc,
+        mask_off, mask_len), "audio": int32 [B, 2] = (ashift, azero)}.  boundaries: the word length of every clip in frames.  Raises
+        ValueError where the reference's own draw would (boundary >= T, T - length <= 0), at the draw that fails."""
+        import numpy as np
+
+        wbs = [int(v) for v in (boundaries.tolist() if hasattr(boundaries, "tolist") else boundaries)]
+        if len(wbs) != B:
+            raise ValueError(f"boundaries must hold one word length per clip: {B}")
+        params = self.clips.draw(B, Hs, Ws)
+        time, audio = np.zeros((B, 4), dtype=np.int32), np.zeros((B, 2), dtype=np.int32)
+        time[:, 1], audio[:, 1] = T, L
+        if self.train:
+            stride = T / L                                          # audio_stride of the reference: a Python float
+            for b, wb in enumerate(wbs):
+                length = int(np.random.randint(self.max_time_masks))
+                if T - length <= 0:
+                    raise ValueError(f"clip {b}: a mask run of {length} frames does not fit a clip of {T} (the reference's randint(T - length) raises)")
+                offset = int(np.random.randint(T - length))
+                if not 0 <= wb < T:
+                    raise ValueError(f"clip {b}: word boundary {wb} must lie in [0, {T}) (the reference's randint(boundary, T) raises)")
+                truncated = int(np.random.randint(wb, T))
+                off2 = int(np.random.randint(truncated - wb + 1))
+                shift = int(off2 - (T - wb) // 2)
+                time[b] = (shift, truncated, offset, length)
+                audio[b] = (int(shift / stride), int(truncated / stride))
+        return {"params": params, "time": torch.from_numpy(time), "audio": torch.from_numpy(audio)}
+
+    def __call__(self, frames_u8: torch.Tensor, waves: torch.Tensor, labels: torch.Tensor, boundaries, lam: float = 0.0,
+                 plan: Optional[dict] = None) -> dict:
+        import numpy as np
+
+        from . import ops
+
+        if frames_u8.dim() != 4 or frames_u8.dtype != torch.uint8:
+            raise ValueError("frames_u8 must be uint8 [B, T, Hs, Ws]")
+        B, T, Hs, Ws = frames_u8.shape
+        if not torch.is_tensor(waves) or not waves.is_floating_point():
+            raise ValueError("waves must be fp32 waveforms [B, L]: pre-tokenised audio cannot be trimmed here, because a waveform shifted by "
+                             "int(shift / (T / L)) samples is not a token row shifted by whole tokens — tokenise after the trim (attach_audio_codec)")
+        if waves.dtype != torch.float32 or waves.dim() != 2 or waves.shape[0] != B:
+            raise ValueError(f"waves must be fp32 [B, L] with B = {B}")
+        L = waves.shape[1]
+        if T > ops.DCTCN_CLIP_MAX_FRAMES:
+            raise ValueError(f"clips of {T} frames: the DC-TCN clip kernels take at most {ops.DCTCN_CLIP_MAX_FRAMES}")
+        lam = float(lam)
+        if not 0.0 <= lam <= 0.5:
+            raise ValueError("lam must lie in [0, 0.5] (draw_lam)")
+        wbs = np.asarray(boundaries.tolist() if hasattr(boundaries, "tolist") else boundaries, dtype=np.int64).reshape(-1)
+        if wbs.shape[0] != B or bool(((wbs < 0) | (wbs > T)).any()):
+            raise ValueError(f"boundaries must hold one word length in [0, {T}] per clip")
+        if plan is None:
+            plan = self.plan(B, T, Hs, Ws, L, wbs)
+        params, time, audio = plan["params"], plan["time"], plan["audio"]
+        if params.dtype != torch.int32 or params.shape != (B, 5) or time.dtype != torch.int32 or time.shape != (B, 4) or \
+                audio.dtype != torch.int32 or audio.shape != (B, 2):
+            raise ValueError("plan: params, time and audio must be int32 [B, 5], [B, 4] and [B, 2]")
+        top, left, h, w = (params[:, i] for i in range(4))
+        if bool(((top < 0) | (left < 0) | (h < 1) | (w < 1) | (top + h > Hs) | (left + w > Ws)).any()):
+            raise ValueError("crop window outside the stored frame")
+        shift, trunc, moff, mlen = (time[:, i].numpy().astype(np.int64) for i in range(4))
+        if bool(((trunc < 0) | (trunc > T)).any()):
+            raise ValueError("trim length outside the clip")
+        if bool(((moff < 0) | (mlen < 0) | (moff + mlen > T)).any()):
+            raise ValueError("frame-mask run outside the clip")
+        trimmed = bool((shift != 0).any() or (trunc != T).any() or (audio[:, 0] != 0).any() or (audio[:, 1] < L).any())
+        # the two [B, T] masks, on the host: the untrimmed word mask [(T - wb) // 2, + wb) rolled by shift, both zeroed from trunc on
+        t = np.arange(T, dtype=np.int64)[None, :]
+        ts = (t - shift[:, None]) % T
+        start = ((T - wbs) // 2)[:, None]
+        alive = t < trunc[:, None]
+        word = (alive & (ts >= start) & (ts < start + wbs[:, None])).astype(np.int32)
+        # every drawn integer and both masks in ONE upload: table [B, 9] | audio [B, 2] | word mask [B, T] | attention mask [B, T]
+        table = torch.cat([params, time], dim=1)
+        meta = torch.cat([table.reshape(-1), audio.reshape(-1), torch.from_numpy(word).reshape(-1), torch.from_numpy(alive.astype(np.int32)).reshape(-1)])
+        dev = frames_u8.device
+        meta = meta.to(dev, non_blocking=True)
+        table_d, audio_d = meta[: 9 * B].view(B, 9), meta[9 * B: 11 * B].view(B, 2)
+        masks = meta[11 * B:].view(2, B, T).long()
+        identity = self.clips.train and not self.clips.use_rrc          # nn.Identity: output size = stored size
+        H, W = (Hs, Ws) if identity else (self.size, self.size)
+        frames_u8 = frames_u8.contiguous()
+        sums = ops.dctcn_clip_sums(frames_u8) if bool((mlen > 0).any()) else None
+        videos = ops.dctcn_clip_mix(frames_u8, table_d, H, W, sums, lam, self.mean, self.std)
+        audios = ops.dctcn_wave_trim(waves.contiguous(), audio_d) if trimmed else waves
+        return {"videos": videos, "audios": audios, "labels": labels, "word_mask": masks[0], "attention_mask": masks[1]}

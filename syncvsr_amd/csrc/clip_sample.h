@@ -1,4 +1,5 @@
-// The sampling of the word-level clip kernels (k_clip_prep in loss_optim.hip; k_lrw_clip_sums / k_lrw_clip_mix in lrw_prep.hip): one stored
+// The sampling of the word-level clip kernels (k_clip_prep in loss_optim.hip; k_lrw_clip_sums / k_lrw_clip_mix in lrw_prep.hip;
+// k_dctcn_clip_mix in dctcn_prep.hip): one stored
 // uint8 frame, a crop window (top, left, h, w) resized to H x W with bilinear sampling (align_corners = False, no antialias, source
 // coordinates clamped to the window like torch's upsample_bilinear2d), the flip mirroring the output.
 // Every kernel that includes this header gets the SAME bits for a pixel: the fused multiply-adds are written out and the compiler's own
@@ -11,15 +12,20 @@
 
 struct ClipWindow { int top, left, ch, cw, flip; };
 
-// params [B][5] = {top, left, h, w, flip}; the window is clamped into the stored frame: no read outside it whatever the host drew
-__device__ __forceinline__ ClipWindow clip_window(const int* __restrict__ params, int b, int Hs, int Ws) {
-    int top = params[b * 5 + 0], left = params[b * 5 + 1], ch = params[b * 5 + 2], cw = params[b * 5 + 3];
-    const int flip = params[b * 5 + 4];
+// row = one clip's {top, left, h, w, flip}; the window is clamped into the stored frame: no read outside it whatever the host drew
+__device__ __forceinline__ ClipWindow clip_window_row(const int* __restrict__ row, int Hs, int Ws) {
+    int top = row[0], left = row[1], ch = row[2], cw = row[3];
+    const int flip = row[4];
     top = top < 0 ? 0 : (top > Hs - 1 ? Hs - 1 : top);
     left = left < 0 ? 0 : (left > Ws - 1 ? Ws - 1 : left);
     ch = ch < 1 ? 1 : (ch > Hs - top ? Hs - top : ch);
     cw = cw < 1 ? 1 : (cw > Ws - left ? Ws - left : cw);
     return ClipWindow{top, left, ch, cw, flip};
+}
+
+// params [B][5]: clip b's window
+__device__ __forceinline__ ClipWindow clip_window(const int* __restrict__ params, int b, int Hs, int Ws) {
+    return clip_window_row(params + b * 5, Hs, Ws);
 }
 
 // output pixel (y, x) of the H x W frame sampled from stored frame f [Hs][Ws]: a value in [0, 255] (x / 255 comes with clip_normalize)

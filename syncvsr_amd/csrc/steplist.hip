@@ -92,6 +92,7 @@ const std::unordered_map<std::string, Entry>& registry() {
         SVSR_REG(svsr_tconv_dgrad_ext), SVSR_REG(svsr_tconv_wgrad_ext), SVSR_REG(svsr_tcn_norm_pool_bwd_bs),
         SVSR_REG(svsr_lrs_clip_prep), SVSR_REG(svsr_wave_prep),
         SVSR_REG(svsr_lrw_clip_sums), SVSR_REG(svsr_lrw_clip_mix),
+        SVSR_REG(svsr_dctcn_clip_sums), SVSR_REG(svsr_dctcn_clip_mix), SVSR_REG(svsr_dctcn_wave_trim),
         SVSR_REG(svsr_vq_conv0_stats), SVSR_REG(svsr_vq_conv0_apply), SVSR_REG(svsr_vq_gn_partial), SVSR_REG(svsr_vq_gn_relu), SVSR_REG(svsr_vq_project),
         SVSR_REG(svsr_vq_assign),
     };

@@ -435,16 +435,18 @@ class DCTCNLightningModule(_StoreModule):
             self._put(*self._grad_of(st, bias, accumulate), dcb)
 
     def _loss_and_grads(self, videos, audios, labels, word_mask, attention_mask, loss_scale, accumulate, want_input_grad, feats=None,
-                        train_stats: bool = False, dropout_seed: Optional[int] = None, lam: float = 0.0):
+                        train_stats: bool = False, dropout_seed: Optional[int] = None, lam: float = 0.0, videos_mixed: bool = False):
         tape: dict[str, Any] = {}
         train = None
+        if videos_mixed and not train_stats:
+            raise ValueError("videos_mixed belongs to train_stats=True, like lam (the eval-statistics gradients have no mixup)")
         if train_stats:
             lam = float(lam)
             if not 0.0 <= lam <= 1.0:
                 raise ValueError("lam must lie in [0, 1]")
             p = float(self.config.model.dctcn.densetcn_options.get("dropout", 0.0)) if dropout_seed is not None else 0.0
             train = dict(lam=lam, seed=None if dropout_seed is None else int(dropout_seed), p=p)
-            if lam and feats is None:
+            if lam and feats is None and not videos_mixed:
                 videos = torch.lerp(videos.float(), videos.float().roll(1, 0), lam)          # (word boundaries are not mixed)
         elif dropout_seed is not None or float(lam) != 0.0:
             raise ValueError("dropout_seed and lam belong to train_stats=True (the eval-statistics gradients have no dropout and no mixup)")
@@ -462,7 +464,7 @@ class DCTCNLightningModule(_StoreModule):
     def loss_and_backend_grads(self, videos: torch.Tensor, audios: torch.Tensor, labels: torch.Tensor, word_mask: torch.Tensor,
                                attention_mask: torch.Tensor, loss_scale: float = 1.0, accumulate: bool = False,
                                want_input_grad: bool = False, train_stats: bool = False, dropout_seed: Optional[int] = None,
-                               lam: float = 0.0) -> dict[str, torch.Tensor]:
+                               lam: float = 0.0, videos_mixed: bool = False) -> dict[str, torch.Tensor]:
         """The eval forward (the same launches: the metrics are forward()'s bits) followed by the hand-written backward of the temporal network
         and the two heads: afterwards every parameter of backend_parameters() has .grad = d(loss_total * loss_scale)/d(param) in fp32
         (accumulate=True adds to an existing .grad).  The front-end and every BatchNorm running statistic are frozen and untouched.  With
@@ -474,9 +476,11 @@ class DCTCNLightningModule(_StoreModule):
         running_mean / running_var / num_batches_tracked are updated afterwards (momentum 0.1, unbiased variance).  The gradients carry the
         statistics' chain rule; a cbcr* conv bias cancels and its gradient is exact zeros.  dropout_seed: dropout0 / dropout1 of every dense
         layer with p = densetcn_options.dropout and the counter-based mask of dropout.py (sites: dropout.dctcn_sites).  lam: mixup, drawn by
-        the caller: videos lerp towards videos.roll(1, 0), both losses towards the rolled targets' (lightning.py:264-299)."""
+        the caller: videos lerp towards videos.roll(1, 0), both losses towards the rolled targets' (lightning.py:264-299).  videos_mixed=True
+        (train_stats only): the videos arrive already lerped with this lam (augment.DeviceDCTCNPipeline) and are taken as they are; the
+        losses still mix."""
         return self._loss_and_grads(videos, audios, labels, word_mask, attention_mask, loss_scale, accumulate, want_input_grad,
-                                    train_stats=train_stats, dropout_seed=dropout_seed, lam=lam)
+                                    train_stats=train_stats, dropout_seed=dropout_seed, lam=lam, videos_mixed=videos_mixed)
 
     def loss_and_backend_grads_from_features(self, feats: torch.Tensor, B: int, T: int, audios: torch.Tensor, labels: torch.Tensor,
                                              word_mask: torch.Tensor, attention_mask: torch.Tensor, loss_scale: float = 1.0,

@@ -1690,6 +1690,77 @@ def lrw_clip_mix(frames_u8: torch.Tensor, params: torch.Tensor, frame_src: torch
     return out
 
 
+DCTCN_CLIP_MAX_FRAMES = 256          # DT_MAXT of csrc/dctcn_prep.hip
+
+
+def _dctcn_clip_check(frames_u8: torch.Tensor) -> tuple[int, int, int, int]:
+    """The argument errors the two DC-TCN clip kernels share, raised before any launch."""
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or not frames_u8.is_contiguous():
+        raise ValueError("frames_u8 must be a contiguous uint8 tensor [B, T, Hs, Ws]")
+    B, T, Hs, Ws = frames_u8.shape
+    if T > DCTCN_CLIP_MAX_FRAMES:
+        raise ValueError(f"clips of {T} frames: the DC-TCN clip kernels take at most {DCTCN_CLIP_MAX_FRAMES}")
+    if B < 1 or T < 1 or min(Hs, Ws) < 1:
+        raise ValueError("empty batch, clip or frame")
+    return B, T, Hs, Ws
+
+
+def dctcn_clip_sums(frames_u8: torch.Tensor, max_blocks: int = 0) -> torch.Tensor:
+    """uint8 clips [B, T, Hs, Ws] -> [B, T], the exact integer sum of every stored frame (svsr_dctcn_clip_sums).  The values are uint32,
+    held in an int32 tensor: widen and mask with 0xFFFFFFFF to read them on the host (a frame of more than 2^23 bright pixels passes
+    2^31).  max_blocks > 0: a grid cap for tests (the result does not depend on it)."""
+    B, T, Hs, Ws = _dctcn_clip_check(frames_u8)
+    out = torch.empty((B, T), dtype=torch.int32, device=frames_u8.device)
+    _call("svsr_dctcn_clip_sums", _p(frames_u8), _p(out), B, T, Hs, Ws, int(max_blocks), _stream(),
+          label="k_dctcn_clip_sums", nbytes=float(frames_u8.numel() + 4 * out.numel()))
+    return out
+
+
+def dctcn_clip_mix(frames_u8: torch.Tensor, table: torch.Tensor, H: int, W: int, frame_sums: Optional[torch.Tensor] = None, lam: float = 0.0,
+                   mean: float = 0.421, std: float = 0.165, max_blocks: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 clips [B, T, Hs, Ws] + int32 table [B, 9] = (top, left, h, w, flip, shift, trunc, mask_off, mask_len) -> fp32 [B, 1, T, H, W]
+    (svsr_dctcn_clip_mix): the reference's DC-TCN scaling, frame mask, trim, crop / flip and Normalize of every clip, mixed with its batch
+    neighbour b - 1 at weight lam (0 <= lam <= 0.5; 0: no neighbour is read).  frame_sums = dctcn_clip_sums(frames_u8), or None when no
+    clip masks anything (mask runs are then ignored).  out: a contiguous fp32 [B, 1, T, H, W] to write into (any alignment).
+    max_blocks as in dctcn_clip_sums."""
+    B, T, Hs, Ws = _dctcn_clip_check(frames_u8)
+    H, W = int(H), int(W)
+    if table.dtype != torch.int32 or table.shape != (B, 9) or not table.is_contiguous():
+        raise ValueError(f"table must be a contiguous int32 tensor [B, 9] = {(B, 9)}")
+    if frame_sums is not None and (frame_sums.dtype != torch.int32 or frame_sums.shape != (B, T) or not frame_sums.is_contiguous()):
+        raise ValueError(f"frame_sums must be what dctcn_clip_sums returns: a contiguous int32 tensor [B, T] = {(B, T)}")
+    if min(H, W) < 1:
+        raise ValueError("empty batch, clip or frame")
+    if not 0.0 <= float(lam) <= 0.5:
+        raise ValueError("lam must lie in [0, 0.5]")
+    if not float(std) > 0.0:
+        raise ValueError("std must be positive")
+    if out is None:
+        out = torch.empty((B, 1, T, H, W), dtype=torch.float32, device=frames_u8.device)
+    elif out.dtype != torch.float32 or out.shape != (B, 1, T, H, W) or not out.is_contiguous() or out.device != frames_u8.device:
+        raise ValueError(f"out must be a contiguous fp32 tensor {(B, 1, T, H, W)} on the clips' device")
+    _call("svsr_dctcn_clip_mix", _p(frames_u8), _p(table), _p(frame_sums), _p(out), B, T, Hs, Ws, H, W, float(lam), float(mean), float(std),
+          int(max_blocks), _stream(), label="k_dctcn_clip_mix", nbytes=float((2 if lam else 1) * frames_u8.numel() + 4 * out.numel()))
+    return out
+
+
+def dctcn_wave_trim(wave: torch.Tensor, table: torch.Tensor, max_blocks: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 waveforms [B, L] + int32 table [B, 2] = (ashift, azero) -> fp32 [B, L]: out[b, i] = wave[b, (i - ashift) mod L] for i < azero,
+    0 behind (svsr_dctcn_wave_trim; out of place).  max_blocks as in dctcn_clip_sums."""
+    if wave.dtype != torch.float32 or wave.dim() != 2 or not wave.is_contiguous() or wave.numel() == 0:
+        raise ValueError("wave must be a contiguous, non-empty fp32 tensor [B, L]")
+    B, L = wave.shape
+    if table.dtype != torch.int32 or table.shape != (B, 2) or not table.is_contiguous():
+        raise ValueError(f"table must be a contiguous int32 tensor [B, 2] = {(B, 2)}")
+    if out is None:
+        out = torch.empty_like(wave)
+    elif out.dtype != torch.float32 or out.shape != wave.shape or not out.is_contiguous() or out.data_ptr() == wave.data_ptr():
+        raise ValueError("out must be a contiguous fp32 tensor of wave's shape and must not be wave itself")
+    _call("svsr_dctcn_wave_trim", _p(wave), _p(table), _p(out), B, L, int(max_blocks), _stream(), label="k_dctcn_wave_trim",
+          nbytes=float(8 * wave.numel()))
+    return out
+
+
 def wave_prep(wave: torch.Tensor, lengths: torch.Tensor, noise: Optional[torch.Tensor] = None, nstart: Optional[torch.Tensor] = None,
               snr_db: Optional[torch.Tensor] = None, eps: float = 1e-8, max_blocks: int = 0) -> torch.Tensor:
     """wave fp32 or int16 [B, Spad] (int16 counts as v / 32768), lengths int32 [B] -> fp32 [B, Spad]: per clip over its real samples,
