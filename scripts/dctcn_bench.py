@@ -224,7 +224,7 @@ def main() -> None:
     if a.backward:
         return backward_leg(a)
     from syncvsr_amd import ops
-    from syncvsr_amd.dctcn import DCTCNLightningModule
+    from syncvsr_amd.dctcn import DCTCNLightningModule, _RunningStats
     from syncvsr_amd.dctcn_init import dctcn_dims, dctcn_init_state_dict, dctcn_synthetic_batch, default_dctcn_config
 
     dev = torch.device("cuda:0")
@@ -242,7 +242,7 @@ def main() -> None:
 
         def hip_backend(feats):
             with torch.no_grad():
-                stack = model._backend(st, feats, wm, B, T)
+                stack = model._backend(_RunningStats(model, st), feats, wm, B, T)
                 h, pooled = ops.tcn_norm_pool_fwd(stack, *model._prep["norm5"], am.contiguous(), B=B, T=T, C=C)
                 return ops.linear_fwd(pooled, st.s16("video_classifier.weight"), st.p32("video_classifier.bias"), rows=B, K=C, N=model.dims["classes"],
                                       x_pitch=C, out_f32=True)[0]

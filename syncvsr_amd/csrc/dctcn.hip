@@ -197,14 +197,17 @@ __global__ __launch_bounds__(256) void k_tconv(TArgs a) {
     }
 }
 
-// branches: HOST table of nb x 8 64-bit words {k, w, gate, scale, shift, slope, out_off, res_off} (read during the call only)
+// branches: HOST table of nb x 8 64-bit words {k, w, gate, scale, shift, slope, out_off, res_off} (read during the call only).
+// mode TC_EXT (svsr_tconv_fwd_ext): the launch's axis is the extended one, T + 2 * hmax rows a clip over the T-row input; the accumulators are
+// the only output, so there is no out and only k, w and gate of a table row are read (the other words may be zero).  hmax is 0 otherwise.
 static int tconv_launch(const void* x, int64_t x_pitch, int B, int T, int n_in, int d, int nb, const int64_t* branches, int co, int act,
-                        void* out, int64_t out_pitch, const void* res, int64_t res_pitch, int res_act, float* save, int64_t save_pitch, bool saving,
-                        hipStream_t stream) {
-    if (saving && (save == nullptr || save_pitch < (int64_t)nb * co)) return SVSR_ERR_ARG;
-    if (x == nullptr || out == nullptr || branches == nullptr) return SVSR_ERR_ARG;
+                        void* out, int64_t out_pitch, const void* res, int64_t res_pitch, int res_act, float* save, int64_t save_pitch, int mode,
+                        int hmax, hipStream_t stream) {
+    const bool ext = mode == TC_EXT;
+    if (mode != TC_PLAIN && (save == nullptr || save_pitch < (int64_t)nb * co)) return SVSR_ERR_ARG;
+    if (x == nullptr || branches == nullptr || (!ext && out == nullptr) || hmax < 0 || hmax > TC_HALO) return SVSR_ERR_ARG;
     if (B < 1 || T < 1 || d < 1 || n_in < 64 || n_in % 64 != 0 || x_pitch < n_in || x_pitch % 8 != 0 || ((uintptr_t)x & 15) != 0) return SVSR_ERR_ARG;
-    if (nb < 1 || nb > 3 || co < TC_BN || co % TC_BN != 0 || out_pitch < co) return SVSR_ERR_ARG;
+    if (nb < 1 || nb > 3 || co < TC_BN || co % TC_BN != 0 || (!ext && out_pitch < co)) return SVSR_ERR_ARG;
     if (act != SVSR_ACT_NONE && act != SVSR_ACT_RELU && act != SVSR_ACT_SWISH && act != TC_ACT_PRELU) return SVSR_ERR_ARG;
     if (res_act != SVSR_ACT_NONE && res_act != SVSR_ACT_SWISH) return SVSR_ERR_ARG;
     if (res != nullptr && res_pitch < co) return SVSR_ERR_ARG;
@@ -221,38 +224,43 @@ static int tconv_launch(const void* x, int64_t x_pitch, int B, int T, int n_in, 
         br.slope = (const float*)(uintptr_t)e[5];
         br.out_off = (int)e[6];
         br.res_off = (int)e[7];
-        if (!tc_taps_ok(e[0], d)) return SVSR_ERR_ARG;
-        if (br.w == nullptr || ((uintptr_t)br.w & 15) != 0 || br.scale == nullptr || br.shift == nullptr) return SVSR_ERR_ARG;
+        if (!tc_taps_ok(e[0], d) || (ext && (e[0] - 1) * (int64_t)d / 2 > hmax)) return SVSR_ERR_ARG;
+        if (br.w == nullptr || ((uintptr_t)br.w & 15) != 0) return SVSR_ERR_ARG;
         if (br.gate != nullptr && ((uintptr_t)br.gate & 15) != 0) return SVSR_ERR_ARG;
+        if (br.k > kmax) kmax = br.k;
+        if (ext) {          // (the other table words are not read: the kernel gets null / 0 for them)
+            br.scale = nullptr; br.shift = nullptr; br.slope = nullptr; br.out_off = 0; br.res_off = 0;
+            continue;
+        }
+        if (br.scale == nullptr || br.shift == nullptr) return SVSR_ERR_ARG;
         if (act == TC_ACT_PRELU && br.slope == nullptr) return SVSR_ERR_ARG;
         if (e[6] < 0 || e[6] + co > out_pitch) return SVSR_ERR_ARG;
         if (res != nullptr && (e[7] < 0 || e[7] + co > res_pitch)) return SVSR_ERR_ARG;
-        if (br.k > kmax) kmax = br.k;
     }
-    if (!tc_geometry(B, T, &a.n_tt, &a.slots) || co / TC_BN > 65535) return SVSR_ERR_ARG;
+    if (!tc_geometry(B, T + 2 * hmax, &a.n_tt, &a.slots) || co / TC_BN > 65535) return SVSR_ERR_ARG;
     a.x = (const bf16_t*)x; a.out = (bf16_t*)out; a.res = (const bf16_t*)res;
     a.x_pitch = x_pitch; a.out_pitch = out_pitch; a.res_pitch = res_pitch;
-    a.B = B; a.T = T; a.n_in = n_in; a.d = d; a.act = act; a.res_act = res_act;
-    a.save = save; a.save_pitch = save_pitch; a.co = co; a.T_src = T; a.shift = 0;
+    a.B = B; a.T = T + 2 * hmax; a.n_in = n_in; a.d = d; a.act = act; a.res_act = res_act;
+    a.save = save; a.save_pitch = save_pitch; a.co = co; a.T_src = T; a.shift = hmax;
     const dim3 grid((unsigned)((a.slots + TC_SLOTS - 1) / TC_SLOTS), (unsigned)(co / TC_BN), (unsigned)nb);
+    void (*const fn)(TArgs) = ext ? k_tconv<TC_EXT> : mode == TC_SAVE ? k_tconv<TC_SAVE> : k_tconv<TC_PLAIN>;
     size_t lds;
-    const hipError_t ae = tc_dynamic_lds(saving ? reinterpret_cast<const void*>(k_tconv<TC_SAVE>) : reinterpret_cast<const void*>(k_tconv<TC_PLAIN>), kmax, &lds);
+    const hipError_t ae = tc_dynamic_lds(reinterpret_cast<const void*>(fn), kmax, &lds);
     if (ae != hipSuccess) return (int)ae;
-    if (saving) hipLaunchKernelGGL(k_tconv<TC_SAVE>, grid, dim3(256), lds, stream, a);
-    else hipLaunchKernelGGL(k_tconv<TC_PLAIN>, grid, dim3(256), lds, stream, a);
+    hipLaunchKernelGGL(fn, grid, dim3(256), lds, stream, a);
     return svsr_check_launch();
 }
 
 extern "C" int svsr_tconv_fwd(const void* x, int64_t x_pitch, int B, int T, int n_in, int d, int nb, const int64_t* branches, int co, int act,
                               void* out, int64_t out_pitch, const void* res, int64_t res_pitch, int res_act, hipStream_t stream) {
-    return tconv_launch(x, x_pitch, B, T, n_in, d, nb, branches, co, act, out, out_pitch, res, res_pitch, res_act, nullptr, 0, false, stream);
+    return tconv_launch(x, x_pitch, B, T, n_in, d, nb, branches, co, act, out, out_pitch, res, res_pitch, res_act, nullptr, 0, TC_PLAIN, 0, stream);
 }
 
 // svsr_tconv_fwd that also stores every fp32 accumulator: acc[b*T + t][i * co + c] for branch i (acc_pitch >= nb * co)
 extern "C" int svsr_tconv_fwd_save(const void* x, int64_t x_pitch, int B, int T, int n_in, int d, int nb, const int64_t* branches, int co, int act,
                                    void* out, int64_t out_pitch, const void* res, int64_t res_pitch, int res_act, float* acc, int64_t acc_pitch,
                                    hipStream_t stream) {
-    return tconv_launch(x, x_pitch, B, T, n_in, d, nb, branches, co, act, out, out_pitch, res, res_pitch, res_act, acc, acc_pitch, true, stream);
+    return tconv_launch(x, x_pitch, B, T, n_in, d, nb, branches, co, act, out, out_pitch, res, res_pitch, res_act, acc, acc_pitch, TC_SAVE, 0, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -927,20 +935,30 @@ extern "C" int svsr_tcn_se_bwd(const void* x, int64_t x_pitch, int B, int T, int
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// norm5 + masked mean backward: g[b][t][c] = dh[b][t][c] + dpooled[b][c] * mask[b][t] / (sum_t mask + 1e-6);  dx = bf16(g * scale[c]);
-// part[b][0][c] = sum_t g, part[b][1][c] = sum_t g * x (t ascending), folded over the clips in order into sums [2][C].
+// norm5 + masked mean backward: g[b][t][c] = dh[b][t][c] + dpooled[b][c] * mask[b][t] / (sum_t mask + 1e-6), then
+//   running statistics (BS false): dx = bf16(g * scale[c]);  part[b][0][c] = sum_t g, part[b][1][c] = sum_t g * x (t ascending), folded over
+//     the clips in order into sums [2][C];
+//   batch statistics (BS true): dx = bf16(scale * (g - ca - xhat * cb)), xhat = (x - mean) * invstd, with ca, cb from the first launch's sums;
+//     no sums of its own.
 // ---------------------------------------------------------------------------------------------------------------------
+template <bool BS>
 __global__ __launch_bounds__(256) void k_tcn_norm_pool_bwd(const bf16_t* __restrict__ dh, const bf16_t* __restrict__ dpooled, const bf16_t* __restrict__ x,
                                                            long x_pitch, int B, int T, int C, const float* __restrict__ scale,
+                                                           const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                           const float* __restrict__ ca, const float* __restrict__ cb,
                                                            const float* __restrict__ mask, bf16_t* __restrict__ dx, long dx_pitch, float* __restrict__ part) {
     const int pieces = C >> 3;
     const long p = (long)blockIdx.x * 256 + threadIdx.x;
     if (p >= (long)B * pieces) return;
     const int b = (int)(p / pieces), c0 = (int)(p - (long)b * pieces) * 8;
-    float sc[8], dp[8], s0[8], s1[8];
+    float sc[8], dp[8], mu[8], is[8], a0[8], b0[8], s0[8], s1[8];
     unpack8(*reinterpret_cast<const u32x4*>(dpooled + (long)b * C + c0), dp);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) { sc[i] = scale[c0 + i]; s0[i] = 0.f; s1[i] = 0.f; }
+    for (int i = 0; i < 8; ++i) {
+        sc[i] = scale[c0 + i];
+        if (BS) { mu[i] = mean[c0 + i]; is[i] = invstd[c0 + i]; a0[i] = ca[c0 + i]; b0[i] = cb[c0 + i]; }
+        else { s0[i] = 0.f; s1[i] = 0.f; }
+    }
     float msum = 0.f;
     for (int t = 0; t < T; ++t) msum += mask[(long)b * T + t];
     const float inv = 1.0f / (msum + 1e-6f);
@@ -953,12 +971,16 @@ __global__ __launch_bounds__(256) void k_tcn_norm_pool_bwd(const bf16_t* __restr
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             g[i] = __builtin_fmaf(dp[i], m, g[i]);
-            s0[i] += g[i];
-            s1[i] = __builtin_fmaf(g[i], xv[i], s1[i]);
-            g[i] *= sc[i];
+            if (BS) g[i] = sc[i] * ((g[i] - a0[i]) - (xv[i] - mu[i]) * is[i] * b0[i]);
+            else {
+                s0[i] += g[i];
+                s1[i] = __builtin_fmaf(g[i], xv[i], s1[i]);
+                g[i] *= sc[i];
+            }
         }
         *reinterpret_cast<u32x4*>(dx + row * dx_pitch + c0) = pack8(g);
     }
+    if (BS) return;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         part[((long)b * 2) * C + c0 + i] = s0[i];
@@ -966,19 +988,35 @@ __global__ __launch_bounds__(256) void k_tcn_norm_pool_bwd(const bf16_t* __restr
     }
 }
 
-extern "C" int svsr_tcn_norm_pool_bwd(const void* dh, const void* dpooled, const void* x, int64_t x_pitch, int B, int T, int C, const float* scale,
-                                      const float* mask, void* dx, int64_t dx_pitch, float* part, float* sums, hipStream_t stream) {
-    if (dh == nullptr || dpooled == nullptr || x == nullptr || scale == nullptr || mask == nullptr || dx == nullptr || part == nullptr || sums == nullptr)
-        return SVSR_ERR_ARG;
+// Both entry points' checks and launch; bs: mean / invstd / ca / cb are read, part is not
+static int norm_pool_bwd_launch(bool bs, const void* dh, const void* dpooled, const void* x, int64_t x_pitch, int B, int T, int C, const float* scale,
+                                const float* mean, const float* invstd, const float* ca, const float* cb, const float* mask, void* dx,
+                                int64_t dx_pitch, float* part, hipStream_t stream) {
+    if (dh == nullptr || dpooled == nullptr || x == nullptr || scale == nullptr || mask == nullptr || dx == nullptr) return SVSR_ERR_ARG;
     if (B < 1 || T < 1 || C < 8 || C % 8 != 0 || x_pitch < C || x_pitch % 8 != 0 || dx_pitch < C || dx_pitch % 8 != 0) return SVSR_ERR_ARG;
     if ((((uintptr_t)dh | (uintptr_t)dpooled | (uintptr_t)x | (uintptr_t)dx) & 15) != 0) return SVSR_ERR_ARG;
     const long n = (long)B * (C >> 3);
     if (n > (1L << 36)) return SVSR_ERR_ARG;
-    hipLaunchKernelGGL(k_tcn_norm_pool_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const bf16_t*)dh, (const bf16_t*)dpooled,
-                       (const bf16_t*)x, (long)x_pitch, B, T, C, scale, mask, (bf16_t*)dx, (long)dx_pitch, part);
-    int rc = svsr_check_launch();
+    hipLaunchKernelGGL(bs ? k_tcn_norm_pool_bwd<true> : k_tcn_norm_pool_bwd<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
+                       (const bf16_t*)dh, (const bf16_t*)dpooled, (const bf16_t*)x, (long)x_pitch, B, T, C, scale, mean, invstd, ca, cb, mask, (bf16_t*)dx,
+                       (long)dx_pitch, part);
+    return svsr_check_launch();
+}
+
+extern "C" int svsr_tcn_norm_pool_bwd(const void* dh, const void* dpooled, const void* x, int64_t x_pitch, int B, int T, int C, const float* scale,
+                                      const float* mask, void* dx, int64_t dx_pitch, float* part, float* sums, hipStream_t stream) {
+    if (part == nullptr || sums == nullptr) return SVSR_ERR_ARG;
+    int rc = norm_pool_bwd_launch(false, dh, dpooled, x, x_pitch, B, T, C, scale, nullptr, nullptr, nullptr, nullptr, mask, dx, dx_pitch, part, stream);
     if (rc != SVSR_OK) return rc;
     return svsr_tcn_fold(part, B, 2L * C, sums, 0, stream);
+}
+
+// norm5 under batch statistics (ca, cb from svsr_tcn_norm_pool_bwd's sums)
+extern "C" int svsr_tcn_norm_pool_bwd_bs(const void* dh, const void* dpooled, const void* x, int64_t x_pitch, int B, int T, int C, const float* scale,
+                                         const float* mean, const float* invstd, const float* ca, const float* cb, const float* mask, void* dx,
+                                         int64_t dx_pitch, hipStream_t stream) {
+    if (mean == nullptr || invstd == nullptr || ca == nullptr || cb == nullptr) return SVSR_ERR_ARG;
+    return norm_pool_bwd_launch(true, dh, dpooled, x, x_pitch, B, T, C, scale, mean, invstd, ca, cb, mask, dx, dx_pitch, nullptr, stream);
 }
 
 // =====================================================================================================================
@@ -1006,34 +1044,8 @@ static bool xgeo_make(XGeo* g, int T, int hmax, int co, int nb, const int* h) {
 // rows u.  branches: svsr_tconv_fwd's table; k, w and gate are read.
 extern "C" int svsr_tconv_fwd_ext(const void* x, int64_t x_pitch, int B, int T, int n_in, int d, int nb, const int64_t* branches, int co, int hmax,
                                   float* acc, int64_t acc_pitch, hipStream_t stream) {
-    if (x == nullptr || acc == nullptr || branches == nullptr) return SVSR_ERR_ARG;
-    if (B < 1 || T < 1 || d < 1 || n_in < 64 || n_in % 64 != 0 || x_pitch < n_in || x_pitch % 8 != 0 || ((uintptr_t)x & 15) != 0) return SVSR_ERR_ARG;
-    if (nb < 1 || nb > 3 || co < TC_BN || co % TC_BN != 0 || acc_pitch < (int64_t)nb * co || hmax < 0 || hmax > TC_HALO) return SVSR_ERR_ARG;
-    TArgs a;
-    int kmax = 1;
-    for (int i = 0; i < 3; ++i) {
-        const int64_t* e = branches + 8 * (i < nb ? i : 0);
-        TBranch& br = a.br[i];
-        br.k = (int)e[0];
-        br.w = (const bf16_t*)(uintptr_t)e[1];
-        br.gate = (const float*)(uintptr_t)e[2];
-        br.scale = nullptr; br.shift = nullptr; br.slope = nullptr; br.out_off = 0; br.res_off = 0;
-        if (!tc_taps_ok(e[0], d) || (e[0] - 1) * (int64_t)d / 2 > hmax) return SVSR_ERR_ARG;
-        if (br.w == nullptr || ((uintptr_t)br.w & 15) != 0) return SVSR_ERR_ARG;
-        if (br.gate != nullptr && ((uintptr_t)br.gate & 15) != 0) return SVSR_ERR_ARG;
-        if (br.k > kmax) kmax = br.k;
-    }
-    if (!tc_geometry(B, T + 2 * hmax, &a.n_tt, &a.slots) || co / TC_BN > 65535) return SVSR_ERR_ARG;
-    a.x = (const bf16_t*)x; a.out = nullptr; a.res = nullptr;
-    a.x_pitch = x_pitch; a.out_pitch = 0; a.res_pitch = 0;
-    a.B = B; a.T = T + 2 * hmax; a.n_in = n_in; a.d = d; a.act = SVSR_ACT_NONE; a.res_act = SVSR_ACT_NONE;
-    a.save = acc; a.save_pitch = acc_pitch; a.co = co; a.T_src = T; a.shift = hmax;
-    const dim3 grid((unsigned)((a.slots + TC_SLOTS - 1) / TC_SLOTS), (unsigned)(co / TC_BN), (unsigned)nb);
-    size_t lds;
-    const hipError_t ae = tc_dynamic_lds(reinterpret_cast<const void*>(k_tconv<TC_EXT>), kmax, &lds);
-    if (ae != hipSuccess) return (int)ae;
-    hipLaunchKernelGGL(k_tconv<TC_EXT>, grid, dim3(256), lds, stream, a);
-    return svsr_check_launch();
+    return tconv_launch(x, x_pitch, B, T, n_in, d, nb, branches, co, SVSR_ACT_NONE, nullptr, 0, nullptr, 0, SVSR_ACT_NONE, acc, acc_pitch, TC_EXT, hmax,
+                        stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1295,52 +1307,5 @@ extern "C" int svsr_tconv_bn_bwd(const void* dy, int64_t dy_pitch, const float* 
     a.dacc = (bf16_t*)dacc; a.dacc_pitch = dacc_pitch;
     const long erows = (long)B * a.g.T_ext;
     hipLaunchKernelGGL(k_tconv_bn_bwd, dim3((unsigned)((erows + EB_ROWS - 1) / EB_ROWS), (unsigned)(C / 64)), dim3(256), 0, stream, a);
-    return svsr_check_launch();
-}
-
-// norm5 under batch statistics: k_tcn_norm_pool_bwd's g with the statistics' chain rule, dx = bf16(scale * (g - ca - xhat * cb)),
-// xhat = (x - mean) * invstd (ca, cb from svsr_tcn_norm_pool_bwd's sums)
-__global__ __launch_bounds__(256) void k_tcn_norm_pool_bwd_bs(const bf16_t* __restrict__ dh, const bf16_t* __restrict__ dpooled, const bf16_t* __restrict__ x,
-                                                              long x_pitch, int B, int T, int C, const float* __restrict__ scale,
-                                                              const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                              const float* __restrict__ ca, const float* __restrict__ cb,
-                                                              const float* __restrict__ mask, bf16_t* __restrict__ dx, long dx_pitch) {
-    const int pieces = C >> 3;
-    const long p = (long)blockIdx.x * 256 + threadIdx.x;
-    if (p >= (long)B * pieces) return;
-    const int b = (int)(p / pieces), c0 = (int)(p - (long)b * pieces) * 8;
-    float sc[8], dp[8], mu[8], is[8], a0[8], b0[8];
-    unpack8(*reinterpret_cast<const u32x4*>(dpooled + (long)b * C + c0), dp);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { sc[i] = scale[c0 + i]; mu[i] = mean[c0 + i]; is[i] = invstd[c0 + i]; a0[i] = ca[c0 + i]; b0[i] = cb[c0 + i]; }
-    float msum = 0.f;
-    for (int t = 0; t < T; ++t) msum += mask[(long)b * T + t];
-    const float inv = 1.0f / (msum + 1e-6f);
-    for (int t = 0; t < T; ++t) {
-        const long row = (long)b * T + t;
-        float g[8], xv[8];
-        unpack8(*reinterpret_cast<const u32x4*>(dh + row * C + c0), g);
-        unpack8(*reinterpret_cast<const u32x4*>(x + row * x_pitch + c0), xv);
-        const float m = mask[row] * inv;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            g[i] = __builtin_fmaf(dp[i], m, g[i]);
-            g[i] = sc[i] * ((g[i] - a0[i]) - (xv[i] - mu[i]) * is[i] * b0[i]);
-        }
-        *reinterpret_cast<u32x4*>(dx + row * dx_pitch + c0) = pack8(g);
-    }
-}
-
-extern "C" int svsr_tcn_norm_pool_bwd_bs(const void* dh, const void* dpooled, const void* x, int64_t x_pitch, int B, int T, int C, const float* scale,
-                                         const float* mean, const float* invstd, const float* ca, const float* cb, const float* mask, void* dx,
-                                         int64_t dx_pitch, hipStream_t stream) {
-    if (dh == nullptr || dpooled == nullptr || x == nullptr || scale == nullptr || mask == nullptr || dx == nullptr) return SVSR_ERR_ARG;
-    if (mean == nullptr || invstd == nullptr || ca == nullptr || cb == nullptr) return SVSR_ERR_ARG;
-    if (B < 1 || T < 1 || C < 8 || C % 8 != 0 || x_pitch < C || x_pitch % 8 != 0 || dx_pitch < C || dx_pitch % 8 != 0) return SVSR_ERR_ARG;
-    if ((((uintptr_t)dh | (uintptr_t)dpooled | (uintptr_t)x | (uintptr_t)dx) & 15) != 0) return SVSR_ERR_ARG;
-    const long n = (long)B * (C >> 3);
-    if (n > (1L << 36)) return SVSR_ERR_ARG;
-    hipLaunchKernelGGL(k_tcn_norm_pool_bwd_bs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const bf16_t*)dh, (const bf16_t*)dpooled,
-                       (const bf16_t*)x, (long)x_pitch, B, T, C, scale, mean, invstd, ca, cb, mask, (bf16_t*)dx, (long)dx_pitch);
     return svsr_check_launch();
 }

@@ -10,6 +10,14 @@ the full-padding convolutions too), dropout0 / dropout1, mixup; the front-end st
 raises NotImplementedError (the front-end backward, engine.TrainStep and the OneCycle schedule are not built): it never runs a wrong forward
 silently.
 
+ONE WALK, TWO STAGE SETS.  ``_backend`` is the only function that walks the network forward (transition0 -> per dense layer: SE gates, first
+stage, downsample, second stage -> transitions) and ``_backward`` the only one that walks it back; both serve every entry point in either
+statistics mode.  What depends on the mode sits below the walks, in two small classes with one signature per function: ``_RunningStats`` and
+``_BatchStats`` each hold a stage forward, a stage backward, norm5's coefficients and norm5's data gradient.  ``_run`` picks the set once per
+call; the walks never ask which one they hold.  A stage's static description (kernel sizes, dilation, widths, parameter names, forward
+branch tables, transposed shadows) is built once in ``_prepare`` / ``_prepare_bwd``; a taped forward leaves one record per stage under
+``tape["rec"]`` (keys ``"t0"``, ``(layer, 0)``, ``(layer, 1)``, ``("tr", block)``, ``"norm5"``).
+
 Back-end layout (csrc/dctcn.hip): channels-last bf16 rows; ONE [B*T, reduced + layers * growth] buffer per dense block is the feature
 stack (a layer reads a channel prefix through the row pitch and writes its channels at an offset: no ``torch.cat``).  Per layer: one launch
 for the three gates (svsr_tcn_se_fwd), one for the three gated first-stage branches, one for the 1x1 downsample, one for the three
@@ -157,6 +165,34 @@ class DCTCNLightningModule(_StoreModule):
             return out
         return w.contiguous()
 
+    def _stage(self, st: _ParamStore, convs, *, n_in: int, co: int, d: int, act: int, out_off: int = 0, pad_to: Optional[int] = None, slope=None,
+               drop_site: Optional[str] = None) -> dict:
+        """The static description of one convolution stage, built once and read by both walks and both statistics modes.  convs: per branch
+        (k, conv, BatchNorm, conv bias or None) by parameter name; branch j writes channels [out_off + j * co, out_off + (j + 1) * co) of the
+        stage's output rows.  branches: what ops.tconv_fwd takes (the folded running-statistic scale / shift included); _prepare_bwd adds the
+        transposed shadows (wt) and the stage-wide scale / shift vectors."""
+        brs = []
+        for j, (k, conv, bn, bias) in enumerate(convs):
+            sc, sh = self._bn_affine(st, bn, bias)
+            brs.append(dict(k=k, w=self._w16(st, f"{conv}.weight", pad_to), scale=sc, shift=sh, slope=slope, out_off=out_off + j * co, res_off=j * co))
+        return dict(ks=[c[0] for c in convs], d=d, co=co, n_in=n_in, act=act, slope=slope, out_off=out_off, drop_site=drop_site, branches=brs,
+                    weights=[f"{c[1]}.weight" for c in convs], norms=[c[2] for c in convs], biases=[c[3] for c in convs])
+
+    @staticmethod
+    def _stages(P: dict):
+        yield P["t0"]
+        for L in P["layers"]:
+            yield from L["stages"]
+        yield from P["trans"].values()
+
+    @staticmethod
+    def _fold_stage(D: dict) -> None:
+        """The stage-wide BatchNorm(eval) vectors the epilogue backward reads: the branches' scale / shift side by side."""
+        brs = D["branches"]
+        one = len(brs) == 1
+        D["scale"] = brs[0]["scale"] if one else torch.cat([br["scale"] for br in brs]).contiguous()
+        D["shift"] = brs[0]["shift"] if one else torch.cat([br["shift"] for br in brs]).contiguous()
+
     def _prepare(self, st: _ParamStore, fold: bool = True) -> dict:
         """fold=False (the batch-statistic path): the folded running-statistic coefficients are not needed; after a train_stats step they are
         stale (P["folded"] False) and only a caller that reads them pays for folding them again (_refold)."""
@@ -167,34 +203,27 @@ class DCTCNLightningModule(_StoreModule):
         st.refresh_shadows()
         st.shadow_fresh = True          # eval only: nothing but load_state_dict / mark_params_dirty changes a weight
         dm, dev = self.dims, st.device
-        ks = dm["ks"]
+        ks, R = dm["ks"], dm["reduced"]
         P: dict[str, Any] = {}
         p = f"{TCN}.transition0"
         self.in_pad = (dm["in_size"] + 63) // 64 * 64
-        sc, sh = self._bn_affine(st, f"{p}.norm", None)
-        P["t0"] = dict(k=1, w=self._w16(st, f"{p}.conv.weight", self.in_pad), scale=sc, shift=sh, slope=st.p32(f"{p}.prelu.weight"), out_off=0)
+        P["t0"] = self._stage(st, [(1, f"{p}.conv", f"{p}.norm", None)], n_in=self.in_pad, co=R, d=1, act=ops.ACT_PRELU, pad_to=self.in_pad,
+                              slope=st.p32(f"{p}.prelu.weight"))
         layers, trans = dctcn_layers(self.config)
-        P["layers"] = []
+        P["layers"], li = [], 0
         for p, n_in, g, d, bi in layers:
             gb = g // len(ks)
-            L: dict[str, Any] = dict(n_in=n_in, g=g, gb=gb, d=d, bi=bi)
+            li = li + 1 if P["layers"] and P["layers"][-1]["bi"] == bi else 1
+            L: dict[str, Any] = dict(p=p, n_in=n_in, g=g, bi=bi)
             L["se_w1"] = torch.stack([st.s16(f"{p}.cbcr0_se_{i}.fc.0.weight").view(n_in // SE_REDUCTION, n_in) for i in range(len(ks))]).contiguous()
             L["se_w2"] = torch.stack([st.s16(f"{p}.cbcr0_se_{i}.fc.2.weight").view(n_in, n_in // SE_REDUCTION) for i in range(len(ks))]).contiguous()
-            for stage in (0, 1):
-                brs = []
-                for i, k in enumerate(ks):
-                    c = f"{p}.cbcr{stage}_{i}.net"
-                    sc, sh = self._bn_affine(st, f"{c}.1", f"{c}.0.bias")
-                    brs.append(dict(k=k, w=self._w16(st, f"{c}.0.weight"), scale=sc, shift=sh, out_off=(i * gb if stage == 0 else n_in + i * gb),
-                                    res_off=i * gb))
-                L[f"stage{stage}"] = brs
+            L["stages"] = [self._stage(st, [(k, f"{p}.cbcr{s}_{i}.net.0", f"{p}.cbcr{s}_{i}.net.1", f"{p}.cbcr{s}_{i}.net.0.bias") for i, k in enumerate(ks)],
+                                       n_in=g if s else n_in, co=gb, d=d, act=ops.ACT_SWISH, out_off=n_in if s else 0,
+                                       drop_site=f"block{bi + 1}.layer{li}.drop{s}") for s in (0, 1)]
             L["down"] = dict(k=1, w=self._w16(st, f"{p}.downsample.weight"), scale=torch.ones(g, dtype=torch.float32, device=dev),
                              shift=st.p32(f"{p}.downsample.bias"), out_off=0)
             P["layers"].append(L)
-        P["trans"] = {}
-        for name, n, bi in trans:
-            sc, sh = self._bn_affine(st, f"{name}.norm", None)
-            P["trans"][bi] = dict(k=1, w=self._w16(st, f"{name}.conv.weight"), scale=sc, shift=sh, out_off=0, n_in=n)
+        P["trans"] = {bi: self._stage(st, [(1, f"{name}.conv", f"{name}.norm", None)], n_in=n, co=R, d=1, act=ops.ACT_SWISH) for name, n, bi in trans}
         P["norm5"] = self._bn_affine(st, f"{TCN}.norm5", None)
         P["folded"] = True
         self._prep = P
@@ -202,52 +231,40 @@ class DCTCNLightningModule(_StoreModule):
 
     def _refold(self, st: _ParamStore, P: dict) -> None:
         """The BatchNorm(eval) coefficients of _prepare again, from the current running statistics; weights and shadows are kept."""
-        ks = self.dims["ks"]
-        layers, trans = dctcn_layers(self.config)
-        P["t0"]["scale"], P["t0"]["shift"] = self._bn_affine(st, f"{TCN}.transition0.norm", None)
-        for (p, _, _, _, _), L in zip(layers, P["layers"]):
-            for stage in (0, 1):
-                for i in range(len(ks)):
-                    c = f"{p}.cbcr{stage}_{i}.net"
-                    L[f"stage{stage}"][i]["scale"], L[f"stage{stage}"][i]["shift"] = self._bn_affine(st, f"{c}.1", f"{c}.0.bias")
-        for name, _, bi in trans:
-            P["trans"][bi]["scale"], P["trans"][bi]["shift"] = self._bn_affine(st, f"{name}.norm", None)
+        for D in self._stages(P):
+            for br, bn, bias in zip(D["branches"], D["norms"], D["biases"]):
+                br["scale"], br["shift"] = self._bn_affine(st, bn, bias)
+            if "bwd" in P:
+                self._fold_stage(D)
         P["norm5"] = self._bn_affine(st, f"{TCN}.norm5", None)
-        if "bwd" in P:
-            for q, L in zip(P["bwd"]["layers"], P["layers"]):
-                for stage in (0, 1):
-                    q[f"scale{stage}"] = torch.cat([br["scale"] for br in L[f"stage{stage}"]]).contiguous()
-                    q[f"shift{stage}"] = torch.cat([br["shift"] for br in L[f"stage{stage}"]]).contiguous()
         P["folded"] = True
 
     # ------------------------------------------------------------------------------------------------
-    @staticmethod
-    def _tconv(tape: Optional[dict], key, x, *, co, branches, **kw):
-        """ops.tconv_fwd; with a tape the same kernel's saving instantiation: the fp32 accumulators are kept under tape["acc"][key]."""
-        if tape is None:
-            return ops.tconv_fwd(x, co=co, branches=branches, **kw)
-        acc = torch.empty((x.shape[0], len(branches) * co), dtype=torch.float32, device=x.device)
-        tape["acc"][key] = acc
-        return ops.tconv_fwd(x, co=co, branches=branches, acc=acc, **kw)
+    def _x0(self, feats: torch.Tensor, word_mask: Optional[torch.Tensor], B: int, T: int) -> torch.Tensor:
+        """transition0's input rows: the features, with use_boundary the word-boundary column beside them (zero-padded to in_pad)."""
+        if not self.use_boundary:
+            return feats
+        if word_mask is None:
+            raise ValueError("use_boundary: word_mask [B, T] is required")
+        x0 = torch.zeros((B * T, self.in_pad), dtype=BF16, device=feats.device)
+        x0[:, :512] = feats
+        x0[:, 512] = word_mask.reshape(B * T).to(BF16)
+        return x0
 
-    def _backend(self, st: _ParamStore, feats: torch.Tensor, word_mask: Optional[torch.Tensor], B: int, T: int, keep: Optional[dict] = None,
+    def _backend(self, S, feats: torch.Tensor, word_mask: Optional[torch.Tensor], B: int, T: int, keep: Optional[dict] = None,
                  tape: Optional[dict] = None):
-        """feats bf16 [B*T, 512] -> the last block's feature stack bf16 [B*T, C] (before norm5).  tape: what the backward reads is kept."""
-        P, dm, dev = self._prepare(st), self.dims, feats.device
+        """feats bf16 [B*T, 512] -> the last block's feature stack bf16 [B*T, C] (before norm5): THE forward walk of the network.  S: the stage
+        set of the call's statistics mode (_RunningStats / _BatchStats); with a tape what the backward reads is kept, one record per stage under
+        tape["rec"]: "t0", (layer, 0), (layer, 1), ("tr", block), and "norm5" (_run)."""
+        P, dm, dev, rec = self._prepare(S.st, fold=S.folds), self.dims, feats.device, None
         if tape is not None:
-            tape.update(acc={}, layers=[], stacks=[])
+            rec = {}
+            tape.update(rec=rec, layers=[], stacks=[], stats=S)          # (the set holds the model and the store, never the tape)
         R = dm["reduced"]
-        if self.use_boundary:
-            if word_mask is None:
-                raise ValueError("use_boundary: word_mask [B, T] is required")
-            x0 = torch.zeros((B * T, self.in_pad), dtype=BF16, device=dev)
-            x0[:, :512] = feats
-            x0[:, 512] = word_mask.reshape(B * T).to(BF16)
-        else:
-            x0 = feats
+        x0 = self._x0(feats, word_mask, B, T)
         width = lambda bi: R + dm["blocks"][bi] * dm["growth"][bi]          # noqa: E731
         stack = torch.empty((B * T, width(0)), dtype=BF16, device=dev)
-        self._tconv(tape, "t0", x0, B=B, T=T, n_in=x0.shape[1], d=1, branches=[P["t0"]], co=R, act=ops.ACT_PRELU, out=stack)
+        S.stage(rec, "t0", P["t0"], x0, stack, B=B, T=T)
         if tape is not None:
             tape["x0"] = x0
             tape["stacks"].append(stack)
@@ -255,24 +272,21 @@ class DCTCNLightningModule(_StoreModule):
             keep["transition0"] = stack[:, :R].float().view(B, T, R)
         nlayers = len(P["layers"])
         for i, L in enumerate(P["layers"]):
-            n_in, g, gb, d, bi = L["n_in"], L["g"], L["gb"], L["d"], L["bi"]
+            n_in, g, bi = L["n_in"], L["g"], L["bi"]
             gates = ops.tcn_se_fwd(stack, L["se_w1"], L["se_w2"], B=B, T=T, n_in=n_in)
             out0 = torch.empty((B * T, g), dtype=BF16, device=dev)
-            self._tconv(tape, (i, 0), stack, B=B, T=T, n_in=n_in, d=d, branches=[dict(br, gate=gates[j]) for j, br in enumerate(L["stage0"])], co=gb,
-                        act=ops.ACT_SWISH, out=out0)
+            S.stage(rec, (i, 0), L["stages"][0], stack, out0, B=B, T=T, gates=gates)
             res = torch.empty((B * T, g), dtype=BF16, device=dev)
             ops.tconv_fwd(stack, B=B, T=T, n_in=n_in, d=1, branches=[L["down"]], co=g, act=ops.ACT_NONE, out=res)
-            self._tconv(tape, (i, 1), out0, B=B, T=T, n_in=g, d=d, branches=L["stage1"], co=gb, act=ops.ACT_SWISH, out=stack, res=res,
-                        res_act=ops.ACT_SWISH)
+            S.stage(rec, (i, 1), L["stages"][1], out0, stack, B=B, T=T, res=res, res_act=ops.ACT_SWISH)
             if tape is not None:
                 tape["layers"].append(dict(stack=stack, gates=gates, out0=out0, res=res))
             if i + 1 == nlayers or P["layers"][i + 1]["bi"] != bi:
                 if keep is not None:
                     keep[f"denseblock{bi + 1}"] = stack.float().view(B, T, -1)
                 if bi in P["trans"]:
-                    tr = P["trans"][bi]
                     nxt = torch.empty((B * T, width(bi + 1)), dtype=BF16, device=dev)
-                    self._tconv(tape, ("tr", bi), stack, B=B, T=T, n_in=tr["n_in"], d=1, branches=[tr], co=R, act=ops.ACT_SWISH, out=nxt)
+                    S.stage(rec, ("tr", bi), P["trans"][bi], stack, nxt, B=B, T=T)
                     stack = nxt
                     if tape is not None:
                         tape["stacks"].append(stack)
@@ -281,7 +295,8 @@ class DCTCNLightningModule(_StoreModule):
     def _run(self, videos: torch.Tensor, word_mask, attention_mask, keep: Optional[dict] = None, tape: Optional[dict] = None,
              feats: Optional[torch.Tensor] = None, train: Optional[dict] = None):
         """feats (bf16 [B*T, 512], with videos = the (B, T) pair): the front-end is skipped (loss_and_backend_grads_from_features).
-        train (loss_and_backend_grads(train_stats=True)): the back-end runs on batch statistics (_backend_bs); the front-end does not."""
+        train (loss_and_backend_grads(train_stats=True)): the back-end runs on batch statistics (_BatchStats); the front-end does not.  The
+        statistics mode is picked here, once per call; the walks only call the stage set."""
         if self.training:
             raise NotImplementedError("DCTCNLightningModule: a forward under .train() is not built (the front-end has no backward yet): call .eval() "
                                       "first; the back-end trains through loss_and_backend_grads(train_stats=True)")
@@ -297,17 +312,14 @@ class DCTCNLightningModule(_StoreModule):
             if feats.dtype != BF16 or tuple(feats.shape) != (B * T, 512) or not feats.is_contiguous():
                 raise ValueError("features must be a contiguous bf16 [B*T, 512] tensor")
         st = self.store()
-        self._prepare(st, fold=train is None)
+        S = _RunningStats(self, st) if train is None else _BatchStats(self, st, train)
+        self._prepare(st, fold=S.folds)
         C = self.dims["out_size"]
         with torch.no_grad():
             if feats is None:
                 feats = _frontend_forward(self, st, {}, videos.float().contiguous(), False)
-            if train is None:
-                stack = self._backend(st, feats, word_mask, B, T, keep, tape)
-                scale, shift = self._prep["norm5"]
-            else:
-                stack = self._backend_bs(st, feats, word_mask, B, T, tape, train)
-                scale, shift = self._norm5_bs(st, stack, B, T, tape)
+            stack = self._backend(S, feats, word_mask, B, T, keep, tape)
+            scale, shift = S.norm5(None if tape is None else tape["rec"], stack, B, T)
             if attention_mask is None:
                 attention_mask = torch.ones((B, T), dtype=torch.float32, device=src.device)
             mask = attention_mask.to(torch.float32).contiguous()
@@ -368,34 +380,29 @@ class DCTCNLightningModule(_StoreModule):
         return {"loss_total": loss_total, "loss_category": loss_c, "loss_audio": loss_a, "accuracy_top1": acc[0], "accuracy_top5": acc[1]}
 
     # ------------------------------------------------------------------------------------------------
-    # backward of the back-end and the two heads (statistics mode of the eval forward: running-statistic BatchNorm, no dropout, lam = 0)
+    # backward of the back-end and the two heads, in the statistics mode its forward ran in
     # ------------------------------------------------------------------------------------------------
     def backend_parameters(self) -> list:
         """The nn.Parameters loss_and_backend_grads fills: everything but the front-end, in state-dict order."""
         return [p for n, p in self.named_parameters() if self._fwd_rank(n) == 2]
 
     def _prepare_bwd(self, st: _ParamStore, fold: bool = True) -> dict:
-        """Transposed, tap-flipped shadows for the data gradients and the per-stage BatchNorm vectors (rebuilt with _prepare's)."""
+        """Transposed, tap-flipped shadows for the data gradients and the stage-wide BatchNorm vectors, stored with each stage's description
+        (rebuilt with _prepare's); -> the heads' transposed weights."""
         P = self._prepare(st, fold)
         if "bwd" in P:
             return P["bwd"]
-        ks, dev = self.dims["ks"], st.device
+        dev = st.device
         wt = lambda name: ops.tconv_wt(st.s16(name).view(st.offsets[name][2]))          # noqa: E731
-        Q: dict[str, Any] = dict(layers=[], trans={})
-        t0 = f"{TCN}.transition0.conv.weight"
-        w = torch.zeros((self.in_pad, 1, self.dims["reduced"]), dtype=BF16, device=dev)
-        w[: self.dims["in_size"]] = wt(t0)
-        Q["t0_wt"] = w
-        layers, trans = dctcn_layers(self.config)
-        for (p, n_in, g, d, bi), L in zip(layers, P["layers"]):
-            q: dict[str, Any] = dict(p=p, down_wt=wt(f"{p}.downsample.weight"))
-            for stage in (0, 1):
-                q[f"wt{stage}"] = [wt(f"{p}.cbcr{stage}_{i}.net.0.weight") for i in range(len(ks))]
-                q[f"scale{stage}"] = torch.cat([br["scale"] for br in L[f"stage{stage}"]]).contiguous()
-                q[f"shift{stage}"] = torch.cat([br["shift"] for br in L[f"stage{stage}"]]).contiguous()
-            Q["layers"].append(q)
-        for name, n, bi in trans:
-            Q["trans"][bi] = dict(name=name, wt=wt(f"{name}.conv.weight"))
+        Q: dict[str, Any] = {}
+        for D in self._stages(P):
+            D["wt"] = [wt(name) for name in D["weights"]]
+            self._fold_stage(D)
+        w = torch.zeros((self.in_pad, 1, self.dims["reduced"]), dtype=BF16, device=dev)          # transition0's, zero rows for the padding
+        w[: self.dims["in_size"]] = P["t0"]["wt"][0]
+        P["t0"]["wt"] = [w]
+        for L in P["layers"]:
+            L["down_wt"] = wt(f"{L['p']}.downsample.weight")
 
         def head_t(name):                    # [N, K] -> [K, N padded to 64] for ops.linear_dgrad
             N, K = st.offsets[name][2]
@@ -452,10 +459,8 @@ class DCTCNLightningModule(_StoreModule):
             raise ValueError("dropout_seed and lam belong to train_stats=True (the eval-statistics gradients have no dropout and no mixup)")
         out = self._losses(videos, audios, labels, word_mask, attention_mask, tape, feats, train)
         with torch.no_grad():
-            if train is None:
-                gf = self._backward(tape, float(loss_scale), bool(accumulate), bool(want_input_grad))
-            else:
-                gf = self._backward_bs(tape, float(loss_scale), bool(accumulate), bool(want_input_grad))
+            gf = self._backward(tape, float(loss_scale), bool(accumulate), bool(want_input_grad))
+            if train is not None:
                 self._update_running(tape)
         if want_input_grad:
             out["grad_features"] = gf
@@ -492,23 +497,10 @@ class DCTCNLightningModule(_StoreModule):
         return self._loss_and_grads((int(B), int(T)), audios, labels, word_mask, attention_mask, loss_scale, accumulate, want_input_grad, feats,
                                     train_stats=train_stats, dropout_seed=dropout_seed, lam=lam)
 
-    def _stage_bwd(self, st: _ParamStore, accumulate: bool, dy, acc, scale, shift, x, convs, *, B: int, T: int, n_in: int, co: int, d: int,
-                   gates=None, **epi):
-        """Backward of one convolution stage short of its data gradient: the epilogue backward over all branches (epi: act, slope, res, res_act
-        of ops.tconv_epi_bwd), then per branch j — convs[j] = (k, conv weight, BatchNorm, conv bias or None), channels [j * co, (j + 1) * co) —
-        the BatchNorm / bias gradients and the weight gradient over the stage's input rows x.  -> (dacc, dres, sums)"""
-        dacc, dres, sums = ops.tconv_epi_bwd(dy, acc, scale, shift, rows=B * T, C=len(convs) * co, **epi)
-        for j, (k, weight, bn, bias) in enumerate(convs):
-            self._bn_grads(st, accumulate, sums, bn, bias, j * co, (j + 1) * co)
-            gw, add = self._grad_of(st, weight, accumulate)
-            ops.tconv_wgrad(x, dacc[:, j * co: (j + 1) * co], gw, B=B, T=T, n_in=n_in, co=co, k=k, d=d, gate=None if gates is None else gates[j],
-                            add=add)
-        return dacc, dres, sums
-
     def _heads_backward(self, tape: dict, loss_scale: float, accumulate: bool):
         """The two heads' parameter gradients -> (dh bf16 [B*T, C], dpooled bf16 [B, C]): the gradients of norm5's output and of the pooled row."""
         st: _ParamStore = tape["st"]
-        Q, dm = self._prepare_bwd(st, fold="bs" not in tape), self.dims
+        Q, dm = self._prepare_bwd(st, fold=tape["stats"].folds), self.dims
         B, T, dev = tape["B"], tape["T"], st.device
         rows, C = B * T, dm["out_size"]
         A, G, V, NC = self.audio_alignment, self.vq_groups, self.audio_vocab_size, dm["classes"]
@@ -544,71 +536,63 @@ class DCTCNLightningModule(_StoreModule):
         dpooled = ops.linear_dgrad(dlc, Q["wc_t"], rows=B, N=NC, K=C, dy_pitch=NCp)
         return dh, dpooled
 
+    def _dgrad(self, tape: dict, key, D: dict, dacc: torch.Tensor, *, B: int, T: int, out: torch.Tensor, gates=None, **kw):
+        """The data gradient of stage `key` from the gradient of its accumulators (extended by the record's hmax under batch statistics;
+        without a halo, as under running statistics, svsr_tconv_dgrad itself)."""
+        brs = [dict(k=k, wt=D["wt"][j], dy_off=j * D["co"], gate=None if gates is None else gates[j]) for j, k in enumerate(D["ks"])]
+        return ops.tconv_dgrad(dacc, B=B, T=T, co=D["co"], d=D["d"], n_out=D["n_in"], out=out, branches=brs, hmax=tape["rec"][key]["hmax"] or None, **kw)
+
     def _backward(self, tape: dict, loss_scale: float, accumulate: bool, want_input_grad: bool):
-        st: _ParamStore = tape["st"]
-        P, Q, dm = self._prepare(st), self._prepare_bwd(st), self.dims
+        """THE backward walk: the forward's in reverse, through the stage set the forward ran with (tape["stats"])."""
+        S, rec = tape["stats"], tape["rec"]
+        st: _ParamStore = S.st
+        P, dm = self._prepare(st, fold=S.folds), self.dims
+        self._prepare_bwd(st, fold=S.folds)
         B, T, dev = tape["B"], tape["T"], st.device
-        rows, C, R, ks = B * T, dm["out_size"], dm["reduced"], dm["ks"]
+        rows, R, nb = B * T, dm["reduced"], len(dm["ks"])
         grad = lambda name: self._grad_of(st, name, accumulate)          # noqa: E731
         dh, dpooled = self._heads_backward(tape, loss_scale, accumulate)
         # norm5 + masked mean
         stacks = tape["stacks"]
-        scale5, _ = P["norm5"]
-        dS = torch.empty_like(stacks[-1])
-        _, sums = ops.tcn_norm_pool_bwd(dh, dpooled, stacks[-1], scale5, tape["mask"], B=B, T=T, C=C, out=dS)
-        self._bn_grads(st, accumulate, sums, f"{TCN}.norm5", None)
+        dS = S.norm5_bwd(rec.get("norm5"), dh, dpooled, stacks[-1], tape["mask"], accumulate, B=B, T=T)
         # dense blocks, last to first; dS: the gradient of the current block's feature stack
         for i in range(len(P["layers"]) - 1, -1, -1):
-            L, q, t = P["layers"][i], Q["layers"][i], tape["layers"][i]
-            n_in, g, gb, d, bi, p = L["n_in"], L["g"], L["gb"], L["d"], L["bi"], q["p"]
+            L, t = P["layers"][i], tape["layers"][i]
+            n_in, g, bi, p, (D0, D1) = L["n_in"], L["g"], L["bi"], L["p"], L["stages"]
             stack = t["stack"]
-            convs = lambda stage: [(k, f"{p}.cbcr{stage}_{j}.net.0.weight", f"{p}.cbcr{stage}_{j}.net.1", f"{p}.cbcr{stage}_{j}.net.0.bias") for j, k in enumerate(ks)]  # noqa: E731
             # second stage: Swish(out1 + res) sends its gradient to out1's convolutions and to the downsample branch
-            dacc1, dres, sums = self._stage_bwd(st, accumulate, dS[:, n_in: n_in + g], tape["acc"][(i, 1)], q["scale1"], q["shift1"], t["out0"],
-                                                convs(1), B=B, T=T, n_in=g, co=gb, d=d, act=ops.ACT_SWISH, res=t["res"], res_act=ops.ACT_SWISH)
+            dacc1, dres, sums = S.stage_bwd(rec[(i, 1)], D1, dS[:, n_in: n_in + g], t["out0"], accumulate, B=B, T=T, res=t["res"], res_act=ops.ACT_SWISH)
             self._put(*grad(f"{p}.downsample.bias"), sums[3])
             dout0 = torch.empty((rows, g), dtype=BF16, device=dev)
-            ops.tconv_dgrad(dacc1, B=B, T=T, co=gb, d=d, n_out=g, out=dout0,
-                            branches=[dict(k=k, wt=q["wt1"][j], dy_off=j * gb) for j, k in enumerate(ks)])
+            self._dgrad(tape, (i, 1), D1, dacc1, B=B, T=T, out=dout0)
             # first stage (gated)
-            dacc0, _, _ = self._stage_bwd(st, accumulate, dout0, tape["acc"][(i, 0)], q["scale0"], q["shift0"], stack, convs(0), B=B, T=T,
-                                          n_in=n_in, co=gb, d=d, gates=t["gates"], act=ops.ACT_SWISH)
-            gpart = ops.tconv_dgrad(dacc0, B=B, T=T, co=gb, d=d, n_out=n_in, out=dS, x=stack, addend=dS,
-                                    branches=[dict(k=k, wt=q["wt0"][j], dy_off=j * gb, gate=t["gates"][j]) for j, k in enumerate(ks)])
-            g1 = [grad(f"{p}.cbcr0_se_{j}.fc.0.weight") for j in range(len(ks))]
-            g2 = [grad(f"{p}.cbcr0_se_{j}.fc.2.weight") for j in range(len(ks))]
-            add = g1[0][1]
+            dacc0, _, _ = S.stage_bwd(rec[(i, 0)], D0, dout0, stack, accumulate, B=B, T=T, gates=t["gates"])
+            gpart = self._dgrad(tape, (i, 0), D0, dacc0, B=B, T=T, out=dS, gates=t["gates"], x=stack, addend=dS)
+            g1 = [grad(f"{p}.cbcr0_se_{j}.fc.0.weight") for j in range(nb)]
+            g2 = [grad(f"{p}.cbcr0_se_{j}.fc.2.weight") for j in range(nb)]
             dmean = ops.tcn_se_bwd(stack, L["se_w1"], L["se_w2"], t["gates"], gpart, [a for a, _ in g1], [a for a, _ in g2], B=B, T=T, n_in=n_in,
-                                   add=add)
+                                   add=g1[0][1])
             # downsample branch; the time mean's gradient (constant over a clip's rows) rides in the same write
             gw, add = grad(f"{p}.downsample.weight")
             ops.tconv_wgrad(stack, dres, gw, B=B, T=T, n_in=n_in, co=g, k=1, d=1, add=add)
             ops.tconv_dgrad(dres, B=B, T=T, co=g, d=1, n_out=n_in, out=dS, addend=dS, cadd=dmean, cadd_scale=1.0 / T,
-                            branches=[dict(k=1, wt=q["down_wt"], dy_off=0)])
+                            branches=[dict(k=1, wt=L["down_wt"], dy_off=0)])
             if i == 0 or P["layers"][i - 1]["bi"] != bi:          # the block's input: a transition's output
                 if bi == 0:
                     break
-                tr, x, ptr = Q["trans"][bi - 1], stacks[bi - 1], P["trans"][bi - 1]
-                dacc, _, _ = self._stage_bwd(st, accumulate, dS[:, :R], tape["acc"][("tr", bi - 1)], ptr["scale"], ptr["shift"], x,
-                                             [(1, f"{tr['name']}.conv.weight", f"{tr['name']}.norm", None)], B=B, T=T, n_in=ptr["n_in"], co=R, d=1,
-                                             act=ops.ACT_SWISH)
+                key, x = ("tr", bi - 1), stacks[bi - 1]
+                dacc, _, _ = S.stage_bwd(rec[key], P["trans"][bi - 1], dS[:, :R], x, accumulate, B=B, T=T)
                 dS = torch.empty_like(x)
-                ops.tconv_dgrad(dacc, B=B, T=T, co=R, d=1, n_out=ptr["n_in"], out=dS, branches=[dict(k=1, wt=tr["wt"], dy_off=0)])
+                self._dgrad(tape, key, P["trans"][bi - 1], dacc, B=B, T=T, out=dS)
         # transition0 (PReLU)
-        p = f"{TCN}.transition0"
-        dacc, _, sums = self._stage_bwd(st, accumulate, dS[:, :R], tape["acc"]["t0"], P["t0"]["scale"], P["t0"]["shift"], tape["x0"],
-                                        [(1, f"{p}.conv.weight", f"{p}.norm", None)], B=B, T=T, n_in=self.in_pad, co=R, d=1, act=ops.ACT_PRELU,
-                                        slope=P["t0"]["slope"])
-        self._put(*grad(f"{p}.prelu.weight"), sums[2])
+        dacc, _, sums = S.stage_bwd(rec["t0"], P["t0"], dS[:, :R], tape["x0"], accumulate, B=B, T=T)
+        self._put(*grad(f"{TCN}.transition0.prelu.weight"), sums[2])
         if not want_input_grad:
             return None
         dx0 = torch.empty((rows, self.in_pad), dtype=BF16, device=dev)
-        ops.tconv_dgrad(dacc, B=B, T=T, co=R, d=1, n_out=self.in_pad, out=dx0, branches=[dict(k=1, wt=Q["t0_wt"], dy_off=0)])
+        self._dgrad(tape, "t0", P["t0"], dacc, B=B, T=T, out=dx0)
         return dx0[:, :512].contiguous()          # (the boundary column's own gradient is discarded)
 
-    # ------------------------------------------------------------------------------------------------
-    # the back-end in the reference's training arithmetic (loss_and_backend_grads(train_stats=True)): batch-statistic BatchNorm1d, dropout
-    # ------------------------------------------------------------------------------------------------
     def _counts(self, B: int, T: int, hs: tuple, co: int, dev) -> torch.Tensor:
         """fp32 [len(hs) * co]: the positions B * (T + 2 h) a channel's statistics run over; built once per shape (a host-to-device copy)."""
         key = (B, T, hs, co, str(dev))
@@ -616,88 +600,16 @@ class DCTCNLightningModule(_StoreModule):
             self._n_cache[key] = torch.tensor([float(B * (T + 2 * h)) for h in hs], dtype=torch.float32, device=dev).repeat_interleave(co)
         return self._n_cache[key]
 
-    def _stage_bs(self, st: _ParamStore, tape: dict, key, x, norms, *, B: int, T: int, n_in: int, d: int, branches, co: int, act: int, out,
-                  slope=None, res=None, res_act: int = ops.ACT_NONE, drop=None) -> None:
-        """One convolution stage on batch statistics: convolution at every position BatchNorm1d sees (the chomped ones included) -> column
-        statistics -> scale / shift -> the epilogue over the T kept rows.  norms: per branch (BatchNorm, conv bias or None).  tape[key] keeps
-        what the backward and the running-statistic update read."""
-        acc, hmax, hs = ops.tconv_fwd_ext(x, B=B, T=T, n_in=n_in, d=d, branches=branches, co=co)
-        stats = ops.tcn_colstats(acc, B=B, T=T, co=co, hmax=hmax, hs=hs)
-        n = self._counts(B, T, tuple(hs), co, x.device)
-        weight = torch.cat([st.p32(f"{bn}.weight") for bn, _ in norms])
-        bias = torch.cat([st.p32(f"{bn}.bias") for bn, _ in norms])
-        scale, shift, mean, invstd, var_u = ops.bn_batch_affine(stats, n, weight, bias)
-        ops.tconv_apply(acc, scale, shift, B=B, T=T, co=co, hmax=hmax, hs=hs, act=act, out=out, slope=slope, res=res, res_act=res_act, drop=drop)
-        tape["bs"][key] = dict(acc=acc, hmax=hmax, hs=hs, scale=scale, shift=shift, mean=mean, invstd=invstd, n=n, var_u=var_u, norms=norms, co=co,
-                               drop=drop)
-
-    def _backend_bs(self, st: _ParamStore, feats: torch.Tensor, word_mask, B: int, T: int, tape: dict, train: dict):
-        """_backend on batch statistics, with dropout0 / dropout1 when train carries a seed.  The tape is always kept."""
-        P, dm, dev = self._prepare(st, fold=False), self.dims, feats.device
-        tape.update(bs={}, layers=[], stacks=[], train=train)
-        R, ks = dm["reduced"], dm["ks"]
-        sites = dropout.dctcn_sites(self.config)
-        layers, _ = dctcn_layers(self.config)
-        if self.use_boundary:
-            if word_mask is None:
-                raise ValueError("use_boundary: word_mask [B, T] is required")
-            x0 = torch.zeros((B * T, self.in_pad), dtype=BF16, device=dev)
-            x0[:, :512] = feats
-            x0[:, 512] = word_mask.reshape(B * T).to(BF16)
-        else:
-            x0 = feats
-        width = lambda bi: R + dm["blocks"][bi] * dm["growth"][bi]          # noqa: E731
-        stack = torch.empty((B * T, width(0)), dtype=BF16, device=dev)
-        p = f"{TCN}.transition0"
-        self._stage_bs(st, tape, "t0", x0, [(f"{p}.norm", None)], B=B, T=T, n_in=x0.shape[1], d=1, branches=[P["t0"]], co=R, act=ops.ACT_PRELU,
-                       slope=P["t0"]["slope"], out=stack)
-        tape["x0"] = x0
-        tape["stacks"].append(stack)
-        nlayers, li = len(P["layers"]), 0
-        for i, (L, (p, _, _, _, _)) in enumerate(zip(P["layers"], layers)):
-            n_in, g, gb, d, bi = L["n_in"], L["g"], L["gb"], L["d"], L["bi"]
-            li = li + 1 if i and P["layers"][i - 1]["bi"] == bi else 1
-            drop = [None, None]
-            if train["seed"] is not None and train["p"] > 0.0:
-                drop = [(dropout.site_key(train["seed"], sites[f"block{bi + 1}.layer{li}.drop{s}"]), train["p"]) for s in (0, 1)]
-            norms = lambda stage: [(f"{p}.cbcr{stage}_{j}.net.1", f"{p}.cbcr{stage}_{j}.net.0.bias") for j in range(len(ks))]  # noqa: E731
-            gates = ops.tcn_se_fwd(stack, L["se_w1"], L["se_w2"], B=B, T=T, n_in=n_in)
-            out0 = torch.empty((B * T, g), dtype=BF16, device=dev)
-            self._stage_bs(st, tape, (i, 0), stack, norms(0), B=B, T=T, n_in=n_in, d=d, co=gb, act=ops.ACT_SWISH, out=out0, drop=drop[0],
-                           branches=[dict(br, gate=gates[j]) for j, br in enumerate(L["stage0"])])
-            res = torch.empty((B * T, g), dtype=BF16, device=dev)
-            ops.tconv_fwd(stack, B=B, T=T, n_in=n_in, d=1, branches=[L["down"]], co=g, act=ops.ACT_NONE, out=res)
-            self._stage_bs(st, tape, (i, 1), out0, norms(1), B=B, T=T, n_in=g, d=d, co=gb, act=ops.ACT_SWISH, out=stack[:, n_in:], res=res,
-                           res_act=ops.ACT_SWISH, drop=drop[1], branches=L["stage1"])
-            tape["layers"].append(dict(stack=stack, gates=gates, out0=out0, res=res))
-            if (i + 1 == nlayers or P["layers"][i + 1]["bi"] != bi) and bi in P["trans"]:
-                tr = P["trans"][bi]
-                name = [t for t in dctcn_layers(self.config)[1] if t[2] == bi][0][0]
-                nxt = torch.empty((B * T, width(bi + 1)), dtype=BF16, device=dev)
-                self._stage_bs(st, tape, ("tr", bi), stack, [(f"{name}.norm", None)], B=B, T=T, n_in=tr["n_in"], d=1, branches=[tr], co=R,
-                               act=ops.ACT_SWISH, out=nxt)
-                stack = nxt
-                tape["stacks"].append(stack)
-        return stack
-
-    def _norm5_bs(self, st: _ParamStore, stack: torch.Tensor, B: int, T: int, tape: dict):
-        """norm5 on batch statistics over the B * T rows of the bf16 stack -> (scale, shift) for svsr_tcn_norm_pool_fwd."""
-        C, bn = self.dims["out_size"], f"{TCN}.norm5"
-        stats = ops.tcn_colstats(stack, B=B, T=T, co=C)
-        n = self._counts(B, T, (0,), C, stack.device)
-        scale, shift, mean, invstd, var_u = ops.bn_batch_affine(stats, n, st.p32(f"{bn}.weight"), st.p32(f"{bn}.bias"))
-        tape["bs"]["norm5"] = dict(scale=scale, shift=shift, mean=mean, invstd=invstd, n=n, var_u=var_u, norms=[(bn, None)], co=C)
-        return scale, shift
-
     def _update_running(self, tape: dict, momentum: float = 0.1) -> None:
         """BatchNorm1d's buffer update of every back-end norm from the step's statistics (the conv bias belongs to the mean, the variance is
         the unbiased one), then the folded eval coefficients are marked stale: the next eval forward folds them again, a training step does not.
         (The buffers are views of the store's one flat vector; nothing else shadows them.)"""
         st: _ParamStore = tape["st"]
-        for S in tape["bs"].values():
-            co = S["co"]
-            for j, (bn, bias) in enumerate(S["norms"]):
-                mean, var = S["mean"][j * co: (j + 1) * co], S["var_u"][j * co: (j + 1) * co]
+        for rec in tape["rec"].values():
+            D = rec["D"]
+            co = D["co"]
+            for j, (bn, bias) in enumerate(zip(D["norms"], D["biases"])):
+                mean, var = rec["mean"][j * co: (j + 1) * co], rec["var_u"][j * co: (j + 1) * co]
                 if bias is not None:
                     mean = mean + st.p32(bias)
                 st.buffers[f"{bn}.running_mean"].mul_(1.0 - momentum).add_(mean, alpha=momentum)
@@ -706,86 +618,127 @@ class DCTCNLightningModule(_StoreModule):
         if self._prep is not None:
             self._prep["folded"] = False
 
-    def _stage_bwd_bs(self, st: _ParamStore, accumulate: bool, dy, S: dict, x, weights, *, B: int, T: int, n_in: int, d: int, ks, gates=None,
-                      act: int, slope=None, res=None, res_act: int = ops.ACT_NONE):
-        """_stage_bwd under batch statistics: pass 1 (sums, dres), the O(C) chain rule, pass 2 (the gradient of every extended accumulator),
-        then per branch the BatchNorm gradients, the conv bias's exact zeros and the weight gradient over the extended rows.
-        -> (dacc bf16 [B * (T + 2 hmax), C], dres, sums)"""
-        co, geo = S["co"], dict(B=B, T=T, co=S["co"], hmax=S["hmax"], hs=S["hs"], act=act, slope=slope, res=res, res_act=res_act, drop=S["drop"])
-        dres, sums = ops.tconv_epi_bwd_bs(dy, S["acc"], S["scale"], S["shift"], **geo)
-        dw, db, ca, cb = ops.bn_batch_param_grads(sums[0], sums[1], S["mean"], S["invstd"], S["n"])
-        dacc = ops.tconv_bn_bwd(dy, S["acc"], S["scale"], S["shift"], S["mean"], S["invstd"], ca, cb, **geo)
-        for j, ((bn, bias), weight, k) in enumerate(zip(S["norms"], weights, ks)):
-            self._put(*self._grad_of(st, f"{bn}.weight", accumulate), dw[j * co: (j + 1) * co])
-            self._put(*self._grad_of(st, f"{bn}.bias", accumulate), db[j * co: (j + 1) * co])
-            if bias is not None:          # cancels under batch statistics: exact zeros (an accumulated .grad is left as it is)
-                gb, add = self._grad_of(st, bias, accumulate)
-                if not add:
-                    gb.zero_()
-            gw, add = self._grad_of(st, weight, accumulate)
-            ops.tconv_wgrad(x, dacc[:, j * co: (j + 1) * co], gw, B=B, T=T, n_in=n_in, co=co, k=k, d=d, gate=None if gates is None else gates[j],
-                            add=add, hmax=S["hmax"])
-        return dacc, dres, sums
-
-    def _backward_bs(self, tape: dict, loss_scale: float, accumulate: bool, want_input_grad: bool):
-        st: _ParamStore = tape["st"]
-        P, Q, dm, bs = self._prepare(st, fold=False), self._prepare_bwd(st, fold=False), self.dims, tape["bs"]
-        B, T, dev = tape["B"], tape["T"], st.device
-        rows, C, R, ks = B * T, dm["out_size"], dm["reduced"], dm["ks"]
-        grad = lambda name: self._grad_of(st, name, accumulate)          # noqa: E731
-        dh, dpooled = self._heads_backward(tape, loss_scale, accumulate)
-        # norm5 + masked mean: the sums first, then the data gradient with the statistics' chain rule (one rounding)
-        stacks, S5 = tape["stacks"], bs["norm5"]
-        dS = torch.empty_like(stacks[-1])
-        _, sums = ops.tcn_norm_pool_bwd(dh, dpooled, stacks[-1], S5["scale"], tape["mask"], B=B, T=T, C=C, out=dS)
-        dw, db, ca, cb = ops.bn_batch_param_grads(sums[0], sums[1], S5["mean"], S5["invstd"], S5["n"])
-        self._put(*grad(f"{TCN}.norm5.weight"), dw)
-        self._put(*grad(f"{TCN}.norm5.bias"), db)
-        ops.tcn_norm_pool_bwd_bs(dh, dpooled, stacks[-1], S5["scale"], S5["mean"], S5["invstd"], ca, cb, tape["mask"], B=B, T=T, C=C, out=dS)
-        for i in range(len(P["layers"]) - 1, -1, -1):
-            L, q, t = P["layers"][i], Q["layers"][i], tape["layers"][i]
-            n_in, g, gb, d, bi, p = L["n_in"], L["g"], L["gb"], L["d"], L["bi"], q["p"]
-            stack = t["stack"]
-            weights = lambda stage: [f"{p}.cbcr{stage}_{j}.net.0.weight" for j in range(len(ks))]          # noqa: E731
-            S1, S0 = bs[(i, 1)], bs[(i, 0)]
-            dacc1, dres, sums = self._stage_bwd_bs(st, accumulate, dS[:, n_in: n_in + g], S1, t["out0"], weights(1), B=B, T=T, n_in=g, d=d, ks=ks,
-                                                   act=ops.ACT_SWISH, res=t["res"], res_act=ops.ACT_SWISH)
-            self._put(*grad(f"{p}.downsample.bias"), sums[3])
-            dout0 = torch.empty((rows, g), dtype=BF16, device=dev)
-            ops.tconv_dgrad(dacc1, B=B, T=T, co=gb, d=d, n_out=g, out=dout0, hmax=S1["hmax"],
-                            branches=[dict(k=k, wt=q["wt1"][j], dy_off=j * gb) for j, k in enumerate(ks)])
-            dacc0, _, _ = self._stage_bwd_bs(st, accumulate, dout0, S0, stack, weights(0), B=B, T=T, n_in=n_in, d=d, ks=ks, gates=t["gates"],
-                                             act=ops.ACT_SWISH)
-            gpart = ops.tconv_dgrad(dacc0, B=B, T=T, co=gb, d=d, n_out=n_in, out=dS, x=stack, addend=dS, hmax=S0["hmax"],
-                                    branches=[dict(k=k, wt=q["wt0"][j], dy_off=j * gb, gate=t["gates"][j]) for j, k in enumerate(ks)])
-            g1 = [grad(f"{p}.cbcr0_se_{j}.fc.0.weight") for j in range(len(ks))]
-            g2 = [grad(f"{p}.cbcr0_se_{j}.fc.2.weight") for j in range(len(ks))]
-            dmean = ops.tcn_se_bwd(stack, L["se_w1"], L["se_w2"], t["gates"], gpart, [a for a, _ in g1], [a for a, _ in g2], B=B, T=T, n_in=n_in,
-                                   add=g1[0][1])
-            gw, add = grad(f"{p}.downsample.weight")
-            ops.tconv_wgrad(stack, dres, gw, B=B, T=T, n_in=n_in, co=g, k=1, d=1, add=add)
-            ops.tconv_dgrad(dres, B=B, T=T, co=g, d=1, n_out=n_in, out=dS, addend=dS, cadd=dmean, cadd_scale=1.0 / T,
-                            branches=[dict(k=1, wt=q["down_wt"], dy_off=0)])
-            if i == 0 or P["layers"][i - 1]["bi"] != bi:
-                if bi == 0:
-                    break
-                tr, x, ptr = Q["trans"][bi - 1], stacks[bi - 1], P["trans"][bi - 1]
-                dacc, _, _ = self._stage_bwd_bs(st, accumulate, dS[:, :R], bs[("tr", bi - 1)], x, [f"{tr['name']}.conv.weight"], B=B, T=T,
-                                                n_in=ptr["n_in"], d=1, ks=[1], act=ops.ACT_SWISH)
-                dS = torch.empty_like(x)
-                ops.tconv_dgrad(dacc, B=B, T=T, co=R, d=1, n_out=ptr["n_in"], out=dS, branches=[dict(k=1, wt=tr["wt"], dy_off=0)])
-        p = f"{TCN}.transition0"
-        dacc, _, sums = self._stage_bwd_bs(st, accumulate, dS[:, :R], bs["t0"], tape["x0"], [f"{p}.conv.weight"], B=B, T=T, n_in=self.in_pad, d=1,
-                                           ks=[1], act=ops.ACT_PRELU, slope=P["t0"]["slope"])
-        self._put(*grad(f"{p}.prelu.weight"), sums[2])
-        if not want_input_grad:
-            return None
-        dx0 = torch.empty((rows, self.in_pad), dtype=BF16, device=dev)
-        ops.tconv_dgrad(dacc, B=B, T=T, co=R, d=1, n_out=self.in_pad, out=dx0, branches=[dict(k=1, wt=Q["t0_wt"], dy_off=0)])
-        return dx0[:, :512].contiguous()
-
     def validation_step(self, batch: dict, idx: int = 0) -> dict:
         return {f"val/{k}": v for k, v in self(**batch).items()}
 
     def test_step(self, batch: dict, idx: int = 0) -> dict:
         return {f"test/{k}": v for k, v in self(**batch).items()}
+
+
+# ----------------------------------------------------------------------------------------------------
+# The two stage sets.  Everything that depends on the BatchNorm statistics mode lives here, behind one signature per function: a stage
+# forward, a stage backward short of its data gradient, norm5's coefficients and norm5's data gradient.  D is a stage's static description
+# (DCTCNLightningModule._stage); with `rec` (tape["rec"]; None without a tape) a stage leaves its record under rec[key], which its backward
+# is handed again and whose hmax the data and weight gradients take.  A set holds the model and the store, never the tape.
+# ----------------------------------------------------------------------------------------------------
+def _gated(D: dict, gates):
+    return D["branches"] if gates is None else [dict(br, gate=gates[j]) for j, br in enumerate(D["branches"])]
+
+
+class _RunningStats:
+    """BatchNorm on the running statistics (features / predict / forward, loss_and_backend_grads): folded with the conv bias into the
+    convolution's epilogue; no dropout.  Without a tape nothing is kept (no accumulator buffer is allocated)."""
+    folds = True          # reads _prepare's folded scale / shift
+
+    def __init__(self, model: DCTCNLightningModule, st: _ParamStore):
+        self.m, self.st = model, st
+
+    def stage(self, rec: Optional[dict], key, D: dict, x, out, *, B: int, T: int, gates=None, res=None, res_act: int = ops.ACT_NONE) -> None:
+        """ops.tconv_fwd; with a tape the same kernel's saving instantiation, the fp32 accumulators kept in the record."""
+        acc = None
+        if rec is not None:
+            acc = torch.empty((x.shape[0], len(D["ks"]) * D["co"]), dtype=torch.float32, device=x.device)
+            rec[key] = dict(acc=acc, hmax=None)          # (None: svsr_tconv_dgrad / svsr_tconv_wgrad, not their _ext entries)
+        ops.tconv_fwd(x, B=B, T=T, n_in=D["n_in"], d=D["d"], branches=_gated(D, gates), co=D["co"], act=D["act"], out=out, res=res, res_act=res_act,
+                      acc=acc)
+
+    def stage_bwd(self, rec: dict, D: dict, dy, x, accumulate: bool, *, B: int, T: int, gates=None, res=None, res_act: int = ops.ACT_NONE):
+        """The epilogue backward over all branches, then per branch j (channels [j * co, (j + 1) * co)) the BatchNorm / bias gradients and
+        the weight gradient over the stage's input rows x.  -> (dacc, dres, sums)"""
+        m, st, co = self.m, self.st, D["co"]
+        dacc, dres, sums = ops.tconv_epi_bwd(dy, rec["acc"], D["scale"], D["shift"], rows=B * T, C=len(D["ks"]) * co, act=D["act"], slope=D["slope"],
+                                             res=res, res_act=res_act)
+        for j, k in enumerate(D["ks"]):
+            m._bn_grads(st, accumulate, sums, D["norms"][j], D["biases"][j], j * co, (j + 1) * co)
+            gw, add = m._grad_of(st, D["weights"][j], accumulate)
+            ops.tconv_wgrad(x, dacc[:, j * co: (j + 1) * co], gw, B=B, T=T, n_in=D["n_in"], co=co, k=k, d=D["d"],
+                            gate=None if gates is None else gates[j], add=add, hmax=rec["hmax"])
+        return dacc, dres, sums
+
+    def norm5(self, rec: Optional[dict], stack, B: int, T: int):
+        return self.m._prep["norm5"]
+
+    def norm5_bwd(self, r, dh, dpooled, stack, mask, accumulate: bool, *, B: int, T: int):
+        dS = torch.empty_like(stack)
+        _, sums = ops.tcn_norm_pool_bwd(dh, dpooled, stack, self.m._prep["norm5"][0], mask, B=B, T=T, C=self.m.dims["out_size"], out=dS)
+        self.m._bn_grads(self.st, accumulate, sums, f"{TCN}.norm5", None)
+        return dS
+
+
+class _BatchStats:
+    """The reference's training arithmetic (loss_and_backend_grads(train_stats=True)): batch-statistic BatchNorm1d over every position the
+    full-padding convolution produces, dropout0 / dropout1 when train carries a seed.  A tape is always kept; a record holds what the
+    backward and the running-statistic update read."""
+    folds = False
+
+    def __init__(self, model: DCTCNLightningModule, st: _ParamStore, train: dict):
+        self.m, self.st, self.train = model, st, train
+        self.sites = dropout.dctcn_sites(model.config)
+
+    def stage(self, rec: dict, key, D: dict, x, out, *, B: int, T: int, gates=None, res=None, res_act: int = ops.ACT_NONE) -> None:
+        """Convolution at every position BatchNorm1d sees (the chomped ones included) -> column statistics -> scale / shift -> the epilogue
+        over the T kept rows."""
+        st, co, train, drop = self.st, D["co"], self.train, None
+        if D["drop_site"] is not None and train["seed"] is not None and train["p"] > 0.0:
+            drop = (dropout.site_key(train["seed"], self.sites[D["drop_site"]]), train["p"])
+        acc, hmax, hs = ops.tconv_fwd_ext(x, B=B, T=T, n_in=D["n_in"], d=D["d"], branches=_gated(D, gates), co=co)
+        stats = ops.tcn_colstats(acc, B=B, T=T, co=co, hmax=hmax, hs=hs)
+        n = self.m._counts(B, T, tuple(hs), co, x.device)
+        weight = torch.cat([st.p32(f"{bn}.weight") for bn in D["norms"]])
+        bias = torch.cat([st.p32(f"{bn}.bias") for bn in D["norms"]])
+        scale, shift, mean, invstd, var_u = ops.bn_batch_affine(stats, n, weight, bias)
+        ops.tconv_apply(acc, scale, shift, B=B, T=T, co=co, hmax=hmax, hs=hs, act=D["act"], out=out[:, D["out_off"]:], slope=D["slope"], res=res,
+                        res_act=res_act, drop=drop)
+        rec[key] = dict(D=D, acc=acc, hmax=hmax, hs=hs, scale=scale, shift=shift, mean=mean, invstd=invstd, n=n, var_u=var_u, drop=drop)
+
+    def stage_bwd(self, rec: dict, D: dict, dy, x, accumulate: bool, *, B: int, T: int, gates=None, res=None, res_act: int = ops.ACT_NONE):
+        """Pass 1 (sums, dres), the O(C) chain rule, pass 2 (the gradient of every extended accumulator), then per branch the BatchNorm
+        gradients, the conv bias's exact zeros and the weight gradient over the extended rows.
+        -> (dacc bf16 [B * (T + 2 hmax), C], dres, sums)"""
+        m, st, co = self.m, self.st, D["co"]
+        geo = dict(B=B, T=T, co=co, hmax=rec["hmax"], hs=rec["hs"], act=D["act"], slope=D["slope"], res=res, res_act=res_act, drop=rec["drop"])
+        dres, sums = ops.tconv_epi_bwd_bs(dy, rec["acc"], rec["scale"], rec["shift"], **geo)
+        dw, db, ca, cb = ops.bn_batch_param_grads(sums[0], sums[1], rec["mean"], rec["invstd"], rec["n"])
+        dacc = ops.tconv_bn_bwd(dy, rec["acc"], rec["scale"], rec["shift"], rec["mean"], rec["invstd"], ca, cb, **geo)
+        for j, k in enumerate(D["ks"]):
+            bn, bias = D["norms"][j], D["biases"][j]
+            m._put(*m._grad_of(st, f"{bn}.weight", accumulate), dw[j * co: (j + 1) * co])
+            m._put(*m._grad_of(st, f"{bn}.bias", accumulate), db[j * co: (j + 1) * co])
+            if bias is not None:          # cancels under batch statistics: exact zeros (an accumulated .grad is left as it is)
+                gb, add = m._grad_of(st, bias, accumulate)
+                if not add:
+                    gb.zero_()
+            gw, add = m._grad_of(st, D["weights"][j], accumulate)
+            ops.tconv_wgrad(x, dacc[:, j * co: (j + 1) * co], gw, B=B, T=T, n_in=D["n_in"], co=co, k=k, d=D["d"],
+                            gate=None if gates is None else gates[j], add=add, hmax=rec["hmax"])
+        return dacc, dres, sums
+
+    def norm5(self, rec: dict, stack, B: int, T: int):
+        """norm5 on batch statistics over the B * T rows of the bf16 stack -> (scale, shift) for svsr_tcn_norm_pool_fwd."""
+        C, bn = self.m.dims["out_size"], f"{TCN}.norm5"
+        stats = ops.tcn_colstats(stack, B=B, T=T, co=C)
+        n = self.m._counts(B, T, (0,), C, stack.device)
+        scale, shift, mean, invstd, var_u = ops.bn_batch_affine(stats, n, self.st.p32(f"{bn}.weight"), self.st.p32(f"{bn}.bias"))
+        rec["norm5"] = dict(D=dict(norms=[bn], biases=[None], co=C), scale=scale, mean=mean, invstd=invstd, n=n, var_u=var_u)
+        return scale, shift
+
+    def norm5_bwd(self, r: dict, dh, dpooled, stack, mask, accumulate: bool, *, B: int, T: int):
+        """The sums first, then the data gradient with the statistics' chain rule (one rounding)."""
+        m, st, C = self.m, self.st, self.m.dims["out_size"]
+        dS = torch.empty_like(stack)
+        _, sums = ops.tcn_norm_pool_bwd(dh, dpooled, stack, r["scale"], mask, B=B, T=T, C=C, out=dS)
+        dw, db, ca, cb = ops.bn_batch_param_grads(sums[0], sums[1], r["mean"], r["invstd"], r["n"])
+        m._put(*m._grad_of(st, f"{TCN}.norm5.weight", accumulate), dw)
+        m._put(*m._grad_of(st, f"{TCN}.norm5.bias", accumulate), db)
+        ops.tcn_norm_pool_bwd_bs(dh, dpooled, stack, r["scale"], r["mean"], r["invstd"], ca, cb, mask, B=B, T=T, C=C, out=dS)
+        return dS

@@ -2330,6 +2330,26 @@ def _host_table(rows) -> torch.Tensor:
     return tab
 
 
+def _tconv_table(branches: Sequence[dict], B: int, n_in: int, co: int, out: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None) -> list:
+    """The per-branch operand checks and host table rows of svsr_tconv_fwd: {k, w, gate, scale, shift, slope, out_off, res_off}.  Without
+    out (svsr_tconv_fwd_ext: no epilogue) only k, w and gate are read and the other words stay zero."""
+    rows = []
+    for br in branches:
+        w, k, g = br["w"], int(br["k"]), br.get("gate")
+        _packed(w, BF16, (co, k, n_in))
+        _packed(g, torch.float32, (B, n_in), optional=True)
+        if out is None:
+            rows.append((k, _p(w), _p(g) or 0, 0, 0, 0, 0, 0))
+            continue
+        for n in ("scale", "shift", "slope"):
+            _packed(br.get(n), torch.float32, numel=co, optional=True)
+        off, roff = int(br["out_off"]), int(br.get("res_off", 0))
+        if not (0 <= off and off + co <= out.shape[1] and (res is None or (0 <= roff and roff + co <= res.shape[1]))):
+            raise ValueError(f"tconv_fwd: channels [{off}, {off + co}) / [{roff}, {roff + co}) lie outside the output / residual rows")
+        rows.append((k, _p(w), _p(g) or 0, _p(br["scale"]), _p(br["shift"]), _p(br.get("slope")) or 0, off, roff))
+    return rows
+
+
 def tconv_fwd(x: torch.Tensor, *, B: int, T: int, n_in: int, d: int, branches: Sequence[dict], co: int, act: int, out: torch.Tensor,
               res: Optional[torch.Tensor] = None, res_act: int = ACT_NONE, acc: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Up to three dilated temporal convolutions of the rows x bf16 [B*T, pitch >= n_in] in one launch (svsr_tconv_fwd).  Each branch is a dict
@@ -2343,17 +2363,7 @@ def tconv_fwd(x: torch.Tensor, *, B: int, T: int, n_in: int, d: int, branches: S
         _rows_view(acc, B * T, len(branches) * co, torch.float32)
     if res is not None:
         _rows_view(res, B * T, 0, BF16)
-    rows = []
-    for br in branches:
-        w, k, g = br["w"], int(br["k"]), br.get("gate")
-        _packed(w, BF16, (co, k, n_in))
-        for n in ("scale", "shift", "slope"):
-            _packed(br.get(n), torch.float32, numel=co, optional=True)
-        _packed(g, torch.float32, (B, n_in), optional=True)
-        off, roff = int(br["out_off"]), int(br.get("res_off", 0))
-        if not (0 <= off and off + co <= out.shape[1] and (res is None or (0 <= roff and roff + co <= res.shape[1]))):
-            raise ValueError(f"tconv_fwd: channels [{off}, {off + co}) / [{roff}, {roff + co}) lie outside the output / residual rows")
-        rows.append((k, _p(w), _p(g) or 0, _p(br["scale"]), _p(br["shift"]), _p(br.get("slope")) or 0, off, roff))
+    rows = _tconv_table(branches, B, n_in, co, out, res)
     flops = sum(2.0 * B * T * n_in * r[0] * co for r in rows)
     tab = _host_table(rows)
     head = (_p(x), x.stride(0), B, T, n_in, int(d), len(branches), tab.data_ptr(), co, int(act), _p(out), out.stride(0), _p(res),
@@ -2426,8 +2436,8 @@ def tconv_dgrad(dy: torch.Tensor, *, B: int, T: int, co: int, d: int, branches: 
     """Data gradient of up to three branches in one launch (svsr_tconv_dgrad).  Each branch: k, wt (bf16 [n_out, k, co], transposed and tap-flipped:
     tconv_wt), dy_off, optionally gate (fp32 [B, n_out]).  out bf16 [B*T, >= n_out] = addend + cadd[b] * cadd_scale + sum gate_i * dxg_i.
     -> the gate partials fp32 [nb, B, tiles, n_out] if any branch is gated (x, the forward's input rows, is required then), else None.
-    hmax given (svsr_tconv_dgrad_ext; 0 is the plain launch through that entry): dy is the gradient of the extended accumulators, bf16
-    [B * (T + 2 * hmax), .] (tconv_bn_bwd)."""
+    hmax None (a running-statistic stage's record): svsr_tconv_dgrad.  hmax given (svsr_tconv_dgrad_ext; 0 is the plain launch through that
+    entry): dy is the gradient of the extended accumulators, bf16 [B * (T + 2 * hmax), .] (tconv_bn_bwd)."""
     rows, ext, hmax = B * T, hmax is not None, int(hmax or 0)
     for br in branches:
         if not tconv_ok(co, n_out, int(br["k"]), int(d)):
@@ -2521,18 +2531,23 @@ def tcn_se_bwd(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, gate: torch.
     return dm
 
 
-def tcn_norm_pool_bwd(dh: torch.Tensor, dpooled: torch.Tensor, x: torch.Tensor, scale: torch.Tensor, mask: torch.Tensor, *, B: int, T: int, C: int,
-                      out: torch.Tensor):
-    """norm5 + masked mean backward (svsr_tcn_norm_pool_bwd): dh bf16 [B*T, C], dpooled bf16 [B, C], x bf16 [B*T, >= C] (the forward's input)
-    -> out bf16 [B*T, >= C] channels [0, C) written, sums fp32 [2, C] = (sum g, sum g * x)."""
+def _norm_pool_bwd_args(what: str, dh, dpooled, x, out, mask, vecs, B: int, T: int, C: int) -> None:
     if C < 8 or C % 8:
-        raise ValueError("tcn_norm_pool_bwd: C must be a multiple of 8")
+        raise ValueError(f"{what}: C must be a multiple of 8")
     _packed(dh, BF16, (B * T, C))
     _packed(dpooled, BF16, (B, C))
     _rows_view(x, B * T, C, BF16)
     _rows_view(out, B * T, C, BF16)
     _packed(mask, torch.float32, numel=B * T)
-    _packed(scale, torch.float32, numel=C)
+    for t in vecs:
+        _packed(t, torch.float32, numel=C)
+
+
+def tcn_norm_pool_bwd(dh: torch.Tensor, dpooled: torch.Tensor, x: torch.Tensor, scale: torch.Tensor, mask: torch.Tensor, *, B: int, T: int, C: int,
+                      out: torch.Tensor):
+    """norm5 + masked mean backward (svsr_tcn_norm_pool_bwd): dh bf16 [B*T, C], dpooled bf16 [B, C], x bf16 [B*T, >= C] (the forward's input)
+    -> out bf16 [B*T, >= C] channels [0, C) written, sums fp32 [2, C] = (sum g, sum g * x)."""
+    _norm_pool_bwd_args("tcn_norm_pool_bwd", dh, dpooled, x, out, mask, (scale,), B, T, C)
     part = torch.empty(B * 2 * C, dtype=torch.float32, device=dh.device)
     sums = torch.empty((2, C), dtype=torch.float32, device=dh.device)
     _call("svsr_tcn_norm_pool_bwd", _p(dh), _p(dpooled), _p(x), x.stride(0), B, T, C, _p(scale), _p(mask), _p(out), out.stride(0), _p(part), _p(sums),
@@ -2583,14 +2598,9 @@ def tconv_fwd_ext(x: torch.Tensor, *, B: int, T: int, n_in: int, d: int, branche
     if acc is None:
         acc = torch.empty((erows, C), dtype=torch.float32, device=x.device)
     _rows_view(acc, erows, C, torch.float32)
-    rows = []
-    for br in branches:
-        w, k, g = br["w"], int(br["k"]), br.get("gate")
-        if not tconv_ok(n_in, co, k, int(d)):
-            raise ValueError("tconv_fwd_ext: outside the shape domain of svsr_tconv_fwd")
-        _packed(w, BF16, (co, k, n_in))
-        _packed(g, torch.float32, (B, n_in), optional=True)
-        rows.append((k, _p(w), _p(g) or 0, 0, 0, 0, 0, 0))
+    if not all(tconv_ok(n_in, co, int(br["k"]), int(d)) for br in branches):
+        raise ValueError("tconv_fwd_ext: outside the shape domain of svsr_tconv_fwd")
+    rows = _tconv_table(branches, B, n_in, co)
     tab = _host_table(rows)
     _call("svsr_tconv_fwd_ext", _p(x), x.stride(0), B, T, n_in, int(d), len(branches), tab.data_ptr(), co, hmax, _p(acc), acc.stride(0), _stream(),
           label="k_tconv<ext>", flops=sum(2.0 * B * (T + 2 * h) * n_in * r[0] * co for r, h in zip(rows, hs)))
@@ -2668,15 +2678,7 @@ def tconv_bn_bwd(dy: torch.Tensor, acc: torch.Tensor, scale: torch.Tensor, shift
 def tcn_norm_pool_bwd_bs(dh: torch.Tensor, dpooled: torch.Tensor, x: torch.Tensor, scale: torch.Tensor, mean: torch.Tensor, invstd: torch.Tensor,
                          ca: torch.Tensor, cb: torch.Tensor, mask: torch.Tensor, *, B: int, T: int, C: int, out: torch.Tensor) -> torch.Tensor:
     """tcn_norm_pool_bwd's dx with norm5's batch statistics in the chain (svsr_tcn_norm_pool_bwd_bs): out = scale * (g - ca - xhat * cb)."""
-    if C < 8 or C % 8:
-        raise ValueError("tcn_norm_pool_bwd_bs: C must be a multiple of 8")
-    _packed(dh, BF16, (B * T, C))
-    _packed(dpooled, BF16, (B, C))
-    _rows_view(x, B * T, C, BF16)
-    _rows_view(out, B * T, C, BF16)
-    _packed(mask, torch.float32, numel=B * T)
-    for t in (scale, mean, invstd, ca, cb):
-        _packed(t, torch.float32, numel=C)
+    _norm_pool_bwd_args("tcn_norm_pool_bwd_bs", dh, dpooled, x, out, mask, (scale, mean, invstd, ca, cb), B, T, C)
     _call("svsr_tcn_norm_pool_bwd_bs", _p(dh), _p(dpooled), _p(x), x.stride(0), B, T, C, _p(scale), _p(mean), _p(invstd), _p(ca), _p(cb), _p(mask),
           _p(out), out.stride(0), _stream(), label="k_tcn_norm_pool_bwd_bs")
     return out

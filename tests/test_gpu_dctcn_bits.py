@@ -1,5 +1,7 @@
-"""Bit identity of the DC-TCN convolution kernels (csrc/dctcn.hip) across library builds: svsr_tconv_fwd, svsr_tconv_fwd_save,
-svsr_tconv_dgrad and svsr_tconv_wgrad, driven through the C ABI alone, against tests/golden/dctcn_kernel_bits.npz.  The golden holds one
+"""Bit identity of the DC-TCN kernels (csrc/dctcn.hip) across library builds: svsr_tconv_fwd, svsr_tconv_fwd_save, svsr_tconv_dgrad and
+svsr_tconv_wgrad, the epilogue backward of both BatchNorm statistics modes (svsr_tconv_epi_bwd, svsr_tconv_apply / svsr_tconv_epi_bwd_bs /
+svsr_tconv_bn_bwd) and norm5's (svsr_tcn_norm_pool_bwd, svsr_tcn_norm_pool_bwd_bs), driven through the C ABI alone, against
+tests/golden/dctcn_kernel_bits.npz.  The golden holds one
 SHA-256 per output buffer (guard bands included), not the bits: the raw outputs of these cases come to about 2 MiB, twice what a committed
 file may hold.  It is recorded by running this file as a program on the build to compare with:
 
@@ -11,7 +13,10 @@ that a changed summation order, a moved rounding of the gate product or a mis-st
 
 Shapes: B = 3, T = 33 (two time tiles per clip, the second one row long; 6 slots, and with B = 3, T = 1 an odd slot count: the last
 workgroup's second slot is empty), 128 staged channels (two chunks) into 64, every (k, d) of {(1, 1), (3, 1), (5, 2), (7, 5)} — the last a halo
-of 15 rows, one short of TC_HALO."""
+of 15 rows, one short of TC_HALO.  The epilogue and norm5 cases: B = 3, two branches of 64 channels (C = 128: two channel blocks; norm5 C = 64),
+99 rows (one full 64-row block and 35 more) and a single row, T = 33 and T = 1, the half reaches (1, 15) under hmax = 15 (the (3, 1) and
+(7, 5) branches), dropout p = 0 and 0.2 with a fixed key, every activation, with and without the Swish residual.  The epilogue backward of the
+two modes must agree bit for bit where the batch-statistic one runs without halo and dropout."""
 import hashlib
 import os
 import sys
@@ -121,6 +126,104 @@ def _wgrad(lib, B, T, n_in, co, k, d, gated, n_valid, add, splits, seed):
     return [x, dy, dw0] + ([gate] if gated else []), dict(dw=dw)
 
 
+ACTS = {"swish_res": (2, True), "prelu": (3, False), "relu": (1, False), "none": (0, False)}          # name -> (act, Swish residual)
+DROP_KEY = 0x9E3779B9
+
+
+def _i32(vals):
+    return torch.tensor(list(vals), dtype=torch.int32)
+
+
+def _epi_inputs(g, rows, erows, C, residual):
+    """dy bf16, acc fp32 in (-2, 2), scale / shift / slope fp32 [C], res bf16 or None; every row pitch wider than C."""
+    dy = _bf(g, rows, C + 8).to(DEV)
+    acc = ((_unit(g, erows, C + 8) - 0.5) * 4.0).to(DEV)
+    scale, shift, slope = (0.5 + _unit(g, C)).to(DEV), (_unit(g, C) - 0.5).to(DEV), (0.5 * _unit(g, C)).to(DEV)
+    res = _bf(g, rows, C + 16).to(DEV) if residual else None
+    return dy, acc, scale, shift, slope, res
+
+
+def _epi(lib, B, T, co, nb, act, residual, seed):
+    """svsr_tconv_epi_bwd over B * T rows, then svsr_tconv_epi_bwd_bs on the same inputs without halo and dropout."""
+    g = _gen(seed)
+    rows, C = B * T, nb * co
+    dy, acc, scale, shift, slope, res = _epi_inputs(g, rows, rows, C, residual)
+    blocks = (rows + 63) // 64
+    outs = {}
+    for bs in (False, True):
+        dacc = torch.full((rows + 1, C + 24), SENT, dtype=BF, device=DEV)
+        dres = torch.full((rows + 1, C + 8), SENT, dtype=BF, device=DEV)
+        sums = torch.full((4 * C + 32,), SENT, device=DEV)
+        part = torch.empty(blocks * 4 * C, device=DEV)
+        r = (None, 0) if res is None else (res.data_ptr(), res.stride(0))
+        dr = (None, 0) if res is None else (dres.data_ptr(), dres.stride(0))
+        if bs:
+            h = _i32([0] * nb)
+            rc = lib.svsr_tconv_epi_bwd_bs(dy.data_ptr(), dy.stride(0), acc.data_ptr(), acc.stride(0), B, T, C, co, 0, nb, h.data_ptr(), act,
+                                           scale.data_ptr(), shift.data_ptr(), slope.data_ptr(), *r, 2 if residual else 0, 0, 0.0, *dr,
+                                           part.data_ptr(), sums.data_ptr(), None)
+        else:
+            rc = lib.svsr_tconv_epi_bwd(dy.data_ptr(), dy.stride(0), acc.data_ptr(), acc.stride(0), rows, C, act, scale.data_ptr(), shift.data_ptr(),
+                                        slope.data_ptr(), *r, 2 if residual else 0, dacc.data_ptr(), dacc.stride(0), *dr, part.data_ptr(),
+                                        sums.data_ptr(), None)
+        assert rc == 0, rc
+        torch.cuda.synchronize()
+        if bs:
+            outs.update({"dres<bs>": dres, "sums<bs>": sums})
+        else:
+            outs.update(dacc=dacc, dres=dres, sums=sums)
+    return [dy, acc, scale, shift, slope] + ([res] if residual else []), outs
+
+
+def _epibs(lib, B, T, co, hs, hmax, act, residual, p, seed):
+    """One batch-statistic stage's epilogue, forward and both backward passes, on the extended axis."""
+    g = _gen(seed)
+    nb, rows, erows = len(hs), B * T, B * (T + 2 * hmax)
+    C = nb * co
+    dy, acc, scale, shift, slope, res = _epi_inputs(g, rows, erows, C, residual)
+    mean, invstd, ca, cb = (_unit(g, C) - 0.5).to(DEV), (0.5 + _unit(g, C)).to(DEV), (0.25 * (_unit(g, C) - 0.5)).to(DEV), (0.25 * (_unit(g, C) - 0.5)).to(DEV)
+    h = _i32(hs)
+    out = torch.full((rows + 1, C + 24), SENT, dtype=BF, device=DEV)
+    dres = torch.full((rows + 1, C + 8), SENT, dtype=BF, device=DEV)
+    sums = torch.full((4 * C + 32,), SENT, device=DEV)
+    dacc = torch.full((erows + 1, C + 24), SENT, dtype=BF, device=DEV)
+    part = torch.empty(((rows + 63) // 64) * 4 * C, device=DEV)
+    r = (None, 0) if res is None else (res.data_ptr(), res.stride(0))
+    dr = (None, 0) if res is None else (dres.data_ptr(), dres.stride(0))
+    geo = (acc.data_ptr(), acc.stride(0), B, T, C, co, hmax, nb, h.data_ptr(), act, scale.data_ptr(), shift.data_ptr(), slope.data_ptr(), *r,
+           2 if residual else 0, DROP_KEY, p)
+    for rc in (lib.svsr_tconv_apply(*geo, out.data_ptr(), out.stride(0), None),
+               lib.svsr_tconv_epi_bwd_bs(dy.data_ptr(), dy.stride(0), *geo, *dr, part.data_ptr(), sums.data_ptr(), None),
+               lib.svsr_tconv_bn_bwd(dy.data_ptr(), dy.stride(0), *geo, mean.data_ptr(), invstd.data_ptr(), ca.data_ptr(), cb.data_ptr(), dacc.data_ptr(),
+                                     dacc.stride(0), None)):
+        assert rc == 0, rc
+    torch.cuda.synchronize()
+    return [dy, acc, scale, shift, slope, mean, invstd, ca, cb] + ([res] if residual else []), dict(out=out, dres=dres, sums=sums, dacc=dacc)
+
+
+def _npool(lib, B, T, C, seed):
+    """norm5 + masked mean backward in both statistics modes: a fractional mask, the second clip's all zeros."""
+    g = _gen(seed)
+    rows = B * T
+    dh, dpooled, x = _bf(g, rows, C).to(DEV), _bf(g, B, C).to(DEV), _bf(g, rows, C + 8).to(DEV)
+    mask = _unit(g, B, T)
+    mask[1] = 0.0
+    mask = mask.to(DEV)
+    scale, mean, invstd = (0.5 + _unit(g, C)).to(DEV), (_unit(g, C) - 0.5).to(DEV), (0.5 + _unit(g, C)).to(DEV)
+    ca, cb = (0.25 * (_unit(g, C) - 0.5)).to(DEV), (0.25 * (_unit(g, C) - 0.5)).to(DEV)
+    dx = torch.full((rows + 1, C + 16), SENT, dtype=BF, device=DEV)
+    dx_bs = torch.full((rows + 1, C + 16), SENT, dtype=BF, device=DEV)
+    sums = torch.full((2 * C + 32,), SENT, device=DEV)
+    part = torch.empty(B * 2 * C, device=DEV)
+    head = (dh.data_ptr(), dpooled.data_ptr(), x.data_ptr(), x.stride(0), B, T, C, scale.data_ptr())
+    for rc in (lib.svsr_tcn_norm_pool_bwd(*head, mask.data_ptr(), dx.data_ptr(), dx.stride(0), part.data_ptr(), sums.data_ptr(), None),
+               lib.svsr_tcn_norm_pool_bwd_bs(*head, mean.data_ptr(), invstd.data_ptr(), ca.data_ptr(), cb.data_ptr(), mask.data_ptr(), dx_bs.data_ptr(),
+                                             dx_bs.stride(0), None)):
+        assert rc == 0, rc
+    torch.cuda.synchronize()
+    return [dh, dpooled, x, mask, scale, mean, invstd, ca, cb], {"dx": dx, "sums": sums, "dx<bs>": dx_bs}
+
+
 def _cases():
     """name -> (function, arguments).  Seeds are fixed per case; B, T, channels as the module docstring says."""
     B, T, n_in, co = 3, 33, 128, 64
@@ -141,6 +244,14 @@ def _cases():
     c["fwd_T1"] = (_fwd, (3, 1, n_in, co, (3,), 1, True, 2, False, 600))
     c["dgrad_T1"] = (_dgrad, (3, 1, n_in, co, (3,), 1, True, True, True, 601))
     c["wgrad_T1"] = (_wgrad, (3, 1, n_in, co, 3, 1, True, 120, 1, 1, 602))
+    for j, (tag, (act, residual)) in enumerate(ACTS.items()):
+        c[f"epi_{tag}"] = (_epi, (B, T, co, 2, act, residual, 700 + j))
+    c["epi_rows1"] = (_epi, (1, 1, co, 2, 2, True, 710))          # (a single row is a single clip of a single frame for the _bs entry)
+    for T_ in (T, 1):
+        for p in (0.0, 0.2):
+            for tag in ("swish_res", "prelu"):
+                c[f"epibs_T{T_}_p{int(p * 10)}_{tag}"] = (_epibs, (B, T_, co, (1, 15), 15, *ACTS[tag], p, 800 + 10 * (T_ == 1) + 2 * (p > 0) + (tag == "prelu")))
+        c[f"npool_T{T_}"] = (_npool, (B, T_, 64, 900 + (T_ == 1)))
     return c
 
 
@@ -177,6 +288,9 @@ def test_kernel_output_bits_match_the_recorded_build(name, golden):
         assert bytes(v) == bytes(golden[k]), f"{k}: output bits differ from the recorded build"
     if f"{name}/out<save>" in got:
         assert bytes(got[f"{name}/out"]) == bytes(got[f"{name}/out<save>"]), "the saving forward stores other output bits"
+    for k in ("dres", "sums"):
+        if f"{name}/{k}<bs>" in got:
+            assert bytes(got[f"{name}/{k}"]) == bytes(got[f"{name}/{k}<bs>"]), f"{k}: the batch-statistic pass 1 without halo and dropout stores other bits"
 
 
 def test_golden_covers_exactly_these_cases(golden):
