@@ -104,7 +104,7 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmFwdArgs& p, f32x16 (&a
         // the global operands (y, x, addend pieces) of ALL rows are requested before the first is used — one round trip per tile —
         // while the staged accumulators are read from LDS row by row (the full-tile batch of the path below plus these would not fit)
         float mu[8], rs[8];
-        if (active) {
+        if (active && n < p.Co) {          // (Co % 8 == 0: the group is inside Co or outside; a column tile's groups behind Co own nothing)
 #pragma unroll
             for (int k = 0; k < 8; ++k) { mu[k] = p.bnb_mean[n + k]; rs[k] = p.bnb_rstd[n + k]; }
             const bool from_x = p.bnb_y == nullptr, swish_act = p.bnb_act == 2;
