@@ -116,7 +116,8 @@ int svsr_colsum_rows_multi(const void* entries, int n, hipStream_t stream);
  *   svsr_conv_plan: k x k / stride / pad convolution over Nimg images whose FORWARD input is H x W; mode 0 forward
  *   (in = x [H][W] -> out = y [Ho][Wo], wt [Co][k*k][Ci]), mode 1 input-gradient (in = dy [Ho][Wo] -> out = dx [H][W], wt =
  *   transposed weights [Ci][k*k][Co]; pixels no tap reaches are written as 0 (+ bias / addend)), mode 2 the same for an
- *   in-place accumulation (addend aliases out): pixels no tap reaches are left alone.
+ *   in-place accumulation (addend aliases out): pixels no tap reaches are left alone; mode 3 (3x3 / stride 2 / pad 1 only) mode 1 with
+ *   the 1x1 / stride 2 input-gradient of the same input folded in as one more tap of the (even, even) pixels (svsr_igemm_dgrad2).
  *   svsr_rows_plan: dense layer over Nimg sequences, row (n, j < P) reads source row n*in_pix + src0 + j and writes target row
  *   n*out_pix + dst0 + j (plain linear: P = 1, in_pix = out_pix = 1).
  * svsr_igemm_fwd(plan_dev = device copy of the words, meta = the host meta): in [Nimg][in_pix] pixels of pitch in_pitch with
@@ -191,6 +192,12 @@ int svsr_igemm_dgrad_bn(const void* in, const void* wt, void* out, const void* a
  * into the first half of stats[meta[3]][2][Co] — the partial rows of the bias gradient of the layer in front (svsr_colsum_rows adds them).
  * zeros / ones: device vectors of Co floats holding 0 / 1.  4-wave plans only (not the persistent 3x3 kernel). */
 int svsr_igemm_dgrad_relu(const void* in, const void* wt, void* out, float* stats, const int* plan_dev, const int* meta, int Nimg, int in_pix, int Ci, int in_pitch, int Co, int out_pix, int out_pitch, int wt_taps, const void* y, const float* zeros, const float* ones, float gscale, hipStream_t stream);
+/* The input gradient of a downsample block (reference tcn/models/resnet.py:36-53,59-72: conv1 3x3 / stride 2 and downsample 1x1 / stride 2
+ * read the same input) in ONE launch: plan = svsr_conv_plan mode 3 (3x3 / stride 2 / pad 1 only), whose (even, even) pixels carry one more tap read
+ * from the second operand pair: in2 = the 1x1 branch's dy (geometry and pitch of `in`), wt2 = its transposed weight [Co][Ci].  Both branches
+ * meet in the fp32 accumulator and are rounded once.  Other arguments: svsr_igemm_fwd / svsr_igemm_dgrad_bn without the addend. */
+int svsr_igemm_dgrad2(const void* in, const void* wt, const void* in2, const void* wt2, void* out, void* out_pre, const float* bias, float* stats, const int* plan_dev, const int* meta, int Nimg, int in_pix, int Ci, int in_pitch, int Co, int out_pix, int out_pitch, int wt_taps, int act, int out_f32, float alpha, const unsigned* drop_seed, unsigned drop_site, float drop_p, hipStream_t stream);
+int svsr_igemm_dgrad2_bn(const void* in, const void* wt, const void* in2, const void* wt2, void* out, float* stats, const int* plan_dev, const int* meta, int Nimg, int in_pix, int Ci, int in_pitch, int Co, int out_pix, int out_pitch, int wt_taps, const void* y, const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int act, hipStream_t stream);
 int svsr_conv3x3_c64_dgrad_bn(const void* in, const void* wt, void* out, const void* addend, float* stats, int Nimg, int H, int W, const int* dy, const int* dx, const int* tw, const void* y, const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int act, const int* pixtab, hipStream_t stream);
 int svsr_bn_bwd_from_stats(const void* g, const void* x, const float* mean, const float* rstd, const float* gamma, const float* stats, int nrows, float* coef, float* dgamma, float* dbeta, void* dx, int64_t npix, int C, hipStream_t stream);
 

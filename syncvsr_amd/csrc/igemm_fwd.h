@@ -26,7 +26,13 @@ struct IgemmFwdArgs {
     const float* bnb_gamma;    // with bnb_y == nullptr (no residual branch): the mask is recomputed as bn(x) > 0 with the forward's own
     const float* bnb_beta;     // expression (norm_act.hip k_bn_act_fwd) instead of being read from y
     int bnb_act;               // 1 ReLU (bnb_y = the output y, or null), 2 Swish: g = result * swish'(bn(x) + r), bnb_y = the residual input r or null
+    // second operand pair (k_igemm_fwd_glds<.., TWO = true>: svsr_igemm_dgrad2): a tap whose plan word tw is IGEMM_TAP2 takes its A rows from
+    // in2 (the geometry and pitch of `in`) and its B rows from wt2 [Co][Ci] (one tap)
+    const bf16_t* in2;
+    const bf16_t* wt2;
 };
+
+#define IGEMM_TAP2 9           // tap word of the second operand pair (a 3x3 weight has taps 0..8)
 
 
 #define LDS_SWZ(row, chunk) ((row) * 64 + ((((chunk) ^ (((row) >> 1) & 7))) << 3))

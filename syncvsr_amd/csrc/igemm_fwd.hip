@@ -31,7 +31,11 @@
 //       rows of the class: m = n * P + j  (image n, j-th position of the class), M_c = Nimg * P, tiled by BM from tile_begin
 //       tap t reads source pixel src + delta[t] with weight tap tw[t]
 //   position table: pairs (src, dst) = source-centre / target pixel index inside one image, per class at pos_off
-// A stride-2 data gradient is ONE launch: its four output-parity classes are just more classes (with their own taps).
+// A stride-2 data gradient is ONE launch: its four output-parity classes are just more classes (with their own taps).  Interior pixels of a
+// 3x3 / pad 1 gradient have 4 / 2 / 2 / 1 taps for (odd, odd) / (odd, even) / (even, odd) / (even, even) coordinates; a last odd row or
+// column of an even-sized map loses one tap row or column and forms border classes of its own.  With the 1x1 stride-2 branch of a
+// downsample block folded in (mode 3) the (even, even) class — exactly the pixels that branch reaches — carries one more tap, IGEMM_TAP2,
+// read from the second operand pair: 4 / 2 / 2 / 2.
 // Classes are ordered by decreasing tap count, so the short ones fill the tail of the launch.
 // ---------------------------------------------------------------------------------------------------------------------
 #define PLAN_CLS_WORDS 24
@@ -368,7 +372,9 @@ __device__ __forceinline__ void split_row(int m, int P, float inv_p, int& n, int
 // over one half of the K steps; the second group's accumulators are added to the first's through LDS (always in that order) before
 // the epilogue.  For launches with far fewer tiles than CUs and a long K (the encoder's 960-row linears with 512 outputs: 120
 // tiles, 24-40 K steps) this halves the serial K loop of the few workgroups there are.
-template <int BM, int BN, int NS, int KG = 1>
+// TWO: the plan may hold taps of the second operand pair (tw == IGEMM_TAP2: A rows from p.in2, B rows from p.wt2).  Which pair a tap reads is a
+// wave-uniform choice made when the K loop enters the tap; a K step adds the same one offset per DMA as without it.
+template <int BM, int BN, int NS, int KG = 1, bool TWO = false>
 __global__ __launch_bounds__(256 * KG) void k_igemm_fwd_glds(const IgemmFwdArgs p) {
     constexpr int BK = 64;
     static_assert(NS >= 2 && (BM / 32 + BN / 32) * (NS - 2) <= 63, "vmcnt immediate is 6 bits");
@@ -454,10 +460,32 @@ __global__ __launch_bounds__(256 * KG) void k_igemm_fwd_glds(const IgemmFwdArgs 
     const int KT = KT_all - k_begin < KT_loop ? (KT_all - k_begin > 0 ? KT_all - k_begin : 0) : KT_loop;
     const int spt = p.Ci / BK;                                           // K steps per tap
     int t_next = k_begin / spt, c_next = (k_begin - (k_begin / spt) * spt) * BK;
+    // TWO: element offsets of tap t_next's operands from a_ptr / b_ptr, refreshed when the K loop moves to another tap.  The second pair's
+    // A rows lie in2 - in behind the first's (same geometry); its B row n is wt2 + n * Ci where b_ptr holds wt + n * wt_taps * Ci: the
+    // difference is b2_lane for the lane's first row and b2_rows more for every 32 rows
+    long a_tap = 0, b_tap = 0, b_rows = 0;
+    const long in2_off = TWO ? (reinterpret_cast<intptr_t>(p.in2) - reinterpret_cast<intptr_t>(p.in)) / (long)sizeof(bf16_t) : 0;
+    const long b2_rows = TWO ? -32L * (p.wt_taps - 1) * p.Ci : 0;
+    const long b2_lane = TWO ? (reinterpret_cast<intptr_t>(p.wt2) - reinterpret_cast<intptr_t>(p.wt)) / (long)sizeof(bf16_t) - (long)(n0 + r0) * (p.wt_taps - 1) * p.Ci : 0;
+    auto enter_tap = [&]() {
+        if (t_next >= 9) return;                                         // (behind the last tap of a nine-tap class)
+        const int tw = __builtin_amdgcn_readfirstlane(sTap[9 + t_next]);
+        const bool second = tw == IGEMM_TAP2;
+        a_tap = (long)sTap[t_next] * p.in_pitch + (second ? in2_off : 0);
+        b_tap = second ? b2_lane : (long)tw * p.Ci;
+        b_rows = second ? b2_rows : 0;
+    };
+    if constexpr (TWO) enter_tap();
     auto stage = [&](int buf) {
-        const int tw = sTap[9 + t_next];
         const int c0 = c_next;
-        const long a_off = (long)sTap[t_next] * p.in_pitch + c0;     // wave-uniform
+        long a_off, b_off;
+        if constexpr (TWO) {
+            a_off = a_tap + c0;
+            b_off = b_tap + c0;
+        } else {
+            a_off = (long)sTap[t_next] * p.in_pitch + c0;     // wave-uniform
+            b_off = (long)sTap[9 + t_next] * p.Ci + c0;
+        }
         bf16_t* dstA = sStage + buf * S_ELEMS + wrow * 64;
 #pragma unroll
         for (int i = 0; i < AR; ++i) {
@@ -468,12 +496,15 @@ __global__ __launch_bounds__(256 * KG) void k_igemm_fwd_glds(const IgemmFwdArgs 
         bf16_t* dstB = sStage + buf * S_ELEMS + A_ELEMS + wrow * 64;
 #pragma unroll
         for (int i = 0; i < BR; ++i) {
-            const bf16_t* src = b_ptr[i] != nullptr ? b_ptr[i] + (long)tw * p.Ci + c0 : zero_src;
+            const bf16_t* src = b_ptr[i] != nullptr ? b_ptr[i] + b_off + (TWO ? i * b_rows : 0) : zero_src;
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                              (__attribute__((address_space(3))) void*)(dstB + i * 32 * 64), 16, 0, 0);
         }
         c_next += BK;
-        if (c_next >= p.Ci) { c_next = 0; ++t_next; }
+        if (c_next >= p.Ci) {
+            c_next = 0; ++t_next;
+            if constexpr (TWO) enter_tap();
+        }
     };
 
     f32x16 acc[TM][TN];
@@ -531,16 +562,16 @@ __global__ __launch_bounds__(256 * KG) void k_igemm_fwd_glds(const IgemmFwdArgs 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-template <int BM, int BN, int NS, int KG = 1>
+template <int BM, int BN, int NS, int KG = 1, bool TWO = false>
 static int launch_glds(const IgemmFwdArgs& a, int gx, int gy, hipStream_t stream) {
     const size_t lds = (size_t)KG * NS * (BM + BN) * 64 * sizeof(bf16_t) + (size_t)BM * sizeof(long) + 128;
     static size_t attr_set = 0;
     if (attr_set < lds) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_igemm_fwd_glds<BM, BN, NS, KG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_igemm_fwd_glds<BM, BN, NS, KG, TWO>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr_set = lds;
     }
     IgemmFwdArgs b = a;
-    hipLaunchKernelGGL((k_igemm_fwd_glds<BM, BN, NS, KG>), dim3(gx, gy), dim3(256 * KG), lds, stream, b);
+    hipLaunchKernelGGL((k_igemm_fwd_glds<BM, BN, NS, KG, TWO>), dim3(gx, gy), dim3(256 * KG), lds, stream, b);
     return svsr_check_launch();
 }
 
@@ -678,10 +709,15 @@ static int plan_emit(std::vector<PlanClass>& cls, int Nimg, int Co, int* words, 
  *   mode 1: data gradient  in = dy [Ho][Wo], out = dx [H][W]        (transposed weights [Ci][k*k][Co]); every pixel of dx is
  *           written, also those no tap reaches (k < stride): they get 0 (+ bias / addend)
  *   mode 2: as mode 1 for an IN-PLACE accumulation (addend aliases out): pixels no tap reaches are left alone
+ *   mode 3: mode 1 of a 3x3 / stride 2 / pad 1 convolution with the data gradient of the 1x1 / stride 2 / pad 0 convolution over the same
+ *           input (the downsample branch of a residual block: the same Ho x Wo) folded in: the pixels that branch reaches are those the 3x3
+ *           centre tap reaches, and their classes carry one more tap, tw = IGEMM_TAP2 with the centre tap's delta, read from the second
+ *           operand pair of svsr_igemm_dgrad2 / svsr_igemm_dgrad2_bn
  * Co_out = output channels of the launch (tile choice).  words == null: only counts.  Returns the number of int32 words, or a
  * negative error.  meta[8] = {bm, bn, ns, tiles, grid_y, classes, max taps, rows}. */
 extern "C" int svsr_conv_plan(int mode, int Nimg, int H, int W, int Co_out, int k, int stride, int pad, int* words, int cap_words, int* meta) {
-    if (Nimg < 1 || H < 1 || W < 1 || k < 1 || k > 3 || stride < 1 || pad < 0 || Co_out < 1 || mode < 0 || mode > 2) return -SVSR_ERR_ARG;
+    if (Nimg < 1 || H < 1 || W < 1 || k < 1 || k > 3 || stride < 1 || pad < 0 || Co_out < 1 || mode < 0 || mode > 3) return -SVSR_ERR_ARG;
+    if (mode == 3 && (k != 3 || stride != 2 || pad != 1)) return -SVSR_ERR_ARG;
     const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
     if (Ho < 1 || Wo < 1) return -SVSR_ERR_ARG;
     std::vector<PlanClass> cls;
@@ -728,6 +764,10 @@ extern "C" int svsr_conv_plan(int mode, int Nimg, int H, int W, int Co_out, int 
                         if (oy < 0 || oy >= Ho || ox < 0 || ox >= Wo) continue;
                         key.push_back(dq * Wo + dp);
                         key.push_back(kh * k + kw);
+                        if (mode == 3 && kh == 1 && kw == 1) {      // the 1x1 stride-2 branch: the same source pixel, the second operand pair
+                            key.push_back(dq * Wo + dp);
+                            key.push_back(IGEMM_TAP2);
+                        }
                     }
                 }
                 // the centre (a, b) of dy may lie outside its grid (odd H with stride 2): clamp it and fold the shift into nothing —
@@ -785,9 +825,11 @@ static int igemm_fwd_run(const void* in, const void* wt, void* out, void* out_pr
                          float* stats, const int* plan_dev, const int* meta, int Nimg, int in_pix, int Ci, int in_pitch, int Co,
                          int out_pix, int out_pitch, int wt_taps, int act, int out_f32, float alpha, const unsigned* drop_seed,
                          unsigned drop_site, float drop_p, const void* bnb_y, const void* bnb_x, const float* bnb_mean,
-                         const float* bnb_rstd, const float* bnb_gamma, const float* bnb_beta, int bnb_act, hipStream_t stream) {
+                         const float* bnb_rstd, const float* bnb_gamma, const float* bnb_beta, int bnb_act, hipStream_t stream,
+                         const void* in2 = nullptr, const void* wt2 = nullptr) {
     if (plan_dev == nullptr || meta == nullptr || Ci % 64 != 0 || Ci <= 0 || Co <= 0 || in_pitch % 8 != 0 || Nimg <= 0 || wt_taps < 1)
         return SVSR_ERR_ARG;
+    if ((in2 == nullptr) != (wt2 == nullptr)) return SVSR_ERR_ARG;
     if (act != 0 && (addend != nullptr || alpha != 1.f)) return SVSR_ERR_ARG;     // the activation is applied before alpha / addend
     IgemmFwdArgs a;
     a.in = (const bf16_t*)in; a.wt = (const bf16_t*)wt; a.out = out; a.out_pre = (bf16_t*)out_pre;
@@ -797,8 +839,20 @@ static int igemm_fwd_run(const void* in, const void* wt, void* out, void* out_pr
     a.drop = svsr_make_drop(drop_seed, drop_site, drop_p);
     a.bnb_y = (const bf16_t*)bnb_y; a.bnb_x = (const bf16_t*)bnb_x; a.bnb_mean = bnb_mean; a.bnb_rstd = bnb_rstd;
     a.bnb_gamma = bnb_gamma; a.bnb_beta = bnb_beta; a.bnb_act = bnb_act;
+    a.in2 = (const bf16_t*)in2; a.wt2 = (const bf16_t*)wt2;
     const int bm = meta[0], bn = meta[1], ns = meta[2], gx = meta[3], gy = (Co + bn - 1) / bn;
     if (gx < 1) return SVSR_ERR_ARG;
+    if (in2 != nullptr) {
+        // the instantiations svsr_conv_plan mode 3 can choose (classes of 1-4 taps: never the persistent kernel, never the single-tap forms)
+        if (bm == 64 && bn == 64 && svsr_igemm_fwd_kgroups(meta, Ci, Co, bnb_x != nullptr) == 2) return launch_glds<64, 64, 4, 2, true>(a, gx, gy, stream);
+#define SVSR_IGEMM_CASE2(BM_, BN_, NS_) if (bm == BM_ && bn == BN_ && ns == NS_) return launch_glds<BM_, BN_, NS_, 1, true>(a, gx, gy, stream)
+        SVSR_IGEMM_CASE2(128, 128, 2);
+        SVSR_IGEMM_CASE2(128, 64, 2);
+        SVSR_IGEMM_CASE2(64, 64, 4);
+        SVSR_IGEMM_CASE2(64, 64, 3);
+#undef SVSR_IGEMM_CASE2
+        return SVSR_ERR_ARG;
+    }
     if (bm == P8_BM) return (bnb_x != nullptr && alpha != 1.f) ? SVSR_ERR_ARG : igemm_p8_launch(a, meta, stream);      // (the persistent kernel's BatchNorm-backward epilogue has no scale)
     // few tiles, long contraction: split K inside the workgroup (see k_igemm_fwd_glds, KG = 2)
     if (svsr_igemm_fwd_kgroups(meta, Ci, Co, bnb_x != nullptr) == 2) {
@@ -854,4 +908,30 @@ extern "C" int svsr_igemm_dgrad_bn(const void* in, const void* wt, void* out, co
     if ((y == nullptr || act == 2) && (gamma == nullptr || beta == nullptr)) return SVSR_ERR_ARG;
     return igemm_fwd_run(in, wt, out, nullptr, nullptr, addend, stats, plan_dev, meta, Nimg, in_pix, Ci, in_pitch, Co, out_pix, out_pitch,
                          wt_taps, 0, 0, 1.0f, nullptr, 0, 0.f, y, x, mean, rstd, gamma, beta, act, stream);
+}
+
+/* svsr_igemm_dgrad2: the input gradient of a downsample block in one launch — the 3x3 / stride 2 / pad 1 data gradient of (in, wt) plus the
+ * 1x1 / stride 2 data gradient of (in2, wt2), summed in the fp32 accumulators and rounded once.  plan: svsr_conv_plan mode 3.  in2 has the
+ * geometry and pitch of `in`; wt2 = the 1x1 branch's transposed weight [Co][Ci].  Everything else as svsr_igemm_fwd without an addend. */
+extern "C" int svsr_igemm_dgrad2(const void* in, const void* wt, const void* in2, const void* wt2, void* out, void* out_pre, const float* bias,
+                                 float* stats, const int* plan_dev, const int* meta, int Nimg, int in_pix, int Ci, int in_pitch, int Co,
+                                 int out_pix, int out_pitch, int wt_taps, int act, int out_f32, float alpha, const unsigned* drop_seed,
+                                 unsigned drop_site, float drop_p, hipStream_t stream) {
+    if (in2 == nullptr || wt2 == nullptr) return SVSR_ERR_ARG;
+    return igemm_fwd_run(in, wt, out, out_pre, bias, nullptr, stats, plan_dev, meta, Nimg, in_pix, Ci, in_pitch, Co, out_pix, out_pitch,
+                         wt_taps, act, out_f32, alpha, drop_seed, drop_site, drop_p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, stream,
+                         in2, wt2);
+}
+
+/* svsr_igemm_dgrad2_bn: svsr_igemm_dgrad2 with the BatchNorm-backward epilogue of svsr_igemm_dgrad_bn on the merged accumulator. */
+extern "C" int svsr_igemm_dgrad2_bn(const void* in, const void* wt, const void* in2, const void* wt2, void* out, float* stats, const int* plan_dev,
+                                    const int* meta, int Nimg, int in_pix, int Ci, int in_pitch, int Co, int out_pix, int out_pitch,
+                                    int wt_taps, const void* y, const void* x, const float* mean, const float* rstd, const float* gamma,
+                                    const float* beta, int act, hipStream_t stream) {
+    if (in2 == nullptr || wt2 == nullptr) return SVSR_ERR_ARG;
+    if (x == nullptr || mean == nullptr || rstd == nullptr || stats == nullptr || Co % 8 != 0 || out_pitch % 8 != 0) return SVSR_ERR_ARG;
+    if (act != 1 && act != 2) return SVSR_ERR_ARG;
+    if ((y == nullptr || act == 2) && (gamma == nullptr || beta == nullptr)) return SVSR_ERR_ARG;
+    return igemm_fwd_run(in, wt, out, nullptr, nullptr, nullptr, stats, plan_dev, meta, Nimg, in_pix, Ci, in_pitch, Co, out_pix, out_pitch,
+                         wt_taps, 0, 0, 1.0f, nullptr, 0, 0.f, y, x, mean, rstd, gamma, beta, act, stream, in2, wt2);
 }

@@ -924,6 +924,38 @@ def conv2d_dgrad_bn(dy: torch.Tensor, w16t: torch.Tensor, k: int, stride: int, p
     return g, (stats, plan.tiles)
 
 
+DGRAD2 = True          # downsample blocks: the 1x1 branch's data gradient rides the 3x3 launch (False: two launches, the second adds to the first)
+
+
+def conv2d_dgrad2(dy: torch.Tensor, w16t: torch.Tensor, dy2: torch.Tensor, w16t2: torch.Tensor, in_hw: tuple[int, int], bn: Optional[tuple] = None):
+    """The input gradient of a downsample block in one launch: the 3x3 / stride 2 / pad 1 data gradient of (dy, w16t [Ci][3][3][Co]) plus the
+    1x1 / stride 2 data gradient of (dy2, w16t2 [Ci][Co]), both [N,Ho,Wo,Co], summed in fp32 and rounded once -> dx [N,H,W,Ci].
+    bn = (y, x, mean, rstd, gamma, beta, act): the epilogue of conv2d_dgrad_bn on the sum -> (g, (stats, rows))."""
+    N, Ho, Wo, Co = dy.shape
+    Ci = w16t.shape[0]
+    H, W = in_hw
+    if dy2.shape != dy.shape or not (dy.is_contiguous() and dy2.is_contiguous()) or w16t2.numel() != Ci * Co or w16t.numel() != Ci * 9 * Co:
+        raise ValueError("conv2d_dgrad2: dy2 must have dy's shape, the weights must be [Ci][3][3][Co] and [Ci][Co]")
+    plan = conv_plan(3, N, H, W, Ci, 3, 2, 1)
+    dx = torch.empty((N, H, W, Ci), dtype=BF16, device=dy.device)
+    flops = 2.0 * N * Ho * Wo * Co * Ci * 10
+    head = (_p(dy), _p(w16t), _p(dy2), _p(w16t2), _p(dx))
+    label = plan.label[:-1] + ",1,true>"          # the profiler's name of the two-operand instantiation
+    if bn is None:
+        _call("svsr_igemm_dgrad2", *head, None, None, None, plan.words.data_ptr(), plan.meta, N, Ho * Wo, Co, Co, Ci, H * W, Ci, 9, 0, 0, 1.0,
+              *_drop(None), _stream(), label=label, flops=flops)
+        return dx
+    y, x, mean, rstd, gamma, beta, act = bn
+    if x.shape != dx.shape or not x.is_contiguous() or (y is not None and (y.shape != x.shape or not y.is_contiguous())):
+        raise ValueError("conv2d_dgrad2: y / x must be contiguous tensors with the geometry of the result")
+    if (y is None or act == 2) and (gamma is None or beta is None):
+        raise ValueError("conv2d_dgrad2: y=None / act=2 need gamma and beta")
+    stats = scratch(plan.tiles * 2 * Ci)
+    _call("svsr_igemm_dgrad2_bn", *head, _p(stats), plan.words.data_ptr(), plan.meta, N, Ho * Wo, Co, Co, Ci, H * W, Ci, 9, _p(y), _p(x),
+          _p(mean), _p(rstd), _p(gamma), _p(beta), act, _stream(), label=label + "+bn", flops=flops)
+    return dx, (stats, plan.tiles)
+
+
 def bn_bwd_from_stats(g, x, mean, rstd, gamma, stats, coef, dgamma, dbeta) -> torch.Tensor:
     """Second half of the BatchNorm backward after conv2d_dgrad_bn: -> dx (gradient of the BatchNorm input x)."""
     part, rows = stats
