@@ -428,6 +428,22 @@ int svsr_adamw_step(float* p, const float* g, float* m, float* v, void* shadow, 
  * with advance != 0 — the last range of a step.  Lets a step update what the next forward needs first and the rest on another stream. */
 int svsr_adamw_range(float* p, const float* g, float* m, float* v, void* shadow, int64_t n, int64_t decay_end, float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, int warmup, int total_steps, void* opt_state, int advance, hipStream_t stream);
 
+/* AdamW under torch.optim.lr_scheduler.OneCycleLR stepped per batch with cycle_momentum (the DC-TCN recipe, lightning.py:314-334): the
+ * learning rate AND beta1 of a step are computed on the device from the step counter, with torch's phase arithmetic in double (phase ends
+ * pct_start * total_steps - 1, [2 * pct_start * total_steps - 2,] total_steps - 1; a phase starts where the one before it ended), and the
+ * bias correction 1 - beta1 ** step takes the step's own beta1.  No learning rate crosses the bus and nothing is read back.
+ * schedule: HOST record {double max_lr, initial_lr, min_lr, base_momentum, max_momentum, pct_start; int32 three_phase, cos_anneal,
+ * total_steps, reserved} (64 bytes), read during the call.
+ * opt_state: the struct of svsr_adamw_step followed by {float beta1_last; int error; int reserved[2]} (4128 bytes), zero-initialised;
+ * lr_last / beta1_last hold what the last counted step used.  The clip (max_norm > 0) reads svsr_grad_sumsq's partial sums; a step whose
+ * gradient norm is not finite is skipped as svsr_adamw_step skips it.  A launch whose counter is already total_steps (torch raises there)
+ * writes NOTHING, and the advancing launch sets `error` to 1001 instead of counting: the counter lives on the device, so that is where
+ * the error code is returned; the call itself returns 1001 for a schedule no step can be taken from (total_steps < 1, pct_start outside
+ * [0, 1], pct_start * total_steps == 1: torch divides by zero at step 0).  No atomics: a step's bits depend on its inputs only.
+ * _range: svsr_adamw_range's contract (pointers offset by the caller, decay_end relative to the range, advance != 0 on the last range). */
+int svsr_adamw_onecycle_step(float* p, const float* g, float* m, float* v, void* shadow, int64_t n, int64_t decay_end, float beta2, float eps, float weight_decay, float max_norm, const void* schedule, void* opt_state, hipStream_t stream);
+int svsr_adamw_onecycle_range(float* p, const float* g, float* m, float* v, void* shadow, int64_t n, int64_t decay_end, float beta2, float eps, float weight_decay, float max_norm, const void* schedule, void* opt_state, int advance, hipStream_t stream);
+
 /* bf16 shadows of fp32 parameters: plain cast, and a table-driven [A][T][B] -> [B][T][Apad] transpose-cast.
  * table: device array of {int64 src_off, dst_off; int32 A, T, Bd, Apad} (elements). */
 int svsr_cast_bf16(const float* src, void* dst, int64_t n, hipStream_t stream);

@@ -6,6 +6,7 @@ out) at B = 96 and B = 32, T = 29, 96 x 96.
     rocprofv3 --kernel-trace --stats -d <dir> -- python scripts/dctcn_bench.py --profile-only        # kernel table, in a run of its own
     python scripts/dctcn_bench.py --backward [--profile-only]      # forward + backward of the back-end and heads against eager bf16 autograd
     python scripts/dctcn_bench.py --train [--batches 96]           # the same in the training arithmetic (batch statistics, dropout) -> profiles/dctcn_train.json
+    python scripts/dctcn_bench.py --step [--batches 32]            # the WHOLE training step (dctcn_train.DCTCNTrainStep, 88 x 88) -> profiles/dctcn_step.json
 
 Times are wall-clock between device synchronisations (host dispatch included), the two implementations ALTERNATING round by round after
 warm-up of every shape; per implementation the median over rounds of the mean of `--iters` calls, and the minimum.  The convolution
@@ -38,10 +39,11 @@ class EagerDCTCN:
         self.W = {k: (v.to(dev).to(torch.bfloat16) if v.is_floating_point() else v.to(dev)) for k, v in sd.items()}
         self.dims = dims
         self.train, self.p_drop = False, 0.0          # --train: batch-statistic BatchNorm1d in the back-end, dropout0 / dropout1
+        self.train_frontend = False                   # --step: batch statistics in the front-end's norms too
 
     def bn(self, x, p):
         W = self.W
-        if self.train and p.startswith(TCN):
+        if self.train and (self.train_frontend or p.startswith(TCN)):
             return F.batch_norm(x, W[f"{p}.running_mean"], W[f"{p}.running_var"], W[f"{p}.weight"], W[f"{p}.bias"], True, 0.1, 1e-5)
         return F.batch_norm(x, W[f"{p}.running_mean"], W[f"{p}.running_var"], W[f"{p}.weight"], W[f"{p}.bias"], False, 0.0, 1e-5)
 
@@ -205,9 +207,111 @@ def backward_leg(a) -> None:
         f.write("\n")
 
 
+def step_leg(a) -> None:
+    """The whole training step at 88 x 88: dctcn_train.DCTCNTrainStep (mixup lam fixed, dropout on, clip, OneCycle AdamW) beside torch eager
+    bf16 autograd of the same model in .train() + clip_grad_norm_ + torch.optim.AdamW + OneCycleLR, alternating rounds.  Merges "timing"
+    into profiles/dctcn_step.json (the file also holds the bf16 floor of the tests): the commit, both medians, and the share of the step
+    the optimiser launches take (device events around the host calls: dispatch gaps included, an upper bound of the kernel time)."""
+    import subprocess
+
+    from syncvsr_amd import ops
+    from syncvsr_amd.dctcn import DCTCNLightningModule
+    from syncvsr_amd.dctcn_init import dctcn_dims, dctcn_init_state_dict, dctcn_synthetic_batch, default_dctcn_config
+    from syncvsr_amd.dctcn_train import DCTCNTrainStep
+
+    dev = torch.device("cuda:0")
+    cfg = default_dctcn_config(data__input_size=88, train__gradient_clip_val=1.0)
+    sd = dctcn_init_state_dict(cfg, seed=0)
+    total = 3 * (a.rounds * a.iters + 16)          # more steps than the run takes: the schedule never ends under the timer
+    lam, T, rows = 0.2, a.frames, []
+    for B in [int(v) for v in a.batches.split(",")]:
+        model = DCTCNLightningModule(cfg)
+        model.load_state_dict(sd)
+        model.to(dev).eval()
+        ts = DCTCNTrainStep(model, total, seed=1)
+        eager = EagerDCTCN(sd, dctcn_dims(cfg), dev)
+        eager.train = eager.train_frontend = True
+        eager.p_drop = float(cfg.model.dctcn.densetcn_options.dropout)
+        leaves = [v for k, v in eager.W.items() if v.is_floating_point() and "running_" not in k]
+        for v in leaves:
+            v.requires_grad_(True)
+        decay = [v for v in leaves if v.ndim > 1]
+        o = cfg.optim.optimizer
+        opt = torch.optim.AdamW([{"params": decay, "weight_decay": float(o.weight_decay)}, {"params": [v for v in leaves if v.ndim <= 1], "weight_decay": 0.0}],
+                                lr=1e-3, betas=tuple(float(b) for b in o.betas), eps=float(o.eps))
+        sch = torch.optim.lr_scheduler.OneCycleLR(opt, total_steps=total, **dict(cfg.optim.scheduler.items()))
+        batch = [t.to(dev) for t in dctcn_synthetic_batch(cfg, B, T, size=88, seed=B)]
+        videos, tokens, labels, wm, am = batch
+        A, V = model.audio_alignment, model.audio_vocab_size
+
+        def eager_step():
+            opt.zero_grad(set_to_none=True)
+            v = torch.lerp(videos, videos.roll(1, 0), lam)
+            logits, h = eager.backend(eager.frontend(v), wm, am, want_hidden=True)
+            la = F.linear(h.transpose(1, 2), eager.W["audio_projection.weight"], eager.W["audio_projection.bias"]).reshape(-1, V).float()
+            tok = tokens[:, : T * A]
+            lc = torch.lerp(F.cross_entropy(logits, labels), F.cross_entropy(logits, labels.roll(1, 0)), lam)
+            laud = torch.lerp(F.cross_entropy(la, tok.reshape(-1)), F.cross_entropy(la, tok.roll(1, 0).reshape(-1)), lam)
+            (lc + model.lambda_audio * laud).backward()
+            torch.nn.utils.clip_grad_norm_(leaves, 1.0)
+            opt.step()
+            sch.step()
+
+        fns = {"hip_step": lambda: ts.step(batch, lam=lam), "eager_step": eager_step}
+        for fn in fns.values():
+            _time(fn, 3)
+        if a.profile_only:
+            continue
+        samples = {k: [] for k in fns}
+        for _ in range(a.rounds):
+            for k, fn in fns.items():
+                samples[k].append(_time(fn, a.iters))
+        ops.start_event_timing()
+        ts.step(batch, lam=lam)
+        torch.cuda.synchronize()
+        ev = ops.stop_event_timing()
+        row = dict(B=B, T=T, size=88, lam=lam)
+        for k, v in samples.items():
+            row[f"{k}_ms_median"], row[f"{k}_ms_min"] = round(statistics.median(v), 4), round(min(v), 4)
+        row["eager_over_hip"] = round(row["eager_step_ms_median"] / row["hip_step_ms_median"], 3)
+        opt_ms = sum(v.get("ms", 0.0) for k, v in ev.items() if k in ("svsr_adamw_onecycle_step", "svsr_grad_sumsq"))
+        row["optimiser_event_ms"] = round(opt_ms, 4)
+        row["adamw_onecycle_event_ms"] = round(ev.get("svsr_adamw_onecycle_step", {}).get("ms", 0.0), 4)
+        row["optimiser_share_of_step"] = round(opt_ms / row["hip_step_ms_median"], 4)
+        row["launches"] = int(sum(v.get("launches", 0) for v in ev.values()))
+        row["parameters"] = int(model.store().numel)
+        row["state"] = ts.state()
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    if a.profile_only:
+        return
+    path = os.path.join(ROOT, "profiles", "dctcn_step.json") if a.out.endswith("dctcn_eval.json") else a.out
+    doc = {}
+    if os.path.exists(path):
+        with open(path) as f:
+            doc = json.load(f)
+    commit, dirty = a.commit, (True if a.dirty else None)
+    if commit is None:
+        try:
+            commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "HEAD"], capture_output=True, text=True).stdout.strip() or None
+            if commit is not None:
+                dirty = bool(subprocess.run(["git", "-C", ROOT, "status", "--porcelain", "-uno"], capture_output=True, text=True).stdout.strip())
+        except OSError:
+            commit = None
+    doc["timing"] = dict(what="DC-TCN whole training step (mixup, front-end + back-end forward and backward on batch statistics, dropout, clip 1.0, "
+                              "OneCycle AdamW) at 88 x 88: dctcn_train.DCTCNTrainStep vs torch eager bf16 autograd + torch.optim.AdamW + OneCycleLR of "
+                              "the same model, same process, alternating rounds (event ms: device events around host calls, not kernel times)",
+                         commit=commit, dirty=dirty, device=torch.cuda.get_device_name(0), rounds=a.rounds, iters=a.iters, rows=rows)
+    with open(path, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--batches", default="96,32")
+    ap.add_argument("--batches", default=None, help="comma-separated batch sizes (default 96,32; with --step 32, the one recorded shape)")
+    ap.add_argument("--commit", default=None, help="--step: the commit the tree was checked out from, for a run without a .git beside it")
+    ap.add_argument("--dirty", action="store_true", help="--step: the tree differs from that commit (without .git the script cannot tell)")
     ap.add_argument("--frames", type=int, default=29)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=50)
@@ -218,7 +322,13 @@ def main() -> None:
                     "(loss_and_backend_grads_from_features) against bf16 autograd of the eager modules -> profiles/dctcn_backward.json")
     ap.add_argument("--train", action="store_true", help="with --backward semantics, the training arithmetic: loss_and_backend_grads_from_features("
                     "train_stats=True, dropout_seed=...) beside eager bf16 autograd in .train() and the eval-statistics backward -> profiles/dctcn_train.json")
+    ap.add_argument("--step", action="store_true", help="the whole training step (dctcn_train.DCTCNTrainStep, 88 x 88) beside eager bf16 autograd + "
+                    "torch.optim.AdamW + OneCycleLR -> profiles/dctcn_step.json")
     a = ap.parse_args()
+    if a.batches is None:
+        a.batches = "32" if a.step else "96,32"
+    if a.step:
+        return step_leg(a)
     if a.train:
         return backward_leg(a)
     if a.backward:

@@ -4,7 +4,10 @@
 //     README.md:47-53)
 //   * top-1 / top-5 accuracy (lightning.py:177-183)
 //   * global-norm clip + AdamW + cosine schedule + bf16 shadow refresh (lightning.py:216-223)
+//   * the same AdamW under OneCycleLR, learning rate and beta1 from the device step counter (lightning.py:314-334, the DC-TCN recipe)
 //   * fp32 -> bf16 shadow casts / transposes of the weights the MFMA kernels consume
+#include <string.h>
+
 #include "common.h"
 #include "clip_sample.h"
 
@@ -207,6 +210,93 @@ __global__ __launch_bounds__(256) void k_opt_advance(OptState* st, float lr_base
     st->gnorm_last = sqrtf(sumsq);
     if (st->gnorm_last <= 3.0e38f) st->step += 1;
     else st->skipped += 1;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// AdamW under torch.optim.lr_scheduler.OneCycleLR (the DC-TCN recipe: timm create_optimizer_v2("adamw") + OneCycleLR stepped per batch,
+// cycle_momentum on: the schedule moves beta1 with the learning rate).  The device state is OptState followed by four more words.
+// ---------------------------------------------------------------------------------------------------------
+struct OneCycleState { OptState o; float beta1_last; int error; int reserved[2]; };
+struct OneCycle { double max_lr, initial_lr, min_lr, base_momentum, max_momentum, pct_start; int three_phase, cos_anneal, total_steps, reserved; };
+
+__device__ __forceinline__ double oc_anneal(const OneCycle& s, double start, double end, double pct) {
+    return s.cos_anneal ? end + (start - end) / 2.0 * (cos(3.141592653589793 * pct) + 1.0) : (end - start) * pct + start;
+}
+
+// OneCycleLR.get_lr at step_num = step, in double as torch computes it (the cosine's "+ 1" cancels near the end of a phase: fp32 there
+// would cost the last steps' learning rate two digits), rounded to fp32 once.  Phase ends are pct_start * total_steps - 1 (first),
+// 2 * pct_start * total_steps - 2 (second of three) and total_steps - 1; a phase is taken when step <= its end or it is the last one,
+// and a phase starts where the one before it ended (the first at 0): pct_start = 0 puts the first end at -1, so the last phase's pct is
+// (step + 1) / total_steps.
+__device__ __forceinline__ void onecycle_at(const OneCycle& s, int step, float* lr, float* beta1) {
+    const double ends[3] = {s.pct_start * (double)s.total_steps - 1.0,
+                            s.three_phase ? 2.0 * s.pct_start * (double)s.total_steps - 2.0 : (double)(s.total_steps - 1), (double)(s.total_steps - 1)};
+    const int nph = s.three_phase ? 3 : 2;
+    double start_step = 0.0, l = 0.0, b = 0.0;
+    for (int i = 0; i < nph; ++i) {
+        const double end_step = ends[i];
+        if ((double)step <= end_step || i == nph - 1) {
+            const double pct = ((double)step - start_step) / (end_step - start_step);
+            const bool up = i == 0, last3 = s.three_phase && i == 2;
+            const double lr0 = up ? s.initial_lr : last3 ? s.initial_lr : s.max_lr;
+            const double lr1 = up ? s.max_lr : (s.three_phase && i == 1) ? s.initial_lr : s.min_lr;
+            const double m0 = up ? s.max_momentum : last3 ? s.max_momentum : s.base_momentum;
+            const double m1 = up ? s.base_momentum : s.max_momentum;
+            l = oc_anneal(s, lr0, lr1, pct);
+            b = oc_anneal(s, m0, m1, pct);
+            break;
+        }
+        start_step = end_step;
+    }
+    *lr = (float)l; *beta1 = (float)b;
+}
+
+struct AdamOneCycleArgs {
+    float* p; const float* g; float* m; float* v; bf16_t* shadow;
+    long n, decay_end;
+    float beta2, eps, weight_decay, max_norm;
+    OneCycle sched;
+    OneCycleState* st;
+};
+
+__global__ __launch_bounds__(256) void k_adamw_onecycle(const AdamOneCycleArgs a) {
+    __shared__ float s4[4];
+    __shared__ float s_sched[2];
+    const int step = a.st->o.step;           // steps already taken
+    if (step >= a.sched.total_steps) return; // past the schedule (torch raises): nothing is written, k_onecycle_advance records the error
+    const float gnorm = sqrtf(opt_sumsq(&a.st->o, s4));
+    if (!(gnorm <= 3.0e38f)) return;         // a step whose gradient norm is not finite is skipped, as k_adamw skips it
+    if (threadIdx.x == 0) onecycle_at(a.sched, step, &s_sched[0], &s_sched[1]);
+    __syncthreads();
+    const float lr = s_sched[0], beta1 = s_sched[1];
+    const float clip = a.max_norm > 0.f ? fminf(1.f, a.max_norm / (gnorm + 1e-6f)) : 1.f;
+    const float t = (float)(step + 1);
+    const float bc1 = 1.f - powf(beta1, t), bc2 = 1.f - powf(a.beta2, t);        // torch: 1 - beta1 ** step with the step's current beta1
+    const float step_size = lr / bc1, inv_sqrt_bc2 = rsqrtf(bc2);
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (long)gridDim.x * 256) {
+        const float g = a.g[i] * clip;
+        float p = a.p[i];
+        if (i < a.decay_end) p *= 1.f - lr * a.weight_decay;
+        const float m = beta1 * a.m[i] + (1.f - beta1) * g;
+        const float v = a.beta2 * a.v[i] + (1.f - a.beta2) * g * g;
+        p -= step_size * m / (sqrtf(v) * inv_sqrt_bc2 + a.eps);
+        a.m[i] = m; a.v[i] = v; a.p[i] = p;
+        if (a.shadow != nullptr) a.shadow[i] = f2bf(p);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_onecycle_advance(OneCycleState* st, const OneCycle sched) {
+    __shared__ float s4[4];
+    const float sumsq = opt_sumsq(&st->o, s4);
+    if (threadIdx.x != 0) return;
+    if (st->o.step >= sched.total_steps) { st->error = SVSR_ERR_ARG; return; }
+    float lr, beta1;
+    onecycle_at(sched, st->o.step, &lr, &beta1);
+    st->o.lr_last = lr;
+    st->beta1_last = beta1;
+    st->o.gnorm_last = sqrtf(sumsq);
+    if (st->o.gnorm_last <= 3.0e38f) st->o.step += 1;
+    else st->o.skipped += 1;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -458,6 +548,31 @@ int svsr_adamw_step(float* p, const float* g, float* m, float* v, void* shadow, 
                     float beta1, float beta2, float eps, float weight_decay, float max_norm, int warmup, int total_steps,
                     void* opt_state, hipStream_t stream) {
     return svsr_adamw_range(p, g, m, v, shadow, n, decay_end, lr, beta1, beta2, eps, weight_decay, max_norm, warmup, total_steps, opt_state, 1, stream);
+}
+
+/* AdamW under OneCycleLR over one RANGE of the flat buffers (svsr_adamw_range's contract: pointers already offset, decay_end relative to
+ * the range, the counter advanced by the last range of a step only).  schedule: HOST record svsr_onecycle_t, read during the call.  The
+ * learning rate and beta1 of the step come from the device counter; a launch at a counter >= total_steps writes nothing, and the
+ * advancing launch then sets the state's error word instead of counting. */
+int svsr_adamw_onecycle_range(float* p, const float* g, float* m, float* v, void* shadow, int64_t n, int64_t decay_end, float beta2,
+                              float eps, float weight_decay, float max_norm, const void* schedule, void* opt_state, int advance,
+                              hipStream_t stream) {
+    if (schedule == nullptr || opt_state == nullptr || n < 0) return SVSR_ERR_ARG;
+    OneCycle s;
+    memcpy(&s, schedule, sizeof s);
+    if (s.total_steps < 1 || !(s.pct_start >= 0.0 && s.pct_start <= 1.0)) return SVSR_ERR_ARG;
+    if (s.pct_start * (double)s.total_steps - 1.0 == 0.0) return SVSR_ERR_ARG;      // step 0 would sit in a phase of length zero (torch divides by zero)
+    if (n > 0) {
+        AdamOneCycleArgs a{p, g, m, v, (bf16_t*)shadow, (long)n, (long)decay_end, beta2, eps, weight_decay, max_norm, s, (OneCycleState*)opt_state};
+        hipLaunchKernelGGL(k_adamw_onecycle, dim3(grid_for(n)), dim3(256), 0, stream, a);
+    }
+    if (advance) hipLaunchKernelGGL(k_onecycle_advance, dim3(1), dim3(256), 0, stream, (OneCycleState*)opt_state, s);
+    return svsr_check_launch();
+}
+
+int svsr_adamw_onecycle_step(float* p, const float* g, float* m, float* v, void* shadow, int64_t n, int64_t decay_end, float beta2,
+                             float eps, float weight_decay, float max_norm, const void* schedule, void* opt_state, hipStream_t stream) {
+    return svsr_adamw_onecycle_range(p, g, m, v, shadow, n, decay_end, beta2, eps, weight_decay, max_norm, schedule, opt_state, 1, stream);
 }
 
 int svsr_cast_bf16(const float* src, void* dst, int64_t n, hipStream_t stream) {

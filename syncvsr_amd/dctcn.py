@@ -6,9 +6,16 @@ consensus and the two heads.
 EVAL / INFERENCE PATH (``validation_step`` / ``test_step`` / ``inference.py``) and, in the same statistics mode, the gradients of the temporal
 network and the two heads (``loss_and_backend_grads``: fine-tuning with the front-end and the BatchNorm statistics frozen) — or, with
 ``train_stats=True``, in the reference's training arithmetic for the back-end: batch-statistic BatchNorm1d (over the chomped positions of
-the full-padding convolutions too), dropout0 / dropout1, mixup; the front-end stays frozen in eval statistics.  A forward under ``.train()``
-raises NotImplementedError (the front-end backward, engine.TrainStep and the OneCycle schedule are not built): it never runs a wrong forward
-silently.
+the full-padding convolutions too), dropout0 / dropout1, mixup; the front-end stays frozen in eval statistics there.
+
+WHOLE-MODEL TRAINING (``training_step``): ``loss_and_grads`` runs the front-end on batch statistics too (``model._frontend_forward`` in
+training mode: the stem's BatchNorm3d, every BatchNorm2d, the pooling arg-max windows kept), the taped back-end walk on those features, the
+back-end's backward and then ``model._frontend_backward`` from the gradient of the features: every parameter's ``.grad`` is a view of the
+store's flat fp32 gradient buffer and every running statistic is updated.  ``dctcn_train.DCTCNTrainStep`` puts mixup's draw, the device
+input pipeline, the global-norm clip and the OneCycle AdamW launch (``svsr_adamw_onecycle_step``) around it.  All of it is entered on a
+module in EVAL mode: the training arithmetic is an entry point, not a mode, and a forward under ``.train()`` raises NotImplementedError —
+it never runs a wrong forward silently.  Not built: native step lists, HIP-graph capture, data-parallel training, gradient accumulation
+across calls of the train step.
 
 ONE WALK, TWO STAGE SETS.  ``_backend`` is the only function that walks the network forward (transition0 -> per dense layer: SE gates, first
 stage, downsample, second stage -> transitions) and ``_backward`` the only one that walks it back; both serve every entry point in either
@@ -38,7 +45,7 @@ import torch
 from . import dropout, ops
 from .config import Config
 from .dctcn_init import (SE_REDUCTION, TCN, dctcn_buffer_specs, dctcn_dims, dctcn_init_state_dict, dctcn_layers, dctcn_param_specs)
-from .model import _frontend_forward, _ParamStore, _StoreModule
+from .model import _frontend_backward, _frontend_forward, _ParamStore, _StoreModule
 
 BF16 = torch.bfloat16
 
@@ -295,11 +302,13 @@ class DCTCNLightningModule(_StoreModule):
     def _run(self, videos: torch.Tensor, word_mask, attention_mask, keep: Optional[dict] = None, tape: Optional[dict] = None,
              feats: Optional[torch.Tensor] = None, train: Optional[dict] = None):
         """feats (bf16 [B*T, 512], with videos = the (B, T) pair): the front-end is skipped (loss_and_backend_grads_from_features).
-        train (loss_and_backend_grads(train_stats=True)): the back-end runs on batch statistics (_BatchStats); the front-end does not.  The
-        statistics mode is picked here, once per call; the walks only call the stage set."""
+        train (loss_and_backend_grads(train_stats=True), loss_and_grads): the back-end runs on batch statistics (_BatchStats); the front-end
+        does too when train carries a tape for it (train["fe_tape"]: loss_and_grads), otherwise it stays in eval statistics.  The statistics
+        mode is picked here, once per call; the walks only call the stage set."""
         if self.training:
-            raise NotImplementedError("DCTCNLightningModule: a forward under .train() is not built (the front-end has no backward yet): call .eval() "
-                                      "first; the back-end trains through loss_and_backend_grads(train_stats=True)")
+            raise NotImplementedError("DCTCNLightningModule: a forward under .train() is not built: call .eval() first; the whole model trains "
+                                      "through loss_and_grads / dctcn_train.DCTCNTrainStep and the back-end alone through "
+                                      "loss_and_backend_grads(train_stats=True), both on a module in eval mode")
         src = videos if feats is None else feats
         if src.device.type != "cuda":
             raise RuntimeError("syncvsr_amd runs on an MI355X HIP device only; there is no CPU fallback")
@@ -317,7 +326,10 @@ class DCTCNLightningModule(_StoreModule):
         C = self.dims["out_size"]
         with torch.no_grad():
             if feats is None:
-                feats = _frontend_forward(self, st, {}, videos.float().contiguous(), False)
+                fe_tape = None if train is None else train.get("fe_tape")          # batch statistics, pooling windows kept: loss_and_grads
+                feats = _frontend_forward(self, st, {} if fe_tape is None else fe_tape, videos.float().contiguous(), fe_tape is not None)
+                if tape is not None:
+                    tape["feats"] = feats
             stack = self._backend(S, feats, word_mask, B, T, keep, tape)
             scale, shift = S.norm5(None if tape is None else tape["rec"], stack, B, T)
             if attention_mask is None:
@@ -442,7 +454,10 @@ class DCTCNLightningModule(_StoreModule):
             self._put(*self._grad_of(st, bias, accumulate), dcb)
 
     def _loss_and_grads(self, videos, audios, labels, word_mask, attention_mask, loss_scale, accumulate, want_input_grad, feats=None,
-                        train_stats: bool = False, dropout_seed: Optional[int] = None, lam: float = 0.0, videos_mixed: bool = False):
+                        train_stats: bool = False, dropout_seed: Optional[int] = None, lam: float = 0.0, videos_mixed: bool = False,
+                        whole: bool = False):
+        """whole (loss_and_grads; train_stats and want_input_grad are then on): the front-end runs on batch statistics too and its backward
+        follows the back-end's."""
         tape: dict[str, Any] = {}
         train = None
         if videos_mixed and not train_stats:
@@ -453,6 +468,9 @@ class DCTCNLightningModule(_StoreModule):
                 raise ValueError("lam must lie in [0, 1]")
             p = float(self.config.model.dctcn.densetcn_options.get("dropout", 0.0)) if dropout_seed is not None else 0.0
             train = dict(lam=lam, seed=None if dropout_seed is None else int(dropout_seed), p=p)
+            if whole:
+                train["fe_tape"] = {}
+                self._drop_backward_state()          # what a call that aborted between its forward and the end of its backward left behind
             if lam and feats is None and not videos_mixed:
                 videos = torch.lerp(videos.float(), videos.float().roll(1, 0), lam)          # (word boundaries are not mixed)
         elif dropout_seed is not None or float(lam) != 0.0:
@@ -460,11 +478,59 @@ class DCTCNLightningModule(_StoreModule):
         out = self._losses(videos, audios, labels, word_mask, attention_mask, tape, feats, train)
         with torch.no_grad():
             gf = self._backward(tape, float(loss_scale), bool(accumulate), bool(want_input_grad))
+            if whole:
+                self._frontend_grads(tape["st"], train["fe_tape"], gf, bool(accumulate))
+                out["features"] = tape["feats"]
             if train is not None:
                 self._update_running(tape)
         if want_input_grad:
             out["grad_features"] = gf
         return out
+
+    def _frontend_spans(self, st: _ParamStore) -> list:
+        """The front-end's parameters as merged [lo, hi) element ranges of the flat buffers (two: its convolution weights open the decayed
+        region, its BatchNorm vectors the other one)."""
+        spans = st._vc.get("fe_spans")          # (kept with the store's cached views: the offsets never change while the store lives)
+        if spans is None:
+            spans = []
+            for lo, n in sorted(st.offsets[name][:2] for name, _, _ in self._specs if self._fwd_rank(name) < 2):
+                if spans and lo - spans[-1][1] < 4:          # (every tensor starts on a 16-byte boundary: up to three pad elements between two)
+                    spans[-1][1] = lo + n
+                else:
+                    spans.append([lo, lo + n])
+            st._vc["fe_spans"] = spans
+        return spans
+
+    def _frontend_grads(self, st: _ParamStore, fe_tape: dict, grad_features: torch.Tensor, accumulate: bool) -> None:
+        """model._frontend_backward from the gradient of the features: every launch of it ADDS into the flat gradient buffer, so the
+        front-end's ranges are zero-filled first (accumulate: left as they are, with _grad_of's rule for a .grad that is None or foreign).
+        The weight-gradient side stream stays off and no reducer is attached: the launches run in line, the gradient-ready notifications are
+        no-ops, and the trunk's chain of 3x3 weight gradients is closed by _frontend_backward itself (model._flush_w3_chain) before the stem."""
+        for name, _, _ in self._specs:
+            if self._fwd_rank(name) < 2:
+                self._grad_of(st, name, accumulate)
+        if not accumulate:
+            for lo, hi in self._frontend_spans(st):
+                ops.memset(st.grad[lo:hi], 0)
+        _frontend_backward(self, st, fe_tape, grad_features)
+        if self._w3_pending is not None:          # (cannot happen: _frontend_backward flushes; a gradient left in slabs would be silently short)
+            raise RuntimeError("loss_and_grads: a 3x3 weight-gradient chain is still pending")
+
+    def loss_and_grads(self, videos: torch.Tensor, audios: torch.Tensor, labels: torch.Tensor, word_mask: torch.Tensor,
+                       attention_mask: torch.Tensor, loss_scale: float = 1.0, accumulate: bool = False, dropout_seed: Optional[int] = None,
+                       lam: float = 0.0, videos_mixed: bool = False) -> dict[str, torch.Tensor]:
+        """The reference's training_step arithmetic for the WHOLE model, on a module in eval mode (as loss_and_backend_grads(train_stats=True)
+        is): model._frontend_forward in training mode (batch statistics in the stem's BatchNorm3d and every BatchNorm2d, the pooling arg-max
+        windows kept), the taped back-end walk on batch statistics over those features, the back-end's backward, then
+        model._frontend_backward from the gradient of the features.  Afterwards EVERY nn.Parameter has .grad = d(loss_total * loss_scale) /
+        d(param), a view of the store's flat fp32 gradient buffer (accumulate=True adds, with _grad_of's rule); the running statistics of
+        all BatchNorms are updated as a .train() forward of the reference updates them (momentum 0.1, unbiased variance,
+        num_batches_tracked: the front-end's inside its forward, the back-end's when the backward is through) and the folded eval
+        coefficients are stale until the next eval forward folds them again.  dropout_seed / lam / videos_mixed: as
+        loss_and_backend_grads(train_stats=True); mixup lerps the clips ahead of the front-end.  Beside the five metrics the dict carries
+        "features" (bf16 [B*T, 512], the training-mode front-end features) and "grad_features" (their gradient)."""
+        return self._loss_and_grads(videos, audios, labels, word_mask, attention_mask, loss_scale, accumulate, True, train_stats=True,
+                                    dropout_seed=dropout_seed, lam=lam, videos_mixed=videos_mixed, whole=True)
 
     def loss_and_backend_grads(self, videos: torch.Tensor, audios: torch.Tensor, labels: torch.Tensor, word_mask: torch.Tensor,
                                attention_mask: torch.Tensor, loss_scale: float = 1.0, accumulate: bool = False,

@@ -294,15 +294,22 @@ class _StoreModule(nn.Module):
         (ops.GradCoverage).  None declared: engine.TrainStep keeps the whole-buffer zero-fill."""
         return []
 
+    def _drop_backward_state(self) -> None:
+        """What a hand-written backward that aborted on a host exception left collected or postponed (linear weight gradients awaiting their
+        grouped launch, deferred reductions, the trunk's pending halo slabs, held-back notifications) is dropped, not issued: its closures
+        hold that pass's tensors and would add into this pass's gradients.  _begin_backward calls it; so does every backward that does not
+        go through _begin_backward (dctcn.DCTCNLightningModule.loss_and_grads)."""
+        self._wg_group = None
+        self._deferred.clear()
+        self._w3_pending = None
+        self._ready_held.clear()
+
 
 def _begin_backward(model: _StoreModule, st: "_ParamStore", dev: torch.device, *grads) -> tuple:
     """The first lines of a hand-written backward: the zero-fill (unless accumulate_into_grads), the p.grad views, and the incoming
     gradients as contiguous fp32 scalars (None: zero).  What a backward that aborted on a host exception left collected or postponed is
     dropped, not issued: its closures hold that pass's tensors and would add into this pass's gradients."""
-    model._wg_group = None
-    model._deferred.clear()
-    model._w3_pending = None
-    model._ready_held.clear()
+    model._drop_backward_state()
     if not model._keep_grads:
         st.zero_grad()
     st.rebind_grads()

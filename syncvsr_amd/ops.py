@@ -1637,6 +1637,107 @@ def adamw_range(p, g, m, v, shadow, lo: int, hi: int, decay_end: int, lr: float,
           lr, betas[0], betas[1], eps, weight_decay, max_norm, warmup, total_steps, _p(opt_state), int(advance), _stream())
 
 
+# -- AdamW under OneCycleLR (svsr_adamw_onecycle_step / _range): the DC-TCN recipe ----------------------------------------------
+ONECYCLE_STATE_WORDS = 4 + SUMSQ_PARTS + 4      # svsr_adamw_step's device state, then {beta1_last, error, 2 reserved words}
+
+
+class _OneCycleRecord(ctypes.Structure):
+    """svsr_onecycle_t of include/syncvsr_hip.h: the host record a launch reads the schedule's constants from."""
+    _fields_ = [(k, ctypes.c_double) for k in ("max_lr", "initial_lr", "min_lr", "base_momentum", "max_momentum", "pct_start")] + \
+               [(k, ctypes.c_int32) for k in ("three_phase", "cos_anneal", "total_steps", "reserved")]
+
+
+def onecycle_schedule(max_lr: float, total_steps: int, pct_start: float = 0.3, anneal_strategy: str = "cos", three_phase: bool = False,
+                      div_factor: float = 25.0, final_div_factor: float = 1e4, base_momentum: float = 0.85, max_momentum: float = 0.95) -> dict:
+    """OneCycleLR's constructor arguments (its names and defaults) -> the constants both the kernel and onecycle_values take."""
+    if anneal_strategy not in ("cos", "linear"):
+        raise ValueError(f"anneal_strategy must be one of 'cos' or 'linear', instead got {anneal_strategy}")
+    if not isinstance(total_steps, int) or total_steps <= 0:
+        raise ValueError(f"Expected positive integer total_steps, but got {total_steps}")
+    pct_start = float(pct_start)
+    if pct_start < 0 or pct_start > 1:
+        raise ValueError(f"Expected float between 0 and 1 pct_start, but got {pct_start}")
+    initial_lr = float(max_lr) / float(div_factor)
+    return dict(max_lr=float(max_lr), initial_lr=initial_lr, min_lr=initial_lr / float(final_div_factor), base_momentum=float(base_momentum),
+                max_momentum=float(max_momentum), pct_start=pct_start, three_phase=bool(three_phase), cos=anneal_strategy == "cos",
+                total_steps=total_steps)
+
+
+def onecycle_values(step: int, *, max_lr: float, initial_lr: float, min_lr: float, base_momentum: float, max_momentum: float, pct_start: float,
+                    three_phase: bool, cos: bool, total_steps: int) -> tuple[float, float]:
+    """(learning rate, beta1) of optimiser step `step` (0-based) as OneCycleLR.get_lr computes them at last_epoch = step, in Python
+    floats: the host restatement of what k_adamw_onecycle computes on the device (for logging and the tests).  A step past the schedule
+    raises ValueError as torch does; a phase of length zero divides by zero as torch does."""
+    import math
+
+    if not 0 <= step < total_steps:
+        raise ValueError(f"Tried to step {step + 1} times. The specified number of total steps is {total_steps}")
+    phases = [(float(pct_start * total_steps) - 1, initial_lr, max_lr, max_momentum, base_momentum)]
+    if three_phase:
+        phases += [(float(2 * pct_start * total_steps) - 2, max_lr, initial_lr, base_momentum, max_momentum),
+                   (total_steps - 1, initial_lr, min_lr, max_momentum, max_momentum)]
+    else:
+        phases += [(total_steps - 1, max_lr, min_lr, base_momentum, max_momentum)]
+
+    def anneal(start, end, pct):
+        if cos:
+            return end + (start - end) / 2.0 * (math.cos(math.pi * pct) + 1)
+        return (end - start) * pct + start
+
+    start_step = 0.0
+    for i, (end_step, lr0, lr1, m0, m1) in enumerate(phases):
+        if step <= end_step or i == len(phases) - 1:
+            pct = (step - start_step) / (end_step - start_step)
+            return anneal(lr0, lr1, pct), anneal(m0, m1, pct)
+        start_step = end_step
+    raise AssertionError("unreachable")
+
+
+_ONECYCLE_RECORDS: dict = {}
+
+
+def _onecycle_record(sched: dict):
+    """The host record of a schedule as a ctypes byte array (what a void* argument takes); cached for the life of the process (a recorded
+    step list keeps reading it)."""
+    key = tuple(sorted(sched.items()))
+    rec = _ONECYCLE_RECORDS.get(key)
+    if rec is None:
+        s = _OneCycleRecord(sched["max_lr"], sched["initial_lr"], sched["min_lr"], sched["base_momentum"], sched["max_momentum"],
+                            sched["pct_start"], int(sched["three_phase"]), int(sched["cos"]), int(sched["total_steps"]), 0)
+        rec = _ONECYCLE_RECORDS[key] = (ctypes.c_uint8 * ctypes.sizeof(s)).from_buffer_copy(bytes(s))
+    return rec
+
+
+def adamw_onecycle_step(p, g, m, v, shadow, decay_end: int, beta2: float, eps: float, weight_decay: float, max_norm: float, sched: dict,
+                        opt_state) -> None:
+    """One AdamW step over the whole flat buffers under the OneCycle schedule `sched` (onecycle_schedule); opt_state: int32
+    [ONECYCLE_STATE_WORDS], zero-initialised.  Nothing is read back: a step past the schedule leaves everything as it is and sets the
+    state's error word (onecycle_state)."""
+    assert opt_state.numel() >= ONECYCLE_STATE_WORDS and opt_state.dtype == torch.int32
+    _call("svsr_adamw_onecycle_step", _p(p), _p(g), _p(m), _p(v), _p(shadow), p.numel(), decay_end, beta2, eps, weight_decay, max_norm,
+          _onecycle_record(sched), _p(opt_state), _stream())
+
+
+def adamw_onecycle_range(p, g, m, v, shadow, lo: int, hi: int, decay_end: int, beta2: float, eps: float, weight_decay: float, max_norm: float,
+                         sched: dict, opt_state, advance: bool) -> None:
+    """The same over elements [lo, hi) of the flat buffers (decay_end: absolute end of the weight-decayed region)."""
+    assert opt_state.numel() >= ONECYCLE_STATE_WORDS and opt_state.dtype == torch.int32
+    n = hi - lo
+    dec = min(max(decay_end - lo, 0), n)
+    _call("svsr_adamw_onecycle_range", p.data_ptr() + 4 * lo, g.data_ptr() + 4 * lo, m.data_ptr() + 4 * lo, v.data_ptr() + 4 * lo,
+          None if shadow is None else shadow.data_ptr() + 2 * lo, n, dec, beta2, eps, weight_decay, max_norm, _onecycle_record(sched),
+          _p(opt_state), int(advance), _stream())
+
+
+def onecycle_state(opt_state: torch.Tensor) -> dict:
+    """The scalar words of the OneCycle optimiser's device state, read back (synchronises): steps taken, skipped steps, the learning rate,
+    beta1 and gradient norm of the last counted step, and the error word (0, or 1001 once a step past total_steps was asked for)."""
+    raw = opt_state.detach().cpu()
+    f = raw.view(torch.float32)
+    tail = 4 + SUMSQ_PARTS
+    return dict(step=int(raw[0]), skipped=int(raw[1]), lr=float(f[2]), gnorm=float(f[3]), beta1=float(f[tail]), error=int(raw[tail + 1]))
+
+
 def transpose_shadows_range(w16, dst, table: torch.Tensor, first: int, count: int) -> None:
     """Entries [first, first + count) of the transposed-shadow table (from the bf16 shadow)."""
     if count > 0:
