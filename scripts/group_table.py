@@ -32,7 +32,7 @@ def main():
         for r in csv.reader(l for l in f if not l.startswith("#")):
             if r and r[0] != "Name":
                 rows.append((r[0], int(r[1]), int(r[2])))
-    steps = int(sys.argv[2]) if len(sys.argv) > 2 else next(c for n, c, _ in rows if n.startswith("k_adamw"))
+    steps = int(sys.argv[2]) if len(sys.argv) > 2 else next(c for n, c, _ in rows if re.match(r"(void )?k_adamw", n))      # (a template's name carries its return type)
     tot = {g: [0, 0] for g, _ in GROUPS}
     other = [0, 0, []]
     for name, calls, ns in rows:

@@ -160,115 +160,49 @@ __global__ __launch_bounds__(256) void k_grad_sumsq(const float* __restrict__ g,
     if (threadIdx.x == 0) st->part[part0 + blockIdx.x] = ((spart[0] + spart[1]) + spart[2]) + spart[3];
 }
 
+// One AdamW update for every schedule: the shared fields travel in AdamArgs, the schedule beside it as a POLICY, which says whether optimiser step
+// `step` (0-based) may run, what lr and beta1 it uses (at), where k_adamw evaluates that (once_per_block), what the advance records (record / refuse).
 struct AdamArgs {
     float* p; const float* g; float* m; float* v; bf16_t* shadow;
     long n, decay_end;       // elements [0, decay_end) get weight decay (ndim >= 2 parameters)
-    float lr, beta1, beta2, eps, weight_decay, max_norm;
-    int warmup, total_steps;  // cosine schedule with linear warm-up; total_steps <= 0 -> constant lr
+    float beta2, eps, weight_decay, max_norm;
     OptState* st;
 };
 
-__device__ __forceinline__ float sched_lr(const AdamArgs& a, int step /* 0-based optimiser step index */) {
-    if (a.total_steps <= 0) return a.lr;
-    if (step < a.warmup) return a.lr * (float)step / (float)max(1, a.warmup);
-    const float prog = (float)(step - a.warmup) / (float)max(1, a.total_steps - a.warmup);
-    return a.lr * fmaxf(0.f, 0.5f * (1.f + cosf(3.14159265358979323846f * prog)));
-}
+// cosine schedule with linear warm-up (total_steps <= 0 -> constant lr), beta1 constant: a handful of fp32 operations, evaluated by every thread
+struct CosineSched {
+    static constexpr bool once_per_block = false;
+    float lr, beta1; int warmup, total_steps;
+    __device__ __forceinline__ bool runs(int) const { return true; }
+    __device__ __forceinline__ void at(int step, float* lr_out, float* beta1_out) const {
+        *beta1_out = beta1;
+        if (total_steps <= 0) { *lr_out = lr; return; }
+        if (step < warmup) { *lr_out = lr * (float)step / (float)max(1, warmup); return; }
+        const float prog = (float)(step - warmup) / (float)max(1, total_steps - warmup);
+        *lr_out = lr * fmaxf(0.f, 0.5f * (1.f + cosf(3.14159265358979323846f * prog)));
+    }
+    __device__ __forceinline__ void record(OptState*, float) const {}
+    __device__ __forceinline__ void refuse(OptState*) const {}
+};
 
-__global__ __launch_bounds__(256) void k_adamw(const AdamArgs a) {
+template <class Sched>
+__global__ __launch_bounds__(256) void k_adamw(const AdamArgs a, const Sched sched) {
     __shared__ float s4[4];
     const int step = a.st->step;             // steps already taken
+    if (!sched.runs(step)) return;           // nothing is written; the advancing launch records why (Sched::refuse)
     const float gnorm = sqrtf(opt_sumsq(a.st, s4));
     // A gradient norm that is not finite (a fused-encoder launch whose cluster wait gave up poisons its outputs with NaN: csrc/enc_fused.hip;
     // an overflow) would turn every parameter and both moments into NaN for good.  Such a step is SKIPPED: nothing is written, the step counter
     // does not advance (k_opt_advance counts it in `skipped`, TrainStep.state() reports it).  The reference (AdamW behind
     // clip_grad_norm_, lightning.py:216-223) would keep training on NaN parameters; there is nothing to be identical to.
     if (!(gnorm <= 3.0e38f)) return;
-    const float clip = a.max_norm > 0.f ? fminf(1.f, a.max_norm / (gnorm + 1e-6f)) : 1.f;
-    const float lr = sched_lr(a, step);
-    const float t = (float)(step + 1);
-    const float bc1 = 1.f - powf(a.beta1, t), bc2 = 1.f - powf(a.beta2, t);
-    const float step_size = lr / bc1, inv_sqrt_bc2 = rsqrtf(bc2);
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (long)gridDim.x * 256) {
-        const float g = a.g[i] * clip;
-        float p = a.p[i];
-        if (i < a.decay_end) p *= 1.f - lr * a.weight_decay;
-        const float m = a.beta1 * a.m[i] + (1.f - a.beta1) * g;
-        const float v = a.beta2 * a.v[i] + (1.f - a.beta2) * g * g;
-        p -= step_size * m / (sqrtf(v) * inv_sqrt_bc2 + a.eps);
-        a.m[i] = m; a.v[i] = v; a.p[i] = p;
-        if (a.shadow != nullptr) a.shadow[i] = f2bf(p);
-    }
-}
-
-__global__ __launch_bounds__(256) void k_opt_advance(OptState* st, float lr_base, int warmup, int total_steps) {
-    __shared__ float s4[4];
-    const float sumsq = opt_sumsq(st, s4);
-    if (threadIdx.x != 0) return;
-    AdamArgs a; a.lr = lr_base; a.warmup = warmup; a.total_steps = total_steps;
-    st->lr_last = sched_lr(a, st->step);
-    st->gnorm_last = sqrtf(sumsq);
-    if (st->gnorm_last <= 3.0e38f) st->step += 1;
-    else st->skipped += 1;
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// AdamW under torch.optim.lr_scheduler.OneCycleLR (the DC-TCN recipe: timm create_optimizer_v2("adamw") + OneCycleLR stepped per batch,
-// cycle_momentum on: the schedule moves beta1 with the learning rate).  The device state is OptState followed by four more words.
-// ---------------------------------------------------------------------------------------------------------
-struct OneCycleState { OptState o; float beta1_last; int error; int reserved[2]; };
-struct OneCycle { double max_lr, initial_lr, min_lr, base_momentum, max_momentum, pct_start; int three_phase, cos_anneal, total_steps, reserved; };
-
-__device__ __forceinline__ double oc_anneal(const OneCycle& s, double start, double end, double pct) {
-    return s.cos_anneal ? end + (start - end) / 2.0 * (cos(3.141592653589793 * pct) + 1.0) : (end - start) * pct + start;
-}
-
-// OneCycleLR.get_lr at step_num = step, in double as torch computes it (the cosine's "+ 1" cancels near the end of a phase: fp32 there
-// would cost the last steps' learning rate two digits), rounded to fp32 once.  Phase ends are pct_start * total_steps - 1 (first),
-// 2 * pct_start * total_steps - 2 (second of three) and total_steps - 1; a phase is taken when step <= its end or it is the last one,
-// and a phase starts where the one before it ended (the first at 0): pct_start = 0 puts the first end at -1, so the last phase's pct is
-// (step + 1) / total_steps.
-__device__ __forceinline__ void onecycle_at(const OneCycle& s, int step, float* lr, float* beta1) {
-    const double ends[3] = {s.pct_start * (double)s.total_steps - 1.0,
-                            s.three_phase ? 2.0 * s.pct_start * (double)s.total_steps - 2.0 : (double)(s.total_steps - 1), (double)(s.total_steps - 1)};
-    const int nph = s.three_phase ? 3 : 2;
-    double start_step = 0.0, l = 0.0, b = 0.0;
-    for (int i = 0; i < nph; ++i) {
-        const double end_step = ends[i];
-        if ((double)step <= end_step || i == nph - 1) {
-            const double pct = ((double)step - start_step) / (end_step - start_step);
-            const bool up = i == 0, last3 = s.three_phase && i == 2;
-            const double lr0 = up ? s.initial_lr : last3 ? s.initial_lr : s.max_lr;
-            const double lr1 = up ? s.max_lr : (s.three_phase && i == 1) ? s.initial_lr : s.min_lr;
-            const double m0 = up ? s.max_momentum : last3 ? s.max_momentum : s.base_momentum;
-            const double m1 = up ? s.base_momentum : s.max_momentum;
-            l = oc_anneal(s, lr0, lr1, pct);
-            b = oc_anneal(s, m0, m1, pct);
-            break;
-        }
-        start_step = end_step;
-    }
-    *lr = (float)l; *beta1 = (float)b;
-}
-
-struct AdamOneCycleArgs {
-    float* p; const float* g; float* m; float* v; bf16_t* shadow;
-    long n, decay_end;
-    float beta2, eps, weight_decay, max_norm;
-    OneCycle sched;
-    OneCycleState* st;
-};
-
-__global__ __launch_bounds__(256) void k_adamw_onecycle(const AdamOneCycleArgs a) {
-    __shared__ float s4[4];
-    __shared__ float s_sched[2];
-    const int step = a.st->o.step;           // steps already taken
-    if (step >= a.sched.total_steps) return; // past the schedule (torch raises): nothing is written, k_onecycle_advance records the error
-    const float gnorm = sqrtf(opt_sumsq(&a.st->o, s4));
-    if (!(gnorm <= 3.0e38f)) return;         // a step whose gradient norm is not finite is skipped, as k_adamw skips it
-    if (threadIdx.x == 0) onecycle_at(a.sched, step, &s_sched[0], &s_sched[1]);
-    __syncthreads();
-    const float lr = s_sched[0], beta1 = s_sched[1];
+    float lr, beta1;
+    if constexpr (Sched::once_per_block) {   // thread 0 evaluates, LDS broadcasts
+        __shared__ float s_sched[2];
+        if (threadIdx.x == 0) sched.at(step, &s_sched[0], &s_sched[1]);
+        __syncthreads();
+        lr = s_sched[0]; beta1 = s_sched[1];
+    } else sched.at(step, &lr, &beta1);
     const float clip = a.max_norm > 0.f ? fminf(1.f, a.max_norm / (gnorm + 1e-6f)) : 1.f;
     const float t = (float)(step + 1);
     const float bc1 = 1.f - powf(beta1, t), bc2 = 1.f - powf(a.beta2, t);        // torch: 1 - beta1 ** step with the step's current beta1
@@ -285,19 +219,67 @@ __global__ __launch_bounds__(256) void k_adamw_onecycle(const AdamOneCycleArgs a
     }
 }
 
-__global__ __launch_bounds__(256) void k_onecycle_advance(OneCycleState* st, const OneCycle sched) {
+template <class Sched>
+__global__ __launch_bounds__(256) void k_opt_advance(OptState* o, const Sched sched) {
     __shared__ float s4[4];
-    const float sumsq = opt_sumsq(&st->o, s4);
+    const float sumsq = opt_sumsq(o, s4);
     if (threadIdx.x != 0) return;
-    if (st->o.step >= sched.total_steps) { st->error = SVSR_ERR_ARG; return; }
+    if (!sched.runs(o->step)) { sched.refuse(o); return; }
     float lr, beta1;
-    onecycle_at(sched, st->o.step, &lr, &beta1);
-    st->o.lr_last = lr;
-    st->beta1_last = beta1;
-    st->o.gnorm_last = sqrtf(sumsq);
-    if (st->o.gnorm_last <= 3.0e38f) st->o.step += 1;
-    else st->o.skipped += 1;
+    sched.at(o->step, &lr, &beta1);
+    o->lr_last = lr;
+    sched.record(o, beta1);
+    o->gnorm_last = sqrtf(sumsq);
+    if (o->gnorm_last <= 3.0e38f) o->step += 1;
+    else o->skipped += 1;
 }
+
+// ---------------------------------------------------------------------------------------------------------
+// AdamW under torch.optim.lr_scheduler.OneCycleLR (the DC-TCN recipe: timm create_optimizer_v2("adamw") + OneCycleLR stepped per batch,
+// cycle_momentum on: the schedule moves beta1 with the learning rate).  The device state is OptState followed by four more words.
+// ---------------------------------------------------------------------------------------------------------
+struct OneCycleState { OptState o; float beta1_last; int error; int reserved[2]; };
+struct OneCycle { double max_lr, initial_lr, min_lr, base_momentum, max_momentum, pct_start; int three_phase, cos_anneal, total_steps, reserved; };
+
+__device__ __forceinline__ double oc_anneal(const OneCycle& s, double start, double end, double pct) {
+    return s.cos_anneal ? end + (start - end) / 2.0 * (cos(3.141592653589793 * pct) + 1.0) : (end - start) * pct + start;
+}
+
+// The policy: a step past the schedule does not run (torch raises), the advance then sets the error word; the doubles are evaluated once per block.
+struct OneCycleSched {
+    static constexpr bool once_per_block = true;
+    OneCycle s;
+    __device__ __forceinline__ bool runs(int step) const { return step < s.total_steps; }
+    // OneCycleLR.get_lr at step_num = step, in double as torch computes it (the cosine's "+ 1" cancels near the end of a phase: fp32 there
+    // would cost the last steps' learning rate two digits), rounded to fp32 once.  Phase ends are pct_start * total_steps - 1 (first),
+    // 2 * pct_start * total_steps - 2 (second of three) and total_steps - 1; a phase is taken when step <= its end or it is the last one,
+    // and a phase starts where the one before it ended (the first at 0): pct_start = 0 puts the first end at -1, so the last phase's pct is
+    // (step + 1) / total_steps.
+    __device__ __forceinline__ void at(int step, float* lr, float* beta1) const {
+        const double ends[3] = {s.pct_start * (double)s.total_steps - 1.0,
+                                s.three_phase ? 2.0 * s.pct_start * (double)s.total_steps - 2.0 : (double)(s.total_steps - 1), (double)(s.total_steps - 1)};
+        const int nph = s.three_phase ? 3 : 2;
+        double start_step = 0.0, l = 0.0, b = 0.0;
+        for (int i = 0; i < nph; ++i) {
+            const double end_step = ends[i];
+            if ((double)step <= end_step || i == nph - 1) {
+                const double pct = ((double)step - start_step) / (end_step - start_step);
+                const bool up = i == 0, last3 = s.three_phase && i == 2;
+                const double lr0 = up ? s.initial_lr : last3 ? s.initial_lr : s.max_lr;
+                const double lr1 = up ? s.max_lr : (s.three_phase && i == 1) ? s.initial_lr : s.min_lr;
+                const double m0 = up ? s.max_momentum : last3 ? s.max_momentum : s.base_momentum;
+                const double m1 = up ? s.base_momentum : s.max_momentum;
+                l = oc_anneal(s, lr0, lr1, pct);
+                b = oc_anneal(s, m0, m1, pct);
+                break;
+            }
+            start_step = end_step;
+        }
+        *lr = (float)l; *beta1 = (float)b;
+    }
+    __device__ __forceinline__ void record(OptState* o, float beta1) const { ((OneCycleState*)o)->beta1_last = beta1; }      // (o is the state's first member)
+    __device__ __forceinline__ void refuse(OptState* o) const { ((OneCycleState*)o)->error = SVSR_ERR_ARG; }
+};
 
 // ---------------------------------------------------------------------------------------------------------
 // shadow casts
@@ -478,6 +460,14 @@ __global__ __launch_bounds__(256) void k_clip_prep(const unsigned char* __restri
 
 static inline int grid_for(long n) { long b = (n + 255) / 256; if (b > 4096) b = 4096; if (b < 1) b = 1; return (int)b; }
 
+/* update if there is anything to update, advance if asked to, check the launch: the shape of every AdamW entry point */
+template <class Sched>
+static int adamw_launch(const AdamArgs& a, const Sched& sched, int advance, hipStream_t stream) {
+    if (a.n > 0) hipLaunchKernelGGL(k_adamw<Sched>, dim3(grid_for(a.n)), dim3(256), 0, stream, a, sched);
+    if (advance) hipLaunchKernelGGL(k_opt_advance<Sched>, dim3(1), dim3(256), 0, stream, a.st, sched);
+    return svsr_check_launch();
+}
+
 extern "C" {
 
 int svsr_colsum_rows(const float* ws, int nrows, int64_t ld, float* out0, int64_t n0, float* out1, int64_t n1, int accumulate, float scale,
@@ -535,13 +525,8 @@ int svsr_grad_sumsq_parts(const float* g, int64_t n, void* opt_state, int part0,
 int svsr_adamw_range(float* p, const float* g, float* m, float* v, void* shadow, int64_t n, int64_t decay_end, float lr,
                      float beta1, float beta2, float eps, float weight_decay, float max_norm, int warmup, int total_steps,
                      void* opt_state, int advance, hipStream_t stream) {
-    if (n > 0) {
-        AdamArgs a{p, g, m, v, (bf16_t*)shadow, (long)n, (long)decay_end, lr, beta1, beta2, eps, weight_decay, max_norm, warmup,
-                   total_steps, (OptState*)opt_state};
-        hipLaunchKernelGGL(k_adamw, dim3(grid_for(n)), dim3(256), 0, stream, a);
-    }
-    if (advance) hipLaunchKernelGGL(k_opt_advance, dim3(1), dim3(256), 0, stream, (OptState*)opt_state, lr, warmup, total_steps);
-    return svsr_check_launch();
+    const AdamArgs a{p, g, m, v, (bf16_t*)shadow, (long)n, (long)decay_end, beta2, eps, weight_decay, max_norm, (OptState*)opt_state};
+    return adamw_launch(a, CosineSched{lr, beta1, warmup, total_steps}, advance, stream);
 }
 
 int svsr_adamw_step(float* p, const float* g, float* m, float* v, void* shadow, int64_t n, int64_t decay_end, float lr,
@@ -558,16 +543,12 @@ int svsr_adamw_onecycle_range(float* p, const float* g, float* m, float* v, void
                               float eps, float weight_decay, float max_norm, const void* schedule, void* opt_state, int advance,
                               hipStream_t stream) {
     if (schedule == nullptr || opt_state == nullptr || n < 0) return SVSR_ERR_ARG;
-    OneCycle s;
-    memcpy(&s, schedule, sizeof s);
-    if (s.total_steps < 1 || !(s.pct_start >= 0.0 && s.pct_start <= 1.0)) return SVSR_ERR_ARG;
-    if (s.pct_start * (double)s.total_steps - 1.0 == 0.0) return SVSR_ERR_ARG;      // step 0 would sit in a phase of length zero (torch divides by zero)
-    if (n > 0) {
-        AdamOneCycleArgs a{p, g, m, v, (bf16_t*)shadow, (long)n, (long)decay_end, beta2, eps, weight_decay, max_norm, s, (OneCycleState*)opt_state};
-        hipLaunchKernelGGL(k_adamw_onecycle, dim3(grid_for(n)), dim3(256), 0, stream, a);
-    }
-    if (advance) hipLaunchKernelGGL(k_onecycle_advance, dim3(1), dim3(256), 0, stream, (OneCycleState*)opt_state, s);
-    return svsr_check_launch();
+    OneCycleSched sched;
+    memcpy(&sched.s, schedule, sizeof sched.s);
+    if (sched.s.total_steps < 1 || !(sched.s.pct_start >= 0.0 && sched.s.pct_start <= 1.0)) return SVSR_ERR_ARG;
+    if (sched.s.pct_start * (double)sched.s.total_steps - 1.0 == 0.0) return SVSR_ERR_ARG;      // step 0 would sit in a phase of length zero (torch divides by zero)
+    const AdamArgs a{p, g, m, v, (bf16_t*)shadow, (long)n, (long)decay_end, beta2, eps, weight_decay, max_norm, &((OneCycleState*)opt_state)->o};
+    return adamw_launch(a, sched, advance, stream);
 }
 
 int svsr_adamw_onecycle_step(float* p, const float* g, float* m, float* v, void* shadow, int64_t n, int64_t decay_end, float beta2,

@@ -25,8 +25,6 @@ from __future__ import annotations
 
 from typing import Optional
 
-import torch
-
 from . import ops
 from .dctcn import DCTCNLightningModule
 
@@ -49,20 +47,17 @@ class DCTCNTrainStep:
         if not bool(sch.get("cycle_momentum", True)):
             raise NotImplementedError("optim.scheduler.cycle_momentum = false is not built (the kernel always cycles beta1)")
         betas = [float(b) for b in opt.get("betas", (0.9, 0.999))]
-        self.beta2, self.eps, self.weight_decay = betas[1], float(opt.get("eps", 1e-8)), float(opt.get("weight_decay", 1e-2))
         self.schedule = ops.onecycle_schedule(float(sch["max_lr"]), int(total_steps), pct_start=float(sch.get("pct_start", 0.3)),
                                               anneal_strategy=str(sch.get("anneal_strategy", "cos")), three_phase=bool(sch.get("three_phase", False)),
                                               div_factor=float(sch.get("div_factor", 25.0)), final_div_factor=float(sch.get("final_div_factor", 1e4)),
                                               base_momentum=float(sch.get("base_momentum", 0.85)), max_momentum=float(sch.get("max_momentum", 0.95)))
         self.total_steps = int(total_steps)
         self.mixup_alpha = float(cfg.get_path("optim.mixup_alpha", 0.0))
-        self.max_norm = float(cfg.get_path("train.gradient_clip_val", 0.0) or 0.0)
         self.model, self.pipeline, self.seed = model, pipeline, int(seed)
-        st = model.store()
-        self.m = torch.zeros_like(st.flat)
-        self.v = torch.zeros_like(st.flat)
-        self.opt_state = torch.zeros(ops.ONECYCLE_STATE_WORDS, dtype=torch.int32, device=st.device)
-        self.steps = 0          # host mirror of the device counter: see the module docstring and resync()
+        self.adamw = ops.AdamW(model.store(), self.schedule, betas[1], float(opt.get("eps", 1e-8)), float(opt.get("weight_decay", 1e-2)),
+                               float(cfg.get_path("train.gradient_clip_val", 0.0) or 0.0))
+        self.m, self.v, self.opt_state = self.adamw.m, self.adamw.v, self.adamw.opt_state
+        self.steps = 0         # host mirror of the device counter: see the module docstring and resync()
 
     def values(self, step: Optional[int] = None) -> tuple:
         """(learning rate, beta1) of optimiser step `step` (default: the next one) on the host, for logging: ops.onecycle_values."""
@@ -93,10 +88,9 @@ class DCTCNTrainStep:
         st = model.store()
         if self.m.device != st.device or self.m.numel() != st.numel:
             raise RuntimeError("the model's parameter store changed under the optimiser state (moved to another device?)")
-        if self.max_norm > 0:
-            ops.grad_sumsq(st.grad, self.opt_state)
-        ops.adamw_onecycle_step(st.flat, st.grad, self.m, self.v, st.w16, st.decay_end, self.beta2, self.eps, self.weight_decay, self.max_norm,
-                                self.schedule, self.opt_state)
+        if self.adamw.max_norm > 0:
+            self.adamw.sumsq(st)
+        self.adamw.apply(st)
         self.steps += 1
         model.mark_params_dirty()          # the tap-major / transposed weight copies and the folded coefficients are rebuilt at the next forward
         return {k: out[k] for k in METRICS}
@@ -107,21 +101,19 @@ class DCTCNTrainStep:
         return self.steps
 
     def state(self) -> dict:
-        """The device state's scalar words (synchronises): ops.onecycle_state."""
-        return ops.onecycle_state(self.opt_state)
+        """The device state's scalar words (synchronises): step, skipped, lr, gnorm, beta1, error (ops.opt_state_words)."""
+        return self.adamw.state()
 
     def state_dict(self) -> dict:
         """AdamW's moments (flat fp32, parameter-store order) and the step counter with the rest of the device state."""
-        return {"exp_avg": self.m.detach().clone(), "exp_avg_sq": self.v.detach().clone(), "opt_state": self.opt_state.detach().clone(),
-                "steps": int(self.steps), "seed": int(self.seed), "total_steps": int(self.total_steps)}
+        return {**self.adamw.moments(), "steps": int(self.steps), "seed": int(self.seed), "total_steps": int(self.total_steps)}
 
     def load_state_dict(self, sd: dict) -> None:
         if sd["exp_avg"].numel() != self.m.numel() or sd["opt_state"].numel() != self.opt_state.numel():
             raise ValueError("optimiser state of another model")
         if int(sd["total_steps"]) != self.total_steps:
             raise ValueError(f"the state was saved under total_steps = {int(sd['total_steps'])}, this schedule has {self.total_steps}")
-        self.m.copy_(sd["exp_avg"])
-        self.v.copy_(sd["exp_avg_sq"])
+        self.adamw.load_moments(sd)
         self.opt_state.copy_(sd["opt_state"])
         self.seed = int(sd["seed"])
         self.resync()          # (the saved mirror, sd["steps"], may have run ahead of the counter: the device's count is the schedule's)

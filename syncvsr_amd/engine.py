@@ -183,13 +183,7 @@ class TrainStep:
         self.window = AccumWindow(accum)
         if accum > 1 or model._loss_scale != 1.0:
             model.set_loss_scale(1.0 / accum)          # the seeds of the backward: written in place, outside any recorded region
-        self.lr = float(opt.lr)
-        self.betas = (float(opt.betas[0]), float(opt.betas[1]))
-        self.eps = float(opt.eps)
-        self.weight_decay = float(opt.weight_decay)
-        self.max_norm = float(clip or 0.0)
-        self.warmup = int(sch.get("num_warmup_steps", 0) or 0)
-        self.total_steps = int(sch.get("num_training_steps", 0) or 0)
+        schedule = ops.CosineSchedule(float(opt.lr), float(opt.betas[0]), int(sch.get("num_warmup_steps", 0) or 0), int(sch.get("num_training_steps", 0) or 0))
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
         # always_reduce: run the collective path even for a 1-rank group (exercises RCCL + graph capture on one GPU)
         # data_parallel=False: a purely local step even inside an initialised process group (no collective is ever issued — e.g. the
@@ -231,12 +225,9 @@ class TrainStep:
         self._graph: Optional[torch.cuda.CUDAGraph] = None
         self._static: Optional[list[torch.Tensor]] = None
         self._out: Optional[dict[str, torch.Tensor]] = None
-        st = model.store()
-        dev = st.flat.device
-        self.m = torch.zeros_like(st.flat)
-        self.v = torch.zeros_like(st.flat)
-        # device state of the optimiser kernels: {step, sumsq, lr_last, gnorm_last, 1024 partial sums of squares}
-        self.opt_state = torch.zeros(4 + 1024, dtype=torch.int32, device=dev)
+        # the optimiser (moments, hyper-parameters, schedule, device state); m, v, opt_state name its tensors for model._early_sumsq and checkpoints
+        self.adamw = ops.AdamW(model.store(), schedule, float(opt.betas[1]), float(opt.eps), float(opt.weight_decay), float(clip or 0.0))
+        self.m, self.v, self.opt_state = self.adamw.m, self.adamw.v, self.adamw.opt_state
 
     # -- one eager step -----------------------------------------------------------------------------
     def _step_impl(self, *batch):
@@ -366,7 +357,7 @@ class TrainStep:
         behind the front-end (two thirds of the word-level model, 95 % of the sentence-level one) on the side stream, where this
         HBM-bound pass runs beside the next step's stem / trunk forward.  The model joins the side stream before its encoder runs and
         before state_dict(); the step counter advances behind the last range."""
-        model = self.model
+        model, adamw = self.model, self.adamw
         early_done = st.sumsq_tail_done  # the backward already summed the squares of everything behind the stem weight
         self._forget_early_sumsq(st)     # (a backward outside a step must not write this optimiser's state)
         stale = ops.end_grad_coverage()
@@ -378,21 +369,19 @@ class TrainStep:
             # two ranges, always the same two (one association whatever ran early): [head, n) -> partial sums 0..1022 — already summed on the
             # side stream beside the stem's weight gradient when the model could (model._early_sumsq) — and the stem weight -> partial 1023
             if not early_done:
-                ops.grad_sumsq_parts(st.grad, st.sumsq_head, st.numel - st.sumsq_head, self.opt_state, 0, ops.SUMSQ_PARTS - 1)
-            ops.grad_sumsq_parts(st.grad, 0, st.sumsq_head, self.opt_state, ops.SUMSQ_PARTS - 1, 1)
+                adamw.sumsq(st, st.sumsq_head, st.numel - st.sumsq_head, 0, ops.SUMSQ_PARTS - 1)
+            adamw.sumsq(st, 0, st.sumsq_head, ops.SUMSQ_PARTS - 1, 1)
         else:
-            ops.grad_sumsq(st.grad, self.opt_state)
+            adamw.sumsq(st)
         side = model._side
-        hp = (self.lr, self.betas, self.eps, self.weight_decay, self.max_norm, self.warmup, self.total_steps, self.opt_state)
         if not (side.enabled and st.front_end < st.decay_end):
-            ops.adamw_step(st.flat, st.grad, self.m, self.v, st.w16, st.decay_end, *hp)
+            adamw.apply(st)
             ops.transpose_shadows(st.flat, st.w16, st.w16t, st.table, st.n_entries)
         else:
-            bufs = (st.flat, st.grad, self.m, self.v, st.w16)
-            ops.adamw_range(*bufs, 0, st.front_end, st.decay_end, *hp, advance=False)
-            ops.adamw_range(*bufs, st.decay_end, st.numel, st.decay_end, *hp, advance=False)
+            adamw.apply(st, 0, st.front_end, advance=False)
+            adamw.apply(st, st.decay_end, st.numel, advance=False)
             nf = st.n_entries_front
-            side.run(lambda: (ops.adamw_range(*bufs, st.front_end, st.decay_end, st.decay_end, *hp, advance=True),
+            side.run(lambda: (adamw.apply(st, st.front_end, st.decay_end, advance=True),
                               ops.transpose_shadows_range(st.w16, st.w16t, st.table, nf, st.n_entries - nf)))
             ops.transpose_shadows_range(st.w16, st.w16t, st.table, 0, nf)
         st.shadow_fresh = True
@@ -696,7 +685,7 @@ class TrainStep:
         """Optimiser state for checkpointing (what Lightning stores next to the model's state_dict): AdamW moments as flat
         fp32 vectors in the parameter store's order, and the 16-byte device state {step, -, lr, grad-norm}."""
         self.synchronize()
-        sd = {"exp_avg": self.m.detach().clone(), "exp_avg_sq": self.v.detach().clone(), "opt_state": self.opt_state.detach().clone(),
+        sd = {**self.adamw.moments(),
               # what the order of the additions inside a weight gradient / a BatchNorm statistic depends on (ops.REDUCTION_KNOBS; the
               # compute-unit count the splits are planned for is one of them and is a fixed 256, not the device's): a resumed run is
               # bit-identical when these agree
@@ -715,10 +704,7 @@ class TrainStep:
 
     def load_state_dict(self, sd: dict[str, torch.Tensor]) -> None:
         self.synchronize()
-        if sd["exp_avg"].numel() != self.m.numel():
-            raise ValueError("optimiser state belongs to a different parameter layout")
-        self.m.copy_(sd["exp_avg"])
-        self.v.copy_(sd["exp_avg_sq"])
+        self.adamw.load_moments(sd)
         self.opt_state[:4].copy_(sd["opt_state"][:4])
         if "reduction_plan" in sd:
             then, now = [int(x) for x in sd["reduction_plan"].tolist()], ops.reduction_plan_params()
@@ -751,14 +737,12 @@ class TrainStep:
         gave up (csrc/enc_fused.hip) produces such a step; it is picked up here as well as before every step (_watch_fused_encoder): the
         encoder continues on the per-layer launch chain, with a warning."""
         self.synchronize()
-        raw = self.opt_state.cpu()
+        w = self.adamw.state()
         if self.is_lrw and ops.check_enc_clusters(reset=False):
             self._watch_fused_encoder()
         if not self.is_lrw:
             self.model.check_targets()          # a label outside [1, odim) reached svsr_lrs_targets: raises with the cause
-        f = raw.view(torch.float32)
-        return {"step": int(raw[0]), "lr": float(f[2]), "grad_norm": float(f[3]), "skipped_steps": int(raw[1]),
-                "micro_step": self.window.pos}
+        return {"step": w["step"], "lr": w["lr"], "grad_norm": w["gnorm"], "skipped_steps": w["skipped"], "micro_step": self.window.pos}
 
 
 def reduce_metrics(metrics, process_group=None):

@@ -10,6 +10,7 @@ import ctypes
 import os
 import struct
 from contextlib import contextmanager, nullcontext
+from collections import namedtuple
 from typing import Callable, Optional, Sequence
 
 import torch
@@ -1614,6 +1615,8 @@ def grad_sumsq(g: torch.Tensor, opt_state: torch.Tensor) -> None:
 
 
 SUMSQ_PARTS = 1024      # partial sums of squares in the optimiser's device state (loss_optim.hip OPT_PARTS)
+OPT_STATE_WORDS = 4 + SUMSQ_PARTS               # svsr_adamw_step's device state: {step, skipped, lr_last, gnorm_last}, then the partial sums
+ONECYCLE_STATE_WORDS = OPT_STATE_WORDS + 4      # svsr_adamw_onecycle_step's: the same, then {beta1_last, error, 2 reserved words}
 
 
 def grad_sumsq_parts(g: torch.Tensor, start: int, n: int, opt_state: torch.Tensor, part0: int, nparts: int) -> None:
@@ -1622,25 +1625,91 @@ def grad_sumsq_parts(g: torch.Tensor, start: int, n: int, opt_state: torch.Tenso
     _call("svsr_grad_sumsq_parts", g.data_ptr() + 4 * start, n, _p(opt_state), part0, nparts, _stream())
 
 
-def adamw_step(p, g, m, v, shadow, decay_end: int, lr: float, betas, eps: float, weight_decay: float, max_norm: float, warmup: int,
-               total_steps: int, opt_state) -> None:
-    _call("svsr_adamw_step", _p(p), _p(g), _p(m), _p(v), _p(shadow), p.numel(), decay_end, lr, betas[0], betas[1], eps, weight_decay,
-          max_norm, warmup, total_steps, _p(opt_state), _stream())
+# the schedule of svsr_adamw_step / _range: lr under a cosine with linear warm-up (total_steps <= 0: constant), beta1 constant
+CosineSchedule = namedtuple("CosineSchedule", "lr beta1 warmup total_steps", defaults=(0, 0))
 
 
-def adamw_range(p, g, m, v, shadow, lo: int, hi: int, decay_end: int, lr: float, betas, eps: float, weight_decay: float, max_norm: float, warmup: int,
-                total_steps: int, opt_state, advance: bool) -> None:
-    """AdamW over elements [lo, hi) of the flat buffers (decay_end: absolute end of the weight-decayed region)."""
-    n = hi - lo
-    dec = min(max(decay_end - lo, 0), n)
-    _call("svsr_adamw_range", p.data_ptr() + 4 * lo, g.data_ptr() + 4 * lo, m.data_ptr() + 4 * lo, v.data_ptr() + 4 * lo, shadow.data_ptr() + 2 * lo, n, dec,
-          lr, betas[0], betas[1], eps, weight_decay, max_norm, warmup, total_steps, _p(opt_state), int(advance), _stream())
+def adamw(p, g, m, v, shadow, decay_end: int, sched, beta2: float, eps: float, weight_decay: float, max_norm: float, opt_state,
+          lo: int = 0, hi: Optional[int] = None, advance: bool = True) -> None:
+    """One AdamW update (clip, bias correction, decoupled decay, bf16 shadow) of elements [lo, hi) of the flat buffers; decay_end: absolute end of
+    the decayed region; advance: count the step (the last range of a step only).  sched: a CosineSchedule (svsr_adamw_*, opt_state int32
+    [OPT_STATE_WORDS]) or onecycle_schedule's dict (svsr_adamw_onecycle_*, [ONECYCLE_STATE_WORDS]).  The whole buffer with advance is the `_step`
+    symbol, anything else `_range`.  Nothing is read back: a step that is skipped or past its schedule shows in opt_state_words."""
+    onecycle = isinstance(sched, dict)
+    assert opt_state.dtype == torch.int32 and opt_state.numel() >= (ONECYCLE_STATE_WORDS if onecycle else OPT_STATE_WORDS)
+    n = (p.numel() if hi is None else hi) - lo
+    whole = bool(advance) and lo == 0 and n == p.numel()
+    ptrs = [None if t is None else t.data_ptr() + t.element_size() * lo for t in (p, g, m, v, shadow)]
+    if onecycle:
+        name, hp = "svsr_adamw_onecycle", (beta2, eps, weight_decay, max_norm, _onecycle_record(sched))
+    else:
+        name, hp = "svsr_adamw", (sched.lr, sched.beta1, beta2, eps, weight_decay, max_norm, sched.warmup, sched.total_steps)
+    sym, dec, tail = (name + "_step", decay_end, ()) if whole else (name + "_range", min(max(decay_end - lo, 0), n), (int(advance),))
+    _call(sym, *ptrs, n, dec, *hp, _p(opt_state), *tail, _stream())
+
+
+# the four earlier wrappers' names and argument orders, kept for their callers (the kernel-level tests): each IS adamw
+def adamw_step(p, g, m, v, shadow, decay_end, lr, betas, eps, weight_decay, max_norm, warmup, total_steps, opt_state):
+    adamw(p, g, m, v, shadow, decay_end, CosineSchedule(lr, betas[0], warmup, total_steps), betas[1], eps, weight_decay, max_norm, opt_state)
+
+
+def adamw_range(p, g, m, v, shadow, lo, hi, decay_end, lr, betas, eps, weight_decay, max_norm, warmup, total_steps, opt_state, advance):
+    adamw(p, g, m, v, shadow, decay_end, CosineSchedule(lr, betas[0], warmup, total_steps), betas[1], eps, weight_decay, max_norm, opt_state, lo, hi, advance)
+
+
+def adamw_onecycle_step(p, g, m, v, shadow, decay_end, beta2, eps, weight_decay, max_norm, sched, opt_state):
+    adamw(p, g, m, v, shadow, decay_end, sched, beta2, eps, weight_decay, max_norm, opt_state)
+
+
+def adamw_onecycle_range(p, g, m, v, shadow, lo, hi, decay_end, beta2, eps, weight_decay, max_norm, sched, opt_state, advance):
+    adamw(p, g, m, v, shadow, decay_end, sched, beta2, eps, weight_decay, max_norm, opt_state, lo, hi, advance)
+
+
+def opt_state_words(opt_state: torch.Tensor) -> dict:
+    """The scalar words of the optimiser's device state, read back (synchronises): steps counted, skipped steps, lr and gradient norm of the last
+    advancing launch; of the OneCycle layout also that step's beta1 and the error word (0, or 1001 once a step past total_steps was asked for)."""
+    raw = opt_state.detach().cpu()
+    f = raw.view(torch.float32)
+    words = dict(step=int(raw[0]), skipped=int(raw[1]), lr=float(f[2]), gnorm=float(f[3]))
+    if raw.numel() >= ONECYCLE_STATE_WORDS:
+        words.update(beta1=float(f[OPT_STATE_WORDS]), error=int(raw[OPT_STATE_WORDS + 1]))
+    return words
+
+
+class AdamW:
+    """The optimiser of one flat parameter store, apart from whatever steps it: both moments, the device state, the hyper-parameters and the
+    schedule (a CosineSchedule or onecycle_schedule's dict).  `store`: the model's ParamStore.  sumsq: the clip's sum of squares of store.grad, all or
+    [start, start + n) into partial sums [part0, part0 + nparts).  load_moments: which words of the saved state come back is the step class's format."""
+
+    def __init__(self, store, sched, beta2: float, eps: float, weight_decay: float, max_norm: float):
+        self.sched, self.beta2, self.eps, self.weight_decay, self.max_norm = sched, float(beta2), float(eps), float(weight_decay), float(max_norm)
+        self.m, self.v = torch.zeros_like(store.flat), torch.zeros_like(store.flat)
+        self.opt_state = torch.zeros(ONECYCLE_STATE_WORDS if isinstance(sched, dict) else OPT_STATE_WORDS, dtype=torch.int32, device=store.flat.device)
+
+    def sumsq(self, store, start: int = 0, n: Optional[int] = None, part0: int = 0, nparts: int = SUMSQ_PARTS) -> None:
+        if n is None:
+            grad_sumsq(store.grad, self.opt_state)
+        else:
+            grad_sumsq_parts(store.grad, start, n, self.opt_state, part0, nparts)
+
+    def apply(self, store, lo: int = 0, hi: Optional[int] = None, advance: bool = True) -> None:
+        adamw(store.flat, store.grad, self.m, self.v, store.w16, store.decay_end, self.sched, self.beta2, self.eps, self.weight_decay,
+              self.max_norm, self.opt_state, lo, hi, advance)
+
+    def state(self) -> dict:
+        return opt_state_words(self.opt_state)
+
+    def moments(self) -> dict:
+        return {"exp_avg": self.m.detach().clone(), "exp_avg_sq": self.v.detach().clone(), "opt_state": self.opt_state.detach().clone()}
+
+    def load_moments(self, sd: dict) -> None:
+        if sd["exp_avg"].numel() != self.m.numel():
+            raise ValueError("optimiser state belongs to a different parameter layout")
+        self.m.copy_(sd["exp_avg"])
+        self.v.copy_(sd["exp_avg_sq"])
 
 
 # -- AdamW under OneCycleLR (svsr_adamw_onecycle_step / _range): the DC-TCN recipe ----------------------------------------------
-ONECYCLE_STATE_WORDS = 4 + SUMSQ_PARTS + 4      # svsr_adamw_step's device state, then {beta1_last, error, 2 reserved words}
-
-
 class _OneCycleRecord(ctypes.Structure):
     """svsr_onecycle_t of include/syncvsr_hip.h: the host record a launch reads the schedule's constants from."""
     _fields_ = [(k, ctypes.c_double) for k in ("max_lr", "initial_lr", "min_lr", "base_momentum", "max_momentum", "pct_start")] + \
@@ -1666,7 +1735,7 @@ def onecycle_schedule(max_lr: float, total_steps: int, pct_start: float = 0.3, a
 def onecycle_values(step: int, *, max_lr: float, initial_lr: float, min_lr: float, base_momentum: float, max_momentum: float, pct_start: float,
                     three_phase: bool, cos: bool, total_steps: int) -> tuple[float, float]:
     """(learning rate, beta1) of optimiser step `step` (0-based) as OneCycleLR.get_lr computes them at last_epoch = step, in Python
-    floats: the host restatement of what k_adamw_onecycle computes on the device (for logging and the tests).  A step past the schedule
+    floats: the host restatement of what k_adamw's OneCycleSched computes on the device (for logging and the tests).  A step past the schedule
     raises ValueError as torch does; a phase of length zero divides by zero as torch does."""
     import math
 
@@ -1708,34 +1777,7 @@ def _onecycle_record(sched: dict):
     return rec
 
 
-def adamw_onecycle_step(p, g, m, v, shadow, decay_end: int, beta2: float, eps: float, weight_decay: float, max_norm: float, sched: dict,
-                        opt_state) -> None:
-    """One AdamW step over the whole flat buffers under the OneCycle schedule `sched` (onecycle_schedule); opt_state: int32
-    [ONECYCLE_STATE_WORDS], zero-initialised.  Nothing is read back: a step past the schedule leaves everything as it is and sets the
-    state's error word (onecycle_state)."""
-    assert opt_state.numel() >= ONECYCLE_STATE_WORDS and opt_state.dtype == torch.int32
-    _call("svsr_adamw_onecycle_step", _p(p), _p(g), _p(m), _p(v), _p(shadow), p.numel(), decay_end, beta2, eps, weight_decay, max_norm,
-          _onecycle_record(sched), _p(opt_state), _stream())
-
-
-def adamw_onecycle_range(p, g, m, v, shadow, lo: int, hi: int, decay_end: int, beta2: float, eps: float, weight_decay: float, max_norm: float,
-                         sched: dict, opt_state, advance: bool) -> None:
-    """The same over elements [lo, hi) of the flat buffers (decay_end: absolute end of the weight-decayed region)."""
-    assert opt_state.numel() >= ONECYCLE_STATE_WORDS and opt_state.dtype == torch.int32
-    n = hi - lo
-    dec = min(max(decay_end - lo, 0), n)
-    _call("svsr_adamw_onecycle_range", p.data_ptr() + 4 * lo, g.data_ptr() + 4 * lo, m.data_ptr() + 4 * lo, v.data_ptr() + 4 * lo,
-          None if shadow is None else shadow.data_ptr() + 2 * lo, n, dec, beta2, eps, weight_decay, max_norm, _onecycle_record(sched),
-          _p(opt_state), int(advance), _stream())
-
-
-def onecycle_state(opt_state: torch.Tensor) -> dict:
-    """The scalar words of the OneCycle optimiser's device state, read back (synchronises): steps taken, skipped steps, the learning rate,
-    beta1 and gradient norm of the last counted step, and the error word (0, or 1001 once a step past total_steps was asked for)."""
-    raw = opt_state.detach().cpu()
-    f = raw.view(torch.float32)
-    tail = 4 + SUMSQ_PARTS
-    return dict(step=int(raw[0]), skipped=int(raw[1]), lr=float(f[2]), gnorm=float(f[3]), beta1=float(f[tail]), error=int(raw[tail + 1]))
+onecycle_state = opt_state_words          # (of a OneCycle optimiser's state: step, skipped, lr, gnorm, beta1, error)
 
 
 def transpose_shadows_range(w16, dst, table: torch.Tensor, first: int, count: int) -> None:

@@ -88,12 +88,15 @@ def test_new_symbols_are_declared_bound_and_exported():
     assert ctypes.sizeof(ops._OneCycleRecord) == 64 and ops.ONECYCLE_STATE_WORDS == 4 + ops.SUMSQ_PARTS + 4
     src = open(os.path.join(ROOT, "syncvsr_amd", "csrc", "loss_optim.hip")).read()
     body = src[src.index("struct OneCycleState"): src.index("// shadow casts")]
-    assert "void k_adamw_onecycle(" in body and "void k_onecycle_advance(" in body
+    # one update kernel and one advancing kernel, templates over the schedule policy; the OneCycle policy sits in the OneCycle section
+    assert src.count("void k_adamw(") == 1 and src.count("void k_opt_advance(") == 1 and "struct OneCycleSched {" in body
+    assert "k_adamw_onecycle" not in src and "k_onecycle_advance" not in src
+    assert src.count("beta2 * a.v[i]") == 1, "the update rule is written once"
     assert "atomic" not in body.lower(), "the OneCycle optimiser uses no atomics"
     assert "struct OneCycleState { OptState o; float beta1_last; int error; int reserved[2]; };" in body
-    # svsr_adamw_range / svsr_adamw_step are as they were: their kernel reads no OneCycle field
+    # svsr_adamw_range / svsr_adamw_step are as they were: what their kernels are instantiated with reads no OneCycle field
     old_body = src[src.index("struct AdamArgs"): src.index("// AdamW under torch.optim.lr_scheduler.OneCycleLR")]
-    assert "OneCycle" not in old_body
+    assert "struct CosineSched {" in old_body and "OneCycle" not in old_body
     if not os.path.exists(_lib.LIB_PATH):
         pytest.skip("library not built")
     lib = _lib.load()

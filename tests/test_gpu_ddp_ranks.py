@@ -128,9 +128,8 @@ def _definition(dev):
         for m, ts, b in reps:
             st = m.store()
             st.grad.copy_(g)
-            ops.grad_sumsq(st.grad, ts.opt_state)
-            ops.adamw_step(st.flat, st.grad, ts.m, ts.v, st.w16, st.decay_end, ts.lr, ts.betas, ts.eps, ts.weight_decay, ts.max_norm, ts.warmup,
-                           ts.total_steps, ts.opt_state)
+            ts.adamw.sumsq(st)
+            ts.adamw.apply(st)
             ops.transpose_shadows(st.flat, st.w16, st.w16t, st.table, st.n_entries)
             st.shadow_fresh = True
         reps[1][0].store().bufflat.copy_(reps[0][0].store().bufflat)          # broadcast_buffers: rank 0's running statistics
