@@ -7,6 +7,9 @@ out) at B = 96 and B = 32, T = 29, 96 x 96.
     python scripts/dctcn_bench.py --backward [--profile-only]      # forward + backward of the back-end and heads against eager bf16 autograd
     python scripts/dctcn_bench.py --train [--batches 96]           # the same in the training arithmetic (batch statistics, dropout) -> profiles/dctcn_train.json
     python scripts/dctcn_bench.py --step [--batches 32]            # the WHOLE training step (dctcn_train.DCTCNTrainStep, 88 x 88) -> profiles/dctcn_step.json
+    python scripts/dctcn_bench.py --step --gpus N [--accumulate M] # the step on N data-parallel ranks (torch.distributed.run, one GPU each; N = 1: the
+                                                                   # 1-rank always_reduce leg) -> profiles/dctcn_step_dp.json
+    python scripts/dctcn_bench.py --step --accumulate M            # windows of M micro-steps in one process -> profiles/dctcn_step_dp.json
 
 Times are wall-clock between device synchronisations (host dispatch included), the two implementations ALTERNATING round by round after
 warm-up of every shape; per implementation the median over rounds of the mean of `--iters` calls, and the minimum.  The convolution
@@ -212,8 +215,6 @@ def step_leg(a) -> None:
     bf16 autograd of the same model in .train() + clip_grad_norm_ + torch.optim.AdamW + OneCycleLR, alternating rounds.  Merges "timing"
     into profiles/dctcn_step.json (the file also holds the bf16 floor of the tests): the commit, both medians, and the share of the step
     the optimiser launches take (device events around the host calls: dispatch gaps included, an upper bound of the kernel time)."""
-    import subprocess
-
     from syncvsr_amd import ops
     from syncvsr_amd.dctcn import DCTCNLightningModule
     from syncvsr_amd.dctcn_init import dctcn_dims, dctcn_init_state_dict, dctcn_synthetic_batch, default_dctcn_config
@@ -290,14 +291,7 @@ def step_leg(a) -> None:
     if os.path.exists(path):
         with open(path) as f:
             doc = json.load(f)
-    commit, dirty = a.commit, (True if a.dirty else None)
-    if commit is None:
-        try:
-            commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "HEAD"], capture_output=True, text=True).stdout.strip() or None
-            if commit is not None:
-                dirty = bool(subprocess.run(["git", "-C", ROOT, "status", "--porcelain", "-uno"], capture_output=True, text=True).stdout.strip())
-        except OSError:
-            commit = None
+    commit, dirty = _commit(a)
     doc["timing"] = dict(what="DC-TCN whole training step (mixup, front-end + back-end forward and backward on batch statistics, dropout, clip 1.0, "
                               "OneCycle AdamW) at 88 x 88: dctcn_train.DCTCNTrainStep vs torch eager bf16 autograd + torch.optim.AdamW + OneCycleLR of "
                               "the same model, same process, alternating rounds (event ms: device events around host calls, not kernel times)",
@@ -307,8 +301,122 @@ def step_leg(a) -> None:
         f.write("\n")
 
 
+def _commit(a):
+    """(commit, dirty) of the tree: --commit / --dirty, else git's word."""
+    import subprocess
+
+    commit, dirty = a.commit, (True if a.dirty else None)
+    if commit is None:
+        try:
+            commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "HEAD"], capture_output=True, text=True).stdout.strip() or None
+            if commit is not None:
+                dirty = bool(subprocess.run(["git", "-C", ROOT, "status", "--porcelain", "-uno"], capture_output=True, text=True).stdout.strip())
+        except OSError:
+            commit = None
+    return commit, dirty
+
+
+def step_dp_launch(a) -> None:
+    """--step --gpus N: N ranks of step_dp_leg under torch.distributed.run, in a fresh child (this process never opens the GPU)."""
+    import subprocess
+
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--standalone", "--nnodes=1", f"--nproc_per_node={a.gpus}", os.path.abspath(__file__),
+           "--step", "--dp-rank", "--gpus", str(a.gpus), "--accumulate", str(a.accumulate), "--batches", a.batches, "--frames", str(a.frames),
+           "--rounds", str(a.rounds), "--iters", str(a.iters), "--bucket-mb", str(a.bucket_mb), "--out", a.out]
+    if a.commit is not None:
+        cmd += ["--commit", a.commit]
+    if a.dirty:
+        cmd.append("--dirty")
+    raise SystemExit(subprocess.run(cmd, cwd=ROOT).returncode)
+
+
+def step_dp_leg(a) -> None:
+    """The training step with a reducer attached and / or gradient accumulation, HIP only (no eager twin: step_leg has it).  As a rank
+    of --gpus N (one GPU per rank, the RCCL group bound to it with device_id=; N = 1: always_reduce) or, without a process group, as
+    the --accumulate M leg of one process.  A timed "step" is one optimiser step: M micro-steps of B clips each per rank.  Per batch size:
+    the median over rounds of the mean of --iters steps (wall clock between device synchronisations, warm-up first), the median time the
+    main stream waited at the reducer's join (dp.exposed_ms) and the buckets of a step (dp.bucket_times; medians, measured in a pass of
+    their own so that the events stay out of the step time), and last_reduce.  Rank 0 merges the row into profiles/dctcn_step_dp.json."""
+    import platform
+
+    import torch.distributed as dist
+
+    from syncvsr_amd.dctcn import DCTCNLightningModule
+    from syncvsr_amd.dctcn_init import dctcn_init_state_dict, dctcn_synthetic_batch, default_dctcn_config
+    from syncvsr_amd.dctcn_train import DCTCNTrainStep
+
+    ranked = bool(a.dp_rank)
+    rank, world, local = (int(os.environ[k]) for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK")) if ranked else (0, 1, 0)
+    dev = torch.device("cuda", local)
+    torch.cuda.set_device(dev)
+    if ranked:
+        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
+    cfg = default_dctcn_config(data__input_size=88, train__gradient_clip_val=1.0)
+    sd = dctcn_init_state_dict(cfg, seed=0)
+    M = int(a.accumulate)
+    total = 3 * (a.rounds * a.iters + 64)
+    lam, T, rows = 0.2, a.frames, []
+    for B in [int(v) for v in a.batches.split(",")]:
+        model = DCTCNLightningModule(cfg)
+        model.load_state_dict(sd)
+        model.to(dev).eval()
+        ts = DCTCNTrainStep(model, total, seed=1, always_reduce=ranked and world == 1, bucket_mb=a.bucket_mb, accumulate=M)
+        batch = [t.to(dev) for t in dctcn_synthetic_batch(cfg, B, T, size=88, seed=B + rank)]          # (a shard of its own per rank)
+
+        def window():
+            for _ in range(M):
+                ts.step(batch, lam=lam)
+
+        _time(window, 3)
+        samples = [_time(window, a.iters) for _ in range(a.rounds)]
+        row = dict(B_per_rank=B, T=T, size=88, lam=lam, ranks=world, accumulate=M, always_reduce=ranked and world == 1,
+                   step_ms_median=round(statistics.median(samples), 4), step_ms_min=round(min(samples), 4), step_ms_rounds=[round(v, 4) for v in samples],
+                   micro_step_ms_median=round(statistics.median(samples) / M, 4), measured=True)
+        if ts.dp is not None:
+            ts.dp.measure = True
+            _time(window, min(a.iters, 16))
+            row["exposed_ms"] = ts.dp.exposed_ms()
+            row["bucket_times"] = ts.dp.bucket_times()
+            row["last_reduce"] = ts.last_reduce
+            row["bucket_mb"] = a.bucket_mb
+            ts.dp.measure = False
+        row["state"] = ts.state()
+        rows.append(row)
+        if rank == 0:
+            print(json.dumps(row), flush=True)
+    if ranked:
+        dist.barrier()
+    if rank == 0:
+        path = os.path.join(ROOT, "profiles", "dctcn_step_dp.json") if a.out.endswith("dctcn_eval.json") else a.out
+        doc = {}
+        if os.path.exists(path):
+            with open(path) as f:
+                doc = json.load(f)
+        commit, dirty = _commit(a)
+        key = f"ranks{world}_accumulate{M}" if ranked else f"local_accumulate{M}"
+        doc.setdefault("legs", {})[key] = dict(
+            what="DC-TCN whole training step (dctcn_train.DCTCNTrainStep at 88 x 88, mixup, dropout, clip 1.0, OneCycle AdamW), one optimiser step = "
+                 "`accumulate` micro-steps of B_per_rank clips on each of `ranks` ranks" + ("; RCCL, one GPU per rank, group bound with device_id" if ranked else "; one process, no process group, no collective"),
+            commit=commit, dirty=dirty, box=platform.node(), device=torch.cuda.get_device_name(local), gpus_visible=torch.cuda.device_count(),
+            gpus_used=world, rounds=a.rounds, iters=a.iters, rows=rows)
+        if ranked and world == 1:
+            doc["legs"][key]["note"] = ("ONE rank: the collectives run inside a 1-rank group (always_reduce), so bucket times hold no link traffic; "
+                                        "no multi-GPU number exists in this file unless a ranksN leg with N > 1 says so")
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "w") as f:
+            json.dump(doc, f, indent=1)
+            f.write("\n")
+    if ranked:
+        dist.destroy_process_group()
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=0, help="--step: run the step on this many data-parallel ranks (torch.distributed.run, one GPU per "
+                    "rank; 1: the 1-rank always_reduce leg) -> profiles/dctcn_step_dp.json")
+    ap.add_argument("--accumulate", type=int, default=1, help="--step: windows of this many micro-steps (alone or with --gpus) -> profiles/dctcn_step_dp.json")
+    ap.add_argument("--bucket-mb", type=float, default=32.0, help="--step --gpus: the reducer's bucket size")
+    ap.add_argument("--dp-rank", action="store_true", help=argparse.SUPPRESS)          # set by --gpus for its ranks
     ap.add_argument("--batches", default=None, help="comma-separated batch sizes (default 96,32; with --step 32, the one recorded shape)")
     ap.add_argument("--commit", default=None, help="--step: the commit the tree was checked out from, for a run without a .git beside it")
     ap.add_argument("--dirty", action="store_true", help="--step: the tree differs from that commit (without .git the script cannot tell)")
@@ -327,6 +435,12 @@ def main() -> None:
     a = ap.parse_args()
     if a.batches is None:
         a.batches = "32" if a.step else "96,32"
+    if a.step and a.dp_rank:
+        return step_dp_leg(a)
+    if a.step and a.gpus > 0:
+        return step_dp_launch(a)
+    if a.step and a.accumulate > 1:
+        return step_dp_leg(a)
     if a.step:
         return step_leg(a)
     if a.train:

@@ -14,8 +14,8 @@ back-end's backward and then ``model._frontend_backward`` from the gradient of t
 store's flat fp32 gradient buffer and every running statistic is updated.  ``dctcn_train.DCTCNTrainStep`` puts mixup's draw, the device
 input pipeline, the global-norm clip and the OneCycle AdamW launch (``svsr_adamw_onecycle_step``) around it.  All of it is entered on a
 module in EVAL mode: the training arithmetic is an entry point, not a mode, and a forward under ``.train()`` raises NotImplementedError —
-it never runs a wrong forward silently.  Not built: native step lists, HIP-graph capture, data-parallel training, gradient accumulation
-across calls of the train step.
+it never runs a wrong forward silently.  The train step also runs data-parallel ranks (an engine.GradReducer fed by the backward's
+gradient-ready notifications) and gradient accumulation over windows of micro-steps.  Not built: native step lists, HIP-graph capture.
 
 ONE WALK, TWO STAGE SETS.  ``_backend`` is the only function that walks the network forward (transition0 -> per dense layer: SE gates, first
 stage, downsample, second stage -> transitions) and ``_backward`` the only one that walks it back; both serve every entry point in either
@@ -45,7 +45,7 @@ import torch
 from . import dropout, ops
 from .config import Config
 from .dctcn_init import (SE_REDUCTION, TCN, dctcn_buffer_specs, dctcn_dims, dctcn_init_state_dict, dctcn_layers, dctcn_param_specs)
-from .model import _frontend_backward, _frontend_forward, _ParamStore, _StoreModule
+from .model import _frontend_backward, _frontend_forward, _ParamStore, _ready, _StoreModule
 
 BF16 = torch.bfloat16
 
@@ -363,6 +363,8 @@ class DCTCNLightningModule(_StoreModule):
         """The eval forward; with a tape (loss_and_backend_grads) the same launches keep what the backward reads."""
         B, T = (videos.shape[0], videos.shape[2]) if feats is None else videos
         A, G, V = self.audio_alignment, self.vq_groups, self.audio_vocab_size
+        if tuple(labels.shape) != (B,):          # (the cross-entropy kernels read B labels: checked here, before anything is launched)
+            raise ValueError(f"labels must be [B] = [{B}], got {list(labels.shape)}")
         audios = self._tokenize_waveforms(audios, T * A)
         if audios.dtype != torch.int64 or audios.dim() != 3 or audios.size(2) != G:
             raise ValueError("pass pre-computed audio tokens int64 [B, >= A*T, 2] in the `audios` slot (no audio tokeniser is attached)")
@@ -479,6 +481,9 @@ class DCTCNLightningModule(_StoreModule):
         with torch.no_grad():
             gf = self._backward(tape, float(loss_scale), bool(accumulate), bool(want_input_grad))
             if whole:
+                # the back-end walk wrote the last of its parameters (transition0): everything above the front-end in the decayed region is
+                # final, and a reducer sends those buckets while the front-end's backward runs (no hook attached: nothing happens)
+                _ready(self, tape["st"], self._backend_first(tape["st"]))
                 self._frontend_grads(tape["st"], train["fe_tape"], gf, bool(accumulate))
                 out["features"] = tape["feats"]
             if train is not None:
@@ -501,11 +506,23 @@ class DCTCNLightningModule(_StoreModule):
             st._vc["fe_spans"] = spans
         return spans
 
+    def _backend_first(self, st: _ParamStore) -> str:
+        """The decayed tensor that opens the back-end's part of the flat buffers (at st.front_end): what the gradient-ready notification
+        behind the back-end's backward names."""
+        name = st._vc.get("be_first")
+        if name is None:
+            name = st._vc["be_first"] = min((st.offsets[n][0], n) for n, s, _ in self._specs if len(s) >= 2 and self._fwd_rank(n) == 2)[1]
+        return name
+
     def _frontend_grads(self, st: _ParamStore, fe_tape: dict, grad_features: torch.Tensor, accumulate: bool) -> None:
         """model._frontend_backward from the gradient of the features: every launch of it ADDS into the flat gradient buffer, so the
         front-end's ranges are zero-filled first (accumulate: left as they are, with _grad_of's rule for a .grad that is None or foreign).
-        The weight-gradient side stream stays off and no reducer is attached: the launches run in line, the gradient-ready notifications are
-        no-ops, and the trunk's chain of 3x3 weight gradients is closed by _frontend_backward itself (model._flush_w3_chain) before the stem."""
+        The weight-gradient side stream stays off: the launches run in line, and the trunk's chain of 3x3 weight gradients is closed by
+        _frontend_backward itself (model._flush_w3_chain) before the stem.  The gradient-ready notifications are no-ops unless a reducer is
+        attached (dctcn_train.DCTCNTrainStep under data parallelism).  The buckets it then has in flight hold back-end gradients only (the
+        notification behind _backward names the front-end's upper edge), and the zero-fill below touches front-end ranges only — the bottom
+        of the decayed region and the front-end's BatchNorm vectors in the 1-D tail, which no bucket holds before on_ready(0) — so it races
+        none of them; keep it that way."""
         for name, _, _ in self._specs:
             if self._fwd_rank(name) < 2:
                 self._grad_of(st, name, accumulate)
