@@ -200,6 +200,12 @@ int svsr_igemm_dgrad2(const void* in, const void* wt, const void* in2, const voi
 int svsr_igemm_dgrad2_bn(const void* in, const void* wt, const void* in2, const void* wt2, void* out, float* stats, const int* plan_dev, const int* meta, int Nimg, int in_pix, int Ci, int in_pitch, int Co, int out_pix, int out_pitch, int wt_taps, const void* y, const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int act, hipStream_t stream);
 int svsr_conv3x3_c64_dgrad_bn(const void* in, const void* wt, void* out, const void* addend, float* stats, int Nimg, int H, int W, const int* dy, const int* dx, const int* tw, const void* y, const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int act, const int* pixtab, hipStream_t stream);
 int svsr_bn_bwd_from_stats(const void* g, const void* x, const float* mean, const float* rstd, const float* gamma, const float* stats, int nrows, float* coef, float* dgamma, float* dbeta, void* dx, int64_t npix, int C, hipStream_t stream);
+/* The same for bn2 of a downsample block (resnet.py:36-53,69-72: out += downsample(x)), where g is the gradient of the 1x1 branch's BatchNorm
+ * output too: the apply pass reads that BatchNorm's input xd along and writes the first pass of ITS backward, the column sums of g and of
+ * g * (xd - mean_d) * rstd_d, into rows_d[svsr_bn_act_bwd_rows(npix, C)][2][C] — bit for bit the rows svsr_bn_act_bwd(g, NULL, xd, ..., act 0)
+ * forms.  svsr_bn_bwd_from_stats(g, xd, mean_d, rstd_d, gamma_d, rows_d, svsr_bn_act_bwd_rows(npix, C), ...) then finishes that branch.
+ * dx as svsr_bn_bwd_from_stats writes it.  rows_d may reuse the memory of `stats`.  Null pointers: SVSR_ERR_ARG. */
+int svsr_bn_bwd_from_stats_ds(const void* g, const void* x, const float* mean, const float* rstd, const float* gamma, const float* stats, int nrows, float* coef, float* dgamma, float* dbeta, void* dx, const void* xd, const float* mean_d, const float* rstd_d, float* rows_d, int64_t npix, int C, hipStream_t stream);
 
 
 /* svsr_conv3x3_wgrad: weight gradient of a 3x3 / stride-1 / pad-1 Conv2d (resnet.py:8-10) with all nine taps sharing one
@@ -256,6 +262,10 @@ int svsr_bn_eval_prepare(const float* running_mean, const float* running_var, in
  * transformer/convolution.py:69); any C % 8 == 0 up to 2048.  Replaces bn1/relu1, bn2/+residual/relu2 and the
  * downsample BatchNorm of BasicBlock.forward (resnet.py:59-72). */
 int svsr_bn_act_fwd(const void* x, const void* res, void* y, const float* mean, const float* rstd, const float* gamma, const float* beta, int64_t npix, int C, int act, hipStream_t stream);
+/* The block-end pass of a downsample block in the ReLU trunk (resnet.py:65-72), both BatchNorms in one launch:
+ * y = relu(bn(x) + bf16(bn_d(xd))), the downsample term rounded to bf16 as the stored tensor was — the bits of
+ * svsr_bn_act_fwd(x, res = svsr_bn_act_fwd(xd, NULL, act 0), act 1) without writing that tensor.  Null x / xd / y: SVSR_ERR_ARG. */
+int svsr_bn_act_fwd2(const void* x, const void* xd, void* y, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* mean_d, const float* rstd_d, const float* gamma_d, const float* beta_d, int64_t npix, int C, hipStream_t stream);
 
 /* backward of the above: dgamma/dbeta accumulated; dx (grad of the conv output) and optional dres (= masked dy).
  * slots: workspace of svsr_bn_act_bwd_rows(npix, C) rows of [2][C] floats (any contents); coef [3][C] scratch.  Swish recomputes its

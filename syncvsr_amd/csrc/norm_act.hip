@@ -122,6 +122,41 @@ __global__ __launch_bounds__(256) void k_bn_act_fwd(const bf16_t* __restrict__ x
     }
 }
 
+// The block-end pass of a downsample block (ReLU trunk): y = relu(bn2(x) + bf16(bn_d(xd))), the residual branch's BatchNorm applied
+// where it is consumed instead of by a launch of its own that writes it out.  The downsample term goes through the bf16 rounding the
+// stored tensor went through and the first fma and the ReLU are k_bn_act_fwd's: y has the bits of
+// k_bn_act_fwd(x, res = k_bn_act_fwd(xd, act 0), act 1).
+__global__ __launch_bounds__(256) void k_bn_act_fwd2(const bf16_t* __restrict__ x, const bf16_t* __restrict__ xd, bf16_t* __restrict__ y,
+                                                     const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                     const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                     const float* __restrict__ mean_d, const float* __restrict__ rstd_d,
+                                                     const float* __restrict__ gamma_d, const float* __restrict__ beta_d, long nvec, int C) {
+    const int cv = C >> 3;
+    long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    const long stride = (long)gridDim.x * 256;
+    if (idx >= nvec) return;
+    const int c0 = (int)(idx % cv) * 8;
+    float sc[8], sh[8], scd[8], shd[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        sc[k] = gamma[c0 + k] * rstd[c0 + k];
+        sh[k] = __builtin_fmaf(-mean[c0 + k], sc[k], beta[c0 + k]);
+        scd[k] = gamma_d[c0 + k] * rstd_d[c0 + k];
+        shd[k] = __builtin_fmaf(-mean_d[c0 + k], scd[k], beta_d[c0 + k]);
+    }
+    for (; idx < nvec; idx += stride) {
+        float f[8], d[8], r[8];
+        unpack8(reinterpret_cast<const u32x4*>(x)[idx], f);
+        unpack8(reinterpret_cast<const u32x4*>(xd)[idx], d);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { f[k] = __builtin_fmaf(f[k], sc[k], sh[k]); d[k] = __builtin_fmaf(d[k], scd[k], shd[k]); }
+        unpack8(pack8(d), r);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) f[k] = fmaxf(f[k] + r[k], 0.f);
+        reinterpret_cast<u32x4*>(y)[idx] = pack8(f);
+    }
+}
+
 // block-level reduction of per-thread 8-channel partials into this workgroup's row of the partials [rows][2][C]
 // (fixed order inside the block; k_bn_bwd_finalize adds the rows in a fixed order)
 __device__ __forceinline__ void reduce_to_row(float* sred, const float* s1, const float* s2, int cv, int C, float* part,
@@ -248,6 +283,42 @@ __global__ __launch_bounds__(256) void k_bn_act_bwd_apply(const bf16_t* __restri
         reinterpret_cast<u32x4*>(dx)[idx] = pack8(o);
         if (dres != nullptr) reinterpret_cast<u32x4*>(dres)[idx] = pack8(g);
     }
+}
+
+// pass 2 of bn2 in a downsample block (ReLU trunk): g is also the gradient of the 1x1 branch's BatchNorm output, so while it is in
+// registers the pass reads that BatchNorm's input xd along and leaves ITS pass 1 behind — the rows k_bn_act_bwd_reduce<0>(g, xd) writes,
+// bit for bit: launched on that kernel's grid, same per-thread order, same row reduction.  dx as k_bn_act_bwd_apply<0> writes it (an
+// element's value does not depend on the grid).  No early exit: every thread reaches reduce_to_row's barrier, a thread past the end adds zeros.
+__global__ __launch_bounds__(256) void k_bn_bwd_apply_ds(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
+                                                         const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                         const float* __restrict__ coef, bf16_t* __restrict__ dx,
+                                                         const bf16_t* __restrict__ xd, const float* __restrict__ mean_d,
+                                                         const float* __restrict__ rstd_d, float* slots_d, long nvec, int C) {
+    __shared__ float sred[256 * 16];
+    const int cv = C >> 3;
+    long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    const long stride = (long)gridDim.x * 256;       // a multiple of cv (host): a thread keeps its channel group
+    const int c0 = (int)(idx % cv) * 8;
+    const int first_group = (int)(((long)blockIdx.x * 256) % cv);
+    float mu[8], rs[8], k0[8], k1[8], k2[8], mud[8], rsd[8], s1[8], s2[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        mu[k] = mean[c0 + k]; rs[k] = rstd[c0 + k];
+        k0[k] = coef[c0 + k]; k1[k] = coef[C + c0 + k]; k2[k] = coef[2 * C + c0 + k];
+        mud[k] = mean_d[c0 + k]; rsd[k] = rstd_d[c0 + k]; s1[k] = 0.f; s2[k] = 0.f;
+    }
+    for (; idx < nvec; idx += stride) {
+        float g[8], xv[8], xdv[8], o[8];
+        unpack8(reinterpret_cast<const u32x4*>(dy)[idx], g);
+        unpack8(reinterpret_cast<const u32x4*>(x)[idx], xv);
+        unpack8(reinterpret_cast<const u32x4*>(xd)[idx], xdv);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o[k] = k0[k] * (g[k] - k1[k] - (xv[k] - mu[k]) * rs[k] * k2[k]);
+        reinterpret_cast<u32x4*>(dx)[idx] = pack8(o);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { s1[k] += g[k]; s2[k] += g[k] * (xdv[k] - mud[k]) * rsd[k]; }
+    }
+    reduce_to_row(sred, s1, s2, cv, C, slots_d, first_group);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -758,6 +829,16 @@ int svsr_bn_act_fwd(const void* x, const void* res, void* y, const float* mean, 
     return svsr_check_launch();
 }
 
+/* y = relu(bn(x) + bf16(bn_d(xd))): svsr_bn_act_fwd(x, res = svsr_bn_act_fwd(xd, act 0), act 1) in one launch, the same bits */
+int svsr_bn_act_fwd2(const void* x, const void* xd, void* y, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                     const float* mean_d, const float* rstd_d, const float* gamma_d, const float* beta_d, int64_t npix, int C, hipStream_t stream) {
+    if (!chan_ok_any(C) || npix < 1 || x == nullptr || xd == nullptr || y == nullptr) return SVSR_ERR_ARG;
+    const long nvec = npix * (C / 8);
+    hipLaunchKernelGGL(k_bn_act_fwd2, dim3(ew_grid_for(nvec, C)), dim3(256), 0, stream, (const bf16_t*)x, (const bf16_t*)xd, (bf16_t*)y,
+                       mean, rstd, gamma, beta, mean_d, rstd_d, gamma_d, beta_d, nvec, C);
+    return svsr_check_launch();
+}
+
 /* rows of [2][C] partials svsr_bn_act_bwd needs in its workspace for this shape */
 int svsr_bn_act_bwd_rows(int64_t npix, int C) { return chan_ok_any(C) && npix > 0 ? bn_bwd_grid(npix * (C / 8), C) : 0; }
 
@@ -790,6 +871,22 @@ int svsr_bn_bwd_from_stats(const void* g, const void* x, const float* mean, cons
     hipLaunchKernelGGL(k_bn_bwd_finalize, dim3((C + BNF_CL - 1) / BNF_CL), dim3(BNF_CL * BNF_RL), 0, stream, stats, nrows, C, (float)npix, gamma, rstd, dgamma, dbeta, coef);
     hipLaunchKernelGGL(k_bn_act_bwd_apply<0>, dim3(ew_grid_for(nvec, C)), dim3(256), 0, stream, (const bf16_t*)g, (const bf16_t*)nullptr,
                        (const bf16_t*)x, mean, rstd, coef, (bf16_t*)dx, (bf16_t*)nullptr, nvec, C, gamma, (const float*)nullptr, (const bf16_t*)nullptr);
+    return svsr_check_launch();
+}
+
+/* svsr_bn_bwd_from_stats for bn2 of a downsample block: g is the gradient of the 1x1 branch's BatchNorm output as well, and the apply pass
+ * takes that BatchNorm's first pass along — xd its input, mean_d / rstd_d its statistics, rows_d: svsr_bn_act_bwd_rows(npix, C) rows of
+ * [2][C] written with the bits svsr_bn_act_bwd(g, NULL, xd, ..., act 0)'s reduce pass leaves.  svsr_bn_bwd_from_stats(g, xd, ..., rows_d,
+ * svsr_bn_act_bwd_rows(npix, C), ...) finishes that branch.  rows_d may be the memory of `stats` (the finaliser has read them), not of dx. */
+int svsr_bn_bwd_from_stats_ds(const void* g, const void* x, const float* mean, const float* rstd, const float* gamma, const float* stats,
+                              int nrows, float* coef, float* dgamma, float* dbeta, void* dx, const void* xd, const float* mean_d,
+                              const float* rstd_d, float* rows_d, int64_t npix, int C, hipStream_t stream) {
+    if (!chan_ok_any(C) || nrows < 1 || npix < 1 || g == nullptr || x == nullptr || stats == nullptr || dx == nullptr) return SVSR_ERR_ARG;
+    if (xd == nullptr || mean_d == nullptr || rstd_d == nullptr || rows_d == nullptr) return SVSR_ERR_ARG;
+    const long nvec = npix * (C / 8);
+    hipLaunchKernelGGL(k_bn_bwd_finalize, dim3((C + BNF_CL - 1) / BNF_CL), dim3(BNF_CL * BNF_RL), 0, stream, stats, nrows, C, (float)npix, gamma, rstd, dgamma, dbeta, coef);
+    hipLaunchKernelGGL(k_bn_bwd_apply_ds, dim3(bn_bwd_grid(nvec, C)), dim3(256), 0, stream, (const bf16_t*)g, (const bf16_t*)x, mean, rstd, coef,
+                       (bf16_t*)dx, (const bf16_t*)xd, mean_d, rstd_d, rows_d, nvec, C);
     return svsr_check_launch();
 }
 

@@ -791,6 +791,32 @@ def _conv_bn(st: _ParamStore, tape: dict, x: torch.Tensor, conv: str, bn: str, k
     return y
 
 
+def _conv_stats(st: _ParamStore, tape: dict, x: torch.Tensor, conv: str, bn: str, k: int, stride: int, pad: int) -> dict:
+    """_conv_bn in training mode without its apply pass: the convolution and its batch statistics; the BatchNorm is applied where its
+    output is consumed (_conv_bn2).  -> the tape entry (y = None)."""
+    o, n, shape = st.offsets[f"{conv}.weight"]
+    w16 = st.w16[o : o + n].view(shape[0], k, k, shape[1])
+    c, stats = ops.conv2d_fwd(x, w16, k, stride, pad, want_stats=True)
+    mean, rstd = _bn_stats(st, bn, True, c.numel() // c.shape[-1], stats)
+    tape[conv] = dict(x=x, c=c, y=None, mean=mean, rstd=rstd, k=k, stride=stride, pad=pad, act=0, bn=bn, res=None)
+    return tape[conv]
+
+
+def _conv_bn2(st: _ParamStore, tape: dict, x: torch.Tensor, conv: str, bn: str, get_td) -> torch.Tensor:
+    """conv2 / bn2 of a downsample block in the training ReLU trunk: relu(bn2(conv2(x)) + bn_d(c_d)) with the 1x1 branch's BatchNorm applied
+    in the block-end pass, so that its output is never written (the backward does not read it).  get_td() -> that branch's _conv_stats
+    entry, called right before the pass: where the branch runs on the side stream this is the join."""
+    o, n, shape = st.offsets[f"{conv}.weight"]
+    w16 = st.w16[o : o + n].view(shape[0], 3, 3, shape[1])
+    c, stats = ops.conv2d_fwd(x, w16, 3, 1, 1, want_stats=True)
+    mean, rstd = _bn_stats(st, bn, True, c.numel() // c.shape[-1], stats)
+    td = get_td()
+    y = ops.bn_act_fwd2(c, td["c"], mean, rstd, st.p32(f"{bn}.weight"), st.p32(f"{bn}.bias"), td["mean"], td["rstd"],
+                        st.p32(f"{td['bn']}.weight"), st.p32(f"{td['bn']}.bias"))
+    tape[conv] = dict(x=x, c=c, y=y, mean=mean, rstd=rstd, k=3, stride=1, pad=1, act=1, bn=bn, res=None)
+    return y
+
+
 def _trunk_blocks(model):
     """(prefix, inplanes, planes, stride, has_downsample) with the model's own trunk name (`resnet` for LRW,
     `encoder.frontend.trunk` for LRS — same BasicBlock topology, different activation)."""
@@ -812,6 +838,19 @@ def _frontend_forward(model, st: "_ParamStore", tape: dict, videos: torch.Tensor
     tape["stem"] = dict(videos=videos, c=c, amax=amax, xwin=xwin, mean=mean, rstd=rstd, pooled_shape=tuple(x.shape))
     for prefix, inp, planes, stride, down in _trunk_blocks(model):
         xin = x
+        if down and training and act == 1:
+            # ReLU trunk: the 1x1 branch is its convolution and statistics only — on the side stream beside conv1 / bn1 / conv2 where there
+            # is one — and its BatchNorm is applied inside the block-end pass, after the join (the Swish trunk's backward recomputes its
+            # pre-activation from the stored residual input and keeps the form below)
+            dn, db = f"{prefix}.downsample.0", f"{prefix}.downsample.1"
+            model._side.run(lambda xin=xin, dn=dn, db=db, stride=stride: _conv_stats(st, tape, xin, dn, db, 1, stride, 0), xin)
+            o1 = _conv_bn(st, tape, xin, f"{prefix}.conv1", f"{prefix}.bn1", 3, stride, 1, training, None, act)
+
+            def joined(dn=dn):
+                model._side.join()
+                return tape[dn]
+            x = _conv_bn2(st, tape, o1, f"{prefix}.conv2", f"{prefix}.bn2", joined)
+            continue
         if down and training and model._side.enabled:
             # (round 6) the downsample branch (1x1 convolution, its statistics and apply pass) meets the main branch only at the residual sum: on the
             # side stream beside conv1 / bn1 (3 blocks x 3 launches off the main chain: -0.035 ms LRW same box, LRS unchanged; the backward
@@ -845,7 +884,16 @@ def _frontend_backward(model, st: "_ParamStore", tape: dict, dfeats: torch.Tenso
             rec[prefix] = (dx.clone(), dx_stats is not None)
         t2 = tape[f"{prefix}.conv2"]
         ws2 = st.bn[t2["bn"]]
-        if dx_stats is not None:
+        dcd = None
+        if dx_stats is not None and down and act == 1:
+            # dx is the gradient of the 1x1 branch's BatchNorm output too: bn2's apply pass takes the first pass of that BatchNorm's backward
+            # along, and the branch is finished right behind it, while its partial rows are what this stream's scratch holds
+            dres, td = dx, tape[f"{prefix}.downsample.0"]
+            dc2, d_stats = ops.bn_bwd_from_stats_ds(dx, t2["c"], t2["mean"], t2["rstd"], st.p32(f"{t2['bn']}.weight"), dx_stats, ws2["coef"],
+                                                    st.g32(f"{t2['bn']}.weight"), st.g32(f"{t2['bn']}.bias"), td["c"], td["mean"], td["rstd"])
+            dcd = ops.bn_bwd_from_stats(dres, td["c"], td["mean"], td["rstd"], st.p32(f"{td['bn']}.weight"), d_stats, st.bn[td["bn"]]["coef"],
+                                        st.g32(f"{td['bn']}.weight"), st.g32(f"{td['bn']}.bias"))
+        elif dx_stats is not None:
             dres = dx
             dc2 = ops.bn_bwd_from_stats(dx, t2["c"], t2["mean"], t2["rstd"], st.p32(f"{t2['bn']}.weight"), dx_stats, ws2["coef"],
                                         st.g32(f"{t2['bn']}.weight"), st.g32(f"{t2['bn']}.bias"))
@@ -877,8 +925,9 @@ def _frontend_backward(model, st: "_ParamStore", tape: dict, dfeats: torch.Tenso
         if down:
             td = tape[f"{prefix}.downsample.0"]
             wsd = st.bn[td["bn"]]
-            dcd, _ = ops.bn_act_bwd(dres, None, td["c"], td["mean"], td["rstd"], st.p32(f"{td['bn']}.weight"), wsd["coef"],
-                                    st.g32(f"{td['bn']}.weight"), st.g32(f"{td['bn']}.bias"), 0, False)
+            if dcd is None:
+                dcd, _ = ops.bn_act_bwd(dres, None, td["c"], td["mean"], td["rstd"], st.p32(f"{td['bn']}.weight"), wsd["coef"],
+                                        st.g32(f"{td['bn']}.weight"), st.g32(f"{td['bn']}.bias"), 0, False)
             _conv_wgrad(model, st, f"{prefix}.downsample.0", td, dcd)
             wdt = st.t16(f"{prefix}.downsample.0.weight").view(inp, 1, 1, planes)
             if ops.DGRAD2 and stride == 2:

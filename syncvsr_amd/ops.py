@@ -967,6 +967,20 @@ def bn_bwd_from_stats(g, x, mean, rstd, gamma, stats, coef, dgamma, dbeta) -> to
     return dx
 
 
+def bn_bwd_from_stats_ds(g, x, mean, rstd, gamma, stats, coef, dgamma, dbeta, xd, mean_d, rstd_d):
+    """bn_bwd_from_stats for bn2 of a downsample block, whose apply pass also takes the first pass of the 1x1 branch's BatchNorm backward
+    (xd its input): -> (dx, (rows, count)) with the partial rows of that branch, in this stream's scratch, for its own bn_bwd_from_stats —
+    which has to be the next call on this stream that uses the scratch."""
+    part, rows = stats
+    C = x.shape[-1]
+    dx = torch.empty_like(x)
+    rows_d = _query("svsr_bn_act_bwd_rows", x.numel() // C, C)[0]
+    slots = scratch(rows_d * 2 * C)
+    _call("svsr_bn_bwd_from_stats_ds", _p(g), _p(x), _p(mean), _p(rstd), _p(gamma), _p(part), rows, _p(coef), _p(dgamma), _p(dbeta), _p(dx),
+          _p(xd), _p(mean_d), _p(rstd_d), _p(slots), x.numel() // C, C, _stream())
+    return dx, (slots, rows_d)
+
+
 def conv2d_wgrad(x: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor, k: int, stride: int, pad: int, use_tr: bool = True, mode: Optional[int] = None) -> None:
     """dw fp32 [Co][k][k][Ci] += sum dy[n,y,x,co] * x[n, y*s+kh-pad, x*s+kw-pad, ci]  (mode 0: = 0.f + sum, see igemm_wgrad)."""
     N, H, W, Ci = x.shape
@@ -1238,6 +1252,15 @@ def bn_act_fwd(x, res, mean, rstd, gamma, beta, act: int) -> torch.Tensor:
     C = x.shape[-1]
     y = torch.empty_like(x)
     _call("svsr_bn_act_fwd", _p(x), _p(res), _p(y), _p(mean), _p(rstd), _p(gamma), _p(beta), x.numel() // C, C, act, _stream())
+    return y
+
+
+def bn_act_fwd2(x, xd, mean, rstd, gamma, beta, mean_d, rstd_d, gamma_d, beta_d) -> torch.Tensor:
+    """relu(bn(x) + bn_d(xd)) in one launch: bn_act_fwd(x, bn_act_fwd(xd, None, ..., 0), ..., 1) bit for bit."""
+    C = x.shape[-1]
+    y = torch.empty_like(x)
+    _call("svsr_bn_act_fwd2", _p(x), _p(xd), _p(y), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(mean_d), _p(rstd_d), _p(gamma_d), _p(beta_d),
+          x.numel() // C, C, _stream())
     return y
 
 
