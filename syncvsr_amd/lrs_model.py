@@ -21,7 +21,7 @@ import torch
 from . import ops
 from .config import Config
 from .lrs_init import LRS_ODIM, lrs_audio_dims, lrs_buffer_specs, lrs_init_state_dict, lrs_param_specs
-from .model import (BF16, _Holder, _NoAutogradCtx, _ParamStore, _StoreModule, _begin_backward, _bn_stats, _defer_list, _flush_lin_wgrads, _frontend_backward,
+from .model import (BF16, _Holder, _NoAutogradCtx, _ParamStore, _StoreModule, _begin_backward, _bn_from_stats, _bn_stats, _defer_list, _flush_lin_wgrads, _frontend_backward,
                     _frontend_forward, _get, _lin_wgrad, _ready, _require_device)
 
 LN_EPS = 1e-12          # transformer/layer_norm.py:19
@@ -577,13 +577,13 @@ def _encoder_layer_fwd(model: E2E, st: _ParamStore, tape: dict, i: int, x, pos16
     t3, m3, r3 = _ln(st, x2, f"{p}.norm_conv")
     cm = f"{p}.conv_module"
     u = _lin(st, t3, f"{cm}.pointwise_cov1", R, D, 2 * D)
-    bn = f"{cm}.norm"
+    bn = st.bnh(f"{cm}.norm")
     c, stats = ops.glu_dwconv_fwd(u, st.p32(f"{cm}.depthwise_conv.weight"), st.p32(f"{cm}.depthwise_conv.bias"), training, B, T, D, K)
-    mean, rstd = _bn_stats(st, bn, training, R, stats)
-    y = ops.bn_act_fwd(c, None, mean, rstd, st.p32(f"{bn}.weight"), st.p32(f"{bn}.bias"), ops.ACT_SWISH)
+    _bn_stats(bn, training, R, stats)
+    y = ops.bn_act_fwd(c, None, bn.mean, bn.rstd, bn.gamma, bn.beta, ops.ACT_SWISH)
     dco = model._d(f"enc.{i}.conv.out")
     x3 = _lin(st, y, f"{cm}.pointwise_cov2", R, D, D, addend=x2, drop=dco)
-    t["conv"] = dict(x=x2, tn=t3, m=m3, r=r3, u=u, c=c, y=y, mean=mean, rstd=rstd, dco=dco)
+    t["conv"] = dict(x=x2, tn=t3, m=m3, r=r3, u=u, c=c, y=y, bn=bn, dco=dco)
     x4 = _ffn_fwd(model, st, t, "ff", x3, f"{p}.feed_forward", R, D, U, 0.5, f"{p}.norm_ff", f"enc.{i}.ff")
     xo, m5, r5 = _ln(st, x4, f"{p}.norm_final")
     t["final"] = dict(x=x4, m=m5, r=r5)
@@ -601,21 +601,17 @@ def _encoder_layer_bwd(model: E2E, st: _ParamStore, tape: dict, i: int, dxo, pos
     dx3 = _ffn_bwd(model, st, t["ff"], dx4, f"{p}.feed_forward", R, D, U, 0.5, f"{p}.norm_ff", branch=(1.0, t["conv"]["dco"]))
     # convolution module
     tc = t["conv"]
-    cm, bn = f"{p}.conv_module", f"{p}.conv_module.norm"
-    ws = st.bn[bn]
+    cm, bn = f"{p}.conv_module", tc["bn"]
     if ops.BN_BWD_FUSED:
         # the data gradient of pointwise_conv2 is the gradient of swish(bn(c)): its launch multiplies by swish' and takes the
         # BatchNorm backward's first pass in its epilogue (ops.linear_dgrad_bn)
         dyo = _branch_grad(dx3, 1.0, tc["dco"])
         _lin_bwd(model, st, f"{cm}.pointwise_cov2", tc["y"], dyo, R, D, D, need_dx=False)
-        g, gst = ops.linear_dgrad_bn(dyo, st.t16(f"{cm}.pointwise_cov2.weight"), rows=R, N=D, K=D, dy_pitch=D, x=tc["c"], mean=tc["mean"],
-                                     rstd=tc["rstd"], gamma=st.p32(f"{bn}.weight"), beta=st.p32(f"{bn}.bias"), act=ops.ACT_SWISH)
-        dc = ops.bn_bwd_from_stats(g, tc["c"], tc["mean"], tc["rstd"], st.p32(f"{bn}.weight"), gst, ws["coef"], st.g32(f"{bn}.weight"),
-                                   st.g32(f"{bn}.bias"))
+        dc = _bn_from_stats(tc, *ops.linear_dgrad_bn(dyo, st.t16(f"{cm}.pointwise_cov2.weight"), rows=R, N=D, K=D, dy_pitch=D, x=tc["c"], mean=bn.mean,
+                                                     rstd=bn.rstd, gamma=bn.gamma, beta=bn.beta, act=ops.ACT_SWISH))
     else:
         dy = _lin_bwd(model, st, f"{cm}.pointwise_cov2", tc["y"], _branch_grad(dx3, 1.0, tc["dco"]), R, D, D)
-        dc, _ = ops.bn_act_bwd(dy, tc["y"], tc["c"], tc["mean"], tc["rstd"], st.p32(f"{bn}.weight"), ws["coef"], st.g32(f"{bn}.weight"),
-                               st.g32(f"{bn}.bias"), ops.ACT_SWISH, False, beta=st.p32(f"{bn}.bias"))
+        dc, _ = ops.bn_act_bwd(dy, tc["y"], tc["c"], bn.mean, bn.rstd, bn.gamma, bn.coef, bn.dgamma, bn.dbeta, ops.ACT_SWISH, False, beta=bn.beta)
     # (round 6) the two parameter-gradient tails of this layer — the depthwise convolution's partial-row sum and the position-table pass of
     # the attention backward — feed nothing but gradients of parameters: with the weight gradients on the side stream they go there too
     # (24 launches fewer in the main stream's chain per layer pair; same launches, same bits)

@@ -11,6 +11,7 @@ so ``loss_total.backward()`` works as in the reference loops while no per-op aut
 from __future__ import annotations
 
 import math
+from collections import namedtuple
 from typing import Any, Optional
 
 import torch
@@ -589,6 +590,9 @@ Model = TransformerLightningModule
 # ----------------------------------------------------------------------------------------------------
 # parameter store: flat fp32 master / gradient buffers + bf16 shadows
 # ----------------------------------------------------------------------------------------------------
+_BnHandle = namedtuple("_BnHandle", "C gamma beta dgamma dbeta coef mean rstd running_mean running_var num_batches_tracked base")
+
+
 class _ParamStore:
     """Flat fp32 master / gradient buffers + bf16 shadows for one model.  The model supplies `_specs`, `_bspecs`,
     `_fwd_rank(name)` (position of a tensor in the forward pass) and `_transposed_entries(offsets)` (which linear weights
@@ -742,6 +746,16 @@ class _ParamStore:
             v = self._vc[("t", key)] = self.w16t[o : o + Bd * T * Apad].view(Bd, T, Apad)
         return v
 
+    def bnh(self, base: str) -> "_BnHandle":
+        """The tensors of the BatchNorm called `base` under one name, the one place where their names are spelled: views of the flat buffers,
+        the workspaces of self.bn[base] and the running buffers (built once, like the views above; nothing is allocated)."""
+        h = self._vc.get(("bn", base))
+        if h is None:
+            ws, w, b = self.bn[base], f"{base}.weight", f"{base}.bias"
+            h = self._vc[("bn", base)] = _BnHandle(ws["mean"].numel(), self.p32(w), self.p32(b), self.g32(w), self.g32(b), ws["coef"], ws["mean"], ws["rstd"],
+                                                   *(self.buffers[f"{base}.{k}"] for k in _BnHandle._fields[-4:-1]), base)
+        return h
+
     def span(self, name: str, numel: Optional[int] = None) -> tuple[int, int]:
         o, n, _ = self.offsets[name]
         return o, o + (numel or n)
@@ -769,52 +783,37 @@ class _ParamStore:
 # ----------------------------------------------------------------------------------------------------
 # forward / backward tape
 # ----------------------------------------------------------------------------------------------------
-def _bn_stats(st: _ParamStore, base: str, training: bool, count: int, stats):
-    """stats: the partial sums (buffer, rows) the producing convolution just wrote on this stream (training mode)."""
-    ws = st.bn[base]
+def _bn_stats(bn: _BnHandle, training: bool, count: int, stats) -> None:
+    """Fills bn.mean / bn.rstd.  stats: the partial sums (buffer, rows) the producing convolution just wrote on this stream (training mode)."""
     if training:
-        ops.bn_finalize(stats, ws["mean"].numel(), count, ws["mean"], ws["rstd"], st.buffers[f"{base}.running_mean"],
-                        st.buffers[f"{base}.running_var"], st.buffers[f"{base}.num_batches_tracked"])
+        ops.bn_finalize(stats, bn.C, count, bn.mean, bn.rstd, bn.running_mean, bn.running_var, bn.num_batches_tracked)
     else:
-        ops.bn_eval_prepare(st.buffers[f"{base}.running_mean"], st.buffers[f"{base}.running_var"], ws["mean"], ws["rstd"])
-    return ws["mean"], ws["rstd"]      # per-layer buffers: valid until this layer's next forward
+        ops.bn_eval_prepare(bn.running_mean, bn.running_var, bn.mean, bn.rstd)
+
+
+def _bn_from_stats(t: dict, g: torch.Tensor, stats) -> torch.Tensor:
+    """Second half of the backward of tape entry t's BatchNorm, behind a launch whose epilogue took the first (g, stats)."""
+    bn = t["bn"]
+    return ops.bn_bwd_from_stats(g, t["c"], bn.mean, bn.rstd, bn.gamma, stats, bn.coef, bn.dgamma, bn.dbeta)
+
+
+def _conv_stats(st: _ParamStore, tape: dict, x: torch.Tensor, conv: str, bn: str, k: int, stride: int, pad: int, training: bool,
+                res: Optional[torch.Tensor] = None, act: int = 0) -> dict:
+    """The convolution and its BatchNorm's statistics -> the tape entry; y = None until an apply pass (bn_act_fwd, bn_act_fwd2) fills it."""
+    o, n, shape = st.offsets[f"{conv}.weight"]
+    w16 = st.w16[o : o + n].view(shape[0], k, k, shape[1])
+    c, stats = ops.conv2d_fwd(x, w16, k, stride, pad, want_stats=training)
+    h = st.bnh(bn)
+    _bn_stats(h, training, c.numel() // c.shape[-1], stats)
+    tape[conv] = t = dict(x=x, c=c, y=None, mean=h.mean, rstd=h.rstd, k=k, stride=stride, pad=pad, act=act, bn=h, res=res)
+    return t
 
 
 def _conv_bn(st: _ParamStore, tape: dict, x: torch.Tensor, conv: str, bn: str, k: int, stride: int, pad: int, training: bool,
              res: Optional[torch.Tensor], act: int) -> torch.Tensor:
-    o, n, shape = st.offsets[f"{conv}.weight"]
-    w16 = st.w16[o : o + n].view(shape[0], k, k, shape[1])
-    c, stats = ops.conv2d_fwd(x, w16, k, stride, pad, want_stats=training)
-    mean, rstd = _bn_stats(st, bn, training, c.numel() // c.shape[-1], stats)
-    y = ops.bn_act_fwd(c, res, mean, rstd, st.p32(f"{bn}.weight"), st.p32(f"{bn}.bias"), act)
-    tape[conv] = dict(x=x, c=c, y=y, mean=mean, rstd=rstd, k=k, stride=stride, pad=pad, act=act, bn=bn, res=res)
-    return y
-
-
-def _conv_stats(st: _ParamStore, tape: dict, x: torch.Tensor, conv: str, bn: str, k: int, stride: int, pad: int) -> dict:
-    """_conv_bn in training mode without its apply pass: the convolution and its batch statistics; the BatchNorm is applied where its
-    output is consumed (_conv_bn2).  -> the tape entry (y = None)."""
-    o, n, shape = st.offsets[f"{conv}.weight"]
-    w16 = st.w16[o : o + n].view(shape[0], k, k, shape[1])
-    c, stats = ops.conv2d_fwd(x, w16, k, stride, pad, want_stats=True)
-    mean, rstd = _bn_stats(st, bn, True, c.numel() // c.shape[-1], stats)
-    tape[conv] = dict(x=x, c=c, y=None, mean=mean, rstd=rstd, k=k, stride=stride, pad=pad, act=0, bn=bn, res=None)
-    return tape[conv]
-
-
-def _conv_bn2(st: _ParamStore, tape: dict, x: torch.Tensor, conv: str, bn: str, get_td) -> torch.Tensor:
-    """conv2 / bn2 of a downsample block in the training ReLU trunk: relu(bn2(conv2(x)) + bn_d(c_d)) with the 1x1 branch's BatchNorm applied
-    in the block-end pass, so that its output is never written (the backward does not read it).  get_td() -> that branch's _conv_stats
-    entry, called right before the pass: where the branch runs on the side stream this is the join."""
-    o, n, shape = st.offsets[f"{conv}.weight"]
-    w16 = st.w16[o : o + n].view(shape[0], 3, 3, shape[1])
-    c, stats = ops.conv2d_fwd(x, w16, 3, 1, 1, want_stats=True)
-    mean, rstd = _bn_stats(st, bn, True, c.numel() // c.shape[-1], stats)
-    td = get_td()
-    y = ops.bn_act_fwd2(c, td["c"], mean, rstd, st.p32(f"{bn}.weight"), st.p32(f"{bn}.bias"), td["mean"], td["rstd"],
-                        st.p32(f"{td['bn']}.weight"), st.p32(f"{td['bn']}.bias"))
-    tape[conv] = dict(x=x, c=c, y=y, mean=mean, rstd=rstd, k=3, stride=1, pad=1, act=1, bn=bn, res=None)
-    return y
+    t = _conv_stats(st, tape, x, conv, bn, k, stride, pad, training, res, act)
+    t["y"] = ops.bn_act_fwd(t["c"], res, t["mean"], t["rstd"], t["bn"].gamma, t["bn"].beta, act)
+    return t["y"]
 
 
 def _trunk_blocks(model):
@@ -824,142 +823,146 @@ def _trunk_blocks(model):
         yield model.trunk_name + prefix[len("resnet"):], inp, planes, stride, down
 
 
+def _block_forward(model, st: "_ParamStore", tape: dict, x: torch.Tensor, blk: tuple, training: bool) -> torch.Tensor:
+    prefix, inp, planes, stride, down = blk
+    act, side = model.trunk_act, model._side
+    conv1, conv2, convd = ((f"{prefix}.{c}", f"{prefix}.{b}") for c, b in (("conv1", "bn1"), ("conv2", "bn2"), ("downsample.0", "downsample.1")))
+    # The 1x1 branch of a downsample block runs behind conv1 / bn1 on the main stream ("serial"), or
+    # "fold"  ReLU trunk in training: its convolution and statistics only — on the side stream beside conv1 / bn1 / conv2 where there is one —
+    #         and its BatchNorm is applied inside the block-end pass, after the join, so that its output is never written (the Swish trunk's
+    #         backward recomputes its pre-activation from the stored residual input and keeps the other forms)
+    # "side"  (round 6) the branch (1x1 convolution, its statistics and apply pass) meets the main branch only at the residual sum: on the
+    #         side stream beside conv1 / bn1 (3 blocks x 3 launches off the main chain: -0.035 ms LRW same box, LRS unchanged; the backward
+    #         twin measured SLOWER — its join waits for the weight gradients queued on that stream — and is not here)
+    branch = None if not down else "fold" if training and act == 1 else "side" if training and side.enabled else "serial"
+    if branch == "fold":
+        side.run(lambda: _conv_stats(st, tape, x, *convd, 1, stride, 0, True), x)
+    elif branch == "side":
+        side.run(lambda: _conv_bn(st, tape, x, *convd, 1, stride, 0, training, None, 0), x)
+    o1 = _conv_bn(st, tape, x, *conv1, 3, stride, 1, training, None, act)
+    if branch == "fold":
+        t2 = _conv_stats(st, tape, o1, *conv2, 3, 1, 1, True, None, 1)
+        side.join()
+        td = tape[convd[0]]
+        b2, bd = t2["bn"], td["bn"]
+        t2["y"] = ops.bn_act_fwd2(t2["c"], td["c"], b2.mean, b2.rstd, b2.gamma, b2.beta, bd.mean, bd.rstd, bd.gamma, bd.beta)      # relu(bn2(c) + bn_d(c_d))
+        return t2["y"]
+    idt = x
+    if branch == "side":
+        side.join()
+        idt = tape[convd[0]]["y"]
+    elif branch == "serial":
+        idt = _conv_bn(st, tape, x, *convd, 1, stride, 0, training, None, 0)
+    return _conv_bn(st, tape, o1, *conv2, 3, 1, 1, training, idt, act)
+
+
 def _frontend_forward(model, st: "_ParamStore", tape: dict, videos: torch.Tensor, training: bool) -> torch.Tensor:
     """videos: fp32 [B,1,T,H,W] (LRW) — the LRS layout [B,T,1,H,W] is the same memory.  -> [B*T, 512] bf16."""
-    B, _, T, H, W = videos.shape
-    N = B * T
-    sc, sb, act = model.stem_name + ".0", model.stem_name + ".1", model.trunk_act
-    c, stats = ops.stem_conv_fwd(videos, st.p32(f"{sc}.weight"), want_stats=training)
-    mean, rstd = _bn_stats(st, sb, training, c.numel() // 64, stats)
-    if training:          # the convolution output at every pooling window's arg-max, for the backward
-        x, amax, xwin = ops.stem_bn_gelu_pool_fwd(c, mean, rstd, st.p32(f"{sb}.weight"), st.p32(f"{sb}.bias"), model.stem_act, want_win=True)
-    else:
-        (x, amax), xwin = ops.stem_bn_gelu_pool_fwd(c, mean, rstd, st.p32(f"{sb}.weight"), st.p32(f"{sb}.bias"), model.stem_act), None
-    tape["stem"] = dict(videos=videos, c=c, amax=amax, xwin=xwin, mean=mean, rstd=rstd, pooled_shape=tuple(x.shape))
-    for prefix, inp, planes, stride, down in _trunk_blocks(model):
-        xin = x
-        if down and training and act == 1:
-            # ReLU trunk: the 1x1 branch is its convolution and statistics only — on the side stream beside conv1 / bn1 / conv2 where there
-            # is one — and its BatchNorm is applied inside the block-end pass, after the join (the Swish trunk's backward recomputes its
-            # pre-activation from the stored residual input and keeps the form below)
-            dn, db = f"{prefix}.downsample.0", f"{prefix}.downsample.1"
-            model._side.run(lambda xin=xin, dn=dn, db=db, stride=stride: _conv_stats(st, tape, xin, dn, db, 1, stride, 0), xin)
-            o1 = _conv_bn(st, tape, xin, f"{prefix}.conv1", f"{prefix}.bn1", 3, stride, 1, training, None, act)
-
-            def joined(dn=dn):
-                model._side.join()
-                return tape[dn]
-            x = _conv_bn2(st, tape, o1, f"{prefix}.conv2", f"{prefix}.bn2", joined)
-            continue
-        if down and training and model._side.enabled:
-            # (round 6) the downsample branch (1x1 convolution, its statistics and apply pass) meets the main branch only at the residual sum: on the
-            # side stream beside conv1 / bn1 (3 blocks x 3 launches off the main chain: -0.035 ms LRW same box, LRS unchanged; the backward
-            # twin measured SLOWER — its join waits for the weight gradients queued on that stream — and is not here)
-            box: dict = {}
-            model._side.run(lambda xin=xin, prefix=prefix, stride=stride: box.__setitem__(
-                "idt", _conv_bn(st, tape, xin, f"{prefix}.downsample.0", f"{prefix}.downsample.1", 1, stride, 0, training, None, 0)), xin)
-            o1 = _conv_bn(st, tape, xin, f"{prefix}.conv1", f"{prefix}.bn1", 3, stride, 1, training, None, act)
-            model._side.join()
-            idt = box["idt"]
-        else:
-            o1 = _conv_bn(st, tape, xin, f"{prefix}.conv1", f"{prefix}.bn1", 3, stride, 1, training, None, act)
-            idt = _conv_bn(st, tape, xin, f"{prefix}.downsample.0", f"{prefix}.downsample.1", 1, stride, 0, training, None, 0) if down else xin
-        x = _conv_bn(st, tape, o1, f"{prefix}.conv2", f"{prefix}.bn2", 3, 1, 1, training, idt, act)
+    bn = st.bnh(model.stem_name + ".1")
+    c, stats = ops.stem_conv_fwd(videos, st.p32(model.stem_name + ".0.weight"), want_stats=training)
+    _bn_stats(bn, training, c.numel() // 64, stats)
+    out = ops.stem_bn_gelu_pool_fwd(c, bn.mean, bn.rstd, bn.gamma, bn.beta, model.stem_act, want_win=training)
+    x, amax, xwin = out if training else (*out, None)          # xwin: the convolution output at every pooling window's arg-max, for the backward
+    tape["stem"] = dict(videos=videos, c=c, amax=amax, xwin=xwin, bn=bn, pooled_shape=tuple(x.shape))
+    for blk in _trunk_blocks(model):
+        x = _block_forward(model, st, tape, x, blk, training)
     tape["trunk_out_shape"] = tuple(x.shape)
     return ops.avgpool_fwd(x)            # [N, 512] bf16
 
 
+def _bn2_backward(t2: dict, td: Optional[dict], dx: torch.Tensor, dx_stats, act: int) -> tuple:
+    """The block-end BatchNorm from dx, the gradient of the block's output -> (dc2, dres, dcd): the gradients of conv2's output, of the
+    residual branch's output and — where this step finishes the 1x1 branch's BatchNorm too — of that branch's convolution (else None)."""
+    bn = t2["bn"]
+    if dx_stats is None:
+        return (*ops.bn_act_bwd(dx, t2["y"], t2["c"], bn.mean, bn.rstd, bn.gamma, bn.coef, bn.dgamma, bn.dbeta, act, True, beta=bn.beta, res=t2["res"]), None)
+    if td is None or act != 1:
+        return _bn_from_stats(t2, dx, dx_stats), dx, None
+    # dx is the gradient of the 1x1 branch's BatchNorm output too: bn2's apply pass takes the first pass of that BatchNorm's backward
+    # along, and the branch is finished right behind it, while its partial rows are what this stream's scratch holds
+    bd = td["bn"]
+    dc2, d_stats = ops.bn_bwd_from_stats_ds(dx, t2["c"], bn.mean, bn.rstd, bn.gamma, dx_stats, bn.coef, bn.dgamma, bn.dbeta, td["c"], bd.mean, bd.rstd)
+    return dc2, dx, _bn_from_stats(td, dx, d_stats)
+
+
+def _bn1_backward(t1: dict, dc2: torch.Tensor, w2t: torch.Tensor, act: int, fused: bool) -> torch.Tensor:
+    """conv2's data gradient and bn1 -> dc1, the gradient of conv1's output."""
+    bn, hw = t1["bn"], t1["c"].shape[1:3]
+    if fused:
+        # bn1 has no residual branch: the mask / pre-activation is recomputed from its input (y is not read)
+        return _bn_from_stats(t1, *ops.conv2d_dgrad_bn(dc2, w2t, 3, 1, 1, hw, None, None, t1["c"], bn.mean, bn.rstd, bn.gamma, bn.beta, act))
+    return ops.bn_act_bwd(ops.conv2d_dgrad(dc2, w2t, 3, 1, 1, hw), t1["y"], t1["c"], bn.mean, bn.rstd, bn.gamma, bn.coef, bn.dgamma, bn.dbeta, act, False, beta=bn.beta)[0]
+
+
+def _epilogue(t: dict, act: int) -> tuple:
+    """What the epilogue of a data-gradient launch needs to turn the gradient of a block's output (t = that block's conv2 entry) into the
+    gradient of bn2's output: (ReLU: the output, its mask; Swish: the residual input, whose pre-activation it rebuilds, c, ..., act)."""
+    bn = t["bn"]
+    return (t["y"] if act == 1 else t["res"], t["c"], bn.mean, bn.rstd, bn.gamma, bn.beta, act)
+
+
+def _dgrad3x3(dy: torch.Tensor, wt: torch.Tensor, stride: int, in_hw, addend: Optional[torch.Tensor], epi: Optional[tuple]) -> tuple:
+    """3x3 data gradient (+ addend, in place), with the epilogue `epi` (_epilogue) when there is one -> (dx, dx_stats or None)."""
+    if epi is None:
+        return ops.conv2d_dgrad(dy, wt, 3, stride, 1, in_hw, addend=addend), None
+    return ops.conv2d_dgrad_bn(dy, wt, 3, stride, 1, in_hw, addend, *epi)
+
+
+def _input_grad(st: "_ParamStore", blk: tuple, in_hw, dc1: torch.Tensor, dres: torch.Tensor, dcd: Optional[torch.Tensor], epi: Optional[tuple]) -> tuple:
+    """The gradient of the block's input from both branches -> (dx, dx_stats or None)."""
+    prefix, inp, planes, stride, down = blk
+    w1t = st.t16(f"{prefix}.conv1.weight").view(inp, 3, 3, planes)
+    if not down:
+        return _dgrad3x3(dc1, w1t, stride, in_hw, dres, epi)
+    wdt = st.t16(f"{prefix}.downsample.0.weight").view(inp, 1, 1, planes)
+    if ops.DGRAD2 and stride == 2:
+        # one launch: the 1x1 branch reaches exactly the pixels of the 3x3 gradient's centre tap and is one more tap of that class
+        out = ops.conv2d_dgrad2(dc1, w1t, dcd, wdt, in_hw, bn=epi)
+        return out if epi is not None else (out, None)
+    # two launches: the 1x1 branch first (pixels its stride skips are written as zeros), the 3x3 branch adds to it
+    return _dgrad3x3(dc1, w1t, stride, in_hw, ops.conv2d_dgrad(dcd, wdt, 1, stride, 0, in_hw), epi)
+
+
+def _block_backward(model, st: "_ParamStore", tape: dict, blk: tuple, below: Optional[dict], dx: torch.Tensor, dx_stats) -> tuple:
+    """One BasicBlock from the gradient of its output to that of its input.  below: the conv2 entry of the block below (None: the stem
+    is), whose output is that input.  dx_stats not None: dx is already masked, these are its bn2's partial rows.  -> the next (dx, dx_stats)."""
+    prefix, planes, act = blk[0], blk[2], model.trunk_act
+    # The launch that produces the gradient of a BatchNorm + activation output also masks it (1 ReLU, LRW) or multiplies it by swish'
+    # (2 Swish, LRS) and takes the first pass of that BatchNorm's backward in its epilogue (ops.conv2d_dgrad_bn)
+    fused = act in (1, 2) and ops.BN_BWD_FUSED
+    t2, t1, td = tape[f"{prefix}.conv2"], tape[f"{prefix}.conv1"], tape.get(f"{prefix}.downsample.0")
+    dc2, dres, dcd = _bn2_backward(t2, td, dx, dx_stats, act)
+    _conv_wgrad(model, st, f"{prefix}.conv2", t2, dc2)
+    dc1 = _bn1_backward(t1, dc2, st.t16(f"{prefix}.conv2.weight").view(planes, 3, 3, planes), act, fused)
+    _conv_wgrad(model, st, f"{prefix}.conv1", t1, dc1)
+    if td is not None:
+        if dcd is None:       # bn2's pass did not take the branch's BatchNorm along
+            bd = td["bn"]
+            dcd, _ = ops.bn_act_bwd(dres, None, td["c"], bd.mean, bd.rstd, bd.gamma, bd.coef, bd.dgamma, bd.dbeta, 0, False)
+        _conv_wgrad(model, st, f"{prefix}.downsample.0", td, dcd)
+    out = _input_grad(st, blk, t1["x"].shape[1:3], dc1, dres, dcd, _epilogue(below, act) if fused and below is not None else None)
+    _ready(model, st, f"{prefix}.conv1.weight")
+    return out
+
+
 def _frontend_backward(model, st: "_ParamStore", tape: dict, dfeats: torch.Tensor) -> None:
-    act = model.trunk_act
-    dx = ops.avgpool_bwd(dfeats, tape["trunk_out_shape"])
-    # ReLU trunk: the launch that produces the gradient of a BatchNorm+ReLU output also masks it and takes the first pass of that
-    # BatchNorm's backward in its epilogue (ops.conv2d_dgrad_bn); dx_stats != None means dx already is that masked gradient.
-    fused = act in (1, 2) and ops.BN_BWD_FUSED       # 1 ReLU (LRW), 2 Swish (LRS): the epilogue masks / multiplies by swish'
-    dx_stats = None
+    dx, dx_stats = ops.avgpool_bwd(dfeats, tape["trunk_out_shape"]), None
     blocks = list(_trunk_blocks(model))
     rec = tape.get("_record_grads")       # tests: {block prefix: (gradient entering the block from above, is it already masked by relu')}
     for bi in range(len(blocks) - 1, -1, -1):
-        prefix, inp, planes, stride, down = blocks[bi]
         if rec is not None:
-            rec[prefix] = (dx.clone(), dx_stats is not None)
-        t2 = tape[f"{prefix}.conv2"]
-        ws2 = st.bn[t2["bn"]]
-        dcd = None
-        if dx_stats is not None and down and act == 1:
-            # dx is the gradient of the 1x1 branch's BatchNorm output too: bn2's apply pass takes the first pass of that BatchNorm's backward
-            # along, and the branch is finished right behind it, while its partial rows are what this stream's scratch holds
-            dres, td = dx, tape[f"{prefix}.downsample.0"]
-            dc2, d_stats = ops.bn_bwd_from_stats_ds(dx, t2["c"], t2["mean"], t2["rstd"], st.p32(f"{t2['bn']}.weight"), dx_stats, ws2["coef"],
-                                                    st.g32(f"{t2['bn']}.weight"), st.g32(f"{t2['bn']}.bias"), td["c"], td["mean"], td["rstd"])
-            dcd = ops.bn_bwd_from_stats(dres, td["c"], td["mean"], td["rstd"], st.p32(f"{td['bn']}.weight"), d_stats, st.bn[td["bn"]]["coef"],
-                                        st.g32(f"{td['bn']}.weight"), st.g32(f"{td['bn']}.bias"))
-        elif dx_stats is not None:
-            dres = dx
-            dc2 = ops.bn_bwd_from_stats(dx, t2["c"], t2["mean"], t2["rstd"], st.p32(f"{t2['bn']}.weight"), dx_stats, ws2["coef"],
-                                        st.g32(f"{t2['bn']}.weight"), st.g32(f"{t2['bn']}.bias"))
-        else:
-            dc2, dres = ops.bn_act_bwd(dx, t2["y"], t2["c"], t2["mean"], t2["rstd"], st.p32(f"{t2['bn']}.weight"), ws2["coef"],
-                                       st.g32(f"{t2['bn']}.weight"), st.g32(f"{t2['bn']}.bias"), act, True,
-                                       beta=st.p32(f"{t2['bn']}.bias"), res=t2["res"])
-        _conv_wgrad(model, st, f"{prefix}.conv2", t2, dc2)
-        t1 = tape[f"{prefix}.conv1"]
-        ws1 = st.bn[t1["bn"]]
-        w2t = st.t16(f"{prefix}.conv2.weight").view(planes, 3, 3, planes)
-        if fused:
-            # bn1 has no residual branch: the mask / pre-activation is recomputed from its input (y is not read)
-            g1, st1 = ops.conv2d_dgrad_bn(dc2, w2t, 3, 1, 1, t2["x"].shape[1:3], None, None, t1["c"], t1["mean"], t1["rstd"],
-                                          st.p32(f"{t1['bn']}.weight"), st.p32(f"{t1['bn']}.bias"), act)
-            dc1 = ops.bn_bwd_from_stats(g1, t1["c"], t1["mean"], t1["rstd"], st.p32(f"{t1['bn']}.weight"), st1, ws1["coef"],
-                                        st.g32(f"{t1['bn']}.weight"), st.g32(f"{t1['bn']}.bias"))
-        else:
-            do1 = ops.conv2d_dgrad(dc2, w2t, 3, 1, 1, t2["x"].shape[1:3])
-            dc1, _ = ops.bn_act_bwd(do1, t1["y"], t1["c"], t1["mean"], t1["rstd"], st.p32(f"{t1['bn']}.weight"), ws1["coef"],
-                                    st.g32(f"{t1['bn']}.weight"), st.g32(f"{t1['bn']}.bias"), act, False, beta=st.p32(f"{t1['bn']}.bias"))
-        _conv_wgrad(model, st, f"{prefix}.conv1", t1, dc1)
-        in_hw = t1["x"].shape[1:3]
-        w1t = st.t16(f"{prefix}.conv1.weight").view(inp, 3, 3, planes)
-        tp = tape[f"{blocks[bi - 1][0]}.conv2"] if fused and bi > 0 else None       # the block below: its output is this block's input
-        if tp is not None:      # what the epilogue needs of that output: ReLU its value (the mask), Swish its residual input
-            tp_aux = tp["y"] if act == 1 else tp["res"]
-            tp_gb = (st.p32(f"{tp['bn']}.weight"), st.p32(f"{tp['bn']}.bias"), act)
-        if down:
-            td = tape[f"{prefix}.downsample.0"]
-            wsd = st.bn[td["bn"]]
-            if dcd is None:
-                dcd, _ = ops.bn_act_bwd(dres, None, td["c"], td["mean"], td["rstd"], st.p32(f"{td['bn']}.weight"), wsd["coef"],
-                                        st.g32(f"{td['bn']}.weight"), st.g32(f"{td['bn']}.bias"), 0, False)
-            _conv_wgrad(model, st, f"{prefix}.downsample.0", td, dcd)
-            wdt = st.t16(f"{prefix}.downsample.0.weight").view(inp, 1, 1, planes)
-            if ops.DGRAD2 and stride == 2:
-                # one launch: the 1x1 branch reaches exactly the pixels of the 3x3 gradient's centre tap and is one more tap of that class
-                if tp is not None:
-                    dx, dx_stats = ops.conv2d_dgrad2(dc1, w1t, dcd, wdt, in_hw, bn=(tp_aux, tp["c"], tp["mean"], tp["rstd"], *tp_gb))
-                else:
-                    dx, dx_stats = ops.conv2d_dgrad2(dc1, w1t, dcd, wdt, in_hw), None
-            else:
-                # two launches: the 1x1 branch first (pixels its stride skips are written as zeros), the 3x3 branch adds to it
-                dxd = ops.conv2d_dgrad(dcd, wdt, 1, stride, 0, in_hw)
-                if tp is not None:
-                    dx, dx_stats = ops.conv2d_dgrad_bn(dc1, w1t, 3, stride, 1, in_hw, dxd, tp_aux, tp["c"], tp["mean"], tp["rstd"], *tp_gb)
-                else:
-                    dx, dx_stats = ops.conv2d_dgrad(dc1, w1t, 3, stride, 1, in_hw, addend=dxd), None
-        elif tp is not None:
-            dx, dx_stats = ops.conv2d_dgrad_bn(dc1, w1t, 3, stride, 1, in_hw, dres, tp_aux, tp["c"], tp["mean"], tp["rstd"], *tp_gb)
-        else:
-            dx, dx_stats = ops.conv2d_dgrad(dc1, w1t, 3, stride, 1, in_hw, addend=dres), None
-        _ready(model, st, f"{prefix}.conv1.weight")
+            rec[blocks[bi][0]] = (dx.clone(), dx_stats is not None)
+        dx, dx_stats = _block_backward(model, st, tape, blocks[bi], tape[f"{blocks[bi - 1][0]}.conv2"] if bi > 0 else None, dx, dx_stats)
     # the chain ends here: its last reduce goes out right behind the last halo launch and runs beside the stem's light passes
     _flush_w3_chain(model)
     ts = tape["stem"]
     if rec is not None:
         rec["stem"] = (dx.clone(), False)
-    sc, sb = model.stem_name + ".0", model.stem_name + ".1"
-    ws = st.bn[sb]
-    fused = ts.get("xwin") is not None and ops.stem_bwd_wgrad_ok(ts["videos"])
-    dconv = ops.stem_bn_gelu_pool_bwd(dx, ts["amax"], ts["c"], ts["mean"], ts["rstd"], st.p32(f"{sb}.weight"), st.p32(f"{sb}.bias"),
-                                      ws["coef"], st.g32(f"{sb}.weight"), st.g32(f"{sb}.bias"), model.stem_act, xwin=ts.get("xwin"),
-                                      want_dx=not fused)
-    if fused:
+    bn, gw = ts["bn"], st.g32(model.stem_name + ".0.weight")
+    in_wgrad = ts["xwin"] is not None and ops.stem_bwd_wgrad_ok(ts["videos"])
+    dconv = ops.stem_bn_gelu_pool_bwd(dx, ts["amax"], ts["c"], bn.mean, bn.rstd, bn.gamma, bn.beta, bn.coef, bn.dgamma, bn.dbeta, model.stem_act,
+                                      xwin=ts["xwin"], want_dx=not in_wgrad)
+    if in_wgrad:
         # The gradient of the convolution output is made tile by tile inside the weight-gradient pass, never written.  The side stream is
         # joined FIRST: the pass is a persistent grid of two 248-register workgroups per CU, and beside the last trunk weight gradients
         # (8-wave workgroups that leave no CU room for them) half its workgroups started late and the step LOST 0.02 / 0.4 ms (LRW / LRS);
@@ -973,9 +976,9 @@ def _frontend_backward(model, st: "_ParamStore", tape: dict, dfeats: torch.Tenso
             with ops.window_group("tail"):
                 model._side.run(lambda: ops.grad_sumsq_parts(st.grad, st.sumsq_head, st.numel - st.sumsq_head, early, 0, ops.SUMSQ_PARTS - 1))
             st.sumsq_tail_done = True
-        ops.stem_bwd_wgrad(ts["videos"], dconv, ts["amax"], ts["c"], ts["mean"], ts["rstd"], ws["coef"], st.g32(f"{sc}.weight"))
+        ops.stem_bwd_wgrad(ts["videos"], dconv, ts["amax"], ts["c"], bn.mean, bn.rstd, bn.coef, gw)
     else:
-        ops.stem_conv_wgrad(ts["videos"], dconv, st.g32(f"{sc}.weight"))
+        ops.stem_conv_wgrad(ts["videos"], dconv, gw)
     _flush_deferred(model)
     model._side.join()
     _ready(model, st, None)

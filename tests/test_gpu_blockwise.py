@@ -69,7 +69,7 @@ def _blockwise(model, sd, videos, relu: bool, cos_floor: float, ratio_band: floa
         if relu:
             return (x.detach() > 0).float()
         tp = tape[f"{blocks[bi - 1][0]}.conv2"]            # z = bn2(c) + residual, rebuilt from what the forward kept
-        gam, bet = (sd[f"{tp['bn']}.{k}"].float().to(dev) for k in ("weight", "bias"))
+        gam, bet = (sd[f"{tp['bn'].base}.{k}"].float().to(dev) for k in ("weight", "bias"))
         z = (tp["c"].float() - tp["mean"]) * tp["rstd"] * gam + bet + tp["res"].float()
         sg = torch.sigmoid(z)
         return _nchw(sg * (1.0 + z * (1.0 - sg)))
