@@ -724,6 +724,27 @@ int svsr_scale_bf16(const void* x, void* y, int64_t n, float alpha, const unsign
 int svsr_mha_table_fwd(const void* pool, int pool_rows, int64_t pitch, const int* table, int table_pitch, int n, int Lq, int L, int H, float scale, void* ctx, int64_t ctx_pitch, hipStream_t stream);
 int svsr_lm_embed_fwd(const void* x, int64_t x_pitch, const float* gamma, const float* beta, const float* pe, int pe_rows, const int* pos, int R, int D, float eps, float scale, void* out, hipStream_t stream);
 
+/* ---- Recurrent language-model scorer of the beam search (lrs_rnnlm.hip) ------------------------------------------------
+ * Replaces one nn.LSTMCell / nn.GRUCell of DefaultRNNLM (reference LRS/video/espnet/nets/pytorch_backend/lm/default.py:396-429) together
+ * with the embedding lookup in front of layer 0 and the per-hypothesis state gather the search does between two steps
+ * (default.py:193-213: a dict of lists of rows, re-stacked every step).
+ * svsr_rnn_cell_step: ONE layer of ONE step for R hypotheses.  gru = 0: LSTM (gates i, f, g, o), 1: GRU (r, z, n) — torch's orders.
+ *   x_r  = x[xidx ? xidx[r * xidx_stride] : r]       x bf16 [x_rows][x_pitch >= Ep]: the embedding table (xidx = the tokens) or the bf16
+ *                                                    output rows of the layer below (xidx = NULL); an index outside [0, x_rows): zeros
+ *   hp_r, cp_r = h_prev[src[r]], c_prev[src[r]]      fp32 [prev_rows][Up], rounded to bf16 for the contraction only; src = NULL, or
+ *                                                    src[r] outside [0, prev_rows): zeros (the first step)
+ *   LSTM: c = sig(f) cp + sig(i) tanh(g), h = sig(o) tanh(c);  GRU: n = tanh(W_in x + b_in + r (W_hn hp + b_hn)), h = (1 - z) n + z hp
+ *   h_out, c_out fp32 [R][Up] (c_out / c_prev unused by the GRU), h16_out bf16 [R][Up] or NULL: the same h, the next layer's / the output
+ *   projection's input.  Units u >= U (the padding) are written as exact zeros.  h_out must not be h_prev (nor c_out c_prev): a step
+ *   reads one buffer of a ping-pong pair and writes the other, which is what folds the search's select_states into the next step.
+ * wpk: bf16 [Up / 16][(Ep + Up) / 32][G][64][8] (G = 4 | 3), the MFMA B fragments in the order the lanes read them: entry (t, s, g, l, j) =
+ *   W_g[16 t + (l & 15)][32 s + 8 (l >> 4) + j] with W_g = [W_ih,g | W_hh,g] zero-padded to [Up][Ep + Up].  bias: fp32 [Up / 16][4][16]:
+ *   LSTM b_ih + b_hh per gate; GRU r, z (summed), b_in, b_hn.  (syncvsr_amd.lrs_lm.pack_rnn_cell / unpack_rnn_cell.)
+ * Grid: one workgroup per 16 units; its four waves share the row tiles, so the weights are streamed once per 320 rows.  No LDS, no
+ * atomics: a pure function of the inputs.  Bounds (SVSR_ERR_ARG): Ep, Up multiples of 64 in [64, 4096]; 1 <= U <= Up; 1 <= R <= 65536;
+ * x_pitch >= Ep and a multiple of 8; wpk, x, h_prev 16-byte aligned. */
+int svsr_rnn_cell_step(int gru, const void* wpk, const float* bias, const void* x, int64_t x_pitch, int x_rows, const int64_t* xidx, int64_t xidx_stride, const float* h_prev, const float* c_prev, const int64_t* src, int prev_rows, float* h_out, float* c_out, void* h16_out, int R, int Ep, int Up, int U, hipStream_t stream);
+
 /* ---- dense temporal back-end of the DC-TCN word-level model (dctcn.hip; syncvsr_amd/dctcn.py, eval path) ---------------------
  * Replaces DenseTemporalConvNet.forward (reference LRW/video/src/tcn/models/densetcn.py:38-192, se_module.py:8-23) and the consensus of
  * DCTCNLightningModule.forward (lightning.py:278-279).  Activations are channels-last bf16 rows [B*T][pitch]; a layer reads the first n_in

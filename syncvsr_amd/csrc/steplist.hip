@@ -82,7 +82,7 @@ const std::unordered_map<std::string, Entry>& registry() {
         SVSR_REG(svsr_memcpy_async), SVSR_REG(svsr_w2v_conv0), SVSR_REG(svsr_w2v_norm_gelu), SVSR_REG(svsr_w2v_quantize),
         SVSR_REG(svsr_igemm_wgrad_v2), SVSR_REG(svsr_igemm_wgrad_group_v2), SVSR_REG(svsr_conv3x3_wgrad_v2), SVSR_REG(svsr_fill_ranges),
         SVSR_REG(svsr_conv3x3_wgrad_chain), SVSR_REG(svsr_conv3x3_wgrad_reduce),
-        SVSR_REG(svsr_mha_table_fwd), SVSR_REG(svsr_lm_embed_fwd),
+        SVSR_REG(svsr_mha_table_fwd), SVSR_REG(svsr_lm_embed_fwd), SVSR_REG(svsr_rnn_cell_step),
         SVSR_REG(svsr_beam_select), SVSR_REG(svsr_ctc_prefix_score_clips), SVSR_REG(svsr_mha_src_step_fwd), SVSR_REG(svsr_ctc_align),
         SVSR_REG(svsr_ctc_frame_best), SVSR_REG(svsr_ctc_collapse), SVSR_REG(svsr_edit_distance),
         SVSR_REG(svsr_tconv_fwd), SVSR_REG(svsr_tcn_se_fwd), SVSR_REG(svsr_tcn_norm_pool_fwd),

@@ -711,9 +711,10 @@ class BatchBeamSearch:
 
 def get_beam_search_decoder(model, token_list, rnnlm=None, rnnlm_conf=None, penalty=0, ctc_weight: float = 0.1, lm_weight: float = 0.0,
                             beam_size: int = 40, scorers: Optional[dict] = None) -> BatchBeamSearch:
-    """LRS/video/lightning.py:237-279.  `rnnlm`: a `lrs_lm.TransformerLM`, or the path of a transformer-LM state dict with `rnnlm_conf` the
-    path of its model.json (default: next to it) or a mapping of its arguments; it scores under "lm" with weight `lm_weight` (and is
-    dropped when that is 0, beam_search.py:73-76).  The reference's RNN language models are not part of this package."""
+    """LRS/video/lightning.py:237-279.  `rnnlm`: a `lrs_lm.TransformerLM` or `lrs_lm.RNNLM`, or the path of such a model's state dict with
+    `rnnlm_conf` the path of its model.json (default: next to it) or a mapping of its arguments — its `model_module` picks the class as in
+    the reference: absent or "default" is the recurrent LM, "transformer" the transformer LM.  It scores under "lm" with weight `lm_weight`
+    (and is dropped when that is 0, beam_search.py:73-76).  The reference's sequential RNN LM (seq_rnn) is not part of this package."""
     sos = eos = model.odim - 1
     scorers = dict(scorers) if scorers is not None else model.scorers()
     if not rnnlm:

@@ -175,30 +175,10 @@ class TransformerLM(nn.Module):
 
     # -- construction from files ------------------------------------------------------------------------------------------
     @classmethod
-    def from_files(cls, n_vocab: int, rnnlm: str, rnnlm_conf: Any = None) -> "TransformerLM":
-        """`rnnlm`: path of a state dict (or of a snapshot holding it under "model", asr_utils.py torch_load); `rnnlm_conf`: path of the
-        reference's model.json (default: next to `rnnlm`, asr_utils.py:678-703), or a mapping / Namespace of the arguments."""
-        import os
-
-        if rnnlm_conf is None:
-            rnnlm_conf = os.path.join(os.path.dirname(str(rnnlm)), "model.json")
-        if isinstance(rnnlm_conf, (str, os.PathLike)):
-            with open(rnnlm_conf, "rb") as f:
-                conf = json.load(f)
-            if not isinstance(conf, dict):
-                raise ValueError(f"{rnnlm_conf} is not a language-model config (a JSON object of arguments)")
-        else:
-            conf = dict(rnnlm_conf) if isinstance(rnnlm_conf, Mapping) else dict(vars(rnnlm_conf))
-        module = conf.get("model_module", "default")                 # lightning.py:255
-        if module not in TRANSFORMER_LM_MODULES:
-            raise NotImplementedError(f"language model module {module!r} is not part of this package: only the transformer LM "
-                                      f"({TRANSFORMER_LM_MODULES[0]!r}) is; the reference's RNN language models stay outside")
-        lm = cls(n_vocab, conf)
-        sd = torch.load(rnnlm, map_location="cpu", weights_only=True)
-        if isinstance(sd, Mapping) and "model" in sd and isinstance(sd["model"], Mapping):
-            sd = sd["model"]
-        lm.load_state_dict(sd, strict=True)
-        return lm
+    def from_files(cls, n_vocab: int, rnnlm: str, rnnlm_conf: Any = None) -> "TransformerLM | RNNLM":
+        """The language model of a state-dict file and its model.json: `lm_from_files`, which picks the class by the config's `model_module`
+        as the reference does (a config without one names the recurrent LM)."""
+        return lm_from_files(n_vocab, rnnlm, rnnlm_conf)
 
     # -- device forms -----------------------------------------------------------------------------------------------------
     def train(self, mode: bool = True):
@@ -380,13 +360,383 @@ def _rename_legacy_keys(state_dict, prefix, local_metadata, strict, missing_keys
             state_dict[new + k[len(old):]] = state_dict.pop(k)
 
 
-def load_lm(n_vocab: int, rnnlm: Any, rnnlm_conf: Any = None) -> TransformerLM:
-    """What `get_beam_search_decoder(rnnlm=, rnnlm_conf=)` accepts -> an eval-mode TransformerLM."""
-    if isinstance(rnnlm, TransformerLM):
+# ======================================================================================================================
+# Recurrent language model: the reference's default (lm_interface.py: model_module "default" -> lm/default.py DefaultRNNLM)
+# ======================================================================================================================
+RNN_PAD = 64                     # embed_unit and unit are zero-padded to this at pack time (svsr_rnn_cell_step's K / N step)
+RNN_MAX_DIM = 4096               # padded width svsr_rnn_cell_step takes
+
+
+def _pad_to(n: int, m: int = RNN_PAD) -> int:
+    return (int(n) + m - 1) // m * m
+
+
+def pack_rnn_cell(w_ih: torch.Tensor, w_hh: torch.Tensor, b_ih: torch.Tensor, b_hh: torch.Tensor, gru: bool):
+    """nn.LSTMCell / nn.GRUCell tensors (w_ih [G U, E], w_hh [G U, U], biases [G U]; G = 4: i, f, g, o | 3: r, z, n) -> what
+    svsr_rnn_cell_step reads: wpk bf16 [Up / 16, (Ep + Up) / 32, G, 64, 8] — per 16-unit tile and 32-wide k-step the MFMA B fragment of EVERY
+    gate, lane l holding W_g[16 t + (l & 15)][32 s + 8 (l >> 4) + j] of W_g = [W_ih,g | W_hh,g] zero-padded to [Up, Ep + Up] — and bias fp32
+    [Up / 16, 4, 16]: LSTM b_ih + b_hh per gate; GRU r, z summed, then b_in and b_hn apart (b_hn sits inside r * (.))."""
+    G = 3 if gru else 4
+    U, E = int(w_hh.shape[1]), int(w_ih.shape[1])
+    if w_ih.shape[0] != G * U or w_hh.shape[0] != G * U or b_ih.numel() != G * U or b_hh.numel() != G * U:
+        raise ValueError(f"cell tensors of shapes {tuple(w_ih.shape)}, {tuple(w_hh.shape)} are not those of a {'GRU' if gru else 'LSTM'} cell")
+    Ep, Up = _pad_to(E), _pad_to(U)
+    W = torch.zeros((G, Up, Ep + Up), dtype=torch.float32, device=w_ih.device)
+    W[:, :U, :E] = w_ih.detach().float().view(G, U, E)
+    W[:, :U, Ep : Ep + U] = w_hh.detach().float().view(G, U, U)
+    T, KS = Up // 16, (Ep + Up) // 32
+    wpk = W.to(BF16).view(G, T, 16, KS, 4, 8).permute(1, 3, 0, 4, 2, 5).reshape(T, KS, G, 64, 8).contiguous()
+    bi, bh = b_ih.detach().float().view(G, U), b_hh.detach().float().view(G, U)
+    b4 = torch.zeros((4, Up), dtype=torch.float32, device=w_ih.device)
+    if gru:
+        b4[0, :U], b4[1, :U], b4[2, :U], b4[3, :U] = bi[0] + bh[0], bi[1] + bh[1], bi[2], bh[2]
+    else:
+        b4[:, :U] = bi + bh
+    return wpk, b4.view(4, T, 16).permute(1, 0, 2).contiguous()
+
+
+def unpack_rnn_cell(wpk: torch.Tensor, bias: torch.Tensor, E: int, U: int, gru: bool):
+    """Inverse of pack_rnn_cell -> (w_ih [G U, E], w_hh [G U, U] as fp32 of the bf16 values, the four bias rows [4, U], the padding [G, Up, Ep + Up]
+    with the real entries zeroed: all zeros for a well-formed pack)."""
+    G = 3 if gru else 4
+    Ep, Up = _pad_to(E), _pad_to(U)
+    T, KS = Up // 16, (Ep + Up) // 32
+    W = wpk.float().view(T, KS, G, 4, 16, 8).permute(2, 0, 4, 1, 3, 5).reshape(G, Up, Ep + Up)
+    w_ih, w_hh = W[:, :U, :E].reshape(G * U, E).clone(), W[:, :U, Ep : Ep + U].reshape(G * U, U).clone()
+    rest = W.clone()
+    rest[:, :U, :E] = 0
+    rest[:, :U, Ep : Ep + U] = 0
+    return w_ih, w_hh, bias.view(T, 4, 16).permute(1, 0, 2).reshape(4, Up)[:, :U].clone(), rest
+
+
+class RNNBuffers:
+    """The state rows of ONE search: fp32 h (and c: LSTM) as a ping-pong pair [2, layers, capacity, Up], plus the bf16 copy of the step's h
+    [layers, capacity, Up] that the layer above and the output projection read.  A step reads side `parity` through the parent rows of the
+    last selection and writes the other side; `gen` counts the steps written here."""
+
+    def __init__(self, layers: int, capacity: int, width: int, lstm: bool, device):
+        self.capacity = max(int(capacity), 1)
+        self.h = torch.empty((2, layers, self.capacity, width), dtype=torch.float32, device=device)
+        self.c = torch.empty_like(self.h) if lstm else None
+        self.h16 = torch.empty((layers, self.capacity, width), dtype=BF16, device=device)
+        self.iota = torch.arange(self.capacity, dtype=torch.int64, device=device)
+        self.parity, self.gen = 1, 0
+
+    def nbytes(self) -> int:
+        return (self.h.numel() * (2 if self.c is not None else 1)) * 4 + self.h16.numel() * 2 + self.iota.numel() * 8
+
+
+class RNNState:
+    """Batched scorer state: the buffers of the search + the int64 rows [n] (or one row, 0-dim) that hold the n hypotheses' states on side
+    `parity`, as written by step `gen`.  rows None: no step yet (zero state).  Indexing gathers the rows — n integers are all that
+    `select_states` and the search's pruning move; the next step's kernels read the state rows through them."""
+
+    __slots__ = ("bufs", "rows", "parity", "gen")
+
+    def __init__(self, bufs: RNNBuffers, rows: Optional[torch.Tensor], parity: int, gen: int):
+        self.bufs, self.rows, self.parity, self.gen = bufs, rows, parity, gen
+
+    def __getitem__(self, idx) -> "RNNState":
+        return RNNState(self.bufs, None if self.rows is None else self.rows[idx], self.parity, self.gen)
+
+    def __len__(self) -> int:
+        return 0 if self.rows is None else self.rows.shape[0]
+
+
+def select_rows(rows: Optional[torch.Tensor], prev: torch.Tensor) -> Optional[torch.Tensor]:
+    """Index arithmetic of `select_states`, device-agnostic: rows [n] name the state rows of the n scored hypotheses, prev [m] the parent of
+    each survivor -> rows [m] of the survivors' states (None stays None: nothing was scored yet)."""
+    return None if rows is None else rows[prev]
+
+
+class RNNLM(nn.Module):
+    """`DefaultRNNLM(n_vocab, args)` of the reference (lm/default.py): args.type ("lstm" | "gru"), layer, unit, embed_unit (None: unit),
+    tie_weights (+ dropout_rate / emb_dropout_rate, accepted and ignored: evaluation only).  nn.Embedding -> `layer` nn.LSTMCell / nn.GRUCell
+    -> nn.Linear(unit, n_vocab), weights as frozen buffers under the reference's state-dict names (`predictor.*`).  A step is one
+    svsr_rnn_cell_step launch per layer + the output projection + log-softmax; the state of a search lives in `RNNBuffers`."""
+
+    def __init__(self, n_vocab: int, args: Any):
+        super().__init__()
+        self.n_vocab = int(n_vocab)
+        self.typ = str(_arg(args, "type", "lstm"))
+        self.layers, self.unit = int(_arg(args, "layer", 2)), int(_arg(args, "unit", 650))
+        eu = _arg(args, "embed_unit", None)
+        self.embed_unit = self.unit if eu is None else int(eu)
+        self.tie_weights = bool(_arg(args, "tie_weights", False))
+        if self.typ not in ("lstm", "gru"):
+            raise ValueError(f"unknown RNN type: {self.typ!r} (lstm or gru)")
+        if self.layers < 1 or self.n_vocab < 2 or self.unit < 1 or self.embed_unit < 1:
+            raise ValueError("the language model needs at least one layer, one unit and two vocabulary units")
+        if self.tie_weights and self.unit != self.embed_unit:
+            raise ValueError("Tie Weights: True need embedding and final dimensions to match")
+        bad = [f"{k} = {v} pads to {_pad_to(v)}" for k, v in (("unit", self.unit), ("embed_unit", self.embed_unit)) if _pad_to(v) > RNN_MAX_DIM]
+        if bad:
+            raise NotImplementedError(f"the recurrent-cell kernel takes widths up to {RNN_MAX_DIM} after padding to multiples of {RNN_PAD}: " + "; ".join(bad))
+        V, E, U, G = self.n_vocab, self.embed_unit, self.unit, (4 if self.typ == "lstm" else 3)
+        g = torch.Generator().manual_seed(0)
+
+        def uni(*shape) -> torch.Tensor:                       # default.py:388-389: every parameter uniform in [-0.1, 0.1]
+            return (torch.rand(*shape, generator=g) * 2 - 1) * 0.1
+
+        self.predictor = nn.Module()
+        self.predictor.embed = _Buffers(weight=uni(V, E))
+        self.predictor.rnn = nn.ModuleList([_Buffers(weight_ih=uni(G * U, E if i == 0 else U), weight_hh=uni(G * U, U), bias_ih=uni(G * U), bias_hh=uni(G * U))
+                                            for i in range(self.layers)])
+        self.predictor.lo = _Buffers(weight=uni(V, U), bias=uni(V))
+        if self.tie_weights:
+            self.predictor.lo.weight = self.predictor.embed.weight
+        self._packed: Optional[dict] = None
+        self.beam_hint = 40
+        self.register_load_state_dict_post_hook(lambda module, incompatible: module._invalidate())
+        self.requires_grad_(False)
+        self.eval()
+
+    @property
+    def lstm(self) -> bool:
+        return self.typ == "lstm"
+
+    @property
+    def unit_pad(self) -> int:
+        return _pad_to(self.unit)
+
+    @property
+    def embed_pad(self) -> int:
+        return _pad_to(self.embed_unit)
+
+    def train(self, mode: bool = True):
+        if mode:
+            raise RuntimeError("RNNLM is a frozen, inference-only scorer: training the language model is outside this package")
+        return super().train(False)
+
+    def _invalidate(self) -> None:
+        self._packed = None
+
+    def _apply(self, fn, *a, **k):
+        out = super()._apply(fn, *a, **k)
+        self._packed = None
+        if self.tie_weights:                                   # (nn.Module._apply maps the shared tensor twice)
+            self.predictor.lo.weight = self.predictor.embed.weight
+        return out
+
+    def packed(self, dev: torch.device) -> dict:
+        """Device forms, made once: the embedding table bf16 [V, Ep] and the output matrix bf16 [V, Up] (zero-padded columns), per layer
+        the gate-interleaved fragments of pack_rnn_cell."""
+        p = self._packed
+        if p is not None and p["dev"] == dev:
+            return p
+        V, E, U, Ep, Up = self.n_vocab, self.embed_unit, self.unit, self.embed_pad, self.unit_pad
+        pr = self.predictor
+        with torch.no_grad():
+            emb = torch.zeros((V, Ep), dtype=BF16, device=dev)
+            emb[:, :E] = pr.embed.weight.detach().to(dev, torch.float32).to(BF16)
+            w_lo = torch.zeros((V, Up), dtype=BF16, device=dev)
+            w_lo[:, :U] = pr.lo.weight.detach().to(dev, torch.float32).to(BF16)
+            p = dict(dev=dev, emb=emb, w_lo=w_lo, b_lo=pr.lo.bias.detach().to(dev, torch.float32).contiguous(), layers=[])
+            for cell in pr.rnn:
+                p["layers"].append(pack_rnn_cell(cell.weight_ih.to(dev), cell.weight_hh.to(dev), cell.bias_ih.to(dev), cell.bias_hh.to(dev), not self.lstm))
+        self._packed = p
+        return p
+
+    def _check(self, ys: torch.Tensor) -> dict:
+        if self.training:
+            raise RuntimeError("RNNLM scores in eval mode only")
+        if ys.device.type != "cuda":
+            raise RuntimeError("syncvsr_amd runs on an MI355X HIP device only; there is no CPU fallback (tests/rnnlm_restatement.py is the fp64 restatement)")
+        return self.packed(ys.device)
+
+    # -- one step over n rows --------------------------------------------------------------------------------------------------
+    def _new_bufs(self, capacity: int, dev) -> RNNBuffers:
+        return RNNBuffers(self.layers, capacity, self.unit_pad, self.lstm, dev)
+
+    def _step(self, p: dict, tok: torch.Tensor, state: Optional[RNNState], n: int):
+        """tok int64 [n] (any stride), state: where the parents' rows are (None / rows None: zero state) -> (logits fp32 [n, V], new state).
+        Writes the other side of the state's own buffers when `state` is their latest step and they are large enough (the search's
+        path: nothing is allocated or copied); otherwise fresh buffers take the result and the state's are only read."""
+        Ep, Up, U, V = self.embed_pad, self.unit_pad, self.unit, self.n_vocab
+        rb = state.bufs if state is not None else None
+        src = state.rows if state is not None else None
+        if src is not None:
+            if rb.gen - state.gen > 1 or (rb.gen != state.gen and rb.parity == state.parity):
+                raise ValueError("the language-model state was overwritten: it is older than the last two scoring calls of its search (a state "
+                                 "is good for the scoring call after the one that made it; select_state() detaches a hypothesis for longer)")
+            if src.dim() == 0:
+                src = src.view(1)
+            if src.numel() != n:
+                raise ValueError(f"the language-model state holds {src.numel()} rows for {n} hypotheses: it must come from the previous scoring "
+                                 "call (through select_states) for the same hypotheses")
+            src = src.contiguous()
+        if rb is not None and rb.gen == state.gen and n <= rb.capacity:
+            wb, side = rb, 1 - state.parity
+        else:
+            wb, side = self._new_bufs(n, tok.device), 0
+        rs = state.parity if state is not None else 0
+        gru = not self.lstm
+        for i, (wpk, bias) in enumerate(p["layers"]):
+            ops.rnn_cell_step(gru, wpk, bias, p["emb"] if i == 0 else wb.h16[i - 1], tok if i == 0 else None,
+                              rb.h[rs, i] if src is not None else None, rb.c[rs, i] if src is not None and self.lstm else None, src,
+                              wb.h[side, i], wb.c[side, i] if self.lstm else None, wb.h16[i], R=n, Ep=Ep if i == 0 else Up, Up=Up, U=U)
+        wb.parity, wb.gen = side, wb.gen + 1
+        Vp = (V + 63) // 64 * 64
+        logits = ops.linear_fwd(wb.h16[self.layers - 1], p["w_lo"], p["b_lo"], rows=n, K=Up, N=V, x_pitch=Up, out_f32=True, out_pitch=Vp)[0][:, :V]
+        return logits, RNNState(wb, wb.iota[:n], side, wb.gen)
+
+    # -- scorer interface (scorer_interface.py; lm/default.py:138-213) -------------------------------------------------------------
+    def init_state(self, x):
+        return None
+
+    def batch_init_state(self, x, beam: Optional[int] = None, maxlen: Optional[int] = None):
+        """Buffers for `beam` hypotheses (default: `self.beam_hint`, which get_beam_search_decoder sets to its beam size), inside a state
+        without rows: the first `batch_score` starts from the zero state (default.py:398-406).  `maxlen` is accepted for the signature
+        the transformer LM has: a recurrent state does not grow with the prefix."""
+        beam = self.beam_hint if beam is None else int(beam)
+        return RNNState(self._new_bufs(beam, x.device), None, 1, 0)
+
+    def batch_init_state_clips(self, xs, lengths):
+        """One pair of buffers for the C clips of a multi-clip search: `beam_hint` rows per clip."""
+        return self.batch_init_state(xs[0], beam=self.beam_hint * len(list(lengths)))
+
+    def batch_score_clips(self, ys: torch.Tensor, states, clip_of: torch.Tensor = None):
+        return self.batch_score(ys, states, None)
+
+    def workspace_bytes(self, beam: int, maxlen: int = 0) -> int:
+        """Device bytes of the state of one search: what `batch_init_state(beam=)` allocates (independent of the prefix length)."""
+        Up = self.unit_pad
+        return self.layers * beam * Up * (2 * 4 * (2 if self.lstm else 1) + 2) + beam * 8
+
+    def final_score(self, state) -> float:
+        return 0.0                                             # default.py:316-322: the predictor has no `final`
+
+    def select_state(self, state, i, new_id=None):
+        """One hypothesis' state, detached from the search's buffers (layers * Up numbers are copied): it stays valid however many steps
+        the search takes afterwards — the per-hypothesis protocol of the reference's BeamSearch keeps states for as long as it likes."""
+        if state is None or state.rows is None:
+            return None
+        row = state.rows.reshape(-1)[i] if state.rows.dim() else state.rows
+        src, own = state.bufs, self._new_bufs(1, state.bufs.h.device)
+        own.h[0, :, 0] = src.h[state.parity, :, row]
+        if self.lstm:
+            own.c[0, :, 0] = src.c[state.parity, :, row]
+        own.parity, own.gen = 0, 1
+        return RNNState(own, own.iota[0], 0, 1)
+
+    def select_states(self, states, prev: torch.Tensor, tok: torch.Tensor):
+        return None if states is None else RNNState(states.bufs, select_rows(states.rows, prev), states.parity, states.gen)
+
+    def _merge(self, states, n: int, dev) -> Optional[RNNState]:
+        """Accepts None, [None] * n, the batched state, or a list of per-hypothesis states (the reference's calling convention): states of
+        one step of one search share their rows' buffers; anything else is gathered into fresh buffers first."""
+        if states is None:
+            return None
+        if isinstance(states, RNNState):
+            return states
+        if not states or any(s is None or s.rows is None for s in states):
+            return None                                        # default.py:193: states[0] is None -> zero state
+        if len(states) != n:
+            raise ValueError(f"{len(states)} language-model states for {n} hypotheses")
+        s0 = states[0]
+        if all(s.bufs is s0.bufs and s.parity == s0.parity and s.gen == s0.gen for s in states):
+            return RNNState(s0.bufs, torch.cat([s.rows.reshape(-1) for s in states]), s0.parity, s0.gen)
+        own = self._new_bufs(n, dev)
+        own.h[0] = torch.stack([s.bufs.h[s.parity][:, s.rows.reshape(-1)[0]] for s in states], dim=1)
+        if self.lstm:
+            own.c[0] = torch.stack([s.bufs.c[s.parity][:, s.rows.reshape(-1)[0]] for s in states], dim=1)
+        own.parity, own.gen = 0, 1
+        return RNNState(own, own.iota[:n], 0, 1)
+
+    def batch_score(self, ys: torch.Tensor, states, xs: torch.Tensor = None):
+        """ys int64 [n, L] prefixes (with <sos>) -> (log-probabilities of the next token fp32 [n, n_vocab], state).  As in the reference
+        (default.py:204) only the LAST token of each prefix is read: the rest of the prefix is what the state stands for, and without a
+        state the step starts from zeros."""
+        p = self._check(ys)
+        n = ys.shape[0]
+        with torch.no_grad():
+            logits, state = self._step(p, ys[:, -1], self._merge(states, n, ys.device), n)
+            logp = torch.log_softmax(logits.float(), dim=-1)
+        return logp, state
+
+    def score(self, y: torch.Tensor, state, x: torch.Tensor = None):
+        logp, st = self.batch_score(y.unsqueeze(0), None if state is None else [state], None)
+        return logp.squeeze(0), st[0]
+
+    # -- perplexity evaluation (default.py:106-136) ---------------------------------------------------------------------------------
+    def forward(self, x: torch.Tensor, t: torch.Tensor):
+        """x, t int64 [B, L] -> the reference's triple (loss / B, loss, count): loss = sum over positions i of mean_b(-log p(t[b, i])) times the
+        number of rows with x[b, i] != 0, count = that number summed.  Forward only."""
+        p = self._check(x)
+        B, L = x.shape
+        with torch.no_grad():
+            state = None
+            loss = torch.zeros((), dtype=torch.float32, device=x.device)
+            count = torch.zeros((), dtype=torch.int64, device=x.device)
+            for i in range(L):
+                logits, state = self._step(p, x[:, i], state, B)
+                nll = -torch.log_softmax(logits.float(), dim=-1).gather(1, t[:, i : i + 1]).squeeze(1)
+                non_zeros = (x[:, i] != 0).sum()
+                loss = loss + nll.mean() * non_zeros.to(nll.dtype)
+                count = count + non_zeros
+        return loss / B, loss, count
+
+    @classmethod
+    def from_files(cls, n_vocab: int, rnnlm: str, rnnlm_conf: Any = None):
+        return load_lm(n_vocab, rnnlm, rnnlm_conf)
+
+
+RNN_LM_MODULES = ("default", "espnet.nets.pytorch_backend.lm.default:DefaultRNNLM")                          # lm_interface.py:61-66
+RNN_LM_REQUIRED = ("type", "layer", "unit")                      # what DefaultRNNLM.__init__ reads as args.<name>: no getattr default
+
+
+def _read_conf(rnnlm: Any, rnnlm_conf: Any) -> dict:
+    import os
+
+    if rnnlm_conf is None:
+        rnnlm_conf = os.path.join(os.path.dirname(str(rnnlm)), "model.json")
+    if isinstance(rnnlm_conf, (str, os.PathLike)):
+        with open(rnnlm_conf, "rb") as f:
+            conf = json.load(f)
+        if not isinstance(conf, dict):
+            raise ValueError(f"{rnnlm_conf} is not a language-model config (a JSON object of arguments)")
+        return conf
+    return dict(rnnlm_conf) if isinstance(rnnlm_conf, Mapping) else dict(vars(rnnlm_conf))
+
+
+def lm_from_files(n_vocab: int, rnnlm: str, rnnlm_conf: Any = None) -> "TransformerLM | RNNLM":
+    """`rnnlm`: path of a state dict (or of a snapshot holding it under "model", asr_utils.py torch_load); `rnnlm_conf`: path of the
+    reference's model.json (default: next to `rnnlm`, asr_utils.py:678-703), or a mapping / Namespace of the arguments.  The class follows
+    `model_module` as in the reference (lightning.py:255, lm_interface.py:61-66): absent or "default" is the recurrent LM, "transformer" the
+    transformer LM; "seq_rnn" and foreign modules are not part of this package, and a recurrent-LM config must carry `type`, `layer` and
+    `unit` as the reference's does."""
+    conf = _read_conf(rnnlm, rnnlm_conf)
+    module = conf.get("model_module", "default")
+    if module in TRANSFORMER_LM_MODULES:
+        lm = TransformerLM(n_vocab, conf)
+    elif module in RNN_LM_MODULES:
+        # default.py:85-96 reads args.type, args.layer and args.unit without defaults, and the trainer writes every argument into model.json: a
+        # config without them was not written for this module (a transformer-LM config whose model_module was lost, say) and is refused
+        # here, by name, rather than by the key mismatch of the strict load below
+        missing = [k for k in RNN_LM_REQUIRED if k not in conf]
+        if missing:
+            raise NotImplementedError(f"language model module {module!r} (the reference's recurrent LM, also what a config without model_module means) "
+                                      f"cannot be built from this config: it lacks {', '.join(missing)}, which the reference's DefaultRNNLM reads "
+                                      f"without defaults; a transformer LM config must say model_module={TRANSFORMER_LM_MODULES[0]!r}")
+        lm = RNNLM(n_vocab, conf)
+    else:
+        raise NotImplementedError(f"language model module {module!r} is not part of this package: the transformer LM ({TRANSFORMER_LM_MODULES[0]!r}) and "
+                                  f"the default recurrent LM ({RNN_LM_MODULES[0]!r}, also meant by a config without model_module) are; the reference's "
+                                  "sequential RNN LM (seq_rnn: cuDNN-style nn.LSTM / nn.GRU / nn.RNN stacks under other state-dict names) stays outside")
+    sd = torch.load(rnnlm, map_location="cpu", weights_only=True)
+    if isinstance(sd, Mapping) and "model" in sd and isinstance(sd["model"], Mapping):
+        sd = sd["model"]
+    lm.load_state_dict(sd, strict=True)
+    return lm
+
+
+def load_lm(n_vocab: int, rnnlm: Any, rnnlm_conf: Any = None) -> "TransformerLM | RNNLM":
+    """What `get_beam_search_decoder(rnnlm=, rnnlm_conf=)` accepts -> an eval-mode TransformerLM or RNNLM."""
+    if isinstance(rnnlm, (TransformerLM, RNNLM)):
         if rnnlm.n_vocab != n_vocab:
             raise ValueError(f"the language model scores {rnnlm.n_vocab} units, the token list has {n_vocab}")
         return rnnlm
     if isinstance(rnnlm, nn.Module) or hasattr(rnnlm, "batch_score"):
-        raise NotImplementedError(f"language-model scorer {type(rnnlm).__name__} is not part of this package: pass a syncvsr_amd.lrs_lm.TransformerLM, "
-                                  "or the path of a transformer-LM state dict")
-    return TransformerLM.from_files(n_vocab, rnnlm, rnnlm_conf)
+        raise NotImplementedError(f"language-model scorer {type(rnnlm).__name__} is not part of this package: pass a syncvsr_amd.lrs_lm.TransformerLM "
+                                  "or RNNLM, or the path of such a model's state dict")
+    return lm_from_files(n_vocab, rnnlm, rnnlm_conf)

@@ -2315,6 +2315,30 @@ def lm_embed_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, pe: t
 
 
 # --------------------------------------------------------------------------------------------------
+# Recurrent language-model scorer (csrc/lrs_rnnlm.hip)
+# --------------------------------------------------------------------------------------------------
+def rnn_cell_step(gru: bool, wpk: torch.Tensor, bias: torch.Tensor, x: torch.Tensor, xidx: Optional[torch.Tensor], h_prev: Optional[torch.Tensor],
+                  c_prev: Optional[torch.Tensor], src: Optional[torch.Tensor], h_out: torch.Tensor, c_out: Optional[torch.Tensor],
+                  h16_out: Optional[torch.Tensor], *, R: int, Ep: int, Up: int, U: int) -> None:
+    """One recurrent layer of one step for R hypotheses (svsr_rnn_cell_step; layouts: include/syncvsr_hip.h).  x bf16 [rows, >= Ep]: the embedding
+    table with xidx int64 [R] (any stride: a column of the prefixes) = the tokens, or the rows of the layer below with xidx None; h_prev / c_prev
+    fp32 [rows, Up] read through src int64 [R] (None: zero state); h_out / c_out fp32 and h16_out bf16 [>= R, Up] are written."""
+    assert wpk.dtype == BF16 and wpk.is_contiguous() and wpk.numel() == (3 if gru else 4) * Up * (Ep + Up)
+    assert bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == 4 * Up
+    assert x.dtype == BF16 and x.dim() == 2 and x.stride(1) == 1 and x.shape[1] >= Ep and (xidx is not None or x.shape[0] >= R)
+    assert xidx is None or (xidx.dtype == torch.int64 and xidx.dim() == 1 and xidx.numel() >= R)
+    assert src is None or (src.dtype == torch.int64 and src.is_contiguous() and src.numel() >= R and h_prev is not None)
+    for t in (h_prev, c_prev, h_out, c_out):
+        assert t is None or (t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous() and t.shape[1] == Up)
+    assert h_out.shape[0] >= R and (c_out is None or c_out.shape[0] >= R)
+    assert h16_out is None or (h16_out.dtype == BF16 and h16_out.is_contiguous() and h16_out.shape[0] >= R and h16_out.shape[1] == Up)
+    G = 3 if gru else 4
+    _call("svsr_rnn_cell_step", int(bool(gru)), _p(wpk), _p(bias), _p(x), x.stride(0), x.shape[0], _p(xidx), 1 if xidx is None else max(xidx.stride(0), 1),
+          _p(h_prev), _p(c_prev), _p(src), 0 if h_prev is None else h_prev.shape[0], _p(h_out), _p(c_out), _p(h16_out), R, Ep, Up, U, _stream(),
+          label="k_rnn_cell", flops=2.0 * R * G * Up * (Ep + Up), nbytes=2.0 * G * Up * (Ep + Up))
+
+
+# --------------------------------------------------------------------------------------------------
 # Multi-clip beam search (csrc/lrs_search.hip)
 # --------------------------------------------------------------------------------------------------
 BEAM_SELECT_MAX_PLANES = 4
